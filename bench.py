@@ -21,6 +21,11 @@ the timed region.
                     "one batch sharded over 1/2/4/8 GPUs"
 
 Prints ONE JSON line on rank 0 (see the keys in main()).
+
+A plain run sets up, warms up, times --steps steps and prints that line.  --full adds what the
+headline does not need: the roofline and per-kernel figures (--profile-steps more steps with hipEvent
+timing, a device copy), the CPU baselines, the other BASELINE configs, the small batches and the host
+path.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs()).
 """
 from __future__ import annotations
 
@@ -96,14 +101,20 @@ def parse_args():
                     help="hint the next batch's feeder stage ahead (fhip_prepare_ahead) so that it "
                          "runs beside the kernels in flight; measured SLOWER on MI355X (DESIGN.md: "
                          "the kernels contend, 0.163-0.194 vs 0.151 ms/step), hence opt-in")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline and per-kernel figures, "
+                         "CPU baselines, the other configs, small batches and the host path (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
                     help="rough budget of CPU work for the cpu_baseline leg")
     ap.add_argument("--profile-steps", type=int, default=200,
-                    help="extra steps with per-kernel hipEvent timing for the roofline object")
+                    help="with --full: extra steps with per-kernel hipEvent timing for the roofline object")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the per-kernel timings of the other BASELINE configs, the small-batch "
-                         "steps and the host path that rank 0 adds at N = 1")
+                    help="with --full: skip the per-kernel timings of the other BASELINE configs, the "
+                         "small-batch steps and the host path that rank 0 adds at N = 1")
     ap.add_argument("--other-steps", type=int, default=20)
     ap.add_argument("--with-residual", action="store_true",
                     help="also write the int32 residual (stage A of SURVEY 8d)")
@@ -288,13 +299,13 @@ def host_cores():
     return max(1, min(n, cap)), n
 
 
-REF_BENCH = os.path.join(ROOT, "build", "ref", "ref_bench")     # oracle/Makefile `refbench`: the reference's own CMake build
-REF_CLI = os.path.join(ROOT, "build", "ref", "flake")
+REF_BENCH = os.path.join(ROOT, "oracle", "_ref", "build", "ref_bench")   # oracle/Makefile `refbench`: the reference's own CMake build
+REF_CLI = os.path.join(ROOT, "oracle", "_ref", "build", "flake")
 
 
 def reference_leg(params, n, frames, seconds=1.0, transient=False):
     """TIMING ONLY: the reference's own flake_encode_frame() loop (flake/flake.c:624-663) over the same
-    synthetic frames, as a child process -- build/ref/ref_bench, linked against the libflake_static.a
+    synthetic frames, as a child process -- oracle/_ref/build/ref_bench, linked against the libflake_static.a
     the reference's CMake build makes (oracle/Makefile target `refbench`; git-ignored, built where
     /root/reference exists and shipped as a binary).  Never a parity witness: nothing compares its
     bytes.  Its calls include the stream MD5 (encode.c:1006), as every libflake caller's do."""
@@ -314,7 +325,7 @@ def reference_leg(params, n, frames, seconds=1.0, transient=False):
             "kind": "reference (timing only)",
             "sample": f"{j['frames']} calls of the reference's flake_encode_frame() on this workload's frames "
                       f"({j['samples'] / 1e6:.1f} Msamples, {j['seconds']:.2f} s; stream MD5 included, as in every call "
-                      "of libflake), build/ref/ref_bench = oracle/ref_bench.c + the reference's CMake-built libflake_static.a"}
+                      "of libflake), oracle/_ref/build/ref_bench = oracle/ref_bench.c + the reference's CMake-built libflake_static.a"}
 
 
 def reference_cli_leg(nframes=16384, n=4096):
@@ -347,7 +358,7 @@ def reference_cli_leg(nframes=16384, n=4096):
                 "kind": "reference (timing only)",
                 "sample": f"`flake -q -2 -b {n} in.wav -o out.flac` on a {samples / 1e6:.1f} Msample mono 16-bit WAV in "
                           f"tmpfs, best of 2 runs ({best:.2f} s wall: WAV parsing, encode, MD5 and file output included), "
-                          f"{os.path.getsize(out)} bytes out; build/ref/flake = the reference's CMake build"}
+                          f"{os.path.getsize(out)} bytes out; oracle/_ref/build/flake = the reference's CMake build"}
     except Exception as e:
         return {"error": repr(e)}
     finally:
@@ -423,7 +434,7 @@ def cpu_baseline(params, n, budget_s, gpu_bits_per_frame=None):
                      one thread, on prepared subframes of the same sample; the integer FIR
                      (optimize.c, not buildable here -- DESIGN.md 4) is a plain C loop beside them.
     reference        TIMING ONLY (round 4): the reference's own flake_encode_frame() loop on the same frames
-                     (reference_leg above: build/ref/ref_bench on the libflake_static.a of the reference's CMake
+                     (reference_leg above: oracle/_ref/build/ref_bench on the libflake_static.a of the reference's CMake
                      build; a child process; never a parity witness -- parity is pinned by oracle/_ref, which is
                      built without the reference's build system).  Includes the stream MD5."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -471,7 +482,7 @@ def cpu_baseline(params, n, budget_s, gpu_bits_per_frame=None):
                 rates.append(j["samples"] / j["seconds"] / 1e6)
             out["reference_all_cores"] = {"value": round(sum(rates), 1), "unit": "Msamples/s", "cores": ncores,
                                           "cores_available": navail, "kind": "reference (timing only)",
-                                          "sample": f"{ncores} processes of build/ref/ref_bench side by side, 256 frames "
+                                          "sample": f"{ncores} processes of oracle/_ref/build/ref_bench side by side, 256 frames "
                                                     "repeated for 3 s each; sum of their rates"}
         except Exception as e:
             out["reference_all_cores"] = {"error": repr(e)}
@@ -844,6 +855,52 @@ def host_path(nframes=4096, n=4096, vbs=True):
     return res
 
 
+DUMP_SEED = 20240611                 # the fixed sample of subframes / frames --dump-outputs writes
+DUMP_INFO_BYTES = 28 << 20           # float64 subframe records
+DUMP_RICE_BYTES = 24 << 20           # float32 bytes of the packed Rice sections
+DUMP_RESID_BYTES = 4 << 20           # float64 residual (--with-residual)
+
+
+def _dump_sample(total, k):
+    """Sorted indices of a fixed, seeded sample of k of `total` items (all of them when k >= total)."""
+    if k >= total:
+        return np.arange(total)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(total, k, replace=False))
+
+
+def dump_outputs(out_dir, info, bits, resid, nsub, slot):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files in out_dir.
+
+    info_<field>.npy   every field of the subframe records (float64: exact for their int32 / uint32
+                       values), of all subframes -- or of info_subframes.npy, a seeded sample, where
+                       they would pass DUMP_INFO_BYTES
+    rice_bits.npy      the packed Rice section of a seeded sample of subframes (rice_subframes.npy), one
+                       row of `slot` bytes each as float32, zero past the section's own rice_nbits
+    residual.npy       with --with-residual: the int32 residual of a seeded sample of frames
+                       (residual_frames.npy) as float64"""
+    import torch
+    import flake_amd
+    os.makedirs(out_dir, exist_ok=True)
+    rec = np.frombuffer(info.cpu().numpy().tobytes(), dtype=flake_amd.INFO_DTYPE)
+    sel = _dump_sample(nsub, DUMP_INFO_BYTES // (flake_amd.INFO_DTYPE.itemsize * 2))
+    if len(sel) < nsub:
+        np.save(os.path.join(out_dir, "info_subframes.npy"), sel.astype(np.float64))
+    for name in flake_amd.INFO_DTYPE.names:
+        np.save(os.path.join(out_dir, f"info_{name}.npy"), rec[name][sel].astype(np.float64))
+    sel = _dump_sample(nsub, max(1, DUMP_RICE_BYTES // (slot * 4)))
+    rows = bits.view(nsub, slot)[torch.from_numpy(sel).to(bits.device)].cpu().numpy()
+    nbytes = (rec["rice_nbits"][sel].clip(min=0).astype(np.int64) + 7) // 8
+    rows = np.where(np.arange(slot)[None, :] < nbytes[:, None], rows, 0)
+    np.save(os.path.join(out_dir, "rice_subframes.npy"), sel.astype(np.float64))
+    np.save(os.path.join(out_dir, "rice_bits.npy"), rows.astype(np.float32))
+    if resid is not None:
+        nframes = resid.shape[0]
+        sel = _dump_sample(nframes, max(1, DUMP_RESID_BYTES // (resid[0].numel() * 8)))
+        r = resid[torch.from_numpy(sel).to(resid.device)].cpu().numpy()
+        np.save(os.path.join(out_dir, "residual_frames.npy"), sel.astype(np.float64))
+        np.save(os.path.join(out_dir, "residual.npy"), r.astype(np.float64))
+
+
 def launch_ranks(ngpus):
     """`python bench.py --gpus N` without a launcher: start the N ranks as CHILD
     processes (torch.distributed.run, one per GPU) and pass their output through;
@@ -1068,10 +1125,12 @@ def main():
     frames_per_step = sum(rank_batch.values())
     samples_per_step = frames_per_step * n * p.channels
     value = samples_per_step * args.steps / dt / 1e6
+    if args.dump_outputs and rank == 0:           # before --full's extra steps overwrite the buffers
+        dump_outputs(args.dump_outputs, info, bits, resid, nsub, slot)
 
     # ---- N > 1: the PCIe-inclusive host path of every rank's shard, side by side ----
     host_ranks = None
-    if use_dist and world > 1 and not args.no_other_configs and args.workload == "configs[1]":
+    if args.full and use_dist and world > 1 and not args.no_other_configs and args.workload == "configs[1]":
         try:
             dist.barrier()
             hp = host_path(nframes=max(64, nframes), n=n, vbs=False)
@@ -1087,13 +1146,13 @@ def main():
                           "note": "each rank: pageable host PCM -> FLAC frames in host memory for its shard "
                                   "(flake_amd_encode_frames), all ranks at once; never `value`"}
 
-    # ---- roofline of the dominant kernel (rank 0, hipEvents on the launch stream)
+    # ---- --full: roofline of the dominant kernel (rank 0, hipEvents on the launch stream) and the extras
     roofline = None
     cpu = None
     others = None
     host = None
     small = None
-    if rank == 0:
+    if args.full and rank == 0:
         rice_bytes = sum(batch_rice_bytes) // 2            # the two alternating batches, averaged
         alg_bytes = (nframes * n * p.channels * 4          # int32 PCM in
                      + rice_bytes                          # packed residual sections out

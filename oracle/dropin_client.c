@@ -8,15 +8,36 @@
  * (only where /root/reference exists; the binary travels to the GPU box).
  *
  *   dropin_client LEVEL NBLOCKS out.flac   (stereo 16-bit synthetic input)
+ *
+ * -DDROPIN_OWN_HEADER builds the same client where the reference tree is absent
+ * (oracle/dropin_client_own): libflake's names declared here on this project's
+ * layout-compatible types (include/flake_amd.h), linked to the same libflake.so.
  */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#ifdef DROPIN_OWN_HEADER
+#include "flake_amd.h"
+typedef FlakeAmdContext FlakeContext;
+typedef FlakeAmdStreaminfo FlakeStreaminfo;
+int flake_set_defaults(FlakeAmdEncodeParams *params);
+int flake_validate_params(const FlakeContext *s);
+int flake_encode_init(FlakeContext *s);
+void *flake_get_buffer(const FlakeContext *s);
+int flake_encode_frame(FlakeContext *s, const int *samples, int block_size);
+void flake_encode_close(FlakeContext *s);
+const char *flake_get_version(void);
+int flake_get_streaminfo(const FlakeContext *s, FlakeStreaminfo *si);
+void flake_write_streaminfo(const FlakeStreaminfo *si, unsigned char *data);
+#else
 #include "flake.h"                      /* the reference's header */
+#endif
 
 /* provided by libflake.so as well (include/flake_amd.h) */
+#ifndef DROPIN_OWN_HEADER
 extern void flake_amd_synth_pcm(int *pcm, long long first_frame, int nframes, int n, int channels, int bps);
+#endif
 
 int main(int argc, char **argv)
 {

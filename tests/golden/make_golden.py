@@ -17,6 +17,10 @@ Two families, kept in separate files and labelled in their `source` field:
                 are re-stated.  Inputs are regenerated from committed seeds and
                 checked against a stored SHA-1.  These pin the oracle (CPU suite) and
                 the HIP path (-m gpu) to reference-compiled arithmetic end to end.
+* ref_calls.npz the compiled reference's answer to every call of tests/test_oracle_vs_ref.py
+                and tests/test_ref_replay.py, which those tests replay where oracle/_ref cannot
+                be built (oraclelib.RecordedRef): a digest of the call and its answer where an
+                oracle function gives that very answer, the answer itself elsewhere.
 * path_*.npz    whole-path outputs (prepare -> encode_residual -> emit -> frame)
                 produced by the oracle restatement, for the parts of libflake
                 that cannot be built here (optimize.c / encode.c / vbs.c need
@@ -203,9 +207,21 @@ def make_path(orc):
                         params=np.array([getattr(p, k) for k, _ in p._fields_], np.int32))
 
 
+def make_ref_calls():
+    """Runs the two test modules with FLAKE_REF=record: the `ref` fixture records the live library's answers."""
+    import subprocess
+    subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider",
+                    os.path.join(ROOT, "tests", "test_oracle_vs_ref.py"), os.path.join(ROOT, "tests", "test_ref_replay.py")],
+                   check=True, cwd=ROOT, env=dict(os.environ, FLAKE_REF="record"))
+
+
 if __name__ == "__main__":
     if not oraclelib.Ref.available():
         raise SystemExit("oracle/_ref is not built: /root/reference is needed to make golden vectors")
+    if sys.argv[1:] == ["ref_calls"]:                   # python tests/golden/make_golden.py ref_calls
+        make_ref_calls()
+        raise SystemExit(0)
+    make_ref_calls()
     make_ref_lpc(oraclelib.Ref())
     make_ref_rice(oraclelib.Ref())
     make_ref_path(oraclelib.Ref())

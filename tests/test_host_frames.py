@@ -220,16 +220,24 @@ def test_cli_wav_to_flac(tmp_path, decoder):
     assert md5 == hashlib.md5(raw).digest()
 
 
+def dropin_client():
+    """The libflake client of oracle/dropin_client.c: built against the reference's flake.h
+    (oracle/_ref/dropin_client) where it was, else against include/flake_amd.h."""
+    import os
+    oracle_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle")
+    for exe in (os.path.join(oracle_dir, "_ref", "dropin_client"), os.path.join(oracle_dir, "dropin_client_own")):
+        if os.path.exists(exe):
+            return exe
+    raise FileNotFoundError("oracle/dropin_client_own is not built: run build()")
+
+
 def test_link_level_dropin_client(tmp_path, decoder, oracle):
     """oracle/_ref/dropin_client is compiled against the REFERENCE's flake.h and linked
     to our libflake.so (libflake's own symbol names): same call sequence as the
-    reference CLI, one flake_encode_frame() per block."""
-    import os
+    reference CLI, one flake_encode_frame() per block.  Where the reference tree was
+    absent at build time, oracle/dropin_client_own: the same client on our own header."""
     import subprocess
-    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref",
-                       "dropin_client")
-    if not os.path.exists(exe):
-        pytest.skip("dropin_client not built (needs /root/reference at build time)")
+    exe = dropin_client()
     out = tmp_path / "d.flac"
     r = subprocess.run([exe, "5", "7", str(out)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr + r.stdout
@@ -254,10 +262,7 @@ def test_lookahead_queue_is_transparent(tmp_path, level, nblocks, look):
     flush comes from the announced stream length; level 10 is variable block size."""
     import os
     import subprocess
-    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref",
-                       "dropin_client")
-    if not os.path.exists(exe):
-        pytest.skip("dropin_client not built (needs /root/reference at build time)")
+    exe = dropin_client()
     outs = []
     for tag, env in (("plain", {}), ("queued", {"FLAKE_AMD_LOOKAHEAD": str(look)})):
         out = tmp_path / f"{tag}.flac"

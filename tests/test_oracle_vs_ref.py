@@ -3,7 +3,8 @@
 oracle/_ref/libflake_ref.so is the reference's own lpc.c, rice.c, crc.c and
 bitio.h compiled where they lie (oracle/Makefile).  Everything here must agree
 bit for bit -- fp64 outputs are compared through their uint64 images.
-Skipped where _ref is absent (no /root/reference and no prebuilt file).
+Where _ref could not be built, the reference's answers to these very calls come
+from tests/golden/ref_calls.npz (oraclelib.RecordedRef).
 """
 import numpy as np
 import pytest

@@ -8,7 +8,8 @@ with oracle/flake_oracle.c field for field and byte for byte: on the BASELINE
 configs, on every order method, on the edge blocks, on every stereo mode, and on
 the 384 seeds of the GPU fuzz sweep.  The same replay generates the committed
 tests/golden/ref_path_*.npz, which the HIP path is held to under -m gpu.
-Skipped where oracle/_ref is absent."""
+Where oracle/_ref could not be built, the compiled reference's answers come from
+tests/golden/ref_calls.npz (oraclelib.RecordedRef)."""
 import numpy as np
 import pytest
 
