@@ -24,7 +24,7 @@ MAX_PARTS = 256
 MAX_LAGS = 33
 MAX_BLOCK = 65535
 
-OK, E_GENERIC, E_HIP, E_UNSUPPORTED, E_INVALID, E_NOMEM = 0, -1, -2, -3, -4, -5
+OK, E_GENERIC, E_HIP, E_UNSUPPORTED, E_INVALID, E_NOMEM, E_VERIFY = 0, -1, -2, -3, -4, -5, -6
 
 SUB_CONSTANT, SUB_VERBATIM, SUB_FIXED, SUB_LPC = 0, 1, 8, 32
 CH_NOT_STEREO, CH_LEFT_RIGHT, CH_LEFT_SIDE, CH_RIGHT_SIDE, CH_MID_SIDE = 0, 1, 8, 9, 10
@@ -124,6 +124,24 @@ class VbsOut(C.Structure):
                 ("block_bytes", C.c_void_p), ("block_frames", C.c_void_p), ("totals", C.c_void_p)]
 
 
+class VerifyIn(C.Structure):
+    """``fhip_verify_in``"""
+    _fields_ = [("stream", C.c_void_p), ("stream_bytes", C.c_int64), ("frame_bytes", C.c_void_p),
+                ("nframes", C.c_int32), ("pcm", C.c_void_p), ("nsamples", C.c_int64), ("first_sample", C.c_int64)]
+
+
+class VerifyOut(C.Structure):
+    """``fhip_verify_out``"""
+    _fields_ = [("frames", C.c_void_p), ("summary", C.c_void_p)]
+
+
+# FHIP_VERIFY_*: a frame's status, the first failing check in stream order
+VERIFY_STATUS = ("OK", "HEADER", "CRC8", "NUMBER", "SYNTAX", "SAMPLES", "PADDING", "CRC16", "LENGTH")
+(V_OK, V_HEADER, V_CRC8, V_NUMBER, V_SYNTAX, V_SAMPLES, V_PADDING, V_CRC16, V_LENGTH) = range(9)
+# fhip_verify_rec
+VERIFY_REC_DTYPE = np.dtype([("status", "<i4"), ("bit", "<i4"), ("subframe", "<i4"), ("sample", "<i4")])
+
+
 class FlakeHipError(RuntimeError):
     def __init__(self, code: int, what: str, detail: str = ""):
         self.code = code
@@ -171,6 +189,9 @@ def load_library() -> C.CDLL:
         "fhip_calc_rice_params": (i, [vp, vp, i, i, i, i, i, i, i, vp, vp, i64]),
         "fhip_vbs_split": (i, [vp, vp, i, i, vp, vp]),
         "fhip_set_profiling": (i, [vp, i]),
+        "fhip_set_verify": (i, [vp, i]),
+        "fhip_verify_frames_dev": (i, [vp, C.POINTER(VerifyIn), C.POINTER(VerifyOut)]),
+        "fhip_verify_frames": (i, [vp, C.POINTER(VerifyIn), C.POINTER(VerifyOut)]),
         "fhip_get_kernel_times": (i, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double),
                                       C.POINTER(i), i, i]),
     }
@@ -191,6 +212,7 @@ ABI_SYMBOLS = (
     "fhip_frames_packed_begin", "fhip_frames_packed_fetch", "fhip_encode_blocks_vbs_packed",
     "fhip_encode_blocks_vbs_dev", "fhip_order_search_bits",
     "fhip_host_alloc", "fhip_host_free", "fhip_host_register", "fhip_host_unregister", "fhip_frames_packed_upload", "fhip_frames_packed_fetch_async", "fhip_frames_packed_fetch_wait",
+    "fhip_set_verify", "fhip_verify_frames_dev", "fhip_verify_frames",
 )
 
 
@@ -258,6 +280,36 @@ class Encoder:
 
     def set_profiling(self, on: bool) -> None:
         self._check(self.lib.fhip_set_profiling(self._h, int(on)), "fhip_set_profiling")
+
+    def set_verify(self, on: bool) -> None:
+        """Verify the handle's own packed output on the device (fhip_set_verify)."""
+        self._check(self.lib.fhip_set_verify(self._h, int(on)), "fhip_set_verify")
+
+    def verify_frames_dev(self, stream, stream_bytes: int, frame_bytes, nframes: int, pcm, nsamples: int,
+                          first_sample: int, summary, records=None) -> None:
+        """K5 on device-resident data (torch tensors or raw device addresses); async.  summary: int64[4]
+        (frames checked, failed, first failing frame or -1, its status); records: VERIFY_REC_DTYPE-sized
+        int32[nframes][4], optional."""
+        vi = VerifyIn(_ptr(stream), stream_bytes, _ptr(frame_bytes), nframes, _ptr(pcm), nsamples, first_sample)
+        vo = VerifyOut(_ptr(records), _ptr(summary))
+        self._check(self.lib.fhip_verify_frames_dev(self._h, C.byref(vi), C.byref(vo)), "fhip_verify_frames_dev")
+
+    def verify_frames(self, stream, frame_bytes, pcm, first_sample: int = 0):
+        """K5 on host data.  stream: uint8 bytes, frame_bytes: int32[nframes], pcm: [nsamples][channels]
+        int32.  Returns (ok, records as a VERIFY_REC_DTYPE array, summary int64[4], error text)."""
+        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
+                                  else stream, dtype=np.uint8)
+        fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
+        pc = np.ascontiguousarray(pcm, dtype=np.int32).reshape(-1, self.params.channels)
+        recs = np.zeros(len(fb), dtype=VERIFY_REC_DTYPE)
+        summary = np.zeros(4, dtype=np.int64)
+        vi = VerifyIn(st.ctypes.data if st.size else None, st.size, fb.ctypes.data if fb.size else None, len(fb),
+                      pc.ctypes.data if pc.size else None, pc.shape[0], first_sample)
+        vo = VerifyOut(recs.ctypes.data if len(fb) else None, summary.ctypes.data)
+        rc = self.lib.fhip_verify_frames(self._h, C.byref(vi), C.byref(vo))
+        if rc not in (OK, E_VERIFY):
+            self._check(rc, "fhip_verify_frames")
+        return rc == OK, recs, summary, self.lib.fhip_last_error(self._h).decode() if rc else ""
 
     def kernel_times(self, reset: bool = True) -> dict:
         names = (C.c_char_p * 8)()
@@ -445,6 +497,8 @@ def load_host_library() -> C.CDLL:
     lib.flake_amd_get_version.restype = C.c_char_p
     lib.flake_amd_last_error.argtypes = [cp]
     lib.flake_amd_last_error.restype = C.c_char_p
+    lib.flake_amd_set_verify.argtypes = [cp, C.c_int]
+    lib.flake_amd_set_verify.restype = C.c_int
     _host = lib
     return lib
 
@@ -533,6 +587,11 @@ class HostEncoder:
             raise FlakeHipError(w, "flake_amd_encode_frame",
                                 self.lib.flake_amd_last_error(C.byref(self.ctx)).decode())
         return bytes(C.string_at(self.lib.flake_amd_get_buffer(C.byref(self.ctx)), w))
+
+    def set_verify(self, on: bool) -> None:
+        """flake_amd_set_verify: every later encode call verifies its frames on the device."""
+        if self.lib.flake_amd_set_verify(C.byref(self.ctx), int(on)) != 0:
+            raise RuntimeError("flake_amd_set_verify")
 
     def streaminfo(self) -> HostStreaminfo:
         si = HostStreaminfo()

@@ -85,13 +85,28 @@ struct fhip_ctx {
     std::vector<Pending> pending;
     std::vector<hipEvent_t> event_pool;
 
+    // K5 (fhip_set_verify, fhip_verify_frames*): per-frame workspace, records, summary; allocated at first use
+    bool verify = false;
+    fhip::VerifyFrame *d_vws = nullptr;
+    fhip_verify_rec *d_vrec = nullptr;
+    size_t vws_cap = 0;
+    long long *d_vsum = nullptr;              // [4] summary, then [1] key scratch
+    uint8_t *d_vstream = nullptr;             // fhip_verify_frames: the host stream / sizes / PCM uploaded
+    size_t d_vstream_bytes = 0;
+    int32_t *d_vfb = nullptr;
+    size_t d_vfb_cap = 0;
+    int32_t *d_vpcm = nullptr;
+    size_t d_vpcm_vals = 0;
+
     std::string err;
 };
 
 namespace {
 
-const char *const kKernelNames[6] = {"k_prepare", "k_autocorr", "k_lpc", "k_encode", "k_assemble",
-                                     "k_order_search"};
+constexpr int kNumKernels = 7;
+const char *const kKernelNames[kNumKernels] = {"k_prepare", "k_autocorr", "k_lpc", "k_encode", "k_assemble",
+                                               "k_order_search", "k_verify"};
+constexpr int kProfVerify = 6;
 
 int fail_hip(fhip_ctx *c, hipError_t e, const char *what)
 {
@@ -343,6 +358,64 @@ int run_pipeline(fhip_ctx *c, const int32_t *pcm, int nframes, int n,
     return FHIP_OK;
 }
 
+// K5's workspace for nframes frames (grows; a handle's own batches never need more than ws_frames)
+int ensure_verify(fhip_ctx *c, size_t nframes)
+{
+    if (!c->d_vsum) HIP_TRY(c, hipMalloc((void **)&c->d_vsum, 5 * sizeof(long long)));
+    const size_t want = std::max(nframes, c->ws_frames);
+    if (want > c->vws_cap) {
+        if (c->d_vws) (void)hipFree(c->d_vws);
+        if (c->d_vrec) (void)hipFree(c->d_vrec);
+        c->d_vws = nullptr; c->d_vrec = nullptr; c->vws_cap = 0;
+        HIP_TRY(c, hipMalloc((void **)&c->d_vws, want * sizeof(fhip::VerifyFrame)));
+        HIP_TRY(c, hipMalloc((void **)&c->d_vrec, want * sizeof(fhip_verify_rec)));
+        c->vws_cap = want;
+    }
+    return FHIP_OK;
+}
+
+// Queue K5 on the handle's stream.  block_size: the numbering unit of a fixed-block stream (the batch's block
+// size for the handle's own batches; params.block_size for a caller's stream).  recs null: the handle's own.
+int run_verify(fhip_ctx *c, const uint8_t *stream, long long stream_bytes, const int32_t *frame_bytes, int nframes,
+               const long long *dev_count, const int32_t *pcm, long long nsamples, long long first_sample,
+               int block_size, fhip_verify_rec *recs, int64_t *summary, long long *totals)
+{
+    int rc = ensure_verify(c, (size_t)nframes);
+    if (rc != FHIP_OK) return rc;
+    const fhip_params &p = c->p;
+    fhip::VerifyArgs a{stream, stream_bytes, frame_bytes, nframes, dev_count, pcm, nsamples, first_sample,
+                       p.channels, p.bits_per_sample, block_size, p.sample_rate, p.allow_vbs ? 1 : 0,
+                       c->d_vws, recs ? recs : c->d_vrec, summary ? reinterpret_cast<long long *>(summary) : c->d_vsum,
+                       reinterpret_cast<unsigned long long *>(c->d_vsum + 4), totals};
+    Prof pr(c, kProfVerify);
+    HIP_TRY(c, fhip::launch_verify(c->stream, a));
+    return FHIP_OK;
+}
+
+const char *verify_status_name(int s)
+{
+    static const char *const names[] = {"OK", "HEADER", "CRC8", "NUMBER", "SYNTAX", "SAMPLES", "PADDING", "CRC16",
+                                        "LENGTH"};
+    return (s >= 0 && s <= 8) ? names[s] : "?";
+}
+
+// After the stream synchronised: summary (host copy) -> FHIP_OK, or FHIP_E_VERIFY with the first failing frame
+// named in the handle's error text (its record read from recs, device).
+int verify_verdict(fhip_ctx *c, const long long *summary, const fhip_verify_rec *recs)
+{
+    if (summary[1] <= 0) return FHIP_OK;
+    fhip_verify_rec r{(int32_t)summary[3], -1, -1, -1};
+    if (recs && summary[2] >= 0)
+        HIP_TRY(c, hipMemcpy(&r, recs + summary[2], sizeof r, hipMemcpyDeviceToHost));
+    char buf[256];
+    snprintf(buf, sizeof buf,
+             "verification failed: %lld of %lld frames do not decode to the input; first: frame %lld, %s "
+             "(subframe %d, sample %d, bit %d)",
+             summary[1], summary[0], summary[2], verify_status_name((int)summary[3]), r.subframe, r.sample, r.bit);
+    c->err = buf;
+    return FHIP_E_VERIFY;
+}
+
 int check_batch(fhip_ctx *c, const fhip_batch *b, bool host = false)
 {
     // host entry: frames alone are a complete result, info / rice_bits optional then
@@ -399,6 +472,7 @@ const char *fhip_strerror(int code)
     case FHIP_E_UNSUPPORTED: return "parameters not supported by the HIP layer";
     case FHIP_E_INVALID: return "invalid parameters";
     case FHIP_E_NOMEM: return "out of memory";
+    case FHIP_E_VERIFY: return "the stream does not decode to the input";
     default: return code > 0 ? "ok" : "unknown error";
     }
 }
@@ -422,7 +496,7 @@ int fhip_create(fhip_ctx **out, int device, const fhip_params *p, int max_frames
     c->device = device;
     c->p = *p;
     c->max_frames = max_frames;
-    for (int i = 0; i < 6; i++) c->ktimes.push_back({kKernelNames[i], 0.0, 0});
+    for (int i = 0; i < kNumKernels; i++) c->ktimes.push_back({kKernelNames[i], 0.0, 0});
 
     // subframe-indexed workspaces: a variable-block-size handle keeps eight bins of fixed capacity
     // (pieces of k eighths: floor(8 / k) per block, 20 slots per block in all); the sample-indexed
@@ -478,7 +552,8 @@ void fhip_destroy(fhip_ctx *c)
     void *bufs[] = {c->d_smp, c->d_autoc, c->d_coefs, c->d_shift, c->d_opt, c->d_fin, c->d_k0rec, c->d_tilectr,
                     c->d_pcm, c->d_info, c->d_res, c->d_bits, c->d_frames, c->d_fbytes, c->d_fnum,
                     c->d_packed, c->d_offsets, c->d_srcoff, c->d_frame_src, c->d_totals, c->d_order,
-                    c->d_vcnt, c->d_first, c->d_stream_bytes, c->d_blk_bytes, c->d_blk_frames};
+                    c->d_vcnt, c->d_first, c->d_stream_bytes, c->d_blk_bytes, c->d_blk_frames,
+                    c->d_vws, c->d_vrec, c->d_vsum, c->d_vstream, c->d_vfb, c->d_vpcm};
     for (void *b : bufs) if (b) (void)hipFree(b);
     for (int h = 0; h < fhip_ctx::NAUX; h++) {
         if (c->aux[h]) { (void)hipStreamSynchronize(c->aux[h]); (void)hipStreamDestroy(c->aux[h]); }
@@ -751,6 +826,15 @@ int fhip_frames_packed_begin(fhip_ctx *c, const fhip_batch *b, int64_t *total_by
     if (rc != FHIP_OK) return rc;
     HIP_TRY(c, fhip::launch_pack_frames(c->stream, c->d_frames, stride, c->d_fbytes, b->nframes,
                                         c->d_offsets, c->d_packed));
+    long long vsum[4] = {0, 0, -1, 0};
+    if (c->verify) {
+        const long long num0 = b->frame_numbers ? (long long)b->frame_numbers[0] : (long long)b->first_frame_number;
+        const long long first = c->p.allow_vbs ? num0 : num0 * (long long)b->block_size;
+        rc = run_verify(c, c->d_packed, (long long)fb, c->d_fbytes, b->nframes, nullptr, c->d_pcm,
+                        (long long)b->nframes * b->block_size, first, b->block_size, nullptr, nullptr, nullptr);
+        if (rc != FHIP_OK) return rc;
+        HIP_TRY(c, hipMemcpyAsync(vsum, c->d_vsum, sizeof vsum, hipMemcpyDeviceToHost, c->stream));
+    }
     long long total = 0;
     HIP_TRY(c, hipMemcpyAsync(b->frame_bytes, c->d_fbytes, (size_t)b->nframes * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(&total, c->d_offsets + b->nframes, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
@@ -760,7 +844,7 @@ int fhip_frames_packed_begin(fhip_ctx *c, const fhip_batch *b, int64_t *total_by
     if (rc != FHIP_OK) return rc;
     c->packed_ready = total;
     *total_bytes = total;
-    return FHIP_OK;
+    return c->verify ? verify_verdict(c, vsum, c->d_vrec) : FHIP_OK;
 }
 
 int fhip_frames_packed_fetch(fhip_ctx *c, uint8_t *out, int64_t out_cap)
@@ -1278,9 +1362,19 @@ int fhip_encode_blocks_vbs_dev(fhip_ctx *c, const int32_t *pcm, int nblocks, int
         HIP_TRY(c, hipMemsetAsync(out->totals, 0, 4 * sizeof(int64_t), c->stream));
         return FHIP_OK;
     }
-    return vbs_dev_core(c, pcm, nblocks, block_size, first_frame_number,
-                        VbsOut{out->packed, (long long)out->packed_cap, out->frame_bytes, out->block_bytes,
-                               out->block_frames, reinterpret_cast<long long *>(out->totals)});
+    int32_t *fbytes = out->frame_bytes;
+    if (c->verify && !fbytes) {          // the verifier needs the stream's frame sizes
+        if (!c->d_stream_bytes) HIP_TRY(c, hipMalloc((void **)&c->d_stream_bytes, (size_t)c->max_frames * sizeof(int32_t)));
+        fbytes = c->d_stream_bytes;
+    }
+    long long *totals = reinterpret_cast<long long *>(out->totals);
+    rc = vbs_dev_core(c, pcm, nblocks, block_size, first_frame_number,
+                      VbsOut{out->packed, (long long)out->packed_cap, fbytes, out->block_bytes, out->block_frames,
+                             totals});
+    if (rc != FHIP_OK || !c->verify) return rc;
+    // totals[3] bit 2 when a frame fails; still no host synchronisation
+    return run_verify(c, out->packed, (long long)out->packed_cap, fbytes, 8 * nblocks, totals, pcm,
+                      (long long)nblocks * block_size, first_frame_number, block_size, nullptr, nullptr, totals);
 }
 
 int fhip_encode_blocks_vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, int block_size,
@@ -1318,10 +1412,20 @@ int fhip_encode_blocks_vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, 
     // one upload, the batch on the device, one download of the stream's bytes
     const size_t nvals = (size_t)nblocks * block_size * (size_t)p.channels;
     HIP_TRY(c, hipMemcpyAsync(c->d_pcm, pcm, nvals * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (c->verify && !c->d_stream_bytes)
+        HIP_TRY(c, hipMalloc((void **)&c->d_stream_bytes, (size_t)c->max_frames * sizeof(int32_t)));
     rc = vbs_dev_core(c, c->d_pcm, nblocks, block_size, first_frame_number,
-                      VbsOut{c->d_packed, (long long)c->d_packed_bytes, nullptr, c->d_blk_bytes,
-                             block_frames ? c->d_blk_frames : nullptr, c->d_totals});
+                      VbsOut{c->d_packed, (long long)c->d_packed_bytes, c->verify ? c->d_stream_bytes : nullptr,
+                             c->d_blk_bytes, block_frames ? c->d_blk_frames : nullptr, c->d_totals});
     if (rc != FHIP_OK) return rc;
+    long long vsum[4] = {0, 0, -1, 0};
+    if (c->verify) {
+        rc = run_verify(c, c->d_packed, (long long)c->d_packed_bytes, c->d_stream_bytes, 8 * nblocks, c->d_totals,
+                        c->d_pcm, (long long)nblocks * block_size, first_frame_number, block_size, nullptr, nullptr,
+                        nullptr);
+        if (rc != FHIP_OK) return rc;
+        HIP_TRY(c, hipMemcpyAsync(vsum, c->d_vsum, sizeof vsum, hipMemcpyDeviceToHost, c->stream));
+    }
     long long totals[4] = {0, 0, 0, 0};
     HIP_TRY(c, hipMemcpyAsync(totals, c->d_totals, sizeof totals, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(block_bytes, c->d_blk_bytes, (size_t)nblocks * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1334,12 +1438,86 @@ int fhip_encode_blocks_vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, 
     if (totals[3] & 2) return fail(c, FHIP_E_GENERIC, "a frame of the batch was not encoded");
     for (int b = 0; b < nblocks; b++)
         if (block_bytes[b] <= 0) return fail(c, FHIP_E_GENERIC, "a frame of the batch was not encoded");
+    if (c->verify) {
+        rc = verify_verdict(c, vsum, c->d_vrec);
+        if (rc != FHIP_OK) return rc;
+    }
     if (totals[1] > out_cap) return fail(c, FHIP_E_INVALID, "output buffer too small for the batch's frames");
     HIP_TRY(c, hipMemcpy(out, c->d_packed, (size_t)totals[1], hipMemcpyDeviceToHost));
     if (max_frame_bytes) *max_frame_bytes = (int32_t)totals[2];
     if (next_frame_number) *next_frame_number = first_frame_number + (uint32_t)((long long)nblocks * block_size);
     *out_bytes = totals[1];
     return FHIP_OK;
+}
+
+int fhip_set_verify(fhip_ctx *c, int on)
+{
+    if (!c) return FHIP_E_INVALID;
+    c->verify = on != 0;
+    return FHIP_OK;
+}
+
+namespace {
+int verify_check(fhip_ctx *c, const fhip_verify_in *in, const fhip_verify_out *out)
+{
+    if (!c) return FHIP_E_INVALID;
+    if (!in || !out || !out->summary) return fail(c, FHIP_E_INVALID, "null argument");
+    if (in->nframes < 0 || in->stream_bytes < 0 || in->nsamples < 0 || in->first_sample < 0)
+        return fail(c, FHIP_E_INVALID, "negative count");
+    if (in->nframes > 0 && (!in->stream || !in->frame_bytes)) return fail(c, FHIP_E_INVALID, "null stream");
+    if (in->nsamples > 0 && !in->pcm) return fail(c, FHIP_E_INVALID, "null pcm");
+    return FHIP_OK;
+}
+}  // namespace
+
+int fhip_verify_frames_dev(fhip_ctx *c, const fhip_verify_in *in, const fhip_verify_out *out)
+{
+    int rc = verify_check(c, in, out);
+    if (rc != FHIP_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return run_verify(c, in->stream, in->stream_bytes, in->frame_bytes, in->nframes, nullptr, in->pcm, in->nsamples,
+                      in->first_sample, c->p.block_size, out->frames, out->summary, nullptr);
+}
+
+int fhip_verify_frames(fhip_ctx *c, const fhip_verify_in *in, const fhip_verify_out *out)
+{
+    int rc = verify_check(c, in, out);
+    if (rc != FHIP_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t sb = (size_t)in->stream_bytes, nf = (size_t)in->nframes;
+    const size_t nv = (size_t)in->nsamples * (size_t)c->p.channels;
+    if (sb > c->d_vstream_bytes) {
+        if (c->d_vstream) (void)hipFree(c->d_vstream);
+        c->d_vstream = nullptr; c->d_vstream_bytes = 0;
+        HIP_TRY(c, hipMalloc((void **)&c->d_vstream, sb));
+        c->d_vstream_bytes = sb;
+    }
+    if (nf > c->d_vfb_cap) {
+        if (c->d_vfb) (void)hipFree(c->d_vfb);
+        c->d_vfb = nullptr; c->d_vfb_cap = 0;
+        HIP_TRY(c, hipMalloc((void **)&c->d_vfb, nf * sizeof(int32_t)));
+        c->d_vfb_cap = nf;
+    }
+    if (nv > c->d_vpcm_vals) {
+        if (c->d_vpcm) (void)hipFree(c->d_vpcm);
+        c->d_vpcm = nullptr; c->d_vpcm_vals = 0;
+        HIP_TRY(c, hipMalloc((void **)&c->d_vpcm, nv * sizeof(int32_t)));
+        c->d_vpcm_vals = nv;
+    }
+    if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_vstream, in->stream, sb, hipMemcpyHostToDevice, c->stream));
+    if (nf) HIP_TRY(c, hipMemcpyAsync(c->d_vfb, in->frame_bytes, nf * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (nv) HIP_TRY(c, hipMemcpyAsync(c->d_vpcm, in->pcm, nv * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    rc = run_verify(c, c->d_vstream, in->stream_bytes, c->d_vfb, in->nframes, nullptr, c->d_vpcm, in->nsamples,
+                    in->first_sample, c->p.block_size, nullptr, nullptr, nullptr);
+    if (rc != FHIP_OK) return rc;
+    long long sum[4] = {0, 0, -1, 0};
+    HIP_TRY(c, hipMemcpyAsync(sum, c->d_vsum, sizeof sum, hipMemcpyDeviceToHost, c->stream));
+    if (out->frames && nf)
+        HIP_TRY(c, hipMemcpyAsync(out->frames, c->d_vrec, nf * sizeof(fhip_verify_rec), hipMemcpyDeviceToHost, c->stream));
+    rc = fhip_sync(c);
+    if (rc != FHIP_OK) return rc;
+    for (int i = 0; i < 4; i++) out->summary[i] = sum[i];
+    return verify_verdict(c, sum, c->d_vrec);
 }
 
 int fhip_prepare_frames(fhip_ctx *c, const int32_t *pcm, int nframes, int n,

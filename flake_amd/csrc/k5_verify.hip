@@ -1,0 +1,777 @@
+// k5_verify.hip -- K5: does every frame of a stream decode to the caller's PCM?
+//
+// The verifier reads the stream's bytes, the frame sizes, the PCM, the index of pcm[0] and the
+// handle's parameters -- nothing the encoder kept on the side.  It checks in the FORWARD direction
+// (DESIGN.md §K5): from the PCM and each subframe header it recomputes what every field of the
+// subframe must hold (warm-up values, residual codewords, partition parameters' positions), and
+// compares those bits with the stream's.  No LPC recurrence runs: the prediction is a FIR over
+// known samples, parallel over samples like K3's.
+//
+//   k_verify_frames  one workgroup: prefix of frame_bytes -> frame offsets, one lane per frame
+//                    parses its header (sync, codes, UTF-8 number, CRC-8) and numbering/coverage
+//                    is checked against the neighbouring frame; VerifyFrame records + summary init
+//   k_verify         one workgroup (256 lanes) per frame: subframes, padding, CRC-16, length
+//   k_verify_final   summary[2..3] from the first failing frame; optional flag bit in totals[3]
+//
+// Every stream read is clamped to the frame's byte range (itself inside the stream, checked by
+// k_verify_frames); every PCM index is checked against nsamples.  A corrupt stream ends in a
+// status code, never in an access outside the buffers.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "kernels.h"
+
+namespace fhip {
+namespace {
+
+constexpr int VT = 256;                 // lanes per frame
+constexpr int RES_CAP = 4608;           // blocks up to this keep their samples and codeword values in LDS
+constexpr int FB_CAP = 12288;           // frames up to this many bytes are staged in LDS
+constexpr int HDR_T = 1024;             // lanes of k_verify_frames
+constexpr unsigned long long KEY_NONE = ~0ull;
+constexpr int ESC = 0x100;              // part_k flag: escape partition, raw width in the low bits
+
+// key: bit position, then subframe, then sample, then status -- the minimum is the first discrepancy
+__device__ __forceinline__ unsigned long long mkkey(long long pos, int sub, int sample, int status)
+{
+    if (pos < 0) pos = 0;
+    if (pos > 0xFFFFFFFFFFll) pos = 0xFFFFFFFFFFll;
+    return ((unsigned long long)pos << 24) | ((unsigned long long)(sub & 15) << 20) |
+           ((unsigned long long)(sample & 0xFFFF) << 4) | (unsigned long long)(status & 15);
+}
+
+// MSB-first bit reader over [0, nbytes) of src; bytes past the end read as zero
+struct Bits {
+    const uint8_t *src;
+    long long nbytes;
+    __device__ __forceinline__ uint32_t byte(long long i) const { return (i >= 0 && i < nbytes) ? src[i] : 0u; }
+    // nb in 0..32
+    __device__ __forceinline__ uint32_t rd(long long p, int nb) const
+    {
+        if (nb <= 0) return 0u;
+        const long long b = p >> 3;
+        uint64_t w = 0;
+        for (int t = 0; t < 5; t++) w = (w << 8) | byte(b + t);
+        const int sh = 40 - (int)(p & 7) - nb;
+        return (uint32_t)((w >> sh) & (nb == 32 ? 0xFFFFFFFFull : ((1ull << nb) - 1ull)));
+    }
+};
+
+__device__ __forceinline__ bool fits_signed(long long v, int w)
+{
+    if (w <= 0) return v == 0;
+    if (w >= 64) return true;
+    const long long lo = -(1ll << (w - 1)), hi = (1ll << (w - 1)) - 1;
+    return v >= lo && v <= hi;
+}
+
+// Compare stream bits [p, p + nb) (nb <= 64) with the low nb bits of val, MSB first.  KEY_NONE when they
+// agree; else the key of the first differing bit (SAMPLES) or of the frame's end (SYNTAX: read past the end).
+__device__ unsigned long long cmp_bits(const Bits &bs, long long p, int nb, uint64_t val, long long end_bits,
+                                       int sub, int sample)
+{
+    while (nb > 0) {
+        if (p >= end_bits) return mkkey(end_bits, sub, 0xFFFF, FHIP_VERIFY_SYNTAX);
+        int take = nb > 32 ? 32 : nb;
+        if (end_bits - p < take) take = (int)(end_bits - p);
+        const uint32_t want = (uint32_t)((val >> (nb - take)) & ((take == 32) ? 0xFFFFFFFFull : ((1ull << take) - 1ull)));
+        const uint32_t got = bs.rd(p, take);
+        const uint32_t d = got ^ want;
+        if (d) return mkkey(p + (__clz(d) - (32 - take)), sub, sample, FHIP_VERIFY_SAMPLES);
+        p += take;
+        nb -= take;
+    }
+    return KEY_NONE;
+}
+
+// q zero bits, a one, the k low bits of u
+__device__ unsigned long long cmp_rice(const Bits &bs, long long p, uint32_t u, int k, long long end_bits, int sub,
+                                       int sample)
+{
+    long long q = (long long)(u >> k);
+    while (q > 0) {
+        if (p >= end_bits) return mkkey(end_bits, sub, 0xFFFF, FHIP_VERIFY_SYNTAX);
+        int take = q > 32 ? 32 : (int)q;
+        if (end_bits - p < take) take = (int)(end_bits - p);
+        const uint32_t got = bs.rd(p, take);
+        if (got) return mkkey(p + (__clz(got) - (32 - take)), sub, sample, FHIP_VERIFY_SAMPLES);
+        p += take;
+        q -= take;
+    }
+    const unsigned long long r = cmp_bits(bs, p, 1, 1u, end_bits, sub, sample);
+    if (r != KEY_NONE) return r;
+    return k ? cmp_bits(bs, p + 1, k, u & ((1u << k) - 1u), end_bits, sub, sample) : KEY_NONE;
+}
+
+__device__ __forceinline__ int sample_rate_code_ok(int code, int rate)
+{
+    switch (code) {
+    case 0: return 1;
+    case 1: return rate == 88200;
+    case 2: return rate == 176400;
+    case 3: return rate == 192000;
+    case 4: return rate == 8000;
+    case 5: return rate == 16000;
+    case 6: return rate == 22050;
+    case 7: return rate == 24000;
+    case 8: return rate == 32000;
+    case 9: return rate == 44100;
+    case 10: return rate == 48000;
+    case 11: return rate == 96000;
+    default: return 0;        // 12..14 carry the rate explicitly (checked there), 15 is invalid
+    }
+}
+
+__device__ __forceinline__ int bps_code_of(int bps)
+{
+    switch (bps) {
+    case 8: return 1;
+    case 12: return 2;
+    case 16: return 4;
+    case 20: return 5;
+    case 24: return 6;
+    case 32: return 7;
+    default: return -1;
+    }
+}
+
+__device__ __forceinline__ uint32_t crc8_byte(uint32_t c, uint32_t b)
+{
+    c ^= b;
+    for (int k = 0; k < 8; k++) c = (c & 0x80u) ? ((c << 1) ^ 0x07u) : (c << 1);
+    return c & 0xFFu;
+}
+
+__device__ __forceinline__ uint32_t crc16_byte(uint32_t c, uint32_t b)
+{
+    c ^= b << 8;
+    for (int k = 0; k < 8; k++) c = (c & 0x8000u) ? ((c << 1) ^ 0x8005u) : (c << 1);
+    return c & 0xFFFFu;
+}
+
+// a * b mod the CRC-16 polynomial x^16 + x^15 + x^2 + 1 (GF(2)); a, b < 2^16
+__device__ __forceinline__ uint32_t gf16_mul(uint32_t a, uint32_t b)
+{
+    uint32_t r = 0;
+    for (int i = 15; i >= 0; i--) {
+        r = (r & 0x8000u) ? (((r << 1) ^ 0x8005u) & 0xFFFFu) : ((r << 1) & 0xFFFFu);
+        if ((b >> i) & 1u) r ^= a;
+    }
+    return r;
+}
+
+// x^(8 m) mod the polynomial: the factor that moves a chunk's CRC past m further bytes
+__device__ uint32_t gf16_xpow8(long long m)
+{
+    uint32_t r = 1u, b = 0x100u;        // x^8
+    while (m > 0) {
+        if (m & 1) r = gf16_mul(r, b);
+        b = gf16_mul(b, b);
+        m >>= 1;
+    }
+    return r;
+}
+
+// ---- k_verify_frames -------------------------------------------------------------------------------
+
+struct HdrOut { int status; long long bit; int n; int hdr_bits; int ch_code; unsigned long long number; };
+
+__device__ HdrOut parse_header(const VerifyArgs &a, const Bits &bs)
+{
+    HdrOut h{FHIP_VERIFY_OK, 0, 0, 0, 0, 0};
+    const long long end = bs.nbytes * 8;
+#define VFAIL(pos, st) do { h.status = (st); h.bit = (pos); return h; } while (0)
+#define NEED(pos, nb) do { if ((pos) + (nb) > end) VFAIL(end, FHIP_VERIFY_SYNTAX); } while (0)
+    NEED(0, 32);
+    const uint32_t w = bs.rd(0, 32);
+    const uint32_t sync = w >> 18;
+    if (sync != 0x3FFEu) VFAIL(__clz((sync ^ 0x3FFEu) << 18), FHIP_VERIFY_HEADER);
+    if ((w >> 17) & 1u) VFAIL(14, FHIP_VERIFY_HEADER);
+    if ((int)((w >> 16) & 1u) != (a.allow_vbs ? 1 : 0)) VFAIL(15, FHIP_VERIFY_HEADER);
+    const int bs_code = (int)((w >> 12) & 15u), sr_code = (int)((w >> 8) & 15u);
+    const int ch_code = (int)((w >> 4) & 15u), bps_code = (int)((w >> 1) & 7u);
+    if (bs_code == 0) VFAIL(16, FHIP_VERIFY_HEADER);
+    int n = bs_code == 1 ? 192 : (bs_code <= 5 ? 576 << (bs_code - 2) : (bs_code >= 8 ? 256 << (bs_code - 8) : 0));
+    if (n && n > a.block_size) VFAIL(16, FHIP_VERIFY_NUMBER);
+    if (sr_code == 15 || (sr_code < 12 && !sample_rate_code_ok(sr_code, a.sample_rate))) VFAIL(20, FHIP_VERIFY_HEADER);
+    if (ch_code > 10 || (ch_code < 8 && ch_code + 1 != a.channels) || (ch_code >= 8 && a.channels != 2))
+        VFAIL(24, FHIP_VERIFY_HEADER);
+    if (bps_code != 0 && bps_code != bps_code_of(a.bps)) VFAIL(28, FHIP_VERIFY_HEADER);
+    if (w & 1u) VFAIL(31, FHIP_VERIFY_HEADER);
+    // UTF-8 style number: 1 .. 7 bytes, up to 36 bits
+    long long p = 32;
+    NEED(p, 8);
+    const uint32_t b0 = bs.rd(p, 8);
+    int extra = 0;
+    unsigned long long num = 0;
+    if (b0 < 0x80u) {
+        num = b0;
+    } else {
+        int ones = 0;
+        while (ones < 8 && ((b0 << ones) & 0x80u)) ones++;
+        if (ones < 2 || ones > 7) VFAIL(p, FHIP_VERIFY_HEADER);
+        extra = ones - 1;
+        num = (ones == 7) ? 0 : (b0 & (0x7Fu >> ones));
+    }
+    p += 8;
+    for (int i = 0; i < extra; i++) {
+        NEED(p, 8);
+        const uint32_t c = bs.rd(p, 8);
+        if ((c & 0xC0u) != 0x80u) VFAIL(p, FHIP_VERIFY_HEADER);
+        num = (num << 6) | (c & 0x3Fu);
+        p += 8;
+    }
+    if (bs_code == 6 || bs_code == 7) {
+        const int nb = bs_code == 6 ? 8 : 16;
+        NEED(p, nb);
+        n = (int)bs.rd(p, nb) + 1;
+        if (n > a.block_size || n > FHIP_MAX_BLOCK) VFAIL(p, FHIP_VERIFY_NUMBER);
+        p += nb;
+    }
+    if (sr_code >= 12) {
+        const int nb = sr_code == 12 ? 8 : 16;
+        NEED(p, nb);
+        const long long v = bs.rd(p, nb);
+        const long long rate = sr_code == 12 ? v * 1000 : (sr_code == 13 ? v : v * 10);
+        if (rate != a.sample_rate) VFAIL(p, FHIP_VERIFY_HEADER);
+        p += nb;
+    }
+    NEED(p, 8);
+    uint32_t c8 = 0;
+    for (long long i = 0; i < (p >> 3); i++) c8 = crc8_byte(c8, bs.byte(i));
+    if (bs.rd(p, 8) != c8) VFAIL(p, FHIP_VERIFY_CRC8);
+    h.n = n;
+    h.hdr_bits = (int)(p + 8);
+    h.ch_code = ch_code;
+    h.number = num;
+    return h;
+#undef NEED
+#undef VFAIL
+}
+
+__device__ long long block_excl_scan(long long v, long long *scratch, int nwaves, long long *total)
+{
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    long long incl = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const long long o = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += o;
+    }
+    if (lane == 63) scratch[wid] = incl;
+    __syncthreads();
+    long long base = 0, tot = 0;
+    for (int q = 0; q < nwaves; q++) {
+        const long long s = scratch[q];
+        if (q < wid) base += s;
+        tot += s;
+    }
+    __syncthreads();
+    *total = tot;
+    return base + incl - v;
+}
+
+__global__ void __launch_bounds__(HDR_T) k_verify_frames(VerifyArgs a)
+{
+    __shared__ long long scratch[HDR_T / 64];
+    __shared__ unsigned long long s_next[HDR_T];      // number + n of each frame of the chunk (VBS)
+    __shared__ int s_ok[HDR_T];
+    __shared__ unsigned long long s_carry_next;
+    __shared__ int s_carry_ok;
+    int count = a.nframes;
+    if (a.dev_count) {
+        const long long d = *a.dev_count;
+        count = d < 0 ? 0 : (d < (long long)a.nframes ? (int)d : a.nframes);
+    }
+    const int t = threadIdx.x;
+    if (t == 0) {
+        a.summary[0] = count;
+        a.summary[1] = 0;
+        a.key[0] = KEY_NONE;
+        s_carry_next = (unsigned long long)a.first_sample;
+        s_carry_ok = 1;
+    }
+    long long base = 0;
+    for (int f0 = 0; f0 < count; f0 += HDR_T) {
+        const int f = f0 + t;
+        const bool live = f < count;
+        const long long fb = live ? (long long)a.frame_bytes[f] : 0;
+        long long tot = 0;
+        const long long off = base + block_excl_scan(fb > 0 ? fb : 0, scratch, HDR_T / 64, &tot);
+        base += tot;
+        VerifyFrame vf{};
+        vf.off = off;
+        vf.bytes = (int)fb;
+        HdrOut h{FHIP_VERIFY_OK, 0, 0, 0, 0, 0};
+        if (live) {
+            if (fb <= 0 || off + fb > a.stream_bytes) {
+                h.status = FHIP_VERIFY_LENGTH;
+                h.bit = fb <= 0 ? 0 : (a.stream_bytes - off) * 8;
+                if (h.bit < 0) h.bit = 0;
+            } else {
+                h = parse_header(a, Bits{a.stream + off, fb});
+            }
+        }
+        // numbering: fixed blocks carry frame numbers (frame f starts at f * block_size), a variable-block-size
+        // stream carries the first sample (the frame before says where this one starts)
+        const unsigned long long snum = a.allow_vbs ? h.number : h.number * (unsigned long long)a.block_size;
+        s_next[t] = snum + (unsigned long long)h.n;
+        s_ok[t] = h.status == FHIP_VERIFY_OK || h.status == FHIP_VERIFY_CRC8;
+        __syncthreads();
+        if (live && (h.status == FHIP_VERIFY_OK || h.status == FHIP_VERIFY_CRC8)) {
+            long long rel;
+            bool num_ok, cover_ok;
+            if (!a.allow_vbs) {
+                rel = (long long)f * a.block_size;
+                num_ok = snum == (unsigned long long)(a.first_sample + rel);
+                cover_ok = (f == count - 1) ? (rel + h.n == a.nsamples) : (h.n == a.block_size);
+            } else {
+                // (a frame whose own header is broken has already failed: its successor is not blamed for it)
+                const unsigned long long prev_next = t ? s_next[t - 1] : s_carry_next;
+                const int prev_ok = t ? s_ok[t - 1] : s_carry_ok;
+                const unsigned long long want = f == 0 ? (unsigned long long)a.first_sample : (prev_ok ? prev_next : snum);
+                rel = (long long)(snum - (unsigned long long)a.first_sample);
+                num_ok = snum == want;
+                cover_ok = (f == count - 1) ? (rel + h.n == a.nsamples) : true;
+            }
+            cover_ok = cover_ok && rel >= 0 && rel <= a.nsamples && h.n <= a.nsamples - rel;
+            if (!num_ok) { h.status = FHIP_VERIFY_NUMBER; h.bit = 32; }
+            else if (!cover_ok) { h.status = FHIP_VERIFY_NUMBER; h.bit = 16; }
+            vf.rel_start = rel;
+        }
+        if (live) {
+            vf.n = h.n;
+            vf.hdr_bits = h.hdr_bits;
+            vf.ch_code = h.ch_code;
+            vf.status = h.status;
+            vf.bit = h.bit;
+            a.ws[f] = vf;
+        }
+        __syncthreads();
+        if (t == HDR_T - 1) { s_carry_next = s_next[t]; s_carry_ok = s_ok[t]; }
+        __syncthreads();
+    }
+}
+
+// ---- k_verify --------------------------------------------------------------------------------------
+
+struct SubHdr {
+    int type;          // FHIP_SUB_*
+    int order, wasted, w, shift, method, porder;
+    long long pos;     // CONSTANT: the value; VERBATIM / FIXED / LPC: the first warm-up (or verbatim) value
+    long long res;     // FIXED / LPC: the residual section (method bits)
+    int coef[FHIP_MAX_ORDER];
+};
+
+__device__ __forceinline__ long long pcm_at(const VerifyArgs &a, long long g, int c)
+{
+    if (g < 0 || g >= a.nsamples) return 0;          // (pass 1 keeps every frame inside [0, nsamples))
+    return (long long)a.pcm[g * a.channels + c];
+}
+
+// the subframe's value before wasted-bit removal: the frame's channel transform of the input.  Samples are
+// restored wrapped to int32 (as the oracle decoder and libFLAC's 32-bit output do), so the side channel of a
+// 32-bit stream is L - R wrapped to int32 -- a no-op below 32 bits
+__device__ __forceinline__ long long wrap32(long long v) { return (long long)(int32_t)(uint32_t)(uint64_t)v; }
+__device__ __forceinline__ long long chan_at(const VerifyArgs &a, long long g, int ch_code, int c)
+{
+    if (ch_code < 8) return pcm_at(a, g, c);
+    const long long l = pcm_at(a, g, 0), r = pcm_at(a, g, 1);
+    if (ch_code == FHIP_CH_LEFT_SIDE) return c == 0 ? l : wrap32(l - r);
+    if (ch_code == FHIP_CH_RIGHT_SIDE) return c == 0 ? wrap32(l - r) : r;
+    return c == 0 ? ((l + r) >> 1) : wrap32(l - r);   // mid / side
+}
+
+// A raw value field of w bits (warm-up, VERBATIM, CONSTANT).  A 33-bit field (the side channel of a 32-bit
+// stream) is read wrapped to int32: only its low 32 bits carry the value.
+__device__ unsigned long long cmp_raw(const Bits &bs, long long p, int w, long long v, long long end, int sub,
+                                      int sample)
+{
+    if (!fits_signed(v, w)) return mkkey(p, sub, sample, FHIP_VERIFY_SAMPLES);
+    if (w > 32) { p += w - 32; w = 32; }
+    return cmp_bits(bs, p, w, (uint64_t)v, end, sub, sample);
+}
+
+struct Ctx {
+    const VerifyArgs *a;
+    long long g0;          // absolute PCM index (relative to pcm[0]) of the frame's first sample
+    int ch_code, c, n;
+    bool resident;
+    const int32_t *y;      // LDS values after wasted-bit removal (resident)
+    const uint32_t *zz;    // LDS zig-zag residuals (resident)
+    const SubHdr *sh;
+};
+
+__device__ __forceinline__ long long y_at(const Ctx &x, int i)
+{
+    if (x.resident) return x.y[i];
+    return chan_at(*x.a, x.g0 + i, x.ch_code, x.c) >> x.sh->wasted;
+}
+
+// residual e_i of a FIXED / LPC subframe at sample i >= order: the int32 e with (int32)(e + prediction) = sample
+__device__ long long resid_at(const Ctx &x, int i, bool *ok)
+{
+    const SubHdr &s = *x.sh;
+    long long pred = 0;
+    if (s.type == FHIP_SUB_FIXED) {
+        switch (s.order) {
+        case 1: pred = y_at(x, i - 1); break;
+        case 2: pred = 2 * y_at(x, i - 1) - y_at(x, i - 2); break;
+        case 3: pred = 3 * y_at(x, i - 1) - 3 * y_at(x, i - 2) + y_at(x, i - 3); break;
+        case 4: pred = 4 * y_at(x, i - 1) - 6 * y_at(x, i - 2) + 4 * y_at(x, i - 3) - y_at(x, i - 4); break;
+        default: break;
+        }
+    } else {
+        long long acc = 0;
+        for (int j = 0; j < s.order; j++) acc += (long long)s.coef[j] * y_at(x, i - 1 - j);
+        pred = acc >> s.shift;
+    }
+    *ok = true;
+    return wrap32(y_at(x, i) - pred);
+}
+
+__device__ __forceinline__ uint32_t zigzag(long long e)
+{
+    const int32_t v = (int32_t)e;
+    return ((uint32_t)v << 1) ^ (uint32_t)(v >> 31);
+}
+
+__device__ __forceinline__ uint32_t zz_at(const Ctx &x, int i)
+{
+    if (x.resident) return x.zz[i];
+    bool ok;
+    return zigzag(resid_at(x, i, &ok));
+}
+
+// lane 0: the subframe header at pos.  Returns KEY_NONE or the key of a syntax error.
+__device__ unsigned long long parse_subframe(const Bits &bs, long long pos, long long end, int sub_bps, int n,
+                                             SubHdr *s, int sub)
+{
+#define SFAIL(p) return mkkey((p), sub, 0xFFFF, FHIP_VERIFY_SYNTAX)
+#define SNEED(p, nb) do { if ((p) + (nb) > end) SFAIL(end); } while (0)
+    long long p = pos;
+    SNEED(p, 8);
+    const uint32_t h = bs.rd(p, 8);
+    if (h & 0x80u) SFAIL(p);
+    const int t = (int)((h >> 1) & 63u);
+    p += 8;
+    int wasted = 0;
+    if (h & 1u) {
+        // unary count of wasted bits - 1
+        int k = 0;
+        for (;;) {
+            SNEED(p, 1);
+            const uint32_t bit = bs.rd(p, 1);
+            p++;
+            if (bit) break;
+            if (++k >= sub_bps) SFAIL(p - 1);
+        }
+        wasted = k + 1;
+        if (wasted >= sub_bps) SFAIL(p - 1);
+    }
+    s->wasted = wasted;
+    s->w = sub_bps - wasted;
+    s->order = 0; s->shift = 0; s->method = 0; s->porder = 0; s->res = 0;
+    if (t == 0) {
+        s->type = FHIP_SUB_CONSTANT;
+    } else if (t == 1) {
+        s->type = FHIP_SUB_VERBATIM;
+    } else if (t >= 8 && t <= 12) {
+        s->type = FHIP_SUB_FIXED;
+        s->order = t - 8;
+    } else if (t >= 32) {
+        s->type = FHIP_SUB_LPC;
+        s->order = t - 31;
+    } else {
+        SFAIL(pos + 1);
+    }
+    s->pos = p;
+    if (s->type == FHIP_SUB_CONSTANT || s->type == FHIP_SUB_VERBATIM) return KEY_NONE;
+    if (s->order > n) SFAIL(pos + 1);
+    p += (long long)s->order * s->w;
+    if (s->type == FHIP_SUB_LPC) {
+        SNEED(p, 9);
+        const int prec = (int)bs.rd(p, 4) + 1;
+        if (prec == 16) SFAIL(p);
+        p += 4;
+        const uint32_t sh = bs.rd(p, 5);
+        if (sh & 0x10u) SFAIL(p);                          // negative shift
+        s->shift = (int)sh;
+        p += 5;
+        SNEED(p, (long long)s->order * prec);
+        for (int j = 0; j < s->order; j++) {
+            uint32_t v = bs.rd(p, prec);
+            if (prec < 32 && (v & (1u << (prec - 1)))) v |= ~((1u << prec) - 1u);
+            s->coef[j] = (int32_t)v;
+            p += prec;
+        }
+    }
+    SNEED(p, 6);
+    s->res = p;
+    const uint32_t m = bs.rd(p, 6);
+    s->method = (int)(m >> 4);
+    s->porder = (int)(m & 15u);
+    if (s->method > 1) SFAIL(p);
+    if ((n & ((1 << s->porder) - 1)) || (n >> s->porder) < s->order) SFAIL(p + 2);
+    return KEY_NONE;
+#undef SNEED
+#undef SFAIL
+}
+
+__global__ void __launch_bounds__(VT) k_verify(VerifyArgs a)
+{
+    __shared__ int32_t y_lds[RES_CAP];
+    __shared__ uint32_t zz_lds[RES_CAP];
+    __shared__ uint8_t fb_lds[FB_CAP];
+    __shared__ long long part_base[FHIP_MAX_PARTS];
+    __shared__ int part_k[FHIP_MAX_PARTS];
+    __shared__ long long scratch[VT / 64];
+    __shared__ SubHdr s_sh;
+    __shared__ unsigned long long s_key;
+    __shared__ int s_bad, s_walked;
+    __shared__ long long s_pos, s_wP, s_wQ;
+    __shared__ int s_stop;
+    __shared__ uint32_t s_crc;
+
+    const int f = blockIdx.x, t = threadIdx.x;
+    if (a.dev_count && (long long)f >= *a.dev_count) return;
+    const VerifyFrame vf = a.ws[f];
+    unsigned long long key = KEY_NONE;
+    if (vf.status != FHIP_VERIFY_OK) {
+        key = mkkey(vf.bit, 15, 0xFFFF, vf.status);
+    } else {
+        // stage the frame (pass 1 put it inside the stream)
+        const uint8_t *src = a.stream + vf.off;
+        const bool staged = vf.bytes <= FB_CAP;
+        if (staged)
+            for (int i = t; i < vf.bytes; i += VT) fb_lds[i] = src[i];
+        const Bits bs{staged ? fb_lds : src, vf.bytes};
+        const long long end = (long long)vf.bytes * 8;
+        const int n = vf.n;
+        const int nch = a.channels;
+        if (t == 0) { s_key = KEY_NONE; s_pos = vf.hdr_bits; }
+        __syncthreads();
+        for (int c = 0; c < nch; c++) {
+            __syncthreads();                   // everybody is done with the previous subframe's shared state
+            const bool side = (vf.ch_code == FHIP_CH_LEFT_SIDE && c == 1) || (vf.ch_code == FHIP_CH_RIGHT_SIDE && c == 0) ||
+                              (vf.ch_code == FHIP_CH_MID_SIDE && c == 1);
+            const int sub_bps = a.bps + (side ? 1 : 0);
+            if (t == 0) {
+                const unsigned long long k = parse_subframe(bs, s_pos, end, sub_bps, n, &s_sh, c);
+                if (k != KEY_NONE) s_key = k;
+                s_bad = n;
+            }
+            __syncthreads();
+            if (s_key != KEY_NONE) break;
+            const SubHdr &sh = s_sh;
+            const bool resident = n <= RES_CAP;
+            Ctx x{&a, vf.rel_start, vf.ch_code, c, n, resident, y_lds, zz_lds, &sh};
+            // the values the subframe must carry; the first sample with set wasted bits has no encoding
+            const long long wmask = (1ll << sh.wasted) - 1;
+            for (int i = t; i < n; i += VT) {
+                const long long v = chan_at(a, vf.rel_start + i, vf.ch_code, c);
+                if (v & wmask) atomicMin(&s_bad, i);
+                if (resident) y_lds[i] = (int32_t)(v >> sh.wasted);
+            }
+            __syncthreads();
+            const int bad = s_bad;
+            const int w = sh.w;
+            unsigned long long mine = KEY_NONE;
+            long long sub_end = 0;
+            if (sh.type == FHIP_SUB_CONSTANT) {
+                if (t == 0) {
+                    const long long v0 = y_at(x, 0);
+                    mine = bad == 0 ? mkkey(sh.pos, c, 0, FHIP_VERIFY_SAMPLES) : cmp_raw(bs, sh.pos, w, v0, end, c, 0);
+                }
+                if (mine == KEY_NONE) {
+                    const long long v0 = y_at(x, 0);
+                    for (int i = t; i < n; i += VT)
+                        if (i == bad || y_at(x, i) != v0) { mine = mkkey(sh.pos, c, i, FHIP_VERIFY_SAMPLES); break; }
+                }
+                sub_end = sh.pos + w;
+            } else {
+                const int nraw = sh.type == FHIP_SUB_VERBATIM ? n : sh.order;
+                for (int i = t; i < nraw && mine == KEY_NONE; i += VT) {
+                    const long long v = y_at(x, i), p = sh.pos + (long long)i * w;
+                    mine = i == bad ? mkkey(p, c, i, FHIP_VERIFY_SAMPLES) : cmp_raw(bs, p, w, v, end, c, i);
+                }
+                sub_end = sh.pos + (long long)nraw * w;
+            }
+            if (sh.type == FHIP_SUB_FIXED || sh.type == FHIP_SUB_LPC) {
+                const int order = sh.order;
+                if (resident) {
+                    for (int i = order + t; i < n; i += VT) {
+                        bool ok;
+                        zz_lds[i] = zigzag(resid_at(x, i, &ok));
+                    }
+                }
+                __syncthreads();
+                const int npart = 1 << sh.porder, psz = n >> sh.porder;
+                const int pbits = sh.method ? 5 : 4, esc = sh.method ? 31 : 15;
+                // partitions in groups of FHIP_MAX_PARTS (FLAC allows partition order 15): the walk over a group's
+                // parameters and lengths (one wave, a step per partition), then every lane checks its codewords
+                if (t == 0) { s_wP = sh.res + 6; s_wQ = 0; s_stop = 0; }
+                __syncthreads();
+                for (int g0 = 0; g0 < npart; g0 += FHIP_MAX_PARTS) {
+                    const int g1 = min(npart, g0 + FHIP_MAX_PARTS);
+                    const long long Qbase = s_wQ;           // codeword bits of the groups before
+                    const long long P0 = s_wP;
+                    __syncthreads();
+                    if (t < 64) {
+                        long long P = P0, Q = Qbase;
+                        int walked = g0;
+                        unsigned long long wkey = KEY_NONE;
+                        for (int j = g0; j < g1; j++) {
+                            if (P + pbits > end) { wkey = mkkey(end, c, 0xFFFF, FHIP_VERIFY_SYNTAX); break; }
+                            int k = (int)bs.rd(P, pbits);
+                            P += pbits;
+                            const int s0 = j ? j * psz : order, s1 = (j + 1) * psz;
+                            long long len;
+                            if (k == esc) {
+                                if (P + 5 > end) { wkey = mkkey(end, c, 0xFFFF, FHIP_VERIFY_SYNTAX); break; }
+                                const int raw = (int)bs.rd(P, 5);
+                                P += 5;
+                                k = ESC | raw;
+                                len = (long long)(s1 - s0) * raw;
+                            } else {
+                                long long sum = 0;
+                                for (int i = s0 + t; i < s1; i += 64) sum += zz_at(x, i) >> k;
+                                for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
+                                len = sum + (long long)(s1 - s0) * (1 + k);
+                            }
+                            if (t == 0) { part_base[j - g0] = P - Q; part_k[j - g0] = k; }
+                            P += len;
+                            Q += len;
+                            walked = j + 1;
+                        }
+                        if (t == 0) {
+                            s_walked = walked;
+                            s_wP = P;
+                            s_wQ = Q;
+                            if (wkey != KEY_NONE) { atomicMin(&s_key, wkey); s_stop = 1; }
+                        }
+                    }
+                    __syncthreads();
+                    const int walked = s_walked;
+                    const int lo = g0 ? g0 * psz : order;
+                    const int lim = walked * psz;                   // samples whose partitions were read
+                    const int nres = lim > lo ? lim - lo : 0;
+                    const int seg = (nres + VT - 1) / VT;
+                    const int i0 = lo + t * seg, i1 = min(i0 + seg, lim);
+                    long long lsum = 0;
+                    for (int i = i0; i < i1; i++) {
+                        const int k = part_k[i / psz - g0];
+                        lsum += (k & ESC) ? (k & 31) : (long long)(zz_at(x, i) >> k) + 1 + k;
+                    }
+                    long long tot;
+                    long long Qi = Qbase + block_excl_scan(lsum, scratch, VT / 64, &tot);
+                    for (int i = i0; i < i1 && mine == KEY_NONE; i++) {
+                        const int j = i / psz - g0, k = part_k[j];
+                        const long long p = part_base[j] + Qi;
+                        bool ok;
+                        const long long e = resid_at(x, i, &ok);
+                        if (i == bad || !ok) { mine = mkkey(p, c, i, FHIP_VERIFY_SAMPLES); break; }
+                        if (k & ESC) {
+                            const int raw = k & 31;
+                            mine = fits_signed(e, raw) ? cmp_bits(bs, p, raw, (uint64_t)e, end, c, i)
+                                                       : mkkey(p, c, i, FHIP_VERIFY_SAMPLES);
+                            Qi += raw;
+                        } else {
+                            const uint32_t u = zigzag(e);
+                            mine = cmp_rice(bs, p, u, k, end, c, i);
+                            Qi += (long long)(u >> k) + 1 + k;
+                        }
+                    }
+                    if (mine != KEY_NONE) atomicMin(&s_key, mine);
+                    mine = KEY_NONE;
+                    __syncthreads();
+                    const bool stop = s_stop || s_key != KEY_NONE;
+                    __syncthreads();
+                    if (stop) break;
+                }
+                if (t == 0) s_pos = s_wP;
+            } else if (t == 0) {
+                s_pos = sub_end;
+            }
+            if (mine != KEY_NONE) atomicMin(&s_key, mine);
+            __syncthreads();
+            if (s_key != KEY_NONE) break;
+        }
+        // padding to the byte, CRC-16, the end
+        const bool clean = s_key == KEY_NONE;
+        __syncthreads();
+        if (clean) {
+            const long long p = s_pos;
+            const long long body = (p + 7) >> 3;                      // bytes the CRC-16 covers
+            if (t == 0) {
+                unsigned long long k = KEY_NONE;
+                if (p > end) k = mkkey(end, 15, 0xFFFF, FHIP_VERIFY_SYNTAX);
+                else if (body * 8 > p && bs.rd(p, (int)(body * 8 - p)) != 0) {
+                    const int nb = (int)(body * 8 - p);
+                    const uint32_t v = bs.rd(p, nb);
+                    k = mkkey(p + (__clz(v) - (32 - nb)), 15, 0xFFFF, FHIP_VERIFY_PADDING);
+                } else if (body + 2 > vf.bytes) {
+                    k = mkkey(end, 15, 0xFFFF, FHIP_VERIFY_LENGTH);
+                }
+                s_key = k;
+                s_crc = 0;
+            }
+            __syncthreads();
+            const bool framed = s_key == KEY_NONE;
+            __syncthreads();
+            if (framed) {
+                // CRC-16 of [0, body): a chunk per lane, moved to the end of the body in GF(2) and xor-ed
+                const long long L = (body + VT - 1) / VT;
+                const long long b0 = (long long)t * L, b1 = min(b0 + L, body);
+                uint32_t crc = 0;
+                for (long long i = b0; i < b1; i++) crc = crc16_byte(crc, bs.byte(i));
+                if (b0 < b1 && crc) crc = gf16_mul(crc, gf16_xpow8(body - b1));
+                for (int d = 32; d > 0; d >>= 1) crc ^= (uint32_t)__shfl_xor((int)crc, d, 64);
+                if ((t & 63) == 0 && crc) atomicXor(&s_crc, crc);
+                __syncthreads();
+                if (t == 0) {
+                    const uint32_t got = bs.rd(body * 8, 16);
+                    if (got != s_crc) s_key = mkkey(body * 8, 15, 0xFFFF, FHIP_VERIFY_CRC16);
+                    else if (body + 2 != vf.bytes) s_key = mkkey((body + 2) * 8, 15, 0xFFFF, FHIP_VERIFY_LENGTH);
+                }
+            }
+        }
+        __syncthreads();
+        key = s_key;
+    }
+    if (t == 0) {
+        const int status = key == KEY_NONE ? FHIP_VERIFY_OK : (int)(key & 15);
+        if (a.recs) {
+            fhip_verify_rec r;
+            r.status = status;
+            r.bit = status == FHIP_VERIFY_OK ? -1 : (int32_t)min((long long)(key >> 24), 0x7FFFFFFFll);
+            const int sub = (int)((key >> 20) & 15), smp = (int)((key >> 4) & 0xFFFF);
+            r.subframe = (status == FHIP_VERIFY_OK || sub == 15) ? -1 : sub;
+            r.sample = (status == FHIP_VERIFY_SAMPLES && smp != 0xFFFF) ? smp : -1;
+            a.recs[f] = r;
+        }
+        if (status != FHIP_VERIFY_OK) {
+            atomicAdd((unsigned long long *)&a.summary[1], 1ull);
+            atomicMin(&a.key[0], ((unsigned long long)f << 8) | (unsigned long long)status);
+        }
+    }
+}
+
+__global__ void k_verify_final(VerifyArgs a)
+{
+    const unsigned long long k = a.key[0];
+    a.summary[2] = k == KEY_NONE ? -1 : (long long)(k >> 8);
+    a.summary[3] = k == KEY_NONE ? 0 : (long long)(k & 0xFF);
+    if (a.totals && k != KEY_NONE) a.totals[3] |= 4;
+}
+
+}  // namespace
+
+hipError_t launch_verify(hipStream_t st, const VerifyArgs &a)
+{
+    hipLaunchKernelGGL(k_verify_frames, dim3(1), dim3(HDR_T), 0, st, a);
+    if (a.nframes > 0) hipLaunchKernelGGL(k_verify, dim3(a.nframes), dim3(VT), 0, st, a);
+    hipLaunchKernelGGL(k_verify_final, dim3(1), dim3(1), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace fhip

@@ -207,4 +207,28 @@ size_t encode_lds_bytes(int n);
 // Fast-path geometry of K3 for a block size: C samples per thread, T threads, n = C*T.
 bool fast_geometry(const fhip_params &p, int n, int *C, int *T);
 
+// K5 (k5_verify.hip): does each frame of a stream decode to the caller's PCM?  Reads the stream, the
+// frame sizes, the PCM and the parameters below -- no encoder intermediate.  Three launches on st:
+// k_verify_frames (one workgroup: offsets, headers, numbering; fills ws[] and zeroes the summary),
+// k_verify (a workgroup per frame), k_verify_final (summary[2..3]; totals[3] |= 4 when a frame failed).
+struct VerifyFrame {
+    long long off;          // byte offset of the frame in the stream
+    long long rel_start;    // its first sample, as an index into pcm
+    long long bit;          // status != OK: bit of the first discrepancy
+    int bytes, n, hdr_bits, ch_code, status;
+};
+struct VerifyArgs {
+    const uint8_t *stream; long long stream_bytes;
+    const int32_t *frame_bytes; int nframes;      // nframes: the grid (and the count when dev_count is null)
+    const long long *dev_count;                  // optional: the real frame count lives on the device
+    const int32_t *pcm; long long nsamples; long long first_sample;
+    int channels, bps, block_size, sample_rate, allow_vbs;
+    VerifyFrame *ws;                             // [nframes]
+    fhip_verify_rec *recs;                       // optional [nframes]
+    long long *summary;                          // [4]
+    unsigned long long *key;                     // [1] scratch: (first failing frame << 8) | status
+    long long *totals;                           // optional: fhip_encode_blocks_vbs_dev's totals
+};
+hipError_t launch_verify(hipStream_t st, const VerifyArgs &a);
+
 }  // namespace fhip

@@ -4,8 +4,11 @@
  * samples, flake_encode_frame(), write the frame, rewrite STREAMINFO at the
  * end), with the frames of many blocks encoded per GPU batch.
  *
- *   flake_amd_cli [-0..-12] [-b blocksize] in.wav out.flac
- *   flake_amd_cli [-0..-12] --synth FRAMES [--channels C] [--bps B] out.flac
+ *   flake_amd_cli [-0..-12] [-b blocksize] [--verify] in.wav out.flac
+ *   flake_amd_cli [-0..-12] --synth FRAMES [--channels C] [--bps B] [--verify] out.flac
+ *
+ * --verify checks on the GPU that every frame decodes to its input (flake_amd_set_verify)
+ * and exits non-zero with the verifier's message when one does not.
  *
  * Only canonical PCM WAV (8/16/24/32 bit) is read; this is a harness for the
  * host API, not a replacement for the reference's libpcm_io.
@@ -74,7 +77,7 @@ int main(int argc, char **argv)
 {
     FlakeAmdContext s;
     memset(&s, 0, sizeof s);
-    int level = 5, bsize = -1, synth = 0, channels = 2, bps = 16;
+    int level = 5, bsize = -1, synth = 0, channels = 2, bps = 16, verify = 0;
     const char *in = NULL, *out = NULL;
     for (int i = 1; i < argc; i++) {
         if (argv[i][0] == '-' && argv[i][1] >= '0' && argv[i][1] <= '9') level = atoi(argv[i] + 1);
@@ -82,11 +85,12 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--synth") && i + 1 < argc) synth = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--channels") && i + 1 < argc) channels = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--bps") && i + 1 < argc) bps = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--verify")) verify = 1;
         else if (!in && !synth) in = argv[i];
         else out = argv[i];
     }
     if (!out || (!in && !synth)) {
-        fprintf(stderr, "usage: %s [-0..-12] [-b blocksize] (in.wav | --synth FRAMES [--channels C] [--bps B]) out.flac\n", argv[0]);
+        fprintf(stderr, "usage: %s [-0..-12] [-b blocksize] [--verify] (in.wav | --synth FRAMES [--channels C] [--bps B]) out.flac\n", argv[0]);
         return 2;
     }
     wav_t w;
@@ -104,6 +108,7 @@ int main(int argc, char **argv)
     if (flake_amd_validate_params(&s) < 0) { fprintf(stderr, "invalid parameters\n"); return 1; }
     int hlen = flake_amd_encode_init(&s);                            /* flake.c:558 */
     if (hlen < 0) { fprintf(stderr, "encoder init failed (%d)\n", hlen); return 1; }
+    if (verify && flake_amd_set_verify(&s, 1)) { fprintf(stderr, "cannot turn verification on\n"); return 1; }
     FILE *fo = fopen(out, "wb");
     if (!fo) { perror(out); return 1; }
     fwrite(s.header, 1, (size_t)hlen, fo);

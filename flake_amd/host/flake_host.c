@@ -50,6 +50,7 @@ typedef struct host_ctx {
                                              on the host, one upload / download per piece length) */
     int md5_off;                          /* FLAKE_AMD_MD5=0: STREAMINFO carries the all-zero "not computed" MD5 */
     int trace;                            /* FLAKE_AMD_TRACE=1: phase times of every batch on stderr */
+    int verify;                           /* flake_amd_set_verify: every batch's frames checked on the device */
     /* FLAKE_AMD_LOOKAHEAD=N: flake_encode_frame() queues up to N whole blocks and
      * encodes them as one GPU batch (see flake_amd_encode_frame) */
     int lookahead;
@@ -232,6 +233,17 @@ FLAKE_AMD_API int flake_amd_validate_params(const FlakeAmdContext *s)
 }
 
 FLAKE_AMD_API const char *flake_amd_get_version(void) { return "flake-amd 0.1"; }
+
+/* Verification (K5) of every later batch on the device, on every path; one switch for both handles. */
+FLAKE_AMD_API int flake_amd_set_verify(FlakeAmdContext *s, int on)
+{
+    if (!s || !s->private_ctx) return -1;
+    host_ctx *c = (host_ctx *)s->private_ctx;
+    c->verify = on != 0;
+    if (c->hip && fhip_set_verify(c->hip, c->verify) != FHIP_OK) return -1;
+    if (c->hip2 && fhip_set_verify(c->hip2, c->verify) != FHIP_OK) return -1;
+    return 0;
+}
 
 FLAKE_AMD_API const char *flake_amd_last_error(const FlakeAmdContext *s)
 {
@@ -880,7 +892,9 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const int32_t *pc
     int *slot_of = (int *)malloc(sizeof(int) * (size_t)np);
     char *done = (char *)calloc((size_t)np, 1);
     uint32_t *num_of = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)np);
-    if (!slot_of || !done || !num_of) goto out;
+    int32_t *fsz = (int32_t *)malloc(sizeof(int32_t) * (size_t)(np ? np : 1));     /* frame sizes, stream order */
+    const uint32_t frame_count0 = c->frame_count;
+    if (!slot_of || !done || !num_of || !fsz) goto out;
     {
         /* frame numbers in stream order (encode.c:969-975) */
         uint32_t fc = c->frame_count;
@@ -910,6 +924,7 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const int32_t *pc
                 fhip_params hp2 = c->hp;
                 hp2.variable_block_size = 0;
                 c->hip2_state = (fhip_create(&c->hip2, c->device, &hp2, c->chunk_frames) == FHIP_OK) ? 1 : -1;
+                if (c->hip2_state > 0) (void)fhip_set_verify(c->hip2, c->verify);
             }
             if (c->hip2_state < 0) c->hip2 = NULL;                 /* fine: one handle, one pass */
             if (c->hip2 && c->chunk_frames > 0 && np >= 2 * c->chunk_frames) {
@@ -1003,6 +1018,7 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const int32_t *pc
                 else fs = -1;
             }
             if (fs < 0) { snprintf(c->err, sizeof c->err, "output buffer too small"); goto out; }
+            fsz[i] = fs;
             if (fs > c->max_frame_size) c->max_frame_size = fs;    /* encode.c:967 */
             c->frame_count += s->params.allow_vbs ? (uint32_t)pieces[i].n : 1u;   /* encode.c:969-975 */
             if (frame_sizes) {
@@ -1013,6 +1029,21 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const int32_t *pc
         }
         total = (long long)pos;
         t_out = now_ms() - to0;
+    }
+    if (c->verify) {
+        /* frames assembled or ordered here: one more upload, the same check (K5) */
+        const long long first = s->params.allow_vbs ? (long long)frame_count0
+                                                     : (long long)frame_count0 * (long long)s->params.block_size;
+        fhip_verify_in vi = {out, total, fsz, np, pcm, (int64_t)count * block_size, first};
+        int64_t summary[4] = {0, 0, -1, 0};
+        fhip_verify_out vo = {NULL, summary};
+        const int rc = fhip_verify_frames(c->hip, &vi, &vo);
+        if (rc != FHIP_OK) {
+            snprintf(c->err, sizeof c->err, "fhip_verify_frames: %s (%s)", fhip_strerror(rc), fhip_last_error(c->hip));
+            c->frame_count = frame_count0;           /* the batch's frames are not part of the stream */
+            total = -1;
+            goto out;
+        }
     }
 hashed:
     if (c->trace)
@@ -1028,7 +1059,7 @@ out:
     if (md5_running) pthread_join(md5_thread, NULL);
     if (md5_done && total >= 0) c->md5 = md5_next;
     free(dev_nf); free(dev_sizes);
-    free(pieces); free(scratch); free(slot_of); free(done); free(num_of);
+    free(pieces); free(scratch); free(slot_of); free(done); free(num_of); free(fsz);
     return total;
 }
 

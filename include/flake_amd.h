@@ -109,6 +109,12 @@ FLAKE_AMD_API void flake_amd_encode_close(FlakeAmdContext *s);
 FLAKE_AMD_API int flake_amd_get_streaminfo(const FlakeAmdContext *s, FlakeAmdStreaminfo *si);
 FLAKE_AMD_API void flake_amd_write_streaminfo(const FlakeAmdStreaminfo *si, unsigned char *data34);
 FLAKE_AMD_API const char *flake_amd_get_version(void);
+/* Verification on the device, off by default (not a field: FlakeAmdEncodeParams keeps libflake's layout).
+ * While on, every frame an encode call writes is checked to decode, by a FLAC decoder that follows the
+ * specification, to the samples it was given (fhip_verify_frames, include/flakehip.h); a batch that fails
+ * makes the call return -1 with flake_amd_last_error() naming the frame.  The bytes are the same either way.
+ * Call after flake_amd_encode_init(); returns 0, or -1 without a context. */
+FLAKE_AMD_API int flake_amd_set_verify(FlakeAmdContext *s, int on);
 /* Text of the last error of this context ("" if none). */
 FLAKE_AMD_API const char *flake_amd_last_error(const FlakeAmdContext *s);
 

@@ -48,7 +48,8 @@ enum {
     FHIP_E_HIP         = -2,    /* a HIP runtime call failed; see fhip_last_error() */
     FHIP_E_UNSUPPORTED = -3,    /* valid libflake parameters this layer does not cover */
     FHIP_E_INVALID     = -4,    /* parameters flake_validate_params() would reject */
-    FHIP_E_NOMEM       = -5
+    FHIP_E_NOMEM       = -5,
+    FHIP_E_VERIFY      = -6     /* the stream does not decode to the input (fhip_set_verify) */
 };
 
 /* subframe types (encode.h:37-40) and channel modes (encode.h:42-46) */
@@ -331,6 +332,72 @@ FHIP_API int fhip_vbs_split(fhip_ctx *ctx, const int32_t *pcm, int nblocks, int 
  * encode.c:541-694, for nframes blocks; fills info[].obits/wasted/ch_mode. */
 FHIP_API int fhip_prepare_frames(fhip_ctx *ctx, const int32_t *pcm, int nframes, int n,
                         int32_t *samples, fhip_subframe_info *info);
+
+/* ---- verification --------------------------------------------------- */
+
+/*
+ * Does every frame of a stream decode, by a FLAC decoder that follows the specification, to the
+ * caller's PCM?  The verifier (K5) reads only what is below and the handle's fhip_params -- never
+ * what the encoder kept on the side -- and checks, per frame: the header (sync, reserved bits,
+ * blocking strategy = allow_vbs, channel assignment, sample-size and sample-rate codes, CRC-8),
+ * numbering and coverage (the frames cover [first_sample, first_sample + nsamples) in order, each
+ * sample once; a fixed-block stream numbers frames, frame f starting at f * block_size, a
+ * variable-block-size one numbers samples), every subframe (CONSTANT, VERBATIM, FIXED 0-4,
+ * LPC 1-32, wasted bits, RICE / RICE2, escape partitions), the zero padding, CRC-16 and the length.
+ * Samples are restored the way libFLAC does: a 64-bit prediction sum, an arithmetic shift, the
+ * sample wrapped to int32.  STREAMINFO's MD5 is not checked.
+ */
+typedef struct fhip_verify_in {
+    const uint8_t *stream;        /* the frames back to back */
+    int64_t        stream_bytes;
+    const int32_t *frame_bytes;   /* [nframes] size of each frame; frame f starts at the sum of those before it */
+    int32_t        nframes;
+    const int32_t *pcm;           /* [nsamples][channels] interleaved int32 (flake_encode_frame's contract) */
+    int64_t        nsamples;
+    int64_t        first_sample;  /* absolute index of pcm[0] in the stream */
+} fhip_verify_in;
+
+/* per-frame status: the first failing check in stream order */
+enum {
+    FHIP_VERIFY_OK = 0,
+    FHIP_VERIFY_HEADER = 1,       /* sync, reserved bit, blocking strategy, a code that disagrees with the params */
+    FHIP_VERIFY_CRC8 = 2,
+    FHIP_VERIFY_NUMBER = 3,       /* frame / sample number, block size or coverage */
+    FHIP_VERIFY_SYNTAX = 4,       /* reserved type or coding method, precision 16, negative shift, a partition
+                                     order the block cannot take, a read past the frame's end */
+    FHIP_VERIFY_SAMPLES = 5,      /* a field decodes to a value other than the input requires */
+    FHIP_VERIFY_PADDING = 6,
+    FHIP_VERIFY_CRC16 = 7,
+    FHIP_VERIFY_LENGTH = 8        /* the frame does not end at its frame_bytes, or runs past the stream */
+};
+
+typedef struct fhip_verify_rec {
+    int32_t status;               /* FHIP_VERIFY_* */
+    int32_t bit;                  /* bit offset within the frame of the first discrepancy; -1 when OK */
+    int32_t subframe;             /* the subframe (stream order) it lies in, or -1 */
+    int32_t sample;               /* SAMPLES: the sample index within the frame, else -1 */
+} fhip_verify_rec;
+
+typedef struct fhip_verify_out {
+    fhip_verify_rec *frames;      /* optional [nframes] */
+    int64_t         *summary;     /* [4]: frames checked, frames failed, first failing frame (-1: none), its status */
+} fhip_verify_out;
+
+/* All pointers DEVICE pointers; asynchronous on the handle's stream, no host synchronisation. */
+FHIP_API int fhip_verify_frames_dev(fhip_ctx *ctx, const fhip_verify_in *in, const fhip_verify_out *out);
+/* The same with HOST pointers: uploads, runs, synchronises.  FHIP_OK or FHIP_E_VERIFY; on
+ * FHIP_E_VERIFY fhip_last_error() names the first failing frame, its status, subframe, sample and bit. */
+FHIP_API int fhip_verify_frames(fhip_ctx *ctx, const fhip_verify_in *in, const fhip_verify_out *out);
+
+/*
+ * Verification of the handle's own output, off by default.  While on:
+ *   fhip_frames_packed_begin (and fhip_encode_frames_packed) and fhip_encode_blocks_vbs_packed run
+ *   the verifier on the device-resident stream and PCM before they return, and return FHIP_E_VERIFY
+ *   (copying nothing to `out`) when a frame fails; after a failed _begin, fhip_frames_packed_fetch
+ *   still delivers the bytes.  fhip_encode_blocks_vbs_dev sets bit 2 of totals[3] when a frame
+ *   fails (no host synchronisation).  The bytes written are the same with verification on or off.
+ */
+FHIP_API int fhip_set_verify(fhip_ctx *ctx, int on);
 
 /* ---- measurement ---------------------------------------------------- */
 
