@@ -56,8 +56,8 @@ struct SmpImg {
 
 struct FastLds {
     int32_t *smp;                        // SmpImg<C,T>: samples, HIST zeros in front
-    unsigned long long *sums;            // [511] heap order
-    int32_t *kpar;                       // [511]
+    unsigned long long *sums;            // [fast_heap_nodes] heap order
+    int32_t *kpar;                       // [fast_heap_nodes]
     double *coefd;                       // [32] coefficients of the candidate as fp64
     unsigned long long *wtot;            // [16] per-wave totals
     uint32_t *lvl_bits, *lvl_meth;       // [9]
@@ -83,21 +83,46 @@ __host__ __device__ inline int fast_window_words(int n, bool wide = false)
 }
 __host__ __device__ inline bool fast_wide_window(int mode, int bps) { return mode == 2 && bps > 16; }
 
-__host__ __device__ inline size_t fast_lds_layout(int n, size_t img_doubles, size_t off[11], bool wide = false)
+// Rice heap nodes a launch needs: 2^(pmax+1) (one spare keeps what follows 16-byte aligned).  Only the lean
+// instance (MODE 0: the workgroup-wide search of rice_search_fast, nodes 0 .. 2^(pmax+1)-2) is sized by its partition
+// orders; the others keep 512 -- the one-wave search puts thread sums and a heap behind them in l.sums, fixed_search5
+// five orders' nodes in l.sums and l.kpar.
+__host__ __device__ inline int fast_heap_nodes(int mode, int max_porder)
 {
+    if (mode != 0) return 512;
+    const int p = max_porder < 0 ? 0 : max_porder > 8 ? 8 : max_porder;
+    return 2 << p;
+}
+// overlay (MODE 0): the emit window shares the bytes of the sample image.  Nothing of that instance reads the image
+// after the Rice search but the residual output and the warm-up samples, which encode_pow2_body takes out first; the
+// window is then cleared after the search instead of under the shadow of the sample loads.  The heap then goes last:
+// its size is the launch's, and in front of the image it would make the image's address a run-time value (six VGPRs
+// spilled at 72).  At n = 4096 this and the 64-node heap of the headline (partition orders <= 5) take the LDS from
+// 31 840 to 18 272 bytes: room for seven workgroups per CU where there was room for five.
+__host__ __device__ inline size_t fast_lds_layout(int n, size_t img_doubles, size_t off[11], bool wide = false,
+                                                  int heap_nodes = 512, bool overlay = false)
+{
+    const size_t img_bytes = 4 * img_doubles, win_bytes = 4 * (size_t)fast_window_words(n, wide);
     size_t o = 0;
-    off[0] = o; o += 8 * 512;                                   // sums
+    if (!overlay) { off[0] = o; o += 8 * (size_t)heap_nodes; }  // sums
     off[1] = o; o += 8 * 48;                                    // coefd (zero-padded past 32)
     off[2] = o; o += 8 * 16;                                    // wtot
-    off[3] = o; o += 4 * img_doubles;                           // smp image (ints)
-    off[4] = o; o += 4 * 512;                                   // kpar
+    off[3] = o; o += overlay ? ((img_bytes > win_bytes ? img_bytes : win_bytes) + 15) & ~(size_t)15
+                             : img_bytes;                       // smp image (ints)
+    if (!overlay) { off[4] = o; o += 4 * (size_t)heap_nodes; }  // kpar
     off[5] = o; o += 4 * 12;                                    // lvl_bits
     off[6] = o; o += 4 * 12;                                    // lvl_meth
     off[7] = o; o += 4 * 32;                                    // coef
     off[8] = o; o += 4 * 16;                                    // misc
     off[9] = o; o += 4 * 32;                                    // trial
     o = (o + 15) & ~(size_t)15;
-    off[10] = o; o += 4 * fast_window_words(n, wide);           // bits
+    if (overlay) {
+        off[10] = off[3];                                       // bits over the image
+        off[0] = o; o += 8 * (size_t)heap_nodes;                // sums
+        off[4] = o; o += 4 * (size_t)heap_nodes;                // kpar
+        return o;
+    }
+    off[10] = o; o += win_bytes;                                // bits
     return o;
 }
 

@@ -1541,6 +1541,8 @@ template <int C, int T, int MODE>
 // packed FIR first spilled).  MODE 3 / MODE 1 at (16, 256) do spill a little at five (6 / 1
 // registers, 20 / 8 bytes of scratch: profiles/r03_kernel_resources.txt) and are still faster there
 // (configs[3] K3 342 -> 320 us, round 2).
+// Seven for that lean instance since round 5: 72 VGPRs without scratch (the emit's fields kept in their loop) and
+// 18 KB of LDS (the emit window over the sample image, the heap by the partition orders): 56.8 -> 51.4 us.
 // Four where five would spill (the order-search instance MODE 2; runs of 18) or where the LDS
 // of a 512- / 1024-thread workgroup stops at four waves per SIMD anyway.
 // Geometry for n = 4096, measured: (C,T) = (16,256) 94 us, (8,512) 137, (4,1024)
@@ -1557,8 +1559,10 @@ void encode_pow2_body(const fhip_params &P, const int n, const int32_t *__restri
                       const int narrow_ok, const int s)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    constexpr bool OVERLAY = MODE == 0;                 // the emit window over the sample image (fast_lds_layout)
     size_t off[12];
-    fast_lds_layout(n, SmpImg<C, T>::SIZE, off, fast_wide_window(MODE, P.bits_per_sample));
+    fast_lds_layout(C * T, SmpImg<C, T>::SIZE, off, fast_wide_window(MODE, P.bits_per_sample),    // n = C T: offsets known
+                    fast_heap_nodes(MODE, P.max_partition_order), OVERLAY);                      // at compile time
     FastCtx<C, T> e;
     e.l.sums = reinterpret_cast<unsigned long long *>(lds_raw + off[0]);
     e.l.coefd = reinterpret_cast<double *>(lds_raw + off[1]);
@@ -1672,9 +1676,9 @@ void encode_pow2_body(const fhip_params &P, const int n, const int32_t *__restri
     }
     // zeros in front: columns 0 .. COL0-1 of every row
     if (tid < SmpImg<C, T>::COL0 * C) l.smp[SmpImg<C, T>::at(tid / C, tid % C)] = 0;
-    // the first emit window is cleared here, under the shadow of the loads above
+    // the first emit window is cleared here, under the shadow of the loads above (OVERLAY: after the search)
     const int wwords = fast_window_words(n, fast_wide_window(MODE, P.bits_per_sample));
-    if (bits_out) for (int q = tid; q < wwords / 4; q += T) reinterpret_cast<uint4 *>(l.bits)[q] = make_uint4(0, 0, 0, 0);
+    if (!OVERLAY && bits_out) for (int q = tid; q < wwords / 4; q += T) reinterpret_cast<uint4 *>(l.bits)[q] = make_uint4(0, 0, 0, 0);
     if (tid < 16) l.coefd[32 + tid] = 0.0;
     if (pre_row && tid < FHIP_MAX_ORDER) {
         l.coef[tid] = fcoef_n;
@@ -1694,6 +1698,9 @@ void encode_pow2_body(const fhip_params &P, const int n, const int32_t *__restri
 #pragma unroll
     for (int w = 0; w < T / WAVE; w++) any_differs |= l.misc[w];
     const bool constant = (__builtin_amdgcn_readfirstlane(any_differs) == 0);
+    // OVERLAY: the warm-up samples the record carries leave the image before the emit window covers it
+    // (l.trial is idle where there is one row: no order search)
+    if (OVERLAY && tid < FHIP_MAX_ORDER) l.trial[tid] = (uint32_t)l.smp[SmpImg<C, T>::at(tid / C + SmpImg<C, T>::COL0, tid % C)];
     STAMP(1);
 
     int32_t r[C];                        // residuals of the current candidate
@@ -1946,6 +1953,12 @@ void encode_pow2_body(const fhip_params &P, const int n, const int32_t *__restri
         const bool part_head = (part > 0) && ((tid & ((1 << tpp) - 1)) == 0);
         // warm-up samples at the front of this thread's run (first threads only)
         const int nwarm = min(max(order - e.i0, 0), C);
+        if (OVERLAY && bits_out) {
+            // the window over the sample image: its last readers were the FIR (behind the search's barriers) and the
+            // residual output above (behind this one); the barrier in front of the emit orders the clear
+            if (res_out) __syncthreads();
+            for (int q = tid; q < wwords / 4; q += T) reinterpret_cast<uint4 *>(l.bits)[q] = make_uint4(0, 0, 0, 0);
+        }
         // the emit-side fold (bitio.h:128) differs from rice.c's for |x| >= 2^30, i.e. for
         // folded values from 2^31 (any sample width: it is the residual that counts)
         uint32_t umax = umax_run;
@@ -2013,6 +2026,12 @@ void encode_pow2_body(const fhip_params &P, const int n, const int32_t *__restri
                         __syncthreads();
                         for (int q = tid; q < (nw + 3) / 4; q += T) reinterpret_cast<uint4 *>(l.bits)[q] = make_uint4(0, 0, 0, 0);
                         __syncthreads();
+                    }
+                    if constexpr (MODE == 0) {
+                        // the codeword fields below are invariant in this loop; hoisted out of it they are 32 more
+                        // live registers (34 spilled at 72): keep them in it
+#pragma unroll
+                        for (int o = 0; o < C; o++) asm volatile("" : "+v"(u[o]));
                     }
                     const long long rel = start - (long long)wlo * 32;
                     // The thread's codewords form one contiguous bit run.  It is
@@ -2129,7 +2148,8 @@ void encode_pow2_body(const fhip_params &P, const int n, const int32_t *__restri
     if (tid < FHIP_MAX_ORDER) {
         out->coefs[tid] = (type == FHIP_SUB_LPC && tid < order) ? l.coef[tid] : 0;
         const int nw = (type == FHIP_SUB_CONSTANT) ? 1 : order;
-        out->warmup[tid] = (tid < nw) ? l.smp[SmpImg<C, T>::at(tid / C + SmpImg<C, T>::COL0, tid % C)] : 0;
+        out->warmup[tid] = (tid >= nw) ? 0 : OVERLAY ? (int32_t)l.trial[tid]
+                                                     : l.smp[SmpImg<C, T>::at(tid / C + SmpImg<C, T>::COL0, tid % C)];
     }
     {
         const int np = has_rice ? (1 << porder) : 0;
@@ -2139,7 +2159,7 @@ void encode_pow2_body(const fhip_params &P, const int n, const int32_t *__restri
 }
 
 template <int C, int T, int MODE>
-__global__ __launch_bounds__(T, (MODE == 2 || C >= 18 || (C >= 14 && T > 256)) ? 4 : 5)
+__global__ __launch_bounds__(T, (MODE == 0 && C == 16 && T == 256) ? 7 : (MODE == 2 || C >= 18 || (C >= 14 && T > 256)) ? 4 : 5)
 void k_encode_pow2(fhip_params P, int n, int nsub, const int32_t *__restrict__ smp_all,
                    const int32_t *__restrict__ coefs_all, const int32_t *__restrict__ shift_all,
                    const int32_t *__restrict__ opt_all, const int32_t *__restrict__ fin_all,
@@ -2286,7 +2306,8 @@ hipError_t launch_encode_bins(hipStream_t st, const fhip_params &p, const MultiB
 #define SZ_(CC) if (fc == CC) img = (size_t)SmpImg<CC, 256>::SIZE
         SZ_(2); SZ_(4); SZ_(8); SZ_(10); SZ_(12); SZ_(14); SZ_(16);
 #undef SZ_
-        const size_t l = fast_lds_layout(mb.n[k], img, off, fast_wide_window(mode, p.bits_per_sample));
+        const size_t l = fast_lds_layout(mb.n[k], img, off, fast_wide_window(mode, p.bits_per_sample),
+                                         fast_heap_nodes(mode, p.max_partition_order), mode == 0);
         lds = l > lds ? l : lds;
     }
 #define LAUNCH_EB(MM)                                                                        \
@@ -2321,7 +2342,8 @@ hipError_t launch_encode(hipStream_t st, const fhip_params &p, const int32_t *sm
 #define LAUNCH_FAST2(CC, TT, MM)                                                             \
     do {                                                                                     \
         lds = fast_lds_layout(n, (size_t)SmpImg<CC, TT>::SIZE, off,                          \
-                              fast_wide_window(MM, p.bits_per_sample));                      \
+                              fast_wide_window(MM, p.bits_per_sample),                       \
+                              fast_heap_nodes(MM, p.max_partition_order), MM == 0);          \
         hipError_t er = hipFuncSetAttribute(                                                 \
             reinterpret_cast<const void *>(&k_encode_pow2<CC, TT, MM>),                      \
             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
