@@ -194,6 +194,7 @@ def load_library() -> C.CDLL:
         "fhip_verify_frames": (i, [vp, C.POINTER(VerifyIn), C.POINTER(VerifyOut)]),
         "fhip_get_kernel_times": (i, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double),
                                       C.POINTER(i), i, i]),
+        "fhip_last_launches": (i, [vp, C.POINTER(C.c_char_p), i]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -212,7 +213,7 @@ ABI_SYMBOLS = (
     "fhip_frames_packed_begin", "fhip_frames_packed_fetch", "fhip_encode_blocks_vbs_packed",
     "fhip_encode_blocks_vbs_dev", "fhip_order_search_bits",
     "fhip_host_alloc", "fhip_host_free", "fhip_host_register", "fhip_host_unregister", "fhip_frames_packed_upload", "fhip_frames_packed_fetch_async", "fhip_frames_packed_fetch_wait",
-    "fhip_set_verify", "fhip_verify_frames_dev", "fhip_verify_frames",
+    "fhip_set_verify", "fhip_verify_frames_dev", "fhip_verify_frames", "fhip_last_launches",
 )
 
 
@@ -317,6 +318,16 @@ class Encoder:
         cnt = (C.c_int * 8)()
         k = self.lib.fhip_get_kernel_times(self._h, names, ms, cnt, 8, int(reset))
         return {names[i].decode(): (ms[i], cnt[i]) for i in range(k)}
+
+    def last_launches(self) -> list:
+        """The kernel instances the handle's most recent encode call (or prepare_ahead) queued, in
+        order: "k_encode_pow2<16,256,0> narrow", ... (fhip_last_launches; host-side, no device work)."""
+        k = self.lib.fhip_last_launches(self._h, None, 0)
+        if k < 0:
+            self._check(k, "fhip_last_launches")
+        names = (C.c_char_p * max(k, 1))()
+        k = self.lib.fhip_last_launches(self._h, names, k)
+        return [names[i].decode() for i in range(k)]
 
     # -- hot path ---------------------------------------------------------
     def frame_stride(self, block_size: int) -> int:

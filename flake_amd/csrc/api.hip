@@ -3,6 +3,7 @@
 // point maps HIP failures to FHIP_E_HIP and never throws.
 #include <hip/hip_runtime.h>
 
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -98,8 +99,27 @@ struct fhip_ctx {
     int32_t *d_vpcm = nullptr;
     size_t d_vpcm_vals = 0;
 
+    std::vector<std::string> launches;        // fhip_last_launches: what the most recent call queued
+
     std::string err;
 };
+
+namespace fhip {
+namespace {
+thread_local std::vector<std::string> *launch_sink = nullptr;
+}
+
+void note_launch(const char *fmt, ...)
+{
+    if (!launch_sink) return;
+    char buf[160];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    launch_sink->emplace_back(buf);
+}
+}  // namespace fhip
 
 namespace {
 
@@ -122,6 +142,17 @@ int fail(fhip_ctx *c, int code, const char *what)
     if (c) c->err = what;
     return code;
 }
+
+// The launches of one encode call go to its handle's list (fhip_last_launches), which the call starts afresh.
+struct LaunchScope {
+    std::vector<std::string> *prev;
+    explicit LaunchScope(fhip_ctx *c) : prev(fhip::launch_sink)
+    {
+        c->launches.clear();
+        fhip::launch_sink = &c->launches;
+    }
+    ~LaunchScope() { fhip::launch_sink = prev; }
+};
 
 #define HIP_TRY(ctx, call)                                   \
     do {                                                     \
@@ -612,10 +643,19 @@ int fhip_get_kernel_times(fhip_ctx *c, const char **names, double *ms, int *laun
     return k;
 }
 
+int fhip_last_launches(fhip_ctx *c, const char **names, int cap)
+{
+    if (!c) return FHIP_E_INVALID;
+    const int k = (int)c->launches.size();
+    for (int i = 0; i < k && i < cap && names; i++) names[i] = c->launches[i].c_str();
+    return k;
+}
+
 int fhip_encode_subframes_dev(fhip_ctx *c, const fhip_batch *b)
 {
     int rc = check_batch(c, b);
     if (rc != FHIP_OK) return rc;
+    LaunchScope ls(c);
     HIP_TRY(c, hipSetDevice(c->device));
     return run_pipeline(c, b->pcm, b->nframes, b->block_size, b->info, b->residual,
                         b->rice_bits, b->rice_slot_bytes, b->samples, b->autoc,
@@ -630,6 +670,7 @@ int fhip_prepare_ahead(fhip_ctx *c, const fhip_batch *b)
         return fail(c, FHIP_E_INVALID, "nframes exceeds the handle's max_frames");
     if (b->block_size < 1 || b->block_size > c->p.block_size)
         return fail(c, FHIP_E_INVALID, "block_size out of range (encode.c:987)");
+    LaunchScope ls(c);
     if (b->nframes == 0) return FHIP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     const fhip_params &p = c->p;
@@ -704,6 +745,7 @@ int fhip_encode_subframes(fhip_ctx *c, const fhip_batch *b)
 {
     int rc = check_batch(c, b, true);
     if (rc != FHIP_OK) return rc;
+    LaunchScope ls(c);
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t nch = (size_t)c->p.channels, n = (size_t)b->block_size;
     const size_t nsub = (size_t)b->nframes * nch;
@@ -787,6 +829,7 @@ int fhip_frames_packed_begin(fhip_ctx *c, const fhip_batch *b, int64_t *total_by
         return fail(c, FHIP_E_INVALID, "block_size out of range (encode.c:987)");
     *total_bytes = 0;
     c->packed_ready = 0;
+    LaunchScope ls(c);
     if (b->nframes == 0) return FHIP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t nch = (size_t)c->p.channels, n = (size_t)b->block_size;
@@ -1357,6 +1400,7 @@ int fhip_encode_blocks_vbs_dev(fhip_ctx *c, const int32_t *pcm, int nblocks, int
     if (rc != FHIP_OK) return rc;
     if (!out || !out->packed || !out->totals || out->packed_cap < 0)
         return fail(c, FHIP_E_INVALID, "null output argument");
+    LaunchScope ls(c);
     HIP_TRY(c, hipSetDevice(c->device));
     if (nblocks == 0) {
         HIP_TRY(c, hipMemsetAsync(out->totals, 0, 4 * sizeof(int64_t), c->stream));
@@ -1385,6 +1429,7 @@ int fhip_encode_blocks_vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, 
     int rc = vbs_check(c, pcm, nblocks, block_size);
     if (rc != FHIP_OK) return rc;
     if (!out || !out_bytes || !block_bytes) return fail(c, FHIP_E_INVALID, "null argument");
+    LaunchScope ls(c);
     const fhip_params &p = c->p;
     *out_bytes = 0;
     c->packed_ready = 0;                     // d_packed is about to be rewritten (and may move)

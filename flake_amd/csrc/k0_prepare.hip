@@ -722,7 +722,7 @@ hipError_t launch_prepare(hipStream_t st, const fhip_params &p, const int32_t *p
         const int est = p.stereo_method == 1 ? 1 : 0;
         const int quads = n >> 2;
         const int nar = (allow_narrow && !decide_only) ? 1 : 0;
-#define LAUNCH_PS(M_, W_, A_) hipLaunchKernelGGL((k_prepare_stereo<M_, W_, A_>), dim3((nframes + 4 / W_ - 1) / (4 / W_)), dim3(NT), 0, st, pcm, smp, info, n, p.bits_per_sample, est, nar, nframes, frame_src, dev_frames)
+#define LAUNCH_PS(M_, W_, A_) do { note_launch("k_prepare_stereo<%d,%d,%s>%s", M_, W_, tf(A_), nar ? " narrow" : ""); hipLaunchKernelGGL((k_prepare_stereo<M_, W_, A_>), dim3((nframes + 4 / W_ - 1) / (4 / W_)), dim3(NT), 0, st, pcm, smp, info, n, p.bits_per_sample, est, nar, nframes, frame_src, dev_frames); } while (0)
         if (decide_only) {
             if (quads <= NT) LAUNCH_PS(1, 4, false); else if (quads <= 2 * NT) LAUNCH_PS(2, 4, false); else LAUNCH_PS(4, 4, false);
         } else {
@@ -738,7 +738,7 @@ hipError_t launch_prepare(hipStream_t st, const fhip_params &p, const int32_t *p
         static const bool two_pass = getenv("FHIP_K0_MULTI_TWO_PASS") != nullptr;      // measurements only
         if (!two_pass && (n & 3) == 0 && n <= 8192 && n >= 256) {
             // the frame in registers: one read of the PCM
-#define LAUNCH_MR(C_, M_) hipLaunchKernelGGL((k_prepare_multi_reg<C_, M_>), dim3(nframes), dim3(RT), 0, st, pcm, smp, info, n, p.bits_per_sample, frame_src, dev_frames)
+#define LAUNCH_MR(C_, M_) do { note_launch("k_prepare_multi_reg<%d,%d>", C_, M_); hipLaunchKernelGGL((k_prepare_multi_reg<C_, M_>), dim3(nframes), dim3(RT), 0, st, pcm, smp, info, n, p.bits_per_sample, frame_src, dev_frames); } while (0)
 #define LAUNCH_MRC(C_) do { if (n <= 4 * RT) LAUNCH_MR(C_, 1); else LAUNCH_MR(C_, 2); } while (0)
             switch (nch) {
             case 1: LAUNCH_MRC(1); break;
@@ -753,6 +753,7 @@ hipError_t launch_prepare(hipStream_t st, const fhip_params &p, const int32_t *p
 #undef LAUNCH_MR
             return hipGetLastError();
         }
+        note_launch("k_prepare_multi");
         hipLaunchKernelGGL(k_prepare_multi, dim3(nframes), dim3(NT), 0, st, pcm, smp, info, n, nch,
                            p.bits_per_sample, frame_src, dev_frames);
         return hipGetLastError();
@@ -762,6 +763,7 @@ hipError_t launch_prepare(hipStream_t st, const fhip_params &p, const int32_t *p
     if (blocks == 0) return hipSuccess;
     if (lds > 150 * 1024) {
         // frames of more than ~19 k sample-frames: streamed from global memory
+        note_launch("k_prepare<false>");
         hipLaunchKernelGGL(k_prepare<false>, dim3(blocks), dim3(NT), 0, st, pcm, smp, info, n, nch,
                            p.bits_per_sample, p.stereo_method == 1 ? 1 : 0, frame_src, dev_frames);
         return hipGetLastError();
@@ -769,6 +771,7 @@ hipError_t launch_prepare(hipStream_t st, const fhip_params &p, const int32_t *p
     hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_prepare<true>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (er != hipSuccess) return er;
+    note_launch("k_prepare<true>");
     hipLaunchKernelGGL(k_prepare<true>, dim3(blocks), dim3(NT), lds, st, pcm, smp, info, n, nch,
                        p.bits_per_sample, p.stereo_method == 1 ? 1 : 0, frame_src, dev_frames);
     return hipGetLastError();
@@ -800,6 +803,9 @@ hipError_t launch_prepare_bins(hipStream_t st, const fhip_params &p, const int32
     if (blocks == 0) return hipSuccess;
     int nmax = 0;
     for (int k = 0; k < mb.nbins; k++) nmax = mb.n[k] > nmax ? mb.n[k] : nmax;
+    bool nar = false;
+    for (int k = 0; k < mb.nbins; k++) nar = nar || mb.narrow[k];
+    note_launch("k_prepare_stereo_bins<%d>%s", (nmax >> 2) <= 4 * NT ? 4 : 8, nar ? " narrow" : "");
     if ((nmax >> 2) <= 4 * NT)
         hipLaunchKernelGGL(k_prepare_stereo_bins<4>, dim3(blocks), dim3(NT), 0, st, pcm, smp, info, p.bits_per_sample,
                            p.stereo_method == 1 ? 1 : 0, frame_src, mb);

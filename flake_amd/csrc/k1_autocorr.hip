@@ -1053,11 +1053,14 @@ hipError_t launch_autocorr_bins(hipStream_t st, const MultiBin &mb, const int32_
     }
     const size_t lds = sizeof(double) * (size_t)WT_NBUF * WT_BUF +
                        (lpcmo ? sizeof(double) * (size_t)WT_SUB * FHIP_MAX_LAGS : 0);
-#define LAUNCH_WTB(N_, L_)                                                                   \
+    bool any_narrow = false;
+    for (int k = 0; k < mb.nbins; k++) any_narrow = any_narrow || mb.narrow[k];
+#define LAUNCH_WTB(N_, L_)                                                                 \
     do {                                                                                     \
         hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_autocorr_wt<N_, false, L_>), \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         if (er != hipSuccess) return er;                                                     \
+        note_launch("k_autocorr_wt<%d,false,%d> split=1%s%s", N_, L_, L_ ? " tail" : "", any_narrow ? " narrow" : ""); \
         hipLaunchKernelGGL((k_autocorr_wt<N_, false, L_>), dim3(blocks), dim3(8 * WAVE), lds, st, smp, \
                            autoc, 0, 0, max_order, gr, 0.0, (const int32_t *)nullptr, (int32_t *)nullptr, info, la, 0, \
                            (const int32_t *)nullptr, mb, wt_groups{}, 1);                    \
@@ -1154,6 +1157,8 @@ hipError_t launch_autocorr(hipStream_t st, const int32_t *smp, int nsub, int n,
         hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_autocorr_wt<N_, F_, L_>), \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_all); \
         if (er != hipSuccess) return er;                                                     \
+        note_launch("k_autocorr_wt<%d,%s,%d> split=%d%s%s%s", N_, tf(F_), L_, split, L_ ? " tail" : "", \
+                    F_ ? " fused" : "", narrow_ok ? " narrow" : "");                         \
         hipLaunchKernelGGL((k_autocorr_wt<N_, F_, L_>), dim3(blocks), dim3(8 * WAVE), lds_all, st, smp, \
                            autoc, nsub, n, max_order, gr, c, pcm_fused, smp_out, info, la, narrow_ok ? 1 : 0, dev_sub, MultiBin{}, gr1, split); \
     } while (0)
@@ -1191,6 +1196,7 @@ hipError_t launch_autocorr(hipStream_t st, const int32_t *smp, int nsub, int n,
     if (use_ps) {
         const int per_block = Gp * AC_WAVES;
         const int blocks = (nsub + per_block - 1) / per_block;
+        note_launch("k_autocorr_ps");
         hipLaunchKernelGGL(k_autocorr_ps, dim3(blocks), dim3(AC_WAVES * WAVE), 0, st, smp, autoc,
                            nsub, n, max_order, Gp, lps, ge, c, dev_sub);
         return hipGetLastError();
@@ -1201,6 +1207,7 @@ hipError_t launch_autocorr(hipStream_t st, const int32_t *smp, int nsub, int n,
     if (const char *dbg = getenv("FHIP_AC_G")) { int v = atoi(dbg); if (v >= 1 && v <= AC_GMAX && v * nl2 <= WAVE) G = v; }
     const int per_block = G * AC_WAVES;
     const int blocks = (nsub + per_block - 1) / per_block;
+    note_launch("k_autocorr");
     hipLaunchKernelGGL(k_autocorr, dim3(blocks), dim3(AC_WAVES * WAVE), 0, st, smp, autoc,
                        nsub, n, max_order, G, nl2, c, dev_sub);
     return hipGetLastError();

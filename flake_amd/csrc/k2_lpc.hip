@@ -342,13 +342,15 @@ static hipError_t launch_lpc_any(hipStream_t st, const double *autoc, int nsub, 
 {
     if (nsub == 0) return hipSuccess;
     const int blocks = (nsub + LPC_NT - 1) / LPC_NT;
+    const bool rows = max_order > 12 && omethod >= 2 && getenv("FHIP_K2_ONE_LANE") == nullptr;
+    note_launch("%s", max_order <= 8 ? "k_lpc_reg<8>" : max_order <= 12 ? "k_lpc_reg<12>" : rows ? "k_lpc_rows" : "k_lpc");
     if (max_order <= 8)
         hipLaunchKernelGGL(k_lpc_reg<8>, dim3(blocks), dim3(LPC_NT), 0, st, autoc, nsub, max_order,
                            precision, omethod, coefs, shift, opt_order, fin, dev_sub, mb);
     else if (max_order <= 12)
         hipLaunchKernelGGL(k_lpc_reg<12>, dim3(blocks), dim3(LPC_NT), 0, st, autoc, nsub, max_order,
                            precision, omethod, coefs, shift, opt_order, fin, dev_sub, mb);
-    else if (omethod >= 2 && getenv("FHIP_K2_ONE_LANE") == nullptr) {
+    else if (rows) {
         // every row wanted (lpc.c:249-254): Levinson in registers, rows quantised side by side
         const size_t lds = (size_t)LR_SUB * LR_STRIDE * sizeof(double);
         hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lpc_rows),

@@ -2298,6 +2298,8 @@ hipError_t launch_encode_bins(hipStream_t st, const fhip_params &p, const MultiB
     if (grid == 0) return hipSuccess;
     if (!prep || prep == info) return hipErrorInvalidValue;
     const int mode = (p.max_prediction_order > 8) ? 3 : 0;           // launch_encode's rule for a single row
+    bool any_narrow = false;
+    for (int k = 0; k < mb.nbins; k++) any_narrow = any_narrow || mb.narrow[k];
     size_t lds = 0;
     for (int k = 0; k < mb.nbins; k++) {
         int fc = 0, ft = 0;
@@ -2315,6 +2317,7 @@ hipError_t launch_encode_bins(hipStream_t st, const fhip_params &p, const MultiB
         hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_encode_bins<MM>), \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         if (er != hipSuccess) return er;                                                     \
+        note_launch("k_encode_bins<%d>%s", MM, any_narrow ? " narrow" : "");                 \
         hipLaunchKernelGGL((k_encode_bins<MM>), dim3(grid), dim3(256), lds, st, p, mb, smp, coefs, shift, opt_order, \
                            fin, info, prep, bits);                                           \
         return hipGetLastError();                                                            \
@@ -2348,6 +2351,7 @@ hipError_t launch_encode(hipStream_t st, const fhip_params &p, const int32_t *sm
             reinterpret_cast<const void *>(&k_encode_pow2<CC, TT, MM>),                      \
             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
         if (er != hipSuccess) return er;                                                     \
+        note_launch("k_encode_pow2<%d,%d,%d>%s", CC, TT, MM, narrow_ok ? " narrow" : "");    \
         hipLaunchKernelGGL((k_encode_pow2<CC, TT, MM>), dim3(nsub), dim3(TT), lds, st, p, n, \
                            nsub, smp, coefs, shift, opt_order, fin, info, prep, residual,    \
                            bits, (long long)slot_bytes, narrow_ok ? 1 : 0, dev_sub);         \
@@ -2404,6 +2408,7 @@ hipError_t launch_encode(hipStream_t st, const fhip_params &p, const int32_t *sm
     const size_t lds = encode_lds_bytes(n);
     if (lds == 0) return hipErrorInvalidValue;
     if (n > FHIP_MAX_RESIDENT_BLOCK) {
+        note_launch("k_encode_big");
         hipLaunchKernelGGL(k_encode_big, dim3(nsub), dim3(NT), lds, st, p, n, smp, coefs, shift,
                            opt_order, info, prep, residual, bits, (long long)slot_bytes, raw_order,
                            raw_lpc, dev_sub);
@@ -2416,6 +2421,7 @@ hipError_t launch_encode(hipStream_t st, const fhip_params &p, const int32_t *sm
                                             hipFuncAttributeMaxDynamicSharedMemorySize,      \
                                             (int)lds);                                       \
         if (er != hipSuccess) return er;                                                     \
+        note_launch("k_encode<%d>", CC);                                                     \
         hipLaunchKernelGGL(k_encode<CC>, dim3(nsub), dim3(NT), lds, st, p, n, smp, coefs,    \
                            shift, opt_order, info, prep, residual, bits,                     \
                            (long long)slot_bytes,                                            \

@@ -1655,6 +1655,7 @@ hipError_t launch_order_search(hipStream_t st, const fhip_params &p, const int32
         hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_order_search<CC, TT, G, true>), \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         if (er != hipSuccess) return er;                                                     \
+        note_launch("k_order_search<%d,%d,%d,true>%s", CC, TT, G, narrow_ok ? " narrow" : ""); \
         hipLaunchKernelGGL((k_order_search<CC, TT, G, true>), dim3(nsub), dim3(TT), lds, st, p, n, smp, coefs, \
                            shift, opt_order, fin, prep, narrow_ok ? 1 : 0, dev_sub, table_out, lg0); \
         return hipGetLastError();                                                            \
@@ -1679,6 +1680,7 @@ hipError_t launch_order_search(hipStream_t st, const fhip_params &p, const int32
             reinterpret_cast<const void *>(&k_order_search<CC, TT, G>),                      \
             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
         if (er != hipSuccess) return er;                                                     \
+        note_launch("k_order_search<%d,%d,%d,false>%s", CC, TT, G, narrow_ok ? " narrow" : ""); \
         hipLaunchKernelGGL((k_order_search<CC, TT, G>), dim3(nsub), dim3(TT), lds, st, p, n, \
                            smp, coefs, shift, opt_order, fin, prep, narrow_ok ? 1 : 0, dev_sub, table_out, lg0); \
     } while (0)
@@ -1748,11 +1750,14 @@ hipError_t launch_order_search_bins(hipStream_t st, const fhip_params &p, const 
         lds = l > lds ? l : lds;
     }
     const LogPlan0 lg0 = (p.order_method == 6) ? log_plan_round0(p.min_prediction_order, p.max_prediction_order, G) : LogPlan0{0u, 0, 0};
+    bool any_narrow = false;
+    for (int k = 0; k < mb.nbins; k++) any_narrow = any_narrow || mb.narrow[k];
 #define LAUNCH_BINS(TT, CS)                                                                  \
     do {                                                                                     \
         hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_order_search_bins<TT, G, CS>), \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         if (er != hipSuccess) return er;                                                     \
+        note_launch("k_order_search_bins<%d,%d,%d>%s", TT, G, CS, any_narrow ? " narrow" : ""); \
         hipLaunchKernelGGL((k_order_search_bins<TT, G, CS>), dim3(grid), dim3(TT), lds, st, p, mb, smp, coefs, \
                            shift, opt_order, fin, prep, lg0);                                \
         return hipGetLastError();                                                            \

@@ -616,6 +616,7 @@ hipError_t launch_vbs_split(hipStream_t st, const int32_t *pcm, int nblocks, int
                             int nch, int32_t *nframes_out, int32_t *sizes_out)
 {
     if (nblocks == 0) return hipSuccess;
+    note_launch("k_vbs_split");
     hipLaunchKernelGGL(k_vbs_split, dim3(nblocks), dim3(NT), 0, st, pcm, nblocks, block_size, nch,
                        nframes_out, sizes_out);
     return hipGetLastError();
@@ -644,6 +645,7 @@ hipError_t launch_assemble(hipStream_t st, const fhip_params &p, const int32_t *
     const int bps = p.bits_per_sample;
     const int vsize = (p.channels == 2) ? 16 + ((n * (bps + bps + 1) + 7) >> 3)
                                         : 16 + ((n * p.channels * bps + 7) >> 3);
+    note_launch("k_assemble");
     hipLaunchKernelGGL(k_assemble, dim3(nframes), dim3(AT), 0, st, p, n, pcm, info, rice,
                        (long long)slot_bytes, frames, (long long)frame_stride, frame_bytes,
                        number_base, number_step, numbers, sr0, sr1, bpsc, vsize, frame_src, dev_frames, MultiBin{});
@@ -669,6 +671,7 @@ hipError_t launch_assemble_bins(hipStream_t st, const fhip_params &p, const Mult
         else if (sr < 65535) { sr0 = 13; sr1 = sr; }
     }
     for (int i = 1; i < 8; i++) if (p.bits_per_sample == bd_table[i]) { bpsc = i; break; }
+    note_launch("k_assemble bins");
     hipLaunchKernelGGL(k_assemble, dim3(slots), dim3(AT), 0, st, p, 0, pcm, info, rice, 0ll, frames, 0ll,
                        frame_bytes, 0u, 0u, numbers, sr0, sr1, bpsc, 0, frame_src, (const int32_t *)nullptr, mb);
     return hipGetLastError();
@@ -971,6 +974,7 @@ hipError_t launch_vbs_plan(hipStream_t st, const int32_t *nfr, const int32_t *si
                            uint32_t *numbers, int32_t *first)
 {
     if (nblocks == 0) return hipSuccess;
+    note_launch("k_vbs_plan");
     hipLaunchKernelGGL(k_vbs_plan, dim3(1), dim3(PLAN_NT), 0, st, nfr, sizes, nblocks, block_size, nch,
                        first_number, bins, cnt, order, frame_src, src_off, numbers, first);
     return hipGetLastError();
@@ -982,8 +986,10 @@ hipError_t launch_pack_frames_perm(hipStream_t st, const uint8_t *frames, const 
                                    long long cap, int32_t *stream_bytes, long long *totals)
 {
     if (max_frames == 0) return hipSuccess;
+    note_launch("k_frame_offsets_perm");
     hipLaunchKernelGGL(k_frame_offsets_perm, dim3(1), dim3(SCAN_NT), 0, st, frame_bytes, order, dev_frames,
                        offsets, cap, totals);
+    note_launch("k_pack_frames_perm");
     hipLaunchKernelGGL(k_pack_frames_perm, dim3(max_frames), dim3(NT), 0, st, frames, src_off, frame_bytes,
                        order, offsets, packed, dev_frames, cap, stream_bytes, totals);
     return hipGetLastError();
@@ -993,6 +999,7 @@ hipError_t launch_vbs_block_bytes(hipStream_t st, const int32_t *first, const lo
                                   int32_t *block_bytes, int32_t *block_frames)
 {
     if (nblocks == 0 || (!block_bytes && !block_frames)) return hipSuccess;
+    note_launch("k_vbs_block_bytes");
     hipLaunchKernelGGL(k_vbs_block_bytes, dim3((nblocks + NT - 1) / NT), dim3(NT), 0, st, first, offsets,
                        nblocks, block_bytes, block_frames);
     return hipGetLastError();
@@ -1003,7 +1010,9 @@ hipError_t launch_pack_frames(hipStream_t st, const uint8_t *frames, int64_t fra
                               uint8_t *packed)
 {
     if (nframes == 0) return hipSuccess;
+    note_launch("k_frame_offsets");
     hipLaunchKernelGGL(k_frame_offsets, dim3(1), dim3(SCAN_NT), 0, st, frame_bytes, nframes, offsets);
+    note_launch("k_pack_frames");
     hipLaunchKernelGGL(k_pack_frames, dim3(nframes), dim3(NT), 0, st, frames, (long long)frame_stride,
                        frame_bytes, offsets, packed);
     return hipGetLastError();

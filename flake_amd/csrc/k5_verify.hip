@@ -768,8 +768,13 @@ __global__ void k_verify_final(VerifyArgs a)
 
 hipError_t launch_verify(hipStream_t st, const VerifyArgs &a)
 {
+    note_launch("k_verify_frames");
     hipLaunchKernelGGL(k_verify_frames, dim3(1), dim3(HDR_T), 0, st, a);
-    if (a.nframes > 0) hipLaunchKernelGGL(k_verify, dim3(a.nframes), dim3(VT), 0, st, a);
+    if (a.nframes > 0) {
+        note_launch("k_verify");
+        hipLaunchKernelGGL(k_verify, dim3(a.nframes), dim3(VT), 0, st, a);
+    }
+    note_launch("k_verify_final");
     hipLaunchKernelGGL(k_verify_final, dim3(1), dim3(1), 0, st, a);
     return hipGetLastError();
 }

@@ -9,6 +9,12 @@
 
 namespace fhip {
 
+// fhip_last_launches: every launcher notes the kernel instance it queues (template spelling, then
+// the runtime switches) into the calling thread's sink, which api.hip sets for the length of an
+// encode call.  Host-side only; a no-op while no sink is set.
+void note_launch(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+inline const char *tf(bool b) { return b ? "true" : "false"; }
+
 // Blocks up to this size keep a subframe's samples in LDS / registers (K3's k_encode and
 // k_encode_pow2); longer ones, up to FHIP_MAX_BLOCK, stream them (k_encode_big).
 constexpr int FHIP_MAX_RESIDENT_BLOCK = 16384;

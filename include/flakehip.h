@@ -408,6 +408,15 @@ FHIP_API int fhip_set_profiling(fhip_ctx *ctx, int on);
  * since the last reset; returns the number of kernels (<= cap). */
 FHIP_API int fhip_get_kernel_times(fhip_ctx *ctx, const char **names, double *ms, int *launches,
                           int cap, int reset);
+/* The kernel instances the handle's most recent call queued, in launch order, one per launch,
+ * spelled as templates (e.g. "k_encode_pow2<16,256,0>"), followed by the switches that change the
+ * path without being template arguments, separated by spaces: "split=1" / "split=2" (K1's lags over
+ * one or two workgroups per tile), "tail" (K2 runs inside K1), "fused" (K1 applies K0's decisions),
+ * "narrow" (16-bit sample rows).  The calls that start a new list are the encode entries
+ * (fhip_encode_subframes*, fhip_frames_packed_begin / fhip_encode_frames_packed, the VBS entries)
+ * and fhip_prepare_ahead.  A host-side record: it adds no device work.  names[0 .. cap) receive
+ * strings owned by the handle, valid until its next such call; returns the number of launches. */
+FHIP_API int fhip_last_launches(fhip_ctx *ctx, const char **names, int cap);
 
 #ifdef __cplusplus
 }

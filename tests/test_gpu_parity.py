@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 import flake_amd
+import oracle_chunks as OC
 from parity import assert_bits_equal, assert_info_equal, assert_residual_equal
 
 pytestmark = pytest.mark.gpu
@@ -207,10 +208,11 @@ def test_slot_too_small_reports_minus_one(oracle):
     assert not out["rice_bits"].any()
 
 
-def test_full_size_batch_properties():
+def test_full_size_batch_properties(oracle):
     """BASELINE configs[1] at full size (4096 frames): properties that need no oracle --
     the residual reproduces the samples through the FLAC decoder recurrence, and the
-    residual section length equals the sum of its codeword lengths."""
+    residual section length equals the sum of its codeword lengths -- and the whole batch
+    against the oracle (int32 rows: want_samples; test_gpu_bench_sizes.py runs the 16-bit ones)."""
     p = flake_amd.level_params(5, order_method=flake_amd.OM_MAX)
     n, nfr = 4096, 4096
     pcm = flake_amd.synth_pcm(nfr, n, 2, 16)
@@ -236,6 +238,8 @@ def test_full_size_batch_properties():
         assert bits == info["rice_nbits"][s], s
     # linearity of the bookkeeping: ch_mode consistent within a frame, obits rule
     assert (info["ch_mode"][0::2] == info["ch_mode"][1::2]).all()
+    OC.compare_batch(oracle, p, pcm, n, info, got["rice_bits"], got["slot_bytes"], residual=got["residual"],
+                     what="configs[1] 4096 frames")
 
 
 def test_vbs_split_matches_reference_rule(oracle):
@@ -300,7 +304,8 @@ def _check_properties(p, pcm, n, got, what):
 
 def test_config3_full_size_properties(oracle, decoder):
     """configs[2]: stereo 24-bit 96 kHz, n=4096, order search 1-32 + partition search 0-8,
-    4096 frames on the GPU; the oracle checks a 48-frame slice bit for bit."""
+    4096 frames on the GPU; the oracle checks the whole batch bit for bit (and a 48-frame slice
+    on its own)."""
     p = flake_amd.level_params(5, bits_per_sample=24, sample_rate=96000,
                                order_method=flake_amd.OM_SEARCH, min_prediction_order=1,
                                max_prediction_order=32, min_partition_order=0, max_partition_order=8)
@@ -319,10 +324,13 @@ def test_config3_full_size_properties(oracle, decoder):
     # frames carry their own numbers, so any subset decodes frame by frame
     out, _ = decoder.decode(stream, 2, 24, (nfr // 8) * n)
     assert (out.reshape(-1, n, 2) == pcm[::8]).all()
+    OC.compare_batch(oracle, p, pcm, n, got["info"], got["rice_bits"], got["slot_bytes"], residual=got["residual"],
+                     what="configs[2] 4096 frames")
 
 
 def test_config4_full_size_properties(oracle, decoder):
-    """configs[3]: 8 channels, 24-bit, 192 kHz, n=4096, LPC-12, 1024 frames (8192 subframes)."""
+    """configs[3]: 8 channels, 24-bit, 192 kHz, n=4096, LPC-12, 1024 frames (8192 subframes); the whole
+    batch against the oracle."""
     p = flake_amd.level_params(5, channels=8, bits_per_sample=24, sample_rate=192000,
                                order_method=flake_amd.OM_MAX, max_prediction_order=12)
     n, nfr = 4096, 1024
@@ -344,6 +352,8 @@ def test_config4_full_size_properties(oracle, decoder):
         a = enc.encode_subframes(pcm[:nfr // 2], n, want_residual=False, want_bits=False)
         b = enc.encode_subframes(pcm[nfr // 2:], n, want_residual=False, want_bits=False)
     assert np.concatenate([a["info"], b["info"]]).tobytes() == got["info"].tobytes()
+    OC.compare_batch(oracle, p, pcm, n, got["info"], got["rice_bits"], got["slot_bytes"], residual=got["residual"],
+                     what="configs[3] 1024 frames")
 
 
 @pytest.mark.parametrize("n", [192, 256, 384, 512, 576, 768, 1024, 1152, 1536, 2048, 2304, 2560, 3072,

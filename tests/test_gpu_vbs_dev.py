@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import flake_amd
+import oracle_chunks as OC
 from test_host_frames import oracle_stream
 
 pytestmark = pytest.mark.gpu
@@ -185,8 +186,9 @@ def test_vbs_dev_buffer_too_small():
 @pytest.mark.parametrize("level,nblocks", [(10, 1024), (12, 1024)])
 def test_vbs_dev_corpus_properties(oracle, decoder, level, nblocks):
     """BASELINE configs[4] at bench size through the device entry: the stream decodes to the input,
-    frames are multiples of n/8, the tables are consistent, and the stream's first blocks equal the
-    oracle's stream of those blocks."""
+    frames are multiples of n/8, the tables are consistent, the stream's first blocks equal the
+    oracle's stream of those blocks, and the whole stream and every block's byte count equal the
+    oracle's."""
     p = flake_amd.level_params(level)
     n = p.block_size
     pcm = split_blocks(nblocks, n, 2, 16, every=3)
@@ -201,6 +203,9 @@ def test_vbs_dev_corpus_properties(oracle, decoder, level, nblocks):
     exp, esizes = oracle_stream(oracle, p, flat[:npre * n], n)
     assert (got["block_bytes"][:npre] == esizes).all()
     assert got["packed"][:exp.size].tobytes() == exp.tobytes()
+    full, fsizes = OC.oracle_blocks(oracle, p, pcm, n)
+    msg = OC.stream_mismatch(got["packed"][:nbytes], full, got["block_bytes"], fsizes)
+    assert msg is None, f"level {level}, {nblocks} blocks: {msg}"
 
 
 _VBS_SEEDS = int(__import__("os").environ.get("FLAKE_FUZZ_VBS_SEEDS", "24"))

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import flake_amd
+import oracle_chunks as OC
 from cases import stereo_frames, _rng
 
 pytestmark = pytest.mark.gpu
@@ -81,15 +82,31 @@ def test_vbs_levels(oracle, decoder, level):
         assert len(bs) > 6 and (bs % (n // 8) == 0).all()
 
 
+def test_uniform_host_path_4096_frames(oracle, decoder):
+    """The host layer's fixed-block path at the headline's batch (level 5, 4096 blocks of 4096): the
+    whole stream and every frame's size equal the oracle's flake_encode_frame() loop."""
+    with flake_amd.HostEncoder(5) as enc:
+        p = enc.params()
+        n, nblocks = p.block_size, 4096
+        pcm = flake_amd.synth_pcm(nblocks, n, 2, 16)
+        data, sizes = enc.encode_frames(pcm.reshape(-1, 2), n)
+    exp, esizes = OC.oracle_blocks(oracle, p, pcm, n)
+    msg = OC.stream_mismatch(data, exp, sizes, esizes)
+    assert msg is None, msg
+    out, bs = decoder.decode(data, 2, 16, nblocks * n)
+    assert (out == pcm.reshape(-1, 2)).all() and (bs == n).all()
+
+
 @pytest.mark.parametrize("level,nblocks", [(10, 3072), (12, 2048)])
 def test_vbs_large_corpus_properties(oracle, decoder, level, nblocks):
-    """BASELINE configs[4] at a corpus size the oracle cannot follow in test time (33.5 M samples
-    at level 12): size-independent properties of the whole stream -- it decodes to the input
+    """BASELINE configs[4] at corpus size (33.5 M samples at level 12) through the host layer: the whole
+    stream and every block's byte count equal the oracle's (its blocks on a thread pool:
+    oracle_chunks.oracle_blocks), plus size-independent properties -- it decodes to the input
     (independent decoder), STREAMINFO carries the input's MD5 (the sample count is the caller's to
-    fill in, as in libflake), every frame is a
-    multiple of n/8 samples, split blocks exist -- plus byte equality with the oracle's stream on
-    the corpus' first blocks encoded as a stream of their own (VBS frame numbers count samples
-    from the stream's start, so a prefix of the corpus is a stream the oracle can check)."""
+    fill in, as in libflake), every frame is a multiple of n/8 samples, split blocks exist -- and
+    byte equality with the oracle's stream on the corpus' first blocks encoded as a stream of their
+    own (VBS frame numbers count samples from the stream's start, so a prefix of the corpus is a
+    stream of its own)."""
     with flake_amd.HostEncoder(level) as enc:
         p = enc.params()
         n = p.block_size
@@ -106,6 +123,9 @@ def test_vbs_large_corpus_properties(oracle, decoder, level, nblocks):
         assert (out == pcm).all()
         assert bs.sum() == pcm.shape[0] and (bs % (n // 8) == 0).all()
         assert len(bs) > nblocks + nblocks // 6                 # the forced splits happened
+        exp, esizes = OC.oracle_blocks(oracle, p, pcm.reshape(nblocks, n, 2), n)
+        msg = OC.stream_mismatch(data, exp, sizes, esizes)
+        assert msg is None, f"level {level}, {nblocks} blocks: {msg}"
     npre = 6
     with flake_amd.HostEncoder(level) as enc:
         pre, psizes = enc.encode_frames(pcm[:npre * n], n)
