@@ -45,7 +45,20 @@ static __device__ long long g_fhip_stamps[64];   // one per kernel file; api.hip
     do {                                                                               \
         if (blockIdx.x == 0 && (threadIdx.x & 255) == 0) for (int z_ = lo; z_ < hi; z_++) g_fhip_stamps[z_] = 0; \
     } while (0)
+// per wave (tools/stamps_k1_waves.py): wave w of workgroup 0 (w < 4) adds to slot i + w
+#define ACCUM_W(i, a_, b_)                                                             \
+    do {                                                                               \
+        if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && threadIdx.x < 256)           \
+            g_fhip_stamps[(i) + (threadIdx.x >> 6)] += (long long)((b_) - (a_));       \
+    } while (0)
+#define ACC_RESET_W(i)                                                                 \
+    do {                                                                               \
+        if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && threadIdx.x < 256)           \
+            g_fhip_stamps[(i) + (threadIdx.x >> 6)] = 0;                               \
+    } while (0)
 #else
+#define ACCUM_W(i, a_, b_) do { } while (0)
+#define ACC_RESET_W(i) do { } while (0)
 #define STAMP(i) do { } while (0)
 #define TICK(v_) do { } while (0)
 #define ACCUM(i, a_, b_) do { } while (0)

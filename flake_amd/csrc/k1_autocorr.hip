@@ -427,7 +427,8 @@ void k_autocorr_ps(const int32_t *__restrict__ smp, double *__restrict__ autoc,
 //    lags) for all 32 subframes: lane = (parity pi, subframe).  The lag shift is
 //    wave-uniform, 32 lanes of one parity read 32 consecutive-stride addresses
 //    (stride odd: conflict-free ds_read_b64), the group with l0 = 0 needs no
-//    second operand stream at all (d[p - 0] is `a`), and the operands of the
+//    second operand stream at all (d[p - 0] is `a`), nor does the even group
+//    after it (its b0 is the lane's own earlier `a`: hist[]), and the operands of the
 //    higher lags of a group are the previous steps' values, carried in registers;
 //  * producer wave p loads rows 8p..8p+7 three tiles ahead (counted waits),
 //    windows them (lpc.c:28-40; two weights per lane and tile serve all rows)
@@ -448,6 +449,18 @@ void k_autocorr_ps(const int32_t *__restrict__ smp, double *__restrict__ autoc,
 // help: a SIMD serves its waves oldest first and the LDS return blocks the SIMD's
 // vector issue, not just the reading wave's (ubench_walk, two waves per SIMD: 1.8x
 // the wall time of one; the clock stays at 2.1-2.4 GHz, tools/fp64_clock.hip).
+// Round 6 (per-wave stamps, tools/stamps_k1_waves.py, profiles/r06_k1_wave_stamps.txt): at the
+// headline all four walks took 46-50 cycles per step and group {5,7} set the tile time; without any
+// b0 read (probe NOB) the three b0 groups fell to 38 and {0,2,4} set it at 49.  Every b0 value is
+// already in some lane's registers.  For the even group after group 0 (l0 = 2 NCH) it is the lane's
+// own `a` from NCH steps back, now kept in hist[] (walk_all / walk_tile, HD): {6,8} walks at 35
+// cycles per step, {0,2,4} at 45 (one LDS stream fewer on the CU), and the launch is 50.5 us, from
+// 55.7.  For an odd group it is the partner half's (lane ^ 32) `a`, at ages (l0 + 1) / 2 and
+// (l0 - 1) / 2 for the two halves: one v_permlane32_swap_b32 pair delivers the two halves' values
+// into two different registers whatever the skew between the halves (the ages always differ by an
+// odd number of steps), so a select follows.  Priced in tools/ubench_walk.hip (mode x): 2 swaps +
+// 2 copies + 2 selects per double cost 30.5 cycles per step over the a-stream alone, the swaps
+// without a select still 22.7, a ds_read_b64 7.7 -- the odd groups keep their b0 stream.
 // Fatter groups were priced too: all even lags of order 8 in one wave (5 chains, one
 // stream) 49.8 cycles per step, all odd ones (4 chains, two streams) 43.5 -- 93 cycles
 // of SIMD time per 32 subframes and step against 32 + 3 x 25.7 = 109 for today's four
@@ -763,12 +776,18 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
     // FIRST is the tile that starts the block: products of positions <= maxlag
     // belong to the head (below), so their `a` is replaced by 0 -- a (+-0) product
     // leaves a running sum, which is never -0, bit for bit as it was.  SAME: the
-    // group starts at lag 0, so b0 is a.
+    // group starts at lag 0, so b0 is a.  HD > 0: an even group with l0 = 2 HD, whose
+    // b0 = d[p - l0] is this lane's own `a` from HD steps back -- taken from hist[]
+    // (the raw `a`, before the head's zeroing; zeros before the block, as the halo of
+    // tile 0 is) instead of a second LDS stream.
     // K = chains of this wave's group (NCH or NCH-1: the groups differ by at most one).
-    auto walk_tile = [&](const double *rowA_, const double *rowB_, auto first, auto same, auto kc) {
+    auto walk_tile = [&](const double *rowA_, const double *rowB_, auto first, auto same, auto histc, auto kc,
+                         auto &hist) {
         constexpr bool FIRST = decltype(first)::value;
         constexpr bool SAME = decltype(same)::value;
+        constexpr int HD = decltype(histc)::value;
         constexpr int K = decltype(kc)::value;
+        constexpr bool NOB = SAME || HD > 0 || wt_probe_nob;     // no b0 stream from the LDS
         constexpr int NS = PS_HALF / PS_CH;
         // stages of operands in flight ahead of their use: two while a stage is short
         constexpr int DEPTH = (K <= 3) ? 2 : 1;
@@ -787,12 +806,12 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
                 const dbl2 v = rowA[(stage * PS_CH + u) / 2];
                 A[set][u] = v.x; A[set][u + 1] = v.y;
             }
-            if (!SAME && !wt_probe_nob) {
+            if (!NOB) {
 #pragma unroll
                 for (int u = 0; u < PS_CH; u++) B[set][u] = rowB[stage * PS_CH + u];
             }
         };
-        constexpr int PER_STAGE = PS_CH / 2 + ((SAME || wt_probe_nob) ? 0 : PS_CH);     // LDS reads per stage
+        constexpr int PER_STAGE = PS_CH / 2 + (NOB ? 0 : PS_CH);     // LDS reads per stage
 #pragma unroll
         for (int k = 0; k < DEPTH; k++) fetch(k, k);
 #pragma unroll
@@ -814,7 +833,8 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int u = 0; u < PS_CH; u++) {
-                const double x = (SAME || wt_probe_nob) ? A[st % NSET][u] : B[st % NSET][u];
+                const double x = (SAME || wt_probe_nob) ? A[st % NSET][u] : (HD > 0) ? hist[HD > 0 ? HD - 1 : 0]
+                                                                                      : B[st % NSET][u];
                 double a = A[st % NSET][u];
                 if (FIRST && 2 * (st * PS_CH + u) <= FHIP_MAX_ORDER)            // steps that can hold p <= maxlag
                     a = (2 * (st * PS_CH + u) + pi > maxlag) ? a : 0.0;
@@ -827,50 +847,73 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
 #pragma unroll
                 for (int j = K - 1; j >= 2; j--) cy[j] = cy[j - 1];
                 if constexpr (K > 1) cy[1] = x;
+                if constexpr (HD > 0) {
+#pragma unroll
+                    for (int k = HD - 1; k >= 1; k--) hist[k] = hist[k - 1];
+                    hist[0] = A[st % NSET][u];
+                }
             }
             __builtin_amdgcn_sched_barrier(0);
         }
     };
 
-    int bi = 0;
-    ACC_RESET(40, 44);
-    for (int t = 0; t < ntiles_pad; t++) {
-        TICK(tc0);
-        __syncthreads();                                   // tile t is in buffer bi
-        TICK(tc1);
-        ACCUM(40, tc0, tc1);
-        if (t >= ntiles || wt_probe_nowalk) continue;      // padding of the producers' unroll
-        const double *buf = wt_lds + bi * WT_BUF;
-        if (t == 0 && pi == pih) {
-            // head (lpc.c:60-61): positions lag..maxlag of BOTH parities, in order,
-            // into this lane's sums (tile 0 holds them all: maxlag <= 32 < AC_TILE)
-            for (int x = 0; x <= maxlag; x++) {
-                const double a = buf[slotc(x)];
+    // The tile loop, one instance per kind of group, so that hist[] is live only in
+    // the instance that uses it.
+    auto walk_all = [&](auto same, auto histc, auto kc) {
+        constexpr int HD = decltype(histc)::value;
+        double hist[HD > 0 ? HD : 1];
 #pragma unroll
-                for (int j = 0; j < NCH; j++) {
-                    const int lag = l0 + 2 * j;
-                    if (j < nch && x >= lag) {
-                        const double pr = a * buf[slotc(x - lag)];
-                        S[j] = S[j] + pr;
+        for (int k = 0; k < (HD > 0 ? HD : 1); k++) hist[k] = 0.0;
+        int bi = 0;
+        for (int t = 0; t < ntiles_pad; t++) {
+            TICK(tc0);
+            __syncthreads();                                   // tile t is in buffer bi
+            TICK(tc1);
+            ACCUM(40, tc0, tc1);
+            ACCUM_W(56, tc0, tc1);
+            if (t >= ntiles || wt_probe_nowalk || nch <= 0) continue;    // padding of the producers' unroll
+            const double *buf = wt_lds + bi * WT_BUF;
+            if (t == 0 && pi == pih) {
+                // head (lpc.c:60-61): positions lag..maxlag of BOTH parities, in order,
+                // into this lane's sums (tile 0 holds them all: maxlag <= 32 < AC_TILE)
+                for (int x = 0; x <= maxlag; x++) {
+                    const double a = buf[slotc(x)];
+#pragma unroll
+                    for (int j = 0; j < NCH; j++) {
+                        const int lag = l0 + 2 * j;
+                        if (j < nch && x >= lag) {
+                            const double pr = a * buf[slotc(x - lag)];
+                            S[j] = S[j] + pr;
+                        }
                     }
                 }
             }
+            if (t == 0) walk_tile(buf + offA, buf + offB, std::true_type{}, same, histc, kc, hist);
+            else walk_tile(buf + offA, buf + offB, std::false_type{}, same, histc, kc, hist);
+            bi = (bi == WT_NBUF - 1) ? 0 : bi + 1;
+            TICK(tc2);
+            ACCUM(t == 0 ? 42 : 41, tc1, tc2);
+            ACCUM_W(t == 0 ? 52 : 48, tc1, tc2);
         }
-        using KF = std::integral_constant<int, NCH>;
-        using KL = std::integral_constant<int, (NCH > 1) ? NCH - 1 : 1>;
-        if (l0 == 0) {                                     // group 0 always has NCH chains
-            if (t == 0) walk_tile(buf + offA, buf + offB, std::true_type{}, std::true_type{}, KF{});
-            else walk_tile(buf + offA, buf + offB, std::false_type{}, std::true_type{}, KF{});
-        } else if (nch == NCH) {
-            if (t == 0) walk_tile(buf + offA, buf + offB, std::true_type{}, std::false_type{}, KF{});
-            else walk_tile(buf + offA, buf + offB, std::false_type{}, std::false_type{}, KF{});
-        } else if (nch > 0) {
-            if (t == 0) walk_tile(buf + offA, buf + offB, std::true_type{}, std::false_type{}, KL{});
-            else walk_tile(buf + offA, buf + offB, std::false_type{}, std::false_type{}, KL{});
-        }
-        bi = (bi == WT_NBUF - 1) ? 0 : bi + 1;
-        TICK(tc2);
-        ACCUM(t == 0 ? 42 : 41, tc1, tc2);
+    };
+
+    ACC_RESET(40, 44);
+    ACC_RESET_W(48); ACC_RESET_W(52); ACC_RESET_W(56);    // per consumer wave: walk, tile 0, barrier wait
+    using KF = std::integral_constant<int, NCH>;
+    using KL = std::integral_constant<int, (NCH > 1) ? NCH - 1 : 1>;
+    using H0 = std::integral_constant<int, 0>;
+    using HN = std::integral_constant<int, NCH>;
+    if (l0 == 0) {                                         // group 0 always has NCH chains
+        walk_all(std::true_type{}, H0{}, KF{});
+    } else if (l0 == 2 * NCH) {
+        // the even group after group 0 (split = 1; with split = 2, the second even group when
+        // it starts there): b0 from registers
+        if (nch == NCH) walk_all(std::false_type{}, HN{}, KF{});
+        else walk_all(std::false_type{}, HN{}, KL{});
+    } else if (nch == NCH) {
+        walk_all(std::false_type{}, H0{}, KF{});
+    } else {                                               // (nch = 0: barriers only)
+        walk_all(std::false_type{}, H0{}, KL{});
     }
     // lpc.c:68: autoc = temp + temp2 -- the two parities of a lag are lanes l, l+32
 #pragma unroll
@@ -960,7 +1003,10 @@ ac_choice pick_autocorr(int nsub, int n, int max_order)
     if ((n % AC_TILE) == 0) {
         const int e0 = (ch.ne + 1) / 2;
         // re-measured after this round's changes: 23 ns per step up to three chains per
-        // group, 8 us per launch for barriers, head and the K2 tail (n = 2560 .. 7168)
+        // group, 8 us per launch for barriers, head and the K2 tail (n = 2560 .. 7168).
+        // Round 6 (b0 of the second even group from registers): the headline walk is (50.5 - 8) us /
+        // 2048 steps = 20.8 ns.  Not re-fitted: the kernel only got faster where it was already
+        // chosen, and a lower constant would move the wt / ps switch onto batches not re-measured.
         const double per_step = (4.8 * e0 > 23.0) ? 4.8 * e0 : 23.0;
         const int tiles = (nsub + WT_SUB - 1) / WT_SUB;
         t_wt = (double)((tiles + 255) / 256) * (0.5 * n * per_step + 8000.0);

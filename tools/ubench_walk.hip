@@ -7,9 +7,29 @@
 
 #define STEPS 65536
 
+// partner-half value for an odd lag group: the low half (parity 0) needs the high half's
+// `a` from k0 = (l0 + 1) / 2 steps back (older), the high half the low half's from k0 - 1
+// steps back (newer).  One swap pair moves the high half of `older` to the low half of
+// `newer` and the low half of `newer` to the high half of `older`: the two halves' operands
+// land in different registers, so a select (or a wrong result, SEL = false) follows.
+template <bool SEL>
+__device__ __forceinline__ double partner_swap(double older, double newer, bool hi)
+{
+    int2 o = __builtin_bit_cast(int2, older), n = __builtin_bit_cast(int2, newer);
+    asm("v_permlane32_swap_b32 %0, %1" : "+v"(o.x), "+v"(n.x));
+    asm("v_permlane32_swap_b32 %0, %1" : "+v"(o.y), "+v"(n.y));
+    if (!SEL) return __builtin_bit_cast(double, n);
+    return __builtin_bit_cast(double, hi ? o : n);
+}
+
 // MODE 0: operands in registers, source order mul,mul,mul,add,add,add
 // MODE 1: same, products of step s+1 issued before the adds of step s
 // MODE 2: MODE 0 with the a-stream from LDS (ds_read_b128 per two steps, waits counted)
+// MODE 6..8 (the operand b0 = d[p - l0] of an odd lag group, l0 = 1; a-stream two stages ahead):
+//   6: b0 from the partner half (lane ^ 32) by v_permlane32_swap_b32 (two per double) and a
+//      per-lane select (two v_cndmask_b32): the cheapest correct register delivery
+//   7: the swaps alone, no select (results wrong: the floor of any register delivery)
+//   8: b0 from the LDS, one ds_read_b64 per step, as k_autocorr_wt reads it
 template <int K, int MODE>
 __global__ void walk(double *out, long long *cyc, double seed)
 {
@@ -82,6 +102,55 @@ __global__ void walk(double *out, long long *cyc, double seed)
 #pragma unroll
                     for (int j = K - 1; j >= 2; j--) cy[j] = cy[j - 1];
                     if (K > 1) cy[1] = b;
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    } else if (MODE == 6 || MODE == 7 || MODE == 8) {
+        constexpr int PS_CH = 8, NS = 8, DEPTH = 2, NSET = DEPTH + 1;
+        constexpr int PER = PS_CH / 2 + (MODE == 8 ? PS_CH : 0);
+        typedef const volatile double __attribute__((address_space(3))) lds_cvd;
+        lds_cvd *rowb = (lds_cvd *)(buf + ((threadIdx.x ^ 32) & 63) * 70 + 1);
+        const bool hi = (threadIdx.x & 32) != 0;
+        double h1 = 0.0;                                   // own a, one step back
+#pragma unroll 1
+        for (int tile = 0; tile < STEPS / 64; tile++) {
+            double A[NSET][PS_CH], B[NSET][PS_CH];
+            auto fetch = [&](int set, int stage) {
+#pragma unroll
+                for (int u = 0; u < PS_CH; u += 2) {
+                    const dbl2 v = row[(stage * PS_CH + u) / 2];
+                    A[set][u] = v.x; A[set][u + 1] = v.y;
+                }
+                if (MODE == 8) {
+#pragma unroll
+                    for (int u = 0; u < PS_CH; u++) B[set][u] = rowb[stage * PS_CH + u];
+                }
+            };
+#pragma unroll
+            for (int k = 0; k < DEPTH; k++) fetch(k, k);
+#pragma unroll
+            for (int st = 0; st < NS; st++) {
+                if (st + DEPTH < NS) fetch((st + DEPTH) % NSET, st + DEPTH);
+                const int newer = (st + DEPTH < NS ? 1 : 0) + (st + 1 < NS ? 1 : 0);
+                if (newer == 2) __builtin_amdgcn_s_waitcnt((3 << 14) | ((2 * PER > 15 ? 15 : 2 * PER) << 8) | (7 << 4) | 0xF);
+                else if (newer == 1) __builtin_amdgcn_s_waitcnt((3 << 14) | (PER << 8) | (7 << 4) | 0xF);
+                else __builtin_amdgcn_s_waitcnt((3 << 14) | (0 << 8) | (7 << 4) | 0xF);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int u = 0; u < PS_CH; u++) {
+                    const double a = A[st % NSET][u];
+                    const double x = (MODE == 8) ? B[st % NSET][u] : partner_swap<MODE == 6>(h1, a, hi);
+                    double pr[K];
+                    pr[0] = a * x;
+#pragma unroll
+                    for (int j = 1; j < K; j++) pr[j] = a * cy[j];
+#pragma unroll
+                    for (int j = 0; j < K; j++) S[j] = S[j] + pr[j];
+#pragma unroll
+                    for (int j = K - 1; j >= 2; j--) cy[j] = cy[j - 1];
+                    if (K > 1) cy[1] = x;
+                    h1 = a;
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -180,8 +249,20 @@ void run(const char *name, int blocks, int threads)
     hipFree(out); hipFree(cyc);
 }
 
-int main()
+int main(int argc, char **argv)
 {
+    if (argc > 1 && argv[1][0] == 'x') {
+        // price of the operand b0 of an odd lag group (K = 2, as groups {1,3} and {5,7} at max
+        // order 8), one wave per SIMD on every CU: against the a-stream alone
+        run<2, 3>("x: a-stream only (no b0)", 256, 256);
+        run<2, 8>("x: b0 from LDS (ds_read_b64 per step)", 256, 256);
+        run<2, 6>("x: b0 by permlane32_swap + select", 256, 256);
+        run<2, 7>("x: permlane32_swap only (wrong)", 256, 256);
+        run<2, 3>("x: a-stream only (no b0), 2 waves/SIMD", 256, 512);
+        run<2, 8>("x: b0 from LDS, 2 waves/SIMD", 256, 512);
+        run<2, 6>("x: permlane32_swap + select, 2 waves/SIMD", 256, 512);
+        return 0;
+    }
     run<3, 0>("regs, 1 wave/SIMD, chip", 256, 256);
     run<3, 1>("regs pipelined, 1 wave/SIMD, chip", 256, 256);
     run<3, 2>("LDS a-stream, 1 wave/SIMD, chip", 256, 256);
