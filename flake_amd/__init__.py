@@ -25,6 +25,7 @@ MAX_LAGS = 33
 MAX_BLOCK = 65535
 
 OK, E_GENERIC, E_HIP, E_UNSUPPORTED, E_INVALID, E_NOMEM, E_VERIFY = 0, -1, -2, -3, -4, -5, -6
+PCM_S32, PCM_S16 = 0, 1      # FHIP_PCM_*: what a handle's pcm pointers address (fhip_set_pcm_format)
 
 SUB_CONSTANT, SUB_VERBATIM, SUB_FIXED, SUB_LPC = 0, 1, 8, 32
 CH_NOT_STEREO, CH_LEFT_RIGHT, CH_LEFT_SIDE, CH_RIGHT_SIDE, CH_MID_SIDE = 0, 1, 8, 9, 10
@@ -170,6 +171,7 @@ def load_library() -> C.CDLL:
         "fhip_destroy": (None, [vp]),
         "fhip_set_stream": (i, [vp, vp]),
         "fhip_sync": (i, [vp]),
+        "fhip_set_pcm_format": (i, [vp, i]),
         "fhip_strerror": (C.c_char_p, [i]),
         "fhip_last_error": (C.c_char_p, [vp]),
         "fhip_version": (C.c_char_p, []),
@@ -214,6 +216,7 @@ ABI_SYMBOLS = (
     "fhip_encode_blocks_vbs_dev", "fhip_order_search_bits",
     "fhip_host_alloc", "fhip_host_free", "fhip_host_register", "fhip_host_unregister", "fhip_frames_packed_upload", "fhip_frames_packed_fetch_async", "fhip_frames_packed_fetch_wait",
     "fhip_set_verify", "fhip_verify_frames_dev", "fhip_verify_frames", "fhip_last_launches",
+    "fhip_set_pcm_format",
 )
 
 
@@ -250,6 +253,7 @@ class Encoder:
         if rc != OK:
             raise FlakeHipError(rc, "fhip_create", self.lib.fhip_strerror(rc).decode())
         self._h = h
+        self.pcm_format = PCM_S32
 
     # -- plumbing ---------------------------------------------------------
     def close(self) -> None:
@@ -282,6 +286,16 @@ class Encoder:
     def set_profiling(self, on: bool) -> None:
         self._check(self.lib.fhip_set_profiling(self._h, int(on)), "fhip_set_profiling")
 
+    def set_pcm_format(self, fmt: int) -> None:
+        """PCM_S32 (default) or PCM_S16: every pcm handed to this handle then addresses interleaved int16
+        (fhip_set_pcm_format); the host-array methods below convert to that dtype.  For tests and tools."""
+        self._check(self.lib.fhip_set_pcm_format(self._h, int(fmt)), "fhip_set_pcm_format")
+        self.pcm_format = int(fmt)
+
+    @property
+    def pcm_dtype(self):
+        return np.int16 if self.pcm_format == PCM_S16 else np.int32
+
     def set_verify(self, on: bool) -> None:
         """Verify the handle's own packed output on the device (fhip_set_verify)."""
         self._check(self.lib.fhip_set_verify(self._h, int(on)), "fhip_set_verify")
@@ -301,7 +315,7 @@ class Encoder:
         st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
                                   else stream, dtype=np.uint8)
         fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
-        pc = np.ascontiguousarray(pcm, dtype=np.int32).reshape(-1, self.params.channels)
+        pc = np.ascontiguousarray(pcm, dtype=self.pcm_dtype).reshape(-1, self.params.channels)
         recs = np.zeros(len(fb), dtype=VERIFY_REC_DTYPE)
         summary = np.zeros(4, dtype=np.int64)
         vi = VerifyIn(st.ctypes.data if st.size else None, st.size, fb.ctypes.data if fb.size else None, len(fb),
@@ -365,9 +379,9 @@ class Encoder:
                          want_bits: bool = True, want_samples: bool = False,
                          want_autoc: bool = False, want_frames: bool = False,
                          first_frame_number: int = 0) -> dict:
-        """Host numpy batch: pcm is [nframes][block_size][channels] int32."""
+        """Host numpy batch: pcm is [nframes][block_size][channels] int32 (int16 under PCM_S16)."""
         ch = self.params.channels
-        pcm = np.ascontiguousarray(pcm, dtype=np.int32).reshape(-1, block_size, ch)
+        pcm = np.ascontiguousarray(pcm, dtype=self.pcm_dtype).reshape(-1, block_size, ch)
         nframes = pcm.shape[0]
         nsub = nframes * ch
         out = {"info": np.zeros(nsub, dtype=INFO_DTYPE)}
@@ -462,7 +476,7 @@ class Encoder:
     def prepare_frames(self, pcm: np.ndarray, block_size: int):
         """copy_samples + channel_decorrelation + remove_wasted_bits (encode.c:541-694)."""
         ch = self.params.channels
-        pcm = np.ascontiguousarray(pcm, dtype=np.int32).reshape(-1, block_size, ch)
+        pcm = np.ascontiguousarray(pcm, dtype=self.pcm_dtype).reshape(-1, block_size, ch)
         nframes = pcm.shape[0]
         smp = np.zeros((nframes, ch, block_size), dtype=np.int32)
         info = np.zeros(nframes * ch, dtype=INFO_DTYPE)
@@ -498,6 +512,8 @@ def load_host_library() -> C.CDLL:
     lib.flake_amd_encode_frames.argtypes = [cp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             C.c_size_t, C.c_void_p]
     lib.flake_amd_encode_frames.restype = C.c_longlong
+    lib.flake_amd_encode_frames_s16.argtypes = lib.flake_amd_encode_frames.argtypes
+    lib.flake_amd_encode_frames_s16.restype = C.c_longlong
     lib.flake_amd_pin_buffers.argtypes = [cp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     lib.flake_amd_pin_buffers.restype = C.c_int
     lib.flake_amd_encode_close.argtypes = [cp]
@@ -575,18 +591,26 @@ class HostEncoder:
 
     def encode_frames(self, pcm: np.ndarray, block_size: int, tail_size: int = 0):
         """pcm: [nblocks*block_size + tail_size][channels] int32.  Returns (bytes, sizes)."""
+        return self._encode_frames(pcm, np.int32, block_size, tail_size)
+
+    def encode_frames_s16(self, pcm: np.ndarray, block_size: int, tail_size: int = 0):
+        """The same from int16 samples (flake_amd_encode_frames_s16).  For tests and tools."""
+        return self._encode_frames(pcm, np.int16, block_size, tail_size)
+
+    def _encode_frames(self, pcm: np.ndarray, dtype, block_size: int, tail_size: int):
         ch = self.ctx.channels
-        pcm = np.ascontiguousarray(pcm, dtype=np.int32).reshape(-1, ch)
+        pcm = np.ascontiguousarray(pcm, dtype=dtype).reshape(-1, ch)
         nblocks = (pcm.shape[0] - tail_size) // block_size
         assert nblocks * block_size + tail_size == pcm.shape[0]
         cap = 64 + pcm.size * 5 + 64 * (nblocks + 1) * 8
         out = np.zeros(cap, dtype=np.uint8)
         sizes = np.zeros(nblocks + (1 if tail_size else 0), dtype=np.int32)
-        w = self.lib.flake_amd_encode_frames(C.byref(self.ctx), pcm.ctypes.data, nblocks, block_size,
-                                             tail_size, out.ctypes.data, cap, sizes.ctypes.data)
+        fn, what = ((self.lib.flake_amd_encode_frames_s16, "flake_amd_encode_frames_s16") if dtype == np.int16
+                    else (self.lib.flake_amd_encode_frames, "flake_amd_encode_frames"))
+        w = fn(C.byref(self.ctx), pcm.ctypes.data, nblocks, block_size, tail_size, out.ctypes.data, cap,
+               sizes.ctypes.data)
         if w < 0:
-            raise FlakeHipError(int(w), "flake_amd_encode_frames",
-                                self.lib.flake_amd_last_error(C.byref(self.ctx)).decode())
+            raise FlakeHipError(int(w), what, self.lib.flake_amd_last_error(C.byref(self.ctx)).decode())
         return out[:w].copy(), sizes
 
     def encode_frame(self, pcm: np.ndarray) -> bytes:

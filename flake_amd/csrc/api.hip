@@ -47,6 +47,13 @@ struct fhip_ctx {
     int max_frames = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
+    int pcm_format = FHIP_PCM_S32;    // fhip_set_pcm_format: what every `pcm` pointer addresses
+    size_t pcm_width() const { return pcm_format == FHIP_PCM_S16 ? sizeof(int16_t) : sizeof(int32_t); }
+    // pcm advanced by `values` samples of the handle's width
+    const int32_t *pcm_step(const int32_t *pcm, size_t values) const
+    {
+        return reinterpret_cast<const int32_t *>(reinterpret_cast<const char *>(pcm) + values * pcm_width());
+    }
 
     // device workspaces, sized for max_frames * channels subframes of p.block_size
     DevBuf<int32_t> d_smp;            // [nsub][n]
@@ -59,7 +66,7 @@ struct fhip_ctx {
     DevBuf<fhip_subframe_info> d_k0rec;      // [nsub] K0's records (obits, wasted, ch_mode, row flag): K1 and
                                              // K3 read them here, K3 copies them into the caller's info[]
     // staging for the host-pointer entry points (ensure_staging; the frame buffers where frames are asked for)
-    DevBuf<int32_t> d_pcm;
+    DevBuf<int32_t> d_pcm;            // (sized for int32; int16 PCM fills half of it)
     DevBuf<fhip_subframe_info> d_info;
     DevBuf<int32_t> d_res;
     DevBuf<uint8_t> d_bits;           // whatever the caller's slots need
@@ -294,7 +301,8 @@ static int run_range(fhip_ctx *c, hipStream_t st, bool prof, const int32_t *pcm,
     // stereo batches in whole tiles: K0 only decides (ch_mode, wasted bits), the K1
     // producers apply that to the PCM they stream anyway and write smp
     // `prepared`: K0 of this batch already ran (fhip_prepare_ahead) into smp and these records
-    const bool fused = !prepared && !rg && lpc_path && fhip::autocorr_fuses_prepare(p, nsub, n);
+    const bool fused = !prepared && !rg && lpc_path && c->pcm_format == FHIP_PCM_S32 &&      // (the experiment is int32 only)
+                       fhip::autocorr_fuses_prepare(p, nsub, n);
     // rows of 16-bit samples where every kernel of this batch reads them that way and
     // nobody outside asked for the int32 rows
     const bool narrow = prepared ? prepared_narrow
@@ -304,7 +312,8 @@ static int run_range(fhip_ctx *c, hipStream_t st, bool prof, const int32_t *pcm,
     const fhip_subframe_info *k0rec = prepared ? prepared : own_rec;
     if (!prepared) {
         Prof pr(c, 0, prof);
-        HIP_TRY(c, fhip::launch_prepare(st, p, pcm, nframes, n, smp, own_rec, fused, narrow, frame_src, dev_frames));
+        HIP_TRY(c, fhip::launch_prepare(st, p, pcm, nframes, n, smp, own_rec, fused, narrow, frame_src, dev_frames,
+                                        c->pcm_format));
     }
     if (lpc_path) {
         // K2 rides on K1's tail where K1 is the wave-typed kernel and the order fits registers
@@ -345,7 +354,8 @@ static int run_range(fhip_ctx *c, hipStream_t st, bool prof, const int32_t *pcm,
         Prof pr(c, 4, prof);
         const uint32_t step = p.allow_vbs ? (uint32_t)n : 1u;
         HIP_TRY(c, fhip::launch_assemble(st, p, pcm, nframes, n, info, bits, slot_bytes, fo.frames,
-                                         fo.stride, fo.bytes, fo.first, step, fo.numbers, frame_src, dev_frames));
+                                         fo.stride, fo.bytes, fo.first, step, fo.numbers, frame_src, dev_frames,
+                                         c->pcm_format));
     }
     return FHIP_OK;
 }
@@ -392,7 +402,7 @@ int run_pipeline(fhip_ctx *c, const int32_t *pcm, int nframes, int n,
         HIP_TRY(c, hipStreamWaitEvent(c->aux[h], c->ev_fork, 0));
         const size_t f0 = (size_t)parts[h], nf = (size_t)(parts[h + 1] - parts[h]);
         const size_t sub0 = f0 * nch;
-        int rc = run_range(c, c->aux[h], false, pcm + f0 * n * nch, (int)nf, n, info + sub0,
+        int rc = run_range(c, c->aux[h], false, c->pcm_step(pcm, f0 * n * nch), (int)nf, n, info + sub0,
                            residual ? residual + sub0 * n : nullptr,
                            bits ? bits + sub0 * (size_t)slot_bytes : nullptr, slot_bytes,
                            smp + sub0 * n, autoc + sub0 * FHIP_MAX_LAGS, sub0,
@@ -427,7 +437,7 @@ int run_verify(fhip_ctx *c, const uint8_t *stream, long long stream_bytes, const
     if (rc != FHIP_OK) return rc;
     const fhip_params &p = c->p;
     fhip::VerifyArgs a{stream, stream_bytes, frame_bytes, nframes, dev_count, pcm, nsamples, first_sample,
-                       p.channels, p.bits_per_sample, block_size, p.sample_rate, p.allow_vbs ? 1 : 0,
+                       p.channels, p.bits_per_sample, block_size, p.sample_rate, p.allow_vbs ? 1 : 0, c->pcm_format,
                        c->d_vws, recs ? recs : c->d_vrec, summary ? reinterpret_cast<long long *>(summary) : c->d_vsum,
                        reinterpret_cast<unsigned long long *>(c->d_vsum + 4), totals};
     Prof pr(c, kProfVerify, c->profiling);
@@ -675,6 +685,24 @@ int fhip_set_stream(fhip_ctx *c, void *hip_stream)
     return FHIP_OK;
 }
 
+int fhip_set_pcm_format(fhip_ctx *c, int format)
+{
+    if (!c) return FHIP_E_INVALID;
+    if (format != FHIP_PCM_S32 && format != FHIP_PCM_S16) return fail(c, FHIP_E_INVALID, "unknown PCM format");
+    if (format == FHIP_PCM_S16 && c->p.bits_per_sample > 16)
+        return fail(c, FHIP_E_INVALID, "FHIP_PCM_S16 needs bits_per_sample <= 16");
+    if (format == c->pcm_format) return FHIP_OK;
+    // what was prepared or uploaded ahead was read at the old width: ordered before the next batch, then dropped
+    if (c->ahead.valid) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_prep[c->ahead.buf], 0));
+        c->ahead.valid = false;
+    }
+    c->uploaded_pcm = nullptr;
+    c->pcm_format = format;
+    return FHIP_OK;
+}
+
 int fhip_sync(fhip_ctx *c)
 {
     if (!c) return FHIP_E_INVALID;
@@ -772,7 +800,7 @@ int fhip_prepare_ahead(fhip_ctx *c, const fhip_batch *b)
     {
         Prof pr(c, 0, c->profiling, c->pre);
         HIP_TRY(c, fhip::launch_prepare(c->pre, p, b->pcm, b->nframes, n, c->d_smp_ahead[buf],
-                                        c->d_prep[buf], false, narrow));
+                                        c->d_prep[buf], false, narrow, nullptr, nullptr, c->pcm_format));
     }
     HIP_TRY(c, hipEventRecord(c->ev_prep[buf], c->pre));
     c->ahead.valid = true;
@@ -813,7 +841,7 @@ int fhip_encode_subframes(fhip_ctx *c, const fhip_batch *b)
     double *d_autoc_out = b->autoc ? c->d_autoc : nullptr;
     // a section that does not fit its slot leaves the slot untouched: what comes back for it is zeros
     if (b->rice_bits) HIP_TRY(c, hipMemsetAsync(c->d_bits, 0, bits_bytes, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_pcm, b->pcm, nsub * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_pcm, b->pcm, nsub * n * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_info, 0, nsub * sizeof(fhip_subframe_info), c->stream));
     FrameOut fo{nullptr, 0, nullptr, 0};
     if (b->frames) {
@@ -859,7 +887,7 @@ int fhip_frames_packed_upload(fhip_ctx *c, const fhip_batch *b)
     const int64_t stride = fhip_frame_stride(&c->p, b->block_size);
     rc = ensure_staging(c, (size_t)b->nframes * c->p.channels * (size_t)((stride + 3) & ~(int64_t)3));
     if (rc != FHIP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->d_pcm, b->pcm, nvals * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_pcm, b->pcm, nvals * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->uploaded_pcm = b->pcm;
     c->uploaded_vals = nvals;
@@ -896,7 +924,7 @@ int fhip_frames_packed_begin(fhip_ctx *c, const fhip_batch *b, int64_t *total_by
     c->uploaded_pcm = nullptr;
     if (c->fetch_pending) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_fetch, 0));     // d_packed is still being read
     if (!uploaded)
-        HIP_TRY(c, hipMemcpyAsync(c->d_pcm, b->pcm, nsub * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_pcm, b->pcm, nsub * n * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
     rc = run_pipeline(c, c->d_pcm, b->nframes, b->block_size, c->d_info, nullptr, c->d_bits, slot,
                       nullptr, nullptr, fo, false);
     if (rc != FHIP_OK) return rc;
@@ -1322,9 +1350,21 @@ int vbs_dev_core(fhip_ctx *c, const int32_t *pcm, int nblocks, int block_size, u
     return FHIP_OK;
 }
 
+// Variable block size reads the caller's pieces where they lie, with 16-byte loads whose alignment rules are those of
+// 4-byte samples: not offered for int16 PCM.  Nothing is launched (clear_list: the encode entries, which start a launch
+// list, leave it empty).
+int vbs_refuse_s16(fhip_ctx *c, bool clear_list = true)
+{
+    if (c->pcm_format != FHIP_PCM_S16) return FHIP_OK;
+    if (clear_list) c->launches.clear();
+    return fail(c, FHIP_E_UNSUPPORTED,
+                "variable block size is not supported for int16 PCM (FHIP_PCM_S16): widen the samples or use FHIP_PCM_S32");
+}
+
 int vbs_check(fhip_ctx *c, const void *pcm, int nblocks, int block_size)
 {
     if (!c || !pcm) return fail(c, FHIP_E_INVALID, "null argument");
+    if (const int rc = vbs_refuse_s16(c)) return rc;
     const fhip_params &p = c->p;
     if (!p.variable_block_size || !p.allow_vbs)
         return fail(c, FHIP_E_INVALID, "the handle's parameters have no variable block size");
@@ -1483,7 +1523,7 @@ int fhip_verify_frames(fhip_ctx *c, const fhip_verify_in *in, const fhip_verify_
     HIP_TRY(c, c->d_vpcm.reserve(nv));
     if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_vstream, in->stream, sb, hipMemcpyHostToDevice, c->stream));
     if (nf) HIP_TRY(c, hipMemcpyAsync(c->d_vfb, in->frame_bytes, nf * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    if (nv) HIP_TRY(c, hipMemcpyAsync(c->d_vpcm, in->pcm, nv * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (nv) HIP_TRY(c, hipMemcpyAsync(c->d_vpcm, in->pcm, nv * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
     rc = run_verify(c, c->d_vstream, in->stream_bytes, c->d_vfb, in->nframes, nullptr, c->d_vpcm, in->nsamples,
                     in->first_sample, c->p.block_size, nullptr, nullptr, nullptr);
     if (rc != FHIP_OK) return rc;
@@ -1508,9 +1548,10 @@ int fhip_prepare_frames(fhip_ctx *c, const int32_t *pcm, int nframes, int n,
     if (rc != FHIP_OK) return rc;
     const size_t nsub = (size_t)nframes * c->p.channels;
     if (nsub == 0) return FHIP_OK;
-    HIP_TRY(c, hipMemcpyAsync(c->d_pcm, pcm, nsub * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_pcm, pcm, nsub * n * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_info, 0, nsub * sizeof(fhip_subframe_info), c->stream));
-    HIP_TRY(c, fhip::launch_prepare(c->stream, c->p, c->d_pcm, nframes, n, c->d_smp, c->d_info));
+    HIP_TRY(c, fhip::launch_prepare(c->stream, c->p, c->d_pcm, nframes, n, c->d_smp, c->d_info, false, false, nullptr,
+                                    nullptr, c->pcm_format));
     HIP_TRY(c, hipMemcpyAsync(samples, c->d_smp, nsub * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(info, c->d_info, nsub * sizeof(fhip_subframe_info), hipMemcpyDeviceToHost, c->stream));
     return fhip_sync(c);
@@ -1615,6 +1656,7 @@ int fhip_vbs_split(fhip_ctx *c, const int32_t *pcm, int nblocks, int block_size,
                    int32_t *frames, int32_t *sizes)
 {
     if (!c || !pcm || !frames || !sizes) return fail(c, FHIP_E_INVALID, "null argument");
+    if (const int rc = vbs_refuse_s16(c, false)) return rc;
     if (nblocks < 0 || nblocks > c->max_frames || block_size > c->p.block_size ||
         block_size < 128 || (block_size % 8))
         return fail(c, FHIP_E_INVALID, "vbs needs block_size % 8 == 0 and >= 128 (vbs.c:93)");

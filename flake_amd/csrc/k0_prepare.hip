@@ -1,9 +1,31 @@
 // k0_prepare.hip -- K0: copy_samples + stereo estimate / decorrelation + wasted bits
 // (encode.c:541-694).  pcm [nframes][n][ch] -> smp [nframes][ch][n].
+#include <type_traits>
+
 #include "device_util.h"
 
 namespace fhip {
 namespace {
+
+// The PCM's sample type S is int32_t (flake_encode_frame's contract) or int16_t (fhip_set_pcm_format: FHIP_PCM_S16).
+// Every body below is a template over S; the kernels of the int32 contract keep their names and their code, the
+// int16 instances are kernels of their own (k_*_s16).  Two int16 samples are the halves of one little-endian word:
+__device__ __forceinline__ int32_t s16_lo(int w) { return (int32_t)((uint32_t)w << 16) >> 16; }
+__device__ __forceinline__ int32_t s16_hi(int w) { return (int32_t)w >> 16; }
+
+// encode.c:668-693 for one sample-frame: (left, right) -> the two output channels of `mode`
+__device__ __forceinline__ void decorrelate(int32_t &a, int32_t &b, int mode)
+{
+    if (mode == FHIP_CH_MID_SIDE) {
+        const int32_t mid = (int32_t)((uint32_t)a + (uint32_t)b) >> 1;
+        const int32_t sd = (int32_t)((uint32_t)a - (uint32_t)b);
+        a = mid; b = sd;
+    } else if (mode == FHIP_CH_LEFT_SIDE) {
+        b = (int32_t)((uint32_t)a - (uint32_t)b);
+    } else if (mode == FHIP_CH_RIGHT_SIDE) {
+        a = (int32_t)((uint32_t)a - (uint32_t)b);
+    }
+}
 
 // ---------------------------------------------------------------------------
 // K0  k_prepare
@@ -14,11 +36,12 @@ namespace {
 // RESIDENT = false: frames too long for LDS (n > 20 k, up to FLAC's 65535) are
 // streamed from global memory in each of the three passes instead (L2 serves the
 // re-reads: a frame is 512 KB at most).
-template <bool RESIDENT>
-__global__ __launch_bounds__(NT)
-void k_prepare(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp,
-               fhip_subframe_info *__restrict__ info, int n, int nch, int bps, int estimate,
-               const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames)
+// int16 PCM: a stereo sample-frame is one 4-byte word (frames start 4-byte aligned whatever n).
+template <bool RESIDENT, class S>
+__device__ __forceinline__
+void prepare_lds_body(const S *__restrict__ pcm, int32_t *__restrict__ smp,
+                      fhip_subframe_info *__restrict__ info, int n, int nch, int bps, int estimate,
+                      const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames)
 {
     extern __shared__ int32_t lds_i32[];
     if (dev_frames && (int)blockIdx.x >= dev_count(dev_frames, 0)) return;
@@ -30,31 +53,26 @@ void k_prepare(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp,
 
     if (nch == 2) {
         const int f = blockIdx.x;
-        const int32_t *src = pcm + (frame_src ? (size_t)frame_src[f] : (size_t)f * n * 2);
+        const S *src = pcm + (frame_src ? (size_t)frame_src[f] : (size_t)f * n * 2);
         int32_t *L = lds_i32, *R = lds_i32 + n;
-        const int2 *src2 = reinterpret_cast<const int2 *>(src);
+        auto frame_at = [&](int i) {                     // (left, right) of sample-frame i
+            if constexpr (sizeof(S) == 4) {
+                return reinterpret_cast<const int2 *>(src)[i];
+            } else {
+                const int w = reinterpret_cast<const int *>(src)[i];
+                return make_int2(s16_lo(w), s16_hi(w));
+            }
+        };
         if (RESIDENT) {
             for (int i = tid; i < n; i += NT) {
-                int2 v = src2[i];
+                int2 v = frame_at(i);
                 L[i] = v.x;
                 R[i] = v.y;
             }
             __syncthreads();
         }
-        auto left = [&](int i) { return RESIDENT ? L[i] : src2[i].x; };
-        auto right = [&](int i) { return RESIDENT ? R[i] : src2[i].y; };
-        // encode.c:668-693 for one sample-frame of the input
-        auto decorrelate = [&](int32_t &a, int32_t &b, int md) {
-            if (md == FHIP_CH_MID_SIDE) {
-                const int32_t mid = (int32_t)((uint32_t)a + (uint32_t)b) >> 1;
-                const int32_t sd = (int32_t)((uint32_t)a - (uint32_t)b);
-                a = mid; b = sd;
-            } else if (md == FHIP_CH_LEFT_SIDE) {
-                b = (int32_t)((uint32_t)a - (uint32_t)b);
-            } else if (md == FHIP_CH_RIGHT_SIDE) {
-                a = (int32_t)((uint32_t)a - (uint32_t)b);
-            }
-        };
+        auto left = [&](int i) { return RESIDENT ? L[i] : frame_at(i).x; };
+        auto right = [&](int i) { return RESIDENT ? R[i] : frame_at(i).y; };
 
         int mode = FHIP_CH_LEFT_RIGHT;
         if (estimate && n > 32) {
@@ -136,23 +154,42 @@ void k_prepare(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp,
     }
 }
 
+template <bool RESIDENT>
+__global__ __launch_bounds__(NT)
+void k_prepare(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp,
+               fhip_subframe_info *__restrict__ info, int n, int nch, int bps, int estimate,
+               const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames)
+{
+    prepare_lds_body<RESIDENT>(pcm, smp, info, n, nch, bps, estimate, frame_src, dev_frames);
+}
+
+template <bool RESIDENT>
+__global__ __launch_bounds__(NT)
+void k_prepare_s16(const int16_t *__restrict__ pcm, int32_t *__restrict__ smp,
+                   fhip_subframe_info *__restrict__ info, int n, int nch, int bps, int estimate,
+                   const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames)
+{
+    prepare_lds_body<RESIDENT>(pcm, smp, info, n, nch, bps, estimate, frame_src, dev_frames);
+}
+
 // K0 for 1 or 3..8 channels (no decorrelation, encode.c:660-663): one
 // workgroup per frame walks it in tiles of 256 sample-frames.  A tile is read
 // with coalesced dword loads, transposed through a padded LDS tile, and each
 // thread then owns one sample-frame with all its channels in registers.  Pass 1
 // ORs every sample per channel (wasted bits, encode.c:558-593), pass 2 re-reads
 // (L2), shifts and writes channel rows coalesced.
-__global__ __launch_bounds__(NT)
-void k_prepare_multi(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp,
-                     fhip_subframe_info *__restrict__ info, int n, int nch, int bps,
-                     const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames)
+template <class S>
+__device__ __forceinline__
+void prepare_multi_body(const S *__restrict__ pcm, int32_t *__restrict__ smp,
+                        fhip_subframe_info *__restrict__ info, int n, int nch, int bps,
+                        const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames)
 {
     __shared__ int32_t s_tile[NT * (FHIP_MAX_CH + 1)];
     __shared__ uint32_t s_orr[4][FHIP_MAX_CH];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int f = blockIdx.x;
     if (dev_frames && f >= dev_count(dev_frames, 0)) return;
-    const int32_t *src = pcm + (frame_src ? (size_t)frame_src[f] : (size_t)f * n * nch);
+    const S *src = pcm + (frame_src ? (size_t)frame_src[f] : (size_t)f * n * nch);
     const int stride = nch + 1;
     const int total = n * nch;
 
@@ -210,6 +247,22 @@ void k_prepare_multi(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp,
     }
 }
 
+__global__ __launch_bounds__(NT)
+void k_prepare_multi(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp,
+                     fhip_subframe_info *__restrict__ info, int n, int nch, int bps,
+                     const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames)
+{
+    prepare_multi_body(pcm, smp, info, n, nch, bps, frame_src, dev_frames);
+}
+
+__global__ __launch_bounds__(NT)
+void k_prepare_multi_s16(const int16_t *__restrict__ pcm, int32_t *__restrict__ smp,
+                         fhip_subframe_info *__restrict__ info, int n, int nch, int bps,
+                         const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames)
+{
+    prepare_multi_body(pcm, smp, info, n, nch, bps, frame_src, dev_frames);
+}
+
 // K0 for 1, 3 .. 8 channels with the frame in REGISTERS (round 2): k_prepare_multi above reads
 // the interleaved block twice (the OR pass, then the shift-and-write pass) through an LDS
 // transpose tile; here thread t owns the sample-frame quads 4(t + RT*m) .. +3 -- 4*NCH
@@ -218,20 +271,28 @@ void k_prepare_multi(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp,
 // encode.c:660-663) and the shift, and stores four consecutive samples of one channel at a time
 // (16 bytes).  One read of the PCM, no LDS beyond the cross-wave OR.  n % 4 == 0 and
 // n <= 4 * RT * M.
+// int16 PCM: the thread's 4*NCH values are 8*NCH bytes at a multiple of 8*NCH bytes from the frame's start (itself a
+// multiple of 8*NCH: n % 4 == 0) -- 16-byte aligned for even NCH only, so NCH / 2 16-byte loads there and NCH 8-byte
+// loads for odd NCH.  The values stay packed, two to a register, until the shift-and-store.
 constexpr int RT = 1024;       // threads per frame
-template <int NCH, int M>
-__global__ __launch_bounds__(RT)
-void k_prepare_multi_reg(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp,
-                         fhip_subframe_info *__restrict__ info, int n, int bps,
-                         const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames)
+template <int NCH, int M, class S>
+__device__ __forceinline__
+void prepare_multi_reg_body(const S *__restrict__ pcm, int32_t *__restrict__ smp,
+                            fhip_subframe_info *__restrict__ info, int n, int bps,
+                            const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames)
 {
     __shared__ uint32_t s_orr[RT / 64][8];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int f = blockIdx.x;
     if (dev_frames && f >= dev_count(dev_frames, 0)) return;
     const int quads = n >> 2;
-    const int32_t *src = pcm + (frame_src ? (size_t)frame_src[f] : (size_t)f * n * NCH);
-    int32_t v[M][4 * NCH];                 // v[m][4*NCH]: element e = sample-frame (e / NCH), channel (e % NCH)
+    const S *src = pcm + (frame_src ? (size_t)frame_src[f] : (size_t)f * n * NCH);
+    constexpr bool S16 = sizeof(S) == 2;
+    int32_t v[M][S16 ? 2 * NCH : 4 * NCH]; // element e = sample-frame (e / NCH), channel (e % NCH); int16: half e & 1 of word e >> 1
+    auto val = [&](int m, int e) {
+        if constexpr (S16) return (e & 1) ? s16_hi(v[m][e >> 1]) : s16_lo(v[m][e >> 1]);
+        else return v[m][e];
+    };
     uint32_t orv[NCH];
 #pragma unroll
     for (int c = 0; c < NCH; c++) orv[c] = 0;
@@ -239,14 +300,30 @@ void k_prepare_multi_reg(const int32_t *__restrict__ pcm, int32_t *__restrict__ 
     for (int m = 0; m < M; m++) {
         const int q = tid + RT * m;
         if (q < quads) {
-            const int4 *p4 = reinterpret_cast<const int4 *>(src + (size_t)q * 4 * NCH);   // 16 * NCH bytes: aligned
+            if constexpr (!S16) {
+                const int4 *p4 = reinterpret_cast<const int4 *>(src + (size_t)q * 4 * NCH);   // 16 * NCH bytes: aligned
 #pragma unroll
-            for (int k = 0; k < NCH; k++) {
-                const int4 t4 = p4[k];
-                v[m][4 * k] = t4.x; v[m][4 * k + 1] = t4.y; v[m][4 * k + 2] = t4.z; v[m][4 * k + 3] = t4.w;
+                for (int k = 0; k < NCH; k++) {
+                    const int4 t4 = p4[k];
+                    v[m][4 * k] = t4.x; v[m][4 * k + 1] = t4.y; v[m][4 * k + 2] = t4.z; v[m][4 * k + 3] = t4.w;
+                }
+            } else if constexpr (NCH % 2 == 0) {
+                const int4 *p4 = reinterpret_cast<const int4 *>(src + (size_t)q * 4 * NCH);   // 8 * NCH bytes: 16-byte aligned
+#pragma unroll
+                for (int k = 0; k < NCH / 2; k++) {
+                    const int4 t4 = p4[k];
+                    v[m][4 * k] = t4.x; v[m][4 * k + 1] = t4.y; v[m][4 * k + 2] = t4.z; v[m][4 * k + 3] = t4.w;
+                }
+            } else {
+                const int2 *p2 = reinterpret_cast<const int2 *>(src + (size_t)q * 4 * NCH);   // 8 * NCH bytes: 8-byte aligned
+#pragma unroll
+                for (int k = 0; k < NCH; k++) {
+                    const int2 t2 = p2[k];
+                    v[m][2 * k] = t2.x; v[m][2 * k + 1] = t2.y;
+                }
             }
 #pragma unroll
-            for (int e = 0; e < 4 * NCH; e++) orv[e % NCH] |= (uint32_t)v[m][e];
+            for (int e = 0; e < 4 * NCH; e++) orv[e % NCH] |= (uint32_t)val(m, e);
         }
     }
 #pragma unroll
@@ -281,12 +358,30 @@ void k_prepare_multi_reg(const int32_t *__restrict__ pcm, int32_t *__restrict__ 
         if (q < quads) {
 #pragma unroll
             for (int c = 0; c < NCH; c++) {
-                const int4 o4 = make_int4(v[m][c] >> wasted[c], v[m][NCH + c] >> wasted[c],
-                                          v[m][2 * NCH + c] >> wasted[c], v[m][3 * NCH + c] >> wasted[c]);
+                const int4 o4 = make_int4(val(m, c) >> wasted[c], val(m, NCH + c) >> wasted[c],
+                                          val(m, 2 * NCH + c) >> wasted[c], val(m, 3 * NCH + c) >> wasted[c]);
                 *reinterpret_cast<int4 *>(smp + ((size_t)f * NCH + c) * n + 4 * q) = o4;
             }
         }
     }
+}
+
+template <int NCH, int M>
+__global__ __launch_bounds__(RT)
+void k_prepare_multi_reg(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp,
+                         fhip_subframe_info *__restrict__ info, int n, int bps,
+                         const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames)
+{
+    prepare_multi_reg_body<NCH, M>(pcm, smp, info, n, bps, frame_src, dev_frames);
+}
+
+template <int NCH, int M>
+__global__ __launch_bounds__(RT)
+void k_prepare_multi_reg_s16(const int16_t *__restrict__ pcm, int32_t *__restrict__ smp,
+                             fhip_subframe_info *__restrict__ info, int n, int bps,
+                             const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames)
+{
+    prepare_multi_reg_body<NCH, M>(pcm, smp, info, n, bps, frame_src, dev_frames);
 }
 
 // K0 fast path for stereo frames with n % 4 == 0 and n <= 8192: the frame never
@@ -303,13 +398,20 @@ void k_prepare_multi_reg(const int32_t *__restrict__ pcm, int32_t *__restrict__ 
 // that its 256 threads have quads to work on (n = 256: one wave per frame; at four
 // waves per frame three quarters of the threads idled and K0 took 5.7x its time per
 // sample).  Thread t of a frame owns quads t + 64 WPF m.
-template <int M, int WPF, bool APPLY>
+// int16 PCM (S = int16_t): a quad is ONE 16-byte load, (l0 r0 | l1 r1 | l2 r2 | l3 r3) with a sample-frame per word, and
+// the two sample-frames in front of it are the 8 bytes before.  The quads stay packed in registers -- four per quad
+// where the int32 body holds eight -- and every stage sign-extends the halves it needs (the decorrelation is then
+// done twice, for the ORs and for the stores: a few ALU operations per sample against half the registers held across
+// the two barriers); from there each stage is the int32 one (bps <= 16: always the estimate's 32-bit form).  Frames
+// start 16-byte aligned under the same condition, n % 4 == 0, and the thread-to-quad ownership is the same: 16 bytes
+// per lane, coalesced.
+template <int M, int WPF, bool APPLY, class S = int32_t>
 // allow_narrow: a channel whose samples (after the shift) all fit 16 bits is stored
 // as int16[n] at the start of its row (info.reserved = 1 tells K1's producers and
 // K3's staging; K3 resets the field) -- half the bytes written here and read there.
 // blk: the workgroup's index within its batch (or within its bin of a ragged batch).
 __device__ __forceinline__
-void prepare_stereo_body(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp,
+void prepare_stereo_body(const S *__restrict__ pcm, int32_t *__restrict__ smp,
                          fhip_subframe_info *__restrict__ info, int n, int bps, int estimate,
                          int allow_narrow, int nframes, const long long *__restrict__ frame_src, int blk)
 {
@@ -327,16 +429,33 @@ void prepare_stereo_body(const int32_t *__restrict__ pcm, int32_t *__restrict__ 
     const int4 *src = reinterpret_cast<const int4 *>(pcm + (frame_src ? (size_t)frame_src[f] : (size_t)f * n * 2));
     const int nquads = n >> 2;
 
-    int32_t L[M][4], R[M][4];
-    int4 prev[M];
+    constexpr bool S16 = sizeof(S) == 2;
+    // the thread's quads: int32 PCM as L / R (eight registers a quad, decorrelated in place); int16 PCM as loaded,
+    // raw = (l | r << 16) x 4 (four registers a quad).  The array the instance does not use has one unused row.
+    int32_t L[S16 ? 1 : M][4], R[S16 ? 1 : M][4];
+    int raw[S16 ? M : 1][4];
+    typename std::conditional<S16, int2, int4>::type prev[M];
+    auto prev_at = [&](int m) {
+        if constexpr (S16) return make_int4(s16_lo(prev[m].x), s16_hi(prev[m].x), s16_lo(prev[m].y), s16_hi(prev[m].y));
+        else return prev[m];
+    };
+    // sample-frame q of quad m
+    auto left_at = [&](int m, int q) { if constexpr (S16) return s16_lo(raw[m][q]); else return L[m][q]; };
+    auto right_at = [&](int m, int q) { if constexpr (S16) return s16_hi(raw[m][q]); else return R[m][q]; };
 #pragma unroll
     for (int m = 0; m < M; m++) {
         const int g = tid + TF * m;
         const int gc = min(g, nquads - 1);                 // clamped: loads stay unconditional
-        const int4 a = src[2 * gc], b = src[2 * gc + 1];   // (l0 r0 l1 r1) (l2 r2 l3 r3)
-        prev[m] = src[max(2 * gc - 1, 0)];                 // (l-2 r-2 l-1 r-1)
-        L[m][0] = a.x; R[m][0] = a.y; L[m][1] = a.z; R[m][1] = a.w;
-        L[m][2] = b.x; R[m][2] = b.y; L[m][3] = b.z; R[m][3] = b.w;
+        if constexpr (!S16) {
+            const int4 a = src[2 * gc], b = src[2 * gc + 1];   // (l0 r0 l1 r1) (l2 r2 l3 r3)
+            prev[m] = src[max(2 * gc - 1, 0)];                 // (l-2 r-2 l-1 r-1)
+            L[m][0] = a.x; R[m][0] = a.y; L[m][1] = a.z; R[m][1] = a.w;
+            L[m][2] = b.x; R[m][2] = b.y; L[m][3] = b.z; R[m][3] = b.w;
+        } else {
+            const int4 a = src[gc];                                                     // (l0 r0 | l1 r1 | l2 r2 | l3 r3)
+            prev[m] = reinterpret_cast<const int2 *>(src)[max(2 * gc - 1, 0)];          // (l-2 r-2 | l-1 r-1)
+            raw[m][0] = a.x; raw[m][1] = a.y; raw[m][2] = a.z; raw[m][3] = a.w;
+        }
     }
 
     int mode = FHIP_CH_LEFT_RIGHT;
@@ -351,10 +470,11 @@ void prepare_stereo_body(const int32_t *__restrict__ pcm, int32_t *__restrict__ 
             for (int m = 0; m < M; m++) {
                 const int g = tid + TF * m;
                 if (g < nquads) {
-                    int32_t l2 = prev[m].x, r2 = prev[m].y, l1 = prev[m].z, r1 = prev[m].w;
+                    const int4 pv = prev_at(m);
+                    int32_t l2 = pv.x, r2 = pv.y, l1 = pv.z, r1 = pv.w;
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
-                        const int32_t l0 = L[m][q], r0 = R[m][q];
+                        const int32_t l0 = left_at(m, q), r0 = right_at(m, q);
                         int32_t lt = l0 - 2 * l1 + l2;
                         int32_t rt = r0 - 2 * r1 + r2;
                         if (q < 2 && g == 0) { lt = 0; rt = 0; }        // no history for the first two (encode.c:607)
@@ -373,11 +493,12 @@ void prepare_stereo_body(const int32_t *__restrict__ pcm, int32_t *__restrict__ 
 #pragma unroll
         for (int m = 0; m < M; m++) {
             const int g = tid + TF * m;
-            uint32_t l2 = (uint32_t)prev[m].x, r2 = (uint32_t)prev[m].y;
-            uint32_t l1 = (uint32_t)prev[m].z, r1 = (uint32_t)prev[m].w;
+            const int4 pv = prev_at(m);
+            uint32_t l2 = (uint32_t)pv.x, r2 = (uint32_t)pv.y;
+            uint32_t l1 = (uint32_t)pv.z, r1 = (uint32_t)pv.w;
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-                const uint32_t l0 = (uint32_t)L[m][q], r0 = (uint32_t)R[m][q];
+                const uint32_t l0 = (uint32_t)left_at(m, q), r0 = (uint32_t)right_at(m, q);
                 const int32_t lt = (int32_t)(l0 - 2u * l1 + l2);
                 const int32_t rt = (int32_t)(r0 - 2u * r1 + r2);
                 const int32_t mm = (int32_t)((uint32_t)lt + (uint32_t)rt) >> 1;
@@ -428,17 +549,9 @@ void prepare_stereo_body(const int32_t *__restrict__ pcm, int32_t *__restrict__ 
         const bool on = (tid + TF * m) < nquads;
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            int32_t a = L[m][q], b = R[m][q];
-            if (mode == FHIP_CH_MID_SIDE) {
-                const int32_t mid = (int32_t)((uint32_t)a + (uint32_t)b) >> 1;
-                const int32_t sd = (int32_t)((uint32_t)a - (uint32_t)b);
-                a = mid; b = sd;
-            } else if (mode == FHIP_CH_LEFT_SIDE) {
-                b = (int32_t)((uint32_t)a - (uint32_t)b);
-            } else if (mode == FHIP_CH_RIGHT_SIDE) {
-                a = (int32_t)((uint32_t)a - (uint32_t)b);
-            }
-            L[m][q] = a; R[m][q] = b;
+            int32_t a = left_at(m, q), b = right_at(m, q);
+            decorrelate(a, b, mode);
+            if constexpr (!S16) { L[m][q] = a; R[m][q] = b; }
             or0 |= on ? (uint32_t)a : 0u;
             or1 |= on ? (uint32_t)b : 0u;
             mg0 |= on ? (uint32_t)(a ^ (a >> 31)) : 0u;
@@ -482,13 +595,30 @@ void prepare_stereo_body(const int32_t *__restrict__ pcm, int32_t *__restrict__ 
 #pragma unroll
     for (int m = 0; m < M; m++) {
         const int g = tid + TF * m;
-        if (APPLY && g < nquads && fvalid) {
-            const int4 vl = make_int4(L[m][0] >> wasted[0], L[m][1] >> wasted[0], L[m][2] >> wasted[0], L[m][3] >> wasted[0]);
-            const int4 vr = make_int4(R[m][0] >> wasted[1], R[m][1] >> wasted[1], R[m][2] >> wasted[1], R[m][3] >> wasted[1]);
-            if (narrow[0]) reinterpret_cast<int2 *>(dl)[g] = make_int2((vl.x & 0xFFFF) | (vl.y << 16), (vl.z & 0xFFFF) | (vl.w << 16));
-            else dl[g] = vl;
-            if (narrow[1]) reinterpret_cast<int2 *>(dr)[g] = make_int2((vr.x & 0xFFFF) | (vr.y << 16), (vr.z & 0xFFFF) | (vr.w << 16));
-            else dr[g] = vr;
+        if constexpr (S16) {
+            if (APPLY && g < nquads && fvalid) {
+                // the decorrelation once more, from the packed quad (encode.c:668-693)
+                int32_t a[4], b[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    a[q] = left_at(m, q); b[q] = right_at(m, q);
+                    decorrelate(a[q], b[q], mode);
+                    a[q] >>= wasted[0]; b[q] >>= wasted[1];
+                }
+                if (narrow[0]) reinterpret_cast<int2 *>(dl)[g] = make_int2((a[0] & 0xFFFF) | (a[1] << 16), (a[2] & 0xFFFF) | (a[3] << 16));
+                else dl[g] = make_int4(a[0], a[1], a[2], a[3]);
+                if (narrow[1]) reinterpret_cast<int2 *>(dr)[g] = make_int2((b[0] & 0xFFFF) | (b[1] << 16), (b[2] & 0xFFFF) | (b[3] << 16));
+                else dr[g] = make_int4(b[0], b[1], b[2], b[3]);
+            }
+        } else {
+            if (APPLY && g < nquads && fvalid) {
+                const int4 vl = make_int4(L[m][0] >> wasted[0], L[m][1] >> wasted[0], L[m][2] >> wasted[0], L[m][3] >> wasted[0]);
+                const int4 vr = make_int4(R[m][0] >> wasted[1], R[m][1] >> wasted[1], R[m][2] >> wasted[1], R[m][3] >> wasted[1]);
+                if (narrow[0]) reinterpret_cast<int2 *>(dl)[g] = make_int2((vl.x & 0xFFFF) | (vl.y << 16), (vl.z & 0xFFFF) | (vl.w << 16));
+                else dl[g] = vl;
+                if (narrow[1]) reinterpret_cast<int2 *>(dr)[g] = make_int2((vr.x & 0xFFFF) | (vr.y << 16), (vr.z & 0xFFFF) | (vr.w << 16));
+                else dr[g] = vr;
+            }
         }
     }
     if (tid < 2 && fvalid) {
@@ -640,6 +770,18 @@ void k_prepare_stereo(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp
                                        dev_count(dev_frames, nframes), frame_src, (int)blockIdx.x);
 }
 
+// The same from int16 PCM (always the applying form: the fused pipeline is int32 only).
+template <int M, int WPF>
+__global__ __launch_bounds__(NT)
+void k_prepare_stereo_s16(const int16_t *__restrict__ pcm, int32_t *__restrict__ smp,
+                          fhip_subframe_info *__restrict__ info, int n, int bps, int estimate,
+                          int allow_narrow, int nframes, const long long *__restrict__ frame_src,
+                          const int32_t *__restrict__ dev_frames)
+{
+    prepare_stereo_body<M, WPF, true>(pcm, smp, info, n, bps, estimate, allow_narrow,
+                                      dev_count(dev_frames, nframes), frame_src, (int)blockIdx.x);
+}
+
 // quads per thread M and waves per frame WPF of a stereo block of n samples (n % 4 == 0, n <= 8192): the
 // fullest threads win for short blocks.  One rule for the launcher and for the kernel of a ragged batch.
 #define FHIP_STEREO_GEOM(QUADS_, DO_)                                                       \
@@ -714,14 +856,24 @@ void k_prepare_stereo_bins(const int32_t *__restrict__ pcm, int32_t *__restrict_
 
 hipError_t launch_prepare(hipStream_t st, const fhip_params &p, const int32_t *pcm,
                           int nframes, int n, int32_t *smp, fhip_subframe_info *info, bool decide_only,
-                          bool allow_narrow, const long long *frame_src, const int32_t *dev_frames)
+                          bool allow_narrow, const long long *frame_src, const int32_t *dev_frames, int pcm_format)
 {
     const int nch = p.channels;
     if (nframes == 0) return hipSuccess;
+    const bool s16 = pcm_format == FHIP_PCM_S16;
+    if (s16 && (decide_only || p.bits_per_sample > 16)) return hipErrorInvalidValue;
+    const int16_t *pcm16 = reinterpret_cast<const int16_t *>(pcm);
     if (nch == 2 && (n & 3) == 0 && n <= 8192) {
         const int est = p.stereo_method == 1 ? 1 : 0;
         const int quads = n >> 2;
         const int nar = (allow_narrow && !decide_only) ? 1 : 0;
+        if (s16) {
+            // the same geometry rule as for int32 PCM
+#define LAUNCH_PS16(M_, W_) do { note_launch("k_prepare_stereo_s16<%d,%d>%s", M_, W_, nar ? " narrow" : ""); hipLaunchKernelGGL((k_prepare_stereo_s16<M_, W_>), dim3((nframes + 4 / W_ - 1) / (4 / W_)), dim3(NT), 0, st, pcm16, smp, info, n, p.bits_per_sample, est, nar, nframes, frame_src, dev_frames); } while (0)
+            FHIP_STEREO_GEOM(quads, LAUNCH_PS16);
+#undef LAUNCH_PS16
+            return hipGetLastError();
+        }
 #define LAUNCH_PS(M_, W_, A_) do { note_launch("k_prepare_stereo<%d,%d,%s>%s", M_, W_, tf(A_), nar ? " narrow" : ""); hipLaunchKernelGGL((k_prepare_stereo<M_, W_, A_>), dim3((nframes + 4 / W_ - 1) / (4 / W_)), dim3(NT), 0, st, pcm, smp, info, n, p.bits_per_sample, est, nar, nframes, frame_src, dev_frames); } while (0)
         if (decide_only) {
             if (quads <= NT) LAUNCH_PS(1, 4, false); else if (quads <= 2 * NT) LAUNCH_PS(2, 4, false); else LAUNCH_PS(4, 4, false);
@@ -739,7 +891,9 @@ hipError_t launch_prepare(hipStream_t st, const fhip_params &p, const int32_t *p
         if (!two_pass && (n & 3) == 0 && n <= 8192 && n >= 256) {
             // the frame in registers: one read of the PCM
 #define LAUNCH_MR(C_, M_) do { note_launch("k_prepare_multi_reg<%d,%d>", C_, M_); hipLaunchKernelGGL((k_prepare_multi_reg<C_, M_>), dim3(nframes), dim3(RT), 0, st, pcm, smp, info, n, p.bits_per_sample, frame_src, dev_frames); } while (0)
-#define LAUNCH_MRC(C_) do { if (n <= 4 * RT) LAUNCH_MR(C_, 1); else LAUNCH_MR(C_, 2); } while (0)
+#define LAUNCH_MR16(C_, M_) do { note_launch("k_prepare_multi_reg_s16<%d,%d>", C_, M_); hipLaunchKernelGGL((k_prepare_multi_reg_s16<C_, M_>), dim3(nframes), dim3(RT), 0, st, pcm16, smp, info, n, p.bits_per_sample, frame_src, dev_frames); } while (0)
+#define LAUNCH_MRC(C_) do { if (s16) { if (n <= 4 * RT) LAUNCH_MR16(C_, 1); else LAUNCH_MR16(C_, 2); } \
+                            else if (n <= 4 * RT) LAUNCH_MR(C_, 1); else LAUNCH_MR(C_, 2); } while (0)
             switch (nch) {
             case 1: LAUNCH_MRC(1); break;
             case 3: LAUNCH_MRC(3); break;
@@ -750,7 +904,14 @@ hipError_t launch_prepare(hipStream_t st, const fhip_params &p, const int32_t *p
             default: LAUNCH_MRC(8); break;
             }
 #undef LAUNCH_MRC
+#undef LAUNCH_MR16
 #undef LAUNCH_MR
+            return hipGetLastError();
+        }
+        if (s16) {
+            note_launch("k_prepare_multi_s16");
+            hipLaunchKernelGGL(k_prepare_multi_s16, dim3(nframes), dim3(NT), 0, st, pcm16, smp, info, n, nch,
+                               p.bits_per_sample, frame_src, dev_frames);
             return hipGetLastError();
         }
         note_launch("k_prepare_multi");
@@ -763,8 +924,23 @@ hipError_t launch_prepare(hipStream_t st, const fhip_params &p, const int32_t *p
     if (blocks == 0) return hipSuccess;
     if (lds > 150 * 1024) {
         // frames of more than ~19 k sample-frames: streamed from global memory
+        if (s16) {
+            note_launch("k_prepare_s16<false>");
+            hipLaunchKernelGGL(k_prepare_s16<false>, dim3(blocks), dim3(NT), 0, st, pcm16, smp, info, n, nch,
+                               p.bits_per_sample, p.stereo_method == 1 ? 1 : 0, frame_src, dev_frames);
+            return hipGetLastError();
+        }
         note_launch("k_prepare<false>");
         hipLaunchKernelGGL(k_prepare<false>, dim3(blocks), dim3(NT), 0, st, pcm, smp, info, n, nch,
+                           p.bits_per_sample, p.stereo_method == 1 ? 1 : 0, frame_src, dev_frames);
+        return hipGetLastError();
+    }
+    if (s16) {
+        hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_prepare_s16<true>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (er != hipSuccess) return er;
+        note_launch("k_prepare_s16<true>");
+        hipLaunchKernelGGL(k_prepare_s16<true>, dim3(blocks), dim3(NT), lds, st, pcm16, smp, info, n, nch,
                            p.bits_per_sample, p.stereo_method == 1 ? 1 : 0, frame_src, dev_frames);
         return hipGetLastError();
     }

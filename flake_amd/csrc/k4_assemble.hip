@@ -145,19 +145,25 @@ __device__ __forceinline__ uint32_t crc16_unshift_bytes(uint32_t crc, int e)
     return (e & 8) ? m3 : crc;
 }
 
-__device__ __forceinline__ int32_t asm_sample(const int32_t *pcm_frame, int nch, int ch, int t,
+// value i of the frame's interleaved PCM at the handle's width (s16: the frame holds int16, fhip_set_pcm_format)
+__device__ __forceinline__ int32_t asm_pcm(const void *pcm_frame, int s16, size_t i)
+{
+    return s16 ? (int32_t)static_cast<const int16_t *>(pcm_frame)[i] : static_cast<const int32_t *>(pcm_frame)[i];
+}
+
+__device__ __forceinline__ int32_t asm_sample(const void *pcm_frame, int s16, int nch, int ch, int t,
                                              int ch_mode, int wasted)
 {
     // FlacSubframe.samples recomputed (encode.c:648-694, :558-593)
     int32_t v;
     if (nch == 2 && ch_mode != FHIP_CH_LEFT_RIGHT) {
-        const int32_t l = pcm_frame[2 * t], r = pcm_frame[2 * t + 1];
+        const int32_t l = asm_pcm(pcm_frame, s16, 2 * (size_t)t), r = asm_pcm(pcm_frame, s16, 2 * (size_t)t + 1);
         const int32_t side = (int32_t)((uint32_t)l - (uint32_t)r);
         if (ch_mode == FHIP_CH_MID_SIDE) v = ch ? side : ((int32_t)((uint32_t)l + (uint32_t)r) >> 1);
         else if (ch_mode == FHIP_CH_LEFT_SIDE) v = ch ? side : l;
         else v = ch ? r : side;
     } else {
-        v = pcm_frame[(size_t)t * nch + ch];
+        v = asm_pcm(pcm_frame, s16, (size_t)t * nch + ch);
     }
     return v >> wasted;
 }
@@ -179,7 +185,8 @@ void k_assemble(fhip_params P, int n, const int32_t *__restrict__ pcm,
                 int32_t *__restrict__ frame_bytes, uint32_t number_base, uint32_t number_step,
                 const uint32_t *__restrict__ numbers,
                 int sr_code0, int sr_code1, int bps_code, int verbatim_size,
-                const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames, MultiBin mb)
+                const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames, int pcm_s16,
+                MultiBin mb)
 {
     if (dev_frames && (int)blockIdx.x >= dev_count(dev_frames, 0)) return;      // (a ragged batch's grid is its bin's capacity)
     int f = blockIdx.x;
@@ -209,7 +216,10 @@ void k_assemble(fhip_params P, int n, const int32_t *__restrict__ pcm,
     const int lane = threadIdx.x;
     const int nch = P.channels;
     const fhip_subframe_info *fi = info + (size_t)f * nch;
-    const int32_t *pcm_frame = pcm + (frame_src ? (size_t)frame_src[f] : (size_t)f * n * nch);
+    // (frame_src and the frame's offset count samples of the handle's width)
+    const size_t pcm_off = frame_src ? (size_t)frame_src[f] : (size_t)f * n * nch;
+    const void *pcm_frame = pcm_s16 ? static_cast<const void *>(reinterpret_cast<const int16_t *>(pcm) + pcm_off)
+                                    : static_cast<const void *>(pcm + pcm_off);
     uint8_t *out = frames + (size_t)f * frame_stride;
     uint32_t *out32 = reinterpret_cast<uint32_t *>(out);
     STAMP(0);
@@ -384,7 +394,7 @@ void k_assemble(fhip_params P, int n, const int32_t *__restrict__ pcm,
                 int i = sp / ob, offb = sp % ob, got = 0;
                 unsigned long long acc = 0;
                 while (got < cnt) {
-                    const uint32_t v = (uint32_t)asm_sample(pcm_frame, nch, c, i, cm, ws) & omask;
+                    const uint32_t v = (uint32_t)asm_sample(pcm_frame, pcm_s16, nch, c, i, cm, ws) & omask;
                     const int take = min(ob - offb, cnt - got);
                     const uint32_t piece = (take >= 32) ? v : ((v >> (ob - offb - take)) & ((1u << take) - 1u));
                     acc = (acc << take) | piece;
@@ -626,7 +636,8 @@ hipError_t launch_assemble(hipStream_t st, const fhip_params &p, const int32_t *
                            int n, const fhip_subframe_info *info, const uint8_t *rice,
                            int64_t slot_bytes, uint8_t *frames, int64_t frame_stride,
                            int32_t *frame_bytes, uint32_t number_base, uint32_t number_step,
-                           const uint32_t *numbers, const long long *frame_src, const int32_t *dev_frames)
+                           const uint32_t *numbers, const long long *frame_src, const int32_t *dev_frames,
+                           int pcm_format)
 {
     if (nframes == 0) return hipSuccess;
     // sample-rate / bit-depth codes of flake_encode_init() (encode.c:400-438)
@@ -648,7 +659,8 @@ hipError_t launch_assemble(hipStream_t st, const fhip_params &p, const int32_t *
     note_launch("k_assemble");
     hipLaunchKernelGGL(k_assemble, dim3(nframes), dim3(AT), 0, st, p, n, pcm, info, rice,
                        (long long)slot_bytes, frames, (long long)frame_stride, frame_bytes,
-                       number_base, number_step, numbers, sr0, sr1, bpsc, vsize, frame_src, dev_frames, MultiBin{});
+                       number_base, number_step, numbers, sr0, sr1, bpsc, vsize, frame_src, dev_frames,
+                       pcm_format == FHIP_PCM_S16 ? 1 : 0, MultiBin{});
     return hipGetLastError();
 }
 
@@ -673,7 +685,7 @@ hipError_t launch_assemble_bins(hipStream_t st, const fhip_params &p, const Mult
     for (int i = 1; i < 8; i++) if (p.bits_per_sample == bd_table[i]) { bpsc = i; break; }
     note_launch("k_assemble bins");
     hipLaunchKernelGGL(k_assemble, dim3(slots), dim3(AT), 0, st, p, 0, pcm, info, rice, 0ll, frames, 0ll,
-                       frame_bytes, 0u, 0u, numbers, sr0, sr1, bpsc, 0, frame_src, (const int32_t *)nullptr, mb);
+                       frame_bytes, 0u, 0u, numbers, sr0, sr1, bpsc, 0, frame_src, (const int32_t *)nullptr, 0, mb);
     return hipGetLastError();
 }
 

@@ -365,6 +365,8 @@ struct SubHdr {
 __device__ __forceinline__ long long pcm_at(const VerifyArgs &a, long long g, int c)
 {
     if (g < 0 || g >= a.nsamples) return 0;          // (pass 1 keeps every frame inside [0, nsamples))
+    // the caller's PCM at the handle's width (fhip_set_pcm_format)
+    if (a.pcm_format == FHIP_PCM_S16) return (long long)reinterpret_cast<const int16_t *>(a.pcm)[g * a.channels + c];
     return (long long)a.pcm[g * a.channels + c];
 }
 

@@ -36,10 +36,13 @@ struct EncodeArgs {
 // dev_frames / dev_sub (optional, every launch_* below): the launch's real frame / subframe count
 // lives on the device; nframes / nsub then size the grid (the bin's capacity) and workgroups past
 // the count leave at once (device_util.h: dev_count).
+// pcm_format (FHIP_PCM_*): with FHIP_PCM_S16, pcm addresses interleaved int16 (the k_*_s16 instances; bits_per_sample
+// <= 16, no decide_only) and frame_src counts int16 units.  K4 and K5 take the format the same way.
 hipError_t launch_prepare(hipStream_t st, const fhip_params &p, const int32_t *pcm,
                           int nframes, int n, int32_t *smp, fhip_subframe_info *info,
                           bool decide_only = false, bool allow_narrow = false,
-                          const long long *frame_src = nullptr, const int32_t *dev_frames = nullptr);
+                          const long long *frame_src = nullptr, const int32_t *dev_frames = nullptr,
+                          int pcm_format = FHIP_PCM_S32);
 
 // True when K0, K1 and K3 all handle 16-bit sample rows for such a batch; the
 // caller then passes allow_narrow / narrow_ok to the three launches of the batch.
@@ -127,7 +130,7 @@ hipError_t launch_assemble(hipStream_t st, const fhip_params &p, const int32_t *
                            int64_t slot_bytes, uint8_t *frames, int64_t frame_stride,
                            int32_t *frame_bytes, uint32_t number_base, uint32_t number_step,
                            const uint32_t *numbers = nullptr, const long long *frame_src = nullptr,
-                           const int32_t *dev_frames = nullptr);
+                           const int32_t *dev_frames = nullptr, int pcm_format = FHIP_PCM_S32);
 
 // K4-P: offsets[f] = exclusive scan of frame_bytes (offsets[nframes] = total) and the frames
 // copied back to back into packed[] -- the stream order flake_encode_frame's callers write.
@@ -229,6 +232,7 @@ struct VerifyArgs {
     const long long *dev_count;                  // optional: the real frame count lives on the device
     const int32_t *pcm; long long nsamples; long long first_sample;
     int channels, bps, block_size, sample_rate, allow_vbs;
+    int pcm_format;                              // FHIP_PCM_*: S16 = pcm addresses int16
     VerifyFrame *ws;                             // [nframes]
     fhip_verify_rec *recs;                       // optional [nframes]
     long long *summary;                          // [4]

@@ -53,8 +53,9 @@ static int wav_open(wav_t *w, const char *path)
     return -1;
 }
 
-/* up to `frames` sample-frames as interleaved int32, sign-extended (pcm_io.c:155-277) */
-static uint32_t wav_read(wav_t *w, int32_t *dst, uint32_t frames)
+/* up to `frames` sample-frames, sign-extended (pcm_io.c:155-277): interleaved int32 into dst, or -- dst16 given, files
+ * of 16 bits per sample or fewer -- interleaved int16 into dst16 */
+static uint32_t wav_read(wav_t *w, int32_t *dst, int16_t *dst16, uint32_t frames)
 {
     const int bytes = (w->bps + 7) / 8;
     const size_t want = (size_t)frames * w->channels;
@@ -67,7 +68,7 @@ static uint32_t wav_read(wav_t *w, int32_t *dst, uint32_t frames)
         else if (bytes == 2) v = (int16_t)rd16(p);
         else if (bytes == 3) v = (int32_t)((uint32_t)p[0] << 8 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 24) >> 8;
         else v = (int32_t)rd32(p);
-        dst[i] = v;
+        if (dst16) dst16[i] = (int16_t)v; else dst[i] = v;
     }
     free(raw);
     return (uint32_t)(got / w->channels);
@@ -115,6 +116,14 @@ int main(int argc, char **argv)
 
     const int bs = s.params.block_size, nch = s.channels, batch = 256;
     int32_t *pcm = (int32_t *)malloc(sizeof(int32_t) * (size_t)batch * bs * nch);
+    /* 16 bits per sample or fewer at a level without variable block size: the samples stay int16 all the way
+     * (flake_amd_encode_frames_s16); everything else is widened to int32 as before -- also under the CPU comparison
+     * modes FLAKE_AMD_HOST_ASSEMBLY=1 / FLAKE_AMD_HOST_VBS=1, which the int16 entry refuses */
+    const char *eha = getenv("FLAKE_AMD_HOST_ASSEMBLY"), *ehv = getenv("FLAKE_AMD_HOST_VBS");
+    const int cpu_mode = (eha && eha[0] == '1') || (ehv && ehv[0] == '1');
+    const int narrow = s.bits_per_sample <= 16 && !s.params.variable_block_size && !cpu_mode;
+    int16_t *pcm16 = narrow ? (int16_t *)malloc(sizeof(int16_t) * (size_t)batch * bs * nch) : NULL;
+    if (!pcm || (narrow && !pcm16)) { fprintf(stderr, "out of memory\n"); return 1; }
     const size_t cap = (size_t)batch * bs * nch * 5 + 65536;
     uint8_t *buf = (uint8_t *)malloc(cap);
     uint64_t total_in = 0, total_out = (uint64_t)hlen;
@@ -127,12 +136,14 @@ int main(int argc, char **argv)
             flake_amd_synth_pcm(pcm, synth_pos, nb, bs, nch, s.bits_per_sample);
             synth_pos += nb; synth_left -= nb;
             frames = (uint32_t)nb * (uint32_t)bs;
+            if (narrow) for (size_t i = 0; i < (size_t)frames * nch; i++) pcm16[i] = (int16_t)pcm[i];
         } else {
-            frames = wav_read(&w, pcm, (uint32_t)batch * (uint32_t)bs);
+            frames = wav_read(&w, pcm, pcm16, (uint32_t)batch * (uint32_t)bs);
             if (!frames) break;
         }
         const int nblocks = (int)(frames / (uint32_t)bs), tail = (int)(frames % (uint32_t)bs);
-        long long n = flake_amd_encode_frames(&s, pcm, nblocks, bs, tail, buf, cap, NULL);   /* flake.c:633 */
+        long long n = narrow ? flake_amd_encode_frames_s16(&s, pcm16, nblocks, bs, tail, buf, cap, NULL)
+                             : flake_amd_encode_frames(&s, pcm, nblocks, bs, tail, buf, cap, NULL);   /* flake.c:633 */
         if (n < 0) { fprintf(stderr, "encode error: %s\n", flake_amd_last_error(&s)); return 1; }
         fwrite(buf, 1, (size_t)n, fo);
         total_in += frames; total_out += (uint64_t)n;
@@ -153,6 +164,6 @@ int main(int argc, char **argv)
             (unsigned long long)total_out,
             total_in ? (double)total_out / ((double)total_in * nch * ((s.bits_per_sample + 7) / 8)) : 0.0);
     flake_amd_encode_close(&s);
-    free(pcm); free(buf);
+    free(pcm); free(pcm16); free(buf);
     return 0;
 }

@@ -51,6 +51,7 @@ typedef struct host_ctx {
     int md5_off;                          /* FLAKE_AMD_MD5=0: STREAMINFO carries the all-zero "not computed" MD5 */
     int trace;                            /* FLAKE_AMD_TRACE=1: phase times of every batch on stderr */
     int verify;                           /* flake_amd_set_verify: every batch's frames checked on the device */
+    int pcm_format;                       /* FHIP_PCM_*: what the handles currently take (flake_amd_encode_frames_s16) */
     /* FLAKE_AMD_LOOKAHEAD=N: flake_encode_frame() queues up to N whole blocks and
      * encodes them as one GPU batch (see flake_amd_encode_frame) */
     int lookahead;
@@ -619,7 +620,8 @@ static int vbs_split(const int32_t *pcm, int channels, int block_size, int sizes
 /* ------------------------------------------------------------------ */
 /* batches                                                            */
 /* ------------------------------------------------------------------ */
-typedef struct { const int32_t *pcm; int n; int block; } piece;       /* one FLAC frame to make */
+typedef struct { const char *pcm; int n; int block; } piece;          /* one FLAC frame to make (pcm: samples of the
+                                                                         call's width, 4 or 2 bytes) */
 
 static int run_gpu(host_ctx *c, const int32_t *pcm, int nframes, int n, size_t first_sub,
                    size_t first_frame)
@@ -655,11 +657,12 @@ static double now_ms(void)
 /* encode.c:1006 md5_accumulate over the batch's input, on a helper thread: the
  * hash is sequential over the whole stream (~0.5 GB/s) and would otherwise sit
  * behind every GPU batch. */
-typedef struct { fa_md5 *m; const int32_t *pcm; size_t nvalues; int bps; } md5_job;
+typedef struct { fa_md5 *m; const void *pcm; size_t nvalues; int bps; int width; } md5_job;
 static void *md5_worker(void *arg)
 {
     md5_job *j = (md5_job *)arg;
-    fa_md5_pcm(j->m, j->pcm, j->nvalues, j->bps);
+    if (j->width == 2) fa_md5_pcm16(j->m, (const int16_t *)j->pcm, j->nvalues, j->bps);
+    else fa_md5_pcm(j->m, (const int32_t *)j->pcm, j->nvalues, j->bps);
     return NULL;
 }
 
@@ -678,7 +681,8 @@ typedef struct {
     host_ctx *c;
     fhip_ctx *h;
     chunk_sync *sy;
-    const int32_t *pcm;
+    const char *pcm;
+    size_t width;                         /* bytes per sample of pcm */
     int n, nch, np, chunk, first, nchunks;
     int split_last, all_chunks;           /* the last full-size chunk runs as two halves (chunks all_chunks-2, all_chunks-1) */
     uint8_t *out;
@@ -701,7 +705,7 @@ static void *chunk_worker(void *arg)
         }
         fhip_batch b;
         memset(&b, 0, sizeof b);
-        b.pcm = j->pcm + (size_t)f0 * (size_t)j->n * (size_t)j->nch;
+        b.pcm = (const int32_t *)(j->pcm + (size_t)f0 * (size_t)j->n * (size_t)j->nch * j->width);
         b.nframes = nf; b.block_size = j->n;
         b.frame_bytes = c->fbytes + f0;
         b.frame_numbers = c->fnum + f0;
@@ -761,7 +765,8 @@ static void *chunk_worker(void *arg)
 }
 
 /* returns bytes written, or -1 */
-static long long run_chunked(host_ctx *c, const int32_t *pcm, int np, int n, int nch, uint8_t *out, size_t cap)
+static long long run_chunked(host_ctx *c, const char *pcm, size_t width, int np, int n, int nch, uint8_t *out,
+                             size_t cap)
 {
     const int chunk = c->chunk_frames;
     int nchunks = (np + chunk - 1) / chunk;
@@ -777,7 +782,7 @@ static long long run_chunked(host_ctx *c, const int32_t *pcm, int np, int n, int
     pthread_mutex_init(&sy.mu, NULL);
     pthread_cond_init(&sy.cv, NULL);
     sy.end = end; sy.failed = 0; sy.upload_turn = 0; sy.t0 = now_ms();
-    chunk_job ja = { c, c->hip, &sy, pcm, n, nch, np, chunk, 0, nchunks, split_last, nchunks, out, (long long)cap, FHIP_OK };
+    chunk_job ja = { c, c->hip, &sy, pcm, width, n, nch, np, chunk, 0, nchunks, split_last, nchunks, out, (long long)cap, FHIP_OK };
     chunk_job jb = ja;
     jb.h = c->hip2; jb.first = 1;
     pthread_t tb;
@@ -804,12 +809,14 @@ static long long run_chunked(host_ctx *c, const int32_t *pcm, int np, int n, int
     return total;
 }
 
-/* Encode `count` blocks starting at pcm (each block_size samples/channel). */
-static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const int32_t *pcm, int count,
+/* Encode `count` blocks starting at pcm_any (each block_size samples/channel; samples of `width` bytes: int32, or
+ * int16 -- then always a uniform batch, the handles' format set by the caller). */
+static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const void *pcm_any, size_t width, int count,
                               int block_size, uint8_t *out, size_t cap, int *frame_sizes)
 {
     const int nch = c->hp.channels;
     const size_t bstride = (size_t)block_size * nch;
+    const int32_t *pcm = (const int32_t *)pcm_any;                 /* the int32-only paths below (width == 4) */
     const int vbs = s->params.variable_block_size > 0 && (block_size % VBS_PARTS) == 0 &&
                     block_size >= VBS_PARTS * MIN_BLOCK;           /* encode.c:997-999 */
     piece *pieces = (piece *)malloc(sizeof(piece) * (size_t)count * VBS_PARTS);
@@ -817,7 +824,7 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const int32_t *pc
     if (!pieces || !scratch) { free(pieces); free(scratch); return -1; }
     /* hash a copy of the state; it is committed only if the batch succeeds */
     fa_md5 md5_next = c->md5;
-    md5_job job = { &md5_next, pcm, (size_t)count * bstride, c->hp.bits_per_sample };
+    md5_job job = { &md5_next, pcm_any, (size_t)count * bstride, c->hp.bits_per_sample, (int)width };
     pthread_t md5_thread;
     int md5_running = 0, md5_done = 0;
     if (!c->md5_off) md5_running = pthread_create(&md5_thread, NULL, md5_worker, &job) == 0;
@@ -845,7 +852,7 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const int32_t *pc
         if (mx > c->max_frame_size) c->max_frame_size = mx;        /* encode.c:967 */
         c->frame_count = next;                                     /* encode.c:969-975 */
         if (c->trace)
-            fprintf(stderr, "flake_amd batch: %d vbs blocks on the device, %.2f ms\n", count, now_ms() - t_begin);
+            fprintf(stderr, "flake_amd batch: %d vbs blocks on the device, %.2f ms, int32 samples\n", count, now_ms() - t_begin);
         if (!c->md5_off) {
             if (md5_running) { pthread_join(md5_thread, NULL); md5_running = 0; }
             else md5_worker(&job);
@@ -879,7 +886,7 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const int32_t *pc
         }
         int pos = 0;
         for (int f = 0; f < nf; f++) {
-            pieces[np].pcm = pcm + b * bstride + (size_t)pos * nch;
+            pieces[np].pcm = (const char *)pcm_any + (b * bstride + (size_t)pos * nch) * width;
             pieces[np].n = sizes[f];
             pieces[np].block = b;
             pos += sizes[f];
@@ -906,12 +913,12 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const int32_t *pc
         int uniform = !c->host_assembly && np > 0;
         for (int i = 1; i < np && uniform; i++)
             uniform = pieces[i].n == pieces[0].n &&
-                      pieces[i].pcm == pieces[0].pcm + (size_t)i * (size_t)pieces[0].n * nch;
+                      pieces[i].pcm == pieces[0].pcm + (size_t)i * (size_t)pieces[0].n * nch * width;
         if (uniform) {
             const double tg0 = now_ms();
             fhip_batch b;
             memset(&b, 0, sizeof b);
-            b.pcm = pieces[0].pcm; b.nframes = np; b.block_size = pieces[0].n;
+            b.pcm = (const int32_t *)pieces[0].pcm; b.nframes = np; b.block_size = pieces[0].n;
             b.frame_bytes = c->fbytes;
             for (int i = 0; i < np; i++) c->fnum[i] = num_of[i];
             b.frame_numbers = c->fnum;
@@ -925,10 +932,14 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const int32_t *pc
                 hp2.variable_block_size = 0;
                 c->hip2_state = (fhip_create(&c->hip2, c->device, &hp2, c->chunk_frames) == FHIP_OK) ? 1 : -1;
                 if (c->hip2_state > 0) (void)fhip_set_verify(c->hip2, c->verify);
+                if (c->hip2_state > 0 && fhip_set_pcm_format(c->hip2, c->pcm_format) != FHIP_OK) {
+                    fhip_destroy(c->hip2);
+                    c->hip2 = NULL; c->hip2_state = -1;
+                }
             }
             if (c->hip2_state < 0) c->hip2 = NULL;                 /* fine: one handle, one pass */
             if (c->hip2 && c->chunk_frames > 0 && np >= 2 * c->chunk_frames) {
-                wrote = run_chunked(c, pieces[0].pcm, np, pieces[0].n, nch, out, cap);
+                wrote = run_chunked(c, pieces[0].pcm, width, np, pieces[0].n, nch, out, cap);
                 if (wrote < 0) goto out;
             } else {
                 const int rc = fhip_encode_frames_packed(c->hip, &b, out, (int64_t)cap, &wrote);
@@ -954,6 +965,10 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const int32_t *pc
             goto hashed;
         }
     }
+    if (width != sizeof(int32_t)) {        /* (the paths below gather and assemble int32 samples) */
+        snprintf(c->err, sizeof c->err, "int16 samples need a uniform batch on the device");
+        goto out;
+    }
     {
         int next_slot = 0;
         for (int i = 0; i < np; i++) {
@@ -961,10 +976,10 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const int32_t *pc
             const int n = pieces[i].n;
             /* gather all pieces of this length */
             int cnt = 0, contiguous = 1;
-            const int32_t *base = pieces[i].pcm;
+            const int32_t *base = (const int32_t *)pieces[i].pcm;
             for (int j = i; j < np; j++) {
                 if (done[j] || pieces[j].n != n) continue;
-                if (pieces[j].pcm != base + (size_t)cnt * n * nch) contiguous = 0;
+                if ((const int32_t *)pieces[j].pcm != base + (size_t)cnt * n * nch) contiguous = 0;
                 cnt++;
             }
             const int32_t *src = base;
@@ -1008,7 +1023,7 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const int32_t *pc
             int fs;
             if (c->host_assembly) {
                 const size_t sub = (size_t)slot_of[i] * nch;
-                fs = assemble_frame(c, c->frame_count, pieces[i].pcm, pieces[i].n,
+                fs = assemble_frame(c, c->frame_count, (const int32_t *)pieces[i].pcm, pieces[i].n,
                                     c->info + sub, c->bits + sub * (size_t)c->slot,
                                     out + pos, cap - pos, scratch);
             } else {
@@ -1048,8 +1063,8 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const int32_t *pc
 hashed:
     if (c->trace)
         fprintf(stderr, "flake_amd batch: %d blocks -> %d frames in %d size groups; split %.2f ms, gather %.2f, "
-                        "gpu (H2D + kernels + D2H) %.2f, copy-out %.2f\n", count, np, ngroups, t_split, t_gather,
-                t_gpu, t_out);
+                        "gpu (H2D + kernels + D2H) %.2f, copy-out %.2f, int%d samples\n", count, np, ngroups, t_split, t_gather,
+                t_gpu, t_out, (int)(8 * width));
     if (!c->md5_off) {
         if (md5_running) { pthread_join(md5_thread, NULL); md5_running = 0; }
         else md5_worker(&job);                         /* no thread: hash here */
@@ -1063,13 +1078,36 @@ out:
     return total;
 }
 
-FLAKE_AMD_API long long flake_amd_encode_frames(FlakeAmdContext *s, const int *samples, int nblocks,
-                                                int block_size, int tail_size, unsigned char *out,
-                                                size_t out_size, int *frame_sizes)
+/* The handles take the samples of this call's width (both, once the second exists). */
+static int set_pcm_format(host_ctx *c, int format)
+{
+    if (c->pcm_format == format) return 0;
+    int rc = fhip_set_pcm_format(c->hip, format);
+    if (rc == FHIP_OK && c->hip2) rc = fhip_set_pcm_format(c->hip2, format);
+    if (rc != FHIP_OK) {
+        snprintf(c->err, sizeof c->err, "fhip_set_pcm_format: %s (%s)", fhip_strerror(rc), fhip_last_error(c->hip));
+        return -1;
+    }
+    c->pcm_format = format;
+    return 0;
+}
+
+/* flake_amd_encode_frames() and flake_amd_encode_frames_s16(): one path, `width` bytes per sample */
+static long long encode_frames_any(FlakeAmdContext *s, const void *samples, size_t width, int nblocks,
+                                   int block_size, int tail_size, unsigned char *out,
+                                   size_t out_size, int *frame_sizes)
 {
     if (!s || !samples || !s->private_ctx || !out) return -1;
     host_ctx *c = (host_ctx *)s->private_ctx;
     c->err[0] = 0;
+    if (width == sizeof(int16_t)) {
+        const char *why = NULL;
+        if (s->bits_per_sample > 16) why = "int16 samples need bits_per_sample <= 16";
+        else if (s->params.variable_block_size) why = "int16 samples are not supported with variable block size (levels 9-12)";
+        else if (c->host_assembly || c->host_vbs)
+            why = "int16 samples are not supported with FLAKE_AMD_HOST_ASSEMBLY / FLAKE_AMD_HOST_VBS (CPU comparison modes)";
+        if (why) { snprintf(c->err, sizeof c->err, "flake_amd_encode_frames_s16: %s", why); return -1; }
+    }
     if (nblocks < 0 || block_size < 1 || block_size > s->params.block_size) return -1;   /* encode.c:987 */
     if (tail_size < 0 || tail_size >= block_size + (nblocks == 0)) return -1;
     if (c->last_frame) return -1;                                                        /* encode.c:989 */
@@ -1078,11 +1116,12 @@ FLAKE_AMD_API long long flake_amd_encode_frames(FlakeAmdContext *s, const int *s
         if (nblocks > 1 || tail_size) return -1;
         c->last_frame = 1;
     }
-    const size_t bstride = (size_t)block_size * (size_t)s->channels;
+    if (set_pcm_format(c, width == sizeof(int16_t) ? FHIP_PCM_S16 : FHIP_PCM_S32)) return -1;
+    const size_t bstride = (size_t)block_size * (size_t)s->channels * width;      /* bytes */
     long long total = 0;
     for (int b0 = 0; b0 < nblocks; b0 += c->max_batch) {
         const int cnt = (nblocks - b0 < c->max_batch) ? nblocks - b0 : c->max_batch;
-        long long w = encode_batch(s, c, (const int32_t *)samples + (size_t)b0 * bstride, cnt, block_size,
+        long long w = encode_batch(s, c, (const char *)samples + (size_t)b0 * bstride, width, cnt, block_size,
                                    out + total, out_size - (size_t)total,
                                    frame_sizes ? frame_sizes + b0 : NULL);
         if (w < 0) return -1;
@@ -1090,13 +1129,27 @@ FLAKE_AMD_API long long flake_amd_encode_frames(FlakeAmdContext *s, const int *s
     }
     if (tail_size > 0) {
         if (!s->params.allow_vbs) c->last_frame = 1;
-        long long w = encode_batch(s, c, (const int32_t *)samples + (size_t)nblocks * bstride, 1, tail_size,
+        long long w = encode_batch(s, c, (const char *)samples + (size_t)nblocks * bstride, width, 1, tail_size,
                                    out + total, out_size - (size_t)total,
                                    frame_sizes ? frame_sizes + nblocks : NULL);
         if (w < 0) return -1;
         total += w;
     }
     return total;
+}
+
+FLAKE_AMD_API long long flake_amd_encode_frames(FlakeAmdContext *s, const int *samples, int nblocks,
+                                                int block_size, int tail_size, unsigned char *out,
+                                                size_t out_size, int *frame_sizes)
+{
+    return encode_frames_any(s, samples, sizeof(int32_t), nblocks, block_size, tail_size, out, out_size, frame_sizes);
+}
+
+FLAKE_AMD_API long long flake_amd_encode_frames_s16(FlakeAmdContext *s, const int16_t *samples, int nblocks,
+                                                    int block_size, int tail_size, unsigned char *out,
+                                                    size_t out_size, int *frame_sizes)
+{
+    return encode_frames_any(s, samples, sizeof(int16_t), nblocks, block_size, tail_size, out, out_size, frame_sizes);
 }
 
 /* Page-lock the caller's batch buffers in place (either may be NULL: left as it is; bytes = 0 releases).

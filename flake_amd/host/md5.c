@@ -125,3 +125,28 @@ void fa_md5_pcm(fa_md5 *m, const int32_t *pcm, size_t nvalues, int bps)
     }
     if (k) fa_md5_update(m, tmp, k);
 }
+
+/* The same over int16 samples (flake_amd_encode_frames_s16).  With 9..16 bits per sample the caller's buffer already
+ * is the image md5.c:281-320 hashes -- two little-endian bytes per sample -- on a little-endian host; with 8 bits or
+ * fewer it is one byte per sample, as above. */
+void fa_md5_pcm16(fa_md5 *m, const int16_t *pcm, size_t nvalues, int bps)
+{
+    const uint16_t probe = 1;
+    if (bps > 8 && *(const uint8_t *)&probe == 1) {
+        fa_md5_update(m, (const uint8_t *)pcm, 2 * nvalues);
+        return;
+    }
+    uint8_t tmp[16384];
+    const int bpsamp = (bps + 7) >> 3;               /* 1 or 2 */
+    for (size_t i = 0; i < nvalues;) {
+        const size_t cnt = (nvalues - i < 8192) ? nvalues - i : 8192;
+        size_t k = 0;
+        for (size_t j = 0; j < cnt; j++) {
+            const uint16_t x = (uint16_t)pcm[i + j];
+            tmp[k++] = (uint8_t)x;
+            if (bpsamp == 2) tmp[k++] = (uint8_t)(x >> 8);
+        }
+        fa_md5_update(m, tmp, k);
+        i += cnt;
+    }
+}

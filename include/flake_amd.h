@@ -95,6 +95,22 @@ FLAKE_AMD_API long long flake_amd_encode_frames(FlakeAmdContext *s, const int *s
                                                 int nblocks, int block_size, int tail_size,
                                                 unsigned char *out, size_t out_size,
                                                 int *frame_sizes);
+/*
+ * The same call for a caller that holds 16-bit (or narrower) audio as channel-interleaved int16_t -- what a 16-bit
+ * WAV file holds: the samples cross the link and are read on the device at 2 bytes each instead of being widened
+ * to int32 on the CPU first.  Semantics, return values and the stream's bookkeeping (frame counter, min / max frame
+ * size, the last-block latch, the MD5 -- hashed straight from the caller's buffer) are those of
+ * flake_amd_encode_frames(), and the bytes written are identical to what that call writes for the widened samples;
+ * calls of the two widths may be mixed on one stream.  Each value is sign-extended to int32 (with bits_per_sample
+ * < 16 it must lie in that range, as the int32 contract says).  Returns -1, with flake_amd_last_error() saying why,
+ * when bits_per_sample > 16, when the context uses variable block size (levels 9-12), or under the CPU comparison
+ * modes FLAKE_AMD_HOST_ASSEMBLY=1 / FLAKE_AMD_HOST_VBS=1.  flake_amd_pin_buffers() takes the int16 buffer as it
+ * is (a byte range).  flake_amd_encode_frame() and its look-ahead queue stay int32.
+ */
+FLAKE_AMD_API long long flake_amd_encode_frames_s16(FlakeAmdContext *s, const int16_t *samples,
+                                                    int nblocks, int block_size, int tail_size,
+                                                    unsigned char *out, size_t out_size,
+                                                    int *frame_sizes);
 /* Page-lock the buffers a caller hands to flake_amd_encode_frames() batch after batch (the loop of
  * flake.c:622-663 reads every block into the same buffer), in place: copies from and to pageable memory run
  * at about two thirds of the link's rate.  Either pointer may be NULL (left as it is); bytes = 0 releases a

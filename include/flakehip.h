@@ -129,6 +129,27 @@ FHIP_API void fhip_destroy(fhip_ctx *ctx);                       /* flake_encode
 FHIP_API int fhip_set_stream(fhip_ctx *ctx, void *hip_stream);
 FHIP_API int fhip_sync(fhip_ctx *ctx);
 
+/*
+ * The handle's PCM format: the width of the samples every `pcm` pointer given to it addresses.
+ *   FHIP_PCM_S32 (default)  channel-interleaved int32, flake_encode_frame()'s contract (flake.h:229)
+ *   FHIP_PCM_S16            channel-interleaved int16_t, each value sign-extended to int32 on the device and
+ *                           from there on treated as the int32 contract says (with bits_per_sample < 16 it
+ *                           must already lie in that range).  16-bit audio then crosses the link and is read
+ *                           by the feeder stage at 2 bytes per sample instead of 4.
+ * The structs keep their layout: while FHIP_PCM_S16 is set, fhip_batch.pcm, fhip_verify_in.pcm and the pcm
+ * arguments of fhip_prepare_frames carry the ADDRESS of int16_t samples in their `const int32_t *`; host-pointer
+ * entries upload 2 bytes per value.  Honoured by fhip_encode_subframes(_dev), fhip_encode_frames_packed and its
+ * _upload / _begin / _fetch steps, fhip_prepare_ahead, fhip_prepare_frames and fhip_verify_frames(_dev)
+ * (including the run behind fhip_set_verify); every output is byte-identical to that of the widened int32 input.
+ * Device pcm must be 16-byte aligned as before.  Variable block size is not covered: under FHIP_PCM_S16
+ * fhip_encode_blocks_vbs_dev, fhip_encode_blocks_vbs_packed and fhip_vbs_split return FHIP_E_UNSUPPORTED (the
+ * ragged path reads pieces where they lie with 16-byte loads; its alignment rules differ for 2-byte samples).
+ * Returns FHIP_E_INVALID for a null handle, an unknown format, or FHIP_PCM_S16 on a handle with
+ * bits_per_sample > 16.  A pending fhip_prepare_ahead / fhip_frames_packed_upload hint is dropped.
+ */
+enum { FHIP_PCM_S32 = 0, FHIP_PCM_S16 = 1 };
+FHIP_API int fhip_set_pcm_format(fhip_ctx *ctx, int format);
+
 FHIP_API const char *fhip_strerror(int code);
 FHIP_API const char *fhip_last_error(const fhip_ctx *ctx);
 FHIP_API const char *fhip_version(void);                          /* flake_get_version, encode.c:1028 */
@@ -143,7 +164,8 @@ FHIP_API const char *fhip_version(void);                          /* flake_get_v
  * Outputs other than info may be NULL.  Asynchronous on the handle's stream.
  */
 typedef struct fhip_batch {
-    const int32_t      *pcm;          /* [nframes][block_size][channels] */
+    const int32_t      *pcm;          /* [nframes][block_size][channels]; the address of int16_t samples
+                                         while the handle's format is FHIP_PCM_S16 (fhip_set_pcm_format) */
     int                 nframes;
     int                 block_size;
     fhip_subframe_info *info;         /* [nframes*channels] */
@@ -352,7 +374,8 @@ typedef struct fhip_verify_in {
     int64_t        stream_bytes;
     const int32_t *frame_bytes;   /* [nframes] size of each frame; frame f starts at the sum of those before it */
     int32_t        nframes;
-    const int32_t *pcm;           /* [nsamples][channels] interleaved int32 (flake_encode_frame's contract) */
+    const int32_t *pcm;           /* [nsamples][channels] interleaved int32 (flake_encode_frame's contract);
+                                     the address of int16_t samples under FHIP_PCM_S16 (fhip_set_pcm_format) */
     int64_t        nsamples;
     int64_t        first_sample;  /* absolute index of pcm[0] in the stream */
 } fhip_verify_in;
