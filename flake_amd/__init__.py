@@ -136,6 +136,13 @@ class VerifyOut(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("summary", C.c_void_p)]
 
 
+# numpy view of fhip_md5_state (96 bytes): K6's running hash of one stream
+MD5_STATE_DTYPE = np.dtype([("h", "<u4", (4,)), ("nbytes", "<u8"), ("fill", "<u4"), ("reserved", "<u4"),
+                            ("tail", "u1", (64,))])
+assert MD5_STATE_DTYPE.itemsize == 96
+MD5_STATE_BYTES = 96
+
+
 # FHIP_VERIFY_*: a frame's status, the first failing check in stream order
 VERIFY_STATUS = ("OK", "HEADER", "CRC8", "NUMBER", "SYNTAX", "SAMPLES", "PADDING", "CRC16", "LENGTH")
 (V_OK, V_HEADER, V_CRC8, V_NUMBER, V_SYNTAX, V_SAMPLES, V_PADDING, V_CRC16, V_LENGTH) = range(9)
@@ -197,6 +204,14 @@ def load_library() -> C.CDLL:
         "fhip_get_kernel_times": (i, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double),
                                       C.POINTER(i), i, i]),
         "fhip_last_launches": (i, [vp, C.POINTER(C.c_char_p), i]),
+        "fhip_md5_init_dev": (i, [vp, vp, i]),
+        "fhip_md5_update_dev": (i, [vp, vp, i, vp, i, vp, vp]),
+        "fhip_md5_final_dev": (i, [vp, vp, i, vp]),
+        "fhip_md5_final": (i, [vp, vp, i, vp]),
+        "fhip_md5_update_uploaded": (i, [vp, vp, i, i, i, vp, vp]),
+        "fhip_frames_packed_upload": (i, [vp, C.POINTER(Batch)]),
+        "fhip_device_alloc": (vp, [C.c_size_t]),
+        "fhip_device_free": (None, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -217,6 +232,8 @@ ABI_SYMBOLS = (
     "fhip_host_alloc", "fhip_host_free", "fhip_host_register", "fhip_host_unregister", "fhip_frames_packed_upload", "fhip_frames_packed_fetch_async", "fhip_frames_packed_fetch_wait",
     "fhip_set_verify", "fhip_verify_frames_dev", "fhip_verify_frames", "fhip_last_launches",
     "fhip_set_pcm_format",
+    "fhip_md5_init_dev", "fhip_md5_update_dev", "fhip_md5_final_dev", "fhip_md5_final", "fhip_md5_update_uploaded",
+    "fhip_device_alloc", "fhip_device_free",
 )
 
 
@@ -342,6 +359,20 @@ class Encoder:
         names = (C.c_char_p * max(k, 1))()
         k = self.lib.fhip_last_launches(self._h, names, k)
         return [names[i].decode() for i in range(k)]
+
+    # -- K6: the MD5 of many streams (device tensors or raw device addresses; async) ------------------
+    def md5_init_dev(self, states, nstreams: int) -> None:
+        """states: device memory for nstreams fhip_md5_state records (MD5_STATE_BYTES each)."""
+        self._check(self.lib.fhip_md5_init_dev(self._h, _ptr(states), nstreams), "fhip_md5_init_dev")
+
+    def md5_update_dev(self, states, nstreams: int, pcm, block_size: int, seg_first, seg_block) -> None:
+        """Stream s absorbs blocks seg_block[seg_first[s]:seg_first[s + 1]] of pcm (int32 device tables)."""
+        self._check(self.lib.fhip_md5_update_dev(self._h, _ptr(states), nstreams, _ptr(pcm), block_size,
+                                                 _ptr(seg_first), _ptr(seg_block)), "fhip_md5_update_dev")
+
+    def md5_final_dev(self, states, nstreams: int, digests) -> None:
+        """digests: device uint8[nstreams][16]; the states stay usable."""
+        self._check(self.lib.fhip_md5_final_dev(self._h, _ptr(states), nstreams, _ptr(digests)), "fhip_md5_final_dev")
 
     # -- hot path ---------------------------------------------------------
     def frame_stride(self, block_size: int) -> int:
@@ -526,6 +557,17 @@ def load_host_library() -> C.CDLL:
     lib.flake_amd_last_error.restype = C.c_char_p
     lib.flake_amd_set_verify.argtypes = [cp, C.c_int]
     lib.flake_amd_set_verify.restype = C.c_int
+    lib.flake_amd_set_open.argtypes = [cp, C.c_int, C.c_uint]
+    lib.flake_amd_set_open.restype = C.c_void_p
+    lib.flake_amd_set_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_size_t, C.c_void_p]
+    lib.flake_amd_set_encode.restype = C.c_longlong
+    lib.flake_amd_set_get_streaminfo.argtypes = [C.c_void_p, C.c_int, C.POINTER(HostStreaminfo)]
+    lib.flake_amd_set_get_streaminfo.restype = C.c_int
+    lib.flake_amd_set_last_error.argtypes = [C.c_void_p]
+    lib.flake_amd_set_last_error.restype = C.c_char_p
+    lib.flake_amd_set_close.argtypes = [C.c_void_p]
+    lib.flake_amd_set_close.restype = None
     _host = lib
     return lib
 
@@ -638,6 +680,81 @@ class HostEncoder:
         if getattr(self, "open", False):
             self.lib.flake_amd_encode_close(C.byref(self.ctx))
             self.open = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+SET_MD5_HOST, SET_MD5_OFF = 1, 2      # FLAKE_AMD_SET_*
+
+
+class StreamSet:
+    """A stream set of the host C layer (flake_amd_set_*): many independent streams of one format per batch,
+    each stream's MD5 carried on the device.  ctypes only; no compute here."""
+
+    def __init__(self, nstreams: int, level: int = 5, channels: int = 2, bits_per_sample: int = 16,
+                 sample_rate: int = 44100, flags: int = 0, **over):
+        self.lib = load_host_library()
+        self.ctx = HostContext(channels=channels, sample_rate=sample_rate, bits_per_sample=bits_per_sample)
+        self.ctx.params.compression = level
+        if self.lib.flake_amd_set_defaults(C.byref(self.ctx.params)) != 0:
+            raise ValueError("flake_amd_set_defaults")
+        for k, v in over.items():
+            if not hasattr(self.ctx.params, k):
+                raise AttributeError(k)
+            setattr(self.ctx.params, k, v)
+        self.nstreams = int(nstreams)
+        self.block_size = self.ctx.params.block_size
+        self._g = self.lib.flake_amd_set_open(C.byref(self.ctx), self.nstreams, int(flags))
+        if not self._g:
+            raise FlakeHipError(-1, "flake_amd_set_open", self.lib.flake_amd_set_last_error(None).decode())
+
+    def last_error(self) -> str:
+        return self.lib.flake_amd_set_last_error(self._g).decode()
+
+    def encode(self, pcm: np.ndarray, block_size: int, stream_of_block, dtype=np.int32):
+        """pcm: [nblocks * block_size][channels] (int32, or int16 with dtype=np.int16), block b of stream
+        stream_of_block[b].  Returns (bytes of all frames in batch order, frame sizes [nblocks])."""
+        ch = self.ctx.channels
+        pcm = np.ascontiguousarray(pcm, dtype=dtype).reshape(-1, ch)
+        sob = np.ascontiguousarray(stream_of_block, dtype=np.int32)
+        nblocks = len(sob)
+        assert nblocks * block_size == pcm.shape[0]
+        cap = 64 + pcm.size * 5 + 64 * (nblocks + 1) * 8
+        out = np.zeros(cap, dtype=np.uint8)
+        sizes = np.zeros(max(nblocks, 1), dtype=np.int32)
+        w = self.lib.flake_amd_set_encode(self._g, pcm.ctypes.data, pcm.dtype.itemsize, nblocks, block_size,
+                                          sob.ctypes.data, out.ctypes.data, cap, sizes.ctypes.data)
+        if w < 0:
+            raise FlakeHipError(int(w), "flake_amd_set_encode", self.last_error())
+        return out[:w].copy(), sizes[:nblocks]
+
+    def streaminfo(self, stream: int) -> HostStreaminfo:
+        si = HostStreaminfo()
+        if self.lib.flake_amd_set_get_streaminfo(self._g, int(stream), C.byref(si)) != 0:
+            raise FlakeHipError(-1, "flake_amd_set_get_streaminfo", self.last_error())
+        return si
+
+    def streaminfo_bytes(self, stream: int) -> bytes:
+        """The 34 STREAMINFO bytes of one stream (flake_amd_write_streaminfo)."""
+        si = self.streaminfo(stream)
+        buf = (C.c_ubyte * 34)()
+        self.lib.flake_amd_write_streaminfo(C.byref(si), buf)
+        return bytes(buf)
+
+    def close(self) -> None:
+        if getattr(self, "_g", None):
+            self.lib.flake_amd_set_close(self._g)
+            self._g = None
 
     def __enter__(self):
         return self

@@ -78,6 +78,7 @@ struct fhip_ctx {
     long long packed_ready = 0;       // bytes waiting in d_packed between _begin and _fetch
     const int32_t *uploaded_pcm = nullptr;   // fhip_frames_packed_upload: this host batch already lies in d_pcm
     size_t uploaded_vals = 0;
+    int uploaded_frames = 0, uploaded_n = 0; // ... as so many blocks of so many samples (fhip_md5_update_uploaded)
     hipEvent_t ev_fetch = nullptr;           // fhip_frames_packed_fetch_async: behind the download of d_packed (on aux[0])
     bool fetch_pending = false;
     // variable-block-size batches (fhip_encode_blocks_vbs_dev): the piece tables k_vbs_plan leaves
@@ -127,6 +128,25 @@ struct fhip_ctx {
 
     std::vector<std::string> launches;        // fhip_last_launches: what the most recent call queued
 
+    // K6 (fhip_md5_*): allocated at first use (ensure_md5)
+    static constexpr int MD5_SLOTS = 16;
+    hipStream_t md5_stream = nullptr;         // fhip_md5_update_uploaded: beside K0...K4 of the batch
+    hipEvent_t ev_md5_up = nullptr;           // behind the last update on md5_stream (it reads d_pcm and the states)
+    hipEvent_t ev_md5_dev = nullptr;          // behind the last fhip_md5_*_dev on the caller's stream
+    hipEvent_t ev_md5_log = nullptr;          // behind the launch fhip_last_launches still has to name the path of
+    bool md5_up_pending = false, md5_dev_pending = false;
+    DevBuf<int32_t> d_md5flag;                // [MD5_SLOTS] k_md5_scan's answers, one slot per call in turn
+    int32_t *h_md5flag = nullptr;             // the same in pinned host memory
+    int md5_slot = 0;
+    int md5_log_entry = -1, md5_log_slot = 0; // launches[md5_log_entry] waits for its path
+    DevBuf<uint8_t> d_md5digest;              // fhip_md5_final: [nstreams][16]
+    DevBuf<int32_t> d_md5seg[2];              // fhip_md5_update_uploaded: the host tables, two sets in turn
+    int32_t *h_md5seg[2] = {nullptr, nullptr};
+    size_t h_md5seg_cap[2] = {0, 0};
+    hipEvent_t ev_md5seg[2] = {nullptr, nullptr};     // behind the copy out of h_md5seg[k]
+    bool md5seg_used[2] = {false, false};
+    int md5seg_next = 0;
+
     std::string err;
 };
 
@@ -175,6 +195,7 @@ struct LaunchScope {
     explicit LaunchScope(fhip_ctx *c) : prev(fhip::launch_sink)
     {
         c->launches.clear();
+        c->md5_log_entry = -1;
         fhip::launch_sink = &c->launches;
     }
     ~LaunchScope() { fhip::launch_sink = prev; }
@@ -469,6 +490,63 @@ int verify_verdict(fhip_ctx *c, const long long *summary, const fhip_verify_rec 
     return FHIP_E_VERIFY;
 }
 
+// Every entry that writes the staging PCM goes through here: what fhip_frames_packed_upload left there is gone
+// (never trusted by pointer identity across entries), and an MD5 update that still reads it finishes first.
+int stage_pcm(fhip_ctx *c, const void *src, size_t bytes)
+{
+    c->uploaded_pcm = nullptr;
+    if (c->md5_up_pending) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_md5_up, 0));
+    HIP_TRY(c, hipMemcpyAsync(c->d_pcm, src, bytes, hipMemcpyHostToDevice, c->stream));
+    return FHIP_OK;
+}
+
+// K6's streams, events and flag slots.
+int ensure_md5(fhip_ctx *c)
+{
+    if (c->md5_stream) return FHIP_OK;
+    HIP_TRY(c, c->d_md5flag.reserve(fhip_ctx::MD5_SLOTS));
+    HIP_TRY(c, hipMemset(c->d_md5flag, 0, fhip_ctx::MD5_SLOTS * sizeof(int32_t)));
+    HIP_TRY(c, hipDeviceSynchronize());      // (null-stream fill; the handle's streams are non-blocking)
+    HIP_TRY(c, hipHostMalloc((void **)&c->h_md5flag, fhip_ctx::MD5_SLOTS * sizeof(int32_t), hipHostMallocDefault));
+    memset(c->h_md5flag, 0, fhip_ctx::MD5_SLOTS * sizeof(int32_t));
+    HIP_TRY(c, hipEventCreateWithFlags(&c->ev_md5_up, hipEventDisableTiming));
+    HIP_TRY(c, hipEventCreateWithFlags(&c->ev_md5_dev, hipEventDisableTiming));
+    HIP_TRY(c, hipEventCreateWithFlags(&c->ev_md5_log, hipEventDisableTiming));
+    for (int k = 0; k < 2; k++) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_md5seg[k], hipEventDisableTiming));
+    HIP_TRY(c, hipStreamCreateWithFlags(&c->md5_stream, hipStreamNonBlocking));
+    return FHIP_OK;
+}
+
+// One update on `st` (the caller's stream or md5_stream); the tables are device memory.  The launch's path goes
+// into the list at once when the shape decides it, else when fhip_last_launches asks.
+int md5_update(fhip_ctx *c, hipStream_t st, fhip_md5_state *states, int nstreams, const void *pcm, int block_size,
+               const int32_t *seg_first, const int32_t *seg_block)
+{
+    const int slot = c->md5_slot;
+    c->md5_slot = (slot + 1) % fhip_ctx::MD5_SLOTS;
+    bool shape_fast = false;
+    c->md5_log_entry = -1;
+    HIP_TRY(c, fhip::launch_md5_streams(st, states, nstreams, pcm, c->pcm_format, block_size * c->p.channels,
+                                        (c->p.bits_per_sample + 7) >> 3, seg_first, seg_block, c->d_md5flag + slot,
+                                        c->h_md5flag + slot, &shape_fast));
+    if (nstreams == 0) return FHIP_OK;
+    if (!shape_fast) {
+        c->launches.back() += " general";
+    } else {
+        HIP_TRY(c, hipEventRecord(c->ev_md5_log, st));
+        c->md5_log_entry = (int)c->launches.size() - 1;
+        c->md5_log_slot = slot;
+    }
+    return FHIP_OK;
+}
+
+int md5_check(fhip_ctx *c, const void *states, int nstreams, bool rest)
+{
+    if (!c || !states || !rest) return fail(c, FHIP_E_INVALID, "null argument");
+    if (nstreams < 0) return fail(c, FHIP_E_INVALID, "negative stream count");
+    return FHIP_OK;
+}
+
 // What every batch entry checks first, in this order: the pointers (rest: the entry's further required ones are
 // there; null_text: its wording), nframes against max_frames, block_size against the handle's.
 int check_range(fhip_ctx *c, const fhip_batch *b, bool rest, const char *null_text)
@@ -670,6 +748,11 @@ void fhip_destroy(fhip_ctx *c)
     if (c->pre) { (void)hipStreamSynchronize(c->pre); (void)hipStreamDestroy(c->pre); }
     if (c->ev_k1) (void)hipEventDestroy(c->ev_k1);
     if (c->ev_fetch) { (void)hipEventSynchronize(c->ev_fetch); (void)hipEventDestroy(c->ev_fetch); }
+    if (c->md5_stream) { (void)hipStreamSynchronize(c->md5_stream); (void)hipStreamDestroy(c->md5_stream); }
+    for (hipEvent_t ev : {c->ev_md5_up, c->ev_md5_dev, c->ev_md5_log, c->ev_md5seg[0], c->ev_md5seg[1]})
+        if (ev) (void)hipEventDestroy(ev);
+    if (c->h_md5flag) (void)hipHostFree(c->h_md5flag);
+    for (int k = 0; k < 2; k++) if (c->h_md5seg[k]) (void)hipHostFree(c->h_md5seg[k]);
     for (int h = 0; h < 2; h++) {
         if (c->ev_prep[h]) (void)hipEventDestroy(c->ev_prep[h]);
         if (c->ev_enc[h]) (void)hipEventDestroy(c->ev_enc[h]);
@@ -738,6 +821,13 @@ int fhip_get_kernel_times(fhip_ctx *c, const char **names, double *ms, int *laun
 int fhip_last_launches(fhip_ctx *c, const char **names, int cap)
 {
     if (!c) return FHIP_E_INVALID;
+    if (c->md5_log_entry >= 0 && c->md5_log_entry < (int)c->launches.size()) {
+        // K6 chose its path on the device (k_md5_scan's answer, mirrored into pinned host memory)
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipEventSynchronize(c->ev_md5_log));
+        c->launches[c->md5_log_entry] += c->h_md5flag[c->md5_log_slot] ? " general" : " fast";
+    }
+    c->md5_log_entry = -1;
     const int k = (int)c->launches.size();
     for (int i = 0; i < k && i < cap && names; i++) names[i] = c->launches[i].c_str();
     return k;
@@ -841,7 +931,8 @@ int fhip_encode_subframes(fhip_ctx *c, const fhip_batch *b)
     double *d_autoc_out = b->autoc ? c->d_autoc : nullptr;
     // a section that does not fit its slot leaves the slot untouched: what comes back for it is zeros
     if (b->rice_bits) HIP_TRY(c, hipMemsetAsync(c->d_bits, 0, bits_bytes, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_pcm, b->pcm, nsub * n * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
+    rc = stage_pcm(c, b->pcm, nsub * n * c->pcm_width());
+    if (rc != FHIP_OK) return rc;
     HIP_TRY(c, hipMemsetAsync(c->d_info, 0, nsub * sizeof(fhip_subframe_info), c->stream));
     FrameOut fo{nullptr, 0, nullptr, 0};
     if (b->frames) {
@@ -887,10 +978,14 @@ int fhip_frames_packed_upload(fhip_ctx *c, const fhip_batch *b)
     const int64_t stride = fhip_frame_stride(&c->p, b->block_size);
     rc = ensure_staging(c, (size_t)b->nframes * c->p.channels * (size_t)((stride + 3) & ~(int64_t)3));
     if (rc != FHIP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->d_pcm, b->pcm, nvals * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
+    rc = stage_pcm(c, b->pcm, nvals * c->pcm_width());
+    if (rc != FHIP_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->md5_up_pending = false;               // (the stream waited for it)
     c->uploaded_pcm = b->pcm;
     c->uploaded_vals = nvals;
+    c->uploaded_frames = b->nframes;
+    c->uploaded_n = b->block_size;
     return FHIP_OK;
 }
 
@@ -923,8 +1018,10 @@ int fhip_frames_packed_begin(fhip_ctx *c, const fhip_batch *b, int64_t *total_by
     const bool uploaded = c->uploaded_pcm == b->pcm && c->uploaded_vals == nsub * n;
     c->uploaded_pcm = nullptr;
     if (c->fetch_pending) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_fetch, 0));     // d_packed is still being read
-    if (!uploaded)
-        HIP_TRY(c, hipMemcpyAsync(c->d_pcm, b->pcm, nsub * n * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
+    if (!uploaded) {
+        rc = stage_pcm(c, b->pcm, nsub * n * c->pcm_width());
+        if (rc != FHIP_OK) return rc;
+    }
     rc = run_pipeline(c, c->d_pcm, b->nframes, b->block_size, c->d_info, nullptr, c->d_bits, slot,
                       nullptr, nullptr, fo, false);
     if (rc != FHIP_OK) return rc;
@@ -961,6 +1058,21 @@ int fhip_frames_packed_fetch(fhip_ctx *c, uint8_t *out, int64_t out_cap)
     }
     c->packed_ready = 0;
     return FHIP_OK;
+}
+
+void *fhip_device_alloc(size_t bytes)
+{
+    void *p = nullptr;
+    if (bytes == 0 || hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return p;
+}
+
+void fhip_device_free(void *p)
+{
+    if (p && hipFree(p) != hipSuccess) (void)hipGetLastError();
 }
 
 void *fhip_host_alloc(size_t bytes)
@@ -1037,6 +1149,120 @@ int fhip_encode_frames_packed(fhip_ctx *c, const fhip_batch *b, uint8_t *out, in
     rc = fhip_frames_packed_fetch(c, out, out_cap);
     if (rc != FHIP_OK) return rc;
     *out_bytes = total;
+    return FHIP_OK;
+}
+
+// ---- K6: the MD5 of many streams ----------------------------------------------------------------
+// The *_dev entries run on the caller's stream, fhip_md5_update_uploaded on md5_stream; each side waits for the
+// other's last launch, so updates of the same states run in call order whichever entries make them.
+
+static int md5_dev_begin(fhip_ctx *c)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int rc = ensure_md5(c);
+    if (rc != FHIP_OK) return rc;
+    if (c->md5_up_pending) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_md5_up, 0));
+    return FHIP_OK;
+}
+
+static int md5_dev_end(fhip_ctx *c)
+{
+    HIP_TRY(c, hipEventRecord(c->ev_md5_dev, c->stream));
+    c->md5_dev_pending = true;
+    return FHIP_OK;
+}
+
+int fhip_md5_init_dev(fhip_ctx *c, fhip_md5_state *states, int nstreams)
+{
+    int rc = md5_check(c, states, nstreams, true);
+    if (rc != FHIP_OK) return rc;
+    LaunchScope ls(c);
+    if ((rc = md5_dev_begin(c)) != FHIP_OK) return rc;
+    HIP_TRY(c, fhip::launch_md5_init(c->stream, states, nstreams));
+    return md5_dev_end(c);
+}
+
+int fhip_md5_update_dev(fhip_ctx *c, fhip_md5_state *states, int nstreams, const void *pcm, int block_size,
+                        const int32_t *seg_first, const int32_t *seg_block)
+{
+    int rc = md5_check(c, states, nstreams, pcm && seg_first && seg_block);
+    if (rc != FHIP_OK) return rc;
+    if (block_size < 1 || block_size > FHIP_MAX_BLOCK) return fail(c, FHIP_E_INVALID, "block_size out of range");
+    LaunchScope ls(c);
+    if ((rc = md5_dev_begin(c)) != FHIP_OK) return rc;
+    if ((rc = md5_update(c, c->stream, states, nstreams, pcm, block_size, seg_first, seg_block)) != FHIP_OK) return rc;
+    return md5_dev_end(c);
+}
+
+int fhip_md5_final_dev(fhip_ctx *c, const fhip_md5_state *states, int nstreams, uint8_t *digests)
+{
+    int rc = md5_check(c, states, nstreams, digests != nullptr);
+    if (rc != FHIP_OK) return rc;
+    LaunchScope ls(c);
+    if ((rc = md5_dev_begin(c)) != FHIP_OK) return rc;
+    HIP_TRY(c, fhip::launch_md5_final(c->stream, states, nstreams, digests));
+    return md5_dev_end(c);
+}
+
+// Host digests: the device's into a buffer of the handle's own, one copy, one synchronisation for all streams.
+int fhip_md5_final(fhip_ctx *c, const fhip_md5_state *states, int nstreams, uint8_t *digests)
+{
+    int rc = md5_check(c, states, nstreams, digests != nullptr);
+    if (rc != FHIP_OK) return rc;
+    if (nstreams == 0) return FHIP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, c->d_md5digest.reserve((size_t)nstreams * 16));
+    rc = fhip_md5_final_dev(c, states, nstreams, c->d_md5digest);
+    if (rc != FHIP_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(digests, c->d_md5digest, (size_t)nstreams * 16, hipMemcpyDeviceToHost, c->stream));
+    return fhip_sync(c);
+}
+
+int fhip_md5_update_uploaded(fhip_ctx *c, fhip_md5_state *states, int nstreams, int nblocks, int block_size,
+                             const int32_t *seg_first, const int32_t *seg_block)
+{
+    int rc = md5_check(c, states, nstreams, seg_first && seg_block);
+    if (rc != FHIP_OK) return rc;
+    if (block_size < 1 || block_size > FHIP_MAX_BLOCK) return fail(c, FHIP_E_INVALID, "block_size out of range");
+    // the upload this call names must still be the staging buffer's content: fhip_frames_packed_upload notes
+    // what it brought, every other writer of the buffer (and _begin, which consumes it) withdraws the note
+    if (!c->uploaded_pcm || nblocks < 1 || c->uploaded_frames != nblocks || c->uploaded_n != block_size)
+        return fail(c, FHIP_E_INVALID, "no matching fhip_frames_packed_upload is pending");
+    // the tables are the host's: nothing out of range reaches the kernel
+    if (seg_first[0] != 0) return fail(c, FHIP_E_INVALID, "seg_first[0] must be 0");
+    for (int s = 0; s < nstreams; s++)
+        if (seg_first[s + 1] < seg_first[s]) return fail(c, FHIP_E_INVALID, "seg_first must not decrease");
+    const int nseg = seg_first[nstreams];
+    for (int i = 0; i < nseg; i++)
+        if (seg_block[i] < 0 || seg_block[i] >= nblocks) return fail(c, FHIP_E_INVALID, "seg_block entry outside the upload");
+    LaunchScope ls(c);
+    if (nstreams == 0 || nseg == 0) return FHIP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = ensure_md5(c)) != FHIP_OK) return rc;
+    // the tables go through page-locked memory of the handle's own (two sets in turn: the set used two calls ago
+    // has long been copied out when it is written again, and the wait below says so)
+    const int k = c->md5seg_next;
+    c->md5seg_next ^= 1;
+    const size_t nfirst = (size_t)nstreams + 1, nvals = nfirst + (size_t)nseg;
+    if (c->md5seg_used[k]) HIP_TRY(c, hipEventSynchronize(c->ev_md5seg[k]));
+    if (c->h_md5seg_cap[k] < nvals) {
+        if (c->h_md5seg[k]) HIP_TRY(c, hipHostFree(c->h_md5seg[k]));
+        c->h_md5seg[k] = nullptr; c->h_md5seg_cap[k] = 0;
+        HIP_TRY(c, hipHostMalloc((void **)&c->h_md5seg[k], nvals * 2 * sizeof(int32_t), hipHostMallocDefault));
+        c->h_md5seg_cap[k] = nvals * 2;
+    }
+    HIP_TRY(c, c->d_md5seg[k].reserve(nvals));
+    memcpy(c->h_md5seg[k], seg_first, nfirst * sizeof(int32_t));
+    memcpy(c->h_md5seg[k] + nfirst, seg_block, (size_t)nseg * sizeof(int32_t));
+    hipStream_t st = c->md5_stream;
+    if (c->md5_dev_pending) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_md5_dev, 0));
+    HIP_TRY(c, hipMemcpyAsync(c->d_md5seg[k], c->h_md5seg[k], nvals * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->ev_md5seg[k], st));
+    c->md5seg_used[k] = true;
+    rc = md5_update(c, st, states, nstreams, c->d_pcm, block_size, c->d_md5seg[k], c->d_md5seg[k] + nfirst);
+    if (rc != FHIP_OK) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev_md5_up, st));
+    c->md5_up_pending = true;
     return FHIP_OK;
 }
 
@@ -1444,7 +1670,8 @@ int fhip_encode_blocks_vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, 
 
     // one upload, the batch on the device, one download of the stream's bytes
     const size_t nvals = (size_t)nblocks * block_size * (size_t)p.channels;
-    HIP_TRY(c, hipMemcpyAsync(c->d_pcm, pcm, nvals * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    rc = stage_pcm(c, pcm, nvals * sizeof(int32_t));
+    if (rc != FHIP_OK) return rc;
     if (c->verify) HIP_TRY(c, c->d_stream_bytes.reserve((size_t)c->max_frames));
     rc = vbs_dev_core(c, c->d_pcm, nblocks, block_size, first_frame_number,
                       VbsOut{c->d_packed, (long long)c->d_packed.cap, c->verify ? c->d_stream_bytes : nullptr,
@@ -1548,7 +1775,8 @@ int fhip_prepare_frames(fhip_ctx *c, const int32_t *pcm, int nframes, int n,
     if (rc != FHIP_OK) return rc;
     const size_t nsub = (size_t)nframes * c->p.channels;
     if (nsub == 0) return FHIP_OK;
-    HIP_TRY(c, hipMemcpyAsync(c->d_pcm, pcm, nsub * n * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
+    rc = stage_pcm(c, pcm, nsub * n * c->pcm_width());
+    if (rc != FHIP_OK) return rc;
     HIP_TRY(c, hipMemsetAsync(c->d_info, 0, nsub * sizeof(fhip_subframe_info), c->stream));
     HIP_TRY(c, fhip::launch_prepare(c->stream, c->p, c->d_pcm, nframes, n, c->d_smp, c->d_info, false, false, nullptr,
                                     nullptr, c->pcm_format));
@@ -1666,7 +1894,8 @@ int fhip_vbs_split(fhip_ctx *c, const int32_t *pcm, int nblocks, int block_size,
     if (rc != FHIP_OK) return rc;
     const size_t nvals = (size_t)nblocks * block_size * c->p.channels;
     // d_opt (>= max_frames ints) and d_shift (>= 32*max_frames ints) are free before K2 runs
-    HIP_TRY(c, hipMemcpyAsync(c->d_pcm, pcm, nvals * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    rc = stage_pcm(c, pcm, nvals * sizeof(int32_t));
+    if (rc != FHIP_OK) return rc;
     HIP_TRY(c, fhip::launch_vbs_split(c->stream, c->d_pcm, nblocks, block_size, c->p.channels,
                                       c->d_opt, c->d_shift));
     HIP_TRY(c, hipMemcpyAsync(frames, c->d_opt, (size_t)nblocks * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));

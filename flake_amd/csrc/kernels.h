@@ -1,5 +1,5 @@
 // kernels.h -- launch interface between the C ABI (api.hip) and the gfx950
-// kernels (k0_prepare.hip ... k4_assemble.hip).  Internal to libflakehip.so.
+// kernels (k0_prepare.hip ... k6_md5.hip).  Internal to libflakehip.so.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -240,5 +240,18 @@ struct VerifyArgs {
     long long *totals;                           // optional: fhip_encode_blocks_vbs_dev's totals
 };
 hipError_t launch_verify(hipStream_t st, const VerifyArgs &a);
+
+// K6 (k6_md5.hip): the STREAMINFO MD5 of many streams, one lane per stream.  The update hashes, for stream s, the
+// blocks seg_block[seg_first[s] .. seg_first[s + 1]) -- indices of block_vals-sample blocks (block_size * channels
+// interleaved values) of pcm -- in that order.  pcm_format as for K0; bytes_per_sample = (bits_per_sample + 7) / 8.
+// The fast path needs md5_shape_fast() (whole 64-byte blocks per PCM block, 16-byte aligned) AND no stream of the
+// launch holding a partial block: the second is only known on the device, so a shape-fast launch is preceded by
+// k_md5_scan, which leaves the answer in flag[0] (device) and host_flag[0] (pinned host memory, optional).
+bool md5_shape_fast(int block_vals, int bytes_per_sample, int pcm_format, const void *pcm);
+hipError_t launch_md5_init(hipStream_t st, fhip_md5_state *states, int nstreams);
+hipError_t launch_md5_streams(hipStream_t st, fhip_md5_state *states, int nstreams, const void *pcm, int pcm_format,
+                              int block_vals, int bytes_per_sample, const int32_t *seg_first,
+                              const int32_t *seg_block, int32_t *flag, int32_t *host_flag, bool *shape_fast_out);
+hipError_t launch_md5_final(hipStream_t st, const fhip_md5_state *states, int nstreams, uint8_t *digests);
 
 }  // namespace fhip

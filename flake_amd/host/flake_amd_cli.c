@@ -6,6 +6,12 @@
  *
  *   flake_amd_cli [-0..-12] [-b blocksize] [--verify] in.wav out.flac
  *   flake_amd_cli [-0..-12] --synth FRAMES [--channels C] [--bps B] [--verify] out.flac
+ *   flake_amd_cli [-0..-8] [-b blocksize] --set OUTDIR in1.wav in2.wav ...
+ *   flake_amd_cli [-0..-8] --set OUTDIR --synth-streams S --synth FRAMES [--channels C] [--bps B]
+ *
+ * --set encodes inputs of one format as a stream set (flake_amd_set_*): their blocks round-robin in shared GPU
+ * batches, every stream's MD5 carried on the device, one OUTDIR/<name>.flac per input with its own STREAMINFO --
+ * the file the single-input form writes for that input.
  *
  * --verify checks on the GPU that every frame decodes to its input (flake_amd_set_verify)
  * and exits non-zero with the verifier's message when one does not.
@@ -74,12 +80,193 @@ static uint32_t wav_read(wav_t *w, int32_t *dst, int16_t *dst16, uint32_t frames
     return (uint32_t)(got / w->channels);
 }
 
+/* ---- --set: many inputs of one format through one stream set -------- */
+typedef struct { uint8_t *p; size_t n, cap; } bytes_t;
+
+static int bytes_add(bytes_t *b, const uint8_t *src, size_t n)
+{
+    if (b->n + n > b->cap) {
+        size_t cap = b->cap ? b->cap * 2 : 65536;
+        while (cap < b->n + n) cap *= 2;
+        uint8_t *q = (uint8_t *)realloc(b->p, cap);
+        if (!q) return -1;
+        b->p = q; b->cap = cap;
+    }
+    memcpy(b->p + b->n, src, n);
+    b->n += n;
+    return 0;
+}
+
+typedef struct {
+    FlakeAmdSet *g;
+    int sample_bytes, bs, nch, cap_blocks, count;
+    char *pcm;                            /* the batch being filled */
+    int *stream_of, *sizes;
+    uint8_t *buf; size_t buf_cap;
+    bytes_t *outs;                        /* per stream: its frames */
+} set_run;
+
+static int set_flush(set_run *r, int block_size)
+{
+    if (!r->count) return 0;
+    const long long n = flake_amd_set_encode(r->g, r->pcm, r->sample_bytes, r->count, block_size, r->stream_of,
+                                             r->buf, r->buf_cap, r->sizes);
+    if (n < 0) { fprintf(stderr, "encode error: %s\n", flake_amd_set_last_error(r->g)); return -1; }
+    size_t pos = 0;
+    for (int b = 0; b < r->count; b++) {
+        if (bytes_add(&r->outs[r->stream_of[b]], r->buf + pos, (size_t)r->sizes[b])) return -1;
+        pos += (size_t)r->sizes[b];
+    }
+    r->count = 0;
+    return 0;
+}
+
+static int set_add(set_run *r, int stream, const char *block, int block_size)
+{
+    const size_t bytes = (size_t)block_size * r->nch * r->sample_bytes;
+    memcpy(r->pcm + (size_t)r->count * bytes, block, bytes);
+    r->stream_of[r->count++] = stream;
+    return r->count == r->cap_blocks ? set_flush(r, block_size) : 0;
+}
+
+static int run_set(const char *outdir, char **inputs, int ninputs, int synth_streams, int synth, int level, int bsize,
+                   int channels, int bps)
+{
+    const int S = ninputs ? ninputs : synth_streams;
+    FlakeAmdContext s;
+    memset(&s, 0, sizeof s);
+    wav_t *wavs = (wav_t *)calloc((size_t)S, sizeof(wav_t));
+    uint32_t *frames = (uint32_t *)calloc((size_t)S, sizeof(uint32_t));
+    char **data = (char **)calloc((size_t)S, sizeof(char *));
+    bytes_t *outs = (bytes_t *)calloc((size_t)S, sizeof(bytes_t));
+    if (!wavs || !frames || !data || !outs) { fprintf(stderr, "out of memory\n"); return 1; }
+    for (int i = 0; i < ninputs; i++) {
+        if (wav_open(&wavs[i], inputs[i])) { fprintf(stderr, "cannot read %s as PCM WAV\n", inputs[i]); return 1; }
+        if (i && (wavs[i].channels != wavs[0].channels || wavs[i].rate != wavs[0].rate || wavs[i].bps != wavs[0].bps)) {
+            fprintf(stderr, "%s: a set's inputs must share channels, sample rate and bits per sample\n", inputs[i]);
+            return 1;
+        }
+    }
+    s.channels = ninputs ? wavs[0].channels : channels;
+    s.sample_rate = ninputs ? wavs[0].rate : 44100;
+    s.bits_per_sample = ninputs ? wavs[0].bps : bps;
+    s.params.compression = level;
+    if (flake_amd_set_defaults(&s.params)) return 1;
+    if (bsize > 0) s.params.block_size = bsize;
+    if (flake_amd_validate_params(&s) < 0) { fprintf(stderr, "invalid parameters\n"); return 1; }
+    const int bs = s.params.block_size, nch = s.channels, narrow = s.bits_per_sample <= 16;
+    const int sample_bytes = narrow ? 2 : 4;
+    /* every input whole in memory (a harness): int16 samples where the files hold 16 bits or fewer */
+    for (int i = 0; i < S; i++) {
+        frames[i] = ninputs ? wavs[i].frames : (uint32_t)synth * (uint32_t)bs;
+        const size_t vals = (size_t)frames[i] * nch;
+        data[i] = (char *)malloc((vals ? vals : 1) * sample_bytes);
+        int32_t *wide = (!ninputs || !narrow) ? (int32_t *)malloc((vals ? vals : 1) * sizeof(int32_t)) : NULL;
+        if (!data[i] || ((!ninputs || !narrow) && !wide)) { fprintf(stderr, "out of memory\n"); return 1; }
+        if (ninputs) {
+            frames[i] = wav_read(&wavs[i], wide, narrow ? (int16_t *)data[i] : NULL, frames[i]);
+            fclose(wavs[i].f);
+        } else {
+            /* stream i: the synthetic signal from frame index i * FRAMES on, so the streams differ */
+            flake_amd_synth_pcm(wide, (int64_t)i * synth, synth, bs, nch, s.bits_per_sample);
+        }
+        if (wide && narrow) for (size_t k = 0; k < vals; k++) ((int16_t *)data[i])[k] = (int16_t)wide[k];
+        else if (wide) memcpy(data[i], wide, (size_t)frames[i] * nch * sizeof(int32_t));
+        free(wide);
+    }
+    /* the stream header of the single-input form (flake.c:558), STREAMINFO rewritten per stream below */
+    const int hlen = flake_amd_encode_init(&s);
+    if (hlen < 0) { fprintf(stderr, "encoder init failed (%d)\n", hlen); return 1; }
+    uint8_t *header = (uint8_t *)malloc((size_t)hlen);
+    memcpy(header, s.header, (size_t)hlen);
+    flake_amd_encode_close(&s);
+
+    set_run r;
+    memset(&r, 0, sizeof r);
+    r.g = flake_amd_set_open(&s, S, 0);
+    if (!r.g) { fprintf(stderr, "%s\n", flake_amd_set_last_error(NULL)); return 1; }
+    r.sample_bytes = sample_bytes; r.bs = bs; r.nch = nch; r.cap_blocks = 1024; r.outs = outs;
+    r.pcm = (char *)malloc((size_t)r.cap_blocks * bs * nch * sample_bytes);
+    r.stream_of = (int *)malloc(sizeof(int) * (size_t)r.cap_blocks);
+    r.sizes = (int *)malloc(sizeof(int) * (size_t)r.cap_blocks);
+    r.buf_cap = (size_t)r.cap_blocks * bs * nch * 5 + 65536;
+    r.buf = (uint8_t *)malloc(r.buf_cap);
+    if (!r.pcm || !r.stream_of || !r.sizes || !r.buf) { fprintf(stderr, "out of memory\n"); return 1; }
+    const size_t bbytes = (size_t)bs * nch * sample_bytes;
+    uint32_t rounds = 0;
+    for (int i = 0; i < S; i++) if (frames[i] / (uint32_t)bs > rounds) rounds = frames[i] / (uint32_t)bs;
+    for (uint32_t k = 0; k < rounds; k++)                       /* whole blocks, round-robin over the streams */
+        for (int i = 0; i < S; i++)
+            if (k < frames[i] / (uint32_t)bs && set_add(&r, i, data[i] + (size_t)k * bbytes, bs)) return 1;
+    if (set_flush(&r, bs)) return 1;
+    for (int i = 0; i < S; i++) {                               /* tails: streams of equal tail length share calls */
+        const int tail = (int)(frames[i] % (uint32_t)bs);
+        int seen = 0;
+        for (int j = 0; j < i && !seen; j++) seen = (int)(frames[j] % (uint32_t)bs) == tail;
+        if (!tail || seen) continue;
+        for (int j = i; j < S; j++)
+            if ((int)(frames[j] % (uint32_t)bs) == tail &&
+                set_add(&r, j, data[j] + (size_t)(frames[j] / (uint32_t)bs) * bbytes, tail)) return 1;
+        if (set_flush(&r, tail)) return 1;
+    }
+    unsigned long long total_in = 0, total_out = 0;
+    for (int i = 0; i < S; i++) {
+        char path[4096];
+        if (ninputs) {
+            const char *base = strrchr(inputs[i], '/');
+            base = base ? base + 1 : inputs[i];
+            size_t len = strlen(base);
+            if (len > 4 && !strcmp(base + len - 4, ".wav")) len -= 4;
+            snprintf(path, sizeof path, "%s/%.*s.flac", outdir, (int)len, base);
+        } else {
+            snprintf(path, sizeof path, "%s/stream%05d.flac", outdir, i);
+        }
+        FlakeAmdStreaminfo si;
+        if (flake_amd_set_get_streaminfo(r.g, i, &si)) { fprintf(stderr, "%s\n", flake_amd_set_last_error(r.g)); return 1; }
+        flake_amd_write_streaminfo(&si, header + 8);            /* flake.c:668-679 */
+        FILE *fo = fopen(path, "wb");
+        if (!fo) { perror(path); return 1; }
+        fwrite(header, 1, (size_t)hlen, fo);
+        fwrite(outs[i].p, 1, outs[i].n, fo);
+        fclose(fo);
+        total_in += frames[i]; total_out += (unsigned long long)hlen + outs[i].n;
+        free(outs[i].p); free(data[i]);
+    }
+    fprintf(stderr, "%d streams, %llu sample-frames -> %llu bytes (ratio %.3f)\n", S, total_in, total_out,
+            total_in ? (double)total_out / ((double)total_in * nch * ((s.bits_per_sample + 7) / 8)) : 0.0);
+    flake_amd_set_close(r.g);
+    free(r.pcm); free(r.stream_of); free(r.sizes); free(r.buf); free(header);
+    free(wavs); free(frames); free(data); free(outs);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     FlakeAmdContext s;
     memset(&s, 0, sizeof s);
-    int level = 5, bsize = -1, synth = 0, channels = 2, bps = 16, verify = 0;
-    const char *in = NULL, *out = NULL;
+    int level = 5, bsize = -1, synth = 0, channels = 2, bps = 16, verify = 0, synth_streams = 0;
+    const char *in = NULL, *out = NULL, *setdir = NULL;
+    for (int i = 1; i < argc; i++) if (!strcmp(argv[i], "--set")) setdir = "";
+    if (setdir) {
+        char **inputs = (char **)calloc((size_t)argc, sizeof(char *));
+        int ninputs = 0;
+        setdir = NULL;
+        for (int i = 1; i < argc; i++) {
+            if (argv[i][0] == '-' && argv[i][1] >= '0' && argv[i][1] <= '9') level = atoi(argv[i] + 1);
+            else if (!strcmp(argv[i], "-b") && i + 1 < argc) bsize = atoi(argv[++i]);
+            else if (!strcmp(argv[i], "--set") && i + 1 < argc) setdir = argv[++i];
+            else if (!strcmp(argv[i], "--synth") && i + 1 < argc) synth = atoi(argv[++i]);
+            else if (!strcmp(argv[i], "--synth-streams") && i + 1 < argc) synth_streams = atoi(argv[++i]);
+            else if (!strcmp(argv[i], "--channels") && i + 1 < argc) channels = atoi(argv[++i]);
+            else if (!strcmp(argv[i], "--bps") && i + 1 < argc) bps = atoi(argv[++i]);
+            else inputs[ninputs++] = argv[i];
+        }
+        if (!setdir || (!ninputs && (synth_streams < 1 || synth < 1)) || (ninputs && synth_streams)) {
+            fprintf(stderr, "usage: %s [-0..-8] [-b blocksize] --set OUTDIR (in1.wav in2.wav ... | --synth-streams S --synth FRAMES [--channels C] [--bps B])\n", argv[0]);
+            return 2;
+        }
+        return run_set(setdir, inputs, ninputs, synth_streams, synth, level, bsize, channels, bps);
+    }
     for (int i = 1; i < argc; i++) {
         if (argv[i][0] == '-' && argv[i][1] >= '0' && argv[i][1] <= '9') level = atoi(argv[i] + 1);
         else if (!strcmp(argv[i], "-b") && i + 1 < argc) bsize = atoi(argv[++i]);

@@ -1,0 +1,280 @@
+/*
+ * flake_set.c -- the stream set of include/flake_amd.h: one batch path for many independent streams that share
+ * their parameters (a library of files, not one long file).
+ *
+ * A batch is nblocks blocks back to back, block b belonging to stream stream_of_block[b].  The encode side needs
+ * nothing new -- frames are independent and fhip_batch.frame_numbers numbers each one explicitly -- so the set keeps
+ * what libflake keeps per stream (frame counter, sample count, min / max frame size, the last-block latch:
+ * encode.c:967-992) and hands the batch to the packed path in chunks.  The MD5 (encode.c:1006, metadata.c:61-62) is
+ * sequential inside a stream and independent across streams: each stream's running hash lives on the device (K6,
+ * fhip_md5_state), updated from the PCM the chunk's upload has already brought there, beside the chunk's encode
+ * kernels.  The samples cross the link once and the host hashes nothing.
+ */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "flake_amd.h"
+#include "flakehip.h"
+#include "host_internal.h"
+
+struct FlakeAmdSet {
+    fhip_ctx *hip;
+    fhip_params hp;
+    int nstreams;
+    unsigned flags;
+    int max_batch;                        /* blocks per GPU batch (FLAKE_AMD_BATCH, default 1024) */
+    int pcm_format;
+    int verbatim_size;                    /* of a full block: where max_frame_size starts (encode.c:446-450) */
+    int broken;                           /* a device call failed half way: the streams' state is unknown */
+    /* per stream */
+    uint32_t *frame_count;
+    uint64_t *samples;
+    int *min_frame, *max_frame;
+    char *ended;
+    int *scratch;                         /* [nstreams + 1] blocks per stream in a call / a chunk's CSR rows */
+    fa_md5 *host_md5;                     /* FLAKE_AMD_SET_MD5_HOST */
+    fhip_md5_state *dev_md5;              /* device memory */
+    uint8_t *digests;                     /* [nstreams][16], fetched for all streams at once ... */
+    int digests_valid;                    /* ... by the first request after an encode */
+    /* per call, grown on demand */
+    uint32_t *fnum;
+    int32_t *fbytes;
+    int32_t *seg_block;
+    int cap_blocks;
+    char err[256];
+};
+
+static __thread char open_err[256];
+
+FLAKE_AMD_API const char *flake_amd_set_last_error(const FlakeAmdSet *g) { return g ? g->err : open_err; }
+
+FLAKE_AMD_API void flake_amd_set_close(FlakeAmdSet *g)
+{
+    if (!g) return;
+    if (g->hip) {
+        (void)fhip_sync(g->hip);
+        (void)fhip_frames_packed_fetch_wait(g->hip);
+        if (g->dev_md5) fhip_device_free(g->dev_md5);
+        fhip_destroy(g->hip);
+    }
+    free(g->frame_count); free(g->samples); free(g->min_frame); free(g->max_frame); free(g->ended);
+    free(g->scratch); free(g->host_md5); free(g->digests); free(g->fnum); free(g->fbytes); free(g->seg_block);
+    free(g);
+}
+
+FLAKE_AMD_API FlakeAmdSet *flake_amd_set_open(const FlakeAmdContext *like, int nstreams, unsigned flags)
+{
+    open_err[0] = 0;
+#define OPEN_FAIL(...) do { snprintf(open_err, sizeof open_err, __VA_ARGS__); flake_amd_set_close(g); return NULL; } while (0)
+    FlakeAmdSet *g = NULL;
+    if (!like || flake_amd_validate_params(like) < 0) OPEN_FAIL("flake_amd_set_open: invalid parameters (flake_validate_params)");
+    if (nstreams < 1) OPEN_FAIL("flake_amd_set_open: nstreams must be at least 1");
+    if ((flags & ~(FLAKE_AMD_SET_MD5_HOST | FLAKE_AMD_SET_MD5_OFF)) ||
+        (flags & (FLAKE_AMD_SET_MD5_HOST | FLAKE_AMD_SET_MD5_OFF)) == (FLAKE_AMD_SET_MD5_HOST | FLAKE_AMD_SET_MD5_OFF))
+        OPEN_FAIL("flake_amd_set_open: unknown or contradictory flags");
+    if (like->params.variable_block_size || like->params.allow_vbs)
+        OPEN_FAIL("flake_amd_set_open: variable block size (levels 9-12) is not supported for stream sets");
+    {
+        const char *eha = getenv("FLAKE_AMD_HOST_ASSEMBLY"), *ehv = getenv("FLAKE_AMD_HOST_VBS");
+        if ((eha && eha[0] == '1') || (ehv && ehv[0] == '1'))
+            OPEN_FAIL("flake_amd_set_open: stream sets are not supported with FLAKE_AMD_HOST_ASSEMBLY / "
+                      "FLAKE_AMD_HOST_VBS (CPU comparison modes)");
+    }
+    g = (FlakeAmdSet *)calloc(1, sizeof *g);
+    if (!g) OPEN_FAIL("flake_amd_set_open: out of host memory");
+    g->nstreams = nstreams;
+    g->flags = flags;
+    fhip_params *hp = &g->hp;
+    hp->channels = like->channels; hp->sample_rate = like->sample_rate;
+    hp->bits_per_sample = like->bits_per_sample; hp->block_size = like->params.block_size;
+    hp->order_method = like->params.order_method; hp->stereo_method = like->params.stereo_method;
+    hp->prediction_type = like->params.prediction_type;
+    hp->min_prediction_order = like->params.min_prediction_order;
+    hp->max_prediction_order = like->params.max_prediction_order;
+    hp->min_partition_order = like->params.min_partition_order;
+    hp->max_partition_order = like->params.max_partition_order;
+    hp->variable_block_size = 0; hp->allow_vbs = 0;
+    hp->lpc_precision = 15;                                       /* encode.c:443 */
+    {
+        const int bps = hp->bits_per_sample, n = hp->block_size;  /* encode.c:521-527 */
+        g->verbatim_size = hp->channels == 2 ? 16 + ((n * (bps + bps + 1) + 7) >> 3)
+                                             : 16 + ((n * hp->channels * bps + 7) >> 3);
+    }
+    const char *eb = getenv("FLAKE_AMD_BATCH"), *ed = getenv("FLAKE_AMD_DEVICE");
+    g->max_batch = eb ? atoi(eb) : 1024;
+    if (g->max_batch < 1) g->max_batch = 1;
+    const int rc = fhip_create(&g->hip, ed ? atoi(ed) : 0, hp, g->max_batch);
+    if (rc != FHIP_OK) { g->hip = NULL; OPEN_FAIL("flake_amd_set_open: fhip_create: %s", fhip_strerror(rc)); }
+    const size_t ns = (size_t)nstreams;
+    g->frame_count = (uint32_t *)calloc(ns, sizeof(uint32_t));
+    g->samples = (uint64_t *)calloc(ns, sizeof(uint64_t));
+    g->min_frame = (int *)calloc(ns, sizeof(int));
+    g->max_frame = (int *)calloc(ns, sizeof(int));
+    g->ended = (char *)calloc(ns, 1);
+    g->scratch = (int *)calloc(ns + 1, sizeof(int));
+    g->digests = (uint8_t *)calloc(ns, 16);
+    if (!g->frame_count || !g->samples || !g->min_frame || !g->max_frame || !g->ended || !g->scratch || !g->digests)
+        OPEN_FAIL("flake_amd_set_open: out of host memory");
+    for (int s = 0; s < nstreams; s++) g->max_frame[s] = g->verbatim_size;
+    if (flags & FLAKE_AMD_SET_MD5_HOST) {
+        g->host_md5 = (fa_md5 *)calloc(ns, sizeof(fa_md5));
+        if (!g->host_md5) OPEN_FAIL("flake_amd_set_open: out of host memory");
+        for (int s = 0; s < nstreams; s++) fa_md5_init(&g->host_md5[s]);
+    } else if (!(flags & FLAKE_AMD_SET_MD5_OFF)) {
+        g->dev_md5 = (fhip_md5_state *)fhip_device_alloc(ns * sizeof(fhip_md5_state));
+        if (!g->dev_md5) OPEN_FAIL("flake_amd_set_open: no device memory for %d MD5 states", nstreams);
+        const int r2 = fhip_md5_init_dev(g->hip, g->dev_md5, nstreams);
+        if (r2 != FHIP_OK) OPEN_FAIL("flake_amd_set_open: fhip_md5_init_dev: %s (%s)", fhip_strerror(r2), fhip_last_error(g->hip));
+    }
+    g->digests_valid = 1;                 /* of the empty message, or zeros: set below / on request */
+    if (g->dev_md5) g->digests_valid = 0;
+    if (g->host_md5) for (int s = 0; s < nstreams; s++) fa_md5_final(&g->host_md5[s], g->digests + 16 * (size_t)s);
+    return g;
+#undef OPEN_FAIL
+}
+
+static int grow_call_tables(FlakeAmdSet *g, int nblocks)
+{
+    if (nblocks <= g->cap_blocks) return 0;
+    free(g->fnum); free(g->fbytes); free(g->seg_block);
+    g->cap_blocks = 0;
+    g->fnum = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)nblocks);
+    g->fbytes = (int32_t *)malloc(sizeof(int32_t) * (size_t)nblocks);
+    g->seg_block = (int32_t *)malloc(sizeof(int32_t) * (size_t)nblocks);
+    if (!g->fnum || !g->fbytes || !g->seg_block) return -1;
+    g->cap_blocks = nblocks;
+    return 0;
+}
+
+#define SET_FAIL(...) do { snprintf(g->err, sizeof g->err, __VA_ARGS__); return -1; } while (0)
+
+FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples, int sample_bytes, int nblocks,
+                                             int block_size, const int *stream_of_block, unsigned char *out,
+                                             size_t out_size, int *frame_sizes)
+{
+    if (!g) return -1;
+    g->err[0] = 0;
+    if (g->broken) SET_FAIL("flake_amd_set_encode: an earlier device error left the set unusable");
+    if (nblocks < 0 || (nblocks > 0 && (!samples || !stream_of_block || !out)))
+        SET_FAIL("flake_amd_set_encode: null argument or negative block count");
+    if (sample_bytes != 4 && sample_bytes != 2) SET_FAIL("flake_amd_set_encode: sample_bytes must be 4 or 2");
+    if (sample_bytes == 2 && g->hp.bits_per_sample > 16)
+        SET_FAIL("flake_amd_set_encode: int16 samples need bits_per_sample <= 16");
+    if (block_size < 1 || block_size > g->hp.block_size)
+        SET_FAIL("flake_amd_set_encode: block_size out of range (encode.c:987)");
+    if (nblocks == 0) return 0;
+    /* everything is checked before anything changes: the streams exist, none has ended (encode.c:989), and a
+     * short block -- which ends its stream (encode.c:991-992) -- is its stream's only block of the call */
+    const int is_short = block_size != g->hp.block_size;
+    int *per = g->scratch;
+    memset(per, 0, sizeof(int) * (size_t)g->nstreams);
+    for (int b = 0; b < nblocks; b++) {
+        const int s = stream_of_block[b];
+        if (s < 0 || s >= g->nstreams) SET_FAIL("flake_amd_set_encode: stream_of_block[%d] = %d is outside the set's %d streams", b, s, g->nstreams);
+        if (g->ended[s] || (is_short && per[s]))
+            SET_FAIL("flake_amd_set_encode: block %d belongs to stream %d, which a short block has ended", b, s);
+        per[s]++;
+    }
+    if (grow_call_tables(g, nblocks)) SET_FAIL("flake_amd_set_encode: out of host memory");
+    const int fmt = sample_bytes == 2 ? FHIP_PCM_S16 : FHIP_PCM_S32;
+    if (fmt != g->pcm_format) {
+        const int rc = fhip_set_pcm_format(g->hip, fmt);
+        if (rc != FHIP_OK) SET_FAIL("fhip_set_pcm_format: %s (%s)", fhip_strerror(rc), fhip_last_error(g->hip));
+        g->pcm_format = fmt;
+    }
+    /* frame numbers: each stream counts its own frames (encode.c:969-975) */
+    memset(per, 0, sizeof(int) * (size_t)g->nstreams);
+    for (int b = 0; b < nblocks; b++) {
+        const int s = stream_of_block[b];
+        g->fnum[b] = g->frame_count[s] + (uint32_t)per[s]++;
+    }
+    const size_t bstride = (size_t)block_size * (size_t)g->hp.channels * (size_t)sample_bytes;
+    long long total = 0;
+    int rc = FHIP_OK;
+    const char *what = "";
+    for (int b0 = 0; b0 < nblocks && rc == FHIP_OK; b0 += g->max_batch) {
+        const int cnt = nblocks - b0 < g->max_batch ? nblocks - b0 : g->max_batch;
+        fhip_batch bt;
+        memset(&bt, 0, sizeof bt);
+        bt.pcm = (const int32_t *)((const char *)samples + (size_t)b0 * bstride);
+        bt.nframes = cnt; bt.block_size = block_size;
+        bt.frame_bytes = g->fbytes + b0;
+        bt.frame_numbers = g->fnum + b0;
+        what = "fhip_frames_packed_upload";
+        rc = fhip_frames_packed_upload(g->hip, &bt);
+        if (rc == FHIP_OK && g->dev_md5) {
+            /* the chunk's blocks per stream, in batch order (CSR), for the hash that runs beside the encode kernels */
+            int *first = g->scratch;
+            memset(first, 0, sizeof(int) * ((size_t)g->nstreams + 1));
+            for (int b = 0; b < cnt; b++) first[stream_of_block[b0 + b] + 1]++;
+            for (int s = 0; s < g->nstreams; s++) first[s + 1] += first[s];
+            for (int b = 0; b < cnt; b++) g->seg_block[first[stream_of_block[b0 + b]]++] = b;
+            for (int s = g->nstreams; s > 0; s--) first[s] = first[s - 1];      /* the fill moved every row's start up */
+            first[0] = 0;
+            what = "fhip_md5_update_uploaded";
+            rc = fhip_md5_update_uploaded(g->hip, g->dev_md5, g->nstreams, cnt, block_size, (const int32_t *)first, g->seg_block);
+        }
+        int64_t bytes = 0;
+        if (rc == FHIP_OK) { what = "fhip_frames_packed_begin"; rc = fhip_frames_packed_begin(g->hip, &bt, &bytes); }
+        if (rc == FHIP_OK && (size_t)(total + bytes) > out_size) {
+            (void)fhip_frames_packed_fetch_wait(g->hip);
+            g->broken = g->dev_md5 != NULL;          /* (its hashes have moved on) */
+            SET_FAIL("flake_amd_set_encode: output buffer too small (%lld bytes needed so far, %zu given)",
+                     total + (long long)bytes, out_size);
+        }
+        /* (not waited for here: the download runs beside the next chunk's upload) */
+        if (rc == FHIP_OK) { what = "fhip_frames_packed_fetch_async"; rc = fhip_frames_packed_fetch_async(g->hip, out + total, (int64_t)(out_size - (size_t)total)); }
+        if (rc == FHIP_OK) total += bytes;
+    }
+    const int rcw = fhip_frames_packed_fetch_wait(g->hip);
+    if (rc == FHIP_OK && rcw != FHIP_OK) { rc = rcw; what = "fhip_frames_packed_fetch_wait"; }
+    if (rc != FHIP_OK) {
+        g->broken = 1;
+        SET_FAIL("%s: %s (%s)", what, fhip_strerror(rc), fhip_last_error(g->hip));
+    }
+    for (int b = 0; b < nblocks; b++)
+        if (g->fbytes[b] <= 0) { g->broken = 1; SET_FAIL("flake_amd_set_encode: frame %d was not encoded", b); }
+    /* the batch is part of its streams now */
+    const size_t nvals = (size_t)block_size * (size_t)g->hp.channels;
+    for (int b = 0; b < nblocks; b++) {
+        const int s = stream_of_block[b], fs = g->fbytes[b];
+        if (frame_sizes) frame_sizes[b] = fs;
+        if (fs > g->max_frame[s]) g->max_frame[s] = fs;                     /* encode.c:967 */
+        if (!g->min_frame[s] || fs < g->min_frame[s]) g->min_frame[s] = fs;
+        g->frame_count[s]++;
+        g->samples[s] += (uint64_t)block_size;
+        if (is_short) g->ended[s] = 1;
+        if (g->host_md5) {
+            const char *p = (const char *)samples + (size_t)b * bstride;
+            if (sample_bytes == 2) fa_md5_pcm16(&g->host_md5[s], (const int16_t *)p, nvals, g->hp.bits_per_sample);
+            else fa_md5_pcm(&g->host_md5[s], (const int32_t *)p, nvals, g->hp.bits_per_sample);
+        }
+    }
+    if (g->host_md5) for (int s = 0; s < g->nstreams; s++) fa_md5_final(&g->host_md5[s], g->digests + 16 * (size_t)s);
+    if (g->dev_md5) g->digests_valid = 0;
+    return total;
+}
+
+FLAKE_AMD_API int flake_amd_set_get_streaminfo(FlakeAmdSet *g, int stream, FlakeAmdStreaminfo *si)
+{
+    if (!g || !si) return -1;
+    g->err[0] = 0;
+    if (stream < 0 || stream >= g->nstreams) SET_FAIL("flake_amd_set_get_streaminfo: no stream %d in a set of %d", stream, g->nstreams);
+    if (!g->digests_valid) {
+        /* one finalisation and one read-back for ALL streams: a caller walking the set pays one synchronisation */
+        const int rc = fhip_md5_final(g->hip, g->dev_md5, g->nstreams, g->digests);
+        if (rc != FHIP_OK) SET_FAIL("fhip_md5_final: %s (%s)", fhip_strerror(rc), fhip_last_error(g->hip));
+        g->digests_valid = 1;
+    }
+    si->min_block_size = (unsigned)g->hp.block_size;
+    si->max_block_size = (unsigned)g->hp.block_size;
+    si->min_frame_size = 0;                                       /* as flake_amd_get_streaminfo leaves it */
+    si->max_frame_size = (unsigned)g->max_frame[stream];
+    si->sample_rate = (unsigned)g->hp.sample_rate;
+    si->channels = (unsigned)g->hp.channels;
+    si->bits_per_sample = (unsigned)g->hp.bits_per_sample;
+    si->samples = (unsigned)g->samples[stream];
+    memcpy(si->md5sum, g->digests + 16 * (size_t)stream, 16);     /* zeros under FLAKE_AMD_SET_MD5_OFF */
+    return 0;
+}

@@ -422,6 +422,57 @@ FHIP_API int fhip_verify_frames(fhip_ctx *ctx, const fhip_verify_in *in, const f
  */
 FHIP_API int fhip_set_verify(fhip_ctx *ctx, int on);
 
+/* ---- MD5 of many streams (K6) ---------------------------------------- */
+
+/*
+ * STREAMINFO's MD5 (metadata.c:61-62, md5.c:281-320) is sequential inside a stream and independent across
+ * streams: the device carries one running hash per stream, one lane each, and reads the samples where the
+ * encoder already has them.  fhip_md5_state is the device twin of the host's running state; callers allocate
+ * nstreams of them in DEVICE memory (16-byte aligned, as hipMalloc gives) and treat the contents as opaque.
+ */
+typedef struct fhip_md5_state {
+    uint32_t h[4];               /* the chaining value */
+    uint64_t nbytes;             /* message bytes so far */
+    uint32_t fill;               /* bytes waiting in tail[], 0..63 */
+    uint32_t reserved;
+    uint8_t  tail[64];           /* the partial block */
+} fhip_md5_state;                /* 96 bytes: records and their tails stay 16-byte aligned */
+
+/* All pointers DEVICE pointers; asynchronous on the handle's stream (fhip_set_stream), no host synchronisation.
+ *   _init    states[0 .. nstreams) = the empty message
+ *   _update  stream s absorbs, in this order, the blocks seg_block[seg_first[s] .. seg_first[s + 1]) (int32
+ *            tables, CSR; seg_first[nstreams + 1] entries): indices of block_size-sample blocks of pcm, i.e. block b
+ *            is the block_size * channels interleaved samples at pcm + b * block_size * channels.  pcm follows the
+ *            handle's format (fhip_set_pcm_format); channels and bits_per_sample are the handle's.  The message
+ *            is the low (bits_per_sample + 7) / 8 bytes of every sample, little-endian (md5.c:281-320).  A stream
+ *            with no block keeps its state bit for bit.  Nothing checks the indices against the buffer: they are
+ *            the caller's, like every device table.  When a block is a whole number of 64-byte MD5 blocks, pcm is
+ *            16-byte aligned and no stream of the call holds a partial block, the kernel builds the message in
+ *            registers from 16-byte loads ("fast" in fhip_last_launches); otherwise bytes go through each stream's
+ *            tail ("general": correct, not tuned).
+ *   _final   digests[s][0 .. 16) from a padded copy of state s; the states stay usable (metadata.c:61-62).
+ * FHIP_E_INVALID for null pointers, negative counts, block_size < 1 or > FHIP_MAX_BLOCK; nothing is queued then. */
+FHIP_API int fhip_md5_init_dev(fhip_ctx *ctx, fhip_md5_state *states, int nstreams);
+FHIP_API int fhip_md5_update_dev(fhip_ctx *ctx, fhip_md5_state *states, int nstreams, const void *pcm,
+                                 int block_size, const int32_t *seg_first, const int32_t *seg_block);
+FHIP_API int fhip_md5_final_dev(fhip_ctx *ctx, const fhip_md5_state *states, int nstreams, uint8_t *digests);
+/* _final with a HOST digests[nstreams][16] (states stay device memory): finalises, copies, synchronises -- once
+ * for all streams. */
+FHIP_API int fhip_md5_final(fhip_ctx *ctx, const fhip_md5_state *states, int nstreams, uint8_t *digests);
+/* Device memory on the current device for callers without a HIP runtime of their own (the host C layer keeps its
+ * set's fhip_md5_state array there); NULL when the runtime refuses.  No handle needed. */
+FHIP_API void *fhip_device_alloc(size_t bytes);
+FHIP_API void fhip_device_free(void *p);
+/* The same update for the packed host path, without a second upload: hashes the PCM that this handle's last
+ * fhip_frames_packed_upload brought to the device (nblocks blocks of block_size samples; both must match that
+ * upload, which must not have been consumed by fhip_frames_packed_begin or displaced by another entry yet:
+ * FHIP_E_INVALID otherwise).  seg_first [nstreams + 1] / seg_block [seg_first[nstreams]] are HOST tables, checked
+ * against nblocks; states are device memory.  Runs on an internal stream of the handle, beside the kernels of the
+ * fhip_frames_packed_begin that follows; it only reads the PCM, and the handle's next upload orders itself behind
+ * it.  Updates of the same states through one handle run in call order. */
+FHIP_API int fhip_md5_update_uploaded(fhip_ctx *ctx, fhip_md5_state *states, int nstreams, int nblocks,
+                                      int block_size, const int32_t *seg_first, const int32_t *seg_block);
+
 /* ---- measurement ---------------------------------------------------- */
 
 /* With profiling on, every kernel launch of the hot path is bracketed by
@@ -437,7 +488,9 @@ FHIP_API int fhip_get_kernel_times(fhip_ctx *ctx, const char **names, double *ms
  * one or two workgroups per tile), "tail" (K2 runs inside K1), "fused" (K1 applies K0's decisions),
  * "narrow" (16-bit sample rows).  The calls that start a new list are the encode entries
  * (fhip_encode_subframes*, fhip_frames_packed_begin / fhip_encode_frames_packed, the VBS entries)
- * and fhip_prepare_ahead.  A host-side record: it adds no device work.  names[0 .. cap) receive
+ * and fhip_prepare_ahead, and the fhip_md5_* entries.  A host-side record: it adds no device work.  (One exception:
+ * "k_md5_streams<int16_t,2> fast" / "... general" name a choice that is made on the device when the block shape
+ * allows the fast path; asking for the list then waits for that launch.)  names[0 .. cap) receive
  * strings owned by the handle, valid until its next such call; returns the number of launches. */
 FHIP_API int fhip_last_launches(fhip_ctx *ctx, const char **names, int cap);
 
