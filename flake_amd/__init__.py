@@ -201,6 +201,9 @@ def load_library() -> C.CDLL:
         "fhip_set_verify": (i, [vp, i]),
         "fhip_verify_frames_dev": (i, [vp, C.POINTER(VerifyIn), C.POINTER(VerifyOut)]),
         "fhip_verify_frames": (i, [vp, C.POINTER(VerifyIn), C.POINTER(VerifyOut)]),
+        "fhip_verify_frames_numbered_dev": (i, [vp, C.POINTER(VerifyIn), vp, C.POINTER(VerifyOut)]),
+        "fhip_verify_frames_numbered": (i, [vp, C.POINTER(VerifyIn), vp, C.POINTER(VerifyOut)]),
+        "fhip_last_verify_failure": (i, [vp, vp, vp]),
         "fhip_get_kernel_times": (i, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double),
                                       C.POINTER(i), i, i]),
         "fhip_last_launches": (i, [vp, C.POINTER(C.c_char_p), i]),
@@ -231,6 +234,7 @@ ABI_SYMBOLS = (
     "fhip_encode_blocks_vbs_dev", "fhip_order_search_bits",
     "fhip_host_alloc", "fhip_host_free", "fhip_host_register", "fhip_host_unregister", "fhip_frames_packed_upload", "fhip_frames_packed_fetch_async", "fhip_frames_packed_fetch_wait",
     "fhip_set_verify", "fhip_verify_frames_dev", "fhip_verify_frames", "fhip_last_launches",
+    "fhip_verify_frames_numbered_dev", "fhip_verify_frames_numbered", "fhip_last_verify_failure",
     "fhip_set_pcm_format",
     "fhip_md5_init_dev", "fhip_md5_update_dev", "fhip_md5_final_dev", "fhip_md5_final", "fhip_md5_update_uploaded",
     "fhip_device_alloc", "fhip_device_free",
@@ -318,17 +322,23 @@ class Encoder:
         self._check(self.lib.fhip_set_verify(self._h, int(on)), "fhip_set_verify")
 
     def verify_frames_dev(self, stream, stream_bytes: int, frame_bytes, nframes: int, pcm, nsamples: int,
-                          first_sample: int, summary, records=None) -> None:
+                          first_sample: int, summary, records=None, frame_numbers=None) -> None:
         """K5 on device-resident data (torch tensors or raw device addresses); async.  summary: int64[4]
         (frames checked, failed, first failing frame or -1, its status); records: VERIFY_REC_DTYPE-sized
-        int32[nframes][4], optional."""
+        int32[nframes][4], optional.  frame_numbers: device uint32[nframes], the number each frame must carry
+        (fhip_verify_frames_numbered_dev; first_sample is ignored then)."""
         vi = VerifyIn(_ptr(stream), stream_bytes, _ptr(frame_bytes), nframes, _ptr(pcm), nsamples, first_sample)
         vo = VerifyOut(_ptr(records), _ptr(summary))
+        if frame_numbers is not None:
+            self._check(self.lib.fhip_verify_frames_numbered_dev(self._h, C.byref(vi), _ptr(frame_numbers),
+                                                                 C.byref(vo)), "fhip_verify_frames_numbered_dev")
+            return
         self._check(self.lib.fhip_verify_frames_dev(self._h, C.byref(vi), C.byref(vo)), "fhip_verify_frames_dev")
 
-    def verify_frames(self, stream, frame_bytes, pcm, first_sample: int = 0):
+    def verify_frames(self, stream, frame_bytes, pcm, first_sample: int = 0, frame_numbers=None):
         """K5 on host data.  stream: uint8 bytes, frame_bytes: int32[nframes], pcm: [nsamples][channels]
-        int32.  Returns (ok, records as a VERIFY_REC_DTYPE array, summary int64[4], error text)."""
+        int32.  frame_numbers: uint32[nframes], the number each frame must carry (fhip_verify_frames_numbered).
+        Returns (ok, records as a VERIFY_REC_DTYPE array, summary int64[4], error text)."""
         st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
                                   else stream, dtype=np.uint8)
         fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
@@ -338,9 +348,16 @@ class Encoder:
         vi = VerifyIn(st.ctypes.data if st.size else None, st.size, fb.ctypes.data if fb.size else None, len(fb),
                       pc.ctypes.data if pc.size else None, pc.shape[0], first_sample)
         vo = VerifyOut(recs.ctypes.data if len(fb) else None, summary.ctypes.data)
-        rc = self.lib.fhip_verify_frames(self._h, C.byref(vi), C.byref(vo))
+        if frame_numbers is not None:
+            fn = np.ascontiguousarray(frame_numbers, dtype=np.uint32)
+            if len(fn) != len(fb):
+                raise ValueError("frame_numbers needs one entry per frame")
+            rc, what = self.lib.fhip_verify_frames_numbered(self._h, C.byref(vi), fn.ctypes.data if fn.size else None,
+                                                            C.byref(vo)), "fhip_verify_frames_numbered"
+        else:
+            rc, what = self.lib.fhip_verify_frames(self._h, C.byref(vi), C.byref(vo)), "fhip_verify_frames"
         if rc not in (OK, E_VERIFY):
-            self._check(rc, "fhip_verify_frames")
+            self._check(rc, what)
         return rc == OK, recs, summary, self.lib.fhip_last_error(self._h).decode() if rc else ""
 
     def kernel_times(self, reset: bool = True) -> dict:
@@ -566,6 +583,11 @@ def load_host_library() -> C.CDLL:
     lib.flake_amd_set_get_streaminfo.restype = C.c_int
     lib.flake_amd_set_last_error.argtypes = [C.c_void_p]
     lib.flake_amd_set_last_error.restype = C.c_char_p
+    lib.flake_amd_set_enable_verify.argtypes = [C.c_void_p, C.c_int]
+    lib.flake_amd_set_enable_verify.restype = C.c_int
+    lib.flake_amd_set_last_verify_failure.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint),
+                                                      C.POINTER(C.c_int)]
+    lib.flake_amd_set_last_verify_failure.restype = C.c_int
     lib.flake_amd_set_close.argtypes = [C.c_void_p]
     lib.flake_amd_set_close.restype = None
     _host = lib
@@ -737,6 +759,20 @@ class StreamSet:
         if w < 0:
             raise FlakeHipError(int(w), "flake_amd_set_encode", self.last_error())
         return out[:w].copy(), sizes[:nblocks]
+
+    def set_verify(self, on: bool) -> None:
+        """flake_amd_set_enable_verify: every later encode call verifies its frames on the device, each against
+        its own stream's frame counter."""
+        if self.lib.flake_amd_set_enable_verify(self._g, int(on)) != 0:
+            raise RuntimeError("flake_amd_set_enable_verify")
+
+    def last_verify_failure(self):
+        """(stream, frame number within it, FHIP_VERIFY_* status) of the frame that failed the last encode call's
+        verification, or None (flake_amd_set_last_verify_failure)."""
+        s, n, st = C.c_int(-1), C.c_uint(0), C.c_int(0)
+        if not self.lib.flake_amd_set_last_verify_failure(self._g, C.byref(s), C.byref(n), C.byref(st)):
+            return None
+        return s.value, n.value, st.value
 
     def streaminfo(self, stream: int) -> HostStreaminfo:
         si = HostStreaminfo()

@@ -125,6 +125,9 @@ struct fhip_ctx {
     DevBuf<uint8_t> d_vstream;                // fhip_verify_frames: the host stream / sizes / PCM uploaded
     DevBuf<int32_t> d_vfb;
     DevBuf<int32_t> d_vpcm;
+    DevBuf<uint32_t> d_vnum;                  // fhip_verify_frames_numbered: the host number table uploaded
+    long long vfail_sum[4] = {0, 0, -1, 0};   // fhip_last_verify_failure: the most recent verdict's summary ...
+    fhip_verify_rec vfail_rec{0, -1, -1, -1}; // ... and its first failing frame's record
 
     std::vector<std::string> launches;        // fhip_last_launches: what the most recent call queued
 
@@ -450,9 +453,11 @@ int ensure_verify(fhip_ctx *c, size_t nframes)
 
 // Queue K5 on the handle's stream.  block_size: the numbering unit of a fixed-block stream (the batch's block
 // size for the handle's own batches; params.block_size for a caller's stream).  recs null: the handle's own.
+// numbers (device, [nframes]; fixed-block handles only): the number each frame must carry, when the batch's
+// frames belong to several streams -- first_sample is unused then.  Null: numbered by position, as a single stream.
 int run_verify(fhip_ctx *c, const uint8_t *stream, long long stream_bytes, const int32_t *frame_bytes, int nframes,
                const long long *dev_count, const int32_t *pcm, long long nsamples, long long first_sample,
-               int block_size, fhip_verify_rec *recs, int64_t *summary, long long *totals)
+               int block_size, fhip_verify_rec *recs, int64_t *summary, long long *totals, const uint32_t *numbers)
 {
     int rc = ensure_verify(c, (size_t)nframes);
     if (rc != FHIP_OK) return rc;
@@ -460,7 +465,7 @@ int run_verify(fhip_ctx *c, const uint8_t *stream, long long stream_bytes, const
     fhip::VerifyArgs a{stream, stream_bytes, frame_bytes, nframes, dev_count, pcm, nsamples, first_sample,
                        p.channels, p.bits_per_sample, block_size, p.sample_rate, p.allow_vbs ? 1 : 0, c->pcm_format,
                        c->d_vws, recs ? recs : c->d_vrec, summary ? reinterpret_cast<long long *>(summary) : c->d_vsum,
-                       reinterpret_cast<unsigned long long *>(c->d_vsum + 4), totals};
+                       reinterpret_cast<unsigned long long *>(c->d_vsum + 4), totals, numbers};
     Prof pr(c, kProfVerify, c->profiling);
     HIP_TRY(c, fhip::launch_verify(c->stream, a));
     return FHIP_OK;
@@ -474,18 +479,26 @@ const char *verify_status_name(int s)
 }
 
 // After the stream synchronised: summary (host copy) -> FHIP_OK, or FHIP_E_VERIFY with the first failing frame
-// named in the handle's error text (its record read from recs, device).
-int verify_verdict(fhip_ctx *c, const long long *summary, const fhip_verify_rec *recs)
+// named in the handle's error text (its record read from recs, device).  numbers (HOST, optional): the table of a
+// numbered batch; the text then also says which number that frame had to carry.
+int verify_verdict(fhip_ctx *c, const long long *summary, const fhip_verify_rec *recs,
+                   const uint32_t *numbers = nullptr)
 {
+    for (int i = 0; i < 4; i++) c->vfail_sum[i] = summary[i];
+    c->vfail_rec = fhip_verify_rec{(int32_t)summary[3], -1, -1, -1};
     if (summary[1] <= 0) return FHIP_OK;
     fhip_verify_rec r{(int32_t)summary[3], -1, -1, -1};
     if (recs && summary[2] >= 0)
         HIP_TRY(c, hipMemcpy(&r, recs + summary[2], sizeof r, hipMemcpyDeviceToHost));
-    char buf[256];
+    c->vfail_rec = r;
+    char want[48] = "";
+    if (numbers && summary[2] >= 0) snprintf(want, sizeof want, ", required to carry number %u", numbers[summary[2]]);
+    char buf[320];
     snprintf(buf, sizeof buf,
-             "verification failed: %lld of %lld frames do not decode to the input; first: frame %lld, %s "
+             "verification failed: %lld of %lld frames do not decode to the input; first: frame %lld%s, %s "
              "(subframe %d, sample %d, bit %d)",
-             summary[1], summary[0], summary[2], verify_status_name((int)summary[3]), r.subframe, r.sample, r.bit);
+             summary[1], summary[0], summary[2], want, verify_status_name((int)summary[3]), r.subframe, r.sample,
+             r.bit);
     c->err = buf;
     return FHIP_E_VERIFY;
 }
@@ -1028,11 +1041,15 @@ int fhip_frames_packed_begin(fhip_ctx *c, const fhip_batch *b, int64_t *total_by
     HIP_TRY(c, fhip::launch_pack_frames(c->stream, c->d_frames, stride, c->d_fbytes, b->nframes,
                                         c->d_offsets, c->d_packed));
     long long vsum[4] = {0, 0, -1, 0};
+    // an explicit number table on a fixed-block handle: the frames may be of many streams, each is held to its own
+    // entry (the table is on the device already); a variable-block-size batch numbers samples and stays in sequence
+    const bool numbered = b->frame_numbers && !c->p.allow_vbs;
     if (c->verify) {
         const long long num0 = b->frame_numbers ? (long long)b->frame_numbers[0] : (long long)b->first_frame_number;
         const long long first = c->p.allow_vbs ? num0 : num0 * (long long)b->block_size;
         rc = run_verify(c, c->d_packed, (long long)fb, c->d_fbytes, b->nframes, nullptr, c->d_pcm,
-                        (long long)b->nframes * b->block_size, first, b->block_size, nullptr, nullptr, nullptr);
+                        (long long)b->nframes * b->block_size, numbered ? 0 : first, b->block_size, nullptr, nullptr,
+                        nullptr, numbered ? (const uint32_t *)c->d_fnum : nullptr);
         if (rc != FHIP_OK) return rc;
         HIP_TRY(c, hipMemcpyAsync(vsum, c->d_vsum, sizeof vsum, hipMemcpyDeviceToHost, c->stream));
     }
@@ -1045,7 +1062,7 @@ int fhip_frames_packed_begin(fhip_ctx *c, const fhip_batch *b, int64_t *total_by
     if (rc != FHIP_OK) return rc;
     c->packed_ready = total;
     *total_bytes = total;
-    return c->verify ? verify_verdict(c, vsum, c->d_vrec) : FHIP_OK;
+    return c->verify ? verify_verdict(c, vsum, c->d_vrec, numbered ? b->frame_numbers : nullptr) : FHIP_OK;
 }
 
 int fhip_frames_packed_fetch(fhip_ctx *c, uint8_t *out, int64_t out_cap)
@@ -1637,7 +1654,8 @@ int fhip_encode_blocks_vbs_dev(fhip_ctx *c, const int32_t *pcm, int nblocks, int
     if (rc != FHIP_OK || !c->verify) return rc;
     // totals[3] bit 2 when a frame fails; still no host synchronisation
     return run_verify(c, out->packed, (long long)out->packed_cap, fbytes, 8 * nblocks, totals, pcm,
-                      (long long)nblocks * block_size, first_frame_number, block_size, nullptr, nullptr, totals);
+                      (long long)nblocks * block_size, first_frame_number, block_size, nullptr, nullptr, totals,
+                      nullptr);
 }
 
 int fhip_encode_blocks_vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, int block_size,
@@ -1681,7 +1699,7 @@ int fhip_encode_blocks_vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, 
     if (c->verify) {
         rc = run_verify(c, c->d_packed, (long long)c->d_packed.cap, c->d_stream_bytes, 8 * nblocks, c->d_totals,
                         c->d_pcm, (long long)nblocks * block_size, first_frame_number, block_size, nullptr, nullptr,
-                        nullptr);
+                        nullptr, nullptr);
         if (rc != FHIP_OK) return rc;
         HIP_TRY(c, hipMemcpyAsync(vsum, c->d_vsum, sizeof vsum, hipMemcpyDeviceToHost, c->stream));
     }
@@ -1717,11 +1735,14 @@ int fhip_set_verify(fhip_ctx *c, int on)
 }
 
 namespace {
-int verify_check(fhip_ctx *c, const fhip_verify_in *in, const fhip_verify_out *out)
+int verify_check(fhip_ctx *c, const fhip_verify_in *in, const fhip_verify_out *out, bool numbered)
 {
     if (!c) return FHIP_E_INVALID;
     if (!in || !out || !out->summary) return fail(c, FHIP_E_INVALID, "null argument");
-    if (in->nframes < 0 || in->stream_bytes < 0 || in->nsamples < 0 || in->first_sample < 0)
+    if (numbered && c->p.allow_vbs)
+        return fail(c, FHIP_E_UNSUPPORTED, "a frame number table needs a fixed-block handle: a variable-block-size "
+                                           "stream numbers samples, and its frames are verified in sequence");
+    if (in->nframes < 0 || in->stream_bytes < 0 || in->nsamples < 0 || (!numbered && in->first_sample < 0))
         return fail(c, FHIP_E_INVALID, "negative count");
     if (in->nframes > 0 && (!in->stream || !in->frame_bytes)) return fail(c, FHIP_E_INVALID, "null stream");
     if (in->nsamples > 0 && !in->pcm) return fail(c, FHIP_E_INVALID, "null pcm");
@@ -1729,30 +1750,42 @@ int verify_check(fhip_ctx *c, const fhip_verify_in *in, const fhip_verify_out *o
 }
 }  // namespace
 
-int fhip_verify_frames_dev(fhip_ctx *c, const fhip_verify_in *in, const fhip_verify_out *out)
+int fhip_verify_frames_numbered_dev(fhip_ctx *c, const fhip_verify_in *in, const uint32_t *frame_numbers,
+                                    const fhip_verify_out *out)
 {
-    int rc = verify_check(c, in, out);
+    int rc = verify_check(c, in, out, frame_numbers != nullptr);
     if (rc != FHIP_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     return run_verify(c, in->stream, in->stream_bytes, in->frame_bytes, in->nframes, nullptr, in->pcm, in->nsamples,
-                      in->first_sample, c->p.block_size, out->frames, out->summary, nullptr);
+                      frame_numbers ? 0 : in->first_sample, c->p.block_size, out->frames, out->summary, nullptr,
+                      frame_numbers);
 }
 
-int fhip_verify_frames(fhip_ctx *c, const fhip_verify_in *in, const fhip_verify_out *out)
+int fhip_verify_frames_dev(fhip_ctx *c, const fhip_verify_in *in, const fhip_verify_out *out)
 {
-    int rc = verify_check(c, in, out);
+    return fhip_verify_frames_numbered_dev(c, in, nullptr, out);
+}
+
+int fhip_verify_frames_numbered(fhip_ctx *c, const fhip_verify_in *in, const uint32_t *frame_numbers,
+                                const fhip_verify_out *out)
+{
+    int rc = verify_check(c, in, out, frame_numbers != nullptr);
     if (rc != FHIP_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t sb = (size_t)in->stream_bytes, nf = (size_t)in->nframes;
     const size_t nv = (size_t)in->nsamples * (size_t)c->p.channels;
+    const bool numbered = frame_numbers && nf;
     HIP_TRY(c, c->d_vstream.reserve(sb));
     HIP_TRY(c, c->d_vfb.reserve(nf));
     HIP_TRY(c, c->d_vpcm.reserve(nv));
+    if (numbered) HIP_TRY(c, c->d_vnum.reserve(nf));
     if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_vstream, in->stream, sb, hipMemcpyHostToDevice, c->stream));
     if (nf) HIP_TRY(c, hipMemcpyAsync(c->d_vfb, in->frame_bytes, nf * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     if (nv) HIP_TRY(c, hipMemcpyAsync(c->d_vpcm, in->pcm, nv * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
+    if (numbered) HIP_TRY(c, hipMemcpyAsync(c->d_vnum, frame_numbers, nf * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     rc = run_verify(c, c->d_vstream, in->stream_bytes, c->d_vfb, in->nframes, nullptr, c->d_vpcm, in->nsamples,
-                    in->first_sample, c->p.block_size, nullptr, nullptr, nullptr);
+                    numbered ? 0 : in->first_sample, c->p.block_size, nullptr, nullptr, nullptr,
+                    numbered ? (const uint32_t *)c->d_vnum : nullptr);
     if (rc != FHIP_OK) return rc;
     long long sum[4] = {0, 0, -1, 0};
     HIP_TRY(c, hipMemcpyAsync(sum, c->d_vsum, sizeof sum, hipMemcpyDeviceToHost, c->stream));
@@ -1761,7 +1794,20 @@ int fhip_verify_frames(fhip_ctx *c, const fhip_verify_in *in, const fhip_verify_
     rc = fhip_sync(c);
     if (rc != FHIP_OK) return rc;
     for (int i = 0; i < 4; i++) out->summary[i] = sum[i];
-    return verify_verdict(c, sum, c->d_vrec);
+    return verify_verdict(c, sum, c->d_vrec, numbered ? frame_numbers : nullptr);
+}
+
+int fhip_verify_frames(fhip_ctx *c, const fhip_verify_in *in, const fhip_verify_out *out)
+{
+    return fhip_verify_frames_numbered(c, in, nullptr, out);
+}
+
+int fhip_last_verify_failure(const fhip_ctx *c, int64_t *summary, fhip_verify_rec *first)
+{
+    if (!c) return FHIP_E_INVALID;
+    if (summary) for (int i = 0; i < 4; i++) summary[i] = c->vfail_sum[i];
+    if (first) *first = c->vfail_rec;
+    return c->vfail_sum[1] > 0 ? 1 : 0;
 }
 
 int fhip_prepare_frames(fhip_ctx *c, const int32_t *pcm, int nframes, int n,

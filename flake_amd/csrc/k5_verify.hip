@@ -9,7 +9,8 @@
 //
 //   k_verify_frames  one workgroup: prefix of frame_bytes -> frame offsets, one lane per frame
 //                    parses its header (sync, codes, UTF-8 number, CRC-8) and numbering/coverage
-//                    is checked against the neighbouring frame; VerifyFrame records + summary init
+//                    is checked against the neighbouring frame -- or, with VerifyArgs.numbers, against
+//                    the frame's own entry of the table; VerifyFrame records + summary init
 //   k_verify         one workgroup (256 lanes) per frame: subframes, padding, CRC-16, length
 //   k_verify_final   summary[2..3] from the first failing frame; optional flag bit in totals[3]
 //
@@ -283,6 +284,7 @@ __global__ void __launch_bounds__(HDR_T) k_verify_frames(VerifyArgs a)
         count = d < 0 ? 0 : (d < (long long)a.nframes ? (int)d : a.nframes);
     }
     const int t = threadIdx.x;
+    const bool numbered = a.numbers && !a.allow_vbs;      // a launch-wide choice: every wave takes one branch
     if (t == 0) {
         a.summary[0] = count;
         a.summary[1] = 0;
@@ -312,7 +314,9 @@ __global__ void __launch_bounds__(HDR_T) k_verify_frames(VerifyArgs a)
             }
         }
         // numbering: fixed blocks carry frame numbers (frame f starts at f * block_size), a variable-block-size
-        // stream carries the first sample (the frame before says where this one starts)
+        // stream carries the first sample (the frame before says where this one starts).  With a number table
+        // (fixed blocks of many streams) frame f carries numbers[f] and its samples lie at f * block_size of pcm:
+        // nothing of a neighbouring frame is read
         const unsigned long long snum = a.allow_vbs ? h.number : h.number * (unsigned long long)a.block_size;
         s_next[t] = snum + (unsigned long long)h.n;
         s_ok[t] = h.status == FHIP_VERIFY_OK || h.status == FHIP_VERIFY_CRC8;
@@ -320,7 +324,12 @@ __global__ void __launch_bounds__(HDR_T) k_verify_frames(VerifyArgs a)
         if (live && (h.status == FHIP_VERIFY_OK || h.status == FHIP_VERIFY_CRC8)) {
             long long rel;
             bool num_ok, cover_ok;
-            if (!a.allow_vbs) {
+            if (numbered) {
+                // every frame is a whole block of its own stream: the table says which, the batch says where
+                rel = (long long)f * a.block_size;
+                num_ok = h.number == (unsigned long long)a.numbers[f];
+                cover_ok = h.n == a.block_size;
+            } else if (!a.allow_vbs) {
                 rel = (long long)f * a.block_size;
                 num_ok = snum == (unsigned long long)(a.first_sample + rel);
                 cover_ok = (f == count - 1) ? (rel + h.n == a.nsamples) : (h.n == a.block_size);

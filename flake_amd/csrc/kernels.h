@@ -238,6 +238,8 @@ struct VerifyArgs {
     long long *summary;                          // [4]
     unsigned long long *key;                     // [1] scratch: (first failing frame << 8) | status
     long long *totals;                           // optional: fhip_encode_blocks_vbs_dev's totals
+    const uint32_t *numbers;                     // optional [nframes], fixed blocks only: the number frame f must carry
+                                                 // (frames of many streams in one batch); first_sample is unused then
 };
 hipError_t launch_verify(hipStream_t st, const VerifyArgs &a);
 

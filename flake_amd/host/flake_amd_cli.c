@@ -6,15 +6,16 @@
  *
  *   flake_amd_cli [-0..-12] [-b blocksize] [--verify] in.wav out.flac
  *   flake_amd_cli [-0..-12] --synth FRAMES [--channels C] [--bps B] [--verify] out.flac
- *   flake_amd_cli [-0..-8] [-b blocksize] --set OUTDIR in1.wav in2.wav ...
- *   flake_amd_cli [-0..-8] --set OUTDIR --synth-streams S --synth FRAMES [--channels C] [--bps B]
+ *   flake_amd_cli [-0..-8] [-b blocksize] --set OUTDIR [--verify] in1.wav in2.wav ...
+ *   flake_amd_cli [-0..-8] --set OUTDIR [--verify] --synth-streams S --synth FRAMES [--channels C] [--bps B]
  *
  * --set encodes inputs of one format as a stream set (flake_amd_set_*): their blocks round-robin in shared GPU
  * batches, every stream's MD5 carried on the device, one OUTDIR/<name>.flac per input with its own STREAMINFO --
  * the file the single-input form writes for that input.
  *
- * --verify checks on the GPU that every frame decodes to its input (flake_amd_set_verify)
- * and exits non-zero with the verifier's message when one does not.
+ * --verify checks on the GPU that every frame decodes to its input (flake_amd_set_verify; for --set
+ * flake_amd_set_enable_verify, every frame held to its own stream's numbering) and exits non-zero with the
+ * verifier's message when one does not.
  *
  * Only canonical PCM WAV (8/16/24/32 bit) is read; this is a harness for the
  * host API, not a replacement for the reference's libpcm_io.
@@ -130,7 +131,7 @@ static int set_add(set_run *r, int stream, const char *block, int block_size)
 }
 
 static int run_set(const char *outdir, char **inputs, int ninputs, int synth_streams, int synth, int level, int bsize,
-                   int channels, int bps)
+                   int channels, int bps, int verify)
 {
     const int S = ninputs ? ninputs : synth_streams;
     FlakeAmdContext s;
@@ -185,6 +186,7 @@ static int run_set(const char *outdir, char **inputs, int ninputs, int synth_str
     memset(&r, 0, sizeof r);
     r.g = flake_amd_set_open(&s, S, 0);
     if (!r.g) { fprintf(stderr, "%s\n", flake_amd_set_last_error(NULL)); return 1; }
+    if (verify && flake_amd_set_enable_verify(r.g, 1)) { fprintf(stderr, "cannot turn verification on\n"); return 1; }
     r.sample_bytes = sample_bytes; r.bs = bs; r.nch = nch; r.cap_blocks = 1024; r.outs = outs;
     r.pcm = (char *)malloc((size_t)r.cap_blocks * bs * nch * sample_bytes);
     r.stream_of = (int *)malloc(sizeof(int) * (size_t)r.cap_blocks);
@@ -259,13 +261,14 @@ int main(int argc, char **argv)
             else if (!strcmp(argv[i], "--synth-streams") && i + 1 < argc) synth_streams = atoi(argv[++i]);
             else if (!strcmp(argv[i], "--channels") && i + 1 < argc) channels = atoi(argv[++i]);
             else if (!strcmp(argv[i], "--bps") && i + 1 < argc) bps = atoi(argv[++i]);
+            else if (!strcmp(argv[i], "--verify")) verify = 1;
             else inputs[ninputs++] = argv[i];
         }
         if (!setdir || (!ninputs && (synth_streams < 1 || synth < 1)) || (ninputs && synth_streams)) {
-            fprintf(stderr, "usage: %s [-0..-8] [-b blocksize] --set OUTDIR (in1.wav in2.wav ... | --synth-streams S --synth FRAMES [--channels C] [--bps B])\n", argv[0]);
+            fprintf(stderr, "usage: %s [-0..-8] [-b blocksize] --set OUTDIR [--verify] (in1.wav in2.wav ... | --synth-streams S --synth FRAMES [--channels C] [--bps B])\n", argv[0]);
             return 2;
         }
-        return run_set(setdir, inputs, ninputs, synth_streams, synth, level, bsize, channels, bps);
+        return run_set(setdir, inputs, ninputs, synth_streams, synth, level, bsize, channels, bps, verify);
     }
     for (int i = 1; i < argc; i++) {
         if (argv[i][0] == '-' && argv[i][1] >= '0' && argv[i][1] <= '9') level = atoi(argv[i] + 1);
@@ -278,7 +281,9 @@ int main(int argc, char **argv)
         else out = argv[i];
     }
     if (!out || (!in && !synth)) {
-        fprintf(stderr, "usage: %s [-0..-12] [-b blocksize] [--verify] (in.wav | --synth FRAMES [--channels C] [--bps B]) out.flac\n", argv[0]);
+        fprintf(stderr, "usage: %s [-0..-12] [-b blocksize] [--verify] (in.wav | --synth FRAMES [--channels C] [--bps B]) out.flac\n"
+                        "       %s [-0..-8] [-b blocksize] --set OUTDIR [--verify] (in1.wav in2.wav ... | --synth-streams S --synth FRAMES [--channels C] [--bps B])\n",
+                argv[0], argv[0]);
         return 2;
     }
     wav_t w;

@@ -9,6 +9,10 @@
  * sequential inside a stream and independent across streams: each stream's running hash lives on the device (K6,
  * fhip_md5_state), updated from the PCM the chunk's upload has already brought there, beside the chunk's encode
  * kernels.  The samples cross the link once and the host hashes nothing.
+ *
+ * Verification (flake_amd_set_enable_verify) is the handle's own (fhip_set_verify): the packed path hands the chunk's
+ * number table to the verifier, which holds every frame to its own stream's counter.  The verifier speaks of batch
+ * indices; this file maps an index back to its stream and that stream's frame number.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,6 +31,8 @@ struct FlakeAmdSet {
     int pcm_format;
     int verbatim_size;                    /* of a full block: where max_frame_size starts (encode.c:446-450) */
     int broken;                           /* a device call failed half way: the streams' state is unknown */
+    int vfail, vfail_stream, vfail_status; /* flake_amd_set_last_verify_failure: the last encode call's, if any */
+    unsigned vfail_number;
     /* per stream */
     uint32_t *frame_count;
     uint64_t *samples;
@@ -134,6 +140,27 @@ FLAKE_AMD_API FlakeAmdSet *flake_amd_set_open(const FlakeAmdContext *like, int n
 #undef OPEN_FAIL
 }
 
+FLAKE_AMD_API int flake_amd_set_enable_verify(FlakeAmdSet *g, int on)
+{
+    if (!g) return -1;
+    return fhip_set_verify(g->hip, on != 0) == FHIP_OK ? 0 : -1;
+}
+
+FLAKE_AMD_API int flake_amd_set_last_verify_failure(const FlakeAmdSet *g, int *stream, unsigned *frame_number, int *status)
+{
+    if (!g || !g->vfail) return 0;
+    if (stream) *stream = g->vfail_stream;
+    if (frame_number) *frame_number = g->vfail_number;
+    if (status) *status = g->vfail_status;
+    return 1;
+}
+
+static const char *verify_status_name(int s)
+{
+    static const char *const names[] = {"OK", "HEADER", "CRC8", "NUMBER", "SYNTAX", "SAMPLES", "PADDING", "CRC16", "LENGTH"};
+    return (s >= 0 && s <= 8) ? names[s] : "?";
+}
+
 static int grow_call_tables(FlakeAmdSet *g, int nblocks)
 {
     if (nblocks <= g->cap_blocks) return 0;
@@ -155,6 +182,7 @@ FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples
 {
     if (!g) return -1;
     g->err[0] = 0;
+    g->vfail = 0;
     if (g->broken) SET_FAIL("flake_amd_set_encode: an earlier device error left the set unusable");
     if (nblocks < 0 || (nblocks > 0 && (!samples || !stream_of_block || !out)))
         SET_FAIL("flake_amd_set_encode: null argument or negative block count");
@@ -217,6 +245,25 @@ FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples
         }
         int64_t bytes = 0;
         if (rc == FHIP_OK) { what = "fhip_frames_packed_begin"; rc = fhip_frames_packed_begin(g->hip, &bt, &bytes); }
+        if (rc == FHIP_E_VERIFY) {
+            /* the verifier's first failing frame is an index into this chunk: name its stream and that stream's frame.
+             * Nothing of the call is committed; the device hashes have moved on, as in the case below */
+            int64_t vs[4] = {0, 0, -1, 0};
+            fhip_verify_rec vr = {0, -1, -1, -1};
+            (void)fhip_last_verify_failure(g->hip, vs, &vr);
+            (void)fhip_frames_packed_fetch_wait(g->hip);
+            g->broken = g->dev_md5 != NULL;
+            if (vs[2] < 0 || vs[2] >= cnt) SET_FAIL("fhip_frames_packed_begin: %s (%s)", fhip_strerror(rc), fhip_last_error(g->hip));
+            const int idx = b0 + (int)vs[2];
+            g->vfail = 1;
+            g->vfail_stream = stream_of_block[idx];
+            g->vfail_number = g->fnum[idx];
+            g->vfail_status = vr.status;
+            SET_FAIL("flake_amd_set_encode: verification failed: %lld of the chunk's %lld frames do not decode to the "
+                     "input; first: stream %d, frame %u (block %d of the call), %s (subframe %d, sample %d, bit %d)",
+                     (long long)vs[1], (long long)vs[0], g->vfail_stream, g->vfail_number, idx,
+                     verify_status_name(vr.status), vr.subframe, vr.sample, vr.bit);
+        }
         if (rc == FHIP_OK && (size_t)(total + bytes) > out_size) {
             (void)fhip_frames_packed_fetch_wait(g->hip);
             g->broken = g->dev_md5 != NULL;          /* (its hashes have moved on) */

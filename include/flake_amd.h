@@ -156,8 +156,9 @@ FLAKE_AMD_API const char *flake_amd_last_error(const FlakeAmdContext *s);
  * Returns NULL -- flake_amd_set_last_error(NULL) says why -- for invalid parameters, variable block size (levels
  * 9-12), unknown flags, or under the CPU comparison modes FLAKE_AMD_HOST_ASSEMBLY=1 / FLAKE_AMD_HOST_VBS=1.  The
  * device is FLAKE_AMD_DEVICE, the blocks per GPU batch FLAKE_AMD_BATCH (default 1024), as for single streams.
- * Verification (flake_amd_set_verify) is not offered for sets: the verifier checks each frame's number against
- * the frame before it in the batch.
+ * Verification is offered for sets through flake_amd_set_enable_verify below (flake_amd_set_verify is the single
+ * stream's switch): the verifier holds every frame of a batch to its own stream's frame counter, whichever stream
+ * owns it.  Variable block size, and blocks of different sizes within one call, stay outside sets.
  */
 #define FLAKE_AMD_SET_MD5_HOST 1u
 #define FLAKE_AMD_SET_MD5_OFF  2u
@@ -179,6 +180,23 @@ FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples
 /* flake_get_streaminfo() for one stream of the set.  The first request after an encode finalises and fetches the
  * digests of ALL streams (one synchronisation); the streams stay open. */
 FLAKE_AMD_API int flake_amd_set_get_streaminfo(FlakeAmdSet *g, int stream, FlakeAmdStreaminfo *si);
+/*
+ * Verification on the device for a set, off by default; returns 0, or -1 without a set.  While on, every frame
+ * flake_amd_set_encode writes is checked on the device, before the call returns, to decode to the block it was
+ * given and to carry its own stream's frame number (fhip_set_verify / fhip_verify_frames_numbered,
+ * include/flakehip.h); with every MD5 mode and both sample widths, and the bytes are the same either way.  A chunk
+ * that fails makes flake_amd_set_encode return -1: flake_amd_set_last_error() names the stream, that stream's frame
+ * number, the block's index in the call, the status and the subframe, sample and bit; no stream's bookkeeping is
+ * committed for the call.  Unless the set was opened with FLAKE_AMD_SET_MD5_HOST or _OFF, the device hashes have
+ * already absorbed the chunk and the set refuses further calls, as after an output buffer that was too small.
+ *
+ * flake_amd_set_last_verify_failure: 1 after a flake_amd_set_encode that failed verification, with the failing
+ * frame's stream, its frame number within that stream and its status (FHIP_VERIFY_*) in the outputs (each may be
+ * NULL); 0 otherwise, outputs untouched -- so that a caller can decide per file without parsing text.
+ */
+FLAKE_AMD_API int flake_amd_set_enable_verify(FlakeAmdSet *g, int on);
+FLAKE_AMD_API int flake_amd_set_last_verify_failure(const FlakeAmdSet *g, int *stream, unsigned *frame_number,
+                                                    int *status);
 FLAKE_AMD_API const char *flake_amd_set_last_error(const FlakeAmdSet *g);
 FLAKE_AMD_API void flake_amd_set_close(FlakeAmdSet *g);
 

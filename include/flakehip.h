@@ -413,14 +413,40 @@ FHIP_API int fhip_verify_frames_dev(fhip_ctx *ctx, const fhip_verify_in *in, con
 FHIP_API int fhip_verify_frames(fhip_ctx *ctx, const fhip_verify_in *in, const fhip_verify_out *out);
 
 /*
+ * The same two entries for a batch whose frames belong to SEVERAL fixed-block streams (a stream set): frame f must
+ * carry exactly frame_numbers[f] ([nframes] uint32: device memory for _dev, host memory for the other, which uploads
+ * the table beside the stream, the sizes and the PCM) in its header's UTF-8 field, whatever its neighbours carry;
+ * otherwise it fails with FHIP_VERIFY_NUMBER at bit 32.  Its samples are the block_size samples at f * block_size
+ * of pcm -- its position in the batch -- and every frame, the last included, must hold exactly params.block_size
+ * samples (FHIP_VERIFY_NUMBER at bit 16 otherwise); in->first_sample is ignored.  Everything else -- header codes,
+ * CRC-8, subframes, padding, CRC-16, length, the records and the summary -- is as above.  What is NOT checked is
+ * which stream a frame belongs to: the table is the caller's statement of that.  frame_numbers == NULL makes them
+ * fhip_verify_frames_dev / fhip_verify_frames.  On a handle with allow_vbs (frames numbered by sample, verified in
+ * sequence) a table is refused with FHIP_E_UNSUPPORTED and nothing is queued.  On FHIP_E_VERIFY the error text also
+ * gives the number the first failing frame was required to carry.
+ */
+FHIP_API int fhip_verify_frames_numbered_dev(fhip_ctx *ctx, const fhip_verify_in *in, const uint32_t *frame_numbers,
+                                             const fhip_verify_out *out);
+FHIP_API int fhip_verify_frames_numbered(fhip_ctx *ctx, const fhip_verify_in *in, const uint32_t *frame_numbers,
+                                         const fhip_verify_out *out);
+
+/*
  * Verification of the handle's own output, off by default.  While on:
  *   fhip_frames_packed_begin (and fhip_encode_frames_packed) and fhip_encode_blocks_vbs_packed run
  *   the verifier on the device-resident stream and PCM before they return, and return FHIP_E_VERIFY
  *   (copying nothing to `out`) when a frame fails; after a failed _begin, fhip_frames_packed_fetch
  *   still delivers the bytes.  fhip_encode_blocks_vbs_dev sets bit 2 of totals[3] when a frame
  *   fails (no host synchronisation).  The bytes written are the same with verification on or off.
+ *   A fixed-block batch with fhip_batch.frame_numbers set is verified against that table, frame by frame (the
+ *   semantics of fhip_verify_frames_numbered: the frames may belong to many streams, in any order); without a table
+ *   the frames must count up from first_frame_number.  A variable-block-size batch is verified in sequence either way.
  */
 FHIP_API int fhip_set_verify(fhip_ctx *ctx, int on);
+/* What the most recent host-synchronising verification of this handle found (fhip_verify_frames, _numbered, and the
+ * encode entries above while fhip_set_verify is on), for callers that act on it rather than print it: summary[4] as
+ * in fhip_verify_out, *first = the record of the first failing frame (status OK and -1s when none failed).  Either
+ * pointer may be NULL.  Returns 1 when a frame failed, 0 when none did, FHIP_E_INVALID for a null handle. */
+FHIP_API int fhip_last_verify_failure(const fhip_ctx *ctx, int64_t *summary, fhip_verify_rec *first);
 
 /* ---- MD5 of many streams (K6) ---------------------------------------- */
 
