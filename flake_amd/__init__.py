@@ -213,6 +213,11 @@ def load_library() -> C.CDLL:
         "fhip_md5_final": (i, [vp, vp, i, vp]),
         "fhip_md5_update_uploaded": (i, [vp, vp, i, i, i, vp, vp]),
         "fhip_frames_packed_upload": (i, [vp, C.POINTER(Batch)]),
+        "fhip_frames_packed_upload_ragged": (i, [vp, C.POINTER(Batch), vp]),
+        "fhip_frames_packed_begin_ragged": (i, [vp, C.POINTER(Batch), vp, C.POINTER(i64)]),
+        "fhip_md5_update_uploaded_ragged": (i, [vp, vp, i, i, vp, vp, vp]),
+        "fhip_verify_frames_ragged_dev": (i, [vp, C.POINTER(VerifyIn), vp, vp, vp, C.POINTER(VerifyOut)]),
+        "fhip_verify_frames_ragged": (i, [vp, C.POINTER(VerifyIn), vp, vp, C.POINTER(VerifyOut)]),
         "fhip_device_alloc": (vp, [C.c_size_t]),
         "fhip_device_free": (None, [vp]),
     }
@@ -238,6 +243,8 @@ ABI_SYMBOLS = (
     "fhip_set_pcm_format",
     "fhip_md5_init_dev", "fhip_md5_update_dev", "fhip_md5_final_dev", "fhip_md5_final", "fhip_md5_update_uploaded",
     "fhip_device_alloc", "fhip_device_free",
+    "fhip_frames_packed_upload_ragged", "fhip_frames_packed_begin_ragged", "fhip_md5_update_uploaded_ragged",
+    "fhip_verify_frames_ragged_dev", "fhip_verify_frames_ragged",
 )
 
 
@@ -579,6 +586,9 @@ def load_host_library() -> C.CDLL:
     lib.flake_amd_set_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_size_t, C.c_void_p]
     lib.flake_amd_set_encode.restype = C.c_longlong
+    lib.flake_amd_set_encode_ragged.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.flake_amd_set_encode_ragged.restype = C.c_longlong
     lib.flake_amd_set_get_streaminfo.argtypes = [C.c_void_p, C.c_int, C.POINTER(HostStreaminfo)]
     lib.flake_amd_set_get_streaminfo.restype = C.c_int
     lib.flake_amd_set_last_error.argtypes = [C.c_void_p]
@@ -758,6 +768,25 @@ class StreamSet:
                                           sob.ctypes.data, out.ctypes.data, cap, sizes.ctypes.data)
         if w < 0:
             raise FlakeHipError(int(w), "flake_amd_set_encode", self.last_error())
+        return out[:w].copy(), sizes[:nblocks]
+
+    def encode_ragged(self, pcm: np.ndarray, block_sizes, stream_of_block, dtype=np.int32):
+        """pcm: the blocks back to back, block b block_sizes[b] samples long ([sum(block_sizes)][channels]) and of
+        stream stream_of_block[b] (flake_amd_set_encode_ragged).  Returns (bytes of all frames in batch order,
+        frame sizes [nblocks])."""
+        ch = self.ctx.channels
+        pcm = np.ascontiguousarray(pcm, dtype=dtype).reshape(-1, ch)
+        sob = np.ascontiguousarray(stream_of_block, dtype=np.int32)
+        bsz = np.ascontiguousarray(block_sizes, dtype=np.int32)
+        nblocks = len(sob)
+        assert len(bsz) == nblocks
+        cap = 64 + pcm.size * 5 + 64 * (nblocks + 1) * 8
+        out = np.zeros(cap, dtype=np.uint8)
+        sizes = np.zeros(max(nblocks, 1), dtype=np.int32)
+        w = self.lib.flake_amd_set_encode_ragged(self._g, pcm.ctypes.data, pcm.dtype.itemsize, nblocks, bsz.ctypes.data,
+                                                 sob.ctypes.data, out.ctypes.data, cap, sizes.ctypes.data)
+        if w < 0:
+            raise FlakeHipError(int(w), "flake_amd_set_encode_ragged", self.last_error())
         return out[:w].copy(), sizes[:nblocks]
 
     def set_verify(self, on: bool) -> None:

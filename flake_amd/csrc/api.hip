@@ -131,6 +131,17 @@ struct fhip_ctx {
 
     std::vector<std::string> launches;        // fhip_last_launches: what the most recent call queued
 
+    // ragged batches (fhip_frames_packed_*_ragged): the per-frame tables, one device block laid out as
+    // long long src[cap], double c[cap], int32 n[cap]; the host copy they are uploaded from; allocated at first use
+    DevBuf<long long> d_rg;
+    size_t rg_cap = 0;
+    std::vector<long long> h_rg;
+    std::vector<int32_t> uploaded_sizes;      // fhip_frames_packed_upload_ragged: the block lengths of the upload
+    std::vector<uint32_t> h_rgnum;            // the numbers the batch's frames carry (the verdict's text)
+    const long long *rg_src() const { return d_rg; }
+    const double *rg_c() const { return reinterpret_cast<const double *>(d_rg.get() + rg_cap); }
+    const int32_t *rg_n() const { return reinterpret_cast<const int32_t *>(d_rg.get() + 2 * rg_cap); }
+
     // K6 (fhip_md5_*): allocated at first use (ensure_md5)
     static constexpr int MD5_SLOTS = 16;
     hipStream_t md5_stream = nullptr;         // fhip_md5_update_uploaded: beside K0...K4 of the batch
@@ -457,7 +468,8 @@ int ensure_verify(fhip_ctx *c, size_t nframes)
 // frames belong to several streams -- first_sample is unused then.  Null: numbered by position, as a single stream.
 int run_verify(fhip_ctx *c, const uint8_t *stream, long long stream_bytes, const int32_t *frame_bytes, int nframes,
                const long long *dev_count, const int32_t *pcm, long long nsamples, long long first_sample,
-               int block_size, fhip_verify_rec *recs, int64_t *summary, long long *totals, const uint32_t *numbers)
+               int block_size, fhip_verify_rec *recs, int64_t *summary, long long *totals, const uint32_t *numbers,
+               const int32_t *frame_n = nullptr, const long long *frame_src = nullptr)
 {
     int rc = ensure_verify(c, (size_t)nframes);
     if (rc != FHIP_OK) return rc;
@@ -466,6 +478,8 @@ int run_verify(fhip_ctx *c, const uint8_t *stream, long long stream_bytes, const
                        p.channels, p.bits_per_sample, block_size, p.sample_rate, p.allow_vbs ? 1 : 0, c->pcm_format,
                        c->d_vws, recs ? recs : c->d_vrec, summary ? reinterpret_cast<long long *>(summary) : c->d_vsum,
                        reinterpret_cast<unsigned long long *>(c->d_vsum + 4), totals, numbers};
+    a.frame_n = frame_n;              // the ragged numbered mode: both tables or neither
+    a.frame_src = frame_src;
     Prof pr(c, kProfVerify, c->profiling);
     HIP_TRY(c, fhip::launch_verify(c->stream, a));
     return FHIP_OK;
@@ -588,6 +602,90 @@ int check_batch(fhip_ctx *c, const fhip_batch *b, bool host = false)
         if ((b->frame_stride & 3) || b->frame_stride < fhip_frame_stride(&c->p, b->block_size))
             return fail(c, FHIP_E_INVALID, "frame_stride too small or not a multiple of 4");
     }
+    return FHIP_OK;
+}
+
+// ---- ragged batches: blocks of different lengths in one call ----
+
+// What the ragged entries check first: the handle, the batch (check_range), then the table -- every entry in
+// 1..params.block_size, the largest equal to b->block_size.  *total = the batch's samples per channel.
+int check_ragged(fhip_ctx *c, const fhip_batch *b, const int32_t *block_sizes, bool rest, long long *total)
+{
+    int rc = check_range(c, b, rest && block_sizes, "null argument");
+    if (rc != FHIP_OK) return rc;
+    if (c->p.allow_vbs)
+        return fail(c, FHIP_E_UNSUPPORTED, "ragged batches need a fixed-block handle (allow_vbs numbers samples)");
+    if (c->p.block_size > fhip::FHIP_MAX_RESIDENT_BLOCK)
+        return fail(c, FHIP_E_UNSUPPORTED, "ragged batches need params.block_size <= 16384: use one call per length");
+    long long sum = 0;
+    int largest = 0;
+    for (int f = 0; f < b->nframes; f++) {
+        const int n = block_sizes[f];
+        if (n < 1 || n > c->p.block_size) return fail(c, FHIP_E_INVALID, "block_sizes entry out of range");
+        largest = n > largest ? n : largest;
+        sum += n;
+    }
+    if (b->nframes > 0 && largest != b->block_size)
+        return fail(c, FHIP_E_INVALID, "block_size must equal the largest entry of block_sizes");
+    *total = sum;
+    return FHIP_OK;
+}
+
+// The tables of a ragged batch, built on the host and queued to the device on the handle's stream.
+int upload_ragged_tables(fhip_ctx *c, const int32_t *block_sizes, int nframes)
+{
+    const size_t cap = (size_t)c->max_frames;
+    if (c->rg_cap != cap) {
+        HIP_TRY(c, c->d_rg.reserve(2 * cap + (cap + 1) / 2));
+        c->rg_cap = cap;
+    }
+    c->h_rg.assign(2 * cap + (cap + 1) / 2, 0);
+    long long *src = c->h_rg.data();
+    double *wc = reinterpret_cast<double *>(c->h_rg.data() + cap);
+    int32_t *len = reinterpret_cast<int32_t *>(c->h_rg.data() + 2 * cap);
+    long long at = 0;
+    for (int f = 0; f < nframes; f++) {
+        const int n = block_sizes[f];
+        src[f] = at;
+        wc[f] = (2.0 / (n - 1.0)) - 1.0;                     // lpc.c:34 (unused where n <= max_order)
+        len[f] = n;
+        at += (long long)n * c->p.channels;
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->d_rg, c->h_rg.data(), c->h_rg.size() * sizeof(long long), hipMemcpyHostToDevice,
+                              c->stream));
+    return FHIP_OK;
+}
+
+// K0 ... K4 of a ragged batch on the handle's stream: the generic instances with the per-frame tables.
+int run_ragged(fhip_ctx *c, const int32_t *pcm, int nframes, int nmax, uint8_t *bits, int64_t slot_bytes,
+               const FrameOut &fo)
+{
+    const fhip_params &p = c->p;
+    const int nsub = nframes * p.channels;
+    const fhip::RaggedFrames rf{c->rg_n(), c->rg_src(), c->rg_c(), p.block_size, nmax};
+    const bool prof = c->profiling;
+    {
+        Prof pr(c, 0, prof);
+        HIP_TRY(c, fhip::launch_prepare_ragged(c->stream, p, pcm, nframes, rf, c->d_smp, c->d_k0rec, c->pcm_format));
+    }
+    if (p.prediction_type == 2) {
+        {
+            Prof pr(c, 1, prof);
+            HIP_TRY(c, fhip::launch_autocorr_ragged(c->stream, c->d_smp, nsub, p.channels, rf, p.max_prediction_order,
+                                                    c->d_autoc));
+        }
+        Prof pr(c, 2, prof);
+        HIP_TRY(c, fhip::launch_lpc(c->stream, c->d_autoc, nsub, p.max_prediction_order, p.lpc_precision, p.order_method,
+                                    c->d_coefs, c->d_shift, c->d_opt, c->d_fin));
+    }
+    {
+        Prof pr(c, 3, prof);
+        HIP_TRY(c, fhip::launch_encode_ragged(c->stream, p, c->d_smp, nsub, rf, c->d_coefs, c->d_shift, c->d_opt, c->d_info,
+                                              bits, slot_bytes, c->d_k0rec));
+    }
+    Prof pr(c, 4, prof);
+    HIP_TRY(c, fhip::launch_assemble(c->stream, p, pcm, nframes, nmax, c->d_info, bits, slot_bytes, fo.frames, fo.stride,
+                                     fo.bytes, fo.first, 1u, fo.numbers, rf.frame_src, nullptr, c->pcm_format, rf.frame_n));
     return FHIP_OK;
 }
 
@@ -1169,6 +1267,95 @@ int fhip_encode_frames_packed(fhip_ctx *c, const fhip_batch *b, uint8_t *out, in
     return FHIP_OK;
 }
 
+int fhip_frames_packed_upload_ragged(fhip_ctx *c, const fhip_batch *b, const int32_t *block_sizes)
+{
+    long long total = 0;
+    int rc = check_ragged(c, b, block_sizes, true, &total);
+    if (rc != FHIP_OK) return rc;
+    c->uploaded_pcm = nullptr;
+    if (b->nframes == 0) return FHIP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nvals = (size_t)total * (size_t)c->p.channels;
+    const int64_t stride = fhip_frame_stride(&c->p, c->p.block_size);
+    rc = ensure_staging(c, (size_t)b->nframes * c->p.channels * (size_t)((stride + 3) & ~(int64_t)3));
+    if (rc != FHIP_OK) return rc;
+    rc = stage_pcm(c, b->pcm, nvals * c->pcm_width());
+    if (rc != FHIP_OK) return rc;
+    rc = upload_ragged_tables(c, block_sizes, b->nframes);
+    if (rc != FHIP_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->md5_up_pending = false;               // (the stream waited for it)
+    c->uploaded_pcm = b->pcm;
+    c->uploaded_vals = nvals;
+    c->uploaded_frames = b->nframes;
+    c->uploaded_n = -1;                      // no uniform length: only the ragged entries take this upload
+    c->uploaded_sizes.assign(block_sizes, block_sizes + b->nframes);
+    return FHIP_OK;
+}
+
+int fhip_frames_packed_begin_ragged(fhip_ctx *c, const fhip_batch *b, const int32_t *block_sizes, int64_t *total_bytes)
+{
+    long long total_n = 0;
+    int rc = check_ragged(c, b, block_sizes, total_bytes && b && b->frame_bytes, &total_n);
+    if (rc != FHIP_OK) return rc;
+    *total_bytes = 0;
+    c->packed_ready = 0;
+    LaunchScope ls(c);
+    if (b->nframes == 0) return FHIP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nch = (size_t)c->p.channels;
+    const size_t nsub = (size_t)b->nframes * nch, nvals = (size_t)total_n * nch;
+    // every slot keeps the size of the handle's block: indexing stays a multiply
+    const int64_t stride = fhip_frame_stride(&c->p, c->p.block_size);
+    const int64_t slot = (stride + 3) & ~(int64_t)3;
+    rc = ensure_staging(c, nsub * (size_t)slot);
+    if (rc != FHIP_OK) return rc;
+    const size_t fb = (size_t)b->nframes * (size_t)stride;
+    HIP_TRY(c, c->d_frames.reserve(fb));
+    HIP_TRY(c, c->d_packed.reserve(fb));
+    HIP_TRY(c, c->d_fbytes.reserve(c->ws_frames));
+    HIP_TRY(c, c->d_offsets.reserve((size_t)c->max_frames + 1));
+    HIP_TRY(c, c->d_fnum.reserve(c->ws_frames));
+    // the numbers always travel as a table: K5 holds every frame of a ragged batch to its own entry
+    c->h_rgnum.resize((size_t)b->nframes);
+    for (int f = 0; f < b->nframes; f++)
+        c->h_rgnum[f] = b->frame_numbers ? b->frame_numbers[f] : b->first_frame_number + (uint32_t)f;
+    const bool uploaded = c->uploaded_pcm == b->pcm && c->uploaded_vals == nvals && c->uploaded_n == -1 &&
+                          c->uploaded_frames == b->nframes &&
+                          std::equal(c->uploaded_sizes.begin(), c->uploaded_sizes.end(), block_sizes);
+    c->uploaded_pcm = nullptr;
+    if (c->fetch_pending) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_fetch, 0));     // d_packed is still being read
+    HIP_TRY(c, hipMemcpyAsync(c->d_fnum, c->h_rgnum.data(), (size_t)b->nframes * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (!uploaded) {
+        rc = stage_pcm(c, b->pcm, nvals * c->pcm_width());
+        if (rc != FHIP_OK) return rc;
+        rc = upload_ragged_tables(c, block_sizes, b->nframes);
+        if (rc != FHIP_OK) return rc;
+    }
+    const FrameOut fo{c->d_frames, stride, c->d_fbytes, b->first_frame_number, c->d_fnum};
+    rc = run_ragged(c, c->d_pcm, b->nframes, b->block_size, c->d_bits, slot, fo);
+    if (rc != FHIP_OK) return rc;
+    HIP_TRY(c, fhip::launch_pack_frames(c->stream, c->d_frames, stride, c->d_fbytes, b->nframes,
+                                        c->d_offsets, c->d_packed));
+    long long vsum[4] = {0, 0, -1, 0};
+    if (c->verify) {
+        rc = run_verify(c, c->d_packed, (long long)fb, c->d_fbytes, b->nframes, nullptr, c->d_pcm, total_n, 0,
+                        c->p.block_size, nullptr, nullptr, nullptr, c->d_fnum, c->rg_n(), c->rg_src());
+        if (rc != FHIP_OK) return rc;
+        HIP_TRY(c, hipMemcpyAsync(vsum, c->d_vsum, sizeof vsum, hipMemcpyDeviceToHost, c->stream));
+    }
+    long long total = 0;
+    HIP_TRY(c, hipMemcpyAsync(b->frame_bytes, c->d_fbytes, (size_t)b->nframes * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&total, c->d_offsets + b->nframes, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    if (b->info)
+        HIP_TRY(c, hipMemcpyAsync(b->info, c->d_info, nsub * sizeof(fhip_subframe_info), hipMemcpyDeviceToHost, c->stream));
+    rc = fhip_sync(c);
+    if (rc != FHIP_OK) return rc;
+    c->packed_ready = total;
+    *total_bytes = total;
+    return c->verify ? verify_verdict(c, vsum, c->d_vrec, c->h_rgnum.data()) : FHIP_OK;
+}
+
 // ---- K6: the MD5 of many streams ----------------------------------------------------------------
 // The *_dev entries run on the caller's stream, fhip_md5_update_uploaded on md5_stream; each side waits for the
 // other's last launch, so updates of the same states run in call order whichever entries make them.
@@ -1278,6 +1465,54 @@ int fhip_md5_update_uploaded(fhip_ctx *c, fhip_md5_state *states, int nstreams, 
     c->md5seg_used[k] = true;
     rc = md5_update(c, st, states, nstreams, c->d_pcm, block_size, c->d_md5seg[k], c->d_md5seg[k] + nfirst);
     if (rc != FHIP_OK) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev_md5_up, st));
+    c->md5_up_pending = true;
+    return FHIP_OK;
+}
+
+int fhip_md5_update_uploaded_ragged(fhip_ctx *c, fhip_md5_state *states, int nstreams, int nblocks,
+                                    const int32_t *block_sizes, const int32_t *seg_first, const int32_t *seg_block)
+{
+    int rc = md5_check(c, states, nstreams, block_sizes && seg_first && seg_block);
+    if (rc != FHIP_OK) return rc;
+    // the upload this call names must still be the staging buffer's content, block for block
+    if (!c->uploaded_pcm || nblocks < 1 || c->uploaded_n != -1 || c->uploaded_frames != nblocks ||
+        !std::equal(c->uploaded_sizes.begin(), c->uploaded_sizes.end(), block_sizes))
+        return fail(c, FHIP_E_INVALID, "no matching fhip_frames_packed_upload_ragged is pending");
+    if (seg_first[0] != 0) return fail(c, FHIP_E_INVALID, "seg_first[0] must be 0");
+    for (int s = 0; s < nstreams; s++)
+        if (seg_first[s + 1] < seg_first[s]) return fail(c, FHIP_E_INVALID, "seg_first must not decrease");
+    const int nseg = seg_first[nstreams];
+    for (int i = 0; i < nseg; i++)
+        if (seg_block[i] < 0 || seg_block[i] >= nblocks) return fail(c, FHIP_E_INVALID, "seg_block entry outside the upload");
+    LaunchScope ls(c);
+    if (nstreams == 0 || nseg == 0) return FHIP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = ensure_md5(c)) != FHIP_OK) return rc;
+    // tables: seg_first, seg_block, then the blocks' lengths in values (their offsets are the upload's frame_src)
+    const int k = c->md5seg_next;
+    c->md5seg_next ^= 1;
+    const size_t nfirst = (size_t)nstreams + 1, nvals = nfirst + (size_t)nseg + (size_t)nblocks;
+    if (c->md5seg_used[k]) HIP_TRY(c, hipEventSynchronize(c->ev_md5seg[k]));
+    if (c->h_md5seg_cap[k] < nvals) {
+        if (c->h_md5seg[k]) HIP_TRY(c, hipHostFree(c->h_md5seg[k]));
+        c->h_md5seg[k] = nullptr; c->h_md5seg_cap[k] = 0;
+        HIP_TRY(c, hipHostMalloc((void **)&c->h_md5seg[k], nvals * 2 * sizeof(int32_t), hipHostMallocDefault));
+        c->h_md5seg_cap[k] = nvals * 2;
+    }
+    HIP_TRY(c, c->d_md5seg[k].reserve(nvals));
+    memcpy(c->h_md5seg[k], seg_first, nfirst * sizeof(int32_t));
+    memcpy(c->h_md5seg[k] + nfirst, seg_block, (size_t)nseg * sizeof(int32_t));
+    for (int b = 0; b < nblocks; b++) c->h_md5seg[k][nfirst + nseg + b] = block_sizes[b] * c->p.channels;
+    hipStream_t st = c->md5_stream;
+    if (c->md5_dev_pending) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_md5_dev, 0));
+    HIP_TRY(c, hipMemcpyAsync(c->d_md5seg[k], c->h_md5seg[k], nvals * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->ev_md5seg[k], st));
+    c->md5seg_used[k] = true;
+    c->md5_log_entry = -1;
+    HIP_TRY(c, fhip::launch_md5_streams_ragged(st, states, nstreams, c->d_pcm, c->pcm_format, (c->p.bits_per_sample + 7) >> 3,
+                                               c->d_md5seg[k], c->d_md5seg[k] + nfirst, c->rg_src(),
+                                               c->d_md5seg[k] + nfirst + nseg));
     HIP_TRY(c, hipEventRecord(c->ev_md5_up, st));
     c->md5_up_pending = true;
     return FHIP_OK;
@@ -1800,6 +2035,68 @@ int fhip_verify_frames_numbered(fhip_ctx *c, const fhip_verify_in *in, const uin
 int fhip_verify_frames(fhip_ctx *c, const fhip_verify_in *in, const fhip_verify_out *out)
 {
     return fhip_verify_frames_numbered(c, in, nullptr, out);
+}
+
+int fhip_verify_frames_ragged_dev(fhip_ctx *c, const fhip_verify_in *in, const uint32_t *frame_numbers,
+                                  const int32_t *block_sizes, const int64_t *frame_src, const fhip_verify_out *out)
+{
+    int rc = verify_check(c, in, out, true);
+    if (rc != FHIP_OK) return rc;
+    if (!frame_numbers || !block_sizes || !frame_src) return fail(c, FHIP_E_INVALID, "null argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return run_verify(c, in->stream, in->stream_bytes, in->frame_bytes, in->nframes, nullptr, in->pcm, in->nsamples, 0,
+                      c->p.block_size, out->frames, out->summary, nullptr, frame_numbers, block_sizes,
+                      reinterpret_cast<const long long *>(frame_src));
+}
+
+int fhip_verify_frames_ragged(fhip_ctx *c, const fhip_verify_in *in, const uint32_t *frame_numbers,
+                              const int32_t *block_sizes, const fhip_verify_out *out)
+{
+    int rc = verify_check(c, in, out, true);
+    if (rc != FHIP_OK) return rc;
+    if (!frame_numbers || !block_sizes) return fail(c, FHIP_E_INVALID, "null argument");
+    long long total = 0;
+    for (int f = 0; f < in->nframes; f++) {
+        if (block_sizes[f] < 1 || block_sizes[f] > c->p.block_size)
+            return fail(c, FHIP_E_INVALID, "block_sizes entry out of range");
+        total += block_sizes[f];
+    }
+    if (total != in->nsamples) return fail(c, FHIP_E_INVALID, "nsamples must be the sum of block_sizes");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t sb = (size_t)in->stream_bytes, nf = (size_t)in->nframes;
+    const size_t nv = (size_t)in->nsamples * (size_t)c->p.channels;
+    if (nf == 0) return fhip_verify_frames_numbered(c, in, frame_numbers, out);
+    // the tables: numbers, lengths, then the offsets (8-byte aligned behind an even count of 4-byte entries)
+    const size_t nf2 = (nf + 1) & ~(size_t)1;
+    std::vector<uint32_t> tab(2 * nf2 + 2 * nf);
+    long long at = 0;
+    for (size_t f = 0; f < nf; f++) {
+        tab[f] = frame_numbers[f];
+        tab[nf2 + f] = (uint32_t)block_sizes[f];
+        memcpy(&tab[2 * nf2 + 2 * f], &at, sizeof at);
+        at += (long long)block_sizes[f] * c->p.channels;
+    }
+    HIP_TRY(c, c->d_vstream.reserve(sb));
+    HIP_TRY(c, c->d_vfb.reserve(nf));
+    HIP_TRY(c, c->d_vpcm.reserve(nv));
+    HIP_TRY(c, c->d_vnum.reserve(tab.size()));
+    if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_vstream, in->stream, sb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_vfb, in->frame_bytes, nf * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (nv) HIP_TRY(c, hipMemcpyAsync(c->d_vpcm, in->pcm, nv * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_vnum, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    rc = run_verify(c, c->d_vstream, in->stream_bytes, c->d_vfb, in->nframes, nullptr, c->d_vpcm, in->nsamples, 0,
+                    c->p.block_size, nullptr, nullptr, nullptr, c->d_vnum,
+                    reinterpret_cast<const int32_t *>(c->d_vnum.get() + nf2),
+                    reinterpret_cast<const long long *>(c->d_vnum.get() + 2 * nf2));
+    if (rc != FHIP_OK) return rc;
+    long long sum[4] = {0, 0, -1, 0};
+    HIP_TRY(c, hipMemcpyAsync(sum, c->d_vsum, sizeof sum, hipMemcpyDeviceToHost, c->stream));
+    if (out->frames)
+        HIP_TRY(c, hipMemcpyAsync(out->frames, c->d_vrec, nf * sizeof(fhip_verify_rec), hipMemcpyDeviceToHost, c->stream));
+    rc = fhip_sync(c);          // (tab is read by the copy above: it lives until here)
+    if (rc != FHIP_OK) return rc;
+    for (int i = 0; i < 4; i++) out->summary[i] = sum[i];
+    return verify_verdict(c, sum, c->d_vrec, frame_numbers);
 }
 
 int fhip_last_verify_failure(const fhip_ctx *c, int64_t *summary, fhip_verify_rec *first)

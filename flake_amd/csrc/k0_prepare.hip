@@ -37,14 +37,19 @@ __device__ __forceinline__ void decorrelate(int32_t &a, int32_t &b, int mode)
 // streamed from global memory in each of the three passes instead (L2 serves the
 // re-reads: a frame is 512 KB at most).
 // int16 PCM: a stereo sample-frame is one 4-byte word (frames start 4-byte aligned whatever n).
-template <bool RESIDENT, class S>
+// RAGGED (a batch of blocks of different lengths): frame f has frame_n[f] samples at frame_src[f]; its rows keep the
+// stride row_n (the handle's block size), and everything below that depends on the length uses the frame's own.
+template <bool RESIDENT, class S, bool RAGGED = false>
 __device__ __forceinline__
 void prepare_lds_body(const S *__restrict__ pcm, int32_t *__restrict__ smp,
                       fhip_subframe_info *__restrict__ info, int n, int nch, int bps, int estimate,
-                      const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames)
+                      const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames,
+                      const int32_t *__restrict__ frame_n = nullptr, int row_n = 0)
 {
     extern __shared__ int32_t lds_i32[];
     if (dev_frames && (int)blockIdx.x >= dev_count(dev_frames, 0)) return;
+    const int row = RAGGED ? row_n : n;                  // stride of a channel's row in smp
+    if constexpr (RAGGED) n = frame_n[blockIdx.x];
     __shared__ unsigned long long s_sum[4][4];
     __shared__ uint32_t s_or[4][2];
     __shared__ int s_mode;
@@ -137,12 +142,12 @@ void prepare_lds_body(const S *__restrict__ pcm, int32_t *__restrict__ smp,
         if (mode == FHIP_CH_MID_SIDE || mode == FHIP_CH_LEFT_SIDE) obits[1]++;
         if (mode == FHIP_CH_RIGHT_SIDE) obits[0]++;
 
-        int32_t *dst = smp + (size_t)f * 2 * n;
+        int32_t *dst = smp + (size_t)f * 2 * row;
         for (int i = tid; i < n; i += NT) {
             int32_t a = left(i), b = right(i);
             if (!RESIDENT) decorrelate(a, b, mode);          // resident rows were decorrelated in place
             dst[i] = a >> wasted[0];
-            dst[n + i] = b >> wasted[1];
+            dst[row + i] = b >> wasted[1];
         }
         if (tid < 2) {
             fhip_subframe_info *o = &info[(size_t)f * 2 + tid];
@@ -172,18 +177,38 @@ void k_prepare_s16(const int16_t *__restrict__ pcm, int32_t *__restrict__ smp,
     prepare_lds_body<RESIDENT>(pcm, smp, info, n, nch, bps, estimate, frame_src, dev_frames);
 }
 
+// The ragged instances (stereo): one workgroup per frame, the LDS sized for the launch's longest frame.
+__global__ __launch_bounds__(NT)
+void k_prepare_ragged(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp,
+                      fhip_subframe_info *__restrict__ info, int bps, int estimate,
+                      const long long *__restrict__ frame_src, const int32_t *__restrict__ frame_n, int row_n)
+{
+    prepare_lds_body<true, int32_t, true>(pcm, smp, info, 0, 2, bps, estimate, frame_src, nullptr, frame_n, row_n);
+}
+
+__global__ __launch_bounds__(NT)
+void k_prepare_ragged_s16(const int16_t *__restrict__ pcm, int32_t *__restrict__ smp,
+                          fhip_subframe_info *__restrict__ info, int bps, int estimate,
+                          const long long *__restrict__ frame_src, const int32_t *__restrict__ frame_n, int row_n)
+{
+    prepare_lds_body<true, int16_t, true>(pcm, smp, info, 0, 2, bps, estimate, frame_src, nullptr, frame_n, row_n);
+}
+
 // K0 for 1 or 3..8 channels (no decorrelation, encode.c:660-663): one
 // workgroup per frame walks it in tiles of 256 sample-frames.  A tile is read
 // with coalesced dword loads, transposed through a padded LDS tile, and each
 // thread then owns one sample-frame with all its channels in registers.  Pass 1
 // ORs every sample per channel (wasted bits, encode.c:558-593), pass 2 re-reads
 // (L2), shifts and writes channel rows coalesced.
-template <class S>
+template <class S, bool RAGGED = false>
 __device__ __forceinline__
 void prepare_multi_body(const S *__restrict__ pcm, int32_t *__restrict__ smp,
                         fhip_subframe_info *__restrict__ info, int n, int nch, int bps,
-                        const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames)
+                        const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames,
+                        const int32_t *__restrict__ frame_n = nullptr, int row_n = 0)
 {
+    const int row = RAGGED ? row_n : n;                  // (prepare_lds_body: the ragged instance)
+    if constexpr (RAGGED) n = frame_n[blockIdx.x];
     __shared__ int32_t s_tile[NT * (FHIP_MAX_CH + 1)];
     __shared__ uint32_t s_orr[4][FHIP_MAX_CH];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -215,7 +240,7 @@ void prepare_multi_body(const S *__restrict__ pcm, int32_t *__restrict__ smp,
                 if (c < nch) {
                     const int32_t v = s_tile[tid * stride + c];
                     if (pass == 0) orv[c] |= (i < n) ? (uint32_t)v : 0u;
-                    else if (i < n) smp[((size_t)f * nch + c) * n + i] = v >> wasted[c];
+                    else if (i < n) smp[((size_t)f * nch + c) * row + i] = v >> wasted[c];
                 }
             }
         }
@@ -261,6 +286,23 @@ void k_prepare_multi_s16(const int16_t *__restrict__ pcm, int32_t *__restrict__ 
                          const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames)
 {
     prepare_multi_body(pcm, smp, info, n, nch, bps, frame_src, dev_frames);
+}
+
+// The ragged instances: element loads only, so an int16 frame may start at any 2-byte boundary.
+__global__ __launch_bounds__(NT)
+void k_prepare_multi_ragged(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp,
+                            fhip_subframe_info *__restrict__ info, int nch, int bps,
+                            const long long *__restrict__ frame_src, const int32_t *__restrict__ frame_n, int row_n)
+{
+    prepare_multi_body<int32_t, true>(pcm, smp, info, 0, nch, bps, frame_src, nullptr, frame_n, row_n);
+}
+
+__global__ __launch_bounds__(NT)
+void k_prepare_multi_ragged_s16(const int16_t *__restrict__ pcm, int32_t *__restrict__ smp,
+                                fhip_subframe_info *__restrict__ info, int nch, int bps,
+                                const long long *__restrict__ frame_src, const int32_t *__restrict__ frame_n, int row_n)
+{
+    prepare_multi_body<int16_t, true>(pcm, smp, info, 0, nch, bps, frame_src, nullptr, frame_n, row_n);
 }
 
 // K0 for 1, 3 .. 8 channels with the frame in REGISTERS (round 2): k_prepare_multi above reads
@@ -950,6 +992,44 @@ hipError_t launch_prepare(hipStream_t st, const fhip_params &p, const int32_t *p
     note_launch("k_prepare<true>");
     hipLaunchKernelGGL(k_prepare<true>, dim3(blocks), dim3(NT), lds, st, pcm, smp, info, n, nch,
                        p.bits_per_sample, p.stereo_method == 1 ? 1 : 0, frame_src, dev_frames);
+    return hipGetLastError();
+}
+
+hipError_t launch_prepare_ragged(hipStream_t st, const fhip_params &p, const int32_t *pcm, int nframes,
+                                 const RaggedFrames &rf, int32_t *smp, fhip_subframe_info *info, int pcm_format)
+{
+    if (nframes == 0) return hipSuccess;
+    const bool s16 = pcm_format == FHIP_PCM_S16;
+    if (!rf.frame_n || !rf.frame_src || rf.nmax < 1 || rf.nmax > rf.row_n || (s16 && p.bits_per_sample > 16))
+        return hipErrorInvalidValue;
+    const int16_t *pcm16 = reinterpret_cast<const int16_t *>(pcm);
+    if (p.channels != 2) {
+        note_launch("k_prepare_multi%s ragged", s16 ? "_s16" : "");
+        if (s16)
+            hipLaunchKernelGGL(k_prepare_multi_ragged_s16, dim3(nframes), dim3(NT), 0, st, pcm16, smp, info, p.channels,
+                               p.bits_per_sample, rf.frame_src, rf.frame_n, rf.row_n);
+        else
+            hipLaunchKernelGGL(k_prepare_multi_ragged, dim3(nframes), dim3(NT), 0, st, pcm, smp, info, p.channels,
+                               p.bits_per_sample, rf.frame_src, rf.frame_n, rf.row_n);
+        return hipGetLastError();
+    }
+    const size_t lds = sizeof(int32_t) * (size_t)rf.nmax * 2;
+    if (lds > 150 * 1024) return hipErrorInvalidValue;       // (callers keep to FHIP_MAX_RESIDENT_BLOCK)
+    const int est = p.stereo_method == 1 ? 1 : 0;
+    note_launch("k_prepare%s<true> ragged", s16 ? "_s16" : "");
+    if (s16) {
+        hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_prepare_ragged_s16),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (er != hipSuccess) return er;
+        hipLaunchKernelGGL(k_prepare_ragged_s16, dim3(nframes), dim3(NT), lds, st, pcm16, smp, info, p.bits_per_sample,
+                           est, rf.frame_src, rf.frame_n, rf.row_n);
+    } else {
+        hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_prepare_ragged),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (er != hipSuccess) return er;
+        hipLaunchKernelGGL(k_prepare_ragged, dim3(nframes), dim3(NT), lds, st, pcm, smp, info, p.bits_per_sample, est,
+                           rf.frame_src, rf.frame_n, rf.row_n);
+    }
     return hipGetLastError();
 }
 

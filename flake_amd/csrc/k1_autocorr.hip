@@ -219,6 +219,71 @@ void k_autocorr(const int32_t *__restrict__ smp, double *__restrict__ autoc,
 }
 
 // ---------------------------------------------------------------------------
+// K1 (ragged batches)  k_autocorr_ragged -- every subframe its own length
+// ---------------------------------------------------------------------------
+// A chain walk lasts as long as its block, so chains of different lengths in one wave would all wait for the
+// longest.  Here a wave is ONE subframe and lane = lag: all live lanes of a wave walk the same n positions and
+// nothing diverges inside a wave; waves of short blocks simply end early and the SIMD takes the next workgroup.
+// The two running sums per lag receive their products one at a time in position order (lpc.c:57-68), as in
+// k_autocorr: positions lag..maxlag go to the first sum, then the sums alternate.  The windowed fp64 samples of a
+// tile of 128 positions (behind a 32-entry halo) go through an LDS row of the wave's own.  frame_c[f] is the window
+// constant of lpc.c:34 for the frame's length, computed on the host.  A frame the reference does not run LPC on
+// (n <= max_order) gets the autocorrelation of silence, 2.0, so that K2 reads defined values; K3 ignores its rows.
+__global__ __launch_bounds__(AC_WAVES * WAVE)
+void k_autocorr_ragged(const int32_t *__restrict__ smp, double *__restrict__ autoc, int nsub, int nch, int row_n,
+                       int maxlag, const int32_t *__restrict__ frame_n, const double *__restrict__ frame_c)
+{
+    __shared__ double s_buf[AC_WAVES][AC_HALO + AC_TILE];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int s = blockIdx.x * AC_WAVES + wv;
+    if (s >= nsub) return;                        // whole wave idle (uniform)
+    double *buf = s_buf[wv];
+    const int f = s / nch;
+    const int n = __builtin_amdgcn_readfirstlane(frame_n[f]);
+    double *dst = autoc + (size_t)s * FHIP_MAX_LAGS;
+    if (n <= maxlag) {
+        if (lane <= maxlag) dst[lane] = 2.0;
+        return;
+    }
+    const double c = frame_c[f];
+    const int32_t *row = smp + (size_t)s * row_n;
+    const int half = n >> 1;
+    const int lag = min(lane, maxlag);
+    double acc1 = 1.0, acc2 = 1.0;                // lpc.c:58-59
+    if (lane < AC_HALO) buf[lane] = 0.0;
+    for (int tb = 0; tb < n; tb += AC_TILE) {
+#pragma unroll
+        for (int u = 0; u < AC_PER_LANE; u++) {
+            const int p = tb + u * WAVE + lane;
+            const int ii = (p < half) ? p : (n - 1 - p);
+            const bool valid = (p < n) && (ii < half);          // (the middle sample of an odd block stays 0: lpc.c:35)
+            const double tt = c - (double)ii;
+            const double w = valid ? (1.0 - (tt * tt)) : 0.0;
+            buf[AC_HALO + u * WAVE + lane] = (double)row[min(p, n - 1)] * w;
+        }
+        wave_lds_fence();
+        const int kend = min(AC_TILE, n - tb);
+        for (int k = 0; k < kend; k++) {
+            const int p = tb + k;
+            const double prod = buf[AC_HALO + k] * buf[AC_HALO + k - lag];
+            if (p <= maxlag) {
+                if (p >= lag) acc1 = acc1 + prod;
+            } else if ((p - maxlag) & 1) {
+                acc1 = acc1 + prod;               // p = maxlag + 1, + 3, ...: lpc.c:64
+            } else {
+                acc2 = acc2 + prod;               // lpc.c:65
+            }
+        }
+        wave_lds_fence();
+        // the last 32 entries of this tile become the halo of the next
+        const double hv = (lane < AC_HALO) ? buf[AC_TILE + lane] : 0.0;
+        wave_lds_fence();
+        if (lane < AC_HALO) buf[lane] = hv;
+    }
+    if (lane <= maxlag) dst[lane] = acc1 + acc2;
+}
+
+// ---------------------------------------------------------------------------
 // K1 (small batches)  k_autocorr_ps -- parity-split chains
 // ---------------------------------------------------------------------------
 // A chain walk in k_autocorr is n positions long whatever the batch size, and
@@ -1139,6 +1204,17 @@ hipError_t launch_autocorr_bins(hipStream_t st, const MultiBin &mb, const int32_
         }
     }
 #undef LAUNCH_WTB
+    return hipGetLastError();
+}
+
+hipError_t launch_autocorr_ragged(hipStream_t st, const int32_t *smp, int nsub, int nch, const RaggedFrames &rf,
+                                  int max_order, double *autoc)
+{
+    if (nsub == 0) return hipSuccess;
+    if (!rf.frame_n || !rf.frame_c || max_order < 1 || max_order > FHIP_MAX_ORDER) return hipErrorInvalidValue;
+    note_launch("k_autocorr ragged");
+    hipLaunchKernelGGL(k_autocorr_ragged, dim3((nsub + AC_WAVES - 1) / AC_WAVES), dim3(AC_WAVES * WAVE), 0, st, smp,
+                       autoc, nsub, nch, rf.row_n, max_order, rf.frame_n, rf.frame_c);
     return hipGetLastError();
 }
 

@@ -253,16 +253,21 @@ __device__ __forceinline__ void put_bits(uint32_t *win, long long wlo, long long
     if (lo && wi + 1 < ENC_WWORDS) atomicOr(&win[wi + 1], lo);
 }
 
-template <int C>
+// RAGGED (a batch of blocks of different lengths): subframe s has frame_n[s / channels] samples in a row of stride
+// row_n; C and the LDS come from the launch's longest frame, the layout and every decision from the subframe's own n.
+template <int C, bool RAGGED = false>
 __global__ __launch_bounds__(NT)
 void k_encode(fhip_params P, int n, const int32_t *__restrict__ smp_all,
               const int32_t *__restrict__ coefs_all, const int32_t *__restrict__ shift_all,
               const int32_t *__restrict__ opt_all, fhip_subframe_info *__restrict__ info,
               const fhip_subframe_info *__restrict__ prep,
               int32_t *__restrict__ res_out, uint8_t *__restrict__ bits_out, long long slot_bytes,
-              int raw_order, int raw_lpc, const int32_t *__restrict__ dev_sub)
+              int raw_order, int raw_lpc, const int32_t *__restrict__ dev_sub,
+              const int32_t *__restrict__ frame_n = nullptr, int row_n = 0)
 {
     if (dev_sub && (int)blockIdx.x >= dev_count(dev_sub, 0)) return;
+    const int row = RAGGED ? row_n : n;
+    if constexpr (RAGGED) n = __builtin_amdgcn_readfirstlane(frame_n[blockIdx.x / P.channels]);
     // raw_order >= 0: the input already IS a residual; only calc_rice_params_*
     // (rice.c:173-187) with that prediction order and the emit run.
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -293,7 +298,7 @@ void k_encode(fhip_params P, int n, const int32_t *__restrict__ smp_all,
     e.pmin_req = P.min_partition_order;
     e.pmax_req = P.max_partition_order;
 
-    const int32_t *src = smp_all + (size_t)s * n;
+    const int32_t *src = smp_all + (size_t)s * row;
     if (tid == 0) l.misc[M_FLAG] = 0;
     __syncthreads();
     {
@@ -455,7 +460,7 @@ void k_encode(fhip_params P, int n, const int32_t *__restrict__ smp_all,
 
     // FlacSubframe.residual
     if (res_out) {
-        int32_t *dst = res_out + (size_t)s * n;
+        int32_t *dst = res_out + (size_t)s * row;
 #pragma unroll
         for (int o = 0; o < C; o++) {
             const int i = e.i0 + o;
@@ -2327,6 +2332,33 @@ hipError_t launch_encode_bins(hipStream_t st, const fhip_params &p, const MultiB
 #undef LAUNCH_EB
 }
 
+hipError_t launch_encode_ragged(hipStream_t st, const fhip_params &p, const int32_t *smp, int nsub,
+                                const RaggedFrames &rf, const int32_t *coefs, const int32_t *shift,
+                                const int32_t *opt_order, fhip_subframe_info *info, uint8_t *bits, int64_t slot_bytes,
+                                const fhip_subframe_info *prep)
+{
+    if (nsub == 0) return hipSuccess;
+    if (!prep || prep == info || !rf.frame_n || rf.nmax < 1 || rf.nmax > rf.row_n || rf.nmax > FHIP_MAX_RESIDENT_BLOCK)
+        return hipErrorInvalidValue;
+    const size_t lds = encode_lds_bytes(rf.nmax);
+    const int chunk = (rf.nmax + NT - 1) / NT;
+#define LAUNCH_ENCR(CC)                                                                      \
+    do {                                                                                     \
+        hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_encode<CC, true>), \
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        if (er != hipSuccess) return er;                                                     \
+        note_launch("k_encode<%d> ragged", CC);                                              \
+        hipLaunchKernelGGL((k_encode<CC, true>), dim3(nsub), dim3(NT), lds, st, p, 0, smp, coefs, shift, opt_order, \
+                           info, prep, (int32_t *)nullptr, bits, (long long)slot_bytes, -1, 0, \
+                           (const int32_t *)nullptr, rf.frame_n, rf.row_n);                  \
+    } while (0)
+    if (chunk <= 16) LAUNCH_ENCR(16);
+    else if (chunk <= 32) LAUNCH_ENCR(32);
+    else LAUNCH_ENCR(64);
+#undef LAUNCH_ENCR
+    return hipGetLastError();
+}
+
 hipError_t launch_encode(hipStream_t st, const fhip_params &p, const int32_t *smp,
                          int nsub, int n, const int32_t *coefs, const int32_t *shift,
                          const int32_t *opt_order, const int32_t *fin,
@@ -2425,7 +2457,7 @@ hipError_t launch_encode(hipStream_t st, const fhip_params &p, const int32_t *sm
         hipLaunchKernelGGL(k_encode<CC>, dim3(nsub), dim3(NT), lds, st, p, n, smp, coefs,    \
                            shift, opt_order, info, prep, residual, bits,                     \
                            (long long)slot_bytes,                                            \
-                           raw_order, raw_lpc, dev_sub);                                     \
+                           raw_order, raw_lpc, dev_sub, (const int32_t *)nullptr, 0);        \
     } while (0)
     if (chunk <= 16) LAUNCH_ENC(16);
     else if (chunk <= 32) LAUNCH_ENC(32);

@@ -178,6 +178,9 @@ __device__ __forceinline__ int32_t asm_sample(const void *pcm_frame, int s16, in
 // better than a fixed walk, and a workgroup that finds its slot empty costs little.)
 constexpr int AT = WAVE;                  // threads per frame
 constexpr int ASM_QB = 4;                 // quads a lane keeps in flight
+// RAGGED (a batch of blocks of different lengths): frame f has frame_n[f] samples at frame_src[f]; its block-size code,
+// the optional size field and its verbatim size (encode.c:521-527) come from that length, the slots keep their strides.
+template <bool RAGGED>
 __global__ __launch_bounds__(AT)
 void k_assemble(fhip_params P, int n, const int32_t *__restrict__ pcm,
                 const fhip_subframe_info *__restrict__ info, const uint8_t *__restrict__ rice,
@@ -186,10 +189,15 @@ void k_assemble(fhip_params P, int n, const int32_t *__restrict__ pcm,
                 const uint32_t *__restrict__ numbers,
                 int sr_code0, int sr_code1, int bps_code, int verbatim_size,
                 const long long *__restrict__ frame_src, const int32_t *__restrict__ dev_frames, int pcm_s16,
-                MultiBin mb)
+                MultiBin mb, const int32_t *__restrict__ frame_n)
 {
     if (dev_frames && (int)blockIdx.x >= dev_count(dev_frames, 0)) return;      // (a ragged batch's grid is its bin's capacity)
     int f = blockIdx.x;
+    if constexpr (RAGGED) {
+        n = __builtin_amdgcn_readfirstlane(frame_n[f]);
+        const int bps = P.bits_per_sample;
+        verbatim_size = (P.channels == 2) ? 16 + ((n * (bps + bps + 1) + 7) >> 3) : 16 + ((n * P.channels * bps + 7) >> 3);
+    }
     if (mb.nbins) {
         // several bins of a ragged batch in one launch (kernels.h: MultiBin; one workgroup per frame slot of the
         // bins listed): info / frame_bytes / numbers / frame_src are the handle's whole slot-indexed arrays, the
@@ -637,9 +645,10 @@ hipError_t launch_assemble(hipStream_t st, const fhip_params &p, const int32_t *
                            int64_t slot_bytes, uint8_t *frames, int64_t frame_stride,
                            int32_t *frame_bytes, uint32_t number_base, uint32_t number_step,
                            const uint32_t *numbers, const long long *frame_src, const int32_t *dev_frames,
-                           int pcm_format)
+                           int pcm_format, const int32_t *frame_n)
 {
     if (nframes == 0) return hipSuccess;
+    if (frame_n && !frame_src) return hipErrorInvalidValue;
     // sample-rate / bit-depth codes of flake_encode_init() (encode.c:400-438)
     static const int sr_table[16] = {0, 0, 0, 0, 8000, 16000, 22050, 24000, 32000, 44100, 48000,
                                      96000, 0, 0, 0, 0};
@@ -656,11 +665,19 @@ hipError_t launch_assemble(hipStream_t st, const fhip_params &p, const int32_t *
     const int bps = p.bits_per_sample;
     const int vsize = (p.channels == 2) ? 16 + ((n * (bps + bps + 1) + 7) >> 3)
                                         : 16 + ((n * p.channels * bps + 7) >> 3);
+    if (frame_n) {
+        note_launch("k_assemble ragged");
+        hipLaunchKernelGGL(k_assemble<true>, dim3(nframes), dim3(AT), 0, st, p, n, pcm, info, rice,
+                           (long long)slot_bytes, frames, (long long)frame_stride, frame_bytes,
+                           number_base, number_step, numbers, sr0, sr1, bpsc, vsize, frame_src, dev_frames,
+                           pcm_format == FHIP_PCM_S16 ? 1 : 0, MultiBin{}, frame_n);
+        return hipGetLastError();
+    }
     note_launch("k_assemble");
-    hipLaunchKernelGGL(k_assemble, dim3(nframes), dim3(AT), 0, st, p, n, pcm, info, rice,
+    hipLaunchKernelGGL(k_assemble<false>, dim3(nframes), dim3(AT), 0, st, p, n, pcm, info, rice,
                        (long long)slot_bytes, frames, (long long)frame_stride, frame_bytes,
                        number_base, number_step, numbers, sr0, sr1, bpsc, vsize, frame_src, dev_frames,
-                       pcm_format == FHIP_PCM_S16 ? 1 : 0, MultiBin{});
+                       pcm_format == FHIP_PCM_S16 ? 1 : 0, MultiBin{}, (const int32_t *)nullptr);
     return hipGetLastError();
 }
 
@@ -684,8 +701,9 @@ hipError_t launch_assemble_bins(hipStream_t st, const fhip_params &p, const Mult
     }
     for (int i = 1; i < 8; i++) if (p.bits_per_sample == bd_table[i]) { bpsc = i; break; }
     note_launch("k_assemble bins");
-    hipLaunchKernelGGL(k_assemble, dim3(slots), dim3(AT), 0, st, p, 0, pcm, info, rice, 0ll, frames, 0ll,
-                       frame_bytes, 0u, 0u, numbers, sr0, sr1, bpsc, 0, frame_src, (const int32_t *)nullptr, 0, mb);
+    hipLaunchKernelGGL(k_assemble<false>, dim3(slots), dim3(AT), 0, st, p, 0, pcm, info, rice, 0ll, frames, 0ll,
+                       frame_bytes, 0u, 0u, numbers, sr0, sr1, bpsc, 0, frame_src, (const int32_t *)nullptr, 0, mb,
+                       (const int32_t *)nullptr);
     return hipGetLastError();
 }
 

@@ -326,9 +326,10 @@ __global__ void __launch_bounds__(HDR_T) k_verify_frames(VerifyArgs a)
             bool num_ok, cover_ok;
             if (numbered) {
                 // every frame is a whole block of its own stream: the table says which, the batch says where
-                rel = (long long)f * a.block_size;
+                // (ragged: the tables say where and how long; frame_src counts interleaved values)
+                rel = a.frame_src ? a.frame_src[f] / a.channels : (long long)f * a.block_size;
                 num_ok = h.number == (unsigned long long)a.numbers[f];
-                cover_ok = h.n == a.block_size;
+                cover_ok = h.n == (a.frame_n ? a.frame_n[f] : a.block_size);
             } else if (!a.allow_vbs) {
                 rel = (long long)f * a.block_size;
                 num_ok = snum == (unsigned long long)(a.first_sample + rel);

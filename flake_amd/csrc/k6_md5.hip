@@ -255,6 +255,53 @@ k_md5_streams(fhip_md5_state *__restrict__ states, int nstreams, const T *__rest
     }
 }
 
+// The general path for blocks of different lengths: block b of the tables is blk_vals[b] values at pcm + blk_off[b].
+template <class T, int BPS>
+__global__ void __launch_bounds__(MD5_WG)
+k_md5_streams_ragged(fhip_md5_state *__restrict__ states, int nstreams, const T *__restrict__ pcm,
+                     const int32_t *__restrict__ seg_first, const int32_t *__restrict__ seg_block,
+                     const long long *__restrict__ blk_off, const int32_t *__restrict__ blk_vals)
+{
+    __shared__ uint32_t tail[16 * MD5_WG];
+    const int lane = threadIdx.x;
+    const int s = blockIdx.x * MD5_WG + lane;
+    if (s >= nstreams) return;
+    const int b0 = seg_first[s], b1 = seg_first[s + 1];
+    if (b1 <= b0) return;                    // no block in this launch: the state is not touched
+    fhip_md5_state *st = states + s;
+    uint32_t h[4] = {st->h[0], st->h[1], st->h[2], st->h[3]};
+    uint32_t fill = st->fill;
+    {
+        const uint32_t *t = reinterpret_cast<const uint32_t *>(st->tail);
+#pragma unroll
+        for (int j = 0; j < 16; j++) tail[j * MD5_WG + lane] = t[j];
+    }
+    uint64_t bytes = 0;
+    for (int b = b0; b < b1; b++) {
+        const int blk = seg_block[b];
+        const T *p = pcm + (size_t)blk_off[blk];
+        const int vals = blk_vals[blk];
+        for (int i = 0; i < vals; i++) {
+            uint32_t x = (uint32_t)(int32_t)p[i];
+#pragma unroll
+            for (int k = 0; k < BPS; k++) {
+                tail_put(tail, lane, fill, x & 0xFFu);
+                x >>= 8;
+                if (++fill == 64) { tail_hash(h, tail, lane); fill = 0; }
+            }
+        }
+        bytes += (uint64_t)vals * BPS;
+    }
+    st->h[0] = h[0]; st->h[1] = h[1]; st->h[2] = h[2]; st->h[3] = h[3];
+    st->nbytes += bytes;
+    st->fill = fill;
+    {
+        uint32_t *t = reinterpret_cast<uint32_t *>(st->tail);
+#pragma unroll
+        for (int j = 0; j < 16; j++) t[j] = tail[j * MD5_WG + lane];
+    }
+}
+
 // fa_md5_final: 0x80, zeros up to 56 mod 64, the bit count; on a copy.
 __global__ void __launch_bounds__(MD5_WG) k_md5_final(const fhip_md5_state *__restrict__ states, int nstreams,
                                                       uint8_t *__restrict__ digests)
@@ -343,6 +390,26 @@ hipError_t launch_md5_streams(hipStream_t st, fhip_md5_state *states, int nstrea
     case 4: return launch_streams<int32_t, 4>(st, states, nstreams, pcm, block_vals, seg_first, seg_block, shape_fast, flag);
     default: return hipErrorInvalidValue;
     }
+}
+
+hipError_t launch_md5_streams_ragged(hipStream_t st, fhip_md5_state *states, int nstreams, const void *pcm,
+                                     int pcm_format, int bytes_per_sample, const int32_t *seg_first,
+                                     const int32_t *seg_block, const long long *blk_off, const int32_t *blk_vals)
+{
+    if (nstreams <= 0) return hipSuccess;
+    const bool s16 = pcm_format == FHIP_PCM_S16;
+    if (bytes_per_sample < 1 || bytes_per_sample > (s16 ? 2 : 4)) return hipErrorInvalidValue;
+    note_launch("k_md5_streams<%s,%d> ragged general", s16 ? "int16_t" : "int32_t", bytes_per_sample);
+    const int grid = (nstreams + MD5_WG - 1) / MD5_WG;
+#define LAUNCH_MR(T_, B_) hipLaunchKernelGGL((k_md5_streams_ragged<T_, B_>), dim3(grid), dim3(MD5_WG), 0, st, states, \
+                                             nstreams, static_cast<const T_ *>(pcm), seg_first, seg_block, blk_off, blk_vals)
+    if (s16) { if (bytes_per_sample == 1) LAUNCH_MR(int16_t, 1); else LAUNCH_MR(int16_t, 2); }
+    else if (bytes_per_sample == 1) LAUNCH_MR(int32_t, 1);
+    else if (bytes_per_sample == 2) LAUNCH_MR(int32_t, 2);
+    else if (bytes_per_sample == 3) LAUNCH_MR(int32_t, 3);
+    else LAUNCH_MR(int32_t, 4);
+#undef LAUNCH_MR
+    return hipGetLastError();
 }
 
 hipError_t launch_md5_final(hipStream_t st, const fhip_md5_state *states, int nstreams, uint8_t *digests)

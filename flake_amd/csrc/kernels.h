@@ -26,6 +26,28 @@ struct EncodeArgs {
     int nsub;         // subframes in this batch
 };
 
+// A ragged batch (fhip_frames_packed_begin_ragged): blocks of different lengths in one launch.  Frame f has frame_n[f]
+// samples per channel and its PCM starts at frame_src[f] (units of the PCM format, as for launch_prepare); frame_c[f]
+// is the window constant of lpc.c:34 for that length.  All three are device tables of nframes entries.  Rows of smp,
+// the Rice slots and the frame slots keep the stride of row_n (the handle's block size); nmax is the launch's longest
+// frame (<= row_n, <= FHIP_MAX_RESIDENT_BLOCK): it sizes LDS and K3's runs, nothing else.  The ragged launchers run the
+// generic instances (k_prepare / k_prepare_multi, k_autocorr_ragged, k_encode<C>, k_assemble) with every decision
+// the reference derives from the block length taken from the frame's own; K2 takes no length and is launch_lpc.
+struct RaggedFrames {
+    const int32_t *frame_n;
+    const long long *frame_src;
+    const double *frame_c;
+    int row_n, nmax;
+};
+hipError_t launch_prepare_ragged(hipStream_t st, const fhip_params &p, const int32_t *pcm, int nframes,
+                                 const RaggedFrames &rf, int32_t *smp, fhip_subframe_info *info, int pcm_format);
+hipError_t launch_autocorr_ragged(hipStream_t st, const int32_t *smp, int nsub, int nch, const RaggedFrames &rf,
+                                  int max_order, double *autoc);
+hipError_t launch_encode_ragged(hipStream_t st, const fhip_params &p, const int32_t *smp, int nsub,
+                                const RaggedFrames &rf, const int32_t *coefs, const int32_t *shift,
+                                const int32_t *opt_order, fhip_subframe_info *info, uint8_t *bits, int64_t slot_bytes,
+                                const fhip_subframe_info *prep);
+
 // K0: copy_samples + channel_decorrelation + remove_wasted_bits
 // (encode.c:541-694).  pcm [nframes][n][ch] -> smp [nframes][ch][n].
 // decide_only: write obits / wasted / ch_mode to info[] and leave smp to the fused K1.
@@ -130,7 +152,8 @@ hipError_t launch_assemble(hipStream_t st, const fhip_params &p, const int32_t *
                            int64_t slot_bytes, uint8_t *frames, int64_t frame_stride,
                            int32_t *frame_bytes, uint32_t number_base, uint32_t number_step,
                            const uint32_t *numbers = nullptr, const long long *frame_src = nullptr,
-                           const int32_t *dev_frames = nullptr, int pcm_format = FHIP_PCM_S32);
+                           const int32_t *dev_frames = nullptr, int pcm_format = FHIP_PCM_S32,
+                           const int32_t *frame_n = nullptr);       // frame_n (with frame_src): the ragged instance
 
 // K4-P: offsets[f] = exclusive scan of frame_bytes (offsets[nframes] = total) and the frames
 // copied back to back into packed[] -- the stream order flake_encode_frame's callers write.
@@ -240,6 +263,8 @@ struct VerifyArgs {
     long long *totals;                           // optional: fhip_encode_blocks_vbs_dev's totals
     const uint32_t *numbers;                     // optional [nframes], fixed blocks only: the number frame f must carry
                                                  // (frames of many streams in one batch); first_sample is unused then
+    const int32_t *frame_n = nullptr;            // optional, with numbers (the ragged numbered mode): frame f must hold exactly
+    const long long *frame_src = nullptr;        // frame_n[f] samples, found at frame_src[f] of pcm (units of the PCM format)
 };
 hipError_t launch_verify(hipStream_t st, const VerifyArgs &a);
 
@@ -254,6 +279,11 @@ hipError_t launch_md5_init(hipStream_t st, fhip_md5_state *states, int nstreams)
 hipError_t launch_md5_streams(hipStream_t st, fhip_md5_state *states, int nstreams, const void *pcm, int pcm_format,
                               int block_vals, int bytes_per_sample, const int32_t *seg_first,
                               const int32_t *seg_block, int32_t *flag, int32_t *host_flag, bool *shape_fast_out);
+// The general path over blocks given as (offset, length) pairs: block b is the blk_vals[b] interleaved values at
+// pcm + blk_off[b] (units of the PCM format); seg_block indexes those tables.
+hipError_t launch_md5_streams_ragged(hipStream_t st, fhip_md5_state *states, int nstreams, const void *pcm,
+                                     int pcm_format, int bytes_per_sample, const int32_t *seg_first,
+                                     const int32_t *seg_block, const long long *blk_off, const int32_t *blk_vals);
 hipError_t launch_md5_final(hipStream_t st, const fhip_md5_state *states, int nstreams, uint8_t *digests);
 
 }  // namespace fhip

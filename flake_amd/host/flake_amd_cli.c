@@ -201,16 +201,31 @@ static int run_set(const char *outdir, char **inputs, int ninputs, int synth_str
         for (int i = 0; i < S; i++)
             if (k < frames[i] / (uint32_t)bs && set_add(&r, i, data[i] + (size_t)k * bbytes, bs)) return 1;
     if (set_flush(&r, bs)) return 1;
-    for (int i = 0; i < S; i++) {                               /* tails: streams of equal tail length share calls */
-        const int tail = (int)(frames[i] % (uint32_t)bs);
-        int seen = 0;
-        for (int j = 0; j < i && !seen; j++) seen = (int)(frames[j] % (uint32_t)bs) == tail;
-        if (!tail || seen) continue;
-        for (int j = i; j < S; j++)
-            if ((int)(frames[j] % (uint32_t)bs) == tail &&
-                set_add(&r, j, data[j] + (size_t)(frames[j] / (uint32_t)bs) * bbytes, tail)) return 1;
-        if (set_flush(&r, tail)) return 1;
+    /* tails: every stream's last, short block in ONE ragged call (per cap_blocks streams), whatever their lengths */
+    int *tail_of = (int *)malloc(sizeof(int) * (size_t)r.cap_blocks);
+    if (!tail_of) { fprintf(stderr, "out of memory\n"); return 1; }
+    for (int i = 0; i <= S; i++) {
+        const int tail = i < S ? (int)(frames[i] % (uint32_t)bs) : 0;
+        if (i < S && tail) {
+            size_t at = 0;
+            for (int b = 0; b < r.count; b++) at += (size_t)tail_of[b] * nch * sample_bytes;
+            memcpy(r.pcm + at, data[i] + (size_t)(frames[i] / (uint32_t)bs) * bbytes, (size_t)tail * nch * sample_bytes);
+            tail_of[r.count] = tail;
+            r.stream_of[r.count++] = i;
+        }
+        if (r.count && (r.count == r.cap_blocks || i == S)) {
+            const long long n = flake_amd_set_encode_ragged(r.g, r.pcm, sample_bytes, r.count, tail_of, r.stream_of, r.buf,
+                                                            r.buf_cap, r.sizes);
+            if (n < 0) { fprintf(stderr, "encode error: %s\n", flake_amd_set_last_error(r.g)); return 1; }
+            size_t pos = 0;
+            for (int b = 0; b < r.count; b++) {
+                if (bytes_add(&outs[r.stream_of[b]], r.buf + pos, (size_t)r.sizes[b])) return 1;
+                pos += (size_t)r.sizes[b];
+            }
+            r.count = 0;
+        }
     }
+    free(tail_of);
     unsigned long long total_in = 0, total_out = 0;
     for (int i = 0; i < S; i++) {
         char path[4096];

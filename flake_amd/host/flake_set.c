@@ -303,6 +303,266 @@ FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples
     return total;
 }
 
+/* The short blocks of a call through the ragged packed path: cnt blocks back to back, block b sizes[b] samples long
+ * (every one shorter than the set's block size, one per stream: the caller has checked).  The twin of the loop in
+ * flake_amd_set_encode.  Returns the bytes written, -1 on an error, or -2 when the ABI does not cover this handle
+ * (FHIP_E_UNSUPPORTED on the first chunk: nothing has changed, the caller takes the per-length calls). */
+static long long set_encode_short(FlakeAmdSet *g, const void *samples, int sample_bytes, int cnt_all, const int *sizes,
+                                  const int *stream_of_block, unsigned char *out, size_t out_size, int *frame_sizes)
+{
+    if (grow_call_tables(g, cnt_all)) SET_FAIL("flake_amd_set_encode_ragged: out of host memory");
+    const int fmt = sample_bytes == 2 ? FHIP_PCM_S16 : FHIP_PCM_S32;
+    if (fmt != g->pcm_format) {
+        const int rc = fhip_set_pcm_format(g->hip, fmt);
+        if (rc != FHIP_OK) SET_FAIL("fhip_set_pcm_format: %s (%s)", fhip_strerror(rc), fhip_last_error(g->hip));
+        g->pcm_format = fmt;
+    }
+    for (int b = 0; b < cnt_all; b++) g->fnum[b] = g->frame_count[stream_of_block[b]];      /* one block per stream */
+    const size_t vbytes = (size_t)g->hp.channels * (size_t)sample_bytes;
+    const char *pcm = (const char *)samples;
+    long long total = 0;
+    int rc = FHIP_OK;
+    const char *what = "";
+    for (int b0 = 0; b0 < cnt_all && rc == FHIP_OK; b0 += g->max_batch) {
+        const int cnt = cnt_all - b0 < g->max_batch ? cnt_all - b0 : g->max_batch;
+        size_t chunk_samples = 0;
+        int largest = 0;
+        for (int b = 0; b < cnt; b++) {
+            chunk_samples += (size_t)sizes[b0 + b];
+            if (sizes[b0 + b] > largest) largest = sizes[b0 + b];
+        }
+        fhip_batch bt;
+        memset(&bt, 0, sizeof bt);
+        bt.pcm = (const int32_t *)pcm;
+        bt.nframes = cnt; bt.block_size = largest;
+        bt.frame_bytes = g->fbytes + b0;
+        bt.frame_numbers = g->fnum + b0;
+        what = "fhip_frames_packed_upload_ragged";
+        rc = fhip_frames_packed_upload_ragged(g->hip, &bt, (const int32_t *)(sizes + b0));
+        if (rc == FHIP_E_UNSUPPORTED && b0 == 0) return -2;
+        if (rc == FHIP_OK && g->dev_md5) {
+            int *first = g->scratch;
+            memset(first, 0, sizeof(int) * ((size_t)g->nstreams + 1));
+            for (int b = 0; b < cnt; b++) first[stream_of_block[b0 + b] + 1]++;
+            for (int s = 0; s < g->nstreams; s++) first[s + 1] += first[s];
+            for (int b = 0; b < cnt; b++) g->seg_block[first[stream_of_block[b0 + b]]++] = b;
+            for (int s = g->nstreams; s > 0; s--) first[s] = first[s - 1];
+            first[0] = 0;
+            what = "fhip_md5_update_uploaded_ragged";
+            rc = fhip_md5_update_uploaded_ragged(g->hip, g->dev_md5, g->nstreams, cnt, (const int32_t *)(sizes + b0),
+                                                 (const int32_t *)first, g->seg_block);
+        }
+        int64_t bytes = 0;
+        if (rc == FHIP_OK) {
+            what = "fhip_frames_packed_begin_ragged";
+            rc = fhip_frames_packed_begin_ragged(g->hip, &bt, (const int32_t *)(sizes + b0), &bytes);
+        }
+        if (rc == FHIP_E_VERIFY) {
+            int64_t vs[4] = {0, 0, -1, 0};
+            fhip_verify_rec vr = {0, -1, -1, -1};
+            (void)fhip_last_verify_failure(g->hip, vs, &vr);
+            (void)fhip_frames_packed_fetch_wait(g->hip);
+            g->broken = g->dev_md5 != NULL;
+            if (vs[2] < 0 || vs[2] >= cnt) SET_FAIL("fhip_frames_packed_begin_ragged: %s (%s)", fhip_strerror(rc), fhip_last_error(g->hip));
+            const int idx = b0 + (int)vs[2];
+            g->vfail = 1;
+            g->vfail_stream = stream_of_block[idx];
+            g->vfail_number = g->fnum[idx];
+            g->vfail_status = vr.status;
+            SET_FAIL("flake_amd_set_encode_ragged: verification failed: %lld of the chunk's %lld frames do not decode to "
+                     "the input; first: stream %d, frame %u (short block %d of the call), %s (subframe %d, sample %d, bit %d)",
+                     (long long)vs[1], (long long)vs[0], g->vfail_stream, g->vfail_number, idx,
+                     verify_status_name(vr.status), vr.subframe, vr.sample, vr.bit);
+        }
+        if (rc == FHIP_OK && (size_t)(total + bytes) > out_size) {
+            (void)fhip_frames_packed_fetch_wait(g->hip);
+            g->broken = g->dev_md5 != NULL;
+            SET_FAIL("flake_amd_set_encode_ragged: output buffer too small (%lld bytes needed so far, %zu given)",
+                     total + (long long)bytes, out_size);
+        }
+        if (rc == FHIP_OK) { what = "fhip_frames_packed_fetch_async"; rc = fhip_frames_packed_fetch_async(g->hip, out + total, (int64_t)(out_size - (size_t)total)); }
+        if (rc == FHIP_OK) total += bytes;
+        pcm += chunk_samples * vbytes;
+    }
+    const int rcw = fhip_frames_packed_fetch_wait(g->hip);
+    if (rc == FHIP_OK && rcw != FHIP_OK) { rc = rcw; what = "fhip_frames_packed_fetch_wait"; }
+    if (rc != FHIP_OK) {
+        g->broken = 1;
+        SET_FAIL("%s: %s (%s)", what, fhip_strerror(rc), fhip_last_error(g->hip));
+    }
+    for (int b = 0; b < cnt_all; b++)
+        if (g->fbytes[b] <= 0) { g->broken = 1; SET_FAIL("flake_amd_set_encode_ragged: frame %d was not encoded", b); }
+    pcm = (const char *)samples;
+    for (int b = 0; b < cnt_all; b++) {
+        const int s = stream_of_block[b], fs = g->fbytes[b];
+        const size_t nvals = (size_t)sizes[b] * (size_t)g->hp.channels;
+        if (frame_sizes) frame_sizes[b] = fs;
+        if (fs > g->max_frame[s]) g->max_frame[s] = fs;
+        if (!g->min_frame[s] || fs < g->min_frame[s]) g->min_frame[s] = fs;
+        g->frame_count[s]++;
+        g->samples[s] += (uint64_t)sizes[b];
+        g->ended[s] = 1;
+        if (g->host_md5) {
+            if (sample_bytes == 2) fa_md5_pcm16(&g->host_md5[s], (const int16_t *)pcm, nvals, g->hp.bits_per_sample);
+            else fa_md5_pcm(&g->host_md5[s], (const int32_t *)pcm, nvals, g->hp.bits_per_sample);
+        }
+        pcm += nvals * (size_t)sample_bytes;
+    }
+    if (g->host_md5) for (int s = 0; s < g->nstreams; s++) fa_md5_final(&g->host_md5[s], g->digests + 16 * (size_t)s);
+    if (g->dev_md5) g->digests_valid = 0;
+    return total;
+}
+
+/* Blocks of different lengths in one call.  The blocks are sorted into groups that one device path serves -- the
+ * full-length blocks (flake_amd_set_encode), the short ones (one ragged call; under FLAKE_AMD_SET_RAGGED=0, or where
+ * the ABI does not cover the handle, one uniform call per distinct length) -- each group is gathered, encoded and its
+ * frames put back in batch order.  A call that is a single group runs in place. */
+FLAKE_AMD_API long long flake_amd_set_encode_ragged(FlakeAmdSet *g, const void *samples, int sample_bytes, int nblocks,
+                                                    const int *block_sizes, const int *stream_of_block,
+                                                    unsigned char *out, size_t out_size, int *frame_sizes)
+{
+    if (!g) return -1;
+    g->err[0] = 0;
+    g->vfail = 0;
+    if (g->broken) SET_FAIL("flake_amd_set_encode_ragged: an earlier device error left the set unusable");
+    if (nblocks < 0 || (nblocks > 0 && (!samples || !block_sizes || !stream_of_block || !out)))
+        SET_FAIL("flake_amd_set_encode_ragged: null argument or negative block count");
+    if (sample_bytes != 4 && sample_bytes != 2) SET_FAIL("flake_amd_set_encode_ragged: sample_bytes must be 4 or 2");
+    if (sample_bytes == 2 && g->hp.bits_per_sample > 16)
+        SET_FAIL("flake_amd_set_encode_ragged: int16 samples need bits_per_sample <= 16");
+    if (nblocks == 0) return 0;
+    /* everything is checked before anything changes */
+    const int full = g->hp.block_size;
+    int *per = g->scratch;                /* 1: the stream has a short block in this call */
+    memset(per, 0, sizeof(int) * (size_t)g->nstreams);
+    int nshort = 0;
+    for (int b = 0; b < nblocks; b++) {
+        const int s = stream_of_block[b], n = block_sizes[b];
+        if (n < 1 || n > full) SET_FAIL("flake_amd_set_encode_ragged: block_sizes[%d] = %d is out of range (encode.c:987)", b, n);
+        if (s < 0 || s >= g->nstreams) SET_FAIL("flake_amd_set_encode_ragged: stream_of_block[%d] = %d is outside the set's %d streams", b, s, g->nstreams);
+        if (g->ended[s] || per[s])
+            SET_FAIL("flake_amd_set_encode_ragged: block %d belongs to stream %d, which a short block has ended", b, s);
+        if (n != full) { per[s] = 1; nshort++; }
+    }
+    if (nshort == 0)
+        return flake_amd_set_encode(g, samples, sample_bytes, nblocks, full, stream_of_block, out, out_size, frame_sizes);
+    const char *er = getenv("FLAKE_AMD_SET_RAGGED");
+    int ragged = !(er && er[0] == '0');
+    if (ragged && nshort == nblocks) {
+        const long long r = set_encode_short(g, samples, sample_bytes, nblocks, block_sizes, stream_of_block, out, out_size, frame_sizes);
+        if (r != -2) return r;
+        ragged = 0;
+    }
+    /* groups: gid[b] = 0 for a full block, 1 for every short one (ragged) or 1 + k for the k-th distinct length */
+    const size_t vbytes = (size_t)g->hp.channels * (size_t)sample_bytes;
+    size_t all_samples = 0;
+    for (int b = 0; b < nblocks; b++) all_samples += (size_t)block_sizes[b];
+    int *gid = (int *)malloc(sizeof(int) * (size_t)nblocks * 6);
+    size_t *off = (size_t *)malloc(sizeof(size_t) * (size_t)nblocks * 2);
+    char *gpcm = (char *)malloc(all_samples * vbytes);
+    unsigned char *stash = (unsigned char *)malloc(out_size ? out_size : 1);
+    const size_t ns = (size_t)g->nstreams;
+    /* the streams as they are, put back if a later group fails */
+    uint32_t *sv_fc = (uint32_t *)malloc(ns * sizeof(uint32_t));
+    uint64_t *sv_sm = (uint64_t *)malloc(ns * sizeof(uint64_t));
+    int *sv_mm = (int *)malloc(ns * 2 * sizeof(int));
+    char *sv_en = (char *)malloc(ns);
+    fa_md5 *sv_md = g->host_md5 ? (fa_md5 *)malloc(ns * sizeof(fa_md5)) : NULL;
+    long long result = -1;
+#define RAGGED_DONE() do { free(gid); free(off); free(gpcm); free(stash); free(sv_fc); free(sv_sm); free(sv_mm); free(sv_en); free(sv_md); } while (0)
+    if (!gid || !off || !gpcm || !stash || !sv_fc || !sv_sm || !sv_mm || !sv_en || (g->host_md5 && !sv_md)) {
+        RAGGED_DONE();
+        SET_FAIL("flake_amd_set_encode_ragged: out of host memory");
+    }
+    int *members = gid + nblocks, *gsizes = gid + 2 * nblocks, *gstreams = gid + 3 * nblocks;
+    int *gfs = gid + 4 * nblocks, *fsz = gid + 5 * nblocks;      /* frame sizes: of the group's members / by block */
+    size_t *src = off + nblocks;          /* byte offset of block b in samples */
+    {
+        size_t at = 0;
+        for (int b = 0; b < nblocks; b++) { src[b] = at; at += (size_t)block_sizes[b] * vbytes; }
+    }
+    int ngroups = 1;                       /* group 0 may be empty */
+    for (int b = 0; b < nblocks; b++) {
+        if (block_sizes[b] == full) { gid[b] = 0; continue; }
+        if (ragged) { gid[b] = 1; ngroups = 2; continue; }
+        gid[b] = -1;
+        for (int a = 0; a < b; a++) if (block_sizes[a] == block_sizes[b]) { gid[b] = gid[a]; break; }
+        if (gid[b] < 0) gid[b] = ngroups++;
+    }
+    memcpy(sv_fc, g->frame_count, ns * sizeof(uint32_t)); memcpy(sv_sm, g->samples, ns * sizeof(uint64_t));
+    memcpy(sv_mm, g->min_frame, ns * sizeof(int)); memcpy(sv_mm + ns, g->max_frame, ns * sizeof(int));
+    memcpy(sv_en, g->ended, ns);
+    if (sv_md) memcpy(sv_md, g->host_md5, ns * sizeof(fa_md5));
+    size_t stash_at = 0;
+    int ok = 1;
+    for (int k = 0; k < ngroups && ok; k++) {
+        int cnt = 0;
+        size_t at = 0;
+        for (int b = 0; b < nblocks; b++) {
+            if (gid[b] != k) continue;
+            const size_t bytes = (size_t)block_sizes[b] * vbytes;
+            memcpy(gpcm + at, (const char *)samples + src[b], bytes);
+            at += bytes;
+            members[cnt] = b; gsizes[cnt] = block_sizes[b]; gstreams[cnt] = stream_of_block[b];
+            cnt++;
+        }
+        if (cnt == 0) continue;
+        long long r;
+        if (k == 1 && ragged) {
+            r = set_encode_short(g, gpcm, sample_bytes, cnt, gsizes, gstreams, stash + stash_at, out_size - stash_at, gfs);
+            if (r == -2) {
+                /* the ABI does not cover this handle: nothing of the short blocks has run; take the per-length calls */
+                ragged = 0;
+                ngroups = 1;
+                for (int b = 0; b < nblocks; b++) {
+                    if (gid[b] == 0) continue;
+                    gid[b] = -1;
+                    for (int a = 0; a < b; a++) if (gid[a] > 0 && block_sizes[a] == block_sizes[b]) { gid[b] = gid[a]; break; }
+                    if (gid[b] < 0) gid[b] = ngroups++;
+                }
+                k = 0;                     /* (the loop's k++ makes it 1: group 0 is done) */
+                continue;
+            }
+        } else {
+            r = flake_amd_set_encode(g, gpcm, sample_bytes, cnt, gsizes[0], gstreams, stash + stash_at, out_size - stash_at, gfs);
+        }
+        if (r < 0) { ok = 0; break; }
+        /* where each member's frame lies in the stash */
+        size_t fat = stash_at;
+        for (int i = 0; i < cnt; i++) {
+            off[members[i]] = fat;
+            fsz[members[i]] = gfs[i];
+            fat += (size_t)gfs[i];
+        }
+        stash_at += (size_t)r;
+    }
+    if (!ok) {
+        /* a group failed: its inner call has said why and committed nothing; the groups before it are taken back */
+        memcpy(g->frame_count, sv_fc, ns * sizeof(uint32_t)); memcpy(g->samples, sv_sm, ns * sizeof(uint64_t));
+        memcpy(g->min_frame, sv_mm, ns * sizeof(int)); memcpy(g->max_frame, sv_mm + ns, ns * sizeof(int));
+        memcpy(g->ended, sv_en, ns);
+        if (sv_md) {
+            memcpy(g->host_md5, sv_md, ns * sizeof(fa_md5));
+            for (int s = 0; s < g->nstreams; s++) fa_md5_final(&g->host_md5[s], g->digests + 16 * (size_t)s);
+        }
+        if (g->dev_md5 && stash_at > 0) g->broken = 1;     /* (the device hashes of the earlier groups have moved on) */
+        RAGGED_DONE();
+        return -1;
+    }
+    {
+        size_t at = 0;
+        for (int b = 0; b < nblocks; b++) {
+            memcpy(out + at, stash + off[b], (size_t)fsz[b]);
+            if (frame_sizes) frame_sizes[b] = fsz[b];
+            at += (size_t)fsz[b];
+        }
+        result = (long long)at;
+    }
+    RAGGED_DONE();
+#undef RAGGED_DONE
+    return result;
+}
+
 FLAKE_AMD_API int flake_amd_set_get_streaminfo(FlakeAmdSet *g, int stream, FlakeAmdStreaminfo *si)
 {
     if (!g || !si) return -1;

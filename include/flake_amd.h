@@ -158,7 +158,8 @@ FLAKE_AMD_API const char *flake_amd_last_error(const FlakeAmdContext *s);
  * device is FLAKE_AMD_DEVICE, the blocks per GPU batch FLAKE_AMD_BATCH (default 1024), as for single streams.
  * Verification is offered for sets through flake_amd_set_enable_verify below (flake_amd_set_verify is the single
  * stream's switch): the verifier holds every frame of a batch to its own stream's frame counter, whichever stream
- * owns it.  Variable block size, and blocks of different sizes within one call, stay outside sets.
+ * owns it.  Variable block size stays outside sets; blocks of different sizes share a call through
+ * flake_amd_set_encode_ragged.
  */
 #define FLAKE_AMD_SET_MD5_HOST 1u
 #define FLAKE_AMD_SET_MD5_OFF  2u
@@ -177,6 +178,26 @@ FLAKE_AMD_API FlakeAmdSet *flake_amd_set_open(const FlakeAmdContext *like, int n
 FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples, int sample_bytes, int nblocks,
                                              int block_size, const int *stream_of_block, unsigned char *out,
                                              size_t out_size, int *frame_sizes);
+/*
+ * The same with a length per block: block b is block_sizes[b] samples per channel (1 .. the streams' block size), the
+ * blocks back to back in `samples`, each at its own length.  This is how the tails of many streams -- which almost
+ * never share a length -- are written in ONE call.  The rules are flake_amd_set_encode's: a block shorter than the
+ * streams' block size ends its stream, so each stream has at most one and it is the stream's last block of the call;
+ * a stream's blocks appear in stream order; the frames arrive in batch order; an error (a second short block or a
+ * block behind a short one for a stream, a stream index outside the set, a size of 0 or above the block size, a bad
+ * argument) returns -1 with nothing changed for any stream.  Full-length and short blocks may share a call: the full
+ * ones take flake_amd_set_encode's path, the short ones the ragged packed path (fhip_frames_packed_begin_ragged,
+ * include/flakehip.h: the generic kernels with a length per frame), each frame byte for byte what a call of its own
+ * length writes.  Every MD5 mode, both sample widths and verification (flake_amd_set_enable_verify) work as above.
+ *   FLAKE_AMD_SET_RAGGED=0   (environment) the short blocks take one flake_amd_set_encode call per distinct length
+ *                            instead -- the comparison leg, and what the entry does by itself where the ragged path
+ *                            does not cover the set (block sizes above 16384).
+ * Closing S streams with distinct tails takes one call per FLAKE_AMD_BATCH short blocks instead of S calls;
+ * tools/set_tail_bench.py times both legs.
+ */
+FLAKE_AMD_API long long flake_amd_set_encode_ragged(FlakeAmdSet *g, const void *samples, int sample_bytes, int nblocks,
+                                                    const int *block_sizes, const int *stream_of_block,
+                                                    unsigned char *out, size_t out_size, int *frame_sizes);
 /* flake_get_streaminfo() for one stream of the set.  The first request after an encode finalises and fetches the
  * digests of ALL streams (one synchronisation); the streams stay open. */
 FLAKE_AMD_API int flake_amd_set_get_streaminfo(FlakeAmdSet *g, int stream, FlakeAmdStreaminfo *si);

@@ -225,6 +225,24 @@ FHIP_API int fhip_frames_packed_upload(fhip_ctx *ctx, const fhip_batch *b);
 FHIP_API int fhip_frames_packed_fetch_async(fhip_ctx *ctx, uint8_t *out, int64_t out_cap);
 FHIP_API int fhip_frames_packed_fetch_wait(fhip_ctx *ctx);
 
+/*
+ * Ragged batches: the same steps for blocks of DIFFERENT lengths in one call -- the last blocks of many streams
+ * (a stream set's tails), each encoded exactly as a uniform call of its own length encodes it.  block_sizes is a
+ * HOST table [b->nframes], every entry in 1 .. params.block_size; b->pcm is the blocks back to back, each at its own
+ * length; b->block_size must equal the largest entry; frame_numbers / first_frame_number as above (without a table
+ * frame f carries first_frame_number + f).  Every frame is byte for byte the frame fhip_encode_frames_packed
+ * produces for that block alone, and b->info / b->frame_bytes likewise.  The generic kernel instances run, with a
+ * per-frame length table on the device ("ragged" in fhip_last_launches); device slots keep the stride of
+ * params.block_size.  While fhip_set_verify is on, frame f must carry its number and hold exactly block_sizes[f]
+ * samples (fhip_verify_frames_ragged).  Both PCM formats are honoured (int16 blocks may start at any 2-byte
+ * boundary).  FHIP_E_UNSUPPORTED on a handle with allow_vbs, or with params.block_size > 16384 (callers fall back to
+ * one uniform call per length); FHIP_E_INVALID for a bad table, with nothing queued.  The fetch steps are
+ * fhip_frames_packed_fetch*.  _upload_ragged is the optional first step, as fhip_frames_packed_upload is.
+ */
+FHIP_API int fhip_frames_packed_upload_ragged(fhip_ctx *ctx, const fhip_batch *b, const int32_t *block_sizes);
+FHIP_API int fhip_frames_packed_begin_ragged(fhip_ctx *ctx, const fhip_batch *b, const int32_t *block_sizes,
+                                             int64_t *total_bytes);
+
 /* Page-locked host memory for the host-pointer entries above (libflake mallocs its frame buffer,
  * encode.c:453-454; a caller's PCM is whatever it read the file into, flake.c:622-630): copies from
  * and to pageable memory go through the runtime's bounce buffers at ~2/3 of the link's rate.
@@ -431,6 +449,19 @@ FHIP_API int fhip_verify_frames_numbered(fhip_ctx *ctx, const fhip_verify_in *in
                                          const fhip_verify_out *out);
 
 /*
+ * The ragged numbered mode: as fhip_verify_frames_numbered, but frame f must hold exactly block_sizes[f] samples
+ * (FHIP_VERIFY_NUMBER at bit 16 otherwise), and they are the samples at frame_src[f] of pcm -- an offset in
+ * interleaved values, a multiple of the channel count.  The host form takes a HOST block_sizes (entries in
+ * 1 .. params.block_size, their sum in->nsamples: FHIP_E_INVALID otherwise) and places the blocks back to back; the
+ * _dev form takes both tables as device memory.  frame_numbers is required.  allow_vbs handles: FHIP_E_UNSUPPORTED.
+ */
+FHIP_API int fhip_verify_frames_ragged_dev(fhip_ctx *ctx, const fhip_verify_in *in, const uint32_t *frame_numbers,
+                                           const int32_t *block_sizes, const int64_t *frame_src,
+                                           const fhip_verify_out *out);
+FHIP_API int fhip_verify_frames_ragged(fhip_ctx *ctx, const fhip_verify_in *in, const uint32_t *frame_numbers,
+                                       const int32_t *block_sizes, const fhip_verify_out *out);
+
+/*
  * Verification of the handle's own output, off by default.  While on:
  *   fhip_frames_packed_begin (and fhip_encode_frames_packed) and fhip_encode_blocks_vbs_packed run
  *   the verifier on the device-resident stream and PCM before they return, and return FHIP_E_VERIFY
@@ -440,6 +471,7 @@ FHIP_API int fhip_verify_frames_numbered(fhip_ctx *ctx, const fhip_verify_in *in
  *   A fixed-block batch with fhip_batch.frame_numbers set is verified against that table, frame by frame (the
  *   semantics of fhip_verify_frames_numbered: the frames may belong to many streams, in any order); without a table
  *   the frames must count up from first_frame_number.  A variable-block-size batch is verified in sequence either way.
+ *   fhip_frames_packed_begin_ragged is verified with the semantics of fhip_verify_frames_ragged.
  */
 FHIP_API int fhip_set_verify(fhip_ctx *ctx, int on);
 /* What the most recent host-synchronising verification of this handle found (fhip_verify_frames, _numbered, and the
@@ -498,6 +530,13 @@ FHIP_API void fhip_device_free(void *p);
  * it.  Updates of the same states through one handle run in call order. */
 FHIP_API int fhip_md5_update_uploaded(fhip_ctx *ctx, fhip_md5_state *states, int nstreams, int nblocks,
                                       int block_size, const int32_t *seg_first, const int32_t *seg_block);
+
+/* The same for a ragged upload (fhip_frames_packed_upload_ragged): block b of the tables is the upload's b-th
+ * block, block_sizes[b] samples long; nblocks and block_sizes (HOST) must match that upload.  Always the general
+ * path ("ragged general" in fhip_last_launches). */
+FHIP_API int fhip_md5_update_uploaded_ragged(fhip_ctx *ctx, fhip_md5_state *states, int nstreams, int nblocks,
+                                             const int32_t *block_sizes, const int32_t *seg_first,
+                                             const int32_t *seg_block);
 
 /* ---- measurement ---------------------------------------------------- */
 
