@@ -218,6 +218,11 @@ def load_library() -> C.CDLL:
         "fhip_md5_update_uploaded_ragged": (i, [vp, vp, i, i, vp, vp, vp]),
         "fhip_verify_frames_ragged_dev": (i, [vp, C.POINTER(VerifyIn), vp, vp, vp, C.POINTER(VerifyOut)]),
         "fhip_verify_frames_ragged": (i, [vp, C.POINTER(VerifyIn), vp, vp, C.POINTER(VerifyOut)]),
+        "fhip_encode_blocks_vbs_packed_numbered": (i, [vp, vp, i, i, vp, vp, i64, vp, vp, vp, C.POINTER(i64)]),
+        "fhip_set_block_numbering": (i, [vp, i]),
+        "fhip_verify_frames_blocks_dev": (i, [vp, C.POINTER(VerifyIn), vp, i, i, C.POINTER(VerifyOut)]),
+        "fhip_verify_frames_blocks": (i, [vp, C.POINTER(VerifyIn), vp, i, i, C.POINTER(VerifyOut)]),
+        "fhip_last_verify_number": (i, [vp, C.POINTER(C.c_uint32)]),
         "fhip_device_alloc": (vp, [C.c_size_t]),
         "fhip_device_free": (None, [vp]),
     }
@@ -245,6 +250,8 @@ ABI_SYMBOLS = (
     "fhip_device_alloc", "fhip_device_free",
     "fhip_frames_packed_upload_ragged", "fhip_frames_packed_begin_ragged", "fhip_md5_update_uploaded_ragged",
     "fhip_verify_frames_ragged_dev", "fhip_verify_frames_ragged",
+    "fhip_encode_blocks_vbs_packed_numbered", "fhip_set_block_numbering", "fhip_verify_frames_blocks_dev",
+    "fhip_verify_frames_blocks", "fhip_last_verify_number",
 )
 
 
@@ -366,6 +373,73 @@ class Encoder:
         if rc not in (OK, E_VERIFY):
             self._check(rc, what)
         return rc == OK, recs, summary, self.lib.fhip_last_error(self._h).decode() if rc else ""
+
+    # -- variable block size for blocks of many streams (the stream set's path at levels 9-12) ------------
+    def set_block_numbering(self, on: bool) -> None:
+        """fhip_set_block_numbering: frame_numbers of the packed path are first-sample numbers of one-frame blocks
+        of independent streams (allow_vbs handles only)."""
+        self._check(self.lib.fhip_set_block_numbering(self._h, int(on)), "fhip_set_block_numbering")
+
+    def encode_blocks_vbs_packed_numbered(self, pcm: np.ndarray, block_size: int, block_first):
+        """fhip_encode_blocks_vbs_packed_numbered on host data: pcm [nblocks * block_size][channels] int32, block b
+        numbered from block_first[b].  Returns (bytes, block_bytes, block_frames, block_max_frame); raises
+        FlakeHipError (code E_VERIFY while set_verify is on and a frame fails)."""
+        ch = self.params.channels
+        pcm = np.ascontiguousarray(pcm, dtype=np.int32).reshape(-1, block_size, ch)
+        bf = np.ascontiguousarray(block_first, dtype=np.uint32)
+        nb = pcm.shape[0]
+        if len(bf) != nb:
+            raise ValueError("block_first needs one entry per block")
+        cap = 64 + pcm.size * 5 + 64 * (nb + 1) * 8
+        out = np.zeros(cap, dtype=np.uint8)
+        bb, bfr, bmx = (np.zeros(max(nb, 1), dtype=np.int32) for _ in range(3))
+        wrote = C.c_int64(0)
+        self._check(self.lib.fhip_encode_blocks_vbs_packed_numbered(
+            self._h, pcm.ctypes.data, nb, block_size, bf.ctypes.data, out.ctypes.data, cap, bb.ctypes.data,
+            bfr.ctypes.data, bmx.ctypes.data, C.byref(wrote)), "fhip_encode_blocks_vbs_packed_numbered")
+        return out[:wrote.value].copy(), bb[:nb], bfr[:nb], bmx[:nb]
+
+    def verify_frames_blocks(self, stream, frame_bytes, pcm, block_first, block_size: int, nblocks: int | None = None):
+        """K5's block-table mode on host data (fhip_verify_frames_blocks): pcm holds nblocks blocks of block_size
+        samples, block b starts at sample block_first[b] of its stream.  nblocks defaults to len(block_first).
+        Returns (ok, records, summary int64[4], error text) as verify_frames does."""
+        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
+                                  else stream, dtype=np.uint8)
+        fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
+        pc = np.ascontiguousarray(pcm, dtype=np.int32).reshape(-1, self.params.channels)
+        bf = np.ascontiguousarray(block_first, dtype=np.uint32)
+        nb = len(bf) if nblocks is None else int(nblocks)
+        if nb > len(bf):
+            raise ValueError("block_first is shorter than nblocks")
+        recs = np.zeros(len(fb), dtype=VERIFY_REC_DTYPE)
+        summary = np.zeros(4, dtype=np.int64)
+        vi = VerifyIn(st.ctypes.data if st.size else None, st.size, fb.ctypes.data if fb.size else None, len(fb),
+                      pc.ctypes.data if pc.size else None, pc.shape[0], 0)
+        vo = VerifyOut(recs.ctypes.data if len(fb) else None, summary.ctypes.data)
+        rc = self.lib.fhip_verify_frames_blocks(self._h, C.byref(vi), bf.ctypes.data if bf.size else None, nb,
+                                                block_size, C.byref(vo))
+        if rc not in (OK, E_VERIFY):
+            self._check(rc, "fhip_verify_frames_blocks")
+        return rc == OK, recs, summary, self.lib.fhip_last_error(self._h).decode() if rc else ""
+
+    def verify_frames_blocks_dev(self, stream, stream_bytes: int, frame_bytes, nframes: int, pcm, nsamples: int,
+                                 block_first, nblocks: int, block_size: int, summary, records=None) -> None:
+        """The same on device-resident data (torch tensors or raw device addresses); async."""
+        vi = VerifyIn(_ptr(stream), stream_bytes, _ptr(frame_bytes), nframes, _ptr(pcm), nsamples, 0)
+        vo = VerifyOut(_ptr(records), _ptr(summary))
+        self._check(self.lib.fhip_verify_frames_blocks_dev(self._h, C.byref(vi), _ptr(block_first), nblocks,
+                                                           block_size, C.byref(vo)), "fhip_verify_frames_blocks_dev")
+
+    def last_verify_failure(self):
+        """(summary int64[4], record, required number or None) of the handle's most recent host-synchronising
+        verification (fhip_last_verify_failure, fhip_last_verify_number); None when no frame failed."""
+        summary = np.zeros(4, dtype=np.int64)
+        rec = np.zeros(1, dtype=VERIFY_REC_DTYPE)
+        if self.lib.fhip_last_verify_failure(self._h, summary.ctypes.data, rec.ctypes.data) != 1:
+            return None
+        num = C.c_uint32(0)
+        have = self.lib.fhip_last_verify_number(self._h, C.byref(num)) == 1
+        return summary, rec[0], (num.value if have else None)
 
     def kernel_times(self, reset: bool = True) -> dict:
         names = (C.c_char_p * 8)()
@@ -726,12 +800,13 @@ class HostEncoder:
             pass
 
 
-SET_MD5_HOST, SET_MD5_OFF = 1, 2      # FLAKE_AMD_SET_*
+SET_MD5_HOST, SET_MD5_OFF, SET_VBS = 1, 2, 4      # FLAKE_AMD_SET_*
 
 
 class StreamSet:
     """A stream set of the host C layer (flake_amd_set_*): many independent streams of one format per batch,
-    each stream's MD5 carried on the device.  ctypes only; no compute here."""
+    each stream's MD5 carried on the device.  flags=SET_VBS opens a set with variable block size (levels 9-12: int32
+    samples only, a block may become several frames).  ctypes only; no compute here."""
 
     def __init__(self, nstreams: int, level: int = 5, channels: int = 2, bits_per_sample: int = 16,
                  sample_rate: int = 44100, flags: int = 0, **over):

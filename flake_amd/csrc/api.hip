@@ -87,6 +87,9 @@ struct fhip_ctx {
     DevBuf<long long> d_srcoff, d_frame_src, d_totals;
     DevBuf<int32_t> d_order, d_vcnt, d_first;
     DevBuf<int32_t> d_stream_bytes, d_blk_bytes, d_blk_frames;
+    DevBuf<int32_t> d_blk_max;        // fhip_encode_blocks_vbs_packed_numbered: every block's largest frame ...
+    DevBuf<uint32_t> d_blk_first;     // ... and the host's block_first table uploaded
+    bool block_numbering = false;     // fhip_set_block_numbering: frame_numbers are one-frame blocks of many streams
 
     // two internal streams for the split-batch overlap (run_pipeline)
     static constexpr int NAUX = 4;       // (run_pipeline's split uses the first two, the VBS groups all)
@@ -128,6 +131,8 @@ struct fhip_ctx {
     DevBuf<uint32_t> d_vnum;                  // fhip_verify_frames_numbered: the host number table uploaded
     long long vfail_sum[4] = {0, 0, -1, 0};   // fhip_last_verify_failure: the most recent verdict's summary ...
     fhip_verify_rec vfail_rec{0, -1, -1, -1}; // ... and its first failing frame's record
+    bool vfail_has_number = false;            // fhip_last_verify_number: the number that frame had to carry, where a
+    uint32_t vfail_number = 0;                // table said so
 
     std::vector<std::string> launches;        // fhip_last_launches: what the most recent call queued
 
@@ -466,10 +471,12 @@ int ensure_verify(fhip_ctx *c, size_t nframes)
 // size for the handle's own batches; params.block_size for a caller's stream).  recs null: the handle's own.
 // numbers (device, [nframes]; fixed-block handles only): the number each frame must carry, when the batch's
 // frames belong to several streams -- first_sample is unused then.  Null: numbered by position, as a single stream.
+// block_first (device, [nblocks]; allow_vbs handles only): the block-table mode of a variable-block-size batch.
 int run_verify(fhip_ctx *c, const uint8_t *stream, long long stream_bytes, const int32_t *frame_bytes, int nframes,
                const long long *dev_count, const int32_t *pcm, long long nsamples, long long first_sample,
                int block_size, fhip_verify_rec *recs, int64_t *summary, long long *totals, const uint32_t *numbers,
-               const int32_t *frame_n = nullptr, const long long *frame_src = nullptr)
+               const int32_t *frame_n = nullptr, const long long *frame_src = nullptr,
+               const uint32_t *block_first = nullptr, int nblocks = 0)
 {
     int rc = ensure_verify(c, (size_t)nframes);
     if (rc != FHIP_OK) return rc;
@@ -480,6 +487,8 @@ int run_verify(fhip_ctx *c, const uint8_t *stream, long long stream_bytes, const
                        reinterpret_cast<unsigned long long *>(c->d_vsum + 4), totals, numbers};
     a.frame_n = frame_n;              // the ragged numbered mode: both tables or neither
     a.frame_src = frame_src;
+    a.block_first = block_first;      // the block-table mode (allow_vbs handles): nblocks blocks of block_size samples
+    a.nblocks = nblocks;
     Prof pr(c, kProfVerify, c->profiling);
     HIP_TRY(c, fhip::launch_verify(c->stream, a));
     return FHIP_OK;
@@ -495,18 +504,38 @@ const char *verify_status_name(int s)
 // After the stream synchronised: summary (host copy) -> FHIP_OK, or FHIP_E_VERIFY with the first failing frame
 // named in the handle's error text (its record read from recs, device).  numbers (HOST, optional): the table of a
 // numbered batch; the text then also says which number that frame had to carry.
+// block_first (HOST, optional, [nblocks] blocks of block_size samples): the table of a block-table batch; the number
+// then follows from where K5 placed the frame (its VerifyFrame), when it could be placed.
 int verify_verdict(fhip_ctx *c, const long long *summary, const fhip_verify_rec *recs,
-                   const uint32_t *numbers = nullptr)
+                   const uint32_t *numbers = nullptr, const uint32_t *block_first = nullptr, int nblocks = 0,
+                   int block_size = 0)
 {
     for (int i = 0; i < 4; i++) c->vfail_sum[i] = summary[i];
     c->vfail_rec = fhip_verify_rec{(int32_t)summary[3], -1, -1, -1};
+    c->vfail_has_number = false;
     if (summary[1] <= 0) return FHIP_OK;
     fhip_verify_rec r{(int32_t)summary[3], -1, -1, -1};
     if (recs && summary[2] >= 0)
         HIP_TRY(c, hipMemcpy(&r, recs + summary[2], sizeof r, hipMemcpyDeviceToHost));
     c->vfail_rec = r;
+    if (numbers && summary[2] >= 0) {
+        c->vfail_has_number = true;
+        c->vfail_number = numbers[summary[2]];
+    } else if (block_first && block_size > 0 && summary[2] >= 0) {
+        fhip::VerifyFrame vf{};
+        HIP_TRY(c, hipMemcpy(&vf, c->d_vws + summary[2], sizeof vf, hipMemcpyDeviceToHost));
+        // K5's header pass left its own status there: OK / CRC8 (placed, numbered right) or NUMBER at bit 32 (placed,
+        // numbered wrong) say that rel_start is where the frame lies; anything else was never placed
+        const long long blk = vf.rel_start / block_size;
+        const bool placed = vf.status == FHIP_VERIFY_OK || vf.status == FHIP_VERIFY_CRC8 ||
+                            (vf.status == FHIP_VERIFY_NUMBER && vf.bit == 32);
+        if (placed && vf.rel_start >= 0 && blk < nblocks) {
+            c->vfail_has_number = true;
+            c->vfail_number = block_first[blk] + (uint32_t)(vf.rel_start - blk * block_size);
+        }
+    }
     char want[48] = "";
-    if (numbers && summary[2] >= 0) snprintf(want, sizeof want, ", required to carry number %u", numbers[summary[2]]);
+    if (c->vfail_has_number) snprintf(want, sizeof want, ", required to carry number %u", c->vfail_number);
     char buf[320];
     snprintf(buf, sizeof buf,
              "verification failed: %lld of %lld frames do not decode to the input; first: frame %lld%s, %s "
@@ -1142,12 +1171,15 @@ int fhip_frames_packed_begin(fhip_ctx *c, const fhip_batch *b, int64_t *total_by
     // an explicit number table on a fixed-block handle: the frames may be of many streams, each is held to its own
     // entry (the table is on the device already); a variable-block-size batch numbers samples and stays in sequence
     const bool numbered = b->frame_numbers && !c->p.allow_vbs;
+    // ... unless the caller has said that the table names one-frame blocks of independent streams (fhip_set_block_numbering)
+    const bool blocks = b->frame_numbers && c->p.allow_vbs && c->block_numbering;
     if (c->verify) {
         const long long num0 = b->frame_numbers ? (long long)b->frame_numbers[0] : (long long)b->first_frame_number;
         const long long first = c->p.allow_vbs ? num0 : num0 * (long long)b->block_size;
         rc = run_verify(c, c->d_packed, (long long)fb, c->d_fbytes, b->nframes, nullptr, c->d_pcm,
                         (long long)b->nframes * b->block_size, numbered ? 0 : first, b->block_size, nullptr, nullptr,
-                        nullptr, numbered ? (const uint32_t *)c->d_fnum : nullptr);
+                        nullptr, numbered ? (const uint32_t *)c->d_fnum : nullptr, nullptr, nullptr,
+                        blocks ? (const uint32_t *)c->d_fnum : nullptr, blocks ? b->nframes : 0);
         if (rc != FHIP_OK) return rc;
         HIP_TRY(c, hipMemcpyAsync(vsum, c->d_vsum, sizeof vsum, hipMemcpyDeviceToHost, c->stream));
     }
@@ -1160,7 +1192,7 @@ int fhip_frames_packed_begin(fhip_ctx *c, const fhip_batch *b, int64_t *total_by
     if (rc != FHIP_OK) return rc;
     c->packed_ready = total;
     *total_bytes = total;
-    return c->verify ? verify_verdict(c, vsum, c->d_vrec, numbered ? b->frame_numbers : nullptr) : FHIP_OK;
+    return c->verify ? verify_verdict(c, vsum, c->d_vrec, (numbered || blocks) ? b->frame_numbers : nullptr) : FHIP_OK;
 }
 
 int fhip_frames_packed_fetch(fhip_ctx *c, uint8_t *out, int64_t out_cap)
@@ -1591,6 +1623,8 @@ struct VbsOut {
     uint8_t *packed; long long cap;           // device
     int32_t *stream_bytes, *block_bytes, *block_frames;   // device, optional
     long long *totals;                        // device [4]
+    const uint32_t *block_first = nullptr;    // device [nblocks], optional: blocks of many streams (k_vbs_plan)
+    int32_t *block_max_frame = nullptr;       // device [nblocks], optional
 };
 
 // The buffers of a VBS batch (first use; grow-only): the piece tables k_vbs_plan leaves, the per-slot frame tables and
@@ -1779,7 +1813,7 @@ int vbs_dev_core(fhip_ctx *c, const int32_t *pcm, int nblocks, int block_size, u
     HIP_TRY(c, fhip::launch_vbs_split(c->stream, pcm, nblocks, block_size, p.channels, c->d_opt, c->d_shift));
     HIP_TRY(c, fhip::launch_vbs_plan(c->stream, c->d_opt, c->d_shift, nblocks, block_size, p.channels,
                                      first_frame_number, b.vb, c->d_vcnt, c->d_order, c->d_frame_src, c->d_srcoff,
-                                     c->d_fnum, c->d_first));
+                                     c->d_fnum, c->d_first, o.block_first));
 
     // ---- one pass of the path per bin ----
     // A bin is a few hundred frames -- too few workgroups to fill the chip, and eight bins one
@@ -1824,7 +1858,7 @@ int vbs_dev_core(fhip_ctx *c, const int32_t *pcm, int nblocks, int block_size, u
                                              8 * nblocks, c->d_vcnt + fhip::VBS_CNT_ALL, c->d_offsets,
                                              o.packed, o.cap, o.stream_bytes, o.totals));
     HIP_TRY(c, fhip::launch_vbs_block_bytes(c->stream, c->d_first, c->d_offsets, nblocks, o.block_bytes,
-                                            o.block_frames));
+                                            o.block_frames, o.block_max_frame));
     return FHIP_OK;
 }
 
@@ -1893,14 +1927,14 @@ int fhip_encode_blocks_vbs_dev(fhip_ctx *c, const int32_t *pcm, int nblocks, int
                       nullptr);
 }
 
-int fhip_encode_blocks_vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, int block_size,
-                                  uint32_t first_frame_number, uint8_t *out, int64_t out_cap,
-                                  int32_t *block_bytes, int32_t *block_frames, int64_t *out_bytes,
-                                  int32_t *max_frame_bytes, uint32_t *next_frame_number)
+namespace {
+// fhip_encode_blocks_vbs_packed and its _numbered twin.  block_first (HOST, [nblocks]) null: one stream numbered from
+// first_frame_number, and every launch is that entry's.  With the table: blocks of many streams, a pending
+// fhip_frames_packed_upload of the same batch is taken over, block_max_frame is filled, K5 runs in block-table mode.
+int vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, int block_size, uint32_t first_frame_number,
+               const uint32_t *block_first, uint8_t *out, int64_t out_cap, int32_t *block_bytes, int32_t *block_frames,
+               int32_t *block_max_frame, int64_t *out_bytes, int32_t *max_frame_bytes, uint32_t *next_frame_number)
 {
-    int rc = vbs_check(c, pcm, nblocks, block_size);
-    if (rc != FHIP_OK) return rc;
-    if (!out || !out_bytes || !block_bytes) return fail(c, FHIP_E_INVALID, "null argument");
     LaunchScope ls(c);
     const fhip_params &p = c->p;
     *out_bytes = 0;
@@ -1909,12 +1943,13 @@ int fhip_encode_blocks_vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, 
     if (next_frame_number) *next_frame_number = first_frame_number;
     if (nblocks == 0) return FHIP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    rc = ensure_staging(c, 0);
+    int rc = ensure_staging(c, 0);
     if (rc != FHIP_OK) return rc;
     fhip::VbsBins vb;
     long long frames_bytes = 0, bits_bytes = 0;
     if (vbs_bins(c, nblocks, block_size, &vb, &frames_bytes, &bits_bytes) != FHIP_OK)
         return fail(c, FHIP_E_INVALID, "nblocks * 8 exceeds the handle's max_frames");
+    if (block_first && c->fetch_pending) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_fetch, 0));   // d_packed is still being read
     HIP_TRY(c, c->d_packed.reserve((size_t)frames_bytes));
     const size_t nb = (size_t)c->max_frames / 8 + 2;
     HIP_TRY(c, c->d_totals.reserve(4));
@@ -1923,18 +1958,37 @@ int fhip_encode_blocks_vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, 
 
     // one upload, the batch on the device, one download of the stream's bytes
     const size_t nvals = (size_t)nblocks * block_size * (size_t)p.channels;
-    rc = stage_pcm(c, pcm, nvals * sizeof(int32_t));
-    if (rc != FHIP_OK) return rc;
-    if (c->verify) HIP_TRY(c, c->d_stream_bytes.reserve((size_t)c->max_frames));
-    rc = vbs_dev_core(c, c->d_pcm, nblocks, block_size, first_frame_number,
-                      VbsOut{c->d_packed, (long long)c->d_packed.cap, c->verify ? c->d_stream_bytes : nullptr,
-                             c->d_blk_bytes, block_frames ? c->d_blk_frames : nullptr, c->d_totals});
+    VbsOut vo{c->d_packed, (long long)c->d_packed.cap, c->verify ? c->d_stream_bytes.get() : nullptr,
+              c->d_blk_bytes, block_frames ? c->d_blk_frames.get() : nullptr, c->d_totals};
+    if (block_first) {
+        HIP_TRY(c, c->d_blk_first.reserve(nb));
+        if (block_max_frame) HIP_TRY(c, c->d_blk_max.reserve(nb));
+        // (what fhip_frames_packed_upload brought is this batch: an MD5 update may be reading it beside us)
+        const bool uploaded = c->uploaded_pcm == pcm && c->uploaded_vals == nvals && c->uploaded_frames == nblocks &&
+                              c->uploaded_n == block_size;
+        c->uploaded_pcm = nullptr;
+        if (!uploaded) {
+            rc = stage_pcm(c, pcm, nvals * sizeof(int32_t));
+            if (rc != FHIP_OK) return rc;
+        }
+        HIP_TRY(c, hipMemcpyAsync(c->d_blk_first, block_first, (size_t)nblocks * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        vo.block_first = c->d_blk_first;
+        vo.block_max_frame = block_max_frame ? c->d_blk_max.get() : nullptr;
+    } else {
+        rc = stage_pcm(c, pcm, nvals * sizeof(int32_t));
+        if (rc != FHIP_OK) return rc;
+    }
+    if (c->verify) {
+        HIP_TRY(c, c->d_stream_bytes.reserve((size_t)c->max_frames));
+        vo.stream_bytes = c->d_stream_bytes;
+    }
+    rc = vbs_dev_core(c, c->d_pcm, nblocks, block_size, first_frame_number, vo);
     if (rc != FHIP_OK) return rc;
     long long vsum[4] = {0, 0, -1, 0};
     if (c->verify) {
         rc = run_verify(c, c->d_packed, (long long)c->d_packed.cap, c->d_stream_bytes, 8 * nblocks, c->d_totals,
-                        c->d_pcm, (long long)nblocks * block_size, first_frame_number, block_size, nullptr, nullptr,
-                        nullptr, nullptr);
+                        c->d_pcm, (long long)nblocks * block_size, block_first ? 0 : first_frame_number, block_size,
+                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, vo.block_first, nblocks);
         if (rc != FHIP_OK) return rc;
         HIP_TRY(c, hipMemcpyAsync(vsum, c->d_vsum, sizeof vsum, hipMemcpyDeviceToHost, c->stream));
     }
@@ -1943,6 +1997,8 @@ int fhip_encode_blocks_vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, 
     HIP_TRY(c, hipMemcpyAsync(block_bytes, c->d_blk_bytes, (size_t)nblocks * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (block_frames)
         HIP_TRY(c, hipMemcpyAsync(block_frames, c->d_blk_frames, (size_t)nblocks * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (vo.block_max_frame)
+        HIP_TRY(c, hipMemcpyAsync(block_max_frame, c->d_blk_max, (size_t)nblocks * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     rc = fhip_sync(c);
     if (rc != FHIP_OK) return rc;
     // every FRAME is checked (k_frame_offsets_perm, totals[3] bit 1), before anything is copied out: a piece that
@@ -1951,7 +2007,7 @@ int fhip_encode_blocks_vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, 
     for (int b = 0; b < nblocks; b++)
         if (block_bytes[b] <= 0) return fail(c, FHIP_E_GENERIC, "a frame of the batch was not encoded");
     if (c->verify) {
-        rc = verify_verdict(c, vsum, c->d_vrec);
+        rc = verify_verdict(c, vsum, c->d_vrec, nullptr, block_first, nblocks, block_size);
         if (rc != FHIP_OK) return rc;
     }
     if (totals[1] > out_cap) return fail(c, FHIP_E_INVALID, "output buffer too small for the batch's frames");
@@ -1959,6 +2015,40 @@ int fhip_encode_blocks_vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, 
     if (max_frame_bytes) *max_frame_bytes = (int32_t)totals[2];
     if (next_frame_number) *next_frame_number = first_frame_number + (uint32_t)((long long)nblocks * block_size);
     *out_bytes = totals[1];
+    return FHIP_OK;
+}
+}  // namespace
+
+int fhip_encode_blocks_vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, int block_size,
+                                  uint32_t first_frame_number, uint8_t *out, int64_t out_cap,
+                                  int32_t *block_bytes, int32_t *block_frames, int64_t *out_bytes,
+                                  int32_t *max_frame_bytes, uint32_t *next_frame_number)
+{
+    int rc = vbs_check(c, pcm, nblocks, block_size);
+    if (rc != FHIP_OK) return rc;
+    if (!out || !out_bytes || !block_bytes) return fail(c, FHIP_E_INVALID, "null argument");
+    return vbs_packed(c, pcm, nblocks, block_size, first_frame_number, nullptr, out, out_cap, block_bytes, block_frames,
+                      nullptr, out_bytes, max_frame_bytes, next_frame_number);
+}
+
+int fhip_encode_blocks_vbs_packed_numbered(fhip_ctx *c, const int32_t *pcm, int nblocks, int block_size,
+                                           const uint32_t *block_first, uint8_t *out, int64_t out_cap,
+                                           int32_t *block_bytes, int32_t *block_frames, int32_t *block_max_frame,
+                                           int64_t *out_bytes)
+{
+    int rc = vbs_check(c, pcm, nblocks, block_size);
+    if (rc != FHIP_OK) return rc;
+    if (!block_first || !out || !out_bytes || !block_bytes) return fail(c, FHIP_E_INVALID, "null argument");
+    return vbs_packed(c, pcm, nblocks, block_size, 0, block_first, out, out_cap, block_bytes, block_frames,
+                      block_max_frame, out_bytes, nullptr, nullptr);
+}
+
+int fhip_set_block_numbering(fhip_ctx *c, int on)
+{
+    if (!c) return FHIP_E_INVALID;
+    if (!c->p.allow_vbs)
+        return fail(c, FHIP_E_UNSUPPORTED, "block numbering needs a handle with allow_vbs (frames numbered by sample)");
+    c->block_numbering = on != 0;
     return FHIP_OK;
 }
 
@@ -2097,6 +2187,72 @@ int fhip_verify_frames_ragged(fhip_ctx *c, const fhip_verify_in *in, const uint3
     if (rc != FHIP_OK) return rc;
     for (int i = 0; i < 4; i++) out->summary[i] = sum[i];
     return verify_verdict(c, sum, c->d_vrec, frame_numbers);
+}
+
+namespace {
+int verify_blocks_check(fhip_ctx *c, const fhip_verify_in *in, const uint32_t *block_first, int nblocks, int block_size,
+                        const fhip_verify_out *out)
+{
+    int rc = verify_check(c, in, out, false);
+    if (rc != FHIP_OK) return rc;
+    if (!c->p.allow_vbs)
+        return fail(c, FHIP_E_UNSUPPORTED, "the block-table mode needs a handle with allow_vbs (frames numbered by "
+                                           "sample); a fixed-block batch takes a frame number table");
+    if (nblocks < 0 || (nblocks > 0 && !block_first)) return fail(c, FHIP_E_INVALID, "null block table or negative count");
+    if (block_size < 1 || block_size > c->p.block_size) return fail(c, FHIP_E_INVALID, "block_size out of range (encode.c:987)");
+    return FHIP_OK;
+}
+}  // namespace
+
+int fhip_verify_frames_blocks_dev(fhip_ctx *c, const fhip_verify_in *in, const uint32_t *block_first, int nblocks,
+                                  int block_size, const fhip_verify_out *out)
+{
+    int rc = verify_blocks_check(c, in, block_first, nblocks, block_size, out);
+    if (rc != FHIP_OK) return rc;
+    if (nblocks == 0 && in->nframes > 0) return fail(c, FHIP_E_INVALID, "frames without blocks");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return run_verify(c, in->stream, in->stream_bytes, in->frame_bytes, in->nframes, nullptr, in->pcm, in->nsamples, 0,
+                      block_size, out->frames, out->summary, nullptr, nullptr, nullptr, nullptr, block_first, nblocks);
+}
+
+int fhip_verify_frames_blocks(fhip_ctx *c, const fhip_verify_in *in, const uint32_t *block_first, int nblocks,
+                              int block_size, const fhip_verify_out *out)
+{
+    int rc = verify_blocks_check(c, in, block_first, nblocks, block_size, out);
+    if (rc != FHIP_OK) return rc;
+    if (nblocks == 0 && in->nframes > 0) return fail(c, FHIP_E_INVALID, "frames without blocks");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t sb = (size_t)in->stream_bytes, nf = (size_t)in->nframes, nb = (size_t)nblocks;
+    const size_t nv = (size_t)in->nsamples * (size_t)c->p.channels;
+    HIP_TRY(c, c->d_vstream.reserve(sb));
+    HIP_TRY(c, c->d_vfb.reserve(nf));
+    HIP_TRY(c, c->d_vpcm.reserve(nv));
+    HIP_TRY(c, c->d_vnum.reserve(nb));
+    if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_vstream, in->stream, sb, hipMemcpyHostToDevice, c->stream));
+    if (nf) HIP_TRY(c, hipMemcpyAsync(c->d_vfb, in->frame_bytes, nf * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (nv) HIP_TRY(c, hipMemcpyAsync(c->d_vpcm, in->pcm, nv * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
+    if (nb) HIP_TRY(c, hipMemcpyAsync(c->d_vnum, block_first, nb * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    // (without blocks there are no frames either: the sequence mode's empty launch)
+    rc = run_verify(c, c->d_vstream, in->stream_bytes, c->d_vfb, in->nframes, nullptr, c->d_vpcm, in->nsamples, 0,
+                    block_size, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                    nb ? (const uint32_t *)c->d_vnum : nullptr, nblocks);
+    if (rc != FHIP_OK) return rc;
+    long long sum[4] = {0, 0, -1, 0};
+    HIP_TRY(c, hipMemcpyAsync(sum, c->d_vsum, sizeof sum, hipMemcpyDeviceToHost, c->stream));
+    if (out->frames && nf)
+        HIP_TRY(c, hipMemcpyAsync(out->frames, c->d_vrec, nf * sizeof(fhip_verify_rec), hipMemcpyDeviceToHost, c->stream));
+    rc = fhip_sync(c);
+    if (rc != FHIP_OK) return rc;
+    for (int i = 0; i < 4; i++) out->summary[i] = sum[i];
+    return verify_verdict(c, sum, c->d_vrec, nullptr, block_first, nblocks, block_size);
+}
+
+int fhip_last_verify_number(const fhip_ctx *c, uint32_t *number)
+{
+    if (!c) return FHIP_E_INVALID;
+    if (!c->vfail_has_number || c->vfail_sum[1] <= 0) return 0;
+    if (number) *number = c->vfail_number;
+    return 1;
 }
 
 int fhip_last_verify_failure(const fhip_ctx *c, int64_t *summary, fhip_verify_rec *first)

@@ -780,15 +780,21 @@ void k_pack_frames(const uint8_t *__restrict__ frames, long long stride, const i
 //   per slot:   frame_src (offset of the piece's PCM in int32 units), src_off (byte offset of the
 //               slot's frame in frames[]), numbers (its first sample: encode.c:969-975, allow_vbs)
 //   first[b]    stream index of block b's first frame (first[nblocks] = frames in all)
+// block_first (optional, a launch-wide choice): the blocks belong to several streams and block b's pieces are numbered
+// from block_first[b] -- block_first[b] + the piece's offset inside its block -- instead of first_number + the piece's
+// offset in the batch; both sums wrap at 32 bits.
 // A block the splitter left whole (nframes <= 1) is one piece of eight eighths (vbs.c:100,
 // encode.c:1001).
 constexpr int PLAN_NT = 1024;
 
+// TABLE: the instance that numbers from block_first[] (the other is the kernel as it was and never reads the pointer)
+template <bool TABLE>
 __global__ __launch_bounds__(PLAN_NT)
 void k_vbs_plan(const int32_t *__restrict__ nfr, const int32_t *__restrict__ sizes, int nblocks,
                 int block_size, int nch, uint32_t first_number, VbsBins bins,
                 int32_t *__restrict__ cnt, int32_t *__restrict__ order, long long *__restrict__ frame_src,
-                long long *__restrict__ src_off, uint32_t *__restrict__ numbers, int32_t *__restrict__ first)
+                long long *__restrict__ src_off, uint32_t *__restrict__ numbers, int32_t *__restrict__ first,
+                const uint32_t *__restrict__ block_first)
 {
     // Round 4: a thread owns one block of every 1024 (coalesced reads of the splitter's verdicts, the running totals
     // carried from chunk to chunk) -- a thread that owned nblocks / 1024 consecutive blocks walked them by dependent
@@ -809,10 +815,12 @@ void k_vbs_plan(const int32_t *__restrict__ nfr, const int32_t *__restrict__ siz
         const bool on = b < nblocks;
         int f = 0;
         int len[8];
+        uint32_t bfirst = 0;
 #pragma unroll
         for (int q = 0; q < 8; q++) len[q] = 0;
         if (on) {
             f = nfr[b];
+            if constexpr (TABLE) bfirst = block_first[b];
             const int4 s0 = *reinterpret_cast<const int4 *>(sizes + (size_t)b * 8);
             const int4 s1 = *reinterpret_cast<const int4 *>(sizes + (size_t)b * 8 + 4);
             len[0] = s0.x; len[1] = s0.y; len[2] = s0.z; len[3] = s0.w;
@@ -857,6 +865,8 @@ void k_vbs_plan(const int32_t *__restrict__ nfr, const int32_t *__restrict__ siz
         if (on) {
             first[b] = run[8];
             long long pos = (long long)b * block_size;
+            // the number of the block's first sample, less pos: numbers[slot] = nbase + pos either way
+            const uint32_t nbase = TABLE ? bfirst - (uint32_t)pos : first_number;
 #pragma unroll
             for (int q = 0; q < 8; q++) {
                 if (q < f) {
@@ -868,7 +878,7 @@ void k_vbs_plan(const int32_t *__restrict__ nfr, const int32_t *__restrict__ siz
                     order[run[8]++] = slot;
                     frame_src[slot] = pos * nch;
                     src_off[slot] = s_froff[k] + (long long)j * s_stride[k];
-                    numbers[slot] = first_number + (uint32_t)pos;
+                    numbers[slot] = nbase + (uint32_t)pos;
                     pos += len[q];
                 }
             }
@@ -984,16 +994,24 @@ void k_pack_frames_perm(const uint8_t *__restrict__ frames, const long long *__r
     }
 }
 
-// bytes and frames of every block (what flake_encode_frame returns for it, vbs.c:104-116)
+// bytes and frames of every block (what flake_encode_frame returns for it, vbs.c:104-116); block_max_frame
+// (optional): the block's largest frame -- what encode.c:967 keeps per stream, for a batch of many streams
 __global__ __launch_bounds__(NT)
 void k_vbs_block_bytes(const int32_t *__restrict__ first, const long long *__restrict__ offsets, int nblocks,
-                       int32_t *__restrict__ block_bytes, int32_t *__restrict__ block_frames)
+                       int32_t *__restrict__ block_bytes, int32_t *__restrict__ block_frames,
+                       int32_t *__restrict__ block_max_frame)
 {
     const int b = blockIdx.x * NT + threadIdx.x;
     if (b >= nblocks) return;
     const int i0 = first[b], i1 = first[b + 1];
     if (block_bytes) block_bytes[b] = (int32_t)(offsets[i1] - offsets[i0]);
     if (block_frames) block_frames[b] = i1 - i0;
+    if (block_max_frame) {
+        // a block is at most eight frames; offsets[] is the scan of their sizes in stream order
+        long long mx = 0;
+        for (int i = i0; i < i1; i++) mx = max(mx, offsets[i + 1] - offsets[i]);
+        block_max_frame[b] = (int32_t)mx;
+    }
 }
 
 }  // namespace
@@ -1001,12 +1019,18 @@ void k_vbs_block_bytes(const int32_t *__restrict__ first, const long long *__res
 hipError_t launch_vbs_plan(hipStream_t st, const int32_t *nfr, const int32_t *sizes, int nblocks,
                            int block_size, int nch, uint32_t first_number, const VbsBins &bins,
                            int32_t *cnt, int32_t *order, long long *frame_src, long long *src_off,
-                           uint32_t *numbers, int32_t *first)
+                           uint32_t *numbers, int32_t *first, const uint32_t *block_first)
 {
     if (nblocks == 0) return hipSuccess;
-    note_launch("k_vbs_plan");
-    hipLaunchKernelGGL(k_vbs_plan, dim3(1), dim3(PLAN_NT), 0, st, nfr, sizes, nblocks, block_size, nch,
-                       first_number, bins, cnt, order, frame_src, src_off, numbers, first);
+    if (block_first) {
+        note_launch("k_vbs_plan<block_first>");
+        hipLaunchKernelGGL(k_vbs_plan<true>, dim3(1), dim3(PLAN_NT), 0, st, nfr, sizes, nblocks, block_size, nch,
+                           first_number, bins, cnt, order, frame_src, src_off, numbers, first, block_first);
+    } else {
+        note_launch("k_vbs_plan");
+        hipLaunchKernelGGL(k_vbs_plan<false>, dim3(1), dim3(PLAN_NT), 0, st, nfr, sizes, nblocks, block_size, nch,
+                           first_number, bins, cnt, order, frame_src, src_off, numbers, first, block_first);
+    }
     return hipGetLastError();
 }
 
@@ -1026,12 +1050,12 @@ hipError_t launch_pack_frames_perm(hipStream_t st, const uint8_t *frames, const 
 }
 
 hipError_t launch_vbs_block_bytes(hipStream_t st, const int32_t *first, const long long *offsets, int nblocks,
-                                  int32_t *block_bytes, int32_t *block_frames)
+                                  int32_t *block_bytes, int32_t *block_frames, int32_t *block_max_frame)
 {
-    if (nblocks == 0 || (!block_bytes && !block_frames)) return hipSuccess;
+    if (nblocks == 0 || (!block_bytes && !block_frames && !block_max_frame)) return hipSuccess;
     note_launch("k_vbs_block_bytes");
     hipLaunchKernelGGL(k_vbs_block_bytes, dim3((nblocks + NT - 1) / NT), dim3(NT), 0, st, first, offsets,
-                       nblocks, block_bytes, block_frames);
+                       nblocks, block_bytes, block_frames, block_max_frame);
     return hipGetLastError();
 }
 

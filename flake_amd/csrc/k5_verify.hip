@@ -10,7 +10,9 @@
 //   k_verify_frames  one workgroup: prefix of frame_bytes -> frame offsets, one lane per frame
 //                    parses its header (sync, codes, UTF-8 number, CRC-8) and numbering/coverage
 //                    is checked against the neighbouring frame -- or, with VerifyArgs.numbers, against
-//                    the frame's own entry of the table; VerifyFrame records + summary init
+//                    the frame's own entry of the table; or, with VerifyArgs.block_first (variable block size,
+//                    blocks of many streams), against the block the frame falls into by the sizes of the frames
+//                    before it; VerifyFrame records + summary init
 //   k_verify         one workgroup (256 lanes) per frame: subframes, padding, CRC-16, length
 //   k_verify_final   summary[2..3] from the first failing frame; optional flag bit in totals[3]
 //
@@ -271,6 +273,8 @@ __device__ long long block_excl_scan(long long v, long long *scratch, int nwaves
     return base + incl - v;
 }
 
+// BLOCKS: the block-table mode (VerifyArgs.block_first), an instance of its own -- the other is the kernel as it was
+template <bool BLOCKS>
 __global__ void __launch_bounds__(HDR_T) k_verify_frames(VerifyArgs a)
 {
     __shared__ long long scratch[HDR_T / 64];
@@ -284,7 +288,11 @@ __global__ void __launch_bounds__(HDR_T) k_verify_frames(VerifyArgs a)
         count = d < 0 ? 0 : (d < (long long)a.nframes ? (int)d : a.nframes);
     }
     const int t = threadIdx.x;
-    const bool numbered = a.numbers && !a.allow_vbs;      // a launch-wide choice: every wave takes one branch
+    const bool numbered = !BLOCKS && a.numbers && !a.allow_vbs;      // a launch-wide choice: every wave takes one branch
+    // block-table mode: the samples so far, and from bit BAD_SHIFT up the frames so far whose header did not parse
+    // (a frame holds at most 65535 samples and a batch far fewer than 2^24 frames: the two never meet)
+    constexpr int BAD_SHIFT = 40;
+    long long sbase = 0;
     if (t == 0) {
         a.summary[0] = count;
         a.summary[1] = 0;
@@ -318,13 +326,35 @@ __global__ void __launch_bounds__(HDR_T) k_verify_frames(VerifyArgs a)
         // (fixed blocks of many streams) frame f carries numbers[f] and its samples lie at f * block_size of pcm:
         // nothing of a neighbouring frame is read
         const unsigned long long snum = a.allow_vbs ? h.number : h.number * (unsigned long long)a.block_size;
-        s_next[t] = snum + (unsigned long long)h.n;
-        s_ok[t] = h.status == FHIP_VERIFY_OK || h.status == FHIP_VERIFY_CRC8;
+        if constexpr (!BLOCKS) {
+            s_next[t] = snum + (unsigned long long)h.n;
+            s_ok[t] = h.status == FHIP_VERIFY_OK || h.status == FHIP_VERIFY_CRC8;
+        }
         __syncthreads();
+        // block-table mode: a frame starts where the frames before it end -- the exclusive scan of their header-parsed
+        // sizes, as a sequential decoder counts -- and a frame behind one whose header did not parse cannot be placed
+        long long S = 0;
+        if constexpr (BLOCKS) {
+            const bool parsed = live && (h.status == FHIP_VERIFY_OK || h.status == FHIP_VERIFY_CRC8);
+            long long stot = 0;
+            S = sbase + block_excl_scan(parsed ? (long long)h.n : (live ? 1ll << BAD_SHIFT : 0ll), scratch, HDR_T / 64, &stot);
+            sbase += stot;
+        }
         if (live && (h.status == FHIP_VERIFY_OK || h.status == FHIP_VERIFY_CRC8)) {
             long long rel;
             bool num_ok, cover_ok;
-            if (numbered) {
+            if constexpr (BLOCKS) {
+                // the frame lies in block S / block_size at offset S % block_size; the table says what the first
+                // sample of that block is called in its own stream.  Only the sample count so far crosses frames.
+                const bool placeable = (S >> BAD_SHIFT) == 0;
+                S &= (1ll << BAD_SHIFT) - 1;
+                const long long blk = S / a.block_size;
+                const int off = (int)(S - blk * a.block_size);
+                const bool placed = placeable && blk < (long long)a.nblocks;
+                rel = S;
+                num_ok = !placed || h.number == (unsigned long long)(uint32_t)(a.block_first[blk] + (uint32_t)off);
+                cover_ok = placed && off + h.n <= a.block_size && (f != count - 1 || S + h.n == a.nsamples);
+            } else if (numbered) {
                 // every frame is a whole block of its own stream: the table says which, the batch says where
                 // (ragged: the tables say where and how long; frame_src counts interleaved values)
                 rel = a.frame_src ? a.frame_src[f] / a.channels : (long long)f * a.block_size;
@@ -780,8 +810,13 @@ __global__ void k_verify_final(VerifyArgs a)
 
 hipError_t launch_verify(hipStream_t st, const VerifyArgs &a)
 {
-    note_launch("k_verify_frames");
-    hipLaunchKernelGGL(k_verify_frames, dim3(1), dim3(HDR_T), 0, st, a);
+    if (a.block_first && a.allow_vbs) {
+        note_launch("k_verify_frames<blocks>");
+        hipLaunchKernelGGL(k_verify_frames<true>, dim3(1), dim3(HDR_T), 0, st, a);
+    } else {
+        note_launch("k_verify_frames");
+        hipLaunchKernelGGL(k_verify_frames<false>, dim3(1), dim3(HDR_T), 0, st, a);
+    }
     if (a.nframes > 0) {
         note_launch("k_verify");
         hipLaunchKernelGGL(k_verify, dim3(a.nframes), dim3(VT), 0, st, a);

@@ -216,7 +216,9 @@ constexpr int VBS_CNT_FRAMES = 0, VBS_CNT_SUB = 8, VBS_CNT_ALL = 16, VBS_CNT_WOR
 hipError_t launch_vbs_plan(hipStream_t st, const int32_t *nfr, const int32_t *sizes, int nblocks,
                            int block_size, int nch, uint32_t first_number, const VbsBins &bins,
                            int32_t *cnt, int32_t *order, long long *frame_src, long long *src_off,
-                           uint32_t *numbers, int32_t *first);
+                           uint32_t *numbers, int32_t *first, const uint32_t *block_first = nullptr);
+// (block_first, optional device [nblocks]: the blocks of many streams -- block b's pieces are numbered from
+// block_first[b] instead of first_number + the block's offset in the batch)
 // The frames of all bins packed in stream order: order[i] = slot of the stream's i-th frame,
 // src_off[slot] = byte offset of that slot's frame in frames[] (4-byte aligned), *dev_frames of them
 // (<= max_frames); offsets[i] / offsets[count] as in launch_pack_frames; stream_bytes[i] (optional)
@@ -226,7 +228,8 @@ hipError_t launch_pack_frames_perm(hipStream_t st, const uint8_t *frames, const 
                                    const int32_t *dev_frames, long long *offsets, uint8_t *packed,
                                    long long cap, int32_t *stream_bytes, long long *totals);
 hipError_t launch_vbs_block_bytes(hipStream_t st, const int32_t *first, const long long *offsets, int nblocks,
-                                  int32_t *block_bytes, int32_t *block_frames);
+                                  int32_t *block_bytes, int32_t *block_frames,
+                                  int32_t *block_max_frame = nullptr);    // optional: block b's largest frame
 
 // K-vbs: split_frame_v1 (vbs.c:36-83) for nblocks blocks: nframes_out [nblocks],
 // sizes_out [nblocks][8].
@@ -265,6 +268,12 @@ struct VerifyArgs {
                                                  // (frames of many streams in one batch); first_sample is unused then
     const int32_t *frame_n = nullptr;            // optional, with numbers (the ragged numbered mode): frame f must hold exactly
     const long long *frame_src = nullptr;        // frame_n[f] samples, found at frame_src[f] of pcm (units of the PCM format)
+    // The block-table mode (allow_vbs only; without the table every launch is the sequence mode's): the batch is nblocks
+    // blocks of block_size samples, each of some stream and of one or more frames; where a frame lies follows from the
+    // header-parsed sizes of the frames before it (a scan), and a frame at offset `off` of block b must carry
+    // block_first[b] + off.  first_sample is unused then.
+    const uint32_t *block_first = nullptr;       // optional [nblocks]
+    int nblocks = 0;
 };
 hipError_t launch_verify(hipStream_t st, const VerifyArgs &a);
 

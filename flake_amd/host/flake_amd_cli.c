@@ -6,8 +6,8 @@
  *
  *   flake_amd_cli [-0..-12] [-b blocksize] [--verify] in.wav out.flac
  *   flake_amd_cli [-0..-12] --synth FRAMES [--channels C] [--bps B] [--verify] out.flac
- *   flake_amd_cli [-0..-8] [-b blocksize] --set OUTDIR [--verify] in1.wav in2.wav ...
- *   flake_amd_cli [-0..-8] --set OUTDIR [--verify] --synth-streams S --synth FRAMES [--channels C] [--bps B]
+ *   flake_amd_cli [-0..-12] [-b blocksize] --set OUTDIR [--verify] in1.wav in2.wav ...
+ *   flake_amd_cli [-0..-12] --set OUTDIR [--verify] --synth-streams S --synth FRAMES [--channels C] [--bps B]
  *
  * --set encodes inputs of one format as a stream set (flake_amd_set_*): their blocks round-robin in shared GPU
  * batches, every stream's MD5 carried on the device, one OUTDIR/<name>.flac per input with its own STREAMINFO --
@@ -155,7 +155,9 @@ static int run_set(const char *outdir, char **inputs, int ninputs, int synth_str
     if (flake_amd_set_defaults(&s.params)) return 1;
     if (bsize > 0) s.params.block_size = bsize;
     if (flake_amd_validate_params(&s) < 0) { fprintf(stderr, "invalid parameters\n"); return 1; }
-    const int bs = s.params.block_size, nch = s.channels, narrow = s.bits_per_sample <= 16;
+    /* (variable block size, levels 9-12: the set takes int32 samples only) */
+    const int bs = s.params.block_size, nch = s.channels;
+    const int narrow = s.bits_per_sample <= 16 && !s.params.variable_block_size;
     const int sample_bytes = narrow ? 2 : 4;
     /* every input whole in memory (a harness): int16 samples where the files hold 16 bits or fewer */
     for (int i = 0; i < S; i++) {
@@ -184,7 +186,7 @@ static int run_set(const char *outdir, char **inputs, int ninputs, int synth_str
 
     set_run r;
     memset(&r, 0, sizeof r);
-    r.g = flake_amd_set_open(&s, S, 0);
+    r.g = flake_amd_set_open(&s, S, s.params.variable_block_size ? FLAKE_AMD_SET_VBS : 0);
     if (!r.g) { fprintf(stderr, "%s\n", flake_amd_set_last_error(NULL)); return 1; }
     if (verify && flake_amd_set_enable_verify(r.g, 1)) { fprintf(stderr, "cannot turn verification on\n"); return 1; }
     r.sample_bytes = sample_bytes; r.bs = bs; r.nch = nch; r.cap_blocks = 1024; r.outs = outs;
@@ -280,7 +282,7 @@ int main(int argc, char **argv)
             else inputs[ninputs++] = argv[i];
         }
         if (!setdir || (!ninputs && (synth_streams < 1 || synth < 1)) || (ninputs && synth_streams)) {
-            fprintf(stderr, "usage: %s [-0..-8] [-b blocksize] --set OUTDIR [--verify] (in1.wav in2.wav ... | --synth-streams S --synth FRAMES [--channels C] [--bps B])\n", argv[0]);
+            fprintf(stderr, "usage: %s [-0..-12] [-b blocksize] --set OUTDIR [--verify] (in1.wav in2.wav ... | --synth-streams S --synth FRAMES [--channels C] [--bps B])\n", argv[0]);
             return 2;
         }
         return run_set(setdir, inputs, ninputs, synth_streams, synth, level, bsize, channels, bps, verify);
@@ -297,7 +299,7 @@ int main(int argc, char **argv)
     }
     if (!out || (!in && !synth)) {
         fprintf(stderr, "usage: %s [-0..-12] [-b blocksize] [--verify] (in.wav | --synth FRAMES [--channels C] [--bps B]) out.flac\n"
-                        "       %s [-0..-8] [-b blocksize] --set OUTDIR [--verify] (in1.wav in2.wav ... | --synth-streams S --synth FRAMES [--channels C] [--bps B])\n",
+                        "       %s [-0..-12] [-b blocksize] --set OUTDIR [--verify] (in1.wav in2.wav ... | --synth-streams S --synth FRAMES [--channels C] [--bps B])\n",
                 argv[0], argv[0]);
         return 2;
     }

@@ -13,6 +13,11 @@
  * Verification (flake_amd_set_enable_verify) is the handle's own (fhip_set_verify): the packed path hands the chunk's
  * number table to the verifier, which holds every frame to its own stream's counter.  The verifier speaks of batch
  * indices; this file maps an index back to its stream and that stream's frame number.
+ *
+ * Variable block size (FLAKE_AMD_SET_VBS, levels 9-12): frames are numbered by their first sample, a block may become
+ * several frames and a short block ends nothing (encode.c:993).  Blocks the splitter takes (a multiple of 8, at least
+ * 128 samples: encode.c:997-999) go through fhip_encode_blocks_vbs_packed_numbered with each block's first-sample
+ * number; every other length goes through the packed path as one frame per block, with fhip_set_block_numbering on.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -28,6 +33,7 @@ struct FlakeAmdSet {
     int nstreams;
     unsigned flags;
     int max_batch;                        /* blocks per GPU batch (FLAKE_AMD_BATCH, default 1024) */
+    int vbs;                              /* FLAKE_AMD_SET_VBS: frames numbered by sample, blocks may split */
     int pcm_format;
     int verbatim_size;                    /* of a full block: where max_frame_size starts (encode.c:446-450) */
     int broken;                           /* a device call failed half way: the streams' state is unknown */
@@ -47,6 +53,7 @@ struct FlakeAmdSet {
     uint32_t *fnum;
     int32_t *fbytes;
     int32_t *seg_block;
+    int32_t *bframes, *bmax;              /* variable block size: frames per block, each block's largest frame */
     int cap_blocks;
     char err[256];
 };
@@ -66,6 +73,7 @@ FLAKE_AMD_API void flake_amd_set_close(FlakeAmdSet *g)
     }
     free(g->frame_count); free(g->samples); free(g->min_frame); free(g->max_frame); free(g->ended);
     free(g->scratch); free(g->host_md5); free(g->digests); free(g->fnum); free(g->fbytes); free(g->seg_block);
+    free(g->bframes); free(g->bmax);
     free(g);
 }
 
@@ -76,11 +84,13 @@ FLAKE_AMD_API FlakeAmdSet *flake_amd_set_open(const FlakeAmdContext *like, int n
     FlakeAmdSet *g = NULL;
     if (!like || flake_amd_validate_params(like) < 0) OPEN_FAIL("flake_amd_set_open: invalid parameters (flake_validate_params)");
     if (nstreams < 1) OPEN_FAIL("flake_amd_set_open: nstreams must be at least 1");
-    if ((flags & ~(FLAKE_AMD_SET_MD5_HOST | FLAKE_AMD_SET_MD5_OFF)) ||
+    if ((flags & ~(FLAKE_AMD_SET_MD5_HOST | FLAKE_AMD_SET_MD5_OFF | FLAKE_AMD_SET_VBS)) ||
         (flags & (FLAKE_AMD_SET_MD5_HOST | FLAKE_AMD_SET_MD5_OFF)) == (FLAKE_AMD_SET_MD5_HOST | FLAKE_AMD_SET_MD5_OFF))
         OPEN_FAIL("flake_amd_set_open: unknown or contradictory flags");
-    if (like->params.variable_block_size || like->params.allow_vbs)
+    if ((like->params.variable_block_size || like->params.allow_vbs) && !(flags & FLAKE_AMD_SET_VBS))
         OPEN_FAIL("flake_amd_set_open: variable block size (levels 9-12) is not supported for stream sets");
+    if ((flags & FLAKE_AMD_SET_VBS) && !like->params.variable_block_size)
+        OPEN_FAIL("flake_amd_set_open: FLAKE_AMD_SET_VBS needs parameters with variable block size (levels 9-12)");
     {
         const char *eha = getenv("FLAKE_AMD_HOST_ASSEMBLY"), *ehv = getenv("FLAKE_AMD_HOST_VBS");
         if ((eha && eha[0] == '1') || (ehv && ehv[0] == '1'))
@@ -91,6 +101,7 @@ FLAKE_AMD_API FlakeAmdSet *flake_amd_set_open(const FlakeAmdContext *like, int n
     if (!g) OPEN_FAIL("flake_amd_set_open: out of host memory");
     g->nstreams = nstreams;
     g->flags = flags;
+    g->vbs = (flags & FLAKE_AMD_SET_VBS) != 0;
     fhip_params *hp = &g->hp;
     hp->channels = like->channels; hp->sample_rate = like->sample_rate;
     hp->bits_per_sample = like->bits_per_sample; hp->block_size = like->params.block_size;
@@ -100,7 +111,7 @@ FLAKE_AMD_API FlakeAmdSet *flake_amd_set_open(const FlakeAmdContext *like, int n
     hp->max_prediction_order = like->params.max_prediction_order;
     hp->min_partition_order = like->params.min_partition_order;
     hp->max_partition_order = like->params.max_partition_order;
-    hp->variable_block_size = 0; hp->allow_vbs = 0;
+    hp->variable_block_size = g->vbs; hp->allow_vbs = g->vbs;        /* (validated: variable_block_size implies allow_vbs) */
     hp->lpc_precision = 15;                                       /* encode.c:443 */
     {
         const int bps = hp->bits_per_sample, n = hp->block_size;  /* encode.c:521-527 */
@@ -110,8 +121,11 @@ FLAKE_AMD_API FlakeAmdSet *flake_amd_set_open(const FlakeAmdContext *like, int n
     const char *eb = getenv("FLAKE_AMD_BATCH"), *ed = getenv("FLAKE_AMD_DEVICE");
     g->max_batch = eb ? atoi(eb) : 1024;
     if (g->max_batch < 1) g->max_batch = 1;
-    const int rc = fhip_create(&g->hip, ed ? atoi(ed) : 0, hp, g->max_batch);
+    /* a block may become eight frames: the handle is sized as flake_amd_encode_init sizes it */
+    const int rc = fhip_create(&g->hip, ed ? atoi(ed) : 0, hp, g->vbs ? g->max_batch * 8 : g->max_batch);
     if (rc != FHIP_OK) { g->hip = NULL; OPEN_FAIL("flake_amd_set_open: fhip_create: %s", fhip_strerror(rc)); }
+    if (g->vbs && fhip_set_block_numbering(g->hip, 1) != FHIP_OK)
+        OPEN_FAIL("flake_amd_set_open: fhip_set_block_numbering: %s", fhip_last_error(g->hip));
     const size_t ns = (size_t)nstreams;
     g->frame_count = (uint32_t *)calloc(ns, sizeof(uint32_t));
     g->samples = (uint64_t *)calloc(ns, sizeof(uint64_t));
@@ -164,12 +178,18 @@ static const char *verify_status_name(int s)
 static int grow_call_tables(FlakeAmdSet *g, int nblocks)
 {
     if (nblocks <= g->cap_blocks) return 0;
-    free(g->fnum); free(g->fbytes); free(g->seg_block);
+    free(g->fnum); free(g->fbytes); free(g->seg_block); free(g->bframes); free(g->bmax);
+    g->bframes = g->bmax = NULL;
     g->cap_blocks = 0;
     g->fnum = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)nblocks);
     g->fbytes = (int32_t *)malloc(sizeof(int32_t) * (size_t)nblocks);
     g->seg_block = (int32_t *)malloc(sizeof(int32_t) * (size_t)nblocks);
     if (!g->fnum || !g->fbytes || !g->seg_block) return -1;
+    if (g->vbs) {
+        g->bframes = (int32_t *)malloc(sizeof(int32_t) * (size_t)nblocks);
+        g->bmax = (int32_t *)malloc(sizeof(int32_t) * (size_t)nblocks);
+        if (!g->bframes || !g->bmax) return -1;
+    }
     g->cap_blocks = nblocks;
     return 0;
 }
@@ -189,12 +209,16 @@ FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples
     if (sample_bytes != 4 && sample_bytes != 2) SET_FAIL("flake_amd_set_encode: sample_bytes must be 4 or 2");
     if (sample_bytes == 2 && g->hp.bits_per_sample > 16)
         SET_FAIL("flake_amd_set_encode: int16 samples need bits_per_sample <= 16");
+    if (sample_bytes == 2 && g->vbs)
+        SET_FAIL("flake_amd_set_encode: int16 samples are not supported with variable block size (levels 9-12)");
     if (block_size < 1 || block_size > g->hp.block_size)
         SET_FAIL("flake_amd_set_encode: block_size out of range (encode.c:987)");
     if (nblocks == 0) return 0;
     /* everything is checked before anything changes: the streams exist, none has ended (encode.c:989), and a
      * short block -- which ends its stream (encode.c:991-992) -- is its stream's only block of the call */
-    const int is_short = block_size != g->hp.block_size;
+    const int is_short = !g->vbs && block_size != g->hp.block_size;       /* (allow_vbs: no latch, encode.c:993) */
+    /* the blocks split_frame_v1 sees (encode.c:997-999); any other length is one frame per block */
+    const int split = g->vbs && (block_size % 8) == 0 && block_size >= 128;
     int *per = g->scratch;
     memset(per, 0, sizeof(int) * (size_t)g->nstreams);
     for (int b = 0; b < nblocks; b++) {
@@ -211,11 +235,11 @@ FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples
         if (rc != FHIP_OK) SET_FAIL("fhip_set_pcm_format: %s (%s)", fhip_strerror(rc), fhip_last_error(g->hip));
         g->pcm_format = fmt;
     }
-    /* frame numbers: each stream counts its own frames (encode.c:969-975) */
+    /* frame numbers: each stream counts its own frames -- its own samples with allow_vbs (encode.c:969-975) */
     memset(per, 0, sizeof(int) * (size_t)g->nstreams);
     for (int b = 0; b < nblocks; b++) {
         const int s = stream_of_block[b];
-        g->fnum[b] = g->frame_count[s] + (uint32_t)per[s]++;
+        g->fnum[b] = g->frame_count[s] + (uint32_t)per[s]++ * (g->vbs ? (uint32_t)block_size : 1u);
     }
     const size_t bstride = (size_t)block_size * (size_t)g->hp.channels * (size_t)sample_bytes;
     long long total = 0;
@@ -244,6 +268,43 @@ FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples
             rc = fhip_md5_update_uploaded(g->hip, g->dev_md5, g->nstreams, cnt, block_size, (const int32_t *)first, g->seg_block);
         }
         int64_t bytes = 0;
+        if (rc == FHIP_OK && split) {
+            /* split, encoded and packed on the device, block b numbered from its stream's sample count; the bytes
+             * come back before the call returns (no download beside the next chunk's upload on this path) */
+            what = "fhip_encode_blocks_vbs_packed_numbered";
+            rc = fhip_encode_blocks_vbs_packed_numbered(g->hip, bt.pcm, cnt, block_size, g->fnum + b0, out + total,
+                                                        (int64_t)(out_size - (size_t)total), g->fbytes + b0,
+                                                        g->bframes + b0, g->bmax + b0, &bytes);
+            if (rc == FHIP_E_VERIFY) {
+                /* the verifier's frame index counts the chunk's FRAMES: the prefix sum of block_frames says which
+                 * block it lies in, the block says which stream */
+                int64_t vs[4] = {0, 0, -1, 0};
+                fhip_verify_rec vr = {0, -1, -1, -1};
+                uint32_t number = 0;
+                (void)fhip_last_verify_failure(g->hip, vs, &vr);
+                const int have_number = fhip_last_verify_number(g->hip, &number) == 1;
+                g->broken = g->dev_md5 != NULL;
+                int blk = -1;
+                long long at = 0;
+                for (int b = 0; b < cnt && blk < 0; b++) {
+                    if (g->bframes[b0 + b] < 1) break;
+                    if (vs[2] >= at && vs[2] < at + g->bframes[b0 + b]) blk = b;
+                    at += g->bframes[b0 + b];
+                }
+                if (vs[2] < 0 || blk < 0) SET_FAIL("%s: %s (%s)", what, fhip_strerror(rc), fhip_last_error(g->hip));
+                const int idx = b0 + blk;
+                g->vfail = 1;
+                g->vfail_stream = stream_of_block[idx];
+                g->vfail_number = have_number ? number : g->fnum[idx];     /* (unplaceable: the block's first sample) */
+                g->vfail_status = vr.status;
+                SET_FAIL("flake_amd_set_encode: verification failed: %lld of the chunk's %lld frames do not decode to the "
+                         "input; first: stream %d, first sample %u (block %d of the call), %s (subframe %d, sample %d, bit %d)",
+                         (long long)vs[1], (long long)vs[0], g->vfail_stream, g->vfail_number, idx,
+                         verify_status_name(vr.status), vr.subframe, vr.sample, vr.bit);
+            }
+            if (rc == FHIP_OK) total += bytes;
+            continue;
+        }
         if (rc == FHIP_OK) { what = "fhip_frames_packed_begin"; rc = fhip_frames_packed_begin(g->hip, &bt, &bytes); }
         if (rc == FHIP_E_VERIFY) {
             /* the verifier's first failing frame is an index into this chunk: name its stream and that stream's frame.
@@ -287,9 +348,10 @@ FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples
     for (int b = 0; b < nblocks; b++) {
         const int s = stream_of_block[b], fs = g->fbytes[b];
         if (frame_sizes) frame_sizes[b] = fs;
-        if (fs > g->max_frame[s]) g->max_frame[s] = fs;                     /* encode.c:967 */
+        const int largest = split ? g->bmax[b] : fs;                        /* of the block's frames */
+        if (largest > g->max_frame[s]) g->max_frame[s] = largest;           /* encode.c:967 */
         if (!g->min_frame[s] || fs < g->min_frame[s]) g->min_frame[s] = fs;
-        g->frame_count[s]++;
+        g->frame_count[s] += g->vbs ? (uint32_t)block_size : 1u;            /* encode.c:969-975 */
         g->samples[s] += (uint64_t)block_size;
         if (is_short) g->ended[s] = 1;
         if (g->host_md5) {
@@ -447,7 +509,7 @@ FLAKE_AMD_API long long flake_amd_set_encode_ragged(FlakeAmdSet *g, const void *
     if (nshort == 0)
         return flake_amd_set_encode(g, samples, sample_bytes, nblocks, full, stream_of_block, out, out_size, frame_sizes);
     const char *er = getenv("FLAKE_AMD_SET_RAGGED");
-    int ragged = !(er && er[0] == '0');
+    int ragged = !(er && er[0] == '0') && !g->vbs;       /* (no ragged kernel path for variable block size) */
     if (ragged && nshort == nblocks) {
         const long long r = set_encode_short(g, samples, sample_bytes, nblocks, block_sizes, stream_of_block, out, out_size, frame_sizes);
         if (r != -2) return r;
@@ -574,7 +636,7 @@ FLAKE_AMD_API int flake_amd_set_get_streaminfo(FlakeAmdSet *g, int stream, Flake
         if (rc != FHIP_OK) SET_FAIL("fhip_md5_final: %s (%s)", fhip_strerror(rc), fhip_last_error(g->hip));
         g->digests_valid = 1;
     }
-    si->min_block_size = (unsigned)g->hp.block_size;
+    si->min_block_size = g->vbs ? 16u : (unsigned)g->hp.block_size;   /* as flake_amd_get_streaminfo reports it */
     si->max_block_size = (unsigned)g->hp.block_size;
     si->min_frame_size = 0;                                       /* as flake_amd_get_streaminfo leaves it */
     si->max_frame_size = (unsigned)g->max_frame[stream];

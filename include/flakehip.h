@@ -305,6 +305,33 @@ typedef struct fhip_vbs_out {
 FHIP_API int fhip_encode_blocks_vbs_dev(fhip_ctx *ctx, const int32_t *pcm, int nblocks, int block_size,
                                         uint32_t first_frame_number, const fhip_vbs_out *out);
 
+/*
+ * fhip_encode_blocks_vbs_packed for blocks of MANY STREAMS (a stream set at levels 9-12): block b belongs to some
+ * stream and its first sample is that stream's sample block_first[b] (HOST table [nblocks]); its frames are numbered
+ * block_first[b] + the frame's offset inside the block, wrapping at 32 bits as the single-stream sum does.  Everything
+ * else -- split_frame_v1 per block, the bins, the frames packed in batch order -- is that entry's, and the bytes of
+ * block b are those it writes for the block at first_frame_number = block_first[b].  block_bytes [nblocks] is
+ * required; block_frames and block_max_frame (block b's largest frame: each stream's own encode.c:967) are optional.
+ * The call consumes a pending fhip_frames_packed_upload of the same pcm / nblocks / block_size, as
+ * fhip_frames_packed_begin does, so that fhip_md5_update_uploaded between the two runs K6 beside the encode kernels.
+ * While fhip_set_verify is on, the stream is verified in the block-table mode (fhip_verify_frames_blocks) before the
+ * call returns: FHIP_E_VERIFY and fhip_last_verify_failure as for the other entries, nothing copied to `out`.
+ * int32 PCM only (FHIP_E_UNSUPPORTED under FHIP_PCM_S16).
+ */
+FHIP_API int fhip_encode_blocks_vbs_packed_numbered(fhip_ctx *ctx, const int32_t *pcm, int nblocks, int block_size,
+                                                    const uint32_t *block_first, uint8_t *out, int64_t out_cap,
+                                                    int32_t *block_bytes, int32_t *block_frames,
+                                                    int32_t *block_max_frame, int64_t *out_bytes);
+/*
+ * Off by default; FHIP_E_UNSUPPORTED on a handle without allow_vbs.  While on, fhip_batch.frame_numbers of
+ * fhip_frames_packed_begin (and fhip_encode_frames_packed) are the first-sample numbers of ONE-FRAME BLOCKS OF
+ * INDEPENDENT STREAMS: K4 writes whatever the table holds, as before, and verification (fhip_set_verify) holds frame
+ * f to frame_numbers[f] in the block-table mode, one frame per block, instead of checking that the numbers run on
+ * from frame_numbers[0].  This is the path for the block lengths variable block size does not split: no multiple
+ * of 8, or below 128 (encode.c:997-999).
+ */
+FHIP_API int fhip_set_block_numbering(fhip_ctx *ctx, int on);
+
 /* Optional hint for a caller that streams batch after batch through one handle
  * (flake.c:622-663 calls flake_encode_frame block after block): start the feeder
  * stage of the NEXT batch -- copy_samples + channel_decorrelation +
@@ -462,6 +489,26 @@ FHIP_API int fhip_verify_frames_ragged(fhip_ctx *ctx, const fhip_verify_in *in, 
                                        const int32_t *block_sizes, const fhip_verify_out *out);
 
 /*
+ * The block-table mode, for a variable-block-size batch whose blocks belong to SEVERAL streams (allow_vbs handles;
+ * FHIP_E_UNSUPPORTED on others): the batch is nblocks blocks of block_size samples (1 .. params.block_size), in->pcm
+ * holds them back to back (in->nsamples = nblocks * block_size), each block is one or more frames, and the first
+ * sample of block b is sample block_first[b] of its stream ([nblocks] uint32: device memory for _dev, host memory for
+ * the other).  The verifier is NOT told how the blocks were split: frame f starts at S_f, the sum of the sizes the
+ * headers of the frames before it carry -- what a sequential decoder has counted when it reaches the frame -- so it
+ * lies in block S_f / block_size at offset S_f % block_size, and must
+ *   carry (uint32)(block_first[blk] + off) in its header                   else FHIP_VERIFY_NUMBER at bit 32
+ *   end inside its block (off + n <= block_size), in a block of the table
+ *   (blk < nblocks), and, the last frame, at in->nsamples                  else FHIP_VERIFY_NUMBER at bit 16
+ * A frame behind one whose header does not parse cannot be placed and fails with FHIP_VERIFY_NUMBER at bit 16 too;
+ * the first failing frame the summary names is still the true first.  in->first_sample is ignored.  Everything else
+ * is as for fhip_verify_frames.  As with the number table, which stream a block belongs to is the caller's statement.
+ */
+FHIP_API int fhip_verify_frames_blocks_dev(fhip_ctx *ctx, const fhip_verify_in *in, const uint32_t *block_first,
+                                           int nblocks, int block_size, const fhip_verify_out *out);
+FHIP_API int fhip_verify_frames_blocks(fhip_ctx *ctx, const fhip_verify_in *in, const uint32_t *block_first,
+                                       int nblocks, int block_size, const fhip_verify_out *out);
+
+/*
  * Verification of the handle's own output, off by default.  While on:
  *   fhip_frames_packed_begin (and fhip_encode_frames_packed) and fhip_encode_blocks_vbs_packed run
  *   the verifier on the device-resident stream and PCM before they return, and return FHIP_E_VERIFY
@@ -470,7 +517,9 @@ FHIP_API int fhip_verify_frames_ragged(fhip_ctx *ctx, const fhip_verify_in *in, 
  *   fails (no host synchronisation).  The bytes written are the same with verification on or off.
  *   A fixed-block batch with fhip_batch.frame_numbers set is verified against that table, frame by frame (the
  *   semantics of fhip_verify_frames_numbered: the frames may belong to many streams, in any order); without a table
- *   the frames must count up from first_frame_number.  A variable-block-size batch is verified in sequence either way.
+ *   the frames must count up from first_frame_number.  A variable-block-size batch is verified in sequence either way,
+ *   unless fhip_set_block_numbering is on (block-table mode, one frame per block); fhip_encode_blocks_vbs_packed_numbered
+ *   is verified in the block-table mode.
  *   fhip_frames_packed_begin_ragged is verified with the semantics of fhip_verify_frames_ragged.
  */
 FHIP_API int fhip_set_verify(fhip_ctx *ctx, int on);
@@ -479,6 +528,12 @@ FHIP_API int fhip_set_verify(fhip_ctx *ctx, int on);
  * in fhip_verify_out, *first = the record of the first failing frame (status OK and -1s when none failed).  Either
  * pointer may be NULL.  Returns 1 when a frame failed, 0 when none did, FHIP_E_INVALID for a null handle. */
 FHIP_API int fhip_last_verify_failure(const fhip_ctx *ctx, int64_t *summary, fhip_verify_rec *first);
+/* The number that first failing frame was REQUIRED to carry, where a table said so: its entry of a frame number table
+ * (the numbered and ragged modes), or block_first[blk] + off in the block-table mode when the frame could be placed
+ * (its header parsed, no frame before it was unplaceable, blk < nblocks).  Returns 1 with *number set (number may be
+ * NULL), 0 when no frame failed or the number is not known, FHIP_E_INVALID for a null handle.  This is what a caller
+ * with many streams needs to name the frame: the frame's index alone does not say where a split block's pieces start. */
+FHIP_API int fhip_last_verify_number(const fhip_ctx *ctx, uint32_t *number);
 
 /* ---- MD5 of many streams (K6) ---------------------------------------- */
 
