@@ -349,30 +349,43 @@ class Encoder:
             return
         self._check(self.lib.fhip_verify_frames_dev(self._h, C.byref(vi), C.byref(vo)), "fhip_verify_frames_dev")
 
-    def verify_frames(self, stream, frame_bytes, pcm, first_sample: int = 0, frame_numbers=None):
-        """K5 on host data.  stream: uint8 bytes, frame_bytes: int32[nframes], pcm: [nsamples][channels]
-        int32.  frame_numbers: uint32[nframes], the number each frame must carry (fhip_verify_frames_numbered).
-        Returns (ok, records as a VERIFY_REC_DTYPE array, summary int64[4], error text)."""
+    def _verify_host(self, what: str, args, stream, frame_bytes, pcm, first_sample: int = 0, pcm_dtype=None):
+        """One host verify entry: lib.<what>(handle, VerifyIn, *args, VerifyOut) on host arrays, its rc mapped to
+        (ok, records as a VERIFY_REC_DTYPE array, summary int64[4], error text)."""
         st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
                                   else stream, dtype=np.uint8)
         fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
-        pc = np.ascontiguousarray(pcm, dtype=self.pcm_dtype).reshape(-1, self.params.channels)
+        pc = np.ascontiguousarray(pcm, dtype=pcm_dtype or self.pcm_dtype).reshape(-1, self.params.channels)
         recs = np.zeros(len(fb), dtype=VERIFY_REC_DTYPE)
         summary = np.zeros(4, dtype=np.int64)
         vi = VerifyIn(st.ctypes.data if st.size else None, st.size, fb.ctypes.data if fb.size else None, len(fb),
                       pc.ctypes.data if pc.size else None, pc.shape[0], first_sample)
         vo = VerifyOut(recs.ctypes.data if len(fb) else None, summary.ctypes.data)
-        if frame_numbers is not None:
-            fn = np.ascontiguousarray(frame_numbers, dtype=np.uint32)
-            if len(fn) != len(fb):
-                raise ValueError("frame_numbers needs one entry per frame")
-            rc, what = self.lib.fhip_verify_frames_numbered(self._h, C.byref(vi), fn.ctypes.data if fn.size else None,
-                                                            C.byref(vo)), "fhip_verify_frames_numbered"
-        else:
-            rc, what = self.lib.fhip_verify_frames(self._h, C.byref(vi), C.byref(vo)), "fhip_verify_frames"
+        rc = getattr(self.lib, what)(self._h, C.byref(vi), *args, C.byref(vo))
         if rc not in (OK, E_VERIFY):
             self._check(rc, what)
         return rc == OK, recs, summary, self.lib.fhip_last_error(self._h).decode() if rc else ""
+
+    def verify_frames(self, stream, frame_bytes, pcm, first_sample: int = 0, frame_numbers=None):
+        """K5 on host data.  stream: uint8 bytes, frame_bytes: int32[nframes], pcm: [nsamples][channels]
+        int32.  frame_numbers: uint32[nframes], the number each frame must carry (fhip_verify_frames_numbered).
+        Returns (ok, records as a VERIFY_REC_DTYPE array, summary int64[4], error text)."""
+        if frame_numbers is None:
+            return self._verify_host("fhip_verify_frames", (), stream, frame_bytes, pcm, first_sample)
+        fn = np.ascontiguousarray(frame_numbers, dtype=np.uint32)
+        if len(fn) != len(frame_bytes):
+            raise ValueError("frame_numbers needs one entry per frame")
+        return self._verify_host("fhip_verify_frames_numbered", (fn.ctypes.data if fn.size else None,), stream,
+                                 frame_bytes, pcm, first_sample)
+
+    def verify_frames_ragged(self, stream, frame_bytes, pcm, frame_numbers, block_sizes):
+        """fhip_verify_frames_ragged on host data: frame f carries frame_numbers[f] and holds block_sizes[f] samples,
+        the blocks back to back in pcm.  Returns what verify_frames returns."""
+        fn = np.ascontiguousarray(frame_numbers, dtype=np.uint32)
+        sz = np.ascontiguousarray(block_sizes, dtype=np.int32)
+        if len(fn) != len(frame_bytes) or len(sz) != len(frame_bytes):
+            raise ValueError("frame_numbers and block_sizes need one entry per frame")
+        return self._verify_host("fhip_verify_frames_ragged", (fn.ctypes.data, sz.ctypes.data), stream, frame_bytes, pcm)
 
     # -- variable block size for blocks of many streams (the stream set's path at levels 9-12) ------------
     def set_block_numbering(self, on: bool) -> None:
@@ -403,24 +416,12 @@ class Encoder:
         """K5's block-table mode on host data (fhip_verify_frames_blocks): pcm holds nblocks blocks of block_size
         samples, block b starts at sample block_first[b] of its stream.  nblocks defaults to len(block_first).
         Returns (ok, records, summary int64[4], error text) as verify_frames does."""
-        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
-                                  else stream, dtype=np.uint8)
-        fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
-        pc = np.ascontiguousarray(pcm, dtype=np.int32).reshape(-1, self.params.channels)
         bf = np.ascontiguousarray(block_first, dtype=np.uint32)
         nb = len(bf) if nblocks is None else int(nblocks)
         if nb > len(bf):
             raise ValueError("block_first is shorter than nblocks")
-        recs = np.zeros(len(fb), dtype=VERIFY_REC_DTYPE)
-        summary = np.zeros(4, dtype=np.int64)
-        vi = VerifyIn(st.ctypes.data if st.size else None, st.size, fb.ctypes.data if fb.size else None, len(fb),
-                      pc.ctypes.data if pc.size else None, pc.shape[0], 0)
-        vo = VerifyOut(recs.ctypes.data if len(fb) else None, summary.ctypes.data)
-        rc = self.lib.fhip_verify_frames_blocks(self._h, C.byref(vi), bf.ctypes.data if bf.size else None, nb,
-                                                block_size, C.byref(vo))
-        if rc not in (OK, E_VERIFY):
-            self._check(rc, "fhip_verify_frames_blocks")
-        return rc == OK, recs, summary, self.lib.fhip_last_error(self._h).decode() if rc else ""
+        return self._verify_host("fhip_verify_frames_blocks", (bf.ctypes.data if bf.size else None, nb, block_size),
+                                 stream, frame_bytes, pcm, pcm_dtype=np.int32)
 
     def verify_frames_blocks_dev(self, stream, stream_bytes: int, frame_bytes, nframes: int, pcm, nsamples: int,
                                  block_first, nblocks: int, block_size: int, summary, records=None) -> None:

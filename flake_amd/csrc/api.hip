@@ -467,30 +467,55 @@ int ensure_verify(fhip_ctx *c, size_t nframes)
     return FHIP_OK;
 }
 
-// Queue K5 on the handle's stream.  block_size: the numbering unit of a fixed-block stream (the batch's block
-// size for the handle's own batches; params.block_size for a caller's stream).  recs null: the handle's own.
-// numbers (device, [nframes]; fixed-block handles only): the number each frame must carry, when the batch's
-// frames belong to several streams -- first_sample is unused then.  Null: numbered by position, as a single stream.
-// block_first (device, [nblocks]; allow_vbs handles only): the block-table mode of a variable-block-size batch.
-int run_verify(fhip_ctx *c, const uint8_t *stream, long long stream_bytes, const int32_t *frame_bytes, int nframes,
-               const long long *dev_count, const int32_t *pcm, long long nsamples, long long first_sample,
-               int block_size, fhip_verify_rec *recs, int64_t *summary, long long *totals, const uint32_t *numbers,
-               const int32_t *frame_n = nullptr, const long long *frame_src = nullptr,
-               const uint32_t *block_first = nullptr, int nblocks = 0)
+// One verification, its fields named where the call is made: what K5 reads and writes (device memory) and which of its
+// four modes holds the frames to their numbers.  run_verify queues it; verify_verdict reads the same job after the sync.
+struct VerifyJob {
+    fhip_verify_in in{};                     // the stream, its bytes, the frame sizes and count, the PCM, its samples
+    const long long *dev_count = nullptr;    // optional: the real frame count lives on the device (in.nframes: the grid)
+    int block_size = 0;                      // the numbering unit: the batch's block size, or the caller's stream's
+    fhip_verify_out out{};                   // optional records and summary; null: the handle's own d_vrec, d_vsum
+    long long *totals = nullptr;             // optional: fhip_encode_blocks_vbs_dev's totals
+    // SEQUENCE: one stream, its first frame at in.first_sample.  NUMBERS (fixed-block handles): frames of many streams,
+    // frame f carries numbers[f]; RAGGED: ... and holds frame_n[f] samples, found at frame_src[f] of the PCM.  BLOCKS
+    // (allow_vbs handles): nblocks blocks of block_size samples, one or more frames each; a frame at offset `off` of
+    // block b carries block_first[b] + off.  A table of another mode is not read.
+    enum Mode { SEQUENCE, NUMBERS, RAGGED, BLOCKS } mode = SEQUENCE;
+    const uint32_t *numbers = nullptr;
+    const int32_t *frame_n = nullptr; const long long *frame_src = nullptr;
+    const uint32_t *block_first = nullptr; int nblocks = 0;
+    // HOST copies for the verdict's text and fhip_last_verify_number, optional: the number frame f must carry (where
+    // each block of a BLOCKS job is one frame too), or block_first: the number follows from where K5 placed the frame
+    const uint32_t *host_numbers = nullptr, *host_block_first = nullptr;
+    long long sum[4] = {0, 0, -1, 0};        // HOST: the summary, once verify_batch's copy has come (the caller's sync)
+};
+
+// Queue K5 on the handle's stream: the one place a job becomes fhip::VerifyArgs.
+int run_verify(fhip_ctx *c, const VerifyJob &j)
 {
-    int rc = ensure_verify(c, (size_t)nframes);
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_verify(c, (size_t)j.in.nframes);
     if (rc != FHIP_OK) return rc;
     const fhip_params &p = c->p;
-    fhip::VerifyArgs a{stream, stream_bytes, frame_bytes, nframes, dev_count, pcm, nsamples, first_sample,
-                       p.channels, p.bits_per_sample, block_size, p.sample_rate, p.allow_vbs ? 1 : 0, c->pcm_format,
-                       c->d_vws, recs ? recs : c->d_vrec, summary ? reinterpret_cast<long long *>(summary) : c->d_vsum,
-                       reinterpret_cast<unsigned long long *>(c->d_vsum + 4), totals, numbers};
-    a.frame_n = frame_n;              // the ragged numbered mode: both tables or neither
-    a.frame_src = frame_src;
-    a.block_first = block_first;      // the block-table mode (allow_vbs handles): nblocks blocks of block_size samples
-    a.nblocks = nblocks;
+    fhip::VerifyArgs a{j.in.stream, j.in.stream_bytes, j.in.frame_bytes, j.in.nframes, j.dev_count, j.in.pcm,
+                       j.in.nsamples, j.mode == VerifyJob::SEQUENCE ? j.in.first_sample : 0, p.channels,
+                       p.bits_per_sample, j.block_size, p.sample_rate, p.allow_vbs ? 1 : 0, c->pcm_format, c->d_vws,
+                       j.out.frames ? j.out.frames : c->d_vrec,
+                       j.out.summary ? reinterpret_cast<long long *>(j.out.summary) : c->d_vsum,
+                       reinterpret_cast<unsigned long long *>(c->d_vsum + 4), j.totals, nullptr};
+    if (j.mode == VerifyJob::NUMBERS || j.mode == VerifyJob::RAGGED) a.numbers = j.numbers;
+    if (j.mode == VerifyJob::RAGGED) { a.frame_n = j.frame_n; a.frame_src = j.frame_src; }
+    if (j.mode == VerifyJob::BLOCKS) { a.block_first = j.block_first; a.nblocks = j.nblocks; }
     Prof pr(c, kProfVerify, c->profiling);
     HIP_TRY(c, fhip::launch_verify(c->stream, a));
+    return FHIP_OK;
+}
+
+// Queue K5 and start the copy of the handle's summary into the job, which lives until verify_verdict has read it.
+int verify_batch(fhip_ctx *c, VerifyJob &j)
+{
+    int rc = run_verify(c, j);
+    if (rc != FHIP_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(j.sum, c->d_vsum, sizeof j.sum, hipMemcpyDeviceToHost, c->stream));
     return FHIP_OK;
 }
 
@@ -501,15 +526,14 @@ const char *verify_status_name(int s)
     return (s >= 0 && s <= 8) ? names[s] : "?";
 }
 
-// After the stream synchronised: summary (host copy) -> FHIP_OK, or FHIP_E_VERIFY with the first failing frame
-// named in the handle's error text (its record read from recs, device).  numbers (HOST, optional): the table of a
-// numbered batch; the text then also says which number that frame had to carry.
-// block_first (HOST, optional, [nblocks] blocks of block_size samples): the table of a block-table batch; the number
-// then follows from where K5 placed the frame (its VerifyFrame), when it could be placed.
-int verify_verdict(fhip_ctx *c, const long long *summary, const fhip_verify_rec *recs,
-                   const uint32_t *numbers = nullptr, const uint32_t *block_first = nullptr, int nblocks = 0,
-                   int block_size = 0)
+// After the stream synchronised: the job's summary -> FHIP_OK, or FHIP_E_VERIFY with the first failing frame named
+// in the handle's error text (its record read from the job's records).  With the job's host_numbers the text also
+// says which number that frame had to carry; with its host_block_first the number follows from where K5 placed the
+// frame (its VerifyFrame), when it could be placed.
+int verify_verdict(fhip_ctx *c, const VerifyJob &j)
 {
+    const long long *summary = j.sum;
+    const fhip_verify_rec *recs = j.out.frames ? j.out.frames : c->d_vrec.get();
     for (int i = 0; i < 4; i++) c->vfail_sum[i] = summary[i];
     c->vfail_rec = fhip_verify_rec{(int32_t)summary[3], -1, -1, -1};
     c->vfail_has_number = false;
@@ -518,20 +542,20 @@ int verify_verdict(fhip_ctx *c, const long long *summary, const fhip_verify_rec 
     if (recs && summary[2] >= 0)
         HIP_TRY(c, hipMemcpy(&r, recs + summary[2], sizeof r, hipMemcpyDeviceToHost));
     c->vfail_rec = r;
-    if (numbers && summary[2] >= 0) {
+    if (j.host_numbers && summary[2] >= 0) {
         c->vfail_has_number = true;
-        c->vfail_number = numbers[summary[2]];
-    } else if (block_first && block_size > 0 && summary[2] >= 0) {
+        c->vfail_number = j.host_numbers[summary[2]];
+    } else if (j.host_block_first && j.block_size > 0 && summary[2] >= 0) {
         fhip::VerifyFrame vf{};
         HIP_TRY(c, hipMemcpy(&vf, c->d_vws + summary[2], sizeof vf, hipMemcpyDeviceToHost));
         // K5's header pass left its own status there: OK / CRC8 (placed, numbered right) or NUMBER at bit 32 (placed,
         // numbered wrong) say that rel_start is where the frame lies; anything else was never placed
-        const long long blk = vf.rel_start / block_size;
+        const long long blk = vf.rel_start / j.block_size;
         const bool placed = vf.status == FHIP_VERIFY_OK || vf.status == FHIP_VERIFY_CRC8 ||
                             (vf.status == FHIP_VERIFY_NUMBER && vf.bit == 32);
-        if (placed && vf.rel_start >= 0 && blk < nblocks) {
+        if (placed && vf.rel_start >= 0 && blk < j.nblocks) {
             c->vfail_has_number = true;
-            c->vfail_number = block_first[blk] + (uint32_t)(vf.rel_start - blk * block_size);
+            c->vfail_number = j.host_block_first[blk] + (uint32_t)(vf.rel_start - blk * j.block_size);
         }
     }
     char want[48] = "";
@@ -544,6 +568,41 @@ int verify_verdict(fhip_ctx *c, const long long *summary, const fhip_verify_rec 
              r.bit);
     c->err = buf;
     return FHIP_E_VERIFY;
+}
+
+// The host entries' body, behind their own checks.  The job arrives with HOST memory in j.in and with its mode,
+// numbering unit and host tables set: the stream, the sizes and the PCM are uploaded, and so is `table` (HOST, read
+// until the sync, table_count 4-byte entries: the mode's table; the ragged mode's three as one -- numbers, lengths from
+// the even-rounded count on, 8-byte offsets from twice that).  K5 runs, `out` is filled, the verdict is returned.
+int verify_host(fhip_ctx *c, VerifyJob j, const uint32_t *table, size_t table_count, const fhip_verify_out *out)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    const fhip_verify_in in = j.in;
+    const size_t sb = (size_t)in.stream_bytes, nf = (size_t)in.nframes;
+    const size_t nv = (size_t)in.nsamples * (size_t)c->p.channels;
+    HIP_TRY(c, c->d_vstream.reserve(sb));
+    HIP_TRY(c, c->d_vfb.reserve(nf));
+    HIP_TRY(c, c->d_vpcm.reserve(nv));
+    HIP_TRY(c, c->d_vnum.reserve(table_count));
+    if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_vstream, in.stream, sb, hipMemcpyHostToDevice, c->stream));
+    if (nf) HIP_TRY(c, hipMemcpyAsync(c->d_vfb, in.frame_bytes, nf * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (nv) HIP_TRY(c, hipMemcpyAsync(c->d_vpcm, in.pcm, nv * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
+    if (table_count) HIP_TRY(c, hipMemcpyAsync(c->d_vnum, table, table_count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    j.in.stream = c->d_vstream; j.in.frame_bytes = c->d_vfb; j.in.pcm = c->d_vpcm;
+    j.numbers = j.block_first = c->d_vnum;          // (whichever the mode reads)
+    if (j.mode == VerifyJob::RAGGED) {
+        const size_t nf2 = (nf + 1) & ~(size_t)1;
+        j.frame_n = reinterpret_cast<const int32_t *>(c->d_vnum.get() + nf2);
+        j.frame_src = reinterpret_cast<const long long *>(c->d_vnum.get() + 2 * nf2);
+    }
+    int rc = verify_batch(c, j);
+    if (rc != FHIP_OK) return rc;
+    if (out->frames && nf)
+        HIP_TRY(c, hipMemcpyAsync(out->frames, c->d_vrec, nf * sizeof(fhip_verify_rec), hipMemcpyDeviceToHost, c->stream));
+    rc = fhip_sync(c);
+    if (rc != FHIP_OK) return rc;
+    for (int i = 0; i < 4; i++) out->summary[i] = j.sum[i];
+    return verify_verdict(c, j);
 }
 
 // Every entry that writes the staging PCM goes through here: what fhip_frames_packed_upload left there is gone
@@ -1167,22 +1226,24 @@ int fhip_frames_packed_begin(fhip_ctx *c, const fhip_batch *b, int64_t *total_by
     if (rc != FHIP_OK) return rc;
     HIP_TRY(c, fhip::launch_pack_frames(c->stream, c->d_frames, stride, c->d_fbytes, b->nframes,
                                         c->d_offsets, c->d_packed));
-    long long vsum[4] = {0, 0, -1, 0};
-    // an explicit number table on a fixed-block handle: the frames may be of many streams, each is held to its own
-    // entry (the table is on the device already); a variable-block-size batch numbers samples and stays in sequence
-    const bool numbered = b->frame_numbers && !c->p.allow_vbs;
-    // ... unless the caller has said that the table names one-frame blocks of independent streams (fhip_set_block_numbering)
-    const bool blocks = b->frame_numbers && c->p.allow_vbs && c->block_numbering;
-    if (c->verify) {
+    VerifyJob vj;
+    vj.in.stream = c->d_packed; vj.in.stream_bytes = (int64_t)fb;
+    vj.in.frame_bytes = c->d_fbytes; vj.in.nframes = b->nframes;
+    vj.in.pcm = c->d_pcm; vj.in.nsamples = (int64_t)b->nframes * b->block_size; vj.block_size = b->block_size;
+    if (b->frame_numbers && !c->p.allow_vbs) {
+        // a table on a fixed-block handle: frames of many streams, each held to its own entry (on the device already)
+        vj.mode = VerifyJob::NUMBERS; vj.numbers = c->d_fnum; vj.host_numbers = b->frame_numbers;
+    } else if (b->frame_numbers && c->block_numbering) {
+        // an allow_vbs handle told that the table names one-frame blocks of many streams (fhip_set_block_numbering)
+        vj.mode = VerifyJob::BLOCKS;
+        vj.block_first = c->d_fnum; vj.nblocks = b->nframes; vj.host_numbers = b->frame_numbers;
+    } else {
+        // no table, or a variable-block-size batch: it numbers samples and stays in sequence
         const long long num0 = b->frame_numbers ? (long long)b->frame_numbers[0] : (long long)b->first_frame_number;
-        const long long first = c->p.allow_vbs ? num0 : num0 * (long long)b->block_size;
-        rc = run_verify(c, c->d_packed, (long long)fb, c->d_fbytes, b->nframes, nullptr, c->d_pcm,
-                        (long long)b->nframes * b->block_size, numbered ? 0 : first, b->block_size, nullptr, nullptr,
-                        nullptr, numbered ? (const uint32_t *)c->d_fnum : nullptr, nullptr, nullptr,
-                        blocks ? (const uint32_t *)c->d_fnum : nullptr, blocks ? b->nframes : 0);
-        if (rc != FHIP_OK) return rc;
-        HIP_TRY(c, hipMemcpyAsync(vsum, c->d_vsum, sizeof vsum, hipMemcpyDeviceToHost, c->stream));
+        vj.in.first_sample = c->p.allow_vbs ? num0 : num0 * (long long)b->block_size;
     }
+    if (c->verify) rc = verify_batch(c, vj);
+    if (rc != FHIP_OK) return rc;
     long long total = 0;
     HIP_TRY(c, hipMemcpyAsync(b->frame_bytes, c->d_fbytes, (size_t)b->nframes * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(&total, c->d_offsets + b->nframes, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
@@ -1192,7 +1253,7 @@ int fhip_frames_packed_begin(fhip_ctx *c, const fhip_batch *b, int64_t *total_by
     if (rc != FHIP_OK) return rc;
     c->packed_ready = total;
     *total_bytes = total;
-    return c->verify ? verify_verdict(c, vsum, c->d_vrec, (numbered || blocks) ? b->frame_numbers : nullptr) : FHIP_OK;
+    return c->verify ? verify_verdict(c, vj) : FHIP_OK;
 }
 
 int fhip_frames_packed_fetch(fhip_ctx *c, uint8_t *out, int64_t out_cap)
@@ -1369,13 +1430,14 @@ int fhip_frames_packed_begin_ragged(fhip_ctx *c, const fhip_batch *b, const int3
     if (rc != FHIP_OK) return rc;
     HIP_TRY(c, fhip::launch_pack_frames(c->stream, c->d_frames, stride, c->d_fbytes, b->nframes,
                                         c->d_offsets, c->d_packed));
-    long long vsum[4] = {0, 0, -1, 0};
-    if (c->verify) {
-        rc = run_verify(c, c->d_packed, (long long)fb, c->d_fbytes, b->nframes, nullptr, c->d_pcm, total_n, 0,
-                        c->p.block_size, nullptr, nullptr, nullptr, c->d_fnum, c->rg_n(), c->rg_src());
-        if (rc != FHIP_OK) return rc;
-        HIP_TRY(c, hipMemcpyAsync(vsum, c->d_vsum, sizeof vsum, hipMemcpyDeviceToHost, c->stream));
-    }
+    VerifyJob vj;
+    vj.in.stream = c->d_packed; vj.in.stream_bytes = (int64_t)fb;
+    vj.in.frame_bytes = c->d_fbytes; vj.in.nframes = b->nframes;
+    vj.in.pcm = c->d_pcm; vj.in.nsamples = total_n; vj.block_size = c->p.block_size;
+    vj.mode = VerifyJob::RAGGED; vj.host_numbers = c->h_rgnum.data();
+    vj.numbers = c->d_fnum; vj.frame_n = c->rg_n(); vj.frame_src = c->rg_src();
+    if (c->verify) rc = verify_batch(c, vj);
+    if (rc != FHIP_OK) return rc;
     long long total = 0;
     HIP_TRY(c, hipMemcpyAsync(b->frame_bytes, c->d_fbytes, (size_t)b->nframes * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(&total, c->d_offsets + b->nframes, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
@@ -1385,7 +1447,7 @@ int fhip_frames_packed_begin_ragged(fhip_ctx *c, const fhip_batch *b, const int3
     if (rc != FHIP_OK) return rc;
     c->packed_ready = total;
     *total_bytes = total;
-    return c->verify ? verify_verdict(c, vsum, c->d_vrec, c->h_rgnum.data()) : FHIP_OK;
+    return c->verify ? verify_verdict(c, vj) : FHIP_OK;
 }
 
 // ---- K6: the MD5 of many streams ----------------------------------------------------------------
@@ -1922,9 +1984,12 @@ int fhip_encode_blocks_vbs_dev(fhip_ctx *c, const int32_t *pcm, int nblocks, int
                              totals});
     if (rc != FHIP_OK || !c->verify) return rc;
     // totals[3] bit 2 when a frame fails; still no host synchronisation
-    return run_verify(c, out->packed, (long long)out->packed_cap, fbytes, 8 * nblocks, totals, pcm,
-                      (long long)nblocks * block_size, first_frame_number, block_size, nullptr, nullptr, totals,
-                      nullptr);
+    VerifyJob vj;
+    vj.in.stream = out->packed; vj.in.stream_bytes = out->packed_cap;
+    vj.in.frame_bytes = fbytes; vj.in.nframes = 8 * nblocks; vj.dev_count = totals;
+    vj.in.pcm = pcm; vj.in.nsamples = (int64_t)nblocks * block_size;
+    vj.in.first_sample = first_frame_number; vj.block_size = block_size; vj.totals = totals;
+    return run_verify(c, vj);
 }
 
 namespace {
@@ -1984,14 +2049,17 @@ int vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, int block_size, uin
     }
     rc = vbs_dev_core(c, c->d_pcm, nblocks, block_size, first_frame_number, vo);
     if (rc != FHIP_OK) return rc;
-    long long vsum[4] = {0, 0, -1, 0};
-    if (c->verify) {
-        rc = run_verify(c, c->d_packed, (long long)c->d_packed.cap, c->d_stream_bytes, 8 * nblocks, c->d_totals,
-                        c->d_pcm, (long long)nblocks * block_size, block_first ? 0 : first_frame_number, block_size,
-                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, vo.block_first, nblocks);
-        if (rc != FHIP_OK) return rc;
-        HIP_TRY(c, hipMemcpyAsync(vsum, c->d_vsum, sizeof vsum, hipMemcpyDeviceToHost, c->stream));
+    VerifyJob vj;
+    vj.in.stream = c->d_packed; vj.in.stream_bytes = (int64_t)c->d_packed.cap;
+    vj.in.frame_bytes = c->d_stream_bytes; vj.in.nframes = 8 * nblocks; vj.dev_count = c->d_totals;
+    vj.in.pcm = c->d_pcm; vj.in.nsamples = (int64_t)nblocks * block_size;
+    vj.in.first_sample = first_frame_number; vj.block_size = block_size;
+    if (block_first) {
+        vj.mode = VerifyJob::BLOCKS;
+        vj.block_first = vo.block_first; vj.nblocks = nblocks; vj.host_block_first = block_first;
     }
+    if (c->verify) rc = verify_batch(c, vj);
+    if (rc != FHIP_OK) return rc;
     long long totals[4] = {0, 0, 0, 0};
     HIP_TRY(c, hipMemcpyAsync(totals, c->d_totals, sizeof totals, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(block_bytes, c->d_blk_bytes, (size_t)nblocks * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -2007,7 +2075,7 @@ int vbs_packed(fhip_ctx *c, const int32_t *pcm, int nblocks, int block_size, uin
     for (int b = 0; b < nblocks; b++)
         if (block_bytes[b] <= 0) return fail(c, FHIP_E_GENERIC, "a frame of the batch was not encoded");
     if (c->verify) {
-        rc = verify_verdict(c, vsum, c->d_vrec, nullptr, block_first, nblocks, block_size);
+        rc = verify_verdict(c, vj);
         if (rc != FHIP_OK) return rc;
     }
     if (totals[1] > out_cap) return fail(c, FHIP_E_INVALID, "output buffer too small for the batch's frames");
@@ -2080,10 +2148,10 @@ int fhip_verify_frames_numbered_dev(fhip_ctx *c, const fhip_verify_in *in, const
 {
     int rc = verify_check(c, in, out, frame_numbers != nullptr);
     if (rc != FHIP_OK) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    return run_verify(c, in->stream, in->stream_bytes, in->frame_bytes, in->nframes, nullptr, in->pcm, in->nsamples,
-                      frame_numbers ? 0 : in->first_sample, c->p.block_size, out->frames, out->summary, nullptr,
-                      frame_numbers);
+    VerifyJob j;
+    j.in = *in; j.out = *out; j.block_size = c->p.block_size;
+    if (frame_numbers) { j.mode = VerifyJob::NUMBERS; j.numbers = frame_numbers; }
+    return run_verify(c, j);
 }
 
 int fhip_verify_frames_dev(fhip_ctx *c, const fhip_verify_in *in, const fhip_verify_out *out)
@@ -2096,30 +2164,10 @@ int fhip_verify_frames_numbered(fhip_ctx *c, const fhip_verify_in *in, const uin
 {
     int rc = verify_check(c, in, out, frame_numbers != nullptr);
     if (rc != FHIP_OK) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t sb = (size_t)in->stream_bytes, nf = (size_t)in->nframes;
-    const size_t nv = (size_t)in->nsamples * (size_t)c->p.channels;
-    const bool numbered = frame_numbers && nf;
-    HIP_TRY(c, c->d_vstream.reserve(sb));
-    HIP_TRY(c, c->d_vfb.reserve(nf));
-    HIP_TRY(c, c->d_vpcm.reserve(nv));
-    if (numbered) HIP_TRY(c, c->d_vnum.reserve(nf));
-    if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_vstream, in->stream, sb, hipMemcpyHostToDevice, c->stream));
-    if (nf) HIP_TRY(c, hipMemcpyAsync(c->d_vfb, in->frame_bytes, nf * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    if (nv) HIP_TRY(c, hipMemcpyAsync(c->d_vpcm, in->pcm, nv * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
-    if (numbered) HIP_TRY(c, hipMemcpyAsync(c->d_vnum, frame_numbers, nf * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    rc = run_verify(c, c->d_vstream, in->stream_bytes, c->d_vfb, in->nframes, nullptr, c->d_vpcm, in->nsamples,
-                    numbered ? 0 : in->first_sample, c->p.block_size, nullptr, nullptr, nullptr,
-                    numbered ? (const uint32_t *)c->d_vnum : nullptr);
-    if (rc != FHIP_OK) return rc;
-    long long sum[4] = {0, 0, -1, 0};
-    HIP_TRY(c, hipMemcpyAsync(sum, c->d_vsum, sizeof sum, hipMemcpyDeviceToHost, c->stream));
-    if (out->frames && nf)
-        HIP_TRY(c, hipMemcpyAsync(out->frames, c->d_vrec, nf * sizeof(fhip_verify_rec), hipMemcpyDeviceToHost, c->stream));
-    rc = fhip_sync(c);
-    if (rc != FHIP_OK) return rc;
-    for (int i = 0; i < 4; i++) out->summary[i] = sum[i];
-    return verify_verdict(c, sum, c->d_vrec, numbered ? frame_numbers : nullptr);
+    VerifyJob j;                                // (a table without frames: the sequence mode's empty launch)
+    j.in = *in; j.block_size = c->p.block_size;
+    if (frame_numbers && in->nframes) { j.mode = VerifyJob::NUMBERS; j.host_numbers = frame_numbers; }
+    return verify_host(c, j, frame_numbers, j.mode == VerifyJob::NUMBERS ? (size_t)in->nframes : 0, out);
 }
 
 int fhip_verify_frames(fhip_ctx *c, const fhip_verify_in *in, const fhip_verify_out *out)
@@ -2133,10 +2181,10 @@ int fhip_verify_frames_ragged_dev(fhip_ctx *c, const fhip_verify_in *in, const u
     int rc = verify_check(c, in, out, true);
     if (rc != FHIP_OK) return rc;
     if (!frame_numbers || !block_sizes || !frame_src) return fail(c, FHIP_E_INVALID, "null argument");
-    HIP_TRY(c, hipSetDevice(c->device));
-    return run_verify(c, in->stream, in->stream_bytes, in->frame_bytes, in->nframes, nullptr, in->pcm, in->nsamples, 0,
-                      c->p.block_size, out->frames, out->summary, nullptr, frame_numbers, block_sizes,
-                      reinterpret_cast<const long long *>(frame_src));
+    VerifyJob j;
+    j.in = *in; j.out = *out; j.block_size = c->p.block_size; j.mode = VerifyJob::RAGGED;
+    j.numbers = frame_numbers; j.frame_n = block_sizes; j.frame_src = reinterpret_cast<const long long *>(frame_src);
+    return run_verify(c, j);
 }
 
 int fhip_verify_frames_ragged(fhip_ctx *c, const fhip_verify_in *in, const uint32_t *frame_numbers,
@@ -2152,9 +2200,7 @@ int fhip_verify_frames_ragged(fhip_ctx *c, const fhip_verify_in *in, const uint3
         total += block_sizes[f];
     }
     if (total != in->nsamples) return fail(c, FHIP_E_INVALID, "nsamples must be the sum of block_sizes");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t sb = (size_t)in->stream_bytes, nf = (size_t)in->nframes;
-    const size_t nv = (size_t)in->nsamples * (size_t)c->p.channels;
+    const size_t nf = (size_t)in->nframes;
     if (nf == 0) return fhip_verify_frames_numbered(c, in, frame_numbers, out);
     // the tables: numbers, lengths, then the offsets (8-byte aligned behind an even count of 4-byte entries)
     const size_t nf2 = (nf + 1) & ~(size_t)1;
@@ -2166,27 +2212,9 @@ int fhip_verify_frames_ragged(fhip_ctx *c, const fhip_verify_in *in, const uint3
         memcpy(&tab[2 * nf2 + 2 * f], &at, sizeof at);
         at += (long long)block_sizes[f] * c->p.channels;
     }
-    HIP_TRY(c, c->d_vstream.reserve(sb));
-    HIP_TRY(c, c->d_vfb.reserve(nf));
-    HIP_TRY(c, c->d_vpcm.reserve(nv));
-    HIP_TRY(c, c->d_vnum.reserve(tab.size()));
-    if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_vstream, in->stream, sb, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_vfb, in->frame_bytes, nf * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    if (nv) HIP_TRY(c, hipMemcpyAsync(c->d_vpcm, in->pcm, nv * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_vnum, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    rc = run_verify(c, c->d_vstream, in->stream_bytes, c->d_vfb, in->nframes, nullptr, c->d_vpcm, in->nsamples, 0,
-                    c->p.block_size, nullptr, nullptr, nullptr, c->d_vnum,
-                    reinterpret_cast<const int32_t *>(c->d_vnum.get() + nf2),
-                    reinterpret_cast<const long long *>(c->d_vnum.get() + 2 * nf2));
-    if (rc != FHIP_OK) return rc;
-    long long sum[4] = {0, 0, -1, 0};
-    HIP_TRY(c, hipMemcpyAsync(sum, c->d_vsum, sizeof sum, hipMemcpyDeviceToHost, c->stream));
-    if (out->frames)
-        HIP_TRY(c, hipMemcpyAsync(out->frames, c->d_vrec, nf * sizeof(fhip_verify_rec), hipMemcpyDeviceToHost, c->stream));
-    rc = fhip_sync(c);          // (tab is read by the copy above: it lives until here)
-    if (rc != FHIP_OK) return rc;
-    for (int i = 0; i < 4; i++) out->summary[i] = sum[i];
-    return verify_verdict(c, sum, c->d_vrec, frame_numbers);
+    VerifyJob j;
+    j.in = *in; j.block_size = c->p.block_size; j.mode = VerifyJob::RAGGED; j.host_numbers = frame_numbers;
+    return verify_host(c, j, tab.data(), tab.size(), out);      // (tab lives until its sync)
 }
 
 namespace {
@@ -2200,6 +2228,7 @@ int verify_blocks_check(fhip_ctx *c, const fhip_verify_in *in, const uint32_t *b
                                            "sample); a fixed-block batch takes a frame number table");
     if (nblocks < 0 || (nblocks > 0 && !block_first)) return fail(c, FHIP_E_INVALID, "null block table or negative count");
     if (block_size < 1 || block_size > c->p.block_size) return fail(c, FHIP_E_INVALID, "block_size out of range (encode.c:987)");
+    if (nblocks == 0 && in->nframes > 0) return fail(c, FHIP_E_INVALID, "frames without blocks");
     return FHIP_OK;
 }
 }  // namespace
@@ -2209,10 +2238,10 @@ int fhip_verify_frames_blocks_dev(fhip_ctx *c, const fhip_verify_in *in, const u
 {
     int rc = verify_blocks_check(c, in, block_first, nblocks, block_size, out);
     if (rc != FHIP_OK) return rc;
-    if (nblocks == 0 && in->nframes > 0) return fail(c, FHIP_E_INVALID, "frames without blocks");
-    HIP_TRY(c, hipSetDevice(c->device));
-    return run_verify(c, in->stream, in->stream_bytes, in->frame_bytes, in->nframes, nullptr, in->pcm, in->nsamples, 0,
-                      block_size, out->frames, out->summary, nullptr, nullptr, nullptr, nullptr, block_first, nblocks);
+    VerifyJob j;
+    j.in = *in; j.out = *out; j.block_size = block_size;
+    if (block_first) { j.mode = VerifyJob::BLOCKS; j.block_first = block_first; j.nblocks = nblocks; }
+    return run_verify(c, j);
 }
 
 int fhip_verify_frames_blocks(fhip_ctx *c, const fhip_verify_in *in, const uint32_t *block_first, int nblocks,
@@ -2220,31 +2249,10 @@ int fhip_verify_frames_blocks(fhip_ctx *c, const fhip_verify_in *in, const uint3
 {
     int rc = verify_blocks_check(c, in, block_first, nblocks, block_size, out);
     if (rc != FHIP_OK) return rc;
-    if (nblocks == 0 && in->nframes > 0) return fail(c, FHIP_E_INVALID, "frames without blocks");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t sb = (size_t)in->stream_bytes, nf = (size_t)in->nframes, nb = (size_t)nblocks;
-    const size_t nv = (size_t)in->nsamples * (size_t)c->p.channels;
-    HIP_TRY(c, c->d_vstream.reserve(sb));
-    HIP_TRY(c, c->d_vfb.reserve(nf));
-    HIP_TRY(c, c->d_vpcm.reserve(nv));
-    HIP_TRY(c, c->d_vnum.reserve(nb));
-    if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_vstream, in->stream, sb, hipMemcpyHostToDevice, c->stream));
-    if (nf) HIP_TRY(c, hipMemcpyAsync(c->d_vfb, in->frame_bytes, nf * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    if (nv) HIP_TRY(c, hipMemcpyAsync(c->d_vpcm, in->pcm, nv * c->pcm_width(), hipMemcpyHostToDevice, c->stream));
-    if (nb) HIP_TRY(c, hipMemcpyAsync(c->d_vnum, block_first, nb * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    // (without blocks there are no frames either: the sequence mode's empty launch)
-    rc = run_verify(c, c->d_vstream, in->stream_bytes, c->d_vfb, in->nframes, nullptr, c->d_vpcm, in->nsamples, 0,
-                    block_size, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                    nb ? (const uint32_t *)c->d_vnum : nullptr, nblocks);
-    if (rc != FHIP_OK) return rc;
-    long long sum[4] = {0, 0, -1, 0};
-    HIP_TRY(c, hipMemcpyAsync(sum, c->d_vsum, sizeof sum, hipMemcpyDeviceToHost, c->stream));
-    if (out->frames && nf)
-        HIP_TRY(c, hipMemcpyAsync(out->frames, c->d_vrec, nf * sizeof(fhip_verify_rec), hipMemcpyDeviceToHost, c->stream));
-    rc = fhip_sync(c);
-    if (rc != FHIP_OK) return rc;
-    for (int i = 0; i < 4; i++) out->summary[i] = sum[i];
-    return verify_verdict(c, sum, c->d_vrec, nullptr, block_first, nblocks, block_size);
+    VerifyJob j;
+    j.in = *in; j.block_size = block_size;
+    if (nblocks) { j.mode = VerifyJob::BLOCKS; j.nblocks = nblocks; j.host_block_first = block_first; }
+    return verify_host(c, j, block_first, (size_t)nblocks, out);
 }
 
 int fhip_last_verify_number(const fhip_ctx *c, uint32_t *number)

@@ -196,6 +196,34 @@ static int grow_call_tables(FlakeAmdSet *g, int nblocks)
 
 #define SET_FAIL(...) do { snprintf(g->err, sizeof g->err, __VA_ARGS__); return -1; } while (0)
 
+/* A chunk (blocks b0 .. b0 + cnt of the call) came back FHIP_E_VERIFY from the entry `what`: the verifier's first
+ * failing frame is an index into the chunk; name its block, from there its stream, and the number it had to carry.
+ * block_frames: the chunk's frames per block where blocks were split (numbered by first sample), null for one frame
+ * per block; ragged: flake_amd_set_encode_ragged's call.  Nothing of the call is committed, the device hashes have
+ * moved on.  Returns -1 with the set's error text and vfail fields filled. */
+static long long set_verify_failed(FlakeAmdSet *g, const char *what, const int *stream_of_block, int b0, int cnt,
+                                   const int32_t *block_frames, int ragged)
+{
+    int64_t vs[4] = {0, 0, -1, 0};
+    fhip_verify_rec vr = {0, -1, -1, -1};
+    uint32_t number = 0;
+    (void)fhip_last_verify_failure(g->hip, vs, &vr);
+    const int have_number = fhip_last_verify_number(g->hip, &number) == 1;
+    g->broken = g->dev_md5 != NULL;
+    const int blk = fa_block_of_frame(vs[2], block_frames, cnt);
+    if (blk < 0) SET_FAIL("%s: %s (%s)", what, fhip_strerror(FHIP_E_VERIFY), fhip_last_error(g->hip));
+    const int idx = b0 + blk;
+    g->vfail = 1;
+    g->vfail_stream = stream_of_block[idx];
+    g->vfail_number = have_number ? number : g->fnum[idx];      /* (the frame's own; unplaceable: the block's first) */
+    g->vfail_status = vr.status;
+    SET_FAIL("flake_amd_set_encode%s: verification failed: %lld of the chunk's %lld frames do not decode to the "
+             "input; first: stream %d, %s %u (%sblock %d of the call), %s (subframe %d, sample %d, bit %d)",
+             ragged ? "_ragged" : "", (long long)vs[1], (long long)vs[0], g->vfail_stream,
+             block_frames ? "first sample" : "frame", g->vfail_number, ragged ? "short " : "", idx,
+             verify_status_name(vr.status), vr.subframe, vr.sample, vr.bit);
+}
+
 FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples, int sample_bytes, int nblocks,
                                              int block_size, const int *stream_of_block, unsigned char *out,
                                              size_t out_size, int *frame_sizes)
@@ -275,55 +303,15 @@ FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples
             rc = fhip_encode_blocks_vbs_packed_numbered(g->hip, bt.pcm, cnt, block_size, g->fnum + b0, out + total,
                                                         (int64_t)(out_size - (size_t)total), g->fbytes + b0,
                                                         g->bframes + b0, g->bmax + b0, &bytes);
-            if (rc == FHIP_E_VERIFY) {
-                /* the verifier's frame index counts the chunk's FRAMES: the prefix sum of block_frames says which
-                 * block it lies in, the block says which stream */
-                int64_t vs[4] = {0, 0, -1, 0};
-                fhip_verify_rec vr = {0, -1, -1, -1};
-                uint32_t number = 0;
-                (void)fhip_last_verify_failure(g->hip, vs, &vr);
-                const int have_number = fhip_last_verify_number(g->hip, &number) == 1;
-                g->broken = g->dev_md5 != NULL;
-                int blk = -1;
-                long long at = 0;
-                for (int b = 0; b < cnt && blk < 0; b++) {
-                    if (g->bframes[b0 + b] < 1) break;
-                    if (vs[2] >= at && vs[2] < at + g->bframes[b0 + b]) blk = b;
-                    at += g->bframes[b0 + b];
-                }
-                if (vs[2] < 0 || blk < 0) SET_FAIL("%s: %s (%s)", what, fhip_strerror(rc), fhip_last_error(g->hip));
-                const int idx = b0 + blk;
-                g->vfail = 1;
-                g->vfail_stream = stream_of_block[idx];
-                g->vfail_number = have_number ? number : g->fnum[idx];     /* (unplaceable: the block's first sample) */
-                g->vfail_status = vr.status;
-                SET_FAIL("flake_amd_set_encode: verification failed: %lld of the chunk's %lld frames do not decode to the "
-                         "input; first: stream %d, first sample %u (block %d of the call), %s (subframe %d, sample %d, bit %d)",
-                         (long long)vs[1], (long long)vs[0], g->vfail_stream, g->vfail_number, idx,
-                         verify_status_name(vr.status), vr.subframe, vr.sample, vr.bit);
-            }
+            /* (the verifier's frame index counts the chunk's FRAMES: block_frames says which block it lies in) */
+            if (rc == FHIP_E_VERIFY) return set_verify_failed(g, what, stream_of_block, b0, cnt, g->bframes + b0, 0);
             if (rc == FHIP_OK) total += bytes;
             continue;
         }
         if (rc == FHIP_OK) { what = "fhip_frames_packed_begin"; rc = fhip_frames_packed_begin(g->hip, &bt, &bytes); }
         if (rc == FHIP_E_VERIFY) {
-            /* the verifier's first failing frame is an index into this chunk: name its stream and that stream's frame.
-             * Nothing of the call is committed; the device hashes have moved on, as in the case below */
-            int64_t vs[4] = {0, 0, -1, 0};
-            fhip_verify_rec vr = {0, -1, -1, -1};
-            (void)fhip_last_verify_failure(g->hip, vs, &vr);
             (void)fhip_frames_packed_fetch_wait(g->hip);
-            g->broken = g->dev_md5 != NULL;
-            if (vs[2] < 0 || vs[2] >= cnt) SET_FAIL("fhip_frames_packed_begin: %s (%s)", fhip_strerror(rc), fhip_last_error(g->hip));
-            const int idx = b0 + (int)vs[2];
-            g->vfail = 1;
-            g->vfail_stream = stream_of_block[idx];
-            g->vfail_number = g->fnum[idx];
-            g->vfail_status = vr.status;
-            SET_FAIL("flake_amd_set_encode: verification failed: %lld of the chunk's %lld frames do not decode to the "
-                     "input; first: stream %d, frame %u (block %d of the call), %s (subframe %d, sample %d, bit %d)",
-                     (long long)vs[1], (long long)vs[0], g->vfail_stream, g->vfail_number, idx,
-                     verify_status_name(vr.status), vr.subframe, vr.sample, vr.bit);
+            return set_verify_failed(g, what, stream_of_block, b0, cnt, NULL, 0);
         }
         if (rc == FHIP_OK && (size_t)(total + bytes) > out_size) {
             (void)fhip_frames_packed_fetch_wait(g->hip);
@@ -420,21 +408,8 @@ static long long set_encode_short(FlakeAmdSet *g, const void *samples, int sampl
             rc = fhip_frames_packed_begin_ragged(g->hip, &bt, (const int32_t *)(sizes + b0), &bytes);
         }
         if (rc == FHIP_E_VERIFY) {
-            int64_t vs[4] = {0, 0, -1, 0};
-            fhip_verify_rec vr = {0, -1, -1, -1};
-            (void)fhip_last_verify_failure(g->hip, vs, &vr);
             (void)fhip_frames_packed_fetch_wait(g->hip);
-            g->broken = g->dev_md5 != NULL;
-            if (vs[2] < 0 || vs[2] >= cnt) SET_FAIL("fhip_frames_packed_begin_ragged: %s (%s)", fhip_strerror(rc), fhip_last_error(g->hip));
-            const int idx = b0 + (int)vs[2];
-            g->vfail = 1;
-            g->vfail_stream = stream_of_block[idx];
-            g->vfail_number = g->fnum[idx];
-            g->vfail_status = vr.status;
-            SET_FAIL("flake_amd_set_encode_ragged: verification failed: %lld of the chunk's %lld frames do not decode to "
-                     "the input; first: stream %d, frame %u (short block %d of the call), %s (subframe %d, sample %d, bit %d)",
-                     (long long)vs[1], (long long)vs[0], g->vfail_stream, g->vfail_number, idx,
-                     verify_status_name(vr.status), vr.subframe, vr.sample, vr.bit);
+            return set_verify_failed(g, what, stream_of_block, b0, cnt, NULL, 1);
         }
         if (rc == FHIP_OK && (size_t)(total + bytes) > out_size) {
             (void)fhip_frames_packed_fetch_wait(g->hip);

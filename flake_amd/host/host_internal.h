@@ -18,4 +18,19 @@ void fa_md5_final(const fa_md5 *m, uint8_t out[16]);
 void fa_md5_pcm(fa_md5 *m, const int32_t *pcm, size_t nvalues, int bps);
 void fa_md5_pcm16(fa_md5 *m, const int16_t *pcm, size_t nvalues, int bps);
 
+/* Which of a chunk's cnt blocks the verifier's frame index (it counts the chunk's frames) lies in: block b holds
+ * block_frames[b] frames, one each when the table is null.  -1: none -- an index below 0 or past the chunk's frames;
+ * an entry below 1 ends the search (nothing behind a block that was not encoded can be placed). */
+static inline int fa_block_of_frame(long long frame, const int32_t *block_frames, int cnt)
+{
+    long long at = 0;
+    for (int b = 0; b < cnt && frame >= 0; b++) {
+        const int nf = block_frames ? block_frames[b] : 1;
+        if (nf < 1) break;
+        at += nf;
+        if (frame < at) return b;
+    }
+    return -1;
+}
+
 #endif

@@ -84,17 +84,8 @@ def test_ragged_begin_equals_uniform_one_frame_calls(encoded, case):
 
 
 def verify_ragged(enc, stream, fb, pcm, numbers, sizes):
-    st = np.frombuffer(bytes(stream), np.uint8)
-    fb = np.ascontiguousarray(fb, np.int32)
-    pc = np.ascontiguousarray(pcm, enc.pcm_dtype)
-    num = np.ascontiguousarray(numbers, np.uint32)
-    sz = np.ascontiguousarray(sizes, np.int32)
-    recs = np.zeros(len(fb), V.VERIFY_REC_DTYPE)
-    summary = np.zeros(4, np.int64)
-    vi = V.VerifyIn(st.ctypes.data, st.size, fb.ctypes.data, len(fb), pc.ctypes.data, pc.shape[0], 0)
-    vo = V.VerifyOut(recs.ctypes.data, summary.ctypes.data)
-    rc = enc.lib.fhip_verify_frames_ragged(enc._h, C.byref(vi), num.ctypes.data, sz.ctypes.data, C.byref(vo))
-    return rc, recs, summary
+    ok, recs, summary, _ = enc.verify_frames_ragged(stream, fb, pcm, numbers, sizes)
+    return (V.OK if ok else V.E_VERIFY), recs, summary
 
 
 @pytest.mark.parametrize("case", [CASES[0], CASES[3]])

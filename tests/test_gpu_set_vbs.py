@@ -26,6 +26,7 @@ if __name__ == "__main__":          # (pytest's conftest does this for the suite
 
 import flake_amd
 from cases import _rng
+from test_set_verify_map_cpu import block_of_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -419,7 +420,7 @@ def test_block_table_verifier(twelve, torch):
 
 def test_set_level_failure_names_stream_and_sample(twelve):
     """What flake_amd_set_encode relays when a chunk fails: the first failing frame, mapped to its block by the prefix
-    sum of block_frames and from there to its stream, and the first-sample number it had to carry
+    sum of block_frames (fa_block_of_frame; test_set_verify_map_cpu.py runs the C) and from there to its stream, and the first-sample number it had to carry
     (fhip_last_verify_number).  The encoder cannot be made to fail from outside without breaking it -- K4 writes what
     the table says and K5 is given the same table -- so the verdict is provoked where a table can be wrong: the entry
     the set encodes through writes the batch by one table, and the verifier is handed another."""
@@ -437,7 +438,7 @@ def test_set_level_failure_names_stream_and_sample(twelve):
         ok, recs, summ, err = enc.verify_frames_blocks(data_w, t["fbytes"], t["pcm"], t["first"], t["bs"])
         assert not ok
         summary, rec, number = enc.last_verify_failure()
-        blk = int(np.searchsorted(np.cumsum(bfr_w), summary[2], side="right"))      # flake_set.c's prefix sum
+        blk = block_of_frame(bfr_w, int(summary[2]))      # flake_set.c's map, held to this expression on the CPU
         assert blk == 7 and t["owner"][blk] == 2 and rec["status"] == V.V_NUMBER and rec["bit"] == 32
         assert number == int(t["first"][7]) == t["bs"]          # stream 2's second block: its sample 4096
 
