@@ -223,6 +223,10 @@ def load_library() -> C.CDLL:
         "fhip_verify_frames_blocks_dev": (i, [vp, C.POINTER(VerifyIn), vp, i, i, C.POINTER(VerifyOut)]),
         "fhip_verify_frames_blocks": (i, [vp, C.POINTER(VerifyIn), vp, i, i, C.POINTER(VerifyOut)]),
         "fhip_last_verify_number": (i, [vp, C.POINTER(C.c_uint32)]),
+        "fhip_encode_blocks_vbs_ragged_numbered": (i, [vp, vp, i, vp, vp, vp, i64, vp, vp, vp, C.POINTER(i64)]),
+        "fhip_vbs_split_ragged": (i, [vp, vp, i, vp, vp, vp]),
+        "fhip_verify_frames_blocks_ragged_dev": (i, [vp, C.POINTER(VerifyIn), vp, i, vp, C.POINTER(VerifyOut)]),
+        "fhip_verify_frames_blocks_ragged": (i, [vp, C.POINTER(VerifyIn), vp, i, vp, C.POINTER(VerifyOut)]),
         "fhip_device_alloc": (vp, [C.c_size_t]),
         "fhip_device_free": (None, [vp]),
     }
@@ -252,6 +256,8 @@ ABI_SYMBOLS = (
     "fhip_verify_frames_ragged_dev", "fhip_verify_frames_ragged",
     "fhip_encode_blocks_vbs_packed_numbered", "fhip_set_block_numbering", "fhip_verify_frames_blocks_dev",
     "fhip_verify_frames_blocks", "fhip_last_verify_number",
+    "fhip_encode_blocks_vbs_ragged_numbered", "fhip_vbs_split_ragged", "fhip_verify_frames_blocks_ragged_dev",
+    "fhip_verify_frames_blocks_ragged",
 )
 
 
@@ -422,6 +428,50 @@ class Encoder:
             raise ValueError("block_first is shorter than nblocks")
         return self._verify_host("fhip_verify_frames_blocks", (bf.ctypes.data if bf.size else None, nb, block_size),
                                  stream, frame_bytes, pcm, pcm_dtype=np.int32)
+
+    def encode_blocks_vbs_ragged_numbered(self, pcm: np.ndarray, block_sizes, block_first):
+        """fhip_encode_blocks_vbs_ragged_numbered on host data: pcm [sum(block_sizes)][channels] int32, the blocks back
+        to back, block b numbered from block_first[b].  Returns (bytes, block_bytes, block_frames, block_max_frame);
+        raises FlakeHipError (code E_VERIFY while set_verify is on and a frame fails)."""
+        ch = self.params.channels
+        pcm = np.ascontiguousarray(pcm, dtype=np.int32).reshape(-1, ch)
+        sz = np.ascontiguousarray(block_sizes, dtype=np.int32)
+        bf = np.ascontiguousarray(block_first, dtype=np.uint32)
+        nb = len(sz)
+        if len(bf) != nb or int(sz.sum()) != pcm.shape[0]:
+            raise ValueError("block_first needs one entry per block and pcm the blocks' samples")
+        cap = 64 + pcm.size * 5 + 64 * (nb + 1) * 8
+        out = np.zeros(cap, dtype=np.uint8)
+        bb, bfr, bmx = (np.zeros(max(nb, 1), dtype=np.int32) for _ in range(3))
+        wrote = C.c_int64(0)
+        self._check(self.lib.fhip_encode_blocks_vbs_ragged_numbered(
+            self._h, pcm.ctypes.data, nb, sz.ctypes.data, bf.ctypes.data, out.ctypes.data, cap, bb.ctypes.data,
+            bfr.ctypes.data, bmx.ctypes.data, C.byref(wrote)), "fhip_encode_blocks_vbs_ragged_numbered")
+        return out[:wrote.value].copy(), bb[:nb], bfr[:nb], bmx[:nb]
+
+    def verify_frames_blocks_ragged(self, stream, frame_bytes, pcm, block_first, block_sizes):
+        """K5's block-table mode with a length per block, on host data (fhip_verify_frames_blocks_ragged): pcm holds
+        the blocks back to back, block b is block_sizes[b] samples and starts at sample block_first[b] of its stream.
+        Returns (ok, records, summary int64[4], error text) as verify_frames does."""
+        bf = np.ascontiguousarray(block_first, dtype=np.uint32)
+        sz = np.ascontiguousarray(block_sizes, dtype=np.int32)
+        if len(bf) != len(sz):
+            raise ValueError("block_first and block_sizes need one entry per block")
+        return self._verify_host("fhip_verify_frames_blocks_ragged",
+                                 (bf.ctypes.data if bf.size else None, len(sz), sz.ctypes.data if sz.size else None),
+                                 stream, frame_bytes, pcm, pcm_dtype=np.int32)
+
+    def vbs_split_ragged(self, pcm: np.ndarray, block_sizes):
+        """fhip_vbs_split_ragged on host data: (frames int32[nblocks], sizes int32[nblocks][8])."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int32).reshape(-1, self.params.channels)
+        sz = np.ascontiguousarray(block_sizes, dtype=np.int32)
+        if int(sz.sum()) != pcm.shape[0]:
+            raise ValueError("pcm must hold the blocks' samples")
+        frames = np.zeros(max(len(sz), 1), dtype=np.int32)
+        sizes = np.zeros((max(len(sz), 1), 8), dtype=np.int32)
+        self._check(self.lib.fhip_vbs_split_ragged(self._h, pcm.ctypes.data, len(sz), sz.ctypes.data, frames.ctypes.data,
+                                                   sizes.ctypes.data), "fhip_vbs_split_ragged")
+        return frames[:len(sz)], sizes[:len(sz)]
 
     def verify_frames_blocks_dev(self, stream, stream_bytes: int, frame_bytes, nframes: int, pcm, nsamples: int,
                                  block_first, nblocks: int, block_size: int, summary, records=None) -> None:
@@ -673,6 +723,8 @@ def load_host_library() -> C.CDLL:
     lib.flake_amd_set_last_verify_failure.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint),
                                                       C.POINTER(C.c_int)]
     lib.flake_amd_set_last_verify_failure.restype = C.c_int
+    lib.flake_amd_set_device_batches.argtypes = [C.c_void_p]
+    lib.flake_amd_set_device_batches.restype = C.c_longlong
     lib.flake_amd_set_close.argtypes = [C.c_void_p]
     lib.flake_amd_set_close.restype = None
     _host = lib
@@ -864,6 +916,10 @@ class StreamSet:
         if w < 0:
             raise FlakeHipError(int(w), "flake_amd_set_encode_ragged", self.last_error())
         return out[:w].copy(), sizes[:nblocks]
+
+    def device_batches(self) -> int:
+        """flake_amd_set_device_batches: chunks handed to an encode entry of the HIP layer since the set was opened."""
+        return int(self.lib.flake_amd_set_device_batches(self._g))
 
     def set_verify(self, on: bool) -> None:
         """flake_amd_set_enable_verify: every later encode call verifies its frames on the device, each against

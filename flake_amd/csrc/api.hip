@@ -16,6 +16,7 @@
 #include "flakehip.h"
 #include "kernels.h"
 #include "vbs_schedule.h"
+#include "vbs_block_lookup.h"
 
 // A device block and its capacity in elements.  The handle's buffers are members of fhip_ctx: they are freed
 // when fhip_destroy() deletes the handle (after it has set the device and waited for the streams), never before.
@@ -90,6 +91,14 @@ struct fhip_ctx {
     DevBuf<int32_t> d_blk_max;        // fhip_encode_blocks_vbs_packed_numbered: every block's largest frame ...
     DevBuf<uint32_t> d_blk_first;     // ... and the host's block_first table uploaded
     bool block_numbering = false;     // fhip_set_block_numbering: frame_numbers are one-frame blocks of many streams
+    // ragged variable-block-size batches (fhip_encode_blocks_vbs_ragged_numbered): the dense piece tables
+    // k_vbs_plan_ragged leaves beside d_frame_src / d_fnum, and the per-block tables the host uploads for it and for K5
+    DevBuf<int32_t> d_pn;             // [max_frames] piece lengths
+    DevBuf<double> d_pc;              // [max_frames] their window constants (lpc.c:34)
+    DevBuf<double> d_blkc;            // [nblocks][8] the constant for m eighths of block b, computed on the host
+    DevBuf<long long> d_blk_start;    // [nblocks + 1] prefix sums of the block lengths
+    std::vector<double> h_blkc;
+    std::vector<long long> h_blk_start;
 
     // two internal streams for the split-batch overlap (run_pipeline)
     static constexpr int NAUX = 4;       // (run_pipeline's split uses the first two, the VBS groups all)
@@ -483,9 +492,11 @@ struct VerifyJob {
     const uint32_t *numbers = nullptr;
     const int32_t *frame_n = nullptr; const long long *frame_src = nullptr;
     const uint32_t *block_first = nullptr; int nblocks = 0;
+    const long long *block_start = nullptr;  // BLOCKS with a length per block: their prefix sums [nblocks + 1] (device)
     // HOST copies for the verdict's text and fhip_last_verify_number, optional: the number frame f must carry (where
     // each block of a BLOCKS job is one frame too), or block_first: the number follows from where K5 placed the frame
     const uint32_t *host_numbers = nullptr, *host_block_first = nullptr;
+    const long long *host_block_start = nullptr;     // (with host_block_first, where the blocks differ in length)
     long long sum[4] = {0, 0, -1, 0};        // HOST: the summary, once verify_batch's copy has come (the caller's sync)
 };
 
@@ -504,7 +515,7 @@ int run_verify(fhip_ctx *c, const VerifyJob &j)
                        reinterpret_cast<unsigned long long *>(c->d_vsum + 4), j.totals, nullptr};
     if (j.mode == VerifyJob::NUMBERS || j.mode == VerifyJob::RAGGED) a.numbers = j.numbers;
     if (j.mode == VerifyJob::RAGGED) { a.frame_n = j.frame_n; a.frame_src = j.frame_src; }
-    if (j.mode == VerifyJob::BLOCKS) { a.block_first = j.block_first; a.nblocks = j.nblocks; }
+    if (j.mode == VerifyJob::BLOCKS) { a.block_first = j.block_first; a.nblocks = j.nblocks; a.block_start = j.block_start; }
     Prof pr(c, kProfVerify, c->profiling);
     HIP_TRY(c, fhip::launch_verify(c->stream, a));
     return FHIP_OK;
@@ -550,12 +561,14 @@ int verify_verdict(fhip_ctx *c, const VerifyJob &j)
         HIP_TRY(c, hipMemcpy(&vf, c->d_vws + summary[2], sizeof vf, hipMemcpyDeviceToHost));
         // K5's header pass left its own status there: OK / CRC8 (placed, numbered right) or NUMBER at bit 32 (placed,
         // numbered wrong) say that rel_start is where the frame lies; anything else was never placed
-        const long long blk = vf.rel_start / j.block_size;
+        const long long blk = j.host_block_start ? fhip_block_lookup(j.host_block_start, j.nblocks, vf.rel_start)
+                                                 : vf.rel_start / j.block_size;
         const bool placed = vf.status == FHIP_VERIFY_OK || vf.status == FHIP_VERIFY_CRC8 ||
                             (vf.status == FHIP_VERIFY_NUMBER && vf.bit == 32);
-        if (placed && vf.rel_start >= 0 && blk < j.nblocks) {
+        if (placed && vf.rel_start >= 0 && blk >= 0 && blk < j.nblocks) {
+            const long long start = j.host_block_start ? j.host_block_start[blk] : blk * j.block_size;
             c->vfail_has_number = true;
-            c->vfail_number = j.host_block_first[blk] + (uint32_t)(vf.rel_start - blk * j.block_size);
+            c->vfail_number = j.host_block_first[blk] + (uint32_t)(vf.rel_start - start);
         }
     }
     char want[48] = "";
@@ -590,6 +603,11 @@ int verify_host(fhip_ctx *c, VerifyJob j, const uint32_t *table, size_t table_co
     if (table_count) HIP_TRY(c, hipMemcpyAsync(c->d_vnum, table, table_count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     j.in.stream = c->d_vstream; j.in.frame_bytes = c->d_vfb; j.in.pcm = c->d_vpcm;
     j.numbers = j.block_first = c->d_vnum;          // (whichever the mode reads)
+    if (j.mode == VerifyJob::BLOCKS && j.host_block_start) {
+        // (block_first, then the prefix sums as 8-byte entries behind an even count of 4-byte ones)
+        const size_t nb2 = ((size_t)j.nblocks + 1) & ~(size_t)1;
+        j.block_start = reinterpret_cast<const long long *>(c->d_vnum.get() + nb2);
+    }
     if (j.mode == VerifyJob::RAGGED) {
         const size_t nf2 = (nf + 1) & ~(size_t)1;
         j.frame_n = reinterpret_cast<const int32_t *>(c->d_vnum.get() + nf2);
@@ -697,12 +715,19 @@ int check_batch(fhip_ctx *c, const fhip_batch *b, bool host = false)
 
 // What the ragged entries check first: the handle, the batch (check_range), then the table -- every entry in
 // 1..params.block_size, the largest equal to b->block_size.  *total = the batch's samples per channel.
-int check_ragged(fhip_ctx *c, const fhip_batch *b, const int32_t *block_sizes, bool rest, long long *total)
+// vbs_ok: the entry also serves handles with allow_vbs (the upload: what it brings is then encoded by
+// fhip_encode_blocks_vbs_ragged_numbered) -- int32 PCM only there, and eight frame slots per block.
+int check_ragged(fhip_ctx *c, const fhip_batch *b, const int32_t *block_sizes, bool rest, long long *total,
+                 bool vbs_ok = false)
 {
     int rc = check_range(c, b, rest && block_sizes, "null argument");
     if (rc != FHIP_OK) return rc;
-    if (c->p.allow_vbs)
+    if (c->p.allow_vbs && !vbs_ok)
         return fail(c, FHIP_E_UNSUPPORTED, "ragged batches need a fixed-block handle (allow_vbs numbers samples)");
+    if (c->p.allow_vbs && c->pcm_format == FHIP_PCM_S16)
+        return fail(c, FHIP_E_UNSUPPORTED, "variable block size is not supported for int16 PCM (FHIP_PCM_S16)");
+    if (c->p.allow_vbs && (long long)b->nframes * 8 > c->max_frames)
+        return fail(c, FHIP_E_INVALID, "nblocks * 8 exceeds the handle's max_frames");
     if (c->p.block_size > fhip::FHIP_MAX_RESIDENT_BLOCK)
         return fail(c, FHIP_E_UNSUPPORTED, "ragged batches need params.block_size <= 16384: use one call per length");
     long long sum = 0;
@@ -745,12 +770,13 @@ int upload_ragged_tables(fhip_ctx *c, const int32_t *block_sizes, int nframes)
 }
 
 // K0 ... K4 of a ragged batch on the handle's stream: the generic instances with the per-frame tables.
-int run_ragged(fhip_ctx *c, const int32_t *pcm, int nframes, int nmax, uint8_t *bits, int64_t slot_bytes,
-               const FrameOut &fo)
+// rf: the tables -- the host's (upload_ragged_tables), or the device's with the live count there too (a ragged
+// variable-block-size batch: nframes is then the capacity the grids are sized for).
+int run_ragged(fhip_ctx *c, const int32_t *pcm, int nframes, const fhip::RaggedFrames &rf, uint8_t *bits,
+               int64_t slot_bytes, const FrameOut &fo)
 {
     const fhip_params &p = c->p;
     const int nsub = nframes * p.channels;
-    const fhip::RaggedFrames rf{c->rg_n(), c->rg_src(), c->rg_c(), p.block_size, nmax};
     const bool prof = c->profiling;
     {
         Prof pr(c, 0, prof);
@@ -764,7 +790,7 @@ int run_ragged(fhip_ctx *c, const int32_t *pcm, int nframes, int nmax, uint8_t *
         }
         Prof pr(c, 2, prof);
         HIP_TRY(c, fhip::launch_lpc(c->stream, c->d_autoc, nsub, p.max_prediction_order, p.lpc_precision, p.order_method,
-                                    c->d_coefs, c->d_shift, c->d_opt, c->d_fin));
+                                    c->d_coefs, c->d_shift, c->d_opt, c->d_fin, rf.dev_sub));
     }
     {
         Prof pr(c, 3, prof);
@@ -772,8 +798,9 @@ int run_ragged(fhip_ctx *c, const int32_t *pcm, int nframes, int nmax, uint8_t *
                                               bits, slot_bytes, c->d_k0rec));
     }
     Prof pr(c, 4, prof);
-    HIP_TRY(c, fhip::launch_assemble(c->stream, p, pcm, nframes, nmax, c->d_info, bits, slot_bytes, fo.frames, fo.stride,
-                                     fo.bytes, fo.first, 1u, fo.numbers, rf.frame_src, nullptr, c->pcm_format, rf.frame_n));
+    HIP_TRY(c, fhip::launch_assemble(c->stream, p, pcm, nframes, rf.nmax, c->d_info, bits, slot_bytes, fo.frames, fo.stride,
+                                     fo.bytes, fo.first, 1u, fo.numbers, rf.frame_src, rf.dev_frames, c->pcm_format,
+                                     rf.frame_n));
     return FHIP_OK;
 }
 
@@ -1363,7 +1390,7 @@ int fhip_encode_frames_packed(fhip_ctx *c, const fhip_batch *b, uint8_t *out, in
 int fhip_frames_packed_upload_ragged(fhip_ctx *c, const fhip_batch *b, const int32_t *block_sizes)
 {
     long long total = 0;
-    int rc = check_ragged(c, b, block_sizes, true, &total);
+    int rc = check_ragged(c, b, block_sizes, true, &total, true);
     if (rc != FHIP_OK) return rc;
     c->uploaded_pcm = nullptr;
     if (b->nframes == 0) return FHIP_OK;
@@ -1426,7 +1453,8 @@ int fhip_frames_packed_begin_ragged(fhip_ctx *c, const fhip_batch *b, const int3
         if (rc != FHIP_OK) return rc;
     }
     const FrameOut fo{c->d_frames, stride, c->d_fbytes, b->first_frame_number, c->d_fnum};
-    rc = run_ragged(c, c->d_pcm, b->nframes, b->block_size, c->d_bits, slot, fo);
+    const fhip::RaggedFrames rf{c->rg_n(), c->rg_src(), c->rg_c(), c->p.block_size, b->block_size};
+    rc = run_ragged(c, c->d_pcm, b->nframes, rf, c->d_bits, slot, fo);
     if (rc != FHIP_OK) return rc;
     HIP_TRY(c, fhip::launch_pack_frames(c->stream, c->d_frames, stride, c->d_fbytes, b->nframes,
                                         c->d_offsets, c->d_packed));
@@ -2111,6 +2139,187 @@ int fhip_encode_blocks_vbs_packed_numbered(fhip_ctx *c, const int32_t *pcm, int 
                       block_max_frame, out_bytes, nullptr, nullptr);
 }
 
+// ---- ragged variable block size: blocks of different lengths (the tails of many streams) in one batch ----
+//
+// split_frame_v1 per block that it sees (k_vbs_split ragged), then k_vbs_plan ragged: with a length per block there are
+// as many piece lengths as pieces, so the bins do not apply -- the pieces go to dense tables in stream order (length,
+// offset, window constant, number) with the live count beside them on the device, and the ragged generic kernels (every
+// order method in-kernel) run once over a grid sized for the capacity, 8 * nblocks.  No host synchronisation between
+// the split and the pack.
+namespace {
+
+// What fhip_encode_blocks_vbs_ragged_numbered and fhip_vbs_split_ragged check first.  *total = samples per channel of
+// the batch, *nmax = its longest block.
+int vbs_ragged_check(fhip_ctx *c, const void *pcm, int nblocks, const int32_t *block_sizes, bool rest,
+                     long long *total, int *nmax)
+{
+    if (!c || !pcm || !block_sizes || !rest) return fail(c, FHIP_E_INVALID, "null argument");
+    const fhip_params &p = c->p;
+    if (!p.variable_block_size || !p.allow_vbs)
+        return fail(c, FHIP_E_INVALID, "the handle's parameters have no variable block size");
+    if (nblocks < 0 || (long long)nblocks * 8 > c->max_frames)
+        return fail(c, FHIP_E_INVALID, "nblocks * 8 exceeds the handle's max_frames");
+    long long sum = 0;
+    int largest = 0;
+    for (int b = 0; b < nblocks; b++) {
+        const int n = block_sizes[b];
+        if (n < 1 || n > p.block_size) return fail(c, FHIP_E_INVALID, "block_sizes entry out of range");
+        largest = n > largest ? n : largest;
+        sum += n;
+    }
+    if (const int rc = vbs_refuse_s16(c, false)) return rc;
+    if (p.block_size > fhip::FHIP_MAX_RESIDENT_BLOCK)
+        return fail(c, FHIP_E_UNSUPPORTED, "ragged batches need params.block_size <= 16384: use one call per length");
+    *total = sum;
+    *nmax = largest;
+    return FHIP_OK;
+}
+
+// The PCM and the block tables (lengths, offsets: upload_ragged_tables) on the device, unless a pending
+// fhip_frames_packed_upload_ragged of this very batch has brought them.
+int vbs_ragged_stage(fhip_ctx *c, const int32_t *pcm, int nblocks, const int32_t *block_sizes, size_t nvals)
+{
+    const bool uploaded = c->uploaded_pcm == pcm && c->uploaded_vals == nvals && c->uploaded_n == -1 &&
+                          c->uploaded_frames == nblocks &&
+                          std::equal(c->uploaded_sizes.begin(), c->uploaded_sizes.end(), block_sizes);
+    c->uploaded_pcm = nullptr;
+    if (uploaded) return FHIP_OK;            // (an MD5 update may be reading it beside us)
+    int rc = stage_pcm(c, pcm, nvals * sizeof(int32_t));
+    if (rc != FHIP_OK) return rc;
+    return upload_ragged_tables(c, block_sizes, nblocks);
+}
+
+}  // namespace
+
+int fhip_encode_blocks_vbs_ragged_numbered(fhip_ctx *c, const int32_t *pcm, int nblocks, const int32_t *block_sizes,
+                                           const uint32_t *block_first, uint8_t *out, int64_t out_cap,
+                                           int32_t *block_bytes, int32_t *block_frames, int32_t *block_max_frame,
+                                           int64_t *out_bytes)
+{
+    long long total_n = 0;
+    int nmax = 0;
+    int rc = vbs_ragged_check(c, pcm, nblocks, block_sizes, block_first && out && out_bytes && block_bytes, &total_n, &nmax);
+    if (rc != FHIP_OK) return rc;
+    LaunchScope ls(c);
+    const fhip_params &p = c->p;
+    *out_bytes = 0;
+    c->packed_ready = 0;                     // d_packed is about to be rewritten (and may move)
+    if (nblocks == 0) return FHIP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nch = (size_t)p.channels, nb = (size_t)nblocks, nvals = (size_t)total_n * nch;
+    const int cap = 8 * nblocks;             // the most pieces there can be: what every grid is sized for
+    // every slot keeps the size of the handle's block, as on the ragged packed path
+    const int64_t stride = fhip_frame_stride(&p, p.block_size);
+    const int64_t slot = (stride + 3) & ~(int64_t)3;
+    rc = vbs_reserve(c, (long long)cap * stride, (long long)cap * (long long)nch * slot);
+    if (rc != FHIP_OK) return rc;
+    // a frame is no larger than its verbatim form (encode.c:949), 16 bytes of overhead each: the stream's bound
+    const size_t packed_cap = nb * ((size_t)stride + 8 * 24);
+    const size_t nbcap = (size_t)c->max_frames / 8 + 2;
+    if (c->fetch_pending) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_fetch, 0));   // d_packed is still being read
+    HIP_TRY(c, c->d_packed.reserve(packed_cap));
+    HIP_TRY(c, c->d_pn.reserve((size_t)c->max_frames));
+    HIP_TRY(c, c->d_pc.reserve((size_t)c->max_frames));
+    HIP_TRY(c, c->d_blkc.reserve(nbcap * 8));
+    HIP_TRY(c, c->d_blk_start.reserve(nbcap + 1));
+    HIP_TRY(c, c->d_totals.reserve(4));
+    HIP_TRY(c, c->d_blk_bytes.reserve(nbcap));
+    HIP_TRY(c, c->d_blk_frames.reserve(nbcap));
+    HIP_TRY(c, c->d_blk_first.reserve(nbcap));
+    HIP_TRY(c, c->d_blk_max.reserve(nbcap));
+    if (c->verify) HIP_TRY(c, c->d_stream_bytes.reserve((size_t)c->max_frames));
+    rc = vbs_ragged_stage(c, pcm, nblocks, block_sizes, nvals);
+    if (rc != FHIP_OK) return rc;
+    // the window constant of lpc.c:34 for every length a piece of block b can have -- m eighths, or the block itself
+    // ([7] either way) -- computed here exactly as the other paths compute it; the plan kernel picks one
+    c->h_blkc.resize(nb * 8);
+    c->h_blk_start.resize(nb + 1);
+    long long at = 0;
+    for (int b = 0; b < nblocks; b++) {
+        const int n = block_sizes[b];
+        const bool splits = (n % 8) == 0 && n >= 128;
+        for (int m = 1; m <= 8; m++) {
+            const int len = (splits && m < 8) ? m * (n / 8) : n;
+            c->h_blkc[(size_t)b * 8 + (m - 1)] = (2.0 / (len - 1.0)) - 1.0;
+        }
+        c->h_blk_start[b] = at;
+        at += n;
+    }
+    c->h_blk_start[nb] = at;
+    HIP_TRY(c, hipMemcpyAsync(c->d_blkc, c->h_blkc.data(), nb * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_blk_start, c->h_blk_start.data(), (nb + 1) * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_blk_first, block_first, nb * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    // (d_opt / d_shift are free until K2 runs, which the plan precedes on this stream)
+    HIP_TRY(c, fhip::launch_vbs_split_ragged(c->stream, c->d_pcm, nblocks, c->rg_n(), c->rg_src(), p.channels, c->d_opt,
+                                             c->d_shift));
+    HIP_TRY(c, fhip::launch_vbs_plan_ragged(c->stream, c->d_opt, c->d_shift, nblocks, c->rg_n(), c->rg_src(), c->d_blkc,
+                                            c->d_blk_first, p.channels, stride, c->d_vcnt, c->d_pn, c->d_frame_src, c->d_pc,
+                                            c->d_fnum, c->d_first, c->d_order, c->d_srcoff));
+    fhip::RaggedFrames rf{c->d_pn, c->d_frame_src, c->d_pc, p.block_size, nmax};
+    rf.dev_frames = c->d_vcnt;
+    rf.dev_sub = c->d_vcnt + 1;
+    const FrameOut fo{c->d_frames, stride, c->d_fbytes, 0, c->d_fnum};
+    rc = run_ragged(c, c->d_pcm, cap, rf, c->d_bits, slot, fo);
+    if (rc != FHIP_OK) return rc;
+    // the pieces lie in stream order: the plan's order[] is the identity and the frames are packed as they lie
+    HIP_TRY(c, fhip::launch_pack_frames_perm(c->stream, c->d_frames, c->d_srcoff, c->d_fbytes, c->d_order, cap, c->d_vcnt,
+                                             c->d_offsets, c->d_packed, (long long)packed_cap,
+                                             c->verify ? c->d_stream_bytes.get() : nullptr, c->d_totals));
+    HIP_TRY(c, fhip::launch_vbs_block_bytes(c->stream, c->d_first, c->d_offsets, nblocks, c->d_blk_bytes,
+                                            block_frames ? c->d_blk_frames.get() : nullptr,
+                                            block_max_frame ? c->d_blk_max.get() : nullptr));
+    VerifyJob vj;
+    vj.in.stream = c->d_packed; vj.in.stream_bytes = (int64_t)packed_cap;
+    vj.in.frame_bytes = c->d_stream_bytes; vj.in.nframes = cap; vj.dev_count = c->d_totals;
+    vj.in.pcm = c->d_pcm; vj.in.nsamples = total_n; vj.block_size = p.block_size;
+    vj.mode = VerifyJob::BLOCKS;
+    vj.block_first = c->d_blk_first; vj.nblocks = nblocks; vj.block_start = c->d_blk_start;
+    vj.host_block_first = block_first; vj.host_block_start = c->h_blk_start.data();
+    if (c->verify) rc = verify_batch(c, vj);
+    if (rc != FHIP_OK) return rc;
+    long long totals[4] = {0, 0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(totals, c->d_totals, sizeof totals, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(block_bytes, c->d_blk_bytes, nb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (block_frames)
+        HIP_TRY(c, hipMemcpyAsync(block_frames, c->d_blk_frames, nb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (block_max_frame)
+        HIP_TRY(c, hipMemcpyAsync(block_max_frame, c->d_blk_max, nb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    rc = fhip_sync(c);
+    if (rc != FHIP_OK) return rc;
+    if (totals[3] & 3) return fail(c, FHIP_E_GENERIC, "a frame of the batch was not encoded");
+    for (int b = 0; b < nblocks; b++)
+        if (block_bytes[b] <= 0) return fail(c, FHIP_E_GENERIC, "a frame of the batch was not encoded");
+    if (c->verify) {
+        rc = verify_verdict(c, vj);
+        if (rc != FHIP_OK) return rc;
+    }
+    if (totals[1] > out_cap) return fail(c, FHIP_E_INVALID, "output buffer too small for the batch's frames");
+    HIP_TRY(c, hipMemcpy(out, c->d_packed, (size_t)totals[1], hipMemcpyDeviceToHost));
+    *out_bytes = totals[1];
+    return FHIP_OK;
+}
+
+int fhip_vbs_split_ragged(fhip_ctx *c, const int32_t *pcm, int nblocks, const int32_t *block_sizes, int32_t *frames,
+                          int32_t *sizes)
+{
+    long long total_n = 0;
+    int nmax = 0;
+    int rc = vbs_ragged_check(c, pcm, nblocks, block_sizes, frames && sizes, &total_n, &nmax);
+    if (rc != FHIP_OK) return rc;
+    if (nblocks == 0) return FHIP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    rc = ensure_staging(c, 0);
+    if (rc != FHIP_OK) return rc;
+    rc = vbs_ragged_stage(c, pcm, nblocks, block_sizes, (size_t)total_n * (size_t)c->p.channels);
+    if (rc != FHIP_OK) return rc;
+    // d_opt (>= max_frames ints) and d_shift (>= 32 * max_frames ints) are free before K2 runs
+    HIP_TRY(c, fhip::launch_vbs_split_ragged(c->stream, c->d_pcm, nblocks, c->rg_n(), c->rg_src(), c->p.channels, c->d_opt,
+                                             c->d_shift));
+    HIP_TRY(c, hipMemcpyAsync(frames, c->d_opt, (size_t)nblocks * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(sizes, c->d_shift, (size_t)nblocks * 8 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    return fhip_sync(c);
+}
+
 int fhip_set_block_numbering(fhip_ctx *c, int on)
 {
     if (!c) return FHIP_E_INVALID;
@@ -2253,6 +2462,47 @@ int fhip_verify_frames_blocks(fhip_ctx *c, const fhip_verify_in *in, const uint3
     j.in = *in; j.block_size = block_size;
     if (nblocks) { j.mode = VerifyJob::BLOCKS; j.nblocks = nblocks; j.host_block_first = block_first; }
     return verify_host(c, j, block_first, (size_t)nblocks, out);
+}
+
+int fhip_verify_frames_blocks_ragged_dev(fhip_ctx *c, const fhip_verify_in *in, const uint32_t *block_first, int nblocks,
+                                         const int64_t *block_start, const fhip_verify_out *out)
+{
+    int rc = verify_blocks_check(c, in, block_first, nblocks, c ? c->p.block_size : 1, out);
+    if (rc != FHIP_OK) return rc;
+    if (nblocks > 0 && !block_start) return fail(c, FHIP_E_INVALID, "null block table or negative count");
+    VerifyJob j;
+    j.in = *in; j.out = *out; j.block_size = c->p.block_size;
+    if (nblocks) {
+        j.mode = VerifyJob::BLOCKS; j.block_first = block_first; j.nblocks = nblocks;
+        j.block_start = reinterpret_cast<const long long *>(block_start);
+    }
+    return run_verify(c, j);
+}
+
+int fhip_verify_frames_blocks_ragged(fhip_ctx *c, const fhip_verify_in *in, const uint32_t *block_first, int nblocks,
+                                     const int32_t *block_sizes, const fhip_verify_out *out)
+{
+    int rc = verify_blocks_check(c, in, block_first, nblocks, c ? c->p.block_size : 1, out);
+    if (rc != FHIP_OK) return rc;
+    if (nblocks > 0 && !block_sizes) return fail(c, FHIP_E_INVALID, "null block table or negative count");
+    for (int b = 0; b < nblocks; b++)
+        if (block_sizes[b] < 1 || block_sizes[b] > c->p.block_size)
+            return fail(c, FHIP_E_INVALID, "block_sizes entry out of range");
+    VerifyJob j;
+    j.in = *in; j.block_size = c->p.block_size;
+    if (nblocks == 0) return verify_host(c, j, nullptr, 0, out);
+    // the tables as one: block_first, then the prefix sums of the lengths (8-byte aligned behind an even count)
+    const size_t nb = (size_t)nblocks, nb2 = (nb + 1) & ~(size_t)1;
+    std::vector<uint32_t> tab(nb2 + 2 * (nb + 1));
+    std::vector<long long> start(nb + 1);
+    for (size_t b = 0; b < nb; b++) {
+        tab[b] = block_first[b];
+        start[b + 1] = start[b] + block_sizes[b];
+    }
+    memcpy(&tab[nb2], start.data(), (nb + 1) * sizeof(long long));
+    j.mode = VerifyJob::BLOCKS; j.nblocks = nblocks;
+    j.host_block_first = block_first; j.host_block_start = start.data();
+    return verify_host(c, j, tab.data(), tab.size(), out);      // (tab and start live until its sync)
 }
 
 int fhip_last_verify_number(const fhip_ctx *c, uint32_t *number)

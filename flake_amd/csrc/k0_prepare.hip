@@ -181,17 +181,19 @@ void k_prepare_s16(const int16_t *__restrict__ pcm, int32_t *__restrict__ smp,
 __global__ __launch_bounds__(NT)
 void k_prepare_ragged(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp,
                       fhip_subframe_info *__restrict__ info, int bps, int estimate,
-                      const long long *__restrict__ frame_src, const int32_t *__restrict__ frame_n, int row_n)
+                      const long long *__restrict__ frame_src, const int32_t *__restrict__ frame_n, int row_n,
+                      const int32_t *__restrict__ dev_frames)
 {
-    prepare_lds_body<true, int32_t, true>(pcm, smp, info, 0, 2, bps, estimate, frame_src, nullptr, frame_n, row_n);
+    prepare_lds_body<true, int32_t, true>(pcm, smp, info, 0, 2, bps, estimate, frame_src, dev_frames, frame_n, row_n);
 }
 
 __global__ __launch_bounds__(NT)
 void k_prepare_ragged_s16(const int16_t *__restrict__ pcm, int32_t *__restrict__ smp,
                           fhip_subframe_info *__restrict__ info, int bps, int estimate,
-                          const long long *__restrict__ frame_src, const int32_t *__restrict__ frame_n, int row_n)
+                          const long long *__restrict__ frame_src, const int32_t *__restrict__ frame_n, int row_n,
+                          const int32_t *__restrict__ dev_frames)
 {
-    prepare_lds_body<true, int16_t, true>(pcm, smp, info, 0, 2, bps, estimate, frame_src, nullptr, frame_n, row_n);
+    prepare_lds_body<true, int16_t, true>(pcm, smp, info, 0, 2, bps, estimate, frame_src, dev_frames, frame_n, row_n);
 }
 
 // K0 for 1 or 3..8 channels (no decorrelation, encode.c:660-663): one
@@ -208,12 +210,12 @@ void prepare_multi_body(const S *__restrict__ pcm, int32_t *__restrict__ smp,
                         const int32_t *__restrict__ frame_n = nullptr, int row_n = 0)
 {
     const int row = RAGGED ? row_n : n;                  // (prepare_lds_body: the ragged instance)
-    if constexpr (RAGGED) n = frame_n[blockIdx.x];
     __shared__ int32_t s_tile[NT * (FHIP_MAX_CH + 1)];
     __shared__ uint32_t s_orr[4][FHIP_MAX_CH];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int f = blockIdx.x;
-    if (dev_frames && f >= dev_count(dev_frames, 0)) return;
+    if (dev_frames && f >= dev_count(dev_frames, 0)) return;          // (before any table entry is read)
+    if constexpr (RAGGED) n = frame_n[blockIdx.x];
     const S *src = pcm + (frame_src ? (size_t)frame_src[f] : (size_t)f * n * nch);
     const int stride = nch + 1;
     const int total = n * nch;
@@ -292,17 +294,19 @@ void k_prepare_multi_s16(const int16_t *__restrict__ pcm, int32_t *__restrict__ 
 __global__ __launch_bounds__(NT)
 void k_prepare_multi_ragged(const int32_t *__restrict__ pcm, int32_t *__restrict__ smp,
                             fhip_subframe_info *__restrict__ info, int nch, int bps,
-                            const long long *__restrict__ frame_src, const int32_t *__restrict__ frame_n, int row_n)
+                            const long long *__restrict__ frame_src, const int32_t *__restrict__ frame_n, int row_n,
+                            const int32_t *__restrict__ dev_frames)
 {
-    prepare_multi_body<int32_t, true>(pcm, smp, info, 0, nch, bps, frame_src, nullptr, frame_n, row_n);
+    prepare_multi_body<int32_t, true>(pcm, smp, info, 0, nch, bps, frame_src, dev_frames, frame_n, row_n);
 }
 
 __global__ __launch_bounds__(NT)
 void k_prepare_multi_ragged_s16(const int16_t *__restrict__ pcm, int32_t *__restrict__ smp,
                                 fhip_subframe_info *__restrict__ info, int nch, int bps,
-                                const long long *__restrict__ frame_src, const int32_t *__restrict__ frame_n, int row_n)
+                                const long long *__restrict__ frame_src, const int32_t *__restrict__ frame_n, int row_n,
+                                const int32_t *__restrict__ dev_frames)
 {
-    prepare_multi_body<int16_t, true>(pcm, smp, info, 0, nch, bps, frame_src, nullptr, frame_n, row_n);
+    prepare_multi_body<int16_t, true>(pcm, smp, info, 0, nch, bps, frame_src, dev_frames, frame_n, row_n);
 }
 
 // K0 for 1, 3 .. 8 channels with the frame in REGISTERS (round 2): k_prepare_multi above reads
@@ -1007,10 +1011,10 @@ hipError_t launch_prepare_ragged(hipStream_t st, const fhip_params &p, const int
         note_launch("k_prepare_multi%s ragged", s16 ? "_s16" : "");
         if (s16)
             hipLaunchKernelGGL(k_prepare_multi_ragged_s16, dim3(nframes), dim3(NT), 0, st, pcm16, smp, info, p.channels,
-                               p.bits_per_sample, rf.frame_src, rf.frame_n, rf.row_n);
+                               p.bits_per_sample, rf.frame_src, rf.frame_n, rf.row_n, rf.dev_frames);
         else
             hipLaunchKernelGGL(k_prepare_multi_ragged, dim3(nframes), dim3(NT), 0, st, pcm, smp, info, p.channels,
-                               p.bits_per_sample, rf.frame_src, rf.frame_n, rf.row_n);
+                               p.bits_per_sample, rf.frame_src, rf.frame_n, rf.row_n, rf.dev_frames);
         return hipGetLastError();
     }
     const size_t lds = sizeof(int32_t) * (size_t)rf.nmax * 2;
@@ -1022,13 +1026,13 @@ hipError_t launch_prepare_ragged(hipStream_t st, const fhip_params &p, const int
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (er != hipSuccess) return er;
         hipLaunchKernelGGL(k_prepare_ragged_s16, dim3(nframes), dim3(NT), lds, st, pcm16, smp, info, p.bits_per_sample,
-                           est, rf.frame_src, rf.frame_n, rf.row_n);
+                           est, rf.frame_src, rf.frame_n, rf.row_n, rf.dev_frames);
     } else {
         hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_prepare_ragged),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (er != hipSuccess) return er;
         hipLaunchKernelGGL(k_prepare_ragged, dim3(nframes), dim3(NT), lds, st, pcm, smp, info, p.bits_per_sample, est,
-                           rf.frame_src, rf.frame_n, rf.row_n);
+                           rf.frame_src, rf.frame_n, rf.row_n, rf.dev_frames);
     }
     return hipGetLastError();
 }

@@ -231,11 +231,13 @@ void k_autocorr(const int32_t *__restrict__ smp, double *__restrict__ autoc,
 // (n <= max_order) gets the autocorrelation of silence, 2.0, so that K2 reads defined values; K3 ignores its rows.
 __global__ __launch_bounds__(AC_WAVES * WAVE)
 void k_autocorr_ragged(const int32_t *__restrict__ smp, double *__restrict__ autoc, int nsub, int nch, int row_n,
-                       int maxlag, const int32_t *__restrict__ frame_n, const double *__restrict__ frame_c)
+                       int maxlag, const int32_t *__restrict__ frame_n, const double *__restrict__ frame_c,
+                       const int32_t *__restrict__ dev_sub)
 {
     __shared__ double s_buf[AC_WAVES][AC_HALO + AC_TILE];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int s = blockIdx.x * AC_WAVES + wv;
+    nsub = dev_count(dev_sub, nsub);              // (the live count of a batch whose pieces the device counted)
     if (s >= nsub) return;                        // whole wave idle (uniform)
     double *buf = s_buf[wv];
     const int f = s / nch;
@@ -1214,7 +1216,7 @@ hipError_t launch_autocorr_ragged(hipStream_t st, const int32_t *smp, int nsub, 
     if (!rf.frame_n || !rf.frame_c || max_order < 1 || max_order > FHIP_MAX_ORDER) return hipErrorInvalidValue;
     note_launch("k_autocorr ragged");
     hipLaunchKernelGGL(k_autocorr_ragged, dim3((nsub + AC_WAVES - 1) / AC_WAVES), dim3(AC_WAVES * WAVE), 0, st, smp,
-                       autoc, nsub, nch, rf.row_n, max_order, rf.frame_n, rf.frame_c);
+                       autoc, nsub, nch, rf.row_n, max_order, rf.frame_n, rf.frame_c, rf.dev_sub);
     return hipGetLastError();
 }
 

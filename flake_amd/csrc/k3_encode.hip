@@ -2350,7 +2350,7 @@ hipError_t launch_encode_ragged(hipStream_t st, const fhip_params &p, const int3
         note_launch("k_encode<%d> ragged", CC);                                              \
         hipLaunchKernelGGL((k_encode<CC, true>), dim3(nsub), dim3(NT), lds, st, p, 0, smp, coefs, shift, opt_order, \
                            info, prep, (int32_t *)nullptr, bits, (long long)slot_bytes, -1, 0, \
-                           (const int32_t *)nullptr, rf.frame_n, rf.row_n);                  \
+                           rf.dev_sub, rf.frame_n, rf.row_n);                                \
     } while (0)
     if (chunk <= 16) LAUNCH_ENCR(16);
     else if (chunk <= 32) LAUNCH_ENCR(32);

@@ -569,21 +569,20 @@ void k_assemble(fhip_params P, int n, const int32_t *__restrict__ pcm,
 // (int32 wrap, then abs), divided by the channel count, plus one; neighbours
 // are merged unless the score changes by more than 25 % -- evaluated with the
 // reference's int abs() and 32-bit multiply.
-__global__ __launch_bounds__(NT)
-void k_vbs_split(const int32_t *__restrict__ pcm, int nblocks, int block_size, int nch,
-                 int32_t *__restrict__ nframes_out, int32_t *__restrict__ sizes_out)
+// The scoring and the cuts of one block whose eighth is n sample-frames, by one workgroup.  vec16 (wave-uniform): the
+// stereo path's 16-byte loads -- every section of the block must then start 16-byte aligned (base aligned, n even).
+__device__ __forceinline__
+void vbs_split_block(const int32_t *__restrict__ base, int n, int nch, bool vec16, int b,
+                     int32_t *__restrict__ nframes_out, int32_t *__restrict__ sizes_out)
 {
     __shared__ long long s_score[8];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int b = blockIdx.x;
-    const int n = block_size / 8;
-    const int32_t *base = pcm + (size_t)b * block_size * nch;
     for (int sec = wv; sec < 8; sec += 4) {
         const int32_t *sp = base + (size_t)sec * n * nch;
         long long acc = 0;
         // element e of the section = (j, ch) interleaved; rows j >= 2 only
         const int total = (n - 2) * nch;
-        if (nch == 2 && (n & 1) == 0) {
+        if (vec16) {
             // stereo (sections of an even length: 16-byte aligned): four elements per lane and step from two aligned 16-byte loads (rows j-2 .. j+1 of
             // both channels); 2 n - 4 elements are whole groups of four
             for (int e = 4 * lane; e < total; e += 4 * WAVE) {
@@ -628,6 +627,41 @@ void k_vbs_split(const int32_t *__restrict__ pcm, int nblocks, int block_size, i
     }
 }
 
+__global__ __launch_bounds__(NT)
+void k_vbs_split(const int32_t *__restrict__ pcm, int nblocks, int block_size, int nch,
+                 int32_t *__restrict__ nframes_out, int32_t *__restrict__ sizes_out)
+{
+    const int b = blockIdx.x;
+    const int n = block_size / 8;
+    // (blocks of one length back to back from a 16-byte aligned pcm: even sections are aligned)
+    vbs_split_block(pcm + (size_t)b * block_size * nch, n, nch, nch == 2 && (n & 1) == 0, b, nframes_out, sizes_out);
+}
+
+// The ragged form: block b is block_n[b] samples at block_src[b] (interleaved values).  Only a block split_frame_v1
+// sees (a multiple of 8, at least 128: encode.c:997-999) is scored; any other is one piece.  Blocks lie back to back
+// at their own lengths, so a block starts at a multiple of 4 * channels bytes and no more: the load width is chosen per
+// block from its real address (one workgroup, one block: wave-uniform), and the 16-byte path is never taken from an
+// address that is not 16-byte aligned.
+__global__ __launch_bounds__(NT)
+void k_vbs_split_ragged(const int32_t *__restrict__ pcm, int nblocks, const int32_t *__restrict__ block_n,
+                        const long long *__restrict__ block_src, int nch,
+                        int32_t *__restrict__ nframes_out, int32_t *__restrict__ sizes_out)
+{
+    const int b = blockIdx.x;
+    if (b >= nblocks) return;
+    const int bn = __builtin_amdgcn_readfirstlane(block_n[b]);
+    if ((bn & 7) != 0 || bn < 128) {
+        if (threadIdx.x < 8) sizes_out[(size_t)b * 8 + threadIdx.x] = threadIdx.x == 0 ? bn : 0;
+        if (threadIdx.x == 0) nframes_out[b] = 1;
+        return;
+    }
+    const int n = bn >> 3;
+    const int32_t *base = pcm + block_src[b];
+    const bool vec16 = nch == 2 && (n & 1) == 0 &&
+                       __builtin_amdgcn_readfirstlane((int)(reinterpret_cast<uintptr_t>(base) & 15)) == 0;
+    vbs_split_block(base, n, nch, vec16, b, nframes_out, sizes_out);
+}
+
 }  // namespace
 
 hipError_t launch_vbs_split(hipStream_t st, const int32_t *pcm, int nblocks, int block_size,
@@ -636,6 +670,17 @@ hipError_t launch_vbs_split(hipStream_t st, const int32_t *pcm, int nblocks, int
     if (nblocks == 0) return hipSuccess;
     note_launch("k_vbs_split");
     hipLaunchKernelGGL(k_vbs_split, dim3(nblocks), dim3(NT), 0, st, pcm, nblocks, block_size, nch,
+                       nframes_out, sizes_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_vbs_split_ragged(hipStream_t st, const int32_t *pcm, int nblocks, const int32_t *block_n,
+                                   const long long *block_src, int nch, int32_t *nframes_out, int32_t *sizes_out)
+{
+    if (nblocks == 0) return hipSuccess;
+    if (!block_n || !block_src) return hipErrorInvalidValue;
+    note_launch("k_vbs_split ragged");
+    hipLaunchKernelGGL(k_vbs_split_ragged, dim3(nblocks), dim3(NT), 0, st, pcm, nblocks, block_n, block_src, nch,
                        nframes_out, sizes_out);
     return hipGetLastError();
 }
@@ -893,6 +938,87 @@ void k_vbs_plan(const int32_t *__restrict__ nfr, const int32_t *__restrict__ siz
     }
 }
 
+// k_vbs_plan for blocks of different lengths (kernels.h: launch_vbs_plan_ragged).  With a length per block there are
+// as many piece lengths as pieces and no bins: the pieces go to DENSE tables in stream order -- slot i is the i-th frame
+// of the batch's stream of frames -- one exclusive scan of the blocks' piece counts.  One workgroup; a thread owns one
+// block of every 1024.
+__global__ __launch_bounds__(PLAN_NT)
+void k_vbs_plan_ragged(const int32_t *__restrict__ nfr, const int32_t *__restrict__ sizes, int nblocks,
+                       const int32_t *__restrict__ block_n, const long long *__restrict__ block_src,
+                       const double *__restrict__ block_c, const uint32_t *__restrict__ block_first, int nch,
+                       long long frame_stride, int32_t *__restrict__ cnt, int32_t *__restrict__ frame_n,
+                       long long *__restrict__ frame_src, double *__restrict__ frame_c, uint32_t *__restrict__ numbers,
+                       int32_t *__restrict__ first, int32_t *__restrict__ order, long long *__restrict__ src_off)
+{
+    __shared__ int32_t s_wtot[PLAN_NT / 64 + 1];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int cap = 8 * nblocks;
+    int base = 0;
+    for (int b0 = 0; b0 < nblocks; b0 += PLAN_NT) {
+        const int b = b0 + tid;
+        const bool on = b < nblocks;
+        int f = 0, bn = 0;
+        int len[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) len[q] = 0;
+        if (on) {
+            f = min(nfr[b], 8);
+            bn = block_n[b];
+            const int4 s0 = *reinterpret_cast<const int4 *>(sizes + (size_t)b * 8);
+            const int4 s1 = *reinterpret_cast<const int4 *>(sizes + (size_t)b * 8 + 4);
+            len[0] = s0.x; len[1] = s0.y; len[2] = s0.z; len[3] = s0.w;
+            len[4] = s1.x; len[5] = s1.y; len[6] = s1.z; len[7] = s1.w;
+            if (f <= 1) { f = 1; len[0] = bn; }                  // left whole (vbs.c:100), or never split (encode.c:997-999)
+        }
+        const int incl = (int)wave_incl_scan_u32_dpp((uint32_t)f);
+        if (lane == 63) s_wtot[wv] = incl;
+        __syncthreads();
+        if (wv == 0) {
+            const int t = (lane < PLAN_NT / 64) ? s_wtot[lane] : 0;
+            const int sc = (int)wave_incl_scan_u32_dpp((uint32_t)t);
+            if (lane < PLAN_NT / 64) s_wtot[lane] = sc - t;
+            if (lane == PLAN_NT / 64 - 1) s_wtot[PLAN_NT / 64] = sc;
+        }
+        __syncthreads();
+        int run = base + s_wtot[wv] + incl - f;
+        base += s_wtot[PLAN_NT / 64];
+        if (on) {
+            first[b] = run;
+            const long long src0 = block_src[b];
+            const uint32_t bfirst = block_first[b];
+            const int eighth = max(bn >> 3, 1);
+            int pos = 0;
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                if (q < f && run < cap) {
+                    // a piece is m eighths of its block (the whole block: 8): the host's constant for that length
+                    const int m = (f == 1) ? 8 : min(max(len[q] / eighth, 1), 8);
+                    frame_n[run] = len[q];
+                    frame_src[run] = src0 + (long long)pos * nch;
+                    frame_c[run] = block_c[(size_t)b * 8 + (m - 1)];
+                    numbers[run] = bfirst + (uint32_t)pos;
+                    pos += len[q];
+                    run++;
+                }
+            }
+        }
+        __syncthreads();                     // s_wtot is written again by the next chunk
+    }
+    const int total = min(base, cap);
+    // every slot of the capacity is defined: the launches behind this one are sized for it, and although a workgroup
+    // past the count leaves before it reads a table, no slot ever holds garbage
+    for (int i = tid; i < cap; i += PLAN_NT) {
+        order[i] = i;
+        src_off[i] = (long long)i * frame_stride;
+        if (i >= total) { frame_n[i] = 1; frame_src[i] = 0; frame_c[i] = 0.0; numbers[i] = 0u; }
+    }
+    if (tid == 0) {
+        cnt[0] = total;
+        cnt[1] = total * nch;
+        first[nblocks] = total;
+    }
+}
+
 // Round 4: chunks of 4096 frames, four consecutive frames per thread (one 16-byte read of order[], four gathers in
 // flight), wave scans and one barrier per chunk -- a thread that walked nframes / 1024 consecutive frames by dependent
 // loads, twice, and a Hillis-Steele scan of twenty barriers took 70-92 us for the frames of 8192 blocks.
@@ -1031,6 +1157,21 @@ hipError_t launch_vbs_plan(hipStream_t st, const int32_t *nfr, const int32_t *si
         hipLaunchKernelGGL(k_vbs_plan<false>, dim3(1), dim3(PLAN_NT), 0, st, nfr, sizes, nblocks, block_size, nch,
                            first_number, bins, cnt, order, frame_src, src_off, numbers, first, block_first);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_vbs_plan_ragged(hipStream_t st, const int32_t *nfr, const int32_t *sizes, int nblocks,
+                                  const int32_t *block_n, const long long *block_src, const double *block_c,
+                                  const uint32_t *block_first, int nch, long long frame_stride, int32_t *cnt,
+                                  int32_t *frame_n, long long *frame_src, double *frame_c, uint32_t *numbers,
+                                  int32_t *first, int32_t *order, long long *src_off)
+{
+    if (nblocks == 0) return hipSuccess;
+    if (!block_n || !block_src || !block_c || !block_first) return hipErrorInvalidValue;
+    note_launch("k_vbs_plan ragged");
+    hipLaunchKernelGGL(k_vbs_plan_ragged, dim3(1), dim3(PLAN_NT), 0, st, nfr, sizes, nblocks, block_n, block_src,
+                       block_c, block_first, nch, frame_stride, cnt, frame_n, frame_src, frame_c, numbers, first,
+                       order, src_off);
     return hipGetLastError();
 }
 

@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "vbs_block_lookup.h"
 
 namespace fhip {
 namespace {
@@ -273,8 +274,9 @@ __device__ long long block_excl_scan(long long v, long long *scratch, int nwaves
     return base + incl - v;
 }
 
-// BLOCKS: the block-table mode (VerifyArgs.block_first), an instance of its own -- the other is the kernel as it was
-template <bool BLOCKS>
+// BLOCKS: the block-table mode (VerifyArgs.block_first), an instance of its own -- the other is the kernel as it was;
+// 2: the table's blocks differ in length (VerifyArgs.block_start), a third instance
+template <int BLOCKS>
 __global__ void __launch_bounds__(HDR_T) k_verify_frames(VerifyArgs a)
 {
     __shared__ long long scratch[HDR_T / 64];
@@ -288,7 +290,7 @@ __global__ void __launch_bounds__(HDR_T) k_verify_frames(VerifyArgs a)
         count = d < 0 ? 0 : (d < (long long)a.nframes ? (int)d : a.nframes);
     }
     const int t = threadIdx.x;
-    const bool numbered = !BLOCKS && a.numbers && !a.allow_vbs;      // a launch-wide choice: every wave takes one branch
+    const bool numbered = BLOCKS == 0 && a.numbers && !a.allow_vbs;      // a launch-wide choice: every wave takes one branch
     // block-table mode: the samples so far, and from bit BAD_SHIFT up the frames so far whose header did not parse
     // (a frame holds at most 65535 samples and a batch far fewer than 2^24 frames: the two never meet)
     constexpr int BAD_SHIFT = 40;
@@ -326,7 +328,7 @@ __global__ void __launch_bounds__(HDR_T) k_verify_frames(VerifyArgs a)
         // (fixed blocks of many streams) frame f carries numbers[f] and its samples lie at f * block_size of pcm:
         // nothing of a neighbouring frame is read
         const unsigned long long snum = a.allow_vbs ? h.number : h.number * (unsigned long long)a.block_size;
-        if constexpr (!BLOCKS) {
+        if constexpr (BLOCKS == 0) {
             s_next[t] = snum + (unsigned long long)h.n;
             s_ok[t] = h.status == FHIP_VERIFY_OK || h.status == FHIP_VERIFY_CRC8;
         }
@@ -334,7 +336,7 @@ __global__ void __launch_bounds__(HDR_T) k_verify_frames(VerifyArgs a)
         // block-table mode: a frame starts where the frames before it end -- the exclusive scan of their header-parsed
         // sizes, as a sequential decoder counts -- and a frame behind one whose header did not parse cannot be placed
         long long S = 0;
-        if constexpr (BLOCKS) {
+        if constexpr (BLOCKS != 0) {
             const bool parsed = live && (h.status == FHIP_VERIFY_OK || h.status == FHIP_VERIFY_CRC8);
             long long stot = 0;
             S = sbase + block_excl_scan(parsed ? (long long)h.n : (live ? 1ll << BAD_SHIFT : 0ll), scratch, HDR_T / 64, &stot);
@@ -343,17 +345,27 @@ __global__ void __launch_bounds__(HDR_T) k_verify_frames(VerifyArgs a)
         if (live && (h.status == FHIP_VERIFY_OK || h.status == FHIP_VERIFY_CRC8)) {
             long long rel;
             bool num_ok, cover_ok;
-            if constexpr (BLOCKS) {
+            if constexpr (BLOCKS != 0) {
                 // the frame lies in block S / block_size at offset S % block_size; the table says what the first
                 // sample of that block is called in its own stream.  Only the sample count so far crosses frames.
                 const bool placeable = (S >> BAD_SHIFT) == 0;
                 S &= (1ll << BAD_SHIFT) - 1;
-                const long long blk = S / a.block_size;
-                const int off = (int)(S - blk * a.block_size);
+                long long blk, bstart, blen = a.block_size;
+                if constexpr (BLOCKS == 2) {
+                    // a length per block: the block is found in the prefix sums of the lengths (vbs_block_lookup.h)
+                    blk = fhip_block_lookup(a.block_start, a.nblocks, S);
+                    const long long bq = blk < (long long)a.nblocks ? blk : 0;      // (an index inside the table either way)
+                    bstart = a.block_start[bq];
+                    blen = a.block_start[bq + 1] - bstart;
+                } else {
+                    blk = S / a.block_size;
+                    bstart = blk * a.block_size;
+                }
+                const int off = (int)(S - bstart);
                 const bool placed = placeable && blk < (long long)a.nblocks;
                 rel = S;
                 num_ok = !placed || h.number == (unsigned long long)(uint32_t)(a.block_first[blk] + (uint32_t)off);
-                cover_ok = placed && off + h.n <= a.block_size && (f != count - 1 || S + h.n == a.nsamples);
+                cover_ok = placed && off + h.n <= blen && (f != count - 1 || S + h.n == a.nsamples);
             } else if (numbered) {
                 // every frame is a whole block of its own stream: the table says which, the batch says where
                 // (ragged: the tables say where and how long; frame_src counts interleaved values)
@@ -810,12 +822,15 @@ __global__ void k_verify_final(VerifyArgs a)
 
 hipError_t launch_verify(hipStream_t st, const VerifyArgs &a)
 {
-    if (a.block_first && a.allow_vbs) {
+    if (a.block_first && a.block_start && a.allow_vbs && a.nblocks > 0) {
+        note_launch("k_verify_frames<blocks ragged>");
+        hipLaunchKernelGGL(k_verify_frames<2>, dim3(1), dim3(HDR_T), 0, st, a);
+    } else if (a.block_first && a.allow_vbs) {
         note_launch("k_verify_frames<blocks>");
-        hipLaunchKernelGGL(k_verify_frames<true>, dim3(1), dim3(HDR_T), 0, st, a);
+        hipLaunchKernelGGL(k_verify_frames<1>, dim3(1), dim3(HDR_T), 0, st, a);
     } else {
         note_launch("k_verify_frames");
-        hipLaunchKernelGGL(k_verify_frames<false>, dim3(1), dim3(HDR_T), 0, st, a);
+        hipLaunchKernelGGL(k_verify_frames<0>, dim3(1), dim3(HDR_T), 0, st, a);
     }
     if (a.nframes > 0) {
         note_launch("k_verify");

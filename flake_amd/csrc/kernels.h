@@ -38,6 +38,10 @@ struct RaggedFrames {
     const long long *frame_src;
     const double *frame_c;
     int row_n, nmax;
+    // optional: the launch's real frame / subframe count lives on the device (the pieces of a ragged variable-block-size
+    // batch, k_vbs_plan_ragged); nframes / nsub then size the grid, and a workgroup or wave at or past the count leaves
+    // before it reads a table entry.  Null: the launch as it was.
+    const int32_t *dev_frames = nullptr, *dev_sub = nullptr;
 };
 hipError_t launch_prepare_ragged(hipStream_t st, const fhip_params &p, const int32_t *pcm, int nframes,
                                  const RaggedFrames &rf, int32_t *smp, fhip_subframe_info *info, int pcm_format);
@@ -236,6 +240,24 @@ hipError_t launch_vbs_block_bytes(hipStream_t st, const int32_t *first, const lo
 hipError_t launch_vbs_split(hipStream_t st, const int32_t *pcm, int nblocks, int block_size,
                             int nch, int32_t *nframes_out, int32_t *sizes_out);
 
+// The same for blocks of DIFFERENT lengths (the tails of many streams): block b is block_n[b] samples at block_src[b]
+// (interleaved values into pcm; device tables).  A block with n % 8 == 0 && n >= 128 is scored and cut as above (the
+// eighth is n / 8); any other is one piece (encode.c:997-999): nframes 1, sizes {n, 0 ...}.
+hipError_t launch_vbs_split_ragged(hipStream_t st, const int32_t *pcm, int nblocks, const int32_t *block_n,
+                                   const long long *block_src, int nch, int32_t *nframes_out, int32_t *sizes_out);
+// The piece tables of such a batch, dense and in stream order (piece i of the batch = the i-th frame of the stream of
+// frames): frame_n / frame_src / frame_c as RaggedFrames takes them, numbers[i] = block_first[b] + the piece's offset in
+// its block (uint32 wrap), first[b] = index of block b's first piece (first[nblocks] = pieces in all), cnt[0] / cnt[1] =
+// live pieces / subframes.  block_c [nblocks][8]: the window constant of lpc.c:34 for m eighths of block b at [m - 1]
+// (the whole block at [7], whatever its length), computed on the host; the kernel picks, it never divides.  All `cap`
+// (= 8 * nblocks) slots of the piece tables are written -- the dead ones as one-sample pieces at offset 0 -- and
+// order[i] = i, src_off[i] = i * frame_stride, so that launch_pack_frames_perm packs the slots as they lie.
+hipError_t launch_vbs_plan_ragged(hipStream_t st, const int32_t *nfr, const int32_t *sizes, int nblocks,
+                                  const int32_t *block_n, const long long *block_src, const double *block_c,
+                                  const uint32_t *block_first, int nch, long long frame_stride, int32_t *cnt,
+                                  int32_t *frame_n, long long *frame_src, double *frame_c, uint32_t *numbers,
+                                  int32_t *first, int32_t *order, long long *src_off);
+
 // Dynamic-LDS need of K3 for a block size (0 if unsupported).
 size_t encode_lds_bytes(int n);
 
@@ -274,6 +296,9 @@ struct VerifyArgs {
     // block_first[b] + off.  first_sample is unused then.
     const uint32_t *block_first = nullptr;       // optional [nblocks]
     int nblocks = 0;
+    // ... with a length per block: block b covers samples block_start[b] .. block_start[b + 1] of the batch (prefix sums,
+    // [nblocks + 1]); a frame's block is found by search (vbs_block_lookup.h) where the uniform mode divides
+    const long long *block_start = nullptr;
 };
 hipError_t launch_verify(hipStream_t st, const VerifyArgs &a);
 

@@ -18,6 +18,8 @@
  * several frames and a short block ends nothing (encode.c:993).  Blocks the splitter takes (a multiple of 8, at least
  * 128 samples: encode.c:997-999) go through fhip_encode_blocks_vbs_packed_numbered with each block's first-sample
  * number; every other length goes through the packed path as one frame per block, with fhip_set_block_numbering on.
+ * The short blocks of a flake_amd_set_encode_ragged call -- splittable or not, each of its own length -- go through
+ * fhip_encode_blocks_vbs_ragged_numbered, one device batch per FLAKE_AMD_BATCH of them.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -37,6 +39,7 @@ struct FlakeAmdSet {
     int pcm_format;
     int verbatim_size;                    /* of a full block: where max_frame_size starts (encode.c:446-450) */
     int broken;                           /* a device call failed half way: the streams' state is unknown */
+    long long device_batches;             /* chunks handed to an encode entry of the HIP layer since the set was opened */
     int vfail, vfail_stream, vfail_status; /* flake_amd_set_last_verify_failure: the last encode call's, if any */
     unsigned vfail_number;
     /* per stream */
@@ -153,6 +156,8 @@ FLAKE_AMD_API FlakeAmdSet *flake_amd_set_open(const FlakeAmdContext *like, int n
     return g;
 #undef OPEN_FAIL
 }
+
+FLAKE_AMD_API long long flake_amd_set_device_batches(const FlakeAmdSet *g) { return g ? g->device_batches : -1; }
 
 FLAKE_AMD_API int flake_amd_set_enable_verify(FlakeAmdSet *g, int on)
 {
@@ -296,6 +301,7 @@ FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples
             rc = fhip_md5_update_uploaded(g->hip, g->dev_md5, g->nstreams, cnt, block_size, (const int32_t *)first, g->seg_block);
         }
         int64_t bytes = 0;
+        if (rc == FHIP_OK) g->device_batches++;
         if (rc == FHIP_OK && split) {
             /* split, encoded and packed on the device, block b numbered from its stream's sample count; the bytes
              * come back before the call returns (no download beside the next chunk's upload on this path) */
@@ -355,7 +361,9 @@ FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples
 
 /* The short blocks of a call through the ragged packed path: cnt blocks back to back, block b sizes[b] samples long
  * (every one shorter than the set's block size, one per stream: the caller has checked).  The twin of the loop in
- * flake_amd_set_encode.  Returns the bytes written, -1 on an error, or -2 when the ABI does not cover this handle
+ * flake_amd_set_encode.  With variable block size the chunk goes through fhip_encode_blocks_vbs_ragged_numbered
+ * instead: a block may become several frames, is numbered from its stream's sample count and ends nothing
+ * (encode.c:993); the bytes come back before the call returns, as on that path of flake_amd_set_encode.  Returns the bytes written, -1 on an error, or -2 when the ABI does not cover this handle
  * (FHIP_E_UNSUPPORTED on the first chunk: nothing has changed, the caller takes the per-length calls). */
 static long long set_encode_short(FlakeAmdSet *g, const void *samples, int sample_bytes, int cnt_all, const int *sizes,
                                   const int *stream_of_block, unsigned char *out, size_t out_size, int *frame_sizes)
@@ -403,6 +411,18 @@ static long long set_encode_short(FlakeAmdSet *g, const void *samples, int sampl
                                                  (const int32_t *)first, g->seg_block);
         }
         int64_t bytes = 0;
+        if (rc == FHIP_OK) g->device_batches++;
+        if (rc == FHIP_OK && g->vbs) {
+            what = "fhip_encode_blocks_vbs_ragged_numbered";
+            rc = fhip_encode_blocks_vbs_ragged_numbered(g->hip, bt.pcm, cnt, (const int32_t *)(sizes + b0), g->fnum + b0,
+                                                        out + total, (int64_t)(out_size - (size_t)total), g->fbytes + b0,
+                                                        g->bframes + b0, g->bmax + b0, &bytes);
+            /* (the verifier's frame index counts the chunk's FRAMES: block_frames says which block it lies in) */
+            if (rc == FHIP_E_VERIFY) return set_verify_failed(g, what, stream_of_block, b0, cnt, g->bframes + b0, 1);
+            if (rc == FHIP_OK) total += bytes;
+            pcm += chunk_samples * vbytes;
+            continue;
+        }
         if (rc == FHIP_OK) {
             what = "fhip_frames_packed_begin_ragged";
             rc = fhip_frames_packed_begin_ragged(g->hip, &bt, (const int32_t *)(sizes + b0), &bytes);
@@ -434,11 +454,12 @@ static long long set_encode_short(FlakeAmdSet *g, const void *samples, int sampl
         const int s = stream_of_block[b], fs = g->fbytes[b];
         const size_t nvals = (size_t)sizes[b] * (size_t)g->hp.channels;
         if (frame_sizes) frame_sizes[b] = fs;
-        if (fs > g->max_frame[s]) g->max_frame[s] = fs;
+        const int largest = g->vbs ? g->bmax[b] : fs;                       /* of the block's frames */
+        if (largest > g->max_frame[s]) g->max_frame[s] = largest;           /* encode.c:967 */
         if (!g->min_frame[s] || fs < g->min_frame[s]) g->min_frame[s] = fs;
-        g->frame_count[s]++;
+        g->frame_count[s] += g->vbs ? (uint32_t)sizes[b] : 1u;              /* encode.c:969-975 */
         g->samples[s] += (uint64_t)sizes[b];
-        g->ended[s] = 1;
+        if (!g->vbs) g->ended[s] = 1;                                       /* (allow_vbs: no latch, encode.c:993) */
         if (g->host_md5) {
             if (sample_bytes == 2) fa_md5_pcm16(&g->host_md5[s], (const int16_t *)pcm, nvals, g->hp.bits_per_sample);
             else fa_md5_pcm(&g->host_md5[s], (const int32_t *)pcm, nvals, g->hp.bits_per_sample);
@@ -467,6 +488,8 @@ FLAKE_AMD_API long long flake_amd_set_encode_ragged(FlakeAmdSet *g, const void *
     if (sample_bytes != 4 && sample_bytes != 2) SET_FAIL("flake_amd_set_encode_ragged: sample_bytes must be 4 or 2");
     if (sample_bytes == 2 && g->hp.bits_per_sample > 16)
         SET_FAIL("flake_amd_set_encode_ragged: int16 samples need bits_per_sample <= 16");
+    if (sample_bytes == 2 && g->vbs)
+        SET_FAIL("flake_amd_set_encode_ragged: int16 samples are not supported with variable block size (levels 9-12)");
     if (nblocks == 0) return 0;
     /* everything is checked before anything changes */
     const int full = g->hp.block_size;
@@ -484,7 +507,7 @@ FLAKE_AMD_API long long flake_amd_set_encode_ragged(FlakeAmdSet *g, const void *
     if (nshort == 0)
         return flake_amd_set_encode(g, samples, sample_bytes, nblocks, full, stream_of_block, out, out_size, frame_sizes);
     const char *er = getenv("FLAKE_AMD_SET_RAGGED");
-    int ragged = !(er && er[0] == '0') && !g->vbs;       /* (no ragged kernel path for variable block size) */
+    int ragged = !(er && er[0] == '0');
     if (ragged && nshort == nblocks) {
         const long long r = set_encode_short(g, samples, sample_bytes, nblocks, block_sizes, stream_of_block, out, out_size, frame_sizes);
         if (r != -2) return r;

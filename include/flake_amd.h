@@ -168,8 +168,10 @@ FLAKE_AMD_API const char *flake_amd_last_error(const FlakeAmdContext *s);
  * -1).  A block_size that is a multiple of 8 and at least 128 is split on the device
  * (fhip_encode_blocks_vbs_packed_numbered); any other length is one frame per block.  All three MD5 modes and
  * verification work; on a verification failure flake_amd_set_last_verify_failure gives the failing frame's stream
- * and FIRST-SAMPLE number.  flake_amd_set_encode_ragged keeps its argument rules and takes one call per distinct
- * length.  The handle is sized for FLAKE_AMD_BATCH * 8 frames, as flake_amd_encode_init sizes it.  Measured per
+ * and FIRST-SAMPLE number.  flake_amd_set_encode_ragged keeps its argument rules; the short blocks of a call, each
+ * of its own length, run as one device batch per FLAKE_AMD_BATCH of them (fhip_encode_blocks_vbs_ragged_numbered:
+ * split where the splitter sees them, numbered from their streams' sample counts; FLAKE_AMD_SET_RAGGED=0 keeps one
+ * call per distinct length, as do set block sizes above 16384).  The handle is sized for FLAKE_AMD_BATCH * 8 frames, as flake_amd_encode_init sizes it.  Measured per
  * 4096 blocks of 4096 stereo 16-bit samples (tools/set_vbs_bench.py): 5.8 ms at level 10 and 8.0 ms
  * at level 12 over 4096 streams, against 78 ms for one stream with its host MD5.
  */
@@ -229,6 +231,10 @@ FLAKE_AMD_API int flake_amd_set_get_streaminfo(FlakeAmdSet *g, int stream, Flake
  * NULL); 0 otherwise, outputs untouched -- so that a caller can decide per file without parsing text.
  */
 FLAKE_AMD_API int flake_amd_set_enable_verify(FlakeAmdSet *g, int on);
+/* A diagnostic: how many device batches the set has run since it was opened -- one per chunk (at most FLAKE_AMD_BATCH
+ * blocks) handed to an encode entry of the HIP layer, whichever entry.  Closing S streams with distinct tails adds
+ * ceil(S / FLAKE_AMD_BATCH) through the ragged paths and about S under FLAKE_AMD_SET_RAGGED=0.  -1 without a set. */
+FLAKE_AMD_API long long flake_amd_set_device_batches(const FlakeAmdSet *g);
 FLAKE_AMD_API int flake_amd_set_last_verify_failure(const FlakeAmdSet *g, int *stream, unsigned *frame_number,
                                                     int *status);
 FLAKE_AMD_API const char *flake_amd_set_last_error(const FlakeAmdSet *g);

@@ -235,9 +235,12 @@ FHIP_API int fhip_frames_packed_fetch_wait(fhip_ctx *ctx);
  * per-frame length table on the device ("ragged" in fhip_last_launches); device slots keep the stride of
  * params.block_size.  While fhip_set_verify is on, frame f must carry its number and hold exactly block_sizes[f]
  * samples (fhip_verify_frames_ragged).  Both PCM formats are honoured (int16 blocks may start at any 2-byte
- * boundary).  FHIP_E_UNSUPPORTED on a handle with allow_vbs, or with params.block_size > 16384 (callers fall back to
- * one uniform call per length); FHIP_E_INVALID for a bad table, with nothing queued.  The fetch steps are
- * fhip_frames_packed_fetch*.  _upload_ragged is the optional first step, as fhip_frames_packed_upload is.
+ * boundary).  _begin_ragged returns FHIP_E_UNSUPPORTED on a handle with allow_vbs (its ragged batches go through
+ * fhip_encode_blocks_vbs_ragged_numbered below), and both entries with params.block_size > 16384 (callers fall back
+ * to one uniform call per length); FHIP_E_INVALID for a bad table, with nothing queued.  The fetch steps are
+ * fhip_frames_packed_fetch*.  _upload_ragged is the optional first step, as fhip_frames_packed_upload is; on a handle
+ * with allow_vbs it takes int32 PCM only (FHIP_E_UNSUPPORTED under FHIP_PCM_S16) and at most max_frames / 8 blocks,
+ * and what it brings is encoded by fhip_encode_blocks_vbs_ragged_numbered.
  */
 FHIP_API int fhip_frames_packed_upload_ragged(fhip_ctx *ctx, const fhip_batch *b, const int32_t *block_sizes);
 FHIP_API int fhip_frames_packed_begin_ragged(fhip_ctx *ctx, const fhip_batch *b, const int32_t *block_sizes,
@@ -323,6 +326,32 @@ FHIP_API int fhip_encode_blocks_vbs_packed_numbered(fhip_ctx *ctx, const int32_t
                                                     int32_t *block_bytes, int32_t *block_frames,
                                                     int32_t *block_max_frame, int64_t *out_bytes);
 /*
+ * The same for blocks of DIFFERENT lengths -- the last blocks of many streams at levels 9-12 -- in ONE batch:
+ * block_sizes is a HOST table [nblocks], every entry in 1 .. params.block_size, pcm the blocks back to back at their own
+ * lengths.  A block split_frame_v1 sees (a multiple of 8, at least 128 samples: encode.c:997-999) is scored and cut on
+ * the device, its eighth being its own length / 8; any other block is one frame.  The pieces go to dense tables in stream
+ * order on the device (length, offset, window constant, number), their count stays there, and the ragged generic
+ * kernels ("ragged" in fhip_last_launches; every order method in-kernel) run once over a grid sized for 8 * nblocks
+ * frames -- no bins, no host synchronisation between the split and the pack.
+ *   The contract: the bytes and the three per-block records of block b are exactly what the existing entries write for
+ *   that block alone -- fhip_encode_blocks_vbs_packed_numbered with one block of that length where the splitter sees it,
+ *   fhip_frames_packed_begin under fhip_set_block_numbering(1) with frame_numbers = {block_first[b]} otherwise -- and do
+ *   not depend on the block's position or its neighbours in the call.
+ * It consumes a pending fhip_frames_packed_upload_ragged of the same pcm / nblocks / block_sizes, so that
+ * fhip_md5_update_uploaded_ragged between the two runs K6 beside the encode kernels.  While fhip_set_verify is on, the
+ * stream is verified in the ragged block-table mode (fhip_verify_frames_blocks_ragged) before the call returns:
+ * FHIP_E_VERIFY with nothing copied to `out`; fhip_last_verify_failure and fhip_last_verify_number as for the entry above.
+ * Refused, with nothing launched and the handle still usable: a handle without variable block size, a size of 0 or above
+ * params.block_size, 8 * nblocks > max_frames, a null argument (block_frames and block_max_frame are optional):
+ * FHIP_E_INVALID; FHIP_PCM_S16 (int32 only, as every variable-block-size entry) and params.block_size > 16384 (the
+ * ragged K3's limit: callers fall back to one call per length): FHIP_E_UNSUPPORTED.  An out_cap that is too small:
+ * FHIP_E_INVALID after the batch has run, nothing written, as for the entry above.
+ */
+FHIP_API int fhip_encode_blocks_vbs_ragged_numbered(fhip_ctx *ctx, const int32_t *pcm, int nblocks,
+                                                    const int32_t *block_sizes, const uint32_t *block_first,
+                                                    uint8_t *out, int64_t out_cap, int32_t *block_bytes,
+                                                    int32_t *block_frames, int32_t *block_max_frame, int64_t *out_bytes);
+/*
  * Off by default; FHIP_E_UNSUPPORTED on a handle without allow_vbs.  While on, fhip_batch.frame_numbers of
  * fhip_frames_packed_begin (and fhip_encode_frames_packed) are the first-sample numbers of ONE-FRAME BLOCKS OF
  * INDEPENDENT STREAMS: K4 writes whatever the table holds, as before, and verification (fhip_set_verify) holds frame
@@ -394,6 +423,12 @@ FHIP_API int fhip_calc_rice_params(fhip_ctx *ctx, const int32_t *residual, int n
  * sizes [nblocks][8] exactly as the reference computes them. */
 FHIP_API int fhip_vbs_split(fhip_ctx *ctx, const int32_t *pcm, int nblocks, int block_size,
                             int32_t *frames, int32_t *sizes);
+/* The same for blocks of different lengths back to back (block_sizes: HOST [nblocks], 1 .. params.block_size), as
+ * fhip_encode_blocks_vbs_ragged_numbered splits them: a block of a multiple of 8 and at least 128 samples as above
+ * with its own eighth, any other one frame of its length (frames[b] = 1, sizes[b] = {n, 0, ...}).  The checks and
+ * refusals are that entry's. */
+FHIP_API int fhip_vbs_split_ragged(fhip_ctx *ctx, const int32_t *pcm, int nblocks, const int32_t *block_sizes,
+                                   int32_t *frames, int32_t *sizes);
 
 /* copy_samples + channel_decorrelation + remove_wasted_bits,
  * encode.c:541-694, for nframes blocks; fills info[].obits/wasted/ch_mode. */
@@ -507,6 +542,20 @@ FHIP_API int fhip_verify_frames_blocks_dev(fhip_ctx *ctx, const fhip_verify_in *
                                            int nblocks, int block_size, const fhip_verify_out *out);
 FHIP_API int fhip_verify_frames_blocks(fhip_ctx *ctx, const fhip_verify_in *in, const uint32_t *block_first,
                                        int nblocks, int block_size, const fhip_verify_out *out);
+/*
+ * The block-table mode with a LENGTH PER BLOCK (the batch of fhip_encode_blocks_vbs_ragged_numbered): block b is
+ * block_sizes[b] samples (1 .. params.block_size) and starts at start[b], the sum of the lengths before it.  Frame f
+ * starts at S_f as above; it lies in the block b with start[b] <= S_f < start[b + 1] -- a search where the uniform mode
+ * divides -- and must carry (uint32)(block_first[b] + S_f - start[b]) (FHIP_VERIFY_NUMBER at bit 32), end inside that
+ * block, lie in a block of the table and, the last frame, end at in->nsamples (FHIP_VERIFY_NUMBER at bit 16).  Every
+ * other status and the rule for frames behind an unparsable one are the uniform mode's.  The host form takes a HOST
+ * block_sizes [nblocks] (an entry out of range: FHIP_E_INVALID); the _dev form takes block_start, the prefix sums
+ * themselves as DEVICE int64 [nblocks + 1] (block_start[0] = 0), beside a device block_first.
+ */
+FHIP_API int fhip_verify_frames_blocks_ragged_dev(fhip_ctx *ctx, const fhip_verify_in *in, const uint32_t *block_first,
+                                                  int nblocks, const int64_t *block_start, const fhip_verify_out *out);
+FHIP_API int fhip_verify_frames_blocks_ragged(fhip_ctx *ctx, const fhip_verify_in *in, const uint32_t *block_first,
+                                              int nblocks, const int32_t *block_sizes, const fhip_verify_out *out);
 
 /*
  * Verification of the handle's own output, off by default.  While on:
@@ -520,7 +569,8 @@ FHIP_API int fhip_verify_frames_blocks(fhip_ctx *ctx, const fhip_verify_in *in, 
  *   the frames must count up from first_frame_number.  A variable-block-size batch is verified in sequence either way,
  *   unless fhip_set_block_numbering is on (block-table mode, one frame per block); fhip_encode_blocks_vbs_packed_numbered
  *   is verified in the block-table mode.
- *   fhip_frames_packed_begin_ragged is verified with the semantics of fhip_verify_frames_ragged.
+ *   fhip_frames_packed_begin_ragged is verified with the semantics of fhip_verify_frames_ragged,
+ *   fhip_encode_blocks_vbs_ragged_numbered with those of fhip_verify_frames_blocks_ragged.
  */
 FHIP_API int fhip_set_verify(fhip_ctx *ctx, int on);
 /* What the most recent host-synchronising verification of this handle found (fhip_verify_frames, _numbered, and the
@@ -588,7 +638,8 @@ FHIP_API int fhip_md5_update_uploaded(fhip_ctx *ctx, fhip_md5_state *states, int
 
 /* The same for a ragged upload (fhip_frames_packed_upload_ragged): block b of the tables is the upload's b-th
  * block, block_sizes[b] samples long; nblocks and block_sizes (HOST) must match that upload.  Always the general
- * path ("ragged general" in fhip_last_launches). */
+ * path ("ragged general" in fhip_last_launches).  Handles with allow_vbs included (the upload that
+ * fhip_encode_blocks_vbs_ragged_numbered then consumes). */
 FHIP_API int fhip_md5_update_uploaded_ragged(fhip_ctx *ctx, fhip_md5_state *states, int nstreams, int nblocks,
                                              const int32_t *block_sizes, const int32_t *seg_first,
                                              const int32_t *seg_block);
