@@ -229,6 +229,7 @@ def load_library() -> C.CDLL:
         "fhip_verify_frames_blocks_ragged": (i, [vp, C.POINTER(VerifyIn), vp, i, vp, C.POINTER(VerifyOut)]),
         "fhip_device_alloc": (vp, [C.c_size_t]),
         "fhip_device_free": (None, [vp]),
+        "fhip_autocorr_tile": (i, [i, i, i]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -258,6 +259,7 @@ ABI_SYMBOLS = (
     "fhip_verify_frames_blocks", "fhip_last_verify_number",
     "fhip_encode_blocks_vbs_ragged_numbered", "fhip_vbs_split_ragged", "fhip_verify_frames_blocks_ragged_dev",
     "fhip_verify_frames_blocks_ragged",
+    "fhip_autocorr_tile",
 )
 
 

@@ -563,6 +563,37 @@ constexpr int WT_NBUF = 3;
 #endif
 constexpr int WT_AHEAD = FHIP_WT_AHEAD;              // tiles of loads in flight per producer
 
+// The long-tile form (k_autocorr_wtl, n % 256 == 0): 256 positions per hand-over on a ring of TWO
+// buffers.  The hand-over (the workgroup barrier and, behind it, four consumers restarting their LDS
+// pipelines at once) costs ~400 cycles whatever the producers do (profiles/r06_k1_tuning.txt), so it is
+// paid half as often.  Two buffers are enough because the producers no longer store the next tile's
+// halo when it is produced (that buffer is the one being walked): the last 32 positions of a tile stay
+// in the registers of the lanes that produced them, across the barrier, and are stored at the start of
+// the next tile's production, into the buffer being filled.  So during walk t every store goes to
+// buffer (t + 1) % 2, and the consumers finished with that buffer -- walk t - 1 -- before barrier t;
+// the stores of walk t + 1's buffer wait behind barrier t + 1, which the consumers reach after walk t.
+// A tile is staged as two 128-position passes with the 128 form's lane-to-position map (the seam needs
+// no halo: the parity arrays are contiguous), loads are counted in 128-position passes, four in flight
+// (the 128 form: three), and the producers' loop is unrolled by two tiles, one per buffer.
+// Per subframe and parity [16 halo][128 body][2 pad] = 146 doubles, subframe stride 294:
+// 2 x 32 x 294 x 8 = 150 528 B, with acbuf 158 976 B of the 163 840 B a workgroup may have.
+template <int TL>
+struct wt_geo {
+    static_assert(TL == AC_TILE || TL == 2 * AC_TILE, "tile length");
+    static constexpr int HALF = TL / 2;                          // steps per tile and parity
+    static constexpr int ROW = PS_HH + HALF + 2;                 // doubles per parity array
+    static constexpr int STRIDE = 2 * ROW + 2;                   // per subframe
+    static constexpr int BUF = WT_SUB * STRIDE;                  // doubles per tile buffer
+    static constexpr int NBUF = (TL == AC_TILE) ? WT_NBUF : 2;
+    static constexpr int UNITS = TL / AC_TILE;                   // 128-position passes per tile
+    static constexpr int AHEAD = (TL == AC_TILE) ? WT_AHEAD : 4; // passes of loads in flight per producer
+    static constexpr int UT = AHEAD / UNITS;                     // tiles per trip of the producers' unrolled loop
+    static_assert(ROW % 2 == 0 && STRIDE % 4 == 2, "16-byte aligned arrays, odd slot stride");
+    static_assert(AHEAD % UNITS == 0 && (TL == AC_TILE || UT % NBUF == 0), "whole tiles per trip");
+};
+static_assert(wt_geo<AC_TILE>::ROW == WT_ROW && wt_geo<AC_TILE>::BUF == WT_BUF, "the 128 form's geometry");
+constexpr int WTL_TILE = 2 * AC_TILE;
+
 struct wt_groups { int l0[4]; int nch[4]; };
 
 // FUSED: the producers read the interleaved stereo PCM instead of smp, apply the
@@ -600,16 +631,21 @@ __device__ __forceinline__ void lpc_reg_one(const double (&ac)[MO + 1], int s, i
                                             int32_t *__restrict__ shift, int32_t *__restrict__ opt_order,
                                             int32_t *__restrict__ fin);
 
-template <int NCH, bool FUSED, int LPCMO>
-__global__ __launch_bounds__(8 * WAVE)
-void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
-                   int nsub, int n, int maxlag, wt_groups grp, double c,
-                   const int32_t *__restrict__ pcm, int32_t *__restrict__ smp_out,
-                   const fhip_subframe_info *__restrict__ info, wt_lpc_args lpc, int narrow_ok,
-                   const int32_t *__restrict__ dev_sub, MultiBin mb, wt_groups grp1, int lsplit)
+// The body of both forms: TL = positions per hand-over (128: k_autocorr_wt, 256: k_autocorr_wtl).
+template <int NCH, bool FUSED, int LPCMO, int TL>
+__device__ __forceinline__
+void wt_body(const int32_t *__restrict__ smp, double *__restrict__ autoc,
+             int nsub, int n, int maxlag, wt_groups grp, double c,
+             const int32_t *__restrict__ pcm, int32_t *__restrict__ smp_out,
+             const fhip_subframe_info *__restrict__ info, wt_lpc_args lpc, int narrow_ok,
+             const int32_t *__restrict__ dev_sub, const MultiBin &mb, wt_groups grp1, int lsplit)
 {
+    using GEO = wt_geo<TL>;
+    constexpr int T_HALF = GEO::HALF, T_ROW = GEO::ROW, T_STRIDE = GEO::STRIDE, T_BUF = GEO::BUF;
+    constexpr int T_NBUF = GEO::NBUF, T_UNITS = GEO::UNITS, T_AHEAD = GEO::AHEAD, T_UT = GEO::UT;
+    constexpr bool LONG = TL != AC_TILE;
     extern __shared__ __attribute__((aligned(16))) double wt_lds[];
-    double *acbuf = wt_lds + WT_NBUF * WT_BUF;          // [32][FHIP_MAX_LAGS], LPCMO > 0 only
+    double *acbuf = wt_lds + T_NBUF * T_BUF;            // [32][FHIP_MAX_LAGS], LPCMO > 0 only
 
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
@@ -646,8 +682,8 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
     const int sub0 = blk * WT_SUB;
     if (sub0 >= nsub) return;                           // (a ragged batch's grid is its bin's capacity)
     const int half = n >> 1;
-    const int ntiles = n / AC_TILE;
-    const int ntiles_pad = ((ntiles + WT_AHEAD - 1) / WT_AHEAD) * WT_AHEAD;   // the producers' unroll
+    const int ntiles = n / TL;
+    const int ntiles_pad = ((ntiles + T_UT - 1) / T_UT) * T_UT;               // the producers' unroll
 
     if (wv >= 4) {
         // ------------------------------ producer ------------------------------
@@ -691,7 +727,7 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
                 }
             }
             typedef typename std::conditional<FUSED, int4, int2>::type ld_t;
-            ld_t pre[WT_AHEAD][NL];
+            ld_t pre[T_AHEAD][NL];
             // pinned: keep the loads in program order.  The waits in the loop are counted, and a
             // prologue whose loads the scheduler shuffled makes the compiler merge both ways into
             // the loop to the smaller count (vmcnt(2) instead of 16: no prefetch left).
@@ -717,12 +753,19 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
                 }
             };
 #pragma unroll
-            for (int a = 0; a < WT_AHEAD; a++) issue_loads(pre[a], a * AC_TILE, true);
+            for (int a = 0; a < T_AHEAD; a++) issue_loads(pre[a], a * AC_TILE, true);
             // the halo of the first tile is zeros (positions -32 .. -1)
-            for (int idx = lane; idx < NR * 2 * PS_HH; idx += WAVE) {
-                const int r = idx / (2 * PS_HH), k = idx - r * 2 * PS_HH;
-                wt_lds[(q0 + r) * WT_STRIDE + (k / PS_HH) * WT_ROW + (k % PS_HH)] = 0.0;
+            if constexpr (!LONG) {
+                for (int idx = lane; idx < NR * 2 * PS_HH; idx += WAVE) {
+                    const int r = idx / (2 * PS_HH), k = idx - r * 2 * PS_HH;
+                    wt_lds[(q0 + r) * T_STRIDE + (k / PS_HH) * T_ROW + (k % PS_HH)] = 0.0;
+                }
             }
+            // LONG: the halo of the tile about to be produced, in the lanes of positions 96..127 of
+            // the previous tile's second pass (the lanes `tail` selects); carried across the barrier
+            double hl0[LONG ? NR : 1], hl1[LONG ? NR : 1];
+#pragma unroll
+            for (int r = 0; r < (LONG ? NR : 1); r++) { hl0[r] = 0.0; hl1[r] = 0.0; }
             // lpc.c:34-39, 0 beyond the block
             auto weight = [&](int p) {
                 const int ii = (p < half) ? p : (n - 1 - p);
@@ -730,74 +773,98 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
                 const double tt = c - (double)ii;
                 return valid ? (1.0 - (tt * tt)) : 0.0;
             };
-            int bi = 0;                                        // t % 3
+            int bi = 0;                                        // t % T_NBUF
             ACC_RESET(44, 48);
-            for (int t0 = 0; t0 < ntiles_pad; t0 += WT_AHEAD) {
+            for (int t0 = 0; t0 < ntiles_pad; t0 += T_UT) {
 #pragma unroll
-                for (int a = 0; a < WT_AHEAD; a++) {
-                    TICK(tp0);
-                    const int tb = (t0 + a) * AC_TILE;
-                    const int bnx = (bi == WT_NBUF - 1) ? 0 : bi + 1;
-                    double *bw = wt_lds + bi * WT_BUF + q0 * WT_STRIDE + PS_HH + lane;
-                    double *bn = wt_lds + bnx * WT_BUF + q0 * WT_STRIDE + PS_HH + lane - PS_HALF;
-                    const double w0 = weight(tb + 2 * lane), w1 = weight(tb + 2 * lane + 1);
-                    const bool tail = lane >= PS_HALF - PS_HH;        // positions 96..127
-                    const int pst = min(tb + 2 * lane, n - 2);        // padding tiles rewrite the last pair
-                    // all rows in one basic block (the scheduler interleaves their dependent
-                    // chains: a producer is alone with its latencies), the halo copies after it
-                    double hv0[NR], hv1[NR];
-#pragma unroll
-                    for (int r = 0; r < (wt_probe_noprod ? 0 : NR); r++) {
-                        int32_t x0, x1;                               // samples 2*lane, 2*lane+1 of row r
-                        if (FUSED) {
-                            const int4 v = *reinterpret_cast<const int4 *>(&pre[a][r / 2]);   // l0 r0 l1 r1
-                            const int md = mode[r / 2];
-                            // encode.c:668-693: channel 0 is mid / left / side(RS), channel 1 side / right
-                            const int32_t s0 = (int32_t)((uint32_t)v.x - (uint32_t)v.y);
-                            const int32_t s1 = (int32_t)((uint32_t)v.z - (uint32_t)v.w);
-                            if ((r & 1) == 0) {
-                                const int32_t m0 = (int32_t)((uint32_t)v.x + (uint32_t)v.y) >> 1;
-                                const int32_t m1 = (int32_t)((uint32_t)v.z + (uint32_t)v.w) >> 1;
-                                x0 = (md == FHIP_CH_MID_SIDE) ? m0 : (md == FHIP_CH_RIGHT_SIDE) ? s0 : v.x;
-                                x1 = (md == FHIP_CH_MID_SIDE) ? m1 : (md == FHIP_CH_RIGHT_SIDE) ? s1 : v.z;
-                                x0 >>= w0s[r / 2]; x1 >>= w0s[r / 2];
-                            } else {
-                                x0 = (md == FHIP_CH_MID_SIDE || md == FHIP_CH_LEFT_SIDE) ? s0 : v.y;
-                                x1 = (md == FHIP_CH_MID_SIDE || md == FHIP_CH_LEFT_SIDE) ? s1 : v.w;
-                                x0 >>= w1s[r / 2]; x1 >>= w1s[r / 2];
-                            }
-                            *reinterpret_cast<int2 *>(reinterpret_cast<int32_t *>(outb[r]) + pst) = make_int2(x0, x1);
-                        } else {
-                            const int2 v = *reinterpret_cast<const int2 *>(&pre[a][r]);
-                            const bool nr = ALLNAR || nar[FUSED ? 0 : r] != 0;        // wave-uniform
-                            x0 = nr ? (int32_t)(int16_t)v.x : v.x;
-                            x1 = nr ? (v.x >> 16) : v.y;
-                        }
-                        const double v0 = (double)x0 * w0;
-                        const double v1 = (double)x1 * w1;
-#ifdef FHIP_PROBE_NOLDSW
-                        if (r == 0) { hv0[0] = 0; hv1[0] = 0; }
-                        hv0[0] += v0; hv1[0] += v1;
-                        if (r == NR - 1) { bw[0] = hv0[0]; bw[WT_ROW] = hv1[0]; }
-#else
-                        bw[r * WT_STRIDE] = v0;
-                        bw[r * WT_STRIDE + WT_ROW] = v1;
-                        hv0[r] = v0; hv1[r] = v1;
-#endif
-                    }
-                    if (tail && !wt_probe_nohalo && !wt_probe_noprod) {   // = positions -32..-1 of the next tile
+                for (int a = 0; a < T_UT; a++) {
+                    const int bnx = (bi == T_NBUF - 1) ? 0 : bi + 1;
+                    const bool tail = lane >= PS_HALF - PS_HH;          // positions 96..127 of a pass
+                    if (LONG && tail && !wt_probe_nohalo && !wt_probe_noprod) {
+                        // positions -32..-1 of this tile, kept since the previous one was produced
+                        double *bh = wt_lds + bi * T_BUF + q0 * T_STRIDE + lane - (PS_HALF - PS_HH);
 #pragma unroll
                         for (int r = 0; r < NR; r++) {
-                            bn[r * WT_STRIDE] = hv0[r];
-                            bn[r * WT_STRIDE + WT_ROW] = hv1[r];
+                            bh[r * T_STRIDE] = hl0[LONG ? r : 0];
+                            bh[r * T_STRIDE + T_ROW] = hl1[LONG ? r : 0];
                         }
                     }
-                    TICK(tp1);
-                    issue_loads(pre[a], tb + WT_AHEAD * AC_TILE);
+#pragma unroll
+                    for (int h = 0; h < T_UNITS; h++) {                 // one 128-position pass
+                        TICK(tp0);
+                        const int ai = a * T_UNITS + h;                   // this pass's load registers
+                        const int tb = (t0 + a) * TL + h * AC_TILE;
+                        double *bw = wt_lds + bi * T_BUF + q0 * T_STRIDE + PS_HH + h * PS_HALF + lane;
+                        double *bn = wt_lds + bnx * T_BUF + q0 * T_STRIDE + PS_HH + lane - PS_HALF;
+                        const double w0 = weight(tb + 2 * lane), w1 = weight(tb + 2 * lane + 1);
+                        const int pst = min(tb + 2 * lane, n - 2);        // padding tiles rewrite the last pair
+                        // all rows in one basic block (the scheduler interleaves their dependent
+                        // chains: a producer is alone with its latencies), the halo copies after it
+                        double hv0[NR], hv1[NR];
+#pragma unroll
+                        for (int r = 0; r < (wt_probe_noprod ? 0 : NR); r++) {
+                            int32_t x0, x1;                               // samples 2*lane, 2*lane+1 of row r
+                            if (FUSED) {
+                                const int4 v = *reinterpret_cast<const int4 *>(&pre[ai][r / 2]);   // l0 r0 l1 r1
+                                const int md = mode[r / 2];
+                                // encode.c:668-693: channel 0 is mid / left / side(RS), channel 1 side / right
+                                const int32_t s0 = (int32_t)((uint32_t)v.x - (uint32_t)v.y);
+                                const int32_t s1 = (int32_t)((uint32_t)v.z - (uint32_t)v.w);
+                                if ((r & 1) == 0) {
+                                    const int32_t m0 = (int32_t)((uint32_t)v.x + (uint32_t)v.y) >> 1;
+                                    const int32_t m1 = (int32_t)((uint32_t)v.z + (uint32_t)v.w) >> 1;
+                                    x0 = (md == FHIP_CH_MID_SIDE) ? m0 : (md == FHIP_CH_RIGHT_SIDE) ? s0 : v.x;
+                                    x1 = (md == FHIP_CH_MID_SIDE) ? m1 : (md == FHIP_CH_RIGHT_SIDE) ? s1 : v.z;
+                                    x0 >>= w0s[r / 2]; x1 >>= w0s[r / 2];
+                                } else {
+                                    x0 = (md == FHIP_CH_MID_SIDE || md == FHIP_CH_LEFT_SIDE) ? s0 : v.y;
+                                    x1 = (md == FHIP_CH_MID_SIDE || md == FHIP_CH_LEFT_SIDE) ? s1 : v.w;
+                                    x0 >>= w1s[r / 2]; x1 >>= w1s[r / 2];
+                                }
+                                *reinterpret_cast<int2 *>(reinterpret_cast<int32_t *>(outb[r]) + pst) = make_int2(x0, x1);
+                            } else {
+                                const int2 v = *reinterpret_cast<const int2 *>(&pre[ai][r]);
+                                const bool nr = ALLNAR || nar[FUSED ? 0 : r] != 0;        // wave-uniform
+                                x0 = nr ? (int32_t)(int16_t)v.x : v.x;
+                                x1 = nr ? (v.x >> 16) : v.y;
+                            }
+                            const double v0 = (double)x0 * w0;
+                            const double v1 = (double)x1 * w1;
+#ifdef FHIP_PROBE_NOLDSW
+                            if (r == 0) { hv0[0] = 0; hv1[0] = 0; }
+                            hv0[0] += v0; hv1[0] += v1;
+                            if (r == NR - 1) { bw[0] = hv0[0]; bw[T_ROW] = hv1[0]; }
+#else
+                            bw[r * T_STRIDE] = v0;
+                            bw[r * T_STRIDE + T_ROW] = v1;
+                            hv0[r] = v0; hv1[r] = v1;
+#endif
+                        }
+                        if constexpr (LONG) {
+                            if (h == T_UNITS - 1) {
+#pragma unroll
+                                for (int r = 0; r < NR; r++) { hl0[r] = hv0[r]; hl1[r] = hv1[r]; }
+                            }
+                        } else if (tail && !wt_probe_nohalo && !wt_probe_noprod) {   // = positions -32..-1 of the next tile
+#pragma unroll
+                            for (int r = 0; r < NR; r++) {
+                                bn[r * T_STRIDE] = hv0[r];
+                                bn[r * T_STRIDE + T_ROW] = hv1[r];
+                            }
+                        }
+                        TICK(tp1);
+                        issue_loads(pre[ai], tb + T_AHEAD * AC_TILE);
+                        TICK(tp2);
+                        ACCUM(44, tp0, tp1); ACCUM(45, tp1, tp2);
+                        if (h < T_UNITS - 1) {
+                            // keep the second pass's conversions below this point, as below the barrier
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
                     TICK(tp2);
-                    __syncthreads();                               // tile handed over
+                    __syncthreads();                                 // tile handed over
                     TICK(tp3);
-                    ACCUM(44, tp0, tp1); ACCUM(45, tp1, tp2); ACCUM(46, tp2, tp3);
+                    ACCUM(46, tp2, tp3);
                     // keep the next tile's conversions below this point: hoisted, they
                     // would wait for loads that still have two tiles of time
                     __builtin_amdgcn_sched_barrier(0);
@@ -831,15 +898,16 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
     const bool live = (sub0 + sl < nsub) && nch > 0;
     const int pib = pi ^ (l0 & 1);                      // parity array that holds d[p - l0]
     const int sft = (l0 + pib - pi) / 2;                // index shift inside that array
-    const int offA = sl * WT_STRIDE + pi * WT_ROW + PS_HH;             // a  = buf[offA + step]
-    const int offB = sl * WT_STRIDE + pib * WT_ROW + PS_HH - sft;      // b0 = buf[offB + step]
+    const int offA = sl * T_STRIDE + pi * T_ROW + PS_HH;               // a  = buf[offA + step]
+    const int offB = sl * T_STRIDE + pib * T_ROW + PS_HH - sft;        // b0 = buf[offB + step]
     const int pih = (maxlag + 1) & 1;                   // parity whose sum owns the head
-    auto slotc = [&](int x) { return sl * WT_STRIDE + (x & 1) * WT_ROW + PS_HH + (x >> 1); };
+    // position x of the tile (x >= -32: the halo; & and >> round towards minus infinity together)
+    auto slotc = [&](int x) { return sl * T_STRIDE + (x & 1) * T_ROW + PS_HH + (x >> 1); };
     double S[NCH], cy[NCH];                             // running sums (lpc.c:58-59); cy[j] = d[p - l0 - 2j] carried
 #pragma unroll
     for (int j = 0; j < NCH; j++) { S[j] = 1.0; cy[j] = 0.0; }
 
-    // One tile: PS_HALF steps of NCH products, operands read two stages ahead.
+    // One tile: T_HALF steps of NCH products, operands read two stages ahead.
     // FIRST is the tile that starts the block: products of positions <= maxlag
     // belong to the head (below), so their `a` is replaced by 0 -- a (+-0) product
     // leaves a running sum, which is never -0, bit for bit as it was.  SAME: the
@@ -855,7 +923,7 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
         constexpr int HD = decltype(histc)::value;
         constexpr int K = decltype(kc)::value;
         constexpr bool NOB = SAME || HD > 0 || wt_probe_nob;     // no b0 stream from the LDS
-        constexpr int NS = PS_HALF / PS_CH;
+        constexpr int NS = T_HALF / PS_CH;
         // stages of operands in flight ahead of their use: two while a stage is short
         constexpr int DEPTH = (K <= 3) ? 2 : 1;
         constexpr int NSET = DEPTH + 1;
@@ -867,6 +935,11 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
         lds_cvd2 *rowA = (lds_cvd2 *)rowA_;
         lds_cvd *rowB = (lds_cvd *)rowB_;
         double A[NSET][PS_CH], B[NSET][PS_CH];
+        // The head's 17 step masks (FIRST) are loop invariants of the tile loop: hoisted, they sat in 34 SGPRs
+        // across every walk.  Compared against an opaque per-lane copy of maxlag they are formed where they are
+        // used, once per launch, in vcc.
+        int maxlag_v = maxlag;
+        if constexpr (FIRST) asm volatile("" : "+v"(maxlag_v));
         auto fetch = [&](int set, int stage) {
 #pragma unroll
             for (int u = 0; u < PS_CH; u += 2) {
@@ -879,11 +952,12 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
             }
         };
         constexpr int PER_STAGE = PS_CH / 2 + (NOB ? 0 : PS_CH);     // LDS reads per stage
-#pragma unroll
-        for (int k = 0; k < DEPTH; k++) fetch(k, k);
-#pragma unroll
-        for (int st = 0; st < NS; st++) {
-            if (st + DEPTH < NS) fetch((st + DEPTH) % NSET, st + DEPTH);
+        // One stage: read the operands DEPTH stages ahead into their set, wait for this stage's, then its
+        // PS_CH steps.  `set` (= st % NSET), `ahead`, `newer` (the stages read after this one that are still in
+        // flight) and `headz` fold to constants where the call is unrolled.
+        // headz: the stage can hold positions <= maxlag of the FIRST tile (st is then a constant too).
+        auto stage = [&](int st, int set, bool ahead, int newer, bool headz) __attribute__((always_inline)) {
+            if (ahead) fetch((set + DEPTH) % NSET, st + DEPTH);
             // one wait per stage: everything but the reads just issued (and, two
             // stages deep, the stage before them) has arrived
             {
@@ -892,7 +966,6 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
                 constexpr int enc1 = (3 << 14) | (w1 << 8) | (7 << 4) | 0xF;
                 constexpr int enc2 = (3 << 14) | (w2 << 8) | (7 << 4) | 0xF;
                 constexpr int enc0 = (3 << 14) | (0 << 8) | (7 << 4) | 0xF;
-                const int newer = (st + DEPTH < NS ? 1 : 0) + ((DEPTH == 2 && st + 1 < NS) ? 1 : 0);
                 if (newer == 2) __builtin_amdgcn_s_waitcnt(enc2);
                 else if (newer == 1) __builtin_amdgcn_s_waitcnt(enc1);
                 else __builtin_amdgcn_s_waitcnt(enc0);
@@ -900,11 +973,11 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int u = 0; u < PS_CH; u++) {
-                const double x = (SAME || wt_probe_nob) ? A[st % NSET][u] : (HD > 0) ? hist[HD > 0 ? HD - 1 : 0]
-                                                                                      : B[st % NSET][u];
-                double a = A[st % NSET][u];
-                if (FIRST && 2 * (st * PS_CH + u) <= FHIP_MAX_ORDER)            // steps that can hold p <= maxlag
-                    a = (2 * (st * PS_CH + u) + pi > maxlag) ? a : 0.0;
+                const double x = (SAME || wt_probe_nob) ? A[set][u] : (HD > 0) ? hist[HD > 0 ? HD - 1 : 0]
+                                                                                : B[set][u];
+                double a = A[set][u];
+                if (FIRST && headz && 2 * (st * PS_CH + u) <= FHIP_MAX_ORDER)   // steps that can hold p <= maxlag
+                    a = (2 * (st * PS_CH + u) + pi > maxlag_v) ? a : 0.0;
                 double pr[K];
                 pr[0] = a * x;
 #pragma unroll
@@ -917,10 +990,35 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
                 if constexpr (HD > 0) {
 #pragma unroll
                     for (int k = HD - 1; k >= 1; k--) hist[k] = hist[k - 1];
-                    hist[0] = A[st % NSET][u];
+                    hist[0] = A[set][u];
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
+        };
+        auto newer_of = [](int st) { return (st + DEPTH < NS ? 1 : 0) + ((DEPTH == 2 && st + 1 < NS) ? 1 : 0); };
+#pragma unroll
+        for (int k = 0; k < DEPTH; k++) fetch(k, k);
+        if constexpr (!LONG) {
+#pragma unroll
+            for (int st = 0; st < NS; st++) stage(st, st % NSET, st + DEPTH < NS, newer_of(st), true);
+        } else {
+            // 16 stages.  Written out they would double each walk instance, and five of them are resident per
+            // kernel already (two per group kind and the head's tile), so the steady stages run as a rolled
+            // loop whose trip is one rotation of the operand sets (NSET stages: the set indices stay
+            // constants).  Written out are only the FIRST tile's leading rotations, which zero the head's
+            // `a`, and the last stages, whose reads ahead run out.
+            constexpr int HEADST = FIRST ? ((FHIP_MAX_ORDER / 2 + PS_CH) / PS_CH + NSET - 1) / NSET * NSET : 0;
+            constexpr int STEADY = (NS - DEPTH) / NSET * NSET;     // stages [0, STEADY) all read ahead
+            static_assert(HEADST <= STEADY && (!FIRST || HEADST * PS_CH * 2 > FHIP_MAX_ORDER), "head inside the peeled stages");
+#pragma unroll
+            for (int st = 0; st < HEADST; st++) stage(st, st % NSET, true, DEPTH, true);
+#pragma unroll 1
+            for (int st0 = HEADST; st0 < STEADY; st0 += NSET) {
+#pragma unroll
+                for (int s = 0; s < NSET; s++) stage(st0 + s, s, true, DEPTH, false);
+            }
+#pragma unroll
+            for (int st = STEADY; st < NS; st++) stage(st, st % NSET, st + DEPTH < NS, newer_of(st), false);
         }
     };
 
@@ -939,10 +1037,36 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
             ACCUM(40, tc0, tc1);
             ACCUM_W(56, tc0, tc1);
             if (t >= ntiles || wt_probe_nowalk || nch <= 0) continue;    // padding of the producers' unroll
-            const double *buf = wt_lds + bi * WT_BUF;
+            const double *buf = wt_lds + bi * T_BUF;
             if (t == 0 && pi == pih) {
                 // head (lpc.c:60-61): positions lag..maxlag of BOTH parities, in order,
                 // into this lane's sums (tile 0 holds them all: maxlag <= 32 < AC_TILE)
+#ifndef FHIP_HEAD_LOOP                                  // (-DFHIP_HEAD_LOOP: the loop everywhere, for timing)
+                // (NCH >= 3 only: with one or two chains the 128 form is allocated for four waves per SIMD,
+                // 128 VGPRs, and the unrolled head took <1|2,false,8|12> to 256 with 29-36 spilled to scratch)
+                if constexpr (LPCMO > 0 && NCH >= 3) {
+                    // maxlag <= LPCMO: d[x] and d[x - l0] for x = 0..LPCMO read once, all reads in flight
+                    // together (the loop below waits for two dependent reads per trip), then the same products
+                    // in the same order from registers.  The loop's tests are folded into the operands:
+                    // x > maxlag zeroes `a`, and a position before the block (x < lag) reads tile 0's halo,
+                    // which is zeros -- a (+-0) product leaves a sum, which is never -0, bit for bit as it
+                    // was (as in walk_tile).  Chains j >= nch are never stored.
+                    double hd[LPCMO + 1], he[LPCMO + 1];
+#pragma unroll
+                    for (int x = 0; x <= LPCMO; x++) { hd[x] = buf[slotc(x)]; he[x] = buf[slotc(x - l0)]; }
+#pragma unroll
+                    for (int x = 0; x <= LPCMO; x++) {
+                        const double a = (x <= maxlag) ? hd[x] : 0.0;
+#pragma unroll
+                        for (int j = 0; j < NCH; j++) {
+                            if (x - 2 * j >= 0) {                       // (compile time)
+                                const double pr = a * he[x - 2 * j];
+                                S[j] = S[j] + pr;
+                            }
+                        }
+                    }
+                } else
+#endif
                 for (int x = 0; x <= maxlag; x++) {
                     const double a = buf[slotc(x)];
 #pragma unroll
@@ -957,7 +1081,7 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
             }
             if (t == 0) walk_tile(buf + offA, buf + offB, std::true_type{}, same, histc, kc, hist);
             else walk_tile(buf + offA, buf + offB, std::false_type{}, same, histc, kc, hist);
-            bi = (bi == WT_NBUF - 1) ? 0 : bi + 1;
+            bi = (bi == T_NBUF - 1) ? 0 : bi + 1;
             TICK(tc2);
             ACCUM(t == 0 ? 42 : 41, tc1, tc2);
             ACCUM_W(t == 0 ? 52 : 48, tc1, tc2);
@@ -1034,6 +1158,31 @@ void k_autocorr_wt(const int32_t *__restrict__ smp, double *__restrict__ autoc,
     }
 }
 
+#define WT_KERNEL_ARGS                                                                              \
+    const int32_t *__restrict__ smp, double *__restrict__ autoc, int nsub, int n, int maxlag,       \
+    wt_groups grp, double c, const int32_t *__restrict__ pcm, int32_t *__restrict__ smp_out,        \
+    const fhip_subframe_info *__restrict__ info, wt_lpc_args lpc, int narrow_ok,                    \
+    const int32_t *__restrict__ dev_sub, MultiBin mb, wt_groups grp1, int lsplit
+#define WT_KERNEL_PASS smp, autoc, nsub, n, maxlag, grp, c, pcm, smp_out, info, lpc, narrow_ok, dev_sub, mb, grp1, lsplit
+
+// 128 positions per hand-over, three buffers: any n % 128 == 0
+template <int NCH, bool FUSED, int LPCMO>
+__global__ __launch_bounds__(8 * WAVE)
+void k_autocorr_wt(WT_KERNEL_ARGS)
+{
+    wt_body<NCH, FUSED, LPCMO, AC_TILE>(WT_KERNEL_PASS);
+}
+
+// 256 positions per hand-over, two buffers: n % 256 == 0 (wt_use_long_tile)
+template <int NCH, bool FUSED, int LPCMO>
+__global__ __launch_bounds__(8 * WAVE)
+void k_autocorr_wtl(WT_KERNEL_ARGS)
+{
+    wt_body<NCH, FUSED, LPCMO, WTL_TILE>(WT_KERNEL_PASS);
+}
+#undef WT_KERNEL_ARGS
+#undef WT_KERNEL_PASS
+
 }  // namespace
 
 namespace {
@@ -1096,7 +1245,38 @@ ac_choice pick_autocorr(int nsub, int n, int max_order)
     }
     return ch;
 }
+
+// Which form of the wave-typed kernel a launch takes: the long-tile one wherever the 128 form would
+// run and every block is whole 256-position tiles (for a ragged batch: every bin's).  FHIP_WT_TILE=128,
+// read per launch and for measurements only, keeps the 128 form, so that one build can alternate the two
+// (a getenv per launch, next to the launch's own cost nothing; the switch goes when the 128 form's
+// timings are no longer wanted beside the long form's).  count == 0 (no block at all) answers true:
+// every caller has at least one bin.
+bool wt_long_tile(const int *n, int count)
+{
+    const char *force = getenv("FHIP_WT_TILE");
+    if (force && atoi(force) == AC_TILE) return false;
+    for (int k = 0; k < count; k++) if (n[k] < WTL_TILE || (n[k] % WTL_TILE) != 0) return false;
+    return true;
+}
+constexpr size_t wt_lds_bytes(bool long_tile)
+{
+    return sizeof(double) * (long_tile ? (size_t)wt_geo<WTL_TILE>::NBUF * wt_geo<WTL_TILE>::BUF
+                                       : (size_t)WT_NBUF * WT_BUF);
+}
+static_assert(wt_lds_bytes(true) + sizeof(double) * WT_SUB * FHIP_MAX_LAGS <= 160 * 1024, "one workgroup's LDS");
 }  // namespace
+
+}  // namespace fhip
+
+extern "C" FHIP_API int fhip_autocorr_tile(int nsub, int n, int max_order)
+{
+    if (nsub < 1 || n < 1 || max_order < 1 || max_order > FHIP_MAX_ORDER) return 0;
+    if (fhip::pick_autocorr(nsub, n, max_order).kernel != 2) return 0;
+    return fhip::wt_long_tile(&n, 1) ? fhip::WTL_TILE : fhip::AC_TILE;
+}
+
+namespace fhip {
 
 bool autocorr_is_wave_typed(int nsub, int n, int max_order)
 {
@@ -1164,17 +1344,20 @@ hipError_t launch_autocorr_bins(hipStream_t st, const MultiBin &mb, const int32_
         la.fin = lpc_out->fin;
         lpcmo = (max_order <= 8) ? 8 : 12;
     }
-    const size_t lds = sizeof(double) * (size_t)WT_NBUF * WT_BUF +
-                       (lpcmo ? sizeof(double) * (size_t)WT_SUB * FHIP_MAX_LAGS : 0);
+    const bool long_tile = wt_long_tile(mb.n, mb.nbins);
+    const size_t lds = wt_lds_bytes(long_tile) + (lpcmo ? sizeof(double) * (size_t)WT_SUB * FHIP_MAX_LAGS : 0);
     bool any_narrow = false;
     for (int k = 0; k < mb.nbins; k++) any_narrow = any_narrow || mb.narrow[k];
+    // (both forms note the same string: the launch log names the instance, not its tile length --
+    // fhip_autocorr_tile answers that)
 #define LAUNCH_WTB(N_, L_)                                                                 \
     do {                                                                                     \
-        hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_autocorr_wt<N_, false, L_>), \
+        auto kern = long_tile ? &k_autocorr_wtl<N_, false, L_> : &k_autocorr_wt<N_, false, L_>; \
+        hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),            \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         if (er != hipSuccess) return er;                                                     \
         note_launch("k_autocorr_wt<%d,false,%d> split=1%s%s", N_, L_, L_ ? " tail" : "", any_narrow ? " narrow" : ""); \
-        hipLaunchKernelGGL((k_autocorr_wt<N_, false, L_>), dim3(blocks), dim3(8 * WAVE), lds, st, smp, \
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(8 * WAVE), lds, st, smp,                 \
                            autoc, 0, 0, max_order, gr, 0.0, (const int32_t *)nullptr, (int32_t *)nullptr, info, la, 0, \
                            (const int32_t *)nullptr, mb, wt_groups{}, 1);                    \
     } while (0)
@@ -1265,7 +1448,8 @@ hipError_t launch_autocorr(hipStream_t st, const int32_t *smp, int nsub, int n,
             nch = e0;                                          // e0 >= e1, o0, o1
         }
         const int blocks = split * ((nsub + WT_SUB - 1) / WT_SUB);
-        const size_t lds = sizeof(double) * (size_t)WT_NBUF * WT_BUF;
+        const bool long_tile = !pcm_fused && wt_long_tile(&n, 1);     // (the fused instances stay on 128)
+        const size_t lds = wt_lds_bytes(long_tile);
         wt_lpc_args la{};
         int lpcmo = 0;
         if (lpc_out) {
@@ -1278,12 +1462,13 @@ hipError_t launch_autocorr(hipStream_t st, const int32_t *smp, int nsub, int n,
         const size_t lds_all = lds + (lpcmo ? sizeof(double) * (size_t)WT_SUB * FHIP_MAX_LAGS : 0);
 #define LAUNCH_WT3(N_, F_, L_)                                                               \
     do {                                                                                     \
-        hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_autocorr_wt<N_, F_, L_>), \
+        auto kern = (long_tile && !F_) ? &k_autocorr_wtl<N_, false, L_> : &k_autocorr_wt<N_, F_, L_>; \
+        hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),            \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_all); \
         if (er != hipSuccess) return er;                                                     \
         note_launch("k_autocorr_wt<%d,%s,%d> split=%d%s%s%s", N_, tf(F_), L_, split, L_ ? " tail" : "", \
                     F_ ? " fused" : "", narrow_ok ? " narrow" : "");                         \
-        hipLaunchKernelGGL((k_autocorr_wt<N_, F_, L_>), dim3(blocks), dim3(8 * WAVE), lds_all, st, smp, \
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(8 * WAVE), lds_all, st, smp,             \
                            autoc, nsub, n, max_order, gr, c, pcm_fused, smp_out, info, la, narrow_ok ? 1 : 0, dev_sub, MultiBin{}, gr1, split); \
     } while (0)
 #define LAUNCH_WT(N_)                                                                        \

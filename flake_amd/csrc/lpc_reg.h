@@ -44,8 +44,12 @@ __device__ __forceinline__ void quantize_row_reg(const double (&a)[MO], int orde
         }
         return;
     }
+    // lpc.c's `while (sh > 0 && cmax * (1 << sh) > qmax) sh--`, as 15 selects: a step acts only while sh
+    // is still at its own k, so the first test that fails stops the descent.  (Unrolled as branches, the
+    // loop became 15 nested per-lane regions, each holding an exec mask.)
     int sh = 15;
-    while (sh > 0 && cmax * (double)(1 << sh) > (double)qmax) sh--;
+#pragma unroll
+    for (int k = 15; k >= 1; k--) sh = (sh == k && cmax * (double)(1 << k) > (double)qmax) ? k - 1 : sh;
     const bool rescale = (sh == 0) && (cmax > (double)qmax);
     const double scale = rescale ? ((double)qmax / cmax) : 1.0;
     const double mul = (double)(1 << sh);
@@ -194,11 +198,15 @@ __device__ __forceinline__ void lpc_reg_one(const double (&ac)[MO + 1], int s, i
             }
             if (all_rows)
                 quantize_row_reg<MO>(a, i + 1, precision, crow + i * FHIP_MAX_ORDER, srow + i);
-            else if (i == levinson_order - 1)       // the one row of MAX / EST, and its compact copy
-                quantize_row_reg<MO>(a, i + 1, precision, crow + i * FHIP_MAX_ORDER, srow + i,
-                                     fin + (size_t)s * FIN_STRIDE, max_order);
         }
     }
+    // The one row of MAX / EST, and its compact copy: a[] stopped changing at i = levinson_order - 1, so it
+    // is quantised once, behind the recursion, with its order a run-time value.  Inside the loop it was MO
+    // copies of the quantiser, whose `j < max_order` masks (shared by all copies, so live across all of them)
+    // alone took more SGPRs than a wave has.
+    if (!all_rows && levinson_order > 0)
+        quantize_row_reg<MO>(a, levinson_order, precision, crow + (levinson_order - 1) * FHIP_MAX_ORDER,
+                             srow + (levinson_order - 1), fin + (size_t)s * FIN_STRIDE, max_order);
     opt_order[s] = levinson_order;
 }
 

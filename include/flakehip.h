@@ -664,6 +664,16 @@ FHIP_API int fhip_get_kernel_times(fhip_ctx *ctx, const char **names, double *ms
  * allows the fast path; asking for the list then waits for that launch.)  names[0 .. cap) receive
  * strings owned by the handle, valid until its next such call; returns the number of launches. */
 FHIP_API int fhip_last_launches(fhip_ctx *ctx, const char **names, int cap);
+/* The tile length of K1's wave-typed kernel for a uniform batch of nsub subframes of n samples at this maximum
+ * prediction order: 256 (positions handed from the staging waves to the walking ones per workgroup barrier; the
+ * long-tile form, n a multiple of 256), 128 (the original form), or 0 where K1 is not the wave-typed kernel at all.
+ * The launch log spells both forms "k_autocorr_wt<...>"; this tells them apart.  A pure host function: no handle,
+ * no device work.  It answers for the launches that read prepared samples (every launch of a default build); the
+ * fused-prepare instances (FHIP_FUSE in the environment, an experiment that is off by default) keep the 128 form and
+ * size their batch from a hint of their own, so for them the answer may name a form that did not run.
+ * It honours FHIP_WT_TILE=128, the measurement switch that keeps the 128 form, which the
+ * launches read each time as well. */
+FHIP_API int fhip_autocorr_tile(int nsub, int n, int max_order);
 
 #ifdef __cplusplus
 }
