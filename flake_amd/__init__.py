@@ -136,6 +136,18 @@ class VerifyOut(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("summary", C.c_void_p)]
 
 
+class DecodeIn(C.Structure):
+    """``fhip_decode_in``"""
+    _fields_ = [("stream", C.c_void_p), ("stream_bytes", C.c_int64), ("frame_bytes", C.c_void_p),
+                ("nframes", C.c_int32), ("variable_blocks", C.c_int32), ("first_number", C.c_int64)]
+
+
+class DecodeOut(C.Structure):
+    """``fhip_decode_out``"""
+    _fields_ = [("pcm", C.c_void_p), ("pcm_cap", C.c_int64), ("frames", C.c_void_p), ("summary", C.c_void_p),
+                ("nsamples", C.c_void_p)]
+
+
 # numpy view of fhip_md5_state (96 bytes): K6's running hash of one stream
 MD5_STATE_DTYPE = np.dtype([("h", "<u4", (4,)), ("nbytes", "<u8"), ("fill", "<u4"), ("reserved", "<u4"),
                             ("tail", "u1", (64,))])
@@ -204,6 +216,8 @@ def load_library() -> C.CDLL:
         "fhip_verify_frames_numbered_dev": (i, [vp, C.POINTER(VerifyIn), vp, C.POINTER(VerifyOut)]),
         "fhip_verify_frames_numbered": (i, [vp, C.POINTER(VerifyIn), vp, C.POINTER(VerifyOut)]),
         "fhip_last_verify_failure": (i, [vp, vp, vp]),
+        "fhip_decode_frames_dev": (i, [vp, C.POINTER(DecodeIn), C.POINTER(DecodeOut)]),
+        "fhip_decode_frames": (i, [vp, C.POINTER(DecodeIn), C.POINTER(DecodeOut)]),
         "fhip_get_kernel_times": (i, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double),
                                       C.POINTER(i), i, i]),
         "fhip_last_launches": (i, [vp, C.POINTER(C.c_char_p), i]),
@@ -260,6 +274,7 @@ ABI_SYMBOLS = (
     "fhip_encode_blocks_vbs_ragged_numbered", "fhip_vbs_split_ragged", "fhip_verify_frames_blocks_ragged_dev",
     "fhip_verify_frames_blocks_ragged",
     "fhip_autocorr_tile",
+    "fhip_decode_frames_dev", "fhip_decode_frames",
 )
 
 
@@ -493,6 +508,43 @@ class Encoder:
         num = C.c_uint32(0)
         have = self.lib.fhip_last_verify_number(self._h, C.byref(num)) == 1
         return summary, rec[0], (num.value if have else None)
+
+    # -- K7: decoding ----------------------------------------------------
+    def decode_frames(self, stream, frame_bytes, pcm_cap: int, variable_blocks: bool = False, first_number: int = -1,
+                      out=None):
+        """fhip_decode_frames on host data.  stream: uint8 bytes, frame_bytes: int32[nframes]; pcm_cap: samples per
+        channel the output may take.  out (optional): a C-contiguous array of the handle's PCM dtype to decode into
+        (at least pcm_cap * channels values), else one is made.  Returns (ok, pcm [pcm_cap][channels], nsamples,
+        records as a VERIFY_REC_DTYPE array, summary int64[4], error text); pcm[:nsamples] is the decoded audio
+        when ok."""
+        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
+                                  else stream, dtype=np.uint8)
+        fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
+        ch = self.params.channels
+        if out is None:
+            out = np.zeros((pcm_cap, ch), dtype=self.pcm_dtype)
+        if out.dtype != self.pcm_dtype or out.size < pcm_cap * ch:
+            raise ValueError("out must hold pcm_cap * channels values of the handle's PCM dtype")
+        recs = np.zeros(len(fb), dtype=VERIFY_REC_DTYPE)
+        summary = np.zeros(4, dtype=np.int64)
+        ns = np.zeros(1, dtype=np.int64)
+        di = DecodeIn(st.ctypes.data if st.size else None, st.size, fb.ctypes.data if fb.size else None, len(fb),
+                      int(bool(variable_blocks)), int(first_number))
+        do = DecodeOut(_ptr(out) if out.size else None, pcm_cap, recs.ctypes.data if len(fb) else None,
+                       summary.ctypes.data, ns.ctypes.data)
+        rc = self.lib.fhip_decode_frames(self._h, C.byref(di), C.byref(do))
+        if rc not in (OK, E_VERIFY):
+            self._check(rc, "fhip_decode_frames")
+        return rc == OK, out, int(ns[0]), recs, summary, self.lib.fhip_last_error(self._h).decode() if rc else ""
+
+    def decode_frames_dev(self, stream, stream_bytes: int, frame_bytes, nframes: int, pcm, pcm_cap: int, summary,
+                          nsamples, records=None, variable_blocks: bool = False, first_number: int = -1) -> None:
+        """K7 on device-resident data (torch tensors or raw device addresses); async.  pcm: the handle's PCM dtype,
+        [pcm_cap][channels]; summary: int64[4]; nsamples: int64[1]; records: int32[nframes][4], optional."""
+        di = DecodeIn(_ptr(stream), stream_bytes, _ptr(frame_bytes), nframes, int(bool(variable_blocks)),
+                      int(first_number))
+        do = DecodeOut(_ptr(pcm), pcm_cap, _ptr(records), _ptr(summary), _ptr(nsamples))
+        self._check(self.lib.fhip_decode_frames_dev(self._h, C.byref(di), C.byref(do)), "fhip_decode_frames_dev")
 
     def kernel_times(self, reset: bool = True) -> dict:
         names = (C.c_char_p * 8)()
@@ -729,6 +781,22 @@ def load_host_library() -> C.CDLL:
     lib.flake_amd_set_device_batches.restype = C.c_longlong
     lib.flake_amd_set_close.argtypes = [C.c_void_p]
     lib.flake_amd_set_close.restype = None
+    lib.flake_amd_read_streaminfo.argtypes = [C.c_void_p, C.POINTER(HostStreaminfo)]
+    lib.flake_amd_read_streaminfo.restype = C.c_int
+    lib.flake_amd_index_frames.argtypes = [C.POINTER(HostStreaminfo), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
+                                           C.POINTER(C.c_size_t)]
+    lib.flake_amd_index_frames.restype = C.c_longlong
+    lib.flake_amd_decode_open.argtypes = [C.POINTER(HostStreaminfo)]
+    lib.flake_amd_decode_open.restype = C.c_void_p
+    lib.flake_amd_decode_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
+                                            C.c_int, C.c_size_t]
+    lib.flake_amd_decode_frames.restype = C.c_longlong
+    lib.flake_amd_decode_md5.argtypes = [C.c_void_p, C.c_void_p]
+    lib.flake_amd_decode_md5.restype = C.c_int
+    lib.flake_amd_decode_last_error.argtypes = [C.c_void_p]
+    lib.flake_amd_decode_last_error.restype = C.c_char_p
+    lib.flake_amd_decode_close.argtypes = [C.c_void_p]
+    lib.flake_amd_decode_close.restype = None
     _host = lib
     return lib
 
@@ -841,6 +909,95 @@ class HostEncoder:
         if getattr(self, "open", False):
             self.lib.flake_amd_encode_close(C.byref(self.ctx))
             self.open = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def write_streaminfo(si: HostStreaminfo) -> bytes:
+    """The 34 STREAMINFO bytes of si (flake_amd_write_streaminfo)."""
+    buf = (C.c_ubyte * 34)()
+    load_host_library().flake_amd_write_streaminfo(C.byref(si), buf)
+    return bytes(buf)
+
+
+def read_streaminfo(data34: bytes):
+    """flake_amd_read_streaminfo: (HostStreaminfo, bits 32..35 of the sample count).  Raises ValueError for a block
+    no stream can carry."""
+    if len(data34) != 34:
+        raise ValueError("a STREAMINFO block is 34 bytes")
+    si = HostStreaminfo()
+    buf = (C.c_ubyte * 34).from_buffer_copy(bytes(data34))
+    hi = load_host_library().flake_amd_read_streaminfo(buf, C.byref(si))
+    if hi < 0:
+        raise ValueError("invalid STREAMINFO")
+    return si, hi
+
+
+def index_frames(si: HostStreaminfo, stream, cap: int | None = None):
+    """flake_amd_index_frames (CPU only): (frame sizes int32[], bytes they cover), or None where the stream does not
+    start with a frame."""
+    st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
+                              else stream, dtype=np.uint8)
+    if cap is None:
+        cap = st.size // 8 + 1            # no frame is shorter than its header and CRC-16
+    sizes = np.zeros(max(cap, 1), dtype=np.int32)
+    used = C.c_size_t(0)
+    n = load_host_library().flake_amd_index_frames(C.byref(si), st.ctypes.data if st.size else None, st.size,
+                                                   sizes.ctypes.data, cap, C.byref(used))
+    if n < 0:
+        return None
+    return sizes[:n].copy(), int(used.value)
+
+
+class HostDecoder:
+    """A decoder of the host C layer (flake_amd_decode_*): indexed frames in, PCM out, the MD5 of everything returned
+    carried along.  ctypes only; no compute here."""
+
+    def __init__(self, si: HostStreaminfo):
+        self.lib = load_host_library()
+        self.si = si
+        self._d = self.lib.flake_amd_decode_open(C.byref(si))
+        if not self._d:
+            raise FlakeHipError(-1, "flake_amd_decode_open", self.lib.flake_amd_decode_last_error(None).decode())
+
+    def last_error(self) -> str:
+        return self.lib.flake_amd_decode_last_error(self._d).decode()
+
+    def decode_frames(self, stream, frame_sizes, pcm_cap: int, sample_bytes: int = 4) -> np.ndarray:
+        """The frames of stream (sizes from index_frames) as [samples][channels] int32, or int16 with sample_bytes 2.
+        Raises FlakeHipError naming the frame that failed."""
+        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
+                                  else stream, dtype=np.uint8)
+        fs = np.ascontiguousarray(frame_sizes, dtype=np.int32)
+        out = np.zeros((pcm_cap, self.si.channels), dtype=np.int16 if sample_bytes == 2 else np.int32)
+        n = self.lib.flake_amd_decode_frames(self._d, st.ctypes.data if st.size else None, st.size,
+                                             fs.ctypes.data if fs.size else None, len(fs),
+                                             out.ctypes.data if out.size else None, sample_bytes, pcm_cap)
+        if n < 0:
+            raise FlakeHipError(int(n), "flake_amd_decode_frames", self.last_error())
+        return out[:n]
+
+    def md5(self) -> bytes:
+        """flake_amd_decode_md5: of everything decoded so far."""
+        buf = (C.c_ubyte * 16)()
+        if self.lib.flake_amd_decode_md5(self._d, buf) != 0:
+            raise RuntimeError("flake_amd_decode_md5")
+        return bytes(buf)
+
+    def close(self) -> None:
+        if getattr(self, "_d", None):
+            self.lib.flake_amd_decode_close(self._d)
+            self._d = None
 
     def __enter__(self):
         return self

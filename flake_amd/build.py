@@ -22,12 +22,15 @@ LIB = os.path.join(PKG, "lib")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 HIP_SRCS = ["csrc/k0_prepare.hip", "csrc/k1_autocorr.hip", "csrc/k2_lpc.hip", "csrc/k3_encode.hip", "csrc/k3s_search.hip",
-            "csrc/k4_assemble.hip", "csrc/k5_verify.hip", "csrc/k6_md5.hip", "csrc/api.hip"]
+            "csrc/k4_assemble.hip", "csrc/k5_verify.hip", "csrc/k6_md5.hip", "csrc/k7_decode.hip", "csrc/api.hip"]
 HIP_HDRS = ["csrc/kernels.h", "csrc/device_util.h", "csrc/lpc_reg.h", "csrc/k3_common.h", "csrc/vbs_schedule.h",
-            "csrc/vbs_block_lookup.h", "../include/flakehip.h"]
+            "csrc/vbs_block_lookup.h", "csrc/flac_parse.h", "../include/flakehip.h"]
 HIP_DEPS = HIP_SRCS + HIP_HDRS
 HOST_SRCS = ["host/flake_host.c", "host/flake_set.c", "host/synth.c", "host/md5.c"]
-HOST_DEPS = HOST_SRCS + ["host/host_internal.h", "../include/flakehip.h", "../include/flake_amd.h"]
+# the decoding side goes into libflake_amd.so only: the drop-in libflake.so exports what libflake has, and libflake
+# has no decoder
+HOST_DECODE_SRCS = ["host/flake_decode.c"]
+HOST_DEPS = HOST_SRCS + HOST_DECODE_SRCS + ["host/host_internal.h", "../include/flakehip.h", "../include/flake_amd.h"]
 
 # -ffp-contract=off is load-bearing: the fp64 LPC stages must round after every
 # multiply and add to reproduce the reference bit for bit.
@@ -78,7 +81,7 @@ def build_hip(force: bool = False, extra: list[str] | None = None, out_name: str
 
 def build_host(force: bool = False) -> str:
     out = os.path.join(LIB, "libflake_amd.so")
-    srcs = [os.path.join(PKG, s) for s in HOST_SRCS if os.path.exists(os.path.join(PKG, s))]
+    srcs = [os.path.join(PKG, s) for s in HOST_SRCS + HOST_DECODE_SRCS if os.path.exists(os.path.join(PKG, s))]
     if not srcs:
         return ""
     if force or _stale(out, HOST_DEPS):

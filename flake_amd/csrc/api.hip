@@ -133,7 +133,7 @@ struct fhip_ctx {
     bool verify = false;
     DevBuf<fhip::VerifyFrame> d_vws;
     DevBuf<fhip_verify_rec> d_vrec;
-    DevBuf<long long> d_vsum;                 // [4] summary, then [1] key scratch
+    DevBuf<long long> d_vsum;                 // [4] summary, then [1] key scratch, then K7's sample count and written end
     DevBuf<uint8_t> d_vstream;                // fhip_verify_frames: the host stream / sizes / PCM uploaded
     DevBuf<int32_t> d_vfb;
     DevBuf<int32_t> d_vpcm;
@@ -197,10 +197,10 @@ void note_launch(const char *fmt, ...)
 
 namespace {
 
-constexpr int kNumKernels = 7;
+constexpr int kNumKernels = 8;
 const char *const kKernelNames[kNumKernels] = {"k_prepare", "k_autocorr", "k_lpc", "k_encode", "k_assemble",
-                                               "k_order_search", "k_verify"};
-constexpr int kProfVerify = 6;
+                                               "k_order_search", "k_verify", "k_decode"};
+constexpr int kProfVerify = 6, kProfDecode = 7;
 
 int fail_hip(fhip_ctx *c, hipError_t e, const char *what)
 {
@@ -469,7 +469,7 @@ int run_pipeline(fhip_ctx *c, const int32_t *pcm, int nframes, int n,
 // K5's workspace for nframes frames (grows; a handle's own batches never need more than ws_frames)
 int ensure_verify(fhip_ctx *c, size_t nframes)
 {
-    HIP_TRY(c, c->d_vsum.reserve(5));
+    HIP_TRY(c, c->d_vsum.reserve(8));          // (K7's host entry keeps its sample count at [5])
     const size_t want = std::max(nframes, c->ws_frames);
     HIP_TRY(c, c->d_vws.reserve(want));
     HIP_TRY(c, c->d_vrec.reserve(want));
@@ -2519,6 +2519,113 @@ int fhip_last_verify_failure(const fhip_ctx *c, int64_t *summary, fhip_verify_re
     if (summary) for (int i = 0; i < 4; i++) summary[i] = c->vfail_sum[i];
     if (first) *first = c->vfail_rec;
     return c->vfail_sum[1] > 0 ? 1 : 0;
+}
+
+// ---- K7: decoding ----------------------------------------------------------------------------------
+
+namespace {
+// The entries' checks, with nothing queued and the launch list left empty where they refuse.
+int decode_check(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *out)
+{
+    if (!c) return FHIP_E_INVALID;
+    c->launches.clear();
+    c->md5_log_entry = -1;
+    if (!in || !out || !out->summary || !out->nsamples) return fail(c, FHIP_E_INVALID, "null argument");
+    if (in->nframes < 0 || in->stream_bytes < 0 || out->pcm_cap < 0 || in->first_number < -1)
+        return fail(c, FHIP_E_INVALID, "negative count");
+    if (in->nframes > c->max_frames) return fail(c, FHIP_E_INVALID, "nframes exceeds the handle's max_frames");
+    if (in->variable_blocks != 0 && in->variable_blocks != 1) return fail(c, FHIP_E_INVALID, "variable_blocks is 0 or 1");
+    if (in->nframes > 0 && (!in->stream || !in->frame_bytes)) return fail(c, FHIP_E_INVALID, "null stream");
+    if (out->pcm_cap > 0 && !out->pcm) return fail(c, FHIP_E_INVALID, "null pcm");
+    return FHIP_OK;
+}
+
+// Queue K7 on the handle's stream; all of in / out is device memory.  The restored subframes go through d_smp, the
+// frame records through K5's workspace: an encode call that follows overwrites both from the start, as it always has.
+int run_decode(fhip_ctx *c, const fhip_decode_in &in, const fhip_decode_out &out)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_verify(c, (size_t)in.nframes);
+    if (rc != FHIP_OK) return rc;
+    const fhip_params &p = c->p;
+    fhip::DecodeArgs a{in.stream, in.stream_bytes, in.frame_bytes, in.nframes, in.variable_blocks, in.first_number,
+                       p.channels, p.bits_per_sample, p.block_size, p.sample_rate, c->pcm_format, out.pcm, out.pcm_cap,
+                       c->d_smp, c->d_vws, out.frames, reinterpret_cast<long long *>(out.summary),
+                       reinterpret_cast<unsigned long long *>(c->d_vsum + 4), reinterpret_cast<long long *>(out.nsamples),
+                       c->d_vsum + 6};
+    Prof pr(c, kProfDecode, c->profiling);
+    HIP_TRY(c, fhip::launch_decode(c->stream, a));
+    return FHIP_OK;
+}
+}  // namespace
+
+int fhip_decode_frames_dev(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *out)
+{
+    int rc = decode_check(c, in, out);
+    if (rc != FHIP_OK) return rc;
+    LaunchScope ls(c);
+    return run_decode(c, *in, *out);
+}
+
+int fhip_decode_frames(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *out)
+{
+    int rc = decode_check(c, in, out);
+    if (rc != FHIP_OK) return rc;
+    const size_t nf = (size_t)in->nframes, sb = (size_t)in->stream_bytes;
+    long long total = 0;
+    for (size_t f = 0; f < nf; f++) {
+        if (in->frame_bytes[f] < 0) return fail(c, FHIP_E_INVALID, "negative frame size");
+        total += in->frame_bytes[f];
+    }
+    if (total != in->stream_bytes) return fail(c, FHIP_E_INVALID, "frame_bytes do not add up to stream_bytes");
+    LaunchScope ls(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    rc = ensure_verify(c, nf);
+    if (rc != FHIP_OK) return rc;
+    // no frame holds more than block_size samples: the staging output never needs more than that, whatever pcm_cap says
+    const long long most = (long long)nf * c->p.block_size;
+    const long long cap = out->pcm_cap < most ? out->pcm_cap : most;
+    const size_t nv = (size_t)cap * (size_t)c->p.channels;
+    HIP_TRY(c, c->d_vstream.reserve(sb));
+    HIP_TRY(c, c->d_vfb.reserve(nf));
+    HIP_TRY(c, c->d_vpcm.reserve(nv));
+    if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_vstream, in->stream, sb, hipMemcpyHostToDevice, c->stream));
+    if (nf) HIP_TRY(c, hipMemcpyAsync(c->d_vfb, in->frame_bytes, nf * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    fhip_decode_in din = *in;
+    din.stream = c->d_vstream; din.frame_bytes = c->d_vfb;
+    // summary [0..4), K7's key scratch [4], the sample count [5], the end of what was written [6]
+    fhip_decode_out dout{c->d_vpcm, cap, c->d_vrec, reinterpret_cast<int64_t *>(c->d_vsum.get()),
+                         reinterpret_cast<int64_t *>(c->d_vsum.get() + 5)};
+    rc = run_decode(c, din, dout);
+    if (rc != FHIP_OK) return rc;
+    long long sum[7] = {0, 0, -1, 0, 0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(sum, c->d_vsum, sizeof sum, hipMemcpyDeviceToHost, c->stream));
+    if (out->frames && nf)
+        HIP_TRY(c, hipMemcpyAsync(out->frames, c->d_vrec, nf * sizeof(fhip_verify_rec), hipMemcpyDeviceToHost, c->stream));
+    rc = fhip_sync(c);
+    if (rc != FHIP_OK) return rc;
+    // the samples, up to the end of the last frame that was placed and written: nothing behind it is touched (a frame
+    // refused for pcm_cap leaves the caller's buffer as it was); a failed frame before it leaves its own range unspecified
+    const long long wend = sum[6] < cap ? sum[6] : cap;
+    if (wend > 0) {
+        HIP_TRY(c, hipMemcpyAsync(out->pcm, c->d_vpcm, (size_t)wend * (size_t)c->p.channels * c->pcm_width(),
+                                  hipMemcpyDeviceToHost, c->stream));
+        rc = fhip_sync(c);
+        if (rc != FHIP_OK) return rc;
+    }
+    for (int i = 0; i < 4; i++) { out->summary[i] = sum[i]; c->vfail_sum[i] = sum[i]; }
+    out->nsamples[0] = sum[5];
+    c->vfail_rec = fhip_verify_rec{(int32_t)sum[3], -1, -1, -1};
+    c->vfail_has_number = false;
+    if (sum[1] <= 0) return FHIP_OK;
+    fhip_verify_rec r{(int32_t)sum[3], -1, -1, -1};
+    if (sum[2] >= 0) HIP_TRY(c, hipMemcpy(&r, c->d_vrec + sum[2], sizeof r, hipMemcpyDeviceToHost));
+    c->vfail_rec = r;
+    char buf[256];
+    snprintf(buf, sizeof buf, "decoding failed: %lld of %lld frames are not valid; first: frame %lld, %s (subframe %d, bit %d)",
+             sum[1], sum[0], sum[2], verify_status_name((int)sum[3]), r.subframe, r.bit);
+    c->err = buf;
+    return FHIP_E_VERIFY;
 }
 
 int fhip_prepare_frames(fhip_ctx *c, const int32_t *pcm, int nframes, int n,

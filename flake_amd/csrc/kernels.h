@@ -302,6 +302,29 @@ struct VerifyArgs {
 };
 hipError_t launch_verify(hipStream_t st, const VerifyArgs &a);
 
+// K7 (k7_decode.hip): a batch of frames back to PCM, by the format alone.  Three launches on st, as K5's:
+// k_decode_frames (one workgroup: offsets, headers, where each frame's samples go, numbering; fills ws[], zeroes the
+// summary, leaves the sample count), k_decode (a wave per frame), k_decode_final (summary[2..3]).
+struct DecodeArgs {
+    const uint8_t *stream; long long stream_bytes;
+    const int32_t *frame_bytes; int nframes;
+    int variable_blocks;                         // the blocking-strategy bit every header must carry: 1 = sample numbers
+    long long first_number;                      // the number frame 0 must carry; < 0: only continuity is checked
+    int channels, bps, block_size, sample_rate;  // the handle's: header codes are held against them; block_size is
+                                                 // the largest block accepted and the stride of rows
+    int pcm_format;                              // FHIP_PCM_*: S16 = pcm addresses int16
+    void *pcm; long long pcm_cap;                // interleaved output, pcm_cap samples per channel
+    int32_t *rows;                               // [nframes][channels][block_size] restored subframes (the handle's d_smp)
+    VerifyFrame *ws;                             // [nframes]
+    fhip_verify_rec *recs;                       // optional [nframes]
+    long long *summary;                          // [4]
+    unsigned long long *key;                     // [1] scratch: (first failing frame << 8) | status
+    long long *nsamples;                         // [1] samples per channel of the frames whose header pass succeeded
+    long long *written_end;                      // [1] where the last of those frames ends in pcm (samples per channel):
+                                                 // nothing at or behind it is written
+};
+hipError_t launch_decode(hipStream_t st, const DecodeArgs &a);
+
 // K6 (k6_md5.hip): the STREAMINFO MD5 of many streams, one lane per stream.  The update hashes, for stream s, the
 // blocks seg_block[seg_first[s] .. seg_first[s + 1]) -- indices of block_vals-sample blocks (block_size * channels
 // interleaved values) of pcm -- in that order.  pcm_format as for K0; bytes_per_sample = (bits_per_sample + 7) / 8.

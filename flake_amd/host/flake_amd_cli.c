@@ -17,6 +17,13 @@
  * flake_amd_set_enable_verify, every frame held to its own stream's numbering) and exits non-zero with the
  * verifier's message when one does not.
  *
+ *   flake_amd_cli --decode in.flac out.wav
+ *
+ * --decode turns a FLAC file back into canonical PCM WAV on the GPU (flake_amd_decode_*): it checks the "fLaC" marker,
+ * reads STREAMINFO, skips the other metadata blocks, finds the frames on the CPU (flake_amd_index_frames), decodes
+ * them in batches and compares the MD5 of what it wrote with STREAMINFO's unless that is all zero.  A frame that does
+ * not decode, or an MD5 mismatch, ends in a non-zero exit status with the frame named on stderr.
+ *
  * Only canonical PCM WAV (8/16/24/32 bit) is read; this is a harness for the
  * host API, not a replacement for the reference's libpcm_io.
  */
@@ -259,12 +266,124 @@ static int run_set(const char *outdir, char **inputs, int ninputs, int synth_str
     return 0;
 }
 
+/* ---- --decode: a FLAC file back to canonical PCM WAV ----------------- */
+static void wr32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
+
+static void wav_header(uint8_t h[44], int channels, int rate, int bps, uint32_t frames)
+{
+    const int bytes = (bps + 7) / 8;
+    const uint32_t data = frames * (uint32_t)(channels * bytes);
+    memcpy(h, "RIFF", 4); wr32(h + 4, 36 + data); memcpy(h + 8, "WAVEfmt ", 8); wr32(h + 16, 16);
+    h[20] = 1; h[21] = 0; h[22] = (uint8_t)channels; h[23] = 0;
+    wr32(h + 24, (uint32_t)rate); wr32(h + 28, (uint32_t)(rate * channels * bytes));
+    h[32] = (uint8_t)(channels * bytes); h[33] = 0; h[34] = (uint8_t)bps; h[35] = 0;
+    memcpy(h + 36, "data", 4); wr32(h + 40, data);
+}
+
+static int run_decode(const char *in, const char *out)
+{
+    FILE *fi = fopen(in, "rb");
+    if (!fi) { perror(in); return 1; }
+    fseek(fi, 0, SEEK_END);
+    const long flen = ftell(fi);
+    fseek(fi, 0, SEEK_SET);
+    uint8_t *file = (uint8_t *)malloc(flen > 0 ? (size_t)flen : 1);          /* the file whole in memory (a harness) */
+    if (!file || flen < 0 || fread(file, 1, (size_t)flen, fi) != (size_t)flen) { fprintf(stderr, "cannot read %s\n", in); return 1; }
+    fclose(fi);
+    const size_t len = (size_t)flen;
+    if (len < 4 + 4 + 34 || memcmp(file, "fLaC", 4) || (file[4] & 0x7F) != 0 ||
+        ((size_t)file[5] << 16 | (size_t)file[6] << 8 | file[7]) != 34) {
+        fprintf(stderr, "%s: not a FLAC file (no fLaC marker followed by STREAMINFO)\n", in);
+        return 1;
+    }
+    FlakeAmdStreaminfo si;
+    if (flake_amd_read_streaminfo(file + 8, &si) < 0) { fprintf(stderr, "%s: invalid STREAMINFO\n", in); return 1; }
+    size_t pos = 4;
+    for (;;) {                                                               /* skip every metadata block */
+        if (pos + 4 > len) { fprintf(stderr, "%s: metadata runs past the file\n", in); return 1; }
+        const int last = file[pos] >> 7;
+        pos += 4 + ((size_t)file[pos + 1] << 16 | (size_t)file[pos + 2] << 8 | file[pos + 3]);
+        if (pos > len) { fprintf(stderr, "%s: metadata runs past the file\n", in); return 1; }
+        if (last) break;
+    }
+    FlakeAmdDecoder *d = flake_amd_decode_open(&si);
+    if (!d) { fprintf(stderr, "decoder init failed: %s\n", flake_amd_decode_last_error(NULL)); return 1; }
+    FILE *fo = fopen(out, "wb");
+    if (!fo) { perror(out); return 1; }
+    const int nch = (int)si.channels, bps = (int)si.bits_per_sample, wbytes = (bps + 7) / 8;
+    const int narrow = bps == 16;                                            /* int16 all the way (the 2-byte path) */
+    const int maxn = si.max_block_size ? (int)si.max_block_size : 65535;
+    const int batch = (4 << 20) / maxn < 1024 ? (4 << 20) / maxn : 1024;     /* frames per round: about 4M samples */
+    int *sizes = (int *)malloc(sizeof(int) * (size_t)batch);
+    const size_t cap = (size_t)batch * (size_t)maxn;
+    void *pcm = malloc(cap * (size_t)nch * (narrow ? 2 : 4));
+    uint8_t *raw = (uint8_t *)malloc(cap * (size_t)nch * (size_t)wbytes);
+    if (!sizes || !pcm || !raw) { fprintf(stderr, "out of memory\n"); return 1; }
+    uint8_t wh[44];
+    memset(wh, 0, sizeof wh);
+    fwrite(wh, 1, 44, fo);
+    unsigned long long total = 0, nframes_done = 0;
+    int rc = 0;
+    while (pos < len) {
+        size_t used = 0;
+        const long long nf = flake_amd_index_frames(&si, file + pos, len - pos, sizes, batch, &used);
+        if (nf <= 0) {
+            fprintf(stderr, "%s: frame %llu (at byte %llu, after %llu samples): %s\n", in, nframes_done,
+                    (unsigned long long)pos, total,
+                    nf < 0 ? "not a frame header of this stream" : "the frame is cut or its CRC-16 fails");
+            rc = 1;
+            break;
+        }
+        const long long ns = flake_amd_decode_frames(d, file + pos, used, sizes, (int)nf, pcm, narrow ? 2 : 4, cap);
+        if (ns < 0) { fprintf(stderr, "decode error: %s\n", flake_amd_decode_last_error(d)); rc = 1; break; }
+        const size_t vals = (size_t)ns * (size_t)nch;
+        if (narrow) {
+            fwrite(pcm, 2, vals, fo);                                        /* (little-endian hosts, as the reader) */
+        } else {
+            const int32_t *v = (const int32_t *)pcm;
+            for (size_t i = 0; i < vals; i++) {
+                const uint32_t u = wbytes == 1 ? (uint32_t)(v[i] + 128) : (uint32_t)v[i];
+                for (int b = 0; b < wbytes; b++) raw[i * (size_t)wbytes + (size_t)b] = (uint8_t)(u >> (8 * b));
+            }
+            fwrite(raw, (size_t)wbytes, vals, fo);
+        }
+        total += (unsigned long long)ns;
+        nframes_done += (unsigned long long)nf;
+        pos += used;
+    }
+    wav_header(wh, nch, (int)si.sample_rate, bps, (uint32_t)total);
+    fseek(fo, 0, SEEK_SET);
+    fwrite(wh, 1, 44, fo);
+    fclose(fo);
+    if (!rc) {
+        static const uint8_t zero[16] = {0};
+        uint8_t md5[16];
+        flake_amd_decode_md5(d, md5);
+        if (memcmp(si.md5sum, zero, 16) && memcmp(si.md5sum, md5, 16)) {
+            fprintf(stderr, "%s: MD5 mismatch: the decoded samples are not what STREAMINFO's signature was made of\n", in);
+            rc = 1;
+        } else if (si.samples && (unsigned long long)si.samples != (total & 0xFFFFFFFFull)) {
+            fprintf(stderr, "%s: %llu samples decoded, STREAMINFO says %u\n", in, total, si.samples);
+            rc = 1;
+        }
+    }
+    if (!rc) fprintf(stderr, "%llu sample-frames decoded\n", total);
+    flake_amd_decode_close(d);
+    free(file); free(sizes); free(pcm); free(raw);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
     FlakeAmdContext s;
     memset(&s, 0, sizeof s);
     int level = 5, bsize = -1, synth = 0, channels = 2, bps = 16, verify = 0, synth_streams = 0;
     const char *in = NULL, *out = NULL, *setdir = NULL;
+    for (int i = 1; i < argc; i++) {
+        if (strcmp(argv[i], "--decode")) continue;
+        if (argc != 4) { fprintf(stderr, "usage: %s --decode in.flac out.wav\n", argv[0]); return 2; }
+        return run_decode(argv[i == 1 ? 2 : 1], argv[i == 3 ? 2 : 3]);
+    }
     for (int i = 1; i < argc; i++) if (!strcmp(argv[i], "--set")) setdir = "";
     if (setdir) {
         char **inputs = (char **)calloc((size_t)argc, sizeof(char *));

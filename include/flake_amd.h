@@ -240,6 +240,54 @@ FLAKE_AMD_API int flake_amd_set_last_verify_failure(const FlakeAmdSet *g, int *s
 FLAKE_AMD_API const char *flake_amd_set_last_error(const FlakeAmdSet *g);
 FLAKE_AMD_API void flake_amd_set_close(FlakeAmdSet *g);
 
+/* ---- decoding ---------------------------------------------------------- */
+
+/*
+ * The inverse of flake_amd_write_streaminfo: the 34 bytes of a STREAMINFO block into *si.  The format's sample count
+ * has 36 bits and FlakeAmdStreaminfo.samples, which keeps libflake's layout, has 32: si->samples receives the low 32
+ * and the return value is the upper four (0 .. 15; 0 for everything flake_amd_write_streaminfo writes).  -1 for a
+ * null pointer or a block no stream can carry (sample rate 0 or above 655350, fewer than 4 bits per sample).
+ */
+FLAKE_AMD_API int flake_amd_read_streaminfo(const unsigned char data34[34], FlakeAmdStreaminfo *si);
+/*
+ * Frame discovery in a foreign stream, on the CPU (no call into the HIP layer): the sizes of the whole frames that
+ * stream[0 .. bytes) begins with, at most cap of them, into frame_sizes; the return value is their count and *consumed
+ * (optional) the bytes they cover, so that a caller can feed a file in pieces, each starting where the last one's
+ * *consumed ended.  A frame starts at a CANDIDATE -- the sync code, header codes that agree with si (channels, bits per
+ * sample, sample rate, a block size within max_block_size), a valid CRC-8, the blocking strategy of the piece's first
+ * frame and the expected number: the previous frame's + 1, or + its size in a variable-block-size stream -- and ends at
+ * the next candidate for which the CRC-16 of the span holds; a candidate that fails either test is skipped, since audio
+ * data may hold a byte sequence that looks like a header.  The last frame ends at `bytes` if its CRC-16 holds there;
+ * otherwise (a piece cut inside a frame) it is not counted.  The first frame of a piece may carry any number.
+ * Returns -1 when stream[0] does not start a frame (garbage at the start) or for a bad argument.
+ */
+FLAKE_AMD_API long long flake_amd_index_frames(const FlakeAmdStreaminfo *si, const unsigned char *stream, size_t bytes,
+                                               int *frame_sizes, int cap, size_t *consumed);
+/*
+ * A decoder for one stream on the device (fhip_decode_frames, include/flakehip.h: K7).  flake_amd_decode_open sizes
+ * its handle from si (channels, sample rate, bits per sample; blocks up to max_block_size, 65535 when that is 0); the
+ * device is FLAKE_AMD_DEVICE and a GPU batch holds up to FLAKE_AMD_BATCH frames (default 1024; fewer for very long
+ * blocks), as for encoding.  NULL on failure: flake_amd_decode_last_error(NULL) says why.
+ *
+ * flake_amd_decode_frames decodes nframes frames, back to back in stream[0 .. bytes) with the sizes
+ * flake_amd_index_frames found, into pcm: channel-interleaved int32 with sample_bytes 4, int16_t with 2
+ * (bits_per_sample <= 16 only); pcm_cap_samples counts samples per channel.  The blocking strategy and the first
+ * number are read from the first frame the decoder ever sees; from then on every frame must carry the number that
+ * follows its predecessor's, across calls.  Returns the samples per channel written, or -1:
+ * flake_amd_decode_last_error names the frame (counted from the decoder's first), its status (FHIP_VERIFY_*), subframe
+ * and bit.  A failed call leaves the decoder's numbering and hash where they were before the failing batch.
+ * Everything returned is hashed (md5.c) at the stream's sample width, so that flake_amd_decode_md5 after the last
+ * frame is what STREAMINFO's md5sum must be.
+ */
+typedef struct FlakeAmdDecoder FlakeAmdDecoder;
+FLAKE_AMD_API FlakeAmdDecoder *flake_amd_decode_open(const FlakeAmdStreaminfo *si);
+FLAKE_AMD_API long long flake_amd_decode_frames(FlakeAmdDecoder *d, const unsigned char *stream, size_t bytes,
+                                                const int *frame_sizes, int nframes, void *pcm, int sample_bytes,
+                                                size_t pcm_cap_samples);
+FLAKE_AMD_API int flake_amd_decode_md5(FlakeAmdDecoder *d, unsigned char md5[16]);
+FLAKE_AMD_API const char *flake_amd_decode_last_error(const FlakeAmdDecoder *d);
+FLAKE_AMD_API void flake_amd_decode_close(FlakeAmdDecoder *d);
+
 /* Deterministic synthetic PCM, channel-interleaved int32 as
  * flake_encode_frame() expects: nframes blocks of n samples per channel,
  * starting at absolute frame index first_frame. */

@@ -585,6 +585,64 @@ FHIP_API int fhip_last_verify_failure(const fhip_ctx *ctx, int64_t *summary, fhi
  * with many streams needs to name the frame: the frame's index alone does not say where a split block's pieces start. */
 FHIP_API int fhip_last_verify_number(const fhip_ctx *ctx, uint32_t *number);
 
+/* ---- decoding ------------------------------------------------------- */
+
+/*
+ * FLAC frames back to PCM (K7): a decoder that follows the specification, for a batch of frames whose byte sizes the
+ * caller knows (flake_amd_index_frames finds them in a foreign stream, on the CPU).  It accepts what the verifier
+ * accepts -- CONSTANT, VERBATIM, FIXED 0-4, LPC 1-32 (precision 1-15, shift 0-31), wasted bits, RICE / RICE2, escape
+ * partitions (raw width 0 included), partition orders 0-15 where the block allows them, channel assignments 0-10,
+ * 4-32 bits per sample, block sizes 1 .. params.block_size -- and restores samples the way libFLAC does: a 64-bit
+ * prediction sum, an arithmetic shift, the sample wrapped to int32 (the side channel of a 32-bit stream is read
+ * wrapped to int32 too).  The header codes are held against the handle's channels, bits_per_sample and sample_rate;
+ * everything else of fhip_params is unused, so any handle serves, fixed-block or allow_vbs.
+ *
+ * Frame f's samples start at the sum of the block sizes carried by the headers before it.  A header that fails a
+ * check of its own (sync, codes, CRC-8) carries none -- its block size cannot be trusted -- so the frames behind it
+ * follow the last good one; a header that is good but misnumbered or too large for pcm_cap keeps its room.  Numbering is the CALL's, not the handle's: with variable_blocks 0 every header carries a frame
+ * number, which goes up by 1, and every frame but the last holds the same number of samples; with 1 it carries a
+ * sample number, which goes up by the previous frame's size.  Bit 15 of every header must equal variable_blocks.
+ * With first_number >= 0 the first frame must carry it; with -1 only continuity is checked.
+ *
+ * Per frame one fhip_verify_rec with the verifier's status codes (SAMPLES is never returned; `sample` is -1):
+ * HEADER, CRC8, NUMBER (numbering, a block larger than params.block_size, or a frame whose samples would not fit
+ * pcm_cap: nothing of it is written), SYNTAX (reserved subframe type or coding method, precision code 15, negative
+ * shift, a partition order the block cannot take, a read past the frame's end -- a unary run that does not end inside
+ * the frame is one), PADDING, CRC16, LENGTH.  A frame that fails leaves unspecified values in its own sample range
+ * only; the other frames are decoded as if it were good.  Every stream read stays inside the frame, every write inside
+ * [0, pcm_cap): a corrupt stream ends in a status code.  STREAMINFO's MD5 is the caller's to check.
+ */
+typedef struct fhip_decode_in {
+    const uint8_t *stream;        /* the frames back to back */
+    int64_t        stream_bytes;
+    const int32_t *frame_bytes;   /* [nframes] size of each frame; nframes <= the handle's max_frames */
+    int32_t        nframes;
+    int32_t        variable_blocks;   /* 0: frames carry frame numbers, 1: sample numbers */
+    int64_t        first_number;  /* the number frame 0 must carry; -1: not checked */
+} fhip_decode_in;
+
+typedef struct fhip_decode_out {
+    int32_t         *pcm;         /* [pcm_cap][channels] interleaved int32; int16_t storage while the handle's format
+                                     is FHIP_PCM_S16 (bits_per_sample <= 16, as that format requires) */
+    int64_t          pcm_cap;     /* samples per channel */
+    fhip_verify_rec *frames;      /* optional [nframes] */
+    int64_t         *summary;     /* [4] as fhip_verify_out: frames, frames failed, first failing frame (-1), its status */
+    int64_t         *nsamples;    /* [1] samples per channel written: the sizes of the frames whose header, number and
+                                     place were good (a frame that fails later still counts: its range is unspecified) */
+} fhip_decode_out;
+
+/* All pointers DEVICE pointers; asynchronous on the handle's stream, no host synchronisation.  Starts a launch list
+ * ("k_decode_frames", "k_decode", "k_decode_final") and is timed as "k_decode" under fhip_set_profiling.  The restored
+ * subframes pass through the handle's sample workspace, so the call must not overlap an encode call of the same
+ * handle on another stream; a later encode call is unaffected.  FHIP_E_INVALID with nothing queued and an empty
+ * launch list for null pointers, negative counts or nframes > max_frames. */
+FHIP_API int fhip_decode_frames_dev(fhip_ctx *ctx, const fhip_decode_in *in, const fhip_decode_out *out);
+/* The same with HOST pointers: uploads, runs, downloads, synchronises; it allocates nothing beyond grow-only staging at
+ * first use.  Also FHIP_E_INVALID when frame_bytes does not add up to stream_bytes.  FHIP_OK, or FHIP_E_VERIFY when a
+ * frame failed: fhip_last_error() names the first failing frame, its status, subframe and bit,
+ * fhip_last_verify_failure() returns the same as numbers, and the samples of the good frames are still delivered. */
+FHIP_API int fhip_decode_frames(fhip_ctx *ctx, const fhip_decode_in *in, const fhip_decode_out *out);
+
 /* ---- MD5 of many streams (K6) ---------------------------------------- */
 
 /*
@@ -659,7 +717,7 @@ FHIP_API int fhip_get_kernel_times(fhip_ctx *ctx, const char **names, double *ms
  * one or two workgroups per tile), "tail" (K2 runs inside K1), "fused" (K1 applies K0's decisions),
  * "narrow" (16-bit sample rows).  The calls that start a new list are the encode entries
  * (fhip_encode_subframes*, fhip_frames_packed_begin / fhip_encode_frames_packed, the VBS entries)
- * and fhip_prepare_ahead, and the fhip_md5_* entries.  A host-side record: it adds no device work.  (One exception:
+ * and fhip_prepare_ahead, the fhip_md5_* entries and fhip_decode_frames(_dev).  A host-side record: it adds no device work.  (One exception:
  * "k_md5_streams<int16_t,2> fast" / "... general" name a choice that is made on the device when the block shape
  * allows the fast path; asking for the list then waits for that launch.)  names[0 .. cap) receive
  * strings owned by the handle, valid until its next such call; returns the number of launches. */
