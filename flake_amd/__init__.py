@@ -148,6 +148,18 @@ class DecodeOut(C.Structure):
                 ("nsamples", C.c_void_p)]
 
 
+class DecodeSegments(C.Structure):
+    """``fhip_decode_segments``"""
+    _fields_ = [("seg_first", C.c_void_p), ("nsegs", C.c_int32), ("seg_number", C.c_void_p),
+                ("seg_variable", C.c_void_p), ("seg_start", C.c_void_p), ("seg_samples", C.c_void_p),
+                ("seg_failed", C.c_void_p)]
+
+
+class DecodeMd5(C.Structure):
+    """``fhip_decode_md5``"""
+    _fields_ = [("states", C.c_void_p), ("nstreams", C.c_int32), ("seg_stream", C.c_void_p)]
+
+
 # numpy view of fhip_md5_state (96 bytes): K6's running hash of one stream
 MD5_STATE_DTYPE = np.dtype([("h", "<u4", (4,)), ("nbytes", "<u8"), ("fill", "<u4"), ("reserved", "<u4"),
                             ("tail", "u1", (64,))])
@@ -218,6 +230,11 @@ def load_library() -> C.CDLL:
         "fhip_last_verify_failure": (i, [vp, vp, vp]),
         "fhip_decode_frames_dev": (i, [vp, C.POINTER(DecodeIn), C.POINTER(DecodeOut)]),
         "fhip_decode_frames": (i, [vp, C.POINTER(DecodeIn), C.POINTER(DecodeOut)]),
+        "fhip_decode_frames_segments_dev": (i, [vp, C.POINTER(DecodeIn), C.POINTER(DecodeSegments),
+                                                C.POINTER(DecodeOut)]),
+        "fhip_decode_frames_segments": (i, [vp, C.POINTER(DecodeIn), C.POINTER(DecodeSegments), C.POINTER(DecodeOut),
+                                            C.POINTER(DecodeMd5)]),
+        "fhip_md5_update_ranges_dev": (i, [vp, vp, i, vp, vp, vp, vp, vp]),
         "fhip_get_kernel_times": (i, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double),
                                       C.POINTER(i), i, i]),
         "fhip_last_launches": (i, [vp, C.POINTER(C.c_char_p), i]),
@@ -275,6 +292,7 @@ ABI_SYMBOLS = (
     "fhip_verify_frames_blocks_ragged",
     "fhip_autocorr_tile",
     "fhip_decode_frames_dev", "fhip_decode_frames",
+    "fhip_decode_frames_segments_dev", "fhip_decode_frames_segments", "fhip_md5_update_ranges_dev",
 )
 
 
@@ -546,6 +564,59 @@ class Encoder:
         do = DecodeOut(_ptr(pcm), pcm_cap, _ptr(records), _ptr(summary), _ptr(nsamples))
         self._check(self.lib.fhip_decode_frames_dev(self._h, C.byref(di), C.byref(do)), "fhip_decode_frames_dev")
 
+    def decode_frames_segments(self, stream, frame_bytes, pcm_cap: int, seg_first, seg_number=None, seg_variable=None,
+                               out=None, md5_states=None, md5_nstreams: int = 0, seg_stream=None, use_segments=True):
+        """fhip_decode_frames_segments on host data: the frames of many streams, cut into segments (CSR seg_first
+        [nsegs + 1]); seg_number int64[nsegs] (default: all -1, unchecked) and seg_variable int32[nsegs] (default: all
+        0).  md5_states (a device address of md5_nstreams fhip_md5_state records) with seg_stream int32[nsegs] also
+        hashes each segment into its stream's state on the device.  use_segments=False passes no table (the call is
+        then fhip_decode_frames with variable_blocks 0 and first_number -1).  Returns (rc, pcm [pcm_cap][channels],
+        nsamples, records, summary, seg_start, seg_samples, seg_failed, error text); rc is OK or E_VERIFY, any other
+        code is returned too (E_INVALID: nothing was queued)."""
+        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
+                                  else stream, dtype=np.uint8)
+        fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
+        sf = np.ascontiguousarray(seg_first, dtype=np.int32)
+        ns = len(sf) - 1
+        ch = self.params.channels
+        if out is None:
+            out = np.zeros((pcm_cap, ch), dtype=self.pcm_dtype)
+        if out.dtype != self.pcm_dtype or out.size < pcm_cap * ch:
+            raise ValueError("out must hold pcm_cap * channels values of the handle's PCM dtype")
+        k = max(ns, 1)
+        num = np.full(k, -1, np.int64) if seg_number is None else np.ascontiguousarray(seg_number, dtype=np.int64)
+        var = np.zeros(k, np.int32) if seg_variable is None else np.ascontiguousarray(seg_variable, dtype=np.int32)
+        s_start, s_samples = np.full(k, -7, np.int64), np.full(k, -7, np.int64)
+        s_failed = np.full(k, -7, np.int32)
+        recs = np.zeros(len(fb), dtype=VERIFY_REC_DTYPE)
+        summary = np.zeros(4, dtype=np.int64)
+        nsm = np.zeros(1, dtype=np.int64)
+        di = DecodeIn(st.ctypes.data if st.size else None, st.size, fb.ctypes.data if fb.size else None, len(fb), 0, -1)
+        do = DecodeOut(_ptr(out) if out.size else None, pcm_cap, recs.ctypes.data if len(fb) else None,
+                       summary.ctypes.data, nsm.ctypes.data)
+        sg = DecodeSegments(sf.ctypes.data, ns, num.ctypes.data, var.ctypes.data, s_start.ctypes.data,
+                            s_samples.ctypes.data, s_failed.ctypes.data)
+        md = None
+        if md5_states is not None:
+            ss = np.ascontiguousarray(seg_stream, dtype=np.int32)
+            md = DecodeMd5(_ptr(md5_states) if not isinstance(md5_states, int) else md5_states, md5_nstreams,
+                           ss.ctypes.data)
+        rc = self.lib.fhip_decode_frames_segments(self._h, C.byref(di), C.byref(sg) if use_segments else None,
+                                                  C.byref(do), C.byref(md) if md is not None else None)
+        return (rc, out, int(nsm[0]), recs, summary, s_start[:ns], s_samples[:ns], s_failed[:ns],
+                self.lib.fhip_last_error(self._h).decode() if rc else "")
+
+    def decode_frames_segments_dev(self, stream, stream_bytes: int, frame_bytes, nframes: int, pcm, pcm_cap: int,
+                                   summary, nsamples, seg_first, nsegs: int, seg_number, seg_variable, seg_start,
+                                   seg_samples, seg_failed, records=None) -> None:
+        """K7's segment mode on device-resident data (torch tensors or raw device addresses); async."""
+        di = DecodeIn(_ptr(stream), stream_bytes, _ptr(frame_bytes), nframes, 0, -1)
+        do = DecodeOut(_ptr(pcm), pcm_cap, _ptr(records), _ptr(summary), _ptr(nsamples))
+        sg = DecodeSegments(_ptr(seg_first), nsegs, _ptr(seg_number), _ptr(seg_variable), _ptr(seg_start),
+                            _ptr(seg_samples), _ptr(seg_failed))
+        self._check(self.lib.fhip_decode_frames_segments_dev(self._h, C.byref(di), C.byref(sg), C.byref(do)),
+                    "fhip_decode_frames_segments_dev")
+
     def kernel_times(self, reset: bool = True) -> dict:
         names = (C.c_char_p * 8)()
         ms = (C.c_double * 8)()
@@ -572,6 +643,13 @@ class Encoder:
         """Stream s absorbs blocks seg_block[seg_first[s]:seg_first[s + 1]] of pcm (int32 device tables)."""
         self._check(self.lib.fhip_md5_update_dev(self._h, _ptr(states), nstreams, _ptr(pcm), block_size,
                                                  _ptr(seg_first), _ptr(seg_block)), "fhip_md5_update_dev")
+
+    def md5_update_ranges_dev(self, states, nstreams: int, pcm, seg_first, seg_range, range_start, range_samples) -> None:
+        """Stream s absorbs ranges seg_range[seg_first[s]:seg_first[s + 1]] (int32 device tables); range r is
+        range_samples[r] samples per channel at sample range_start[r] of pcm (int64 device tables)."""
+        self._check(self.lib.fhip_md5_update_ranges_dev(self._h, _ptr(states), nstreams, _ptr(pcm), _ptr(seg_first),
+                                                        _ptr(seg_range), _ptr(range_start), _ptr(range_samples)),
+                    "fhip_md5_update_ranges_dev")
 
     def md5_final_dev(self, states, nstreams: int, digests) -> None:
         """digests: device uint8[nstreams][16]; the states stay usable."""
@@ -797,6 +875,23 @@ def load_host_library() -> C.CDLL:
     lib.flake_amd_decode_last_error.restype = C.c_char_p
     lib.flake_amd_decode_close.argtypes = [C.c_void_p]
     lib.flake_amd_decode_close.restype = None
+    lib.flake_amd_decode_set_open.argtypes = [C.POINTER(HostStreaminfo), C.c_int, C.c_uint]
+    lib.flake_amd_decode_set_open.restype = C.c_void_p
+    lib.flake_amd_decode_set_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
+    lib.flake_amd_decode_set_frames.restype = C.c_longlong
+    lib.flake_amd_decode_set_run_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    lib.flake_amd_decode_set_run_offsets.restype = C.c_int
+    lib.flake_amd_decode_set_md5.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.flake_amd_decode_set_md5.restype = C.c_int
+    lib.flake_amd_decode_set_failed.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
+    lib.flake_amd_decode_set_failed.restype = C.c_int
+    lib.flake_amd_decode_set_device_batches.argtypes = [C.c_void_p]
+    lib.flake_amd_decode_set_device_batches.restype = C.c_longlong
+    lib.flake_amd_decode_set_last_error.argtypes = [C.c_void_p]
+    lib.flake_amd_decode_set_last_error.restype = C.c_char_p
+    lib.flake_amd_decode_set_close.argtypes = [C.c_void_p]
+    lib.flake_amd_decode_set_close.restype = None
     _host = lib
     return lib
 
@@ -1110,6 +1205,83 @@ class StreamSet:
     def close(self) -> None:
         if getattr(self, "_g", None):
             self.lib.flake_amd_set_close(self._g)
+            self._g = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DecodeSet:
+    """A decode set of the host C layer (flake_amd_decode_set_*): runs of frames of many streams of one format per
+    call, decoded in shared device batches, each stream's MD5 carried on the device (flags: SET_MD5_HOST, SET_MD5_OFF).
+    ctypes only; no compute here."""
+
+    def __init__(self, like: HostStreaminfo, nstreams: int, flags: int = 0):
+        self.lib = load_host_library()
+        self.si = like
+        self.nstreams = int(nstreams)
+        self._g = self.lib.flake_amd_decode_set_open(C.byref(like), self.nstreams, int(flags))
+        if not self._g:
+            raise FlakeHipError(-1, "flake_amd_decode_set_open", self.lib.flake_amd_decode_set_last_error(None).decode())
+
+    def last_error(self) -> str:
+        return self.lib.flake_amd_decode_set_last_error(self._g).decode()
+
+    def decode_runs(self, runs, pcm_cap: int, sample_bytes: int = 4):
+        """runs: [(stream index, frame bytes, frame sizes)], a run being consecutive frames of one stream.  Returns a
+        list with one entry per run: its samples [n][channels] (a view of one buffer), or None for a run of a stream
+        that failed (failed(stream) says where).  Raises FlakeHipError when the call is refused: nothing changed then."""
+        sor = np.asarray([r[0] for r in runs], dtype=np.int32)
+        fs = [np.ascontiguousarray(r[2], dtype=np.int32) for r in runs]
+        fof = np.asarray([len(f) for f in fs], dtype=np.int32)
+        parts = [np.frombuffer(bytes(r[1]), dtype=np.uint8) if isinstance(r[1], (bytes, bytearray))
+                 else np.asarray(r[1], dtype=np.uint8) for r in runs]
+        st = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, np.uint8)
+        sizes = np.ascontiguousarray(np.concatenate(fs)) if fs else np.zeros(0, np.int32)
+        out = np.zeros((pcm_cap, self.si.channels), dtype=np.int16 if sample_bytes == 2 else np.int32)
+        rs = np.zeros(max(len(runs), 1), dtype=np.int64)
+        n = self.lib.flake_amd_decode_set_frames(self._g, len(runs), sor.ctypes.data if len(runs) else None,
+                                                 fof.ctypes.data if len(runs) else None,
+                                                 st.ctypes.data if st.size else None, st.size,
+                                                 sizes.ctypes.data if sizes.size else None,
+                                                 out.ctypes.data if out.size else None, sample_bytes, pcm_cap,
+                                                 rs.ctypes.data)
+        if n < 0:
+            raise FlakeHipError(int(n), "flake_amd_decode_set_frames", self.last_error())
+        off = np.zeros(max(len(runs), 1), dtype=np.int64)
+        self.lib.flake_amd_decode_set_run_offsets(self._g, off.ctypes.data, len(runs))
+        return [None if rs[r] < 0 else out[off[r]:off[r] + rs[r]] if rs[r] else out[:0] for r in range(len(runs))]
+
+    def md5(self, stream: int):
+        """The digest of everything the stream has returned, or None (a failed stream; a set without MD5)."""
+        buf = (C.c_ubyte * 16)()
+        if self.lib.flake_amd_decode_set_md5(self._g, int(stream), buf) != 0:
+            return None
+        return bytes(buf)
+
+    def failed(self, stream: int):
+        """None while the stream is good, else (frame counted from the stream's first, FHIP_VERIFY_* status)."""
+        fr, st = C.c_longlong(-1), C.c_int(0)
+        rc = self.lib.flake_amd_decode_set_failed(self._g, int(stream), C.byref(fr), C.byref(st))
+        if rc < 0:
+            raise IndexError(stream)
+        return (fr.value, st.value) if rc else None
+
+    def device_batches(self) -> int:
+        return int(self.lib.flake_amd_decode_set_device_batches(self._g))
+
+    def close(self) -> None:
+        if getattr(self, "_g", None):
+            self.lib.flake_amd_decode_set_close(self._g)
             self._g = None
 
     def __enter__(self):

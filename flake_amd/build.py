@@ -29,8 +29,9 @@ HIP_DEPS = HIP_SRCS + HIP_HDRS
 HOST_SRCS = ["host/flake_host.c", "host/flake_set.c", "host/synth.c", "host/md5.c"]
 # the decoding side goes into libflake_amd.so only: the drop-in libflake.so exports what libflake has, and libflake
 # has no decoder
-HOST_DECODE_SRCS = ["host/flake_decode.c"]
-HOST_DEPS = HOST_SRCS + HOST_DECODE_SRCS + ["host/host_internal.h", "../include/flakehip.h", "../include/flake_amd.h"]
+HOST_DECODE_SRCS = ["host/flake_decode.c", "host/flake_decode_set.c"]
+HOST_DEPS = HOST_SRCS + HOST_DECODE_SRCS + ["host/host_internal.h", "host/decode_set_plan.h", "../include/flakehip.h",
+                                            "../include/flake_amd.h"]
 
 # -ffp-contract=off is load-bearing: the fp64 LPC stages must round after every
 # multiply and add to reproduce the reference bit for bit.

@@ -138,6 +138,8 @@ struct fhip_ctx {
     DevBuf<int32_t> d_vfb;
     DevBuf<int32_t> d_vpcm;
     DevBuf<uint32_t> d_vnum;                  // fhip_verify_frames_numbered: the host number table uploaded
+    DevBuf<long long> d_dseg;                 // fhip_decode_frames_segments: the segment tables, their outputs, K6's CSR
+    std::vector<long long> h_dseg;            // ... and the host image they are uploaded from
     long long vfail_sum[4] = {0, 0, -1, 0};   // fhip_last_verify_failure: the most recent verdict's summary ...
     fhip_verify_rec vfail_rec{0, -1, -1, -1}; // ... and its first failing frame's record
     bool vfail_has_number = false;            // fhip_last_verify_number: the number that frame had to carry, where a
@@ -1520,6 +1522,29 @@ int fhip_md5_update_dev(fhip_ctx *c, fhip_md5_state *states, int nstreams, const
     return md5_dev_end(c);
 }
 
+// k_md5_ranges on the handle's stream; every table is device memory
+static int md5_ranges(fhip_ctx *c, fhip_md5_state *states, int nstreams, const void *pcm, const int32_t *seg_first,
+                      const int32_t *seg_range, const int64_t *range_start, const int64_t *range_samples)
+{
+    HIP_TRY(c, fhip::launch_md5_ranges(c->stream, states, nstreams, pcm, c->pcm_format, (c->p.bits_per_sample + 7) >> 3,
+                                       c->p.channels, seg_first, seg_range,
+                                       reinterpret_cast<const long long *>(range_start),
+                                       reinterpret_cast<const long long *>(range_samples)));
+    return FHIP_OK;
+}
+
+int fhip_md5_update_ranges_dev(fhip_ctx *c, fhip_md5_state *states, int nstreams, const void *pcm,
+                               const int32_t *seg_first, const int32_t *seg_range, const int64_t *range_start,
+                               const int64_t *range_samples)
+{
+    int rc = md5_check(c, states, nstreams, pcm && seg_first && seg_range && range_start && range_samples);
+    if (rc != FHIP_OK) return rc;
+    LaunchScope ls(c);
+    if ((rc = md5_dev_begin(c)) != FHIP_OK) return rc;
+    if ((rc = md5_ranges(c, states, nstreams, pcm, seg_first, seg_range, range_start, range_samples)) != FHIP_OK) return rc;
+    return md5_dev_end(c);
+}
+
 int fhip_md5_final_dev(fhip_ctx *c, const fhip_md5_state *states, int nstreams, uint8_t *digests)
 {
     int rc = md5_check(c, states, nstreams, digests != nullptr);
@@ -2525,24 +2550,33 @@ int fhip_last_verify_failure(const fhip_ctx *c, int64_t *summary, fhip_verify_re
 
 namespace {
 // The entries' checks, with nothing queued and the launch list left empty where they refuse.
-int decode_check(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *out)
+// (segs: the segment mode, which does not read the call's variable_blocks and first_number; its tables must be there)
+int decode_check(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *out, const fhip_decode_segments *segs = nullptr)
 {
     if (!c) return FHIP_E_INVALID;
     c->launches.clear();
     c->md5_log_entry = -1;
     if (!in || !out || !out->summary || !out->nsamples) return fail(c, FHIP_E_INVALID, "null argument");
-    if (in->nframes < 0 || in->stream_bytes < 0 || out->pcm_cap < 0 || in->first_number < -1)
+    if (in->nframes < 0 || in->stream_bytes < 0 || out->pcm_cap < 0 || (!segs && in->first_number < -1))
         return fail(c, FHIP_E_INVALID, "negative count");
     if (in->nframes > c->max_frames) return fail(c, FHIP_E_INVALID, "nframes exceeds the handle's max_frames");
-    if (in->variable_blocks != 0 && in->variable_blocks != 1) return fail(c, FHIP_E_INVALID, "variable_blocks is 0 or 1");
+    if (!segs && in->variable_blocks != 0 && in->variable_blocks != 1) return fail(c, FHIP_E_INVALID, "variable_blocks is 0 or 1");
     if (in->nframes > 0 && (!in->stream || !in->frame_bytes)) return fail(c, FHIP_E_INVALID, "null stream");
     if (out->pcm_cap > 0 && !out->pcm) return fail(c, FHIP_E_INVALID, "null pcm");
+    if (segs) {
+        if (segs->nsegs < 1) return fail(c, FHIP_E_INVALID, "nsegs must be at least 1");
+        if (!segs->seg_first || !segs->seg_number || !segs->seg_variable || !segs->seg_start || !segs->seg_samples ||
+            !segs->seg_failed)
+            return fail(c, FHIP_E_INVALID, "null segment table");
+    }
     return FHIP_OK;
 }
 
 // Queue K7 on the handle's stream; all of in / out is device memory.  The restored subframes go through d_smp, the
 // frame records through K5's workspace: an encode call that follows overwrites both from the start, as it always has.
-int run_decode(fhip_ctx *c, const fhip_decode_in &in, const fhip_decode_out &out)
+// segs (optional, device memory as well): the segment mode; its end reads the frames' records, so a caller who asks for
+// none gets the handle's own.
+int run_decode(fhip_ctx *c, const fhip_decode_in &in, const fhip_decode_out &out, const fhip_decode_segments *segs = nullptr)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     int rc = ensure_verify(c, (size_t)in.nframes);
@@ -2553,6 +2587,18 @@ int run_decode(fhip_ctx *c, const fhip_decode_in &in, const fhip_decode_out &out
                        c->d_smp, c->d_vws, out.frames, reinterpret_cast<long long *>(out.summary),
                        reinterpret_cast<unsigned long long *>(c->d_vsum + 4), reinterpret_cast<long long *>(out.nsamples),
                        c->d_vsum + 6};
+    if (segs) {
+        a.variable_blocks = 0;
+        a.first_number = -1;
+        if (!a.recs) a.recs = c->d_vrec;
+        a.seg_first = segs->seg_first;
+        a.nsegs = segs->nsegs;
+        a.seg_number = reinterpret_cast<const long long *>(segs->seg_number);
+        a.seg_variable = segs->seg_variable;
+        a.seg_start = reinterpret_cast<long long *>(segs->seg_start);
+        a.seg_samples = reinterpret_cast<long long *>(segs->seg_samples);
+        a.seg_failed = segs->seg_failed;
+    }
     Prof pr(c, kProfDecode, c->profiling);
     HIP_TRY(c, fhip::launch_decode(c->stream, a));
     return FHIP_OK;
@@ -2567,10 +2613,46 @@ int fhip_decode_frames_dev(fhip_ctx *c, const fhip_decode_in *in, const fhip_dec
     return run_decode(c, *in, *out);
 }
 
+int fhip_decode_frames_segments_dev(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
+                                    const fhip_decode_out *out)
+{
+    if (!segs) return fhip_decode_frames_dev(c, in, out);
+    int rc = decode_check(c, in, out, segs);
+    if (rc != FHIP_OK) return rc;
+    LaunchScope ls(c);
+    return run_decode(c, *in, *out, segs);
+}
+
 int fhip_decode_frames(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *out)
 {
-    int rc = decode_check(c, in, out);
+    return fhip_decode_frames_segments(c, in, nullptr, out, nullptr);
+}
+
+// The host form, with and without segments.  The segment tables travel in one block of the handle's (d_dseg): the
+// 8-byte ones first -- seg_number, seg_start, seg_samples -- then seg_first, seg_variable, seg_failed and, with md5, K6's
+// CSR (md5_first [nstreams + 1], md5_range [nsegs]), which is built here.
+int fhip_decode_frames_segments(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
+                                const fhip_decode_out *out, const fhip_decode_md5 *md5)
+{
+    int rc = decode_check(c, in, out, segs);
     if (rc != FHIP_OK) return rc;
+    if (md5 && !segs) return fail(c, FHIP_E_INVALID, "md5 needs a segment table");
+    const size_t ns = segs ? (size_t)segs->nsegs : 0, nst = md5 ? (size_t)(md5->nstreams > 0 ? md5->nstreams : 0) : 0;
+    if (segs) {
+        if (segs->seg_first[0] != 0) return fail(c, FHIP_E_INVALID, "seg_first[0] must be 0");
+        for (size_t s = 0; s < ns; s++) {
+            if (segs->seg_first[s + 1] < segs->seg_first[s]) return fail(c, FHIP_E_INVALID, "seg_first must not decrease");
+            if (segs->seg_variable[s] != 0 && segs->seg_variable[s] != 1) return fail(c, FHIP_E_INVALID, "seg_variable is 0 or 1");
+            if (segs->seg_number[s] < -1) return fail(c, FHIP_E_INVALID, "seg_number is -1 or a number");
+        }
+        if (segs->seg_first[ns] != in->nframes) return fail(c, FHIP_E_INVALID, "seg_first must end at nframes");
+    }
+    if (md5) {
+        if (!md5->states || !md5->seg_stream || md5->nstreams < 1) return fail(c, FHIP_E_INVALID, "null md5 argument");
+        for (size_t s = 0; s < ns; s++)
+            if (md5->seg_stream[s] < 0 || md5->seg_stream[s] >= md5->nstreams)
+                return fail(c, FHIP_E_INVALID, "seg_stream entry outside the states");
+    }
     const size_t nf = (size_t)in->nframes, sb = (size_t)in->stream_bytes;
     long long total = 0;
     for (size_t f = 0; f < nf; f++) {
@@ -2596,12 +2678,53 @@ int fhip_decode_frames(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_
     // summary [0..4), K7's key scratch [4], the sample count [5], the end of what was written [6]
     fhip_decode_out dout{c->d_vpcm, cap, c->d_vrec, reinterpret_cast<int64_t *>(c->d_vsum.get()),
                          reinterpret_cast<int64_t *>(c->d_vsum.get() + 5)};
-    rc = run_decode(c, din, dout);
+    fhip_decode_segments dsegs{};
+    int32_t *d_i32 = nullptr;
+    if (segs) {
+        const size_t n32 = 4 * ns + nst + 2, words = 3 * ns + (n32 + 1) / 2;
+        c->h_dseg.assign(words, 0);
+        HIP_TRY(c, c->d_dseg.reserve(words));
+        int32_t *h_i32 = reinterpret_cast<int32_t *>(c->h_dseg.data() + 3 * ns);
+        d_i32 = reinterpret_cast<int32_t *>(c->d_dseg.get() + 3 * ns);
+        memcpy(c->h_dseg.data(), segs->seg_number, ns * sizeof(int64_t));
+        memcpy(h_i32, segs->seg_first, (ns + 1) * sizeof(int32_t));
+        memcpy(h_i32 + ns + 1, segs->seg_variable, ns * sizeof(int32_t));
+        if (md5) {
+            // stream s absorbs its segments in batch order: a counting sort of the segments by stream
+            int32_t *first = h_i32 + 3 * ns + 1, *range = first + nst + 1;
+            for (size_t s = 0; s < ns; s++) first[md5->seg_stream[s] + 1]++;
+            for (size_t k = 0; k < nst; k++) first[k + 1] += first[k];
+            std::vector<int32_t> at(first, first + nst);
+            for (size_t s = 0; s < ns; s++) range[at[md5->seg_stream[s]]++] = (int32_t)s;
+        }
+        HIP_TRY(c, hipMemcpyAsync(c->d_dseg, c->h_dseg.data(), words * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+        dsegs.seg_first = d_i32;
+        dsegs.nsegs = segs->nsegs;
+        dsegs.seg_number = reinterpret_cast<const int64_t *>(c->d_dseg.get());
+        dsegs.seg_variable = d_i32 + ns + 1;
+        dsegs.seg_start = reinterpret_cast<int64_t *>(c->d_dseg.get() + ns);
+        dsegs.seg_samples = reinterpret_cast<int64_t *>(c->d_dseg.get() + 2 * ns);
+        dsegs.seg_failed = d_i32 + 2 * ns + 1;
+    }
+    rc = run_decode(c, din, dout, segs ? &dsegs : nullptr);
     if (rc != FHIP_OK) return rc;
+    if (md5) {
+        // the hash reads the PCM where K7 left it and the ranges K7 named, behind it on the same stream
+        if ((rc = md5_dev_begin(c)) != FHIP_OK) return rc;
+        rc = md5_ranges(c, md5->states, md5->nstreams, c->d_vpcm, d_i32 + 3 * ns + 1, d_i32 + 3 * ns + 1 + nst + 1,
+                        dsegs.seg_start, dsegs.seg_samples);
+        if (rc != FHIP_OK) return rc;
+        if ((rc = md5_dev_end(c)) != FHIP_OK) return rc;
+    }
     long long sum[7] = {0, 0, -1, 0, 0, 0, 0};
     HIP_TRY(c, hipMemcpyAsync(sum, c->d_vsum, sizeof sum, hipMemcpyDeviceToHost, c->stream));
     if (out->frames && nf)
         HIP_TRY(c, hipMemcpyAsync(out->frames, c->d_vrec, nf * sizeof(fhip_verify_rec), hipMemcpyDeviceToHost, c->stream));
+    if (segs) {
+        HIP_TRY(c, hipMemcpyAsync(segs->seg_start, dsegs.seg_start, ns * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(segs->seg_samples, dsegs.seg_samples, ns * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(segs->seg_failed, dsegs.seg_failed, ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    }
     rc = fhip_sync(c);
     if (rc != FHIP_OK) return rc;
     // the samples, up to the end of the last frame that was placed and written: nothing behind it is touched (a frame

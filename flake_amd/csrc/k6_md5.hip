@@ -302,6 +302,101 @@ k_md5_streams_ragged(fhip_md5_state *__restrict__ states, int nstreams, const T 
     }
 }
 
+// A unit's raw dwords from an address that is only as aligned as T itself (a range starts at any sample, and the bytes
+// taken to empty the tail move it further): the copies tell the compiler exactly that, and it picks loads that are
+// legal there.  Nothing past the unit's last sample is read.
+template <class T, int BPS>
+__device__ __forceinline__ void unit_load_at_sample(const T *__restrict__ p, uint32_t (&raw)[Unit<T, BPS>::RAW])
+{
+#pragma unroll
+    for (int i = 0; i < Unit<T, BPS>::LOADS; i++) {
+        uint32_t v[4];
+        __builtin_memcpy(v, p + i * (16 / (int)sizeof(T)), 16);
+        raw[4 * i] = v[0]; raw[4 * i + 1] = v[1]; raw[4 * i + 2] = v[2]; raw[4 * i + 3] = v[3];
+    }
+}
+
+// The update over ranges the device names: stream s absorbs, in order, the ranges seg_range[seg_first[s] ..
+// seg_first[s + 1]); range r is the range_samples[r] samples per channel at sample range_start[r] of pcm (nch
+// interleaved values each); a length <= 0 absorbs nothing.  Per range a lane (1) feeds samples through its tail until the
+// tail is empty, (2) hashes whole units from registers, the next unit's loads in flight during the current one's steps,
+// (3) feeds the rest through the tail.  The loops are plain structured loops, so the wave runs each phase together: in
+// (2) every lane that still has a unit hashes one per trip and the others are masked off.  A tail that cannot empty on a
+// sample boundary (a fill that is no multiple of the sample's bytes: never from whole samples at 1, 2 or 4 bytes) leaves
+// everything to (1), which is correct at any fill.
+template <class T, int BPS>
+__global__ void __launch_bounds__(MD5_WG)
+k_md5_ranges(fhip_md5_state *__restrict__ states, int nstreams, const T *__restrict__ pcm, int nch,
+             const int32_t *__restrict__ seg_first, const int32_t *__restrict__ seg_range,
+             const long long *__restrict__ range_start, const long long *__restrict__ range_samples)
+{
+    __shared__ uint32_t tail[16 * MD5_WG];
+    using U = Unit<T, BPS>;
+    const int lane = threadIdx.x;
+    const int s = blockIdx.x * MD5_WG + lane;
+    if (s >= nstreams) return;
+    const int b0 = seg_first[s], b1 = seg_first[s + 1];
+    if (b1 <= b0) return;                    // no range in this launch: the state is not touched
+    fhip_md5_state *st = states + s;
+    uint32_t h[4] = {st->h[0], st->h[1], st->h[2], st->h[3]};
+    uint32_t fill = st->fill & 63u;
+    {
+        const uint32_t *t = reinterpret_cast<const uint32_t *>(st->tail);
+#pragma unroll
+        for (int j = 0; j < 16; j++) tail[j * MD5_WG + lane] = t[j];
+    }
+    uint64_t bytes = 0;
+    for (int b = b0; b < b1; b++) {
+        const int r = seg_range[b];
+        const long long ns = range_samples[r];
+        if (ns <= 0) continue;
+        const long long vals = ns * nch;
+        const T *p = pcm + (size_t)range_start[r] * (size_t)nch;
+        bytes += (uint64_t)vals * BPS;
+        long long i = 0;
+        for (; i < vals && fill != 0; i++) {
+            uint32_t x = (uint32_t)(int32_t)p[i];
+#pragma unroll
+            for (int k = 0; k < BPS; k++) {
+                tail_put(tail, lane, fill, x & 0xFFu);
+                x >>= 8;
+                if (++fill == 64) { tail_hash(h, tail, lane); fill = 0; }
+            }
+        }
+        const long long units = (vals - i) / U::SAMPLES;          // (fill is 0 here, or i == vals)
+        if (units > 0) {
+            const T *q = p + i;
+            uint32_t cur[U::RAW], nxt[U::RAW];
+            unit_load_at_sample<T, BPS>(q, cur);
+            for (long long u = 1; u < units; u++) {
+                unit_load_at_sample<T, BPS>(q + (size_t)u * U::SAMPLES, nxt);    // in flight during the 64 steps below
+                unit_hash<T, BPS>(h, cur);
+#pragma unroll
+                for (int k = 0; k < U::RAW; k++) cur[k] = nxt[k];
+            }
+            unit_hash<T, BPS>(h, cur);
+            i += units * U::SAMPLES;
+        }
+        for (; i < vals; i++) {
+            uint32_t x = (uint32_t)(int32_t)p[i];
+#pragma unroll
+            for (int k = 0; k < BPS; k++) {
+                tail_put(tail, lane, fill, x & 0xFFu);
+                x >>= 8;
+                if (++fill == 64) { tail_hash(h, tail, lane); fill = 0; }
+            }
+        }
+    }
+    st->h[0] = h[0]; st->h[1] = h[1]; st->h[2] = h[2]; st->h[3] = h[3];
+    st->nbytes += bytes;
+    st->fill = fill;
+    {
+        uint32_t *t = reinterpret_cast<uint32_t *>(st->tail);
+#pragma unroll
+        for (int j = 0; j < 16; j++) t[j] = tail[j * MD5_WG + lane];
+    }
+}
+
 // fa_md5_final: 0x80, zeros up to 56 mod 64, the bit count; on a copy.
 __global__ void __launch_bounds__(MD5_WG) k_md5_final(const fhip_md5_state *__restrict__ states, int nstreams,
                                                       uint8_t *__restrict__ digests)
@@ -409,6 +504,27 @@ hipError_t launch_md5_streams_ragged(hipStream_t st, fhip_md5_state *states, int
     else if (bytes_per_sample == 3) LAUNCH_MR(int32_t, 3);
     else LAUNCH_MR(int32_t, 4);
 #undef LAUNCH_MR
+    return hipGetLastError();
+}
+
+hipError_t launch_md5_ranges(hipStream_t st, fhip_md5_state *states, int nstreams, const void *pcm, int pcm_format,
+                             int bytes_per_sample, int channels, const int32_t *seg_first, const int32_t *seg_range,
+                             const long long *range_start, const long long *range_samples)
+{
+    if (nstreams <= 0) return hipSuccess;
+    const bool s16 = pcm_format == FHIP_PCM_S16;
+    if (bytes_per_sample < 1 || bytes_per_sample > (s16 ? 2 : 4) || channels < 1) return hipErrorInvalidValue;
+    note_launch("k_md5_ranges<%s,%d>", s16 ? "int16_t" : "int32_t", bytes_per_sample);
+    const int grid = (nstreams + MD5_WG - 1) / MD5_WG;
+#define LAUNCH_RG(T_, B_) hipLaunchKernelGGL((k_md5_ranges<T_, B_>), dim3(grid), dim3(MD5_WG), 0, st, states, nstreams, \
+                                             static_cast<const T_ *>(pcm), channels, seg_first, seg_range, range_start, \
+                                             range_samples)
+    if (s16) { if (bytes_per_sample == 1) LAUNCH_RG(int16_t, 1); else LAUNCH_RG(int16_t, 2); }
+    else if (bytes_per_sample == 1) LAUNCH_RG(int32_t, 1);
+    else if (bytes_per_sample == 2) LAUNCH_RG(int32_t, 2);
+    else if (bytes_per_sample == 3) LAUNCH_RG(int32_t, 3);
+    else LAUNCH_RG(int32_t, 4);
+#undef LAUNCH_RG
     return hipGetLastError();
 }
 

@@ -42,6 +42,10 @@ __device__ __forceinline__ bool hdr_parsed(int status) { return status == FHIP_V
 
 // ---- k_decode_frames -------------------------------------------------------------------------------
 
+// SEG: the segment mode (DecodeArgs::seg_first): the strategy bit, the first number, continuity and the size rule of
+// fixed blocks are a segment's; placement, pcm_cap, the records and the counts stay the batch's.  The carry across the
+// chunks of DHDR_T frames is about frame f - 1 whatever its segment: a segment's first frame never looks at it.
+template <bool SEG>
 __global__ void __launch_bounds__(DHDR_T) k_decode_frames(DecodeArgs a)
 {
     __shared__ long long scratch[DHDR_T / 64];
@@ -68,6 +72,10 @@ __global__ void __launch_bounds__(DHDR_T) k_decode_frames(DecodeArgs a)
         s_carry_ok = 0;
         s_end = 0;
     }
+    if constexpr (SEG) {
+        for (int s = t; s < a.nsegs; s += DHDR_T) { a.seg_samples[s] = 0; a.seg_failed[s] = -1; }
+        __syncthreads();                               // (the sums below are atomic adds onto these zeros)
+    }
     long long base = 0, sbase = 0, good = 0;
     for (int f0 = 0; f0 < count; f0 += DHDR_T) {
         const int f = f0 + t;
@@ -80,6 +88,23 @@ __global__ void __launch_bounds__(DHDR_T) k_decode_frames(DecodeArgs a)
         vf.off = off;
         vf.bytes = (int)fb;
         HdrOut h{FHIP_VERIFY_OK, 0, 0, 0, 0, 0};
+        // the frame's segment: the last one that starts at or before it (empty segments in front of it start there too)
+        int seg = 0, variable = a.variable_blocks;
+        bool seg_head = f == 0, seg_last = f == count - 1;
+        if constexpr (SEG) {
+            if (live) {
+                int lo = 0, hi = a.nsegs - 1;
+                while (lo < hi) {
+                    const int mid = (lo + hi + 1) >> 1;
+                    if (a.seg_first[mid] <= f) lo = mid; else hi = mid - 1;
+                }
+                seg = lo;
+                seg_head = a.seg_first[seg] == f;
+                seg_last = a.seg_first[seg + 1] == f + 1;
+                variable = a.seg_variable[seg] != 0;
+                va.allow_vbs = variable;
+            }
+        }
         if (live) {
             if (fb <= 0 || off + fb > a.stream_bytes) {
                 h.status = FHIP_VERIFY_LENGTH;
@@ -102,23 +127,37 @@ __global__ void __launch_bounds__(DHDR_T) k_decode_frames(DecodeArgs a)
             // (a frame whose own header is broken has already failed: its successor is not blamed for it)
             const unsigned long long prev_num = t ? s_num[t - 1] : s_carry_num;
             const int prev_n = t ? s_n[t - 1] : s_carry_n;
-            const bool prev_ok = f > 0 && (t ? s_ok[t - 1] : s_carry_ok);
+            const bool prev_ok = !seg_head && (t ? s_ok[t - 1] : s_carry_ok);
             unsigned long long want = h.number;
-            if (f == 0) {
-                if (a.first_number >= 0) want = (unsigned long long)a.first_number;
+            if (seg_head) {
+                const long long first = SEG ? a.seg_number[seg] : a.first_number;
+                if (first >= 0) want = (unsigned long long)first;
             } else if (prev_ok) {
-                want = prev_num + (a.variable_blocks ? (unsigned long long)prev_n : 1ull);
+                want = prev_num + (variable ? (unsigned long long)prev_n : 1ull);
             }
             // fixed blocks: every frame but the last holds the same number of samples
             bool size_ok = true;
-            if (!a.variable_blocks && prev_ok) size_ok = f == count - 1 ? h.n <= prev_n : h.n == prev_n;
+            if (!variable && prev_ok) size_ok = seg_last ? h.n <= prev_n : h.n == prev_n;
             const bool fits = S + h.n <= a.pcm_cap;
             if (h.number != want) { h.status = FHIP_VERIFY_NUMBER; h.bit = 32; }
             else if (!size_ok || !fits) { h.status = FHIP_VERIFY_NUMBER; h.bit = 16; }
         }
         long long gtot = 0;
-        (void)block_excl_scan(live && h.status == FHIP_VERIFY_OK ? (long long)h.n : 0ll, scratch, DHDR_T / 64, &gtot);
+        const long long G = good + block_excl_scan(live && h.status == FHIP_VERIFY_OK ? (long long)h.n : 0ll, scratch,
+                                                   DHDR_T / 64, &gtot);
         good += gtot;
+        if constexpr (SEG) {
+            if (live && seg_head) {
+                // the segment begins at S, and G good samples lie before it: they end the count of the last segment
+                // with a frame and start this one's (two adds per segment, in any order).  Empty segments in front
+                // of this frame begin here as well.
+                a.seg_start[seg] = S;
+                atomicAdd((unsigned long long *)&a.seg_samples[seg], (unsigned long long)-G);
+                int sp = seg - 1;
+                for (; sp >= 0 && a.seg_first[sp] == f; sp--) a.seg_start[sp] = S;
+                if (sp >= 0) atomicAdd((unsigned long long *)&a.seg_samples[sp], (unsigned long long)G);
+            }
+        }
         if (live && h.status == FHIP_VERIFY_OK) atomicMax(&s_end, (unsigned long long)(S + h.n));
         if (live) {
             vf.rel_start = S;
@@ -136,6 +175,12 @@ __global__ void __launch_bounds__(DHDR_T) k_decode_frames(DecodeArgs a)
     if (t == 0) {
         a.nsamples[0] = good;
         a.written_end[0] = (long long)s_end;
+        if constexpr (SEG) {
+            // segments behind the last frame are empty and begin at the batch's end; the last one with a frame ends there
+            int sp = a.nsegs - 1;
+            for (; sp >= 0 && a.seg_first[sp] == count; sp--) a.seg_start[sp] = sbase;
+            if (sp >= 0) atomicAdd((unsigned long long *)&a.seg_samples[sp], (unsigned long long)good);
+        }
     }
 }
 
@@ -411,18 +456,48 @@ __global__ void k_decode_final(DecodeArgs a)
     a.summary[3] = k == KEY_NONE ? 0 : (long long)(k & 0xFF);
 }
 
+// The segment mode's end: seg_failed[s] = the first frame of segment s whose record k_decode left with a status (the
+// header pass's failures went through k_decode into the records like every other).  A wave per segment, 64 frames a step.
+__global__ void __launch_bounds__(DT) k_decode_seg_final(DecodeArgs a)
+{
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int f0 = max(a.seg_first[s], 0), f1 = min(a.seg_first[s + 1], a.nframes);    // (never past the records)
+    for (int fb = f0; fb < f1; fb += DT) {
+        const int f = fb + lane;
+        const bool bad = f < f1 && a.recs[f].status != FHIP_VERIFY_OK;
+        const unsigned long long m = __ballot(bad);
+        if (m) {                                          // wave-uniform
+            if (lane == 0) a.seg_failed[s] = fb + __ffsll(m) - 1;
+            return;
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t launch_decode(hipStream_t st, const DecodeArgs &a)
 {
-    note_launch("k_decode_frames");
-    hipLaunchKernelGGL(k_decode_frames, dim3(1), dim3(DHDR_T), 0, st, a);
+    const bool seg = a.seg_first != nullptr;
+    if (seg) {
+        if (a.nsegs < 1 || !a.seg_number || !a.seg_variable || !a.seg_start || !a.seg_samples || !a.seg_failed ||
+            (a.nframes > 0 && !a.recs))
+            return hipErrorInvalidValue;
+        note_launch("k_decode_frames segments");
+        hipLaunchKernelGGL(k_decode_frames<true>, dim3(1), dim3(DHDR_T), 0, st, a);
+    } else {
+        note_launch("k_decode_frames");
+        hipLaunchKernelGGL(k_decode_frames<false>, dim3(1), dim3(DHDR_T), 0, st, a);
+    }
     if (a.nframes > 0) {
         note_launch("k_decode");
         hipLaunchKernelGGL(k_decode, dim3(a.nframes), dim3(DT), 0, st, a);
     }
     note_launch("k_decode_final");
     hipLaunchKernelGGL(k_decode_final, dim3(1), dim3(1), 0, st, a);
+    if (seg && a.nframes > 0) {
+        note_launch("k_decode_seg_final");
+        hipLaunchKernelGGL(k_decode_seg_final, dim3(a.nsegs), dim3(DT), 0, st, a);
+    }
     return hipGetLastError();
 }
 

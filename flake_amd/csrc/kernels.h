@@ -322,6 +322,18 @@ struct DecodeArgs {
     long long *nsamples;                         // [1] samples per channel of the frames whose header pass succeeded
     long long *written_end;                      // [1] where the last of those frames ends in pcm (samples per channel):
                                                  // nothing at or behind it is written
+    // The segment mode (null seg_first: every launch is as it was): the batch is nsegs runs of consecutive frames, each
+    // of one stream -- segment s is frames seg_first[s] .. seg_first[s + 1] (CSR, [nsegs + 1], 0 .. nframes, a frame's
+    // segment is found by search).  Numbering, the size rule of fixed blocks and the strategy bit are held per segment:
+    // variable_blocks and first_number above are unused.  Placement stays the batch's.  recs is required then: the
+    // segment pass of the end reads the frames' final statuses from it.
+    const int32_t *seg_first = nullptr;
+    int nsegs = 0;
+    const long long *seg_number = nullptr;       // [nsegs] the number the segment's first frame must carry; < 0: not checked
+    const int32_t *seg_variable = nullptr;       // [nsegs] the strategy bit of the segment's headers
+    long long *seg_start = nullptr;              // [nsegs] out: where the segment's samples begin in pcm
+    long long *seg_samples = nullptr;            // [nsegs] out: as nsamples, of the segment's frames
+    int32_t *seg_failed = nullptr;               // [nsegs] out: index in the batch of its first failing frame, -1: none
 };
 hipError_t launch_decode(hipStream_t st, const DecodeArgs &a);
 
@@ -341,6 +353,13 @@ hipError_t launch_md5_streams(hipStream_t st, fhip_md5_state *states, int nstrea
 hipError_t launch_md5_streams_ragged(hipStream_t st, fhip_md5_state *states, int nstreams, const void *pcm,
                                      int pcm_format, int bytes_per_sample, const int32_t *seg_first,
                                      const int32_t *seg_block, const long long *blk_off, const int32_t *blk_vals);
+// The update over ranges of samples that the device names (k_md5_ranges): stream s absorbs the ranges
+// seg_range[seg_first[s] .. seg_first[s + 1]) in order; range r is range_samples[r] samples per channel (<= 0: nothing)
+// at sample range_start[r] of pcm.  Both tables are device int64 -- in a decode set K7's seg_start / seg_samples.  Any
+// fill, any length, any sample-aligned start: whole units go through registers, the ends through the tail.
+hipError_t launch_md5_ranges(hipStream_t st, fhip_md5_state *states, int nstreams, const void *pcm, int pcm_format,
+                             int bytes_per_sample, int channels, const int32_t *seg_first, const int32_t *seg_range,
+                             const long long *range_start, const long long *range_samples);
 hipError_t launch_md5_final(hipStream_t st, const fhip_md5_state *states, int nstreams, uint8_t *digests);
 
 }  // namespace fhip

@@ -24,6 +24,14 @@
  * them in batches and compares the MD5 of what it wrote with STREAMINFO's unless that is all zero.  A frame that does
  * not decode, or an MD5 mismatch, ends in a non-zero exit status with the frame named on stderr.
  *
+ *   flake_amd_cli --decode --set OUTDIR a.flac b.flac ...
+ *
+ * --decode --set decodes files of one format through one decode set (flake_amd_decode_set_*): every file is indexed
+ * on the CPU, their frames go round-robin into shared GPU batches, every stream's MD5 is carried on the device and
+ * held against its STREAMINFO, and OUTDIR/<name>.wav is written per input.  An input whose format differs from the
+ * first's is an error that names it.  A file that fails is named on stderr and makes the exit status non-zero; the other
+ * files are still written in full.
+ *
  * Only canonical PCM WAV (8/16/24/32 bit) is read; this is a harness for the
  * host API, not a replacement for the reference's libpcm_io.
  */
@@ -373,6 +381,231 @@ static int run_decode(const char *in, const char *out)
     return rc;
 }
 
+/* ---- --decode --set: many FLAC files of one format through one decode set ---- */
+typedef struct {
+    const char *path;
+    uint8_t *file;
+    size_t len, pos;                 /* the file, and where its next frame starts */
+    FlakeAmdStreaminfo si;
+    int *sizes;                      /* every frame's size (flake_amd_index_frames over the whole file) */
+    long long nframes, next;         /* ... how many, and the next one to hand over */
+    FILE *fo;
+    unsigned long long total;
+    int bad;                         /* named on stderr already */
+    int skip;                        /* ... before it was a stream at all: it has no output file */
+    char name[1024];                 /* OUTDIR/<name>.wav */
+} dset_file;
+
+static void dset_free(dset_file *fs, int n)
+{
+    for (int i = 0; i < n; i++) {
+        if (fs[i].fo) fclose(fs[i].fo);
+        free(fs[i].file);
+        free(fs[i].sizes);
+    }
+    free(fs);
+}
+
+static int dset_load(dset_file *f)
+{
+    FILE *fi = fopen(f->path, "rb");
+    if (!fi) { perror(f->path); return 1; }
+    fseek(fi, 0, SEEK_END);
+    const long flen = ftell(fi);
+    fseek(fi, 0, SEEK_SET);
+    f->file = (uint8_t *)malloc(flen > 0 ? (size_t)flen : 1);
+    if (!f->file || flen < 0 || fread(f->file, 1, (size_t)flen, fi) != (size_t)flen) { fprintf(stderr, "cannot read %s\n", f->path); fclose(fi); return 1; }
+    fclose(fi);
+    f->len = (size_t)flen;
+    if (f->len < 4 + 4 + 34 || memcmp(f->file, "fLaC", 4) || (f->file[4] & 0x7F) != 0 ||
+        ((size_t)f->file[5] << 16 | (size_t)f->file[6] << 8 | f->file[7]) != 34) {
+        fprintf(stderr, "%s: not a FLAC file (no fLaC marker followed by STREAMINFO)\n", f->path);
+        return 1;
+    }
+    if (flake_amd_read_streaminfo(f->file + 8, &f->si) < 0) { fprintf(stderr, "%s: invalid STREAMINFO\n", f->path); return 1; }
+    size_t pos = 4;
+    for (;;) {
+        if (pos + 4 > f->len) { fprintf(stderr, "%s: metadata runs past the file\n", f->path); return 1; }
+        const int last = f->file[pos] >> 7;
+        pos += 4 + ((size_t)f->file[pos + 1] << 16 | (size_t)f->file[pos + 2] << 8 | f->file[pos + 3]);
+        if (pos > f->len) { fprintf(stderr, "%s: metadata runs past the file\n", f->path); return 1; }
+        if (last) break;
+    }
+    f->pos = pos;
+    return 0;
+}
+
+static int run_decode_set(const char *outdir, char **inputs, int n)
+{
+    if (n < 1) { fprintf(stderr, "--decode --set needs input files\n"); return 2; }
+    dset_file *fs = (dset_file *)calloc((size_t)n, sizeof *fs);
+    if (!fs) return 1;
+    int rc = 0, ref = -1;
+    unsigned maxn = 16;
+    /* a file that cannot be read or is no FLAC file is named (dset_load) and left out, like one that fails later; the
+     * first one that loads sets the format */
+    for (int i = 0; i < n; i++) {
+        dset_file *f = &fs[i];
+        f->path = inputs[i];
+        if (dset_load(f)) {
+            f->bad = f->skip = 1;
+            rc = 1;
+            continue;
+        }
+        if (ref < 0) ref = i;
+        if (f->si.channels != fs[ref].si.channels || f->si.bits_per_sample != fs[ref].si.bits_per_sample ||
+            f->si.sample_rate != fs[ref].si.sample_rate) {
+            fprintf(stderr, "%s: its format (%u channels, %u bits, %u Hz) differs from %s's: a decode set takes one format\n",
+                    f->path, f->si.channels, f->si.bits_per_sample, f->si.sample_rate, fs[ref].path);
+            dset_free(fs, n);
+            return 1;
+        }
+        const unsigned mb = f->si.max_block_size ? f->si.max_block_size : 65535u;
+        if (mb > maxn) maxn = mb;
+        const char *base = strrchr(f->path, '/');
+        base = base ? base + 1 : f->path;
+        const char *dot = strrchr(base, '.');
+        snprintf(f->name, sizeof f->name, "%s/%.*s.wav", outdir, (int)(dot ? dot - base : (long)strlen(base)), base);
+        for (int j = 0; j < i; j++)
+            if (!fs[j].skip && !strcmp(fs[j].name, f->name)) {
+                fprintf(stderr, "%s and %s would both be written to %s\n", fs[j].path, f->path, f->name);
+                dset_free(fs, n);
+                return 1;
+            }
+    }
+    if (ref < 0) { dset_free(fs, n); return 1; }
+    FlakeAmdStreaminfo like = fs[ref].si;
+    like.max_block_size = maxn;
+    const int nch = (int)like.channels, bps = (int)like.bits_per_sample, wbytes = (bps + 7) / 8, narrow = bps == 16;
+    /* the frames of every file, found on the CPU; a file whose frames end early is named now and decoded up to there */
+    for (int i = 0; i < n; i++) {
+        dset_file *f = &fs[i];
+        if (f->skip) continue;
+        const size_t left = f->len - f->pos;
+        const int cap = (int)(left / 8 + 1);
+        f->sizes = (int *)malloc(sizeof(int) * (size_t)cap);
+        size_t used = 0;
+        f->nframes = f->sizes ? flake_amd_index_frames(&f->si, f->file + f->pos, left, f->sizes, cap, &used) : -1;
+        if (f->nframes < 0 || used != left) {
+            fprintf(stderr, "%s: frame %lld (at byte %llu): %s\n", f->path, f->nframes < 0 ? 0ll : f->nframes,
+                    (unsigned long long)(f->pos + used), f->nframes < 0 ? "not a frame header of this stream" : "the frame is cut or its CRC-16 fails");
+            f->bad = 1;
+            rc = 1;
+            if (f->nframes < 0) f->nframes = 0;
+        }
+        f->fo = fopen(f->name, "wb");
+        if (!f->fo) { perror(f->name); dset_free(fs, n); return 1; }
+        uint8_t wh[44];
+        memset(wh, 0, sizeof wh);
+        fwrite(wh, 1, 44, f->fo);
+    }
+    /* (everything the loop below needs, so that every way out frees it) */
+    int *sor = NULL, *fof = NULL, *csz = NULL;
+    long long *rs = NULL, *ro = NULL;
+    void *pcm = NULL;
+    uint8_t *raw = NULL, *bytes = NULL;
+    size_t bytes_cap = 0;
+    FlakeAmdDecodeSet *g = flake_amd_decode_set_open(&like, n, 0);
+    if (!g) { fprintf(stderr, "decode set init failed: %s\n", flake_amd_decode_set_last_error(NULL)); rc = 1; goto out; }
+    /* round-robin: a call takes up to `per` frames of every file that has some left */
+    int per = (int)((4u << 20) / maxn / (unsigned)n);
+    if (per > 64) per = 64;
+    if (per < 1) per = 1;
+    sor = (int *)malloc(sizeof(int) * (size_t)n);
+    fof = (int *)malloc(sizeof(int) * (size_t)n);
+    csz = (int *)malloc(sizeof(int) * (size_t)n * (size_t)per);
+    rs = (long long *)malloc(sizeof(long long) * (size_t)n);
+    ro = (long long *)malloc(sizeof(long long) * (size_t)n);
+    const size_t cap = (size_t)n * (size_t)per * (size_t)maxn;
+    pcm = malloc(cap * (size_t)nch * (narrow ? 2 : 4));
+    raw = (uint8_t *)malloc((size_t)per * (size_t)maxn * (size_t)nch * (size_t)wbytes);
+    if (!sor || !fof || !csz || !rs || !ro || !pcm || !raw) { fprintf(stderr, "out of memory\n"); rc = 1; goto out; }
+    for (;;) {
+        int nruns = 0, nfr = 0;
+        size_t nb = 0;
+        for (int i = 0; i < n; i++) {
+            dset_file *f = &fs[i];
+            if (f->skip || f->next >= f->nframes || flake_amd_decode_set_failed(g, i, NULL, NULL) == 1) continue;
+            const int take = f->nframes - f->next < per ? (int)(f->nframes - f->next) : per;
+            size_t rb = 0;
+            for (int k = 0; k < take; k++) { csz[nfr++] = f->sizes[f->next + k]; rb += (size_t)f->sizes[f->next + k]; }
+            if (nb + rb > bytes_cap) {
+                uint8_t *more = (uint8_t *)realloc(bytes, (nb + rb) * 2);
+                if (!more) { fprintf(stderr, "out of memory\n"); rc = 1; goto out; }
+                bytes = more;
+                bytes_cap = (nb + rb) * 2;
+            }
+            memcpy(bytes + nb, f->file + f->pos, rb);
+            nb += rb;
+            f->pos += rb;
+            f->next += take;
+            sor[nruns] = i;
+            fof[nruns++] = take;
+        }
+        if (!nruns) break;
+        if (flake_amd_decode_set_frames(g, nruns, sor, fof, bytes, nb, csz, pcm, narrow ? 2 : 4, cap, rs) < 0 ||
+            flake_amd_decode_set_run_offsets(g, ro, nruns) != nruns) {
+            fprintf(stderr, "decode error: %s\n", flake_amd_decode_set_last_error(g));
+            rc = 1;
+            goto out;
+        }
+        for (int r = 0; r < nruns; r++) {
+            dset_file *f = &fs[sor[r]];
+            if (rs[r] < 0) {
+                long long fr = -1;
+                int st = 0;
+                flake_amd_decode_set_failed(g, sor[r], &fr, &st);
+                fprintf(stderr, "%s: frame %lld does not decode (status %d)\n", f->path, fr, st);
+                f->bad = 1;
+                rc = 1;
+                continue;
+            }
+            const size_t vals = (size_t)rs[r] * (size_t)nch;
+            if (narrow) {
+                fwrite((const int16_t *)pcm + (size_t)ro[r] * (size_t)nch, 2, vals, f->fo);
+            } else {
+                const int32_t *v = (const int32_t *)pcm + (size_t)ro[r] * (size_t)nch;
+                for (size_t i = 0; i < vals; i++) {
+                    const uint32_t u = wbytes == 1 ? (uint32_t)(v[i] + 128) : (uint32_t)v[i];
+                    for (int b = 0; b < wbytes; b++) raw[i * (size_t)wbytes + (size_t)b] = (uint8_t)(u >> (8 * b));
+                }
+                fwrite(raw, (size_t)wbytes, vals, f->fo);
+            }
+            f->total += (unsigned long long)rs[r];
+        }
+    }
+    for (int i = 0; i < n; i++) {
+        dset_file *f = &fs[i];
+        if (f->skip) continue;
+        uint8_t wh[44];
+        wav_header(wh, nch, (int)like.sample_rate, bps, (uint32_t)f->total);
+        fseek(f->fo, 0, SEEK_SET);
+        fwrite(wh, 1, 44, f->fo);
+        if (!f->bad) {
+            static const uint8_t zero[16] = {0};
+            uint8_t md5[16];
+            if (flake_amd_decode_set_md5(g, i, md5) != 0) {
+                fprintf(stderr, "%s: %s\n", f->path, flake_amd_decode_set_last_error(g));
+                f->bad = 1;
+            } else if (memcmp(f->si.md5sum, zero, 16) && memcmp(f->si.md5sum, md5, 16)) {
+                fprintf(stderr, "%s: MD5 mismatch: the decoded samples are not what STREAMINFO's signature was made of\n", f->path);
+                f->bad = 1;
+            } else if (f->si.samples && (unsigned long long)f->si.samples != (f->total & 0xFFFFFFFFull)) {
+                fprintf(stderr, "%s: %llu samples decoded, STREAMINFO says %u\n", f->path, f->total, f->si.samples);
+                f->bad = 1;
+            }
+            if (f->bad) rc = 1;
+        }
+        if (!f->bad) fprintf(stderr, "%s: %llu sample-frames decoded\n", f->path, f->total);
+    }
+    fprintf(stderr, "%lld device batches\n", flake_amd_decode_set_device_batches(g));
+out:
+    if (g) flake_amd_decode_set_close(g);
+    free(sor); free(fof); free(csz); free(rs); free(ro); free(pcm); free(raw); free(bytes);
+    dset_free(fs, n);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
     FlakeAmdContext s;
@@ -381,7 +614,18 @@ int main(int argc, char **argv)
     const char *in = NULL, *out = NULL, *setdir = NULL;
     for (int i = 1; i < argc; i++) {
         if (strcmp(argv[i], "--decode")) continue;
-        if (argc != 4) { fprintf(stderr, "usage: %s --decode in.flac out.wav\n", argv[0]); return 2; }
+        for (int j = 1; j + 1 < argc; j++) {
+            if (strcmp(argv[j], "--set")) continue;
+            /* --decode --set OUTDIR a.flac b.flac ...: everything that is neither switch nor OUTDIR is an input */
+            char **inputs = (char **)calloc((size_t)argc, sizeof(char *));
+            int ninputs = 0;
+            for (int k = 1; k < argc && inputs; k++)
+                if (k != i && k != j && k != j + 1) inputs[ninputs++] = argv[k];
+            const int rcs = inputs ? run_decode_set(argv[j + 1], inputs, ninputs) : 1;
+            free(inputs);
+            return rcs;
+        }
+        if (argc != 4) { fprintf(stderr, "usage: %s --decode in.flac out.wav\n       %s --decode --set OUTDIR a.flac b.flac ...\n", argv[0], argv[0]); return 2; }
         return run_decode(argv[i == 1 ? 2 : 1], argv[i == 3 ? 2 : 3]);
     }
     for (int i = 1; i < argc; i++) if (!strcmp(argv[i], "--set")) setdir = "";

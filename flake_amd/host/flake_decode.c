@@ -34,8 +34,6 @@ FLAKE_AMD_API int flake_amd_read_streaminfo(const unsigned char d[34], FlakeAmdS
 
 /* ---- a frame header on the CPU ---------------------------------------- */
 
-typedef struct { int n, vbs, len; unsigned long long number; } fa_hdr;
-
 static unsigned fa_crc8(const unsigned char *d, size_t n)
 {
     unsigned c = 0;
@@ -66,8 +64,8 @@ static int fa_bps_code(unsigned bps)
 }
 
 /* The header at d[0 .. avail): 0 when it is one whose codes agree with si and whose CRC-8 holds, else -1.  Never
- * reads at or past avail. */
-static int fa_parse_header(const FlakeAmdStreaminfo *si, const unsigned char *d, size_t avail, fa_hdr *h)
+ * reads at or past avail.  (Shared with flake_decode_set.c: host_internal.h.) */
+int fa_parse_header(const FlakeAmdStreaminfo *si, const unsigned char *d, size_t avail, fa_hdr *h)
 {
     if (avail < 6 || d[0] != 0xFF || (d[1] & 0xFE) != 0xF8) return -1;
     const int bs_code = d[2] >> 4, sr_code = d[2] & 15, ch_code = d[3] >> 4, bps_code = (d[3] >> 1) & 7;

@@ -1,0 +1,329 @@
+/*
+ * flake_decode_set.c -- a decode set: the frames of many streams of one format decoded in shared device batches
+ * (fhip_decode_frames_segments: K7's segment mode), each stream's MD5 carried on the device (K6, k_md5_ranges, fed by
+ * the ranges K7 leaves there).  The counterpart of flake_set.c on the decoding side.
+ *
+ * The planner (decode_set_plan.h) cuts a call into batches and writes the tables; this file owns the handle, the
+ * streams' states and what a batch's results mean for them: a failing frame fails its stream, for good, and no other.
+ */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "flake_amd.h"
+#include "flakehip.h"
+#include "host_internal.h"
+#include "decode_set_plan.h"
+
+typedef struct {
+    long long frames_done;        /* frames committed so far */
+    long long fail_frame;         /* failed: the frame, counted from the stream's first, and its status */
+    int fail_status;
+    fa_md5 md5;                   /* FLAKE_AMD_SET_MD5_HOST */
+} ds_stream;
+
+struct FlakeAmdDecodeSet {
+    fhip_ctx *hip;
+    FlakeAmdStreaminfo si;
+    int nstreams, max_batch;
+    unsigned flags;
+    fa_ds_stream *st;             /* what the planner reads */
+    ds_stream *sx;                /* the rest */
+    fhip_md5_state *states;       /* device: one per stream (neither _HOST nor _OFF) */
+    unsigned char *digests;       /* [nstreams][16], valid while have_digests */
+    int have_digests;
+    long long device_batches;
+    fa_ds_batch b;                /* the planner's tables and the device's answers, max_batch entries each */
+    int64_t *seg_start, *seg_samples;
+    int32_t *seg_failed;
+    fhip_verify_rec *recs;
+    long long *run_off;           /* the last call's run offsets in pcm */
+    int run_off_cap, run_off_n;
+    char err[384];
+};
+
+static char g_open_err[256];
+
+static int ds_device_md5(const FlakeAmdDecodeSet *g) { return !(g->flags & (FLAKE_AMD_SET_MD5_HOST | FLAKE_AMD_SET_MD5_OFF)); }
+
+FLAKE_AMD_API FlakeAmdDecodeSet *flake_amd_decode_set_open(const FlakeAmdStreaminfo *like, int nstreams, unsigned flags)
+{
+    g_open_err[0] = 0;
+    if (!like || like->channels < 1 || like->channels > 8 || like->bits_per_sample < 4 || like->bits_per_sample > 32 ||
+        like->sample_rate < 1 || like->sample_rate > 655350u || like->max_block_size > 65535u) {
+        snprintf(g_open_err, sizeof g_open_err, "STREAMINFO is out of range");
+        return NULL;
+    }
+    if (nstreams < 1 || nstreams > (1 << 20)) {
+        snprintf(g_open_err, sizeof g_open_err, "nstreams out of range");
+        return NULL;
+    }
+    if ((flags & ~(FLAKE_AMD_SET_MD5_HOST | FLAKE_AMD_SET_MD5_OFF)) ||
+        (flags & (FLAKE_AMD_SET_MD5_HOST | FLAKE_AMD_SET_MD5_OFF)) == (FLAKE_AMD_SET_MD5_HOST | FLAKE_AMD_SET_MD5_OFF)) {
+        snprintf(g_open_err, sizeof g_open_err, "unknown or contradictory flags");
+        return NULL;
+    }
+    FlakeAmdDecodeSet *g = (FlakeAmdDecodeSet *)calloc(1, sizeof *g);
+    if (!g) return NULL;
+    g->si = *like;
+    g->nstreams = nstreams;
+    g->flags = flags;
+    const char *eb = getenv("FLAKE_AMD_BATCH"), *ed = getenv("FLAKE_AMD_DEVICE");
+    g->max_batch = eb ? atoi(eb) : 1024;
+    if (g->max_batch < 1) g->max_batch = 1;
+    /* the handle, as flake_amd_decode_open makes it */
+    int bs = like->max_block_size ? (int)like->max_block_size : 65535;
+    if (bs < 16) bs = 16;
+    if ((long long)g->max_batch * bs > (4ll << 20)) g->max_batch = (int)((4ll << 20) / bs);
+    if (g->max_batch < 1) g->max_batch = 1;
+    fhip_params p;
+    memset(&p, 0, sizeof p);
+    p.channels = (int)like->channels; p.sample_rate = (int)like->sample_rate; p.bits_per_sample = (int)like->bits_per_sample;
+    p.block_size = bs; p.order_method = 1; p.stereo_method = 1; p.prediction_type = 2;
+    p.min_prediction_order = 1; p.max_prediction_order = 8; p.min_partition_order = 0; p.max_partition_order = 5;
+    p.lpc_precision = 15;
+    const size_t mb = (size_t)g->max_batch, ns = (size_t)nstreams;
+    fa_ds_batch *b = &g->b;
+    g->st = (fa_ds_stream *)calloc(ns, sizeof *g->st);
+    g->sx = (ds_stream *)calloc(ns, sizeof *g->sx);
+    g->digests = (unsigned char *)calloc(ns, 16);
+    b->seg_first = (int32_t *)calloc(mb + 1, sizeof(int32_t));
+    b->seg_number = (int64_t *)calloc(mb, sizeof(int64_t));
+    b->seg_variable = (int32_t *)calloc(mb, sizeof(int32_t));
+    b->seg_stream = (int32_t *)calloc(mb, sizeof(int32_t));
+    b->seg_run = (int32_t *)calloc(mb, sizeof(int32_t));
+    b->seg_frame0 = (int32_t *)calloc(mb, sizeof(int32_t));
+    b->seg_prev = (int32_t *)calloc(mb, sizeof(int32_t));
+    b->md5_first = (int32_t *)calloc(ns + 1, sizeof(int32_t));
+    b->md5_range = (int32_t *)calloc(mb, sizeof(int32_t));
+    b->last_seg = (int32_t *)calloc(ns, sizeof(int32_t));
+    b->planned = (long long *)calloc(ns, sizeof(long long));
+    g->seg_start = (int64_t *)calloc(mb, sizeof(int64_t));
+    g->seg_samples = (int64_t *)calloc(mb, sizeof(int64_t));
+    g->seg_failed = (int32_t *)calloc(mb, sizeof(int32_t));
+    g->recs = (fhip_verify_rec *)calloc(mb, sizeof(fhip_verify_rec));
+    const int have = g->st && g->sx && g->digests && b->seg_first && b->seg_number && b->seg_variable && b->seg_stream &&
+                     b->seg_run && b->seg_frame0 && b->seg_prev && b->md5_first && b->md5_range && b->last_seg &&
+                     b->planned && g->seg_start && g->seg_samples && g->seg_failed && g->recs;
+    int rc = have ? fhip_create(&g->hip, ed ? atoi(ed) : 0, &p, g->max_batch) : FHIP_E_NOMEM;
+    if (rc == FHIP_OK && ds_device_md5(g)) {
+        g->states = (fhip_md5_state *)fhip_device_alloc(ns * sizeof(fhip_md5_state));
+        rc = g->states ? fhip_md5_init_dev(g->hip, g->states, nstreams) : FHIP_E_NOMEM;
+        if (rc == FHIP_OK) rc = fhip_sync(g->hip);
+    }
+    if (rc != FHIP_OK) {
+        snprintf(g_open_err, sizeof g_open_err, "%s", g->hip ? fhip_last_error(g->hip) : fhip_strerror(rc));
+        flake_amd_decode_set_close(g);
+        return NULL;
+    }
+    for (int s = 0; s < nstreams; s++) { fa_md5_init(&g->sx[s].md5); g->sx[s].fail_frame = -1; }
+    return g;
+}
+
+static void ds_fail_stream(FlakeAmdDecodeSet *g, int s, long long frame, int status)
+{
+    if (g->st[s].failed) return;
+    g->st[s].failed = 1;
+    g->sx[s].fail_frame = frame;
+    g->sx[s].fail_status = status;
+}
+
+FLAKE_AMD_API long long flake_amd_decode_set_frames(FlakeAmdDecodeSet *g, int nruns, const int *stream_of_run,
+                                                    const int *frames_of_run, const unsigned char *stream, size_t bytes,
+                                                    const int *frame_sizes, void *pcm, int sample_bytes,
+                                                    size_t pcm_cap_samples, long long *run_samples)
+{
+    if (!g) return -1;
+    g->err[0] = 0;
+    if ((!stream && bytes) || (!pcm && pcm_cap_samples) || (nruns > 0 && !run_samples) ||
+        (sample_bytes != 2 && sample_bytes != 4)) {
+        snprintf(g->err, sizeof g->err, "bad argument");
+        return -1;
+    }
+    if (sample_bytes == 2 && g->si.bits_per_sample > 16) {
+        snprintf(g->err, sizeof g->err, "2-byte samples need bits_per_sample <= 16");
+        return -1;
+    }
+    long long total_frames = 0;
+    const int chk = fa_ds_check(g->nstreams, g->st, nruns, stream_of_run, frames_of_run, frame_sizes, bytes, &total_frames);
+    if (chk != FA_DS_OK) {
+        snprintf(g->err, sizeof g->err, "%s",
+                 chk == FA_DS_BAD_STREAM ? "a run names a stream outside the set" :
+                 chk == FA_DS_BAD_SIZE ? "the frame sizes run past the stream" :
+                 chk == FA_DS_FAILED_STREAM ? "a run names a stream that has failed" : "bad argument");
+        return -1;
+    }
+    if (nruns > g->run_off_cap) {
+        long long *n = (long long *)realloc(g->run_off, sizeof(long long) * (size_t)nruns);
+        if (!n) { snprintf(g->err, sizeof g->err, "out of memory"); return -1; }
+        g->run_off = n;
+        g->run_off_cap = nruns;
+    }
+    if (fhip_set_pcm_format(g->hip, sample_bytes == 2 ? FHIP_PCM_S16 : FHIP_PCM_S32) != FHIP_OK) {
+        snprintf(g->err, sizeof g->err, "%s", fhip_last_error(g->hip));
+        return -1;
+    }
+    /* from here on the call changes the set */
+    g->have_digests = 0;
+    g->run_off_n = nruns;
+    for (int r = 0; r < nruns; r++) { run_samples[r] = 0; g->run_off[r] = -1; }
+    /* a stream seen for the first time tells its blocking strategy and first number in its first frame */
+    {
+        size_t at = 0;
+        long long f = 0;
+        for (int r = 0; r < nruns; r++) {
+            const int s = stream_of_run[r];
+            if (frames_of_run[r] > 0 && !g->st[s].started && !g->st[s].failed) {
+                fa_hdr h;
+                if (fa_parse_header(&g->si, stream + at, (size_t)frame_sizes[f], &h)) {
+                    /* not a header this parser takes: the device decides what is wrong with it (its status is the
+                     * stream's, as for any later frame); it is shown the strategy bit the frame carries */
+                    g->st[s].variable = frame_sizes[f] >= 2 ? (stream[at + 1] & 1) : 0;
+                } else {
+                    g->st[s].started = 1;
+                    g->st[s].variable = h.vbs;
+                    g->st[s].next_number = (long long)h.number;
+                }
+            }
+            for (int k = 0; k < frames_of_run[r]; k++) at += (size_t)frame_sizes[f++];
+        }
+    }
+    const size_t nch = g->si.channels;
+    const int bps = (int)g->si.bits_per_sample;
+    fa_ds_cursor cur;
+    memset(&cur, 0, sizeof cur);
+    fa_ds_batch *b = &g->b;
+    size_t base = 0;                                  /* where the batch's samples begin in pcm */
+    long long total = 0;
+    while (fa_ds_plan(&cur, nruns, stream_of_run, frames_of_run, frame_sizes, g->nstreams, g->st, g->max_batch, b) > 0) {
+        int64_t summary[4] = {0, 0, -1, 0}, nsmp = 0;
+        fhip_decode_in in = {stream + b->byte0, (int64_t)b->nbytes, frame_sizes + b->frame0, b->nframes, 0, -1};
+        fhip_decode_segments sg = {b->seg_first, b->nsegs, b->seg_number, b->seg_variable, g->seg_start, g->seg_samples,
+                                   g->seg_failed};
+        fhip_decode_out out = {(int32_t *)((char *)pcm + base * nch * (size_t)sample_bytes),
+                               (int64_t)(pcm_cap_samples - base), g->recs, summary, &nsmp};
+        fhip_decode_md5 md = {g->states, g->nstreams, b->seg_stream};
+        const int rc = fhip_decode_frames_segments(g->hip, &in, &sg, &out, ds_device_md5(g) ? &md : NULL);
+        g->device_batches++;
+        if (rc != FHIP_OK && rc != FHIP_E_VERIFY) {
+            snprintf(g->err, sizeof g->err, "fhip_decode_frames_segments: %s", fhip_last_error(g->hip));
+            return -1;
+        }
+        /* the batch's segments in order: a good one commits its stream, a bad one fails it */
+        size_t extent = 0;
+        size_t hdr_at = b->byte0;
+        for (int k = 0; k < b->nsegs; k++) {
+            const int s = b->seg_stream[k], r = b->seg_run[k];
+            const int nf = b->seg_first[k + 1] - b->seg_first[k];
+            fa_ds_stream *t = &g->st[s];
+            const size_t seg_bytes_at = hdr_at;
+            for (int f = b->seg_first[k]; f < b->seg_first[k + 1]; f++) hdr_at += (size_t)frame_sizes[b->frame0 + f];
+            if (!t->failed && g->seg_failed[k] >= 0) {
+                const int bad = g->seg_failed[k];
+                ds_fail_stream(g, s, g->sx[s].frames_done + (bad - b->seg_first[k]), (int)g->recs[bad].status);
+            }
+            if (!t->failed && b->seg_number[k] < 0 && b->seg_prev[k] >= 0) {
+                /* a variable-block-size stream's later segment of the batch: numbered on from the earlier one */
+                fa_hdr h;
+                if (fa_parse_header(&g->si, stream + seg_bytes_at, (size_t)frame_sizes[b->frame0 + b->seg_first[k]], &h) ||
+                    (long long)h.number != t->next_number)
+                    ds_fail_stream(g, s, g->sx[s].frames_done, FHIP_VERIFY_NUMBER);
+            }
+            if (!t->failed && !t->started)       /* the device took a first frame that the CPU parser did not */
+                ds_fail_stream(g, s, g->sx[s].frames_done, FHIP_VERIFY_HEADER);
+            if (!t->failed && !t->variable) {
+                /* fixed blocks: the size rule from segment to segment (fa_ds_fixed_sizes), on the first and last header */
+                fa_hdr h0, h1;
+                const size_t last_bytes = (size_t)frame_sizes[b->frame0 + b->seg_first[k + 1] - 1];
+                if (fa_parse_header(&g->si, stream + seg_bytes_at, (size_t)frame_sizes[b->frame0 + b->seg_first[k]], &h0) ||
+                    fa_parse_header(&g->si, stream + hdr_at - last_bytes, last_bytes, &h1) ||
+                    fa_ds_fixed_sizes(t, nf, h0.n, h1.n))
+                    ds_fail_stream(g, s, g->sx[s].frames_done, FHIP_VERIFY_NUMBER);
+            }
+            if (t->failed) {
+                run_samples[r] = -1;
+                continue;
+            }
+            const size_t at = base + (size_t)g->seg_start[k], n = (size_t)g->seg_samples[k];
+            if (b->seg_frame0[k] == 0) g->run_off[r] = (long long)at;
+            if (g->flags & FLAKE_AMD_SET_MD5_HOST) {
+                if (sample_bytes == 2) fa_md5_pcm16(&g->sx[s].md5, (const int16_t *)pcm + at * nch, n * nch, bps);
+                else fa_md5_pcm(&g->sx[s].md5, (const int32_t *)pcm + at * nch, n * nch, bps);
+            }
+            t->next_number += t->variable ? (long long)n : (long long)nf;
+            g->sx[s].frames_done += nf;
+            run_samples[r] += (long long)n;
+            if (at + n - base > extent) extent = at + n - base;
+        }
+        base += extent;
+    }
+    for (int r = 0; r < nruns; r++)
+        if (run_samples[r] > 0) total += run_samples[r];              /* (a stream's runs before its failing one stand) */
+    (void)total_frames;
+    return total;
+}
+
+FLAKE_AMD_API int flake_amd_decode_set_run_offsets(const FlakeAmdDecodeSet *g, long long *offsets, int cap)
+{
+    if (!g || (!offsets && cap > 0)) return -1;
+    for (int r = 0; r < g->run_off_n && r < cap; r++) offsets[r] = g->run_off[r];
+    return g->run_off_n;
+}
+
+FLAKE_AMD_API int flake_amd_decode_set_md5(FlakeAmdDecodeSet *g, int stream, unsigned char md5[16])
+{
+    if (!g || !md5 || stream < 0 || stream >= g->nstreams) return -1;
+    if (g->flags & FLAKE_AMD_SET_MD5_OFF) {
+        snprintf(g->err, sizeof g->err, "the set was opened with FLAKE_AMD_SET_MD5_OFF: it has no digest");
+        return -1;
+    }
+    if (g->st[stream].failed) {
+        snprintf(g->err, sizeof g->err, "stream %d has failed: it has no digest", stream);
+        return -1;
+    }
+    if (g->flags & FLAKE_AMD_SET_MD5_HOST) {
+        fa_md5_final(&g->sx[stream].md5, md5);
+        return 0;
+    }
+    if (!g->have_digests) {                           /* every stream's at once: one launch, one copy, one wait */
+        if (fhip_md5_final(g->hip, g->states, g->nstreams, g->digests) != FHIP_OK) {
+            snprintf(g->err, sizeof g->err, "fhip_md5_final: %s", fhip_last_error(g->hip));
+            return -1;
+        }
+        g->have_digests = 1;
+    }
+    memcpy(md5, g->digests + (size_t)stream * 16, 16);
+    return 0;
+}
+
+FLAKE_AMD_API int flake_amd_decode_set_failed(const FlakeAmdDecodeSet *g, int stream, long long *frame, int *status)
+{
+    if (!g || stream < 0 || stream >= g->nstreams) return -1;
+    if (!g->st[stream].failed) return 0;
+    if (frame) *frame = g->sx[stream].fail_frame;
+    if (status) *status = g->sx[stream].fail_status;
+    return 1;
+}
+
+FLAKE_AMD_API long long flake_amd_decode_set_device_batches(const FlakeAmdDecodeSet *g)
+{
+    return g ? g->device_batches : -1;
+}
+
+FLAKE_AMD_API const char *flake_amd_decode_set_last_error(const FlakeAmdDecodeSet *g)
+{
+    return g ? g->err : g_open_err;
+}
+
+FLAKE_AMD_API void flake_amd_decode_set_close(FlakeAmdDecodeSet *g)
+{
+    if (!g) return;
+    if (g->hip) { (void)fhip_sync(g->hip); fhip_destroy(g->hip); }
+    if (g->states) fhip_device_free(g->states);
+    fa_ds_batch *b = &g->b;
+    free(b->seg_first); free(b->seg_number); free(b->seg_variable); free(b->seg_stream); free(b->seg_run);
+    free(b->seg_frame0); free(b->seg_prev); free(b->md5_first); free(b->md5_range); free(b->last_seg); free(b->planned);
+    free(g->seg_start); free(g->seg_samples); free(g->seg_failed); free(g->recs); free(g->run_off);
+    free(g->st); free(g->sx); free(g->digests);
+    free(g);
+}

@@ -18,6 +18,12 @@ void fa_md5_final(const fa_md5 *m, uint8_t out[16]);
 void fa_md5_pcm(fa_md5 *m, const int32_t *pcm, size_t nvalues, int bps);
 void fa_md5_pcm16(fa_md5 *m, const int16_t *pcm, size_t nvalues, int bps);
 
+/* A frame header read on the CPU (flake_decode.c): block size, blocking-strategy bit, header length in bytes, the
+ * coded frame or sample number. */
+typedef struct { int n, vbs, len; unsigned long long number; } fa_hdr;
+struct FlakeAmdStreaminfo;
+int fa_parse_header(const struct FlakeAmdStreaminfo *si, const unsigned char *d, size_t avail, fa_hdr *h);
+
 /* Which of a chunk's cnt blocks the verifier's frame index (it counts the chunk's frames) lies in: block b holds
  * block_frames[b] frames, one each when the table is null.  -1: none -- an index below 0 or past the chunk's frames;
  * an entry below 1 ends the search (nothing behind a block that was not encoded can be placed). */

@@ -288,6 +288,67 @@ FLAKE_AMD_API int flake_amd_decode_md5(FlakeAmdDecoder *d, unsigned char md5[16]
 FLAKE_AMD_API const char *flake_amd_decode_last_error(const FlakeAmdDecoder *d);
 FLAKE_AMD_API void flake_amd_decode_close(FlakeAmdDecoder *d);
 
+/*
+ * A decode set: the frames of MANY streams decoded in shared device batches (fhip_decode_frames_segments: K7's segment
+ * mode), each stream's MD5 carried on the device (K6's k_md5_ranges, fed on the device by the ranges K7 leaves) -- the
+ * counterpart of flake_amd_set_* for decoding.  A folder of ordinary files, one FlakeAmdDecoder after another, is a few
+ * dozen frames per launch and one host hash per file; through a set it is FLAKE_AMD_BATCH frames per launch.
+ *
+ * All streams share like's channels, sample rate and bits per sample; their blocks are at most like->max_block_size
+ * (65535 when that is 0).  The blocking strategy and the first number are read PER STREAM from the first frame the set
+ * sees of it.  flags: FLAKE_AMD_SET_MD5_HOST (hash on the CPU, on the calling thread: the comparison leg) or
+ * FLAKE_AMD_SET_MD5_OFF (no hash); anything else, or both, is an error.  One handle; the device is FLAKE_AMD_DEVICE, a
+ * device batch holds up to FLAKE_AMD_BATCH frames (default 1024; fewer for very long blocks).  NULL on failure:
+ * flake_amd_decode_set_last_error(NULL) says why.
+ *
+ * flake_amd_decode_set_frames hands over nruns RUNS: run r is frames_of_run[r] consecutive frames of stream
+ * stream_of_run[r]; all frames lie back to back in stream[0 .. bytes) with their frame_sizes (flake_amd_index_frames).
+ * A stream may have several runs in a call, in stream order; a run may be empty.  pcm (int32 with sample_bytes 4,
+ * int16_t with 2, bits_per_sample <= 16 only; pcm_cap_samples per channel) receives the runs' samples back to back in
+ * call order -- as flake_amd_set_encode's `out`, the caller scatters -- and run_samples[r] each run's count.  The call is
+ * cut into device batches at frame boundaries, inside a run where that falls; the run's numbering carries over.
+ * Returns the samples per channel of the good runs, or -1 with NOTHING changed for a bad argument: a stream index
+ * outside the set, frame sizes below 1 or past `bytes`, 2-byte samples above 16 bits, or a run that names a FAILED stream.
+ *
+ * Failure is per stream, not per call.  A frame that fails (any FHIP_VERIFY_* status; also a frame that does not fit
+ * pcm_cap_samples) fails its stream, for good: flake_amd_decode_set_failed returns 1 with the frame, counted from the
+ * stream's first, and the status (0: the stream is good; -1: no such stream).  The failing run and that stream's later
+ * runs of the call get run_samples[r] = -1; their samples are unspecified, and what lies behind them in pcm is no
+ * longer where the counts alone put it: flake_amd_decode_set_run_offsets gives every run's first sample in pcm for the
+ * last call (-1 for a run without one; returns the number of runs).  Every other stream is committed as if nothing had
+ * happened.  (A failing run's samples are NOT kept as a hole of their size -- a size nobody knows once a header is
+ * broken: the next device batch's samples begin behind the last good segment's.  Hence the offsets entry.)
+ *
+ * Two rules are held on the CPU where the device has no predecessor to compare with.  A fixed-block stream keeps ONE
+ * block size from segment to segment: a frame shorter than it ends the stream, and a frame behind such a frame fails
+ * with NUMBER even where a device batch or a run was cut between the two -- there the frame BEHIND the short one is
+ * named, inside one segment the short one itself.  A variable-block-size stream's later run in a device batch is held
+ * to the sample number that its earlier run's samples lead to.  A stream whose first header the CPU cannot read is
+ * still handed to the device, which names what is wrong with it (CRC8 for a CRC-8, as for any later frame).
+ *
+ * flake_amd_decode_set_md5: the digest of everything stream `stream` has returned -- what its STREAMINFO's md5sum must
+ * be after the last frame.  The first request after a call finalises ALL streams' digests (one launch, one copy, one
+ * synchronisation); later requests are copies.  -1 for a failed stream or a set opened with FLAKE_AMD_SET_MD5_OFF.
+ * flake_amd_decode_set_device_batches: device batches run so far (-1 without a set).
+ *
+ * Measured (profiles/decode_set_bench.txt, 4096 stereo 16-bit frames of 4096): 256 streams of 16 frames take 77.7 ms
+ * through one set, 3704 ms through one FlakeAmdDecoder each and 134.5 ms as one stream through one decoder.  A lane
+ * hashes 87 MB/s, a CPU core about 1 GB/s: the device hash loses to FLAKE_AMD_SET_MD5_HOST up to 32 streams (16 streams:
+ * 259 against 134.5 ms) and wins from 64 on; below a few dozen streams open the set with FLAKE_AMD_SET_MD5_HOST.
+ */
+typedef struct FlakeAmdDecodeSet FlakeAmdDecodeSet;
+FLAKE_AMD_API FlakeAmdDecodeSet *flake_amd_decode_set_open(const FlakeAmdStreaminfo *like, int nstreams, unsigned flags);
+FLAKE_AMD_API long long flake_amd_decode_set_frames(FlakeAmdDecodeSet *g, int nruns, const int *stream_of_run,
+                                                    const int *frames_of_run, const unsigned char *stream, size_t bytes,
+                                                    const int *frame_sizes, void *pcm, int sample_bytes,
+                                                    size_t pcm_cap_samples, long long *run_samples);
+FLAKE_AMD_API int flake_amd_decode_set_run_offsets(const FlakeAmdDecodeSet *g, long long *offsets, int cap);
+FLAKE_AMD_API int flake_amd_decode_set_md5(FlakeAmdDecodeSet *g, int stream, unsigned char md5[16]);
+FLAKE_AMD_API int flake_amd_decode_set_failed(const FlakeAmdDecodeSet *g, int stream, long long *frame, int *status);
+FLAKE_AMD_API long long flake_amd_decode_set_device_batches(const FlakeAmdDecodeSet *g);
+FLAKE_AMD_API const char *flake_amd_decode_set_last_error(const FlakeAmdDecodeSet *g);
+FLAKE_AMD_API void flake_amd_decode_set_close(FlakeAmdDecodeSet *g);
+
 /* Deterministic synthetic PCM, channel-interleaved int32 as
  * flake_encode_frame() expects: nframes blocks of n samples per channel,
  * starting at absolute frame index first_frame. */

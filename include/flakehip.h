@@ -643,6 +643,53 @@ FHIP_API int fhip_decode_frames_dev(fhip_ctx *ctx, const fhip_decode_in *in, con
  * fhip_last_verify_failure() returns the same as numbers, and the samples of the good frames are still delivered. */
 FHIP_API int fhip_decode_frames(fhip_ctx *ctx, const fhip_decode_in *in, const fhip_decode_out *out);
 
+/*
+ * The frames of MANY streams in one call: the batch is cut into nsegs SEGMENTS, runs of consecutive frames that each
+ * belong to one stream (CSR: segment s is frames seg_first[s] .. seg_first[s + 1], seg_first[0] = 0,
+ * seg_first[nsegs] = nframes; a segment may be empty).  The rules above hold per segment: continuity only against a
+ * predecessor in the same segment, the segment's first frame against seg_number[s] (-1: not checked), bit 15 of its
+ * headers against seg_variable[s], and on fixed blocks "every frame but the last has one size" inside the segment, whose
+ * last frame may be shorter.  in->variable_blocks and in->first_number are not read.  Placement is the batch's: a
+ * frame's samples start at the sum of the sizes of all good headers before it, so the segments lie back to back in pcm;
+ * pcm_cap, the records, summary and nsamples keep their meaning for the batch as a whole.  Per segment the call
+ * leaves seg_start (where its samples begin in pcm), seg_samples (the samples of its frames whose header, number and
+ * place were good: nsamples' rule) and seg_failed (the index in the batch of its first frame that failed with any
+ * status, -1 if none).  The launch list is "k_decode_frames segments", "k_decode", "k_decode_final",
+ * "k_decode_seg_final"; timed as "k_decode".
+ */
+typedef struct fhip_decode_segments {
+    const int32_t *seg_first;     /* [nsegs + 1] */
+    int32_t        nsegs;         /* >= 1 */
+    const int64_t *seg_number;    /* [nsegs] */
+    const int32_t *seg_variable;  /* [nsegs] 0 or 1 */
+    int64_t       *seg_start;     /* [nsegs] out */
+    int64_t       *seg_samples;   /* [nsegs] out */
+    int32_t       *seg_failed;    /* [nsegs] out */
+} fhip_decode_segments;
+
+/* The host form's optional hash: segment s is absorbed into states[seg_stream[s]] on the device (K6, from the decoded
+ * PCM where it lies, its range being what K7 left in seg_start / seg_samples: no host round trip), segments of one
+ * stream in batch order. */
+typedef struct fhip_decode_md5 {
+    struct fhip_md5_state *states; /* DEVICE memory, nstreams records (declared below) */
+    int32_t         nstreams;
+    const int32_t  *seg_stream;   /* HOST [nsegs], each 0 .. nstreams - 1 */
+} fhip_decode_md5;
+
+/* As fhip_decode_frames_dev; every table and output of segs is DEVICE memory too (the kernels keep every table read and
+ * every output inside [0, nsegs) whatever seg_first holds; its values are the caller's).  segs == NULL: exactly
+ * fhip_decode_frames_dev.  FHIP_E_INVALID with nothing queued and an empty launch list also for nsegs < 1 or a null
+ * table. */
+FHIP_API int fhip_decode_frames_segments_dev(fhip_ctx *ctx, const fhip_decode_in *in, const fhip_decode_segments *segs,
+                                             const fhip_decode_out *out);
+/* As fhip_decode_frames, with HOST tables and outputs in segs: also FHIP_E_INVALID, nothing queued, when seg_first does
+ * not start at 0, decreases or does not end at nframes, when a seg_variable is not 0 or 1, a seg_number is below -1 or a
+ * seg_stream is outside the states.  segs == NULL (md5 must then be NULL): exactly fhip_decode_frames.  With md5 the
+ * hash is queued behind K7 and before the download ("k_md5_ranges<...>" ends the launch list).  FHIP_E_VERIFY when any
+ * frame failed; the good segments' samples, all three per-segment outputs and the hashes are still delivered. */
+FHIP_API int fhip_decode_frames_segments(fhip_ctx *ctx, const fhip_decode_in *in, const fhip_decode_segments *segs,
+                                         const fhip_decode_out *out, const fhip_decode_md5 *md5);
+
 /* ---- MD5 of many streams (K6) ---------------------------------------- */
 
 /*
@@ -677,6 +724,16 @@ FHIP_API int fhip_md5_init_dev(fhip_ctx *ctx, fhip_md5_state *states, int nstrea
 FHIP_API int fhip_md5_update_dev(fhip_ctx *ctx, fhip_md5_state *states, int nstreams, const void *pcm,
                                  int block_size, const int32_t *seg_first, const int32_t *seg_block);
 FHIP_API int fhip_md5_final_dev(fhip_ctx *ctx, const fhip_md5_state *states, int nstreams, uint8_t *digests);
+/* The update over ranges of samples that the DEVICE names: stream s absorbs, in this order, the ranges
+ * seg_range[seg_first[s] .. seg_first[s + 1]) (int32 tables, CSR, as _update's); range r is the range_samples[r]
+ * samples per channel at sample range_start[r] of pcm (both DEVICE int64: K7's seg_start / seg_samples serve as they
+ * are).  A length <= 0 absorbs nothing; a stream with no range keeps its state bit for bit.  Any fill, any length, any
+ * start: bytes go through the stream's tail until it is empty, whole 64-byte units (192 at 3 bytes per sample) are
+ * then built in registers from loads that need no more than the sample's own alignment, and the rest goes through the
+ * tail ("k_md5_ranges<int16_t,2>" in fhip_last_launches).  Nothing checks the ranges against the buffer. */
+FHIP_API int fhip_md5_update_ranges_dev(fhip_ctx *ctx, fhip_md5_state *states, int nstreams, const void *pcm,
+                                        const int32_t *seg_first, const int32_t *seg_range, const int64_t *range_start,
+                                        const int64_t *range_samples);
 /* _final with a HOST digests[nstreams][16] (states stay device memory): finalises, copies, synchronises -- once
  * for all streams. */
 FHIP_API int fhip_md5_final(fhip_ctx *ctx, const fhip_md5_state *states, int nstreams, uint8_t *digests);
@@ -717,7 +774,7 @@ FHIP_API int fhip_get_kernel_times(fhip_ctx *ctx, const char **names, double *ms
  * one or two workgroups per tile), "tail" (K2 runs inside K1), "fused" (K1 applies K0's decisions),
  * "narrow" (16-bit sample rows).  The calls that start a new list are the encode entries
  * (fhip_encode_subframes*, fhip_frames_packed_begin / fhip_encode_frames_packed, the VBS entries)
- * and fhip_prepare_ahead, the fhip_md5_* entries and fhip_decode_frames(_dev).  A host-side record: it adds no device work.  (One exception:
+ * and fhip_prepare_ahead, the fhip_md5_* entries, fhip_decode_frames(_dev) and fhip_decode_frames_segments(_dev).  A host-side record: it adds no device work.  (One exception:
  * "k_md5_streams<int16_t,2> fast" / "... general" name a choice that is made on the device when the block shape
  * allows the fast path; asking for the list then waits for that launch.)  names[0 .. cap) receive
  * strings owned by the handle, valid until its next such call; returns the number of launches. */
