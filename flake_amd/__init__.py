@@ -155,6 +155,18 @@ class DecodeSegments(C.Structure):
                 ("seg_failed", C.c_void_p)]
 
 
+class IndexIn(C.Structure):
+    """``fhip_index_in``"""
+    _fields_ = [("stream", C.c_void_p), ("stream_bytes", C.c_int64), ("range_first", C.c_void_p),
+                ("nranges", C.c_int32), ("max_block_size", C.c_int32), ("frame_cap", C.c_int32)]
+
+
+class IndexOut(C.Structure):
+    """``fhip_index_out``"""
+    _fields_ = [("frame_bytes", C.c_void_p), ("range_frames", C.c_void_p), ("range_consumed", C.c_void_p),
+                ("range_variable", C.c_void_p)]
+
+
 class DecodeMd5(C.Structure):
     """``fhip_decode_md5``"""
     _fields_ = [("states", C.c_void_p), ("nstreams", C.c_int32), ("seg_stream", C.c_void_p)]
@@ -235,6 +247,9 @@ def load_library() -> C.CDLL:
         "fhip_decode_frames_segments": (i, [vp, C.POINTER(DecodeIn), C.POINTER(DecodeSegments), C.POINTER(DecodeOut),
                                             C.POINTER(DecodeMd5)]),
         "fhip_md5_update_ranges_dev": (i, [vp, vp, i, vp, vp, vp, vp, vp]),
+        "fhip_index_frames_dev": (i, [vp, C.POINTER(IndexIn), C.POINTER(IndexOut)]),
+        "fhip_index_frames": (i, [vp, C.POINTER(IndexIn), C.POINTER(IndexOut)]),
+        "fhip_index_geometry": (None, [C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
         "fhip_get_kernel_times": (i, [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double),
                                       C.POINTER(i), i, i]),
         "fhip_last_launches": (i, [vp, C.POINTER(C.c_char_p), i]),
@@ -293,6 +308,7 @@ ABI_SYMBOLS = (
     "fhip_autocorr_tile",
     "fhip_decode_frames_dev", "fhip_decode_frames",
     "fhip_decode_frames_segments_dev", "fhip_decode_frames_segments", "fhip_md5_update_ranges_dev",
+    "fhip_index_frames_dev", "fhip_index_frames", "fhip_index_geometry",
 )
 
 
@@ -617,12 +633,42 @@ class Encoder:
         self._check(self.lib.fhip_decode_frames_segments_dev(self._h, C.byref(di), C.byref(sg), C.byref(do)),
                     "fhip_decode_frames_segments_dev")
 
+    # -- K8: frame discovery ----------------------------------------------
+    def index_ranges(self, stream, range_first, max_block_size: int = 0, frame_cap: int | None = None, sentinel=None):
+        """fhip_index_frames on host data: the CPU indexer's answer for the streams stream[range_first[r] :
+        range_first[r + 1]] (channels, bits per sample and rate are the handle's).  frame_cap defaults to room for
+        every frame there can be.  Returns (rc, frame_bytes int32[frame_cap], range_frames int32[nranges],
+        range_consumed int64[nranges], range_variable int32[nranges]); entries of frame_bytes behind the last frame keep
+        `sentinel` (default 0).  rc other than OK is returned, not raised (E_INVALID: nothing was queued)."""
+        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
+                                  else stream, dtype=np.uint8)
+        rf = np.ascontiguousarray(range_first, dtype=np.int64)
+        nr = len(rf) - 1
+        if frame_cap is None:
+            frame_cap = st.size // 8 + nr + 1           # a frame is no shorter than its header and CRC-16
+        fb = np.full(max(frame_cap, 1), 0 if sentinel is None else sentinel, dtype=np.int32)
+        k = max(nr, 1)
+        r_frames, r_var = np.full(k, -7, np.int32), np.full(k, -7, np.int32)
+        r_cons = np.full(k, -7, np.int64)
+        ii = IndexIn(st.ctypes.data if st.size else None, st.size, rf.ctypes.data, nr, int(max_block_size), int(frame_cap))
+        io = IndexOut(fb.ctypes.data, r_frames.ctypes.data, r_cons.ctypes.data, r_var.ctypes.data)
+        rc = self.lib.fhip_index_frames(self._h, C.byref(ii), C.byref(io))
+        return rc, fb[:frame_cap], r_frames[:nr], r_cons[:nr], r_var[:nr]
+
+    def index_ranges_dev(self, stream, stream_bytes: int, range_first, nranges: int, max_block_size: int, frame_cap: int,
+                         frame_bytes, range_frames, range_consumed, range_variable) -> None:
+        """K8 on device-resident data (torch tensors or raw device addresses); async.  range_first, range_consumed:
+        int64; the other tables int32."""
+        ii = IndexIn(_ptr(stream), stream_bytes, _ptr(range_first), nranges, int(max_block_size), int(frame_cap))
+        io = IndexOut(_ptr(frame_bytes), _ptr(range_frames), _ptr(range_consumed), _ptr(range_variable))
+        self._check(self.lib.fhip_index_frames_dev(self._h, C.byref(ii), C.byref(io)), "fhip_index_frames_dev")
+
     def kernel_times(self, reset: bool = True) -> dict:
-        names = (C.c_char_p * 8)()
-        ms = (C.c_double * 8)()
-        cnt = (C.c_int * 8)()
-        k = self.lib.fhip_get_kernel_times(self._h, names, ms, cnt, 8, int(reset))
-        return {names[i].decode(): (ms[i], cnt[i]) for i in range(k)}
+        names = (C.c_char_p * 32)()
+        ms = (C.c_double * 32)()
+        cnt = (C.c_int * 32)()
+        k = self.lib.fhip_get_kernel_times(self._h, names, ms, cnt, 32, int(reset))
+        return {names[i].decode(): (ms[i], cnt[i]) for i in range(min(k, 32))}
 
     def last_launches(self) -> list:
         """The kernel instances the handle's most recent encode call (or prepare_ahead) queued, in
@@ -869,6 +915,11 @@ def load_host_library() -> C.CDLL:
     lib.flake_amd_decode_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
                                             C.c_int, C.c_size_t]
     lib.flake_amd_decode_frames.restype = C.c_longlong
+    lib.flake_amd_decode_index.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
+    lib.flake_amd_decode_index.restype = C.c_longlong
+    lib.flake_amd_decode_set_index.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_void_p]
+    lib.flake_amd_decode_set_index.restype = C.c_int
     lib.flake_amd_decode_md5.argtypes = [C.c_void_p, C.c_void_p]
     lib.flake_amd_decode_md5.restype = C.c_int
     lib.flake_amd_decode_last_error.argtypes = [C.c_void_p]
@@ -1082,6 +1133,24 @@ class HostDecoder:
             raise FlakeHipError(int(n), "flake_amd_decode_frames", self.last_error())
         return out[:n]
 
+    def index(self, stream, cap: int | None = None):
+        """flake_amd_decode_index: index_frames' answer, found on the device (K8) -- (frame sizes int32[], bytes they
+        cover), or None where the stream does not start with a frame.  Raises FlakeHipError where the device cannot
+        answer (2 GiB and more)."""
+        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
+                                  else stream, dtype=np.uint8)
+        if cap is None:
+            cap = st.size // 8 + 1            # no frame is shorter than its header and CRC-16
+        sizes = np.zeros(max(cap, 1), dtype=np.int32)
+        used = C.c_size_t(0)
+        n = self.lib.flake_amd_decode_index(self._d, st.ctypes.data if st.size else None, st.size, sizes.ctypes.data, cap,
+                                            C.byref(used))
+        if n < -1:
+            raise FlakeHipError(int(n), "flake_amd_decode_index", self.last_error())
+        if n < 0:
+            return None
+        return sizes[:n].copy(), int(used.value)
+
     def md5(self) -> bytes:
         """flake_amd_decode_md5: of everything decoded so far."""
         buf = (C.c_ubyte * 16)()
@@ -1260,6 +1329,35 @@ class DecodeSet:
         off = np.zeros(max(len(runs), 1), dtype=np.int64)
         self.lib.flake_amd_decode_set_run_offsets(self._g, off.ctypes.data, len(runs))
         return [None if rs[r] < 0 else out[off[r]:off[r] + rs[r]] if rs[r] else out[:0] for r in range(len(runs))]
+
+    def index(self, streams, max_block_size: int | None = None):
+        """flake_amd_decode_set_index: the frames of many files in one device call (K8).  streams: the files' bytes,
+        each from its first frame header on; max_block_size: their STREAMINFO value (default: the set's).  Returns one
+        entry per stream, each what index_frames returns for it: (frame sizes int32[], bytes they cover) or None."""
+        parts = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.asarray(x, dtype=np.uint8)
+                 for x in streams]
+        if not parts:
+            return []
+        st = np.ascontiguousarray(np.concatenate(parts))
+        first = np.zeros(len(parts) + 1, dtype=np.uintp)
+        first[1:] = np.cumsum([x.size for x in parts])
+        cap = st.size // 8 + len(parts) + 1
+        sizes = np.zeros(cap, dtype=np.int32)
+        frames = np.zeros(len(parts), dtype=np.int64)
+        cons = np.zeros(len(parts), dtype=np.uintp)
+        rc = self.lib.flake_amd_decode_set_index(self._g, int(self.si.max_block_size if max_block_size is None else max_block_size),
+                                                 st.ctypes.data if st.size else None, first.ctypes.data, len(parts),
+                                                 sizes.ctypes.data, cap, frames.ctypes.data, cons.ctypes.data)
+        if rc != 0:
+            raise FlakeHipError(int(rc), "flake_amd_decode_set_index", self.last_error())
+        out, at = [], 0
+        for r in range(len(parts)):
+            if frames[r] < 0:
+                out.append(None)
+                continue
+            out.append((sizes[at:at + frames[r]].copy(), int(cons[r])))
+            at += int(frames[r])
+        return out
 
     def md5(self, stream: int):
         """The digest of everything the stream has returned, or None (a failed stream; a set without MD5)."""

@@ -145,6 +145,16 @@ struct fhip_ctx {
     bool vfail_has_number = false;            // fhip_last_verify_number: the number that frame had to carry, where a
     uint32_t vfail_number = 0;                // table said so
 
+    // K8 (fhip_index_frames*): working memory, grow-only, allocated at first use (ensure_index)
+    DevBuf<int32_t> d_iwg;                    // wg_cnt [nwg], wg_key [nwg + 1], ncand [1]
+    DevBuf<int32_t> d_icand;                  // cand_pos, cand_meta, cand_end: [table_cap] each
+    DevBuf<unsigned long long> d_inumkey;     // [table_cap]
+    DevBuf<long long> d_irng;                 // rng_off [nranges], then rng_cf, rng_cnt, rng_vbs as int32
+    DevBuf<uint8_t> d_istream;                // fhip_index_frames: the host stream uploaded ...
+    DevBuf<long long> d_iio;                  // ... range_first [nranges + 1], range_consumed [nranges], then int32:
+                                              // range_frames, range_variable [nranges], frame_bytes
+    std::vector<long long> h_iio;             // ... and the host image the outputs come back to
+
     std::vector<std::string> launches;        // fhip_last_launches: what the most recent call queued
 
     // ragged batches (fhip_frames_packed_*_ragged): the per-frame tables, one device block laid out as
@@ -199,10 +209,13 @@ void note_launch(const char *fmt, ...)
 
 namespace {
 
-constexpr int kNumKernels = 8;
+constexpr int kNumKernels = 8 + fhip::INDEX_STEPS;
 const char *const kKernelNames[kNumKernels] = {"k_prepare", "k_autocorr", "k_lpc", "k_encode", "k_assemble",
-                                               "k_order_search", "k_verify", "k_decode"};
-constexpr int kProfVerify = 6, kProfDecode = 7;
+                                               "k_order_search", "k_verify", "k_decode",
+                                               // K8's launches, one name each (fhip::index_step_name without the <>)
+                                               "k_index_count", "k_index_wgscan", "k_index_scatter", "k_index_walk",
+                                               "k_index_ranges", "k_index_emit"};
+constexpr int kProfVerify = 6, kProfDecode = 7, kProfIndex = 8;
 
 int fail_hip(fhip_ctx *c, hipError_t e, const char *what)
 {
@@ -2749,6 +2762,136 @@ int fhip_decode_frames_segments(fhip_ctx *c, const fhip_decode_in *in, const fhi
              sum[1], sum[0], sum[2], verify_status_name((int)sum[3]), r.subframe, r.bit);
     c->err = buf;
     return FHIP_E_VERIFY;
+}
+
+// ---- K8: frame discovery ---------------------------------------------------------------------------
+
+namespace {
+int index_check(fhip_ctx *c, const fhip_index_in *in, const fhip_index_out *out)
+{
+    if (!c) return FHIP_E_INVALID;
+    c->launches.clear();
+    c->md5_log_entry = -1;
+    if (!in || !out || !in->range_first || !out->range_frames || !out->range_consumed || !out->range_variable)
+        return fail(c, FHIP_E_INVALID, "null argument");
+    if (in->nranges < 1) return fail(c, FHIP_E_INVALID, "nranges must be at least 1");
+    if (in->stream_bytes < 0 || in->frame_cap < 0 || in->max_block_size < 0) return fail(c, FHIP_E_INVALID, "negative count");
+    if (in->stream_bytes >= (1ll << 31)) return fail(c, FHIP_E_INVALID, "stream_bytes must be below 2^31");
+    if (in->stream_bytes > 0 && !in->stream) return fail(c, FHIP_E_INVALID, "null stream");
+    if (in->frame_cap > 0 && !out->frame_bytes) return fail(c, FHIP_E_INVALID, "null frame_bytes");
+    return FHIP_OK;
+}
+
+// Two headers lie at least five bytes apart (byte 1 .. 4 of a header cannot be 0xFF: the sync's second byte, the
+// reserved rate code 15, the reserved bit, a number that begins with eight ones), and a range holds one more than its
+// length / 5 at most: the table is sized for that, so no candidate is ever dropped and nothing waits for a count.
+size_t index_table_cap(long long stream_bytes, int nranges) { return (size_t)(stream_bytes / 5) + (size_t)nranges + 1; }
+
+// Queue K8 on the handle's stream; all of in / out is device memory.
+int run_index(fhip_ctx *c, const fhip_index_in &in, const fhip_index_out &out)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nr = (size_t)in.nranges, cap = index_table_cap(in.stream_bytes, in.nranges);
+    const int nwg = fhip::index_nwg(in.stream_bytes);
+    HIP_TRY(c, c->d_iwg.reserve(2 * (size_t)nwg + 2));
+    HIP_TRY(c, c->d_icand.reserve(3 * cap));
+    HIP_TRY(c, c->d_inumkey.reserve(cap));
+    HIP_TRY(c, c->d_irng.reserve(nr + (3 * nr + 1) / 2));
+    int32_t *rng32 = reinterpret_cast<int32_t *>(c->d_irng.get() + nr);
+    fhip::IndexArgs a{};
+    a.stream = in.stream; a.stream_bytes = in.stream_bytes;
+    a.range_first = reinterpret_cast<const long long *>(in.range_first); a.nranges = in.nranges;
+    a.channels = c->p.channels; a.bps = c->p.bits_per_sample; a.sample_rate = c->p.sample_rate;
+    a.max_block_size = in.max_block_size;
+    a.frame_cap = in.frame_cap;
+    a.frame_bytes = out.frame_bytes; a.range_frames = out.range_frames;
+    a.range_consumed = reinterpret_cast<long long *>(out.range_consumed); a.range_variable = out.range_variable;
+    a.nwg = nwg;
+    a.wg_cnt = c->d_iwg; a.wg_key = reinterpret_cast<uint32_t *>(c->d_iwg.get() + nwg); a.ncand = c->d_iwg.get() + 2 * (size_t)nwg + 1;
+    a.table_cap = (long long)cap;
+    a.cand_pos = c->d_icand; a.cand_meta = reinterpret_cast<uint32_t *>(c->d_icand.get() + cap); a.cand_end = c->d_icand.get() + 2 * cap;
+    a.cand_numkey = c->d_inumkey;
+    a.rng_off = c->d_irng; a.rng_cf = rng32; a.rng_cnt = rng32 + nr; a.rng_vbs = rng32 + 2 * nr;
+    for (int step = 0; step < fhip::INDEX_STEPS; step++) {
+        Prof pr(c, kProfIndex + step, c->profiling);
+        HIP_TRY(c, fhip::launch_index_step(c->stream, a, step));
+    }
+    return FHIP_OK;
+}
+}  // namespace
+
+int fhip_index_frames_dev(fhip_ctx *c, const fhip_index_in *in, const fhip_index_out *out)
+{
+    int rc = index_check(c, in, out);
+    if (rc != FHIP_OK) return rc;
+    LaunchScope ls(c);
+    return run_index(c, *in, *out);
+}
+
+int fhip_index_frames(fhip_ctx *c, const fhip_index_in *in, const fhip_index_out *out)
+{
+    int rc = index_check(c, in, out);
+    if (rc != FHIP_OK) return rc;
+    const size_t nr = (size_t)in->nranges, sb = (size_t)in->stream_bytes;
+    if (in->range_first[0] != 0) return fail(c, FHIP_E_INVALID, "range_first[0] must be 0");
+    for (size_t r = 0; r < nr; r++)
+        if (in->range_first[r + 1] < in->range_first[r]) return fail(c, FHIP_E_INVALID, "range_first must not decrease");
+    if (in->range_first[nr] != in->stream_bytes) return fail(c, FHIP_E_INVALID, "range_first must end at stream_bytes");
+    LaunchScope ls(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    // no range holds more frames than candidates: the device never needs more room than the table has
+    const size_t tcap = index_table_cap(in->stream_bytes, in->nranges);
+    const size_t fcap = (size_t)in->frame_cap < tcap ? (size_t)in->frame_cap : tcap;
+    // one block: range_first [nr + 1], range_consumed [nr] (8 bytes each), then range_frames, range_variable [nr] and
+    // frame_bytes [fcap] (4 bytes each).  The sizes come back with the rest as far as `first` entries go -- one wait
+    // for any batch the decoder takes -- and the remainder, where there is one, in a second copy.
+    const size_t words = 2 * nr + 1 + (2 * nr + fcap + 1) / 2;
+    const size_t first = fcap < 65536 ? fcap : 65536;
+    HIP_TRY(c, c->d_istream.reserve(sb));
+    HIP_TRY(c, c->d_iio.reserve(words));
+    c->h_iio.resize(2 * nr + 1 + (2 * nr + first + 1) / 2);
+    if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_istream, in->stream, sb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_iio, in->range_first, (nr + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    int32_t *d32 = reinterpret_cast<int32_t *>(c->d_iio.get() + 2 * nr + 1);
+    fhip_index_in din = *in;
+    din.stream = c->d_istream; din.range_first = reinterpret_cast<const int64_t *>(c->d_iio.get());
+    din.frame_cap = (int32_t)fcap;
+    fhip_index_out dout{d32 + 2 * nr, d32, reinterpret_cast<int64_t *>(c->d_iio.get() + nr + 1), d32 + nr};
+    rc = run_index(c, din, dout);
+    if (rc != FHIP_OK) return rc;
+    long long *h = c->h_iio.data();
+    HIP_TRY(c, hipMemcpyAsync(h + nr + 1, c->d_iio.get() + nr + 1, nr * sizeof(int64_t) + (2 * nr + first) * sizeof(int32_t),
+                              hipMemcpyDeviceToHost, c->stream));
+    rc = fhip_sync(c);
+    if (rc != FHIP_OK) return rc;
+    const int32_t *h32 = reinterpret_cast<const int32_t *>(h + 2 * nr + 1);
+    size_t total = 0;
+    for (size_t r = 0; r < nr; r++) {
+        out->range_frames[r] = h32[r];
+        out->range_consumed[r] = h[nr + 1 + r];
+        out->range_variable[r] = h32[nr + r];
+        if (h32[r] > 0) total += (size_t)h32[r];
+    }
+    if (total > fcap) total = fcap;
+    const size_t got = total < first ? total : first;
+    if (got) memcpy(out->frame_bytes, h32 + 2 * nr, got * sizeof(int32_t));
+    if (total > got) {
+        HIP_TRY(c, hipMemcpyAsync(out->frame_bytes + got, d32 + 2 * nr + got, (total - got) * sizeof(int32_t),
+                                  hipMemcpyDeviceToHost, c->stream));
+        rc = fhip_sync(c);
+        if (rc != FHIP_OK) return rc;
+    }
+    return FHIP_OK;
+}
+
+void fhip_index_geometry(int *lane_bytes, int *wg_bytes, int *end_lane_bytes, int *xinv8)
+{
+    int g[4];
+    fhip::index_geometry(&g[0], &g[1], &g[2], &g[3]);
+    if (lane_bytes) *lane_bytes = g[0];
+    if (wg_bytes) *wg_bytes = g[1];
+    if (end_lane_bytes) *end_lane_bytes = g[2];
+    if (xinv8) *xinv8 = g[3];
 }
 
 int fhip_prepare_frames(fhip_ctx *c, const int32_t *pcm, int nframes, int n,

@@ -362,4 +362,29 @@ hipError_t launch_md5_ranges(hipStream_t st, fhip_md5_state *states, int nstream
                              const long long *range_start, const long long *range_samples);
 hipError_t launch_md5_final(hipStream_t st, const fhip_md5_state *states, int nstreams, uint8_t *digests);
 
+// K8 (k8_index.hip): frame discovery, the CPU indexer's answer for nranges streams at once.  INDEX_STEPS launches on st,
+// one per launch_index_step so that the caller can time each: the candidate pass (count), the scan over its
+// workgroups, the candidate pass again (scatter), the walk (a wave per range), the ranges' places, the sizes.
+struct IndexArgs {
+    const uint8_t *stream; long long stream_bytes;
+    const long long *range_first; int nranges;   // [nranges + 1]; read clamped into the stream
+    int channels, bps, sample_rate, max_block_size;      // what the header codes are held against (max_block_size 0: not checked)
+    long long frame_cap;
+    int32_t *frame_bytes, *range_frames; long long *range_consumed; int32_t *range_variable;
+    // working memory (the handle's)
+    int nwg;                                     // index_nwg(stream_bytes): the candidate pass's workgroups
+    int32_t *wg_cnt;                             // [nwg] candidates per workgroup, then their exclusive prefix
+    uint32_t *wg_key;                            // [nwg + 1] key terms per workgroup, then the key at each one's first byte
+    int32_t *ncand;                              // [1] candidates found (may exceed table_cap: the table keeps the first)
+    long long table_cap;                         // entries of the four candidate arrays
+    int32_t *cand_pos; uint32_t *cand_meta; unsigned long long *cand_numkey;
+    int32_t *cand_end;                           // the walk's frame ends, from the range's first table index on
+    int32_t *rng_cf, *rng_cnt, *rng_vbs; long long *rng_off;     // [nranges] each
+};
+constexpr int INDEX_STEPS = 6;
+const char *index_step_name(int step);
+int index_nwg(long long stream_bytes);
+void index_geometry(int *lane_bytes, int *wg_bytes, int *end_lane_bytes, int *xinv8);
+hipError_t launch_index_step(hipStream_t st, const IndexArgs &a, int step);
+
 }  // namespace fhip

@@ -20,7 +20,8 @@
  *   flake_amd_cli --decode in.flac out.wav
  *
  * --decode turns a FLAC file back into canonical PCM WAV on the GPU (flake_amd_decode_*): it checks the "fLaC" marker,
- * reads STREAMINFO, skips the other metadata blocks, finds the frames on the CPU (flake_amd_index_frames), decodes
+ * reads STREAMINFO, skips the other metadata blocks, finds the frames on the device (flake_amd_decode_index; on the CPU,
+ * flake_amd_index_frames, with FLAKE_AMD_INDEX_HOST=1 or for a file of 2 GiB and more), decodes
  * them in batches and compares the MD5 of what it wrote with STREAMINFO's unless that is all zero.  A frame that does
  * not decode, or an MD5 mismatch, ends in a non-zero exit status with the frame named on stderr.
  *
@@ -288,6 +289,13 @@ static void wav_header(uint8_t h[44], int channels, int rate, int bps, uint32_t 
     memcpy(h + 36, "data", 4); wr32(h + 40, data);
 }
 
+/* FLAKE_AMD_INDEX_HOST=1: frame discovery stays on the CPU (flake_amd_index_frames) */
+static int index_on_host(void)
+{
+    const char *e = getenv("FLAKE_AMD_INDEX_HOST");
+    return e && *e && strcmp(e, "0");
+}
+
 static int run_decode(const char *in, const char *out)
 {
     FILE *fi = fopen(in, "rb");
@@ -332,9 +340,29 @@ static int run_decode(const char *in, const char *out)
     fwrite(wh, 1, 44, fo);
     unsigned long long total = 0, nframes_done = 0;
     int rc = 0;
+    /* the frames of the whole file, found on the device in one call (K8): the same frames as the CPU finds piece by
+     * piece below, since a piece's last frame ends at the header the next piece begins with.  FLAKE_AMD_INDEX_HOST=1,
+     * or a file the device indexer refuses (2 GiB and more), keeps the CPU */
+    int *all = NULL;
+    long long all_n = 0, all_next = 0;
+    int on_device = 0;
+    if (!index_on_host() && pos < len && len - pos < ((size_t)1 << 31)) {
+        const int all_cap = (int)((len - pos) / 8 + 1);
+        size_t all_used = 0;
+        all = (int *)malloc(sizeof(int) * (size_t)all_cap);
+        all_n = all ? flake_amd_decode_index(d, file + pos, len - pos, all, all_cap, &all_used) : -2;
+        on_device = all_n != -2;
+    }
     while (pos < len) {
         size_t used = 0;
-        const long long nf = flake_amd_index_frames(&si, file + pos, len - pos, sizes, batch, &used);
+        long long nf;
+        if (on_device) {
+            nf = all_n < 0 ? -1 : (all_n - all_next < batch ? all_n - all_next : batch);
+            for (long long k = 0; k < nf; k++) { sizes[k] = all[all_next + k]; used += (size_t)sizes[k]; }
+            if (nf > 0) all_next += nf;
+        } else {
+            nf = flake_amd_index_frames(&si, file + pos, len - pos, sizes, batch, &used);
+        }
         if (nf <= 0) {
             fprintf(stderr, "%s: frame %llu (at byte %llu, after %llu samples): %s\n", in, nframes_done,
                     (unsigned long long)pos, total,
@@ -377,7 +405,7 @@ static int run_decode(const char *in, const char *out)
     }
     if (!rc) fprintf(stderr, "%llu sample-frames decoded\n", total);
     flake_amd_decode_close(d);
-    free(file); free(sizes); free(pcm); free(raw);
+    free(file); free(sizes); free(pcm); free(raw); free(all);
     return rc;
 }
 
@@ -387,7 +415,8 @@ typedef struct {
     uint8_t *file;
     size_t len, pos;                 /* the file, and where its next frame starts */
     FlakeAmdStreaminfo si;
-    int *sizes;                      /* every frame's size (flake_amd_index_frames over the whole file) */
+    int *sizes;                      /* every frame's size (the indexer's, over the whole file) */
+    int own_sizes;                   /* ... in a block of the file's own (the CPU indexer's), not in the group's */
     long long nframes, next;         /* ... how many, and the next one to hand over */
     FILE *fo;
     unsigned long long total;
@@ -401,7 +430,7 @@ static void dset_free(dset_file *fs, int n)
     for (int i = 0; i < n; i++) {
         if (fs[i].fo) fclose(fs[i].fo);
         free(fs[i].file);
-        free(fs[i].sizes);
+        if (fs[i].own_sizes) free(fs[i].sizes);
     }
     free(fs);
 }
@@ -477,15 +506,88 @@ static int run_decode_set(const char *outdir, char **inputs, int n)
     FlakeAmdStreaminfo like = fs[ref].si;
     like.max_block_size = maxn;
     const int nch = (int)like.channels, bps = (int)like.bits_per_sample, wbytes = (bps + 7) / 8, narrow = bps == 16;
-    /* the frames of every file, found on the CPU; a file whose frames end early is named now and decoded up to there */
+    /* (everything the loops below need, so that every way out frees it) */
+    int *sor = NULL, *fof = NULL, *csz = NULL, *group_sizes = NULL;
+    long long *rs = NULL, *ro = NULL;
+    void *pcm = NULL;
+    uint8_t *raw = NULL, *bytes = NULL;
+    size_t bytes_cap = 0;
+    FlakeAmdDecodeSet *g = flake_amd_decode_set_open(&like, n, 0);
+    if (!g) { fprintf(stderr, "decode set init failed: %s\n", flake_amd_decode_set_last_error(NULL)); rc = 1; goto out; }
+    /* the frames of every file, found on the device (K8): all files in one call, as ranges of one buffer, while they
+     * stay below 2 GiB together.  FLAKE_AMD_INDEX_HOST=1, a device that cannot answer, or what is left over, goes to
+     * the CPU file by file */
+    size_t *used_of = (size_t *)calloc((size_t)n, sizeof(size_t));
+    char *indexed = (char *)calloc((size_t)n, 1);
+    if (!used_of || !indexed) { fprintf(stderr, "out of memory\n"); free(used_of); free(indexed); rc = 1; goto out; }
+    char *tried = (char *)calloc((size_t)n, 1);
+    if (!tried) { fprintf(stderr, "out of memory\n"); free(used_of); free(indexed); rc = 1; goto out; }
+    long long group_at = 0, group_cap = 0;
+    for (int i = 0; i < n && !index_on_host(); i++) group_cap += fs[i].skip ? 0 : (long long)((fs[i].len - fs[i].pos) / 8 + 2);
+    if (group_cap) group_sizes = (int *)malloc(sizeof(int) * (size_t)group_cap);
+    /* one call per max_block_size among the files (a call holds one format): as a rule, one call */
+    for (int lead = 0; lead < n && group_sizes; lead++) {
+        if (fs[lead].skip || tried[lead]) continue;
+        const unsigned mbs = fs[lead].si.max_block_size;
+        size_t tot = 0;
+        int members = 0;
+        for (int i = lead; i < n; i++) {
+            const size_t left = fs[i].len - fs[i].pos;
+            if (fs[i].skip || tried[i] || fs[i].si.max_block_size != mbs || tot + left >= ((size_t)1 << 31)) continue;
+            tried[i] = 2;
+            tot += left;
+            members++;
+        }
+        size_t *first = (size_t *)malloc(sizeof(size_t) * ((size_t)members + 1));
+        long long *frames = (long long *)malloc(sizeof(long long) * ((size_t)members + 1));
+        size_t *cons = (size_t *)malloc(sizeof(size_t) * ((size_t)members + 1));
+        if (tot > bytes_cap) {
+            free(bytes);
+            bytes = (uint8_t *)malloc(tot);
+            bytes_cap = bytes ? tot : 0;
+        }
+        int ok = members > 0 && first && frames && cons && (bytes || !tot);
+        if (ok) {
+            size_t at = 0;
+            int r = 0;
+            for (int i = lead; i < n; i++) {
+                if (tried[i] != 2) continue;
+                first[r++] = at;
+                if (fs[i].len > fs[i].pos) memcpy(bytes + at, fs[i].file + fs[i].pos, fs[i].len - fs[i].pos);
+                at += fs[i].len - fs[i].pos;
+            }
+            first[r] = at;
+            ok = flake_amd_decode_set_index(g, mbs, bytes, first, members, group_sizes + group_at, (int)(tot / 8) + members + 1,
+                                            frames, cons) == 0;
+        }
+        int r = 0;
+        for (int i = lead; i < n; i++) {
+            if (tried[i] != 2) continue;
+            tried[i] = 1;
+            if (ok) {
+                indexed[i] = 1;
+                fs[i].sizes = group_sizes + group_at;
+                fs[i].nframes = frames[r];
+                used_of[i] = cons[r];
+                if (frames[r] > 0) group_at += frames[r];
+            }
+            r++;
+        }
+        free(first); free(frames); free(cons);
+    }
+    free(tried);
+    /* a file whose frames end early is named now and decoded up to there */
     for (int i = 0; i < n; i++) {
         dset_file *f = &fs[i];
         if (f->skip) continue;
         const size_t left = f->len - f->pos;
-        const int cap = (int)(left / 8 + 1);
-        f->sizes = (int *)malloc(sizeof(int) * (size_t)cap);
-        size_t used = 0;
-        f->nframes = f->sizes ? flake_amd_index_frames(&f->si, f->file + f->pos, left, f->sizes, cap, &used) : -1;
+        size_t used = used_of[i];
+        if (!indexed[i]) {
+            const int cap = (int)(left / 8 + 1);
+            f->sizes = (int *)malloc(sizeof(int) * (size_t)cap);
+            f->own_sizes = 1;
+            f->nframes = f->sizes ? flake_amd_index_frames(&f->si, f->file + f->pos, left, f->sizes, cap, &used) : -1;
+        }
         if (f->nframes < 0 || used != left) {
             fprintf(stderr, "%s: frame %lld (at byte %llu): %s\n", f->path, f->nframes < 0 ? 0ll : f->nframes,
                     (unsigned long long)(f->pos + used), f->nframes < 0 ? "not a frame header of this stream" : "the frame is cut or its CRC-16 fails");
@@ -494,19 +596,12 @@ static int run_decode_set(const char *outdir, char **inputs, int n)
             if (f->nframes < 0) f->nframes = 0;
         }
         f->fo = fopen(f->name, "wb");
-        if (!f->fo) { perror(f->name); dset_free(fs, n); return 1; }
+        if (!f->fo) { perror(f->name); free(used_of); free(indexed); rc = 1; goto out; }
         uint8_t wh[44];
         memset(wh, 0, sizeof wh);
         fwrite(wh, 1, 44, f->fo);
     }
-    /* (everything the loop below needs, so that every way out frees it) */
-    int *sor = NULL, *fof = NULL, *csz = NULL;
-    long long *rs = NULL, *ro = NULL;
-    void *pcm = NULL;
-    uint8_t *raw = NULL, *bytes = NULL;
-    size_t bytes_cap = 0;
-    FlakeAmdDecodeSet *g = flake_amd_decode_set_open(&like, n, 0);
-    if (!g) { fprintf(stderr, "decode set init failed: %s\n", flake_amd_decode_set_last_error(NULL)); rc = 1; goto out; }
+    free(used_of); free(indexed);
     /* round-robin: a call takes up to `per` frames of every file that has some left */
     int per = (int)((4u << 20) / maxn / (unsigned)n);
     if (per > 64) per = 64;
@@ -601,7 +696,7 @@ static int run_decode_set(const char *outdir, char **inputs, int n)
     fprintf(stderr, "%lld device batches\n", flake_amd_decode_set_device_batches(g));
 out:
     if (g) flake_amd_decode_set_close(g);
-    free(sor); free(fof); free(csz); free(rs); free(ro); free(pcm); free(raw); free(bytes);
+    free(sor); free(fof); free(csz); free(rs); free(ro); free(pcm); free(raw); free(bytes); free(group_sizes);
     dset_free(fs, n);
     return rc;
 }

@@ -4,7 +4,8 @@
  * hands batches of indexed frames to fhip_decode_frames (K7), carries the expected number from call to call and
  * hashes what it returns, so that the caller can hold it against STREAMINFO's MD5.
  *
- * flake_amd_read_streaminfo and flake_amd_index_frames make no call into the HIP layer.
+ * flake_amd_read_streaminfo and flake_amd_index_frames make no call into the HIP layer.  flake_amd_decode_index is the
+ * same discovery on the device (fhip_index_frames, K8), held to flake_amd_index_frames' answer.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -286,6 +287,61 @@ FLAKE_AMD_API long long flake_amd_decode_frames(FlakeAmdDecoder *d, const unsign
         off += cb;
     }
     return (long long)done;
+}
+
+/* ---- frame discovery on the device ------------------------------------- */
+
+int fa_index_ranges(struct fhip_ctx *hip, unsigned max_block_size, const unsigned char *stream, const size_t *range_first,
+                    int nranges, int *frame_sizes, int cap, long long *range_frames, size_t *range_consumed, char *err,
+                    size_t err_len)
+{
+    if (!hip || !range_first || nranges < 1 || cap < 0 || (!frame_sizes && cap) || !range_frames || !range_consumed ||
+        range_first[0] != 0 || (!stream && range_first[nranges]))
+        return -1;
+    for (int r = 0; r < nranges; r++)
+        if (range_first[r + 1] < range_first[r]) return -1;
+    if (range_first[nranges] >= ((size_t)1 << 31)) {
+        snprintf(err, err_len, "the device indexes less than 2 GiB per call");
+        return -2;
+    }
+    const size_t nr = (size_t)nranges;
+    /* one block: range_first and consumed as int64, then frames and variable as int32 */
+    int64_t *w = (int64_t *)malloc((2 * nr + 1) * sizeof(int64_t) + 2 * nr * sizeof(int32_t));
+    if (!w) { snprintf(err, err_len, "out of memory"); return -2; }
+    int64_t *first = w, *cons = w + nr + 1;
+    int32_t *frames = (int32_t *)(w + 2 * nr + 1), *variable = frames + nr;
+    for (size_t r = 0; r <= nr; r++) first[r] = (int64_t)range_first[r];
+    fhip_index_in in = {stream, first[nr], first, nranges, (int32_t)(max_block_size > 65535u ? 65535u : max_block_size), cap};   /* (no block is larger) */
+    fhip_index_out out = {frame_sizes, frames, cons, variable};
+    const int rc = fhip_index_frames(hip, &in, &out);
+    if (rc != FHIP_OK) {
+        snprintf(err, err_len, "fhip_index_frames: %s", fhip_last_error(hip));
+        free(w);
+        return -2;
+    }
+    for (size_t r = 0; r < nr; r++) {
+        range_frames[r] = frames[r];
+        range_consumed[r] = (size_t)cons[r];
+    }
+    free(w);
+    return 0;
+}
+
+FLAKE_AMD_API long long flake_amd_decode_index(FlakeAmdDecoder *d, const unsigned char *stream, size_t bytes,
+                                               int *frame_sizes, int cap, size_t *consumed)
+{
+    if (consumed) *consumed = 0;
+    if (!d) return -1;
+    d->err[0] = 0;
+    if ((!stream && bytes) || !frame_sizes || cap < 0) return -1;      /* flake_amd_index_frames' own refusals */
+    const size_t first[2] = {0, bytes};
+    long long frames = 0;
+    size_t cons = 0;
+    const int rc = fa_index_ranges(d->hip, d->si.max_block_size, stream, first, 1, frame_sizes, cap, &frames, &cons, d->err,
+                                   sizeof d->err);
+    if (rc) return rc;
+    if (consumed) *consumed = cons;
+    return frames;
 }
 
 FLAKE_AMD_API int flake_amd_decode_md5(FlakeAmdDecoder *d, unsigned char md5[16])

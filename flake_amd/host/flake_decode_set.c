@@ -310,6 +310,18 @@ FLAKE_AMD_API long long flake_amd_decode_set_device_batches(const FlakeAmdDecode
     return g ? g->device_batches : -1;
 }
 
+FLAKE_AMD_API int flake_amd_decode_set_index(FlakeAmdDecodeSet *g, unsigned max_block_size, const unsigned char *stream,
+                                             const size_t *range_first, int nranges, int *frame_sizes, int cap,
+                                             long long *range_frames, size_t *range_consumed)
+{
+    if (!g) return -1;
+    g->err[0] = 0;
+    const int rc = fa_index_ranges(g->hip, max_block_size, stream, range_first, nranges, frame_sizes, cap,
+                                   range_frames, range_consumed, g->err, sizeof g->err);
+    if (rc == -1) snprintf(g->err, sizeof g->err, "bad argument");
+    return rc;
+}
+
 FLAKE_AMD_API const char *flake_amd_decode_set_last_error(const FlakeAmdDecodeSet *g)
 {
     return g ? g->err : g_open_err;

@@ -24,6 +24,13 @@ typedef struct { int n, vbs, len; unsigned long long number; } fa_hdr;
 struct FlakeAmdStreaminfo;
 int fa_parse_header(const struct FlakeAmdStreaminfo *si, const unsigned char *d, size_t avail, fa_hdr *h);
 
+/* K8 for the decoder and the decode set (flake_decode.c): fhip_index_frames over nranges ranges of stream, the answers
+ * in the host layer's types.  0, -1 for a bad argument, -2 where the device could not answer (err says why). */
+struct fhip_ctx;
+int fa_index_ranges(struct fhip_ctx *hip, unsigned max_block_size, const unsigned char *stream, const size_t *range_first,
+                    int nranges, int *frame_sizes, int cap, long long *range_frames, size_t *range_consumed, char *err,
+                    size_t err_len);
+
 /* Which of a chunk's cnt blocks the verifier's frame index (it counts the chunk's frames) lies in: block b holds
  * block_frames[b] frames, one each when the table is null.  -1: none -- an index below 0 or past the chunk's frames;
  * an entry below 1 ends the search (nothing behind a block that was not encoded can be placed). */

@@ -284,6 +284,14 @@ FLAKE_AMD_API FlakeAmdDecoder *flake_amd_decode_open(const FlakeAmdStreaminfo *s
 FLAKE_AMD_API long long flake_amd_decode_frames(FlakeAmdDecoder *d, const unsigned char *stream, size_t bytes,
                                                 const int *frame_sizes, int nframes, void *pcm, int sample_bytes,
                                                 size_t pcm_cap_samples);
+/*
+ * flake_amd_index_frames on the device (fhip_index_frames, include/flakehip.h: K8), on the decoder's handle and against
+ * its STREAMINFO: the same sizes, the same count, the same *consumed and the same -1 for every input, good or corrupt.
+ * It neither reads nor changes the decoder's numbering or hash.  -2 where the device could not answer (a stream of
+ * 2 GiB or more, or a HIP failure: flake_amd_decode_last_error says which); the CPU function still can.
+ */
+FLAKE_AMD_API long long flake_amd_decode_index(FlakeAmdDecoder *d, const unsigned char *stream, size_t bytes,
+                                               int *frame_sizes, int cap, size_t *consumed);
 FLAKE_AMD_API int flake_amd_decode_md5(FlakeAmdDecoder *d, unsigned char md5[16]);
 FLAKE_AMD_API const char *flake_amd_decode_last_error(const FlakeAmdDecoder *d);
 FLAKE_AMD_API void flake_amd_decode_close(FlakeAmdDecoder *d);
@@ -346,6 +354,20 @@ FLAKE_AMD_API int flake_amd_decode_set_run_offsets(const FlakeAmdDecodeSet *g, l
 FLAKE_AMD_API int flake_amd_decode_set_md5(FlakeAmdDecodeSet *g, int stream, unsigned char md5[16]);
 FLAKE_AMD_API int flake_amd_decode_set_failed(const FlakeAmdDecodeSet *g, int stream, long long *frame, int *status);
 FLAKE_AMD_API long long flake_amd_decode_set_device_batches(const FlakeAmdDecodeSet *g);
+/*
+ * Frame discovery for many files in ONE device call (K8) on the set's handle: range r is stream[range_first[r] ..
+ * range_first[r + 1]) (nranges + 1 offsets, from 0, not decreasing, the last one the byte count), one file's frames
+ * from its first header on.  Exactly
+ *   for r in ranges: range_frames[r] = flake_amd_index_frames(si, range r, frame_sizes + frames so far,
+ *                                                             cap - frames so far, &range_consumed[r])
+ * where si is the set's format with the call's max_block_size (the files' STREAMINFO value; 0: not checked) -- a call holds one format, so files whose max_block_size differ go through calls of their own --
+ * with the ranges' sizes back to back in frame_sizes: a range that is refused (-1) takes no room, ranges behind the
+ * one that cap cut get 0.  Returns 0, -1 for a bad argument, -2 where the device could not answer (2 GiB or more in
+ * one call, or a HIP failure: flake_amd_decode_set_last_error says which).  The set's streams are not touched.
+ */
+FLAKE_AMD_API int flake_amd_decode_set_index(FlakeAmdDecodeSet *g, unsigned max_block_size, const unsigned char *stream,
+                                             const size_t *range_first, int nranges, int *frame_sizes, int cap,
+                                             long long *range_frames, size_t *range_consumed);
 FLAKE_AMD_API const char *flake_amd_decode_set_last_error(const FlakeAmdDecodeSet *g);
 FLAKE_AMD_API void flake_amd_decode_set_close(FlakeAmdDecodeSet *g);
 

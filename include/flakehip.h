@@ -690,6 +690,63 @@ FHIP_API int fhip_decode_frames_segments_dev(fhip_ctx *ctx, const fhip_decode_in
 FHIP_API int fhip_decode_frames_segments(fhip_ctx *ctx, const fhip_decode_in *in, const fhip_decode_segments *segs,
                                          const fhip_decode_out *out, const fhip_decode_md5 *md5);
 
+/* ---- frame discovery (K8) --------------------------------------------- */
+
+/*
+ * Where do the frames of a stream begin?  The answer is the CPU indexer's (flake_amd_index_frames of the host layer),
+ * exactly, for every input, good or corrupt.  For one stream s[0 .. bytes):
+ *   - position p is a CANDIDATE iff a frame header stands there whose sync, reserved bits, rate, channel and
+ *     bits-per-sample codes agree with the handle's format, whose block size is at most max_block_size (where that is
+ *     not 0) and 65535, whose UTF-8 number is well formed and whose CRC-8 holds, all inside bytes - p;
+ *   - position 0 must be a candidate (else the answer is -1), and its blocking-strategy bit is the stream's;
+ *   - from a boundary a (header length len, block size n, number num) the frame ends at the smallest q >= a + len + 2
+ *     where the CRC-16 of s[a .. q - 2) is what lies at q - 2 and either q == bytes or q is a candidate with the
+ *     stream's strategy bit and the number num + (variable ? n : 1); the next boundary is q;
+ *   - the walk stops at the capacity, at q == bytes, or where no such q exists (that frame is not consumed).
+ * No limit on a frame's length.  Many streams per call: range r is the bytes range_first[r] .. range_first[r + 1] of
+ * `stream`, one stream's frames from its first header on, and the call means exactly
+ *   for r in ranges: index range r with capacity frame_cap - (frames found so far)
+ * so a range that does not fit is cut as the capacity cuts it, the ranges behind it get 0 frames and 0 consumed, a
+ * range that is refused (-1) takes no room and an empty range gives 0 and 0.  Entries of frame_bytes behind the last
+ * frame are not written.  All ranges share the handle's channels, bits_per_sample and sample_rate and the call's
+ * max_block_size; everything else of fhip_params is unused.
+ */
+typedef struct fhip_index_in {
+    const uint8_t *stream;        /* the ranges' bytes */
+    int64_t        stream_bytes;  /* < 2^31 */
+    const int64_t *range_first;   /* [nranges + 1] CSR byte offsets: range r is one stream's frames from its first header on */
+    int32_t        nranges;       /* >= 1 */
+    int32_t        max_block_size;/* STREAMINFO's; 0: not checked (channels, rate, bits per sample are the handle's) */
+    int32_t        frame_cap;     /* room in frame_bytes */
+} fhip_index_in;
+
+typedef struct fhip_index_out {
+    int32_t *frame_bytes;         /* [frame_cap] the sizes of all ranges' frames, back to back in range order */
+    int32_t *range_frames;        /* [nranges] frames found; -1: the range does not begin with a header of this format */
+    int64_t *range_consumed;      /* [nranges] bytes those frames cover */
+    int32_t *range_variable;      /* [nranges] the strategy bit of the range's first header (0 where there is none) */
+} fhip_index_out;
+
+/* All pointers DEVICE pointers; asynchronous on the handle's stream, no host synchronisation.  Starts a launch list
+ * ("k_index_scan<false>", "k_index_wgscan", "k_index_scan<true>", "k_index_walk", "k_index_ranges", "k_index_emit";
+ * the two scans are absent for an empty stream) and is timed per launch under fhip_set_profiling as "k_index_count",
+ * "k_index_wgscan", "k_index_scatter", "k_index_walk", "k_index_ranges", "k_index_emit".  range_first is read clamped:
+ * every offset into [0, stream_bytes], every range's end to no less than its start, so every stream read stays inside
+ * the stream and every header read inside its own range whatever the table holds; every table read and every output
+ * stays inside its array.  The working memory (a candidate table of stream_bytes / 5 + nranges + 1 entries of 20
+ * bytes -- two headers lie at least five bytes apart, so no candidate is ever dropped -- and a few words per 4 KiB of
+ * stream and per range) is the handle's, allocated at first use and grow-only.  FHIP_E_INVALID with nothing queued and
+ * an empty launch list for null pointers, nranges < 1, negative counts or stream_bytes >= 2^31. */
+FHIP_API int fhip_index_frames_dev(fhip_ctx *ctx, const fhip_index_in *in, const fhip_index_out *out);
+/* The same with HOST pointers: uploads, runs, downloads, and waits once (a second time only where the call finds more
+ * than 65536 frames: the sizes behind those come in a copy of their own).  Also FHIP_E_INVALID when range_first does
+ * not start at 0, decreases or does not end at stream_bytes. */
+FHIP_API int fhip_index_frames(fhip_ctx *ctx, const fhip_index_in *in, const fhip_index_out *out);
+/* K8's constants, for tests that place frame starts on every residue of a chunk: the bytes per lane and per workgroup
+ * of the candidate pass (which takes the CRC-16 prefixes as well), the bytes per lane of the pass that takes the key
+ * at a range's end, and x^(-8) modulo the CRC-16 polynomial.  A pure host function; any pointer may be NULL. */
+FHIP_API void fhip_index_geometry(int *lane_bytes, int *wg_bytes, int *end_lane_bytes, int *xinv8);
+
 /* ---- MD5 of many streams (K6) ---------------------------------------- */
 
 /*
@@ -774,7 +831,7 @@ FHIP_API int fhip_get_kernel_times(fhip_ctx *ctx, const char **names, double *ms
  * one or two workgroups per tile), "tail" (K2 runs inside K1), "fused" (K1 applies K0's decisions),
  * "narrow" (16-bit sample rows).  The calls that start a new list are the encode entries
  * (fhip_encode_subframes*, fhip_frames_packed_begin / fhip_encode_frames_packed, the VBS entries)
- * and fhip_prepare_ahead, the fhip_md5_* entries, fhip_decode_frames(_dev) and fhip_decode_frames_segments(_dev).  A host-side record: it adds no device work.  (One exception:
+ * and fhip_prepare_ahead, the fhip_md5_* entries, fhip_decode_frames(_dev), fhip_decode_frames_segments(_dev) and fhip_index_frames(_dev).  A host-side record: it adds no device work.  (One exception:
  * "k_md5_streams<int16_t,2> fast" / "... general" name a choice that is made on the device when the block shape
  * allows the fast path; asking for the list then waits for that launch.)  names[0 .. cap) receive
  * strings owned by the handle, valid until its next such call; returns the number of launches. */
