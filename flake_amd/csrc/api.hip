@@ -2801,8 +2801,7 @@ int run_index(fhip_ctx *c, const fhip_index_in &in, const fhip_index_out &out)
     fhip::IndexArgs a{};
     a.stream = in.stream; a.stream_bytes = in.stream_bytes;
     a.range_first = reinterpret_cast<const long long *>(in.range_first); a.nranges = in.nranges;
-    a.channels = c->p.channels; a.bps = c->p.bits_per_sample; a.sample_rate = c->p.sample_rate;
-    a.max_block_size = in.max_block_size;
+    a.fmt = flac_format{c->p.channels, c->p.bits_per_sample, c->p.sample_rate, in.max_block_size};
     a.frame_cap = in.frame_cap;
     a.frame_bytes = out.frame_bytes; a.range_frames = out.range_frames;
     a.range_consumed = reinterpret_cast<long long *>(out.range_consumed); a.range_variable = out.range_variable;

@@ -1,12 +1,14 @@
-// flac_parse.h -- reading a FLAC frame on the device: what K5 (k5_verify.hip, the verifier) and K7
-// (k7_decode.hip, the decoder) share.  A clamped MSB-first bit reader, the discrepancy key, CRC-8 / CRC-16
-// (CRC-16 also as GF(2) products, for the chunk-per-lane form), the frame-header parser, the subframe-header
-// parser and the workgroup scan both header passes use.  Everything is internal to the including file.
+// flac_parse.h -- reading a FLAC frame on the device.  For K5 (k5_verify.hip, the verifier) and K7 (k7_decode.hip, the
+// decoder): a clamped MSB-first bit reader, the discrepancy key, the frame-header parser that says where and why a
+// header fails (its tables and its CRC-8 step are flac_header.h's) and the subframe-header parser.  For those two and
+// K8 (k8_index.hip, frame discovery): CRC-16 a byte at a time and as GF(2) products (a chunk per lane, moved to its
+// place) and the workgroup's exclusive scan.  Everything is internal to the including file.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "flac_header.h"
 #include "kernels.h"
 
 namespace fhip {
@@ -40,45 +42,6 @@ struct Bits {
     }
 };
 
-__device__ __forceinline__ int sample_rate_code_ok(int code, int rate)
-{
-    switch (code) {
-    case 0: return 1;
-    case 1: return rate == 88200;
-    case 2: return rate == 176400;
-    case 3: return rate == 192000;
-    case 4: return rate == 8000;
-    case 5: return rate == 16000;
-    case 6: return rate == 22050;
-    case 7: return rate == 24000;
-    case 8: return rate == 32000;
-    case 9: return rate == 44100;
-    case 10: return rate == 48000;
-    case 11: return rate == 96000;
-    default: return 0;        // 12..14 carry the rate explicitly (checked there), 15 is invalid
-    }
-}
-
-__device__ __forceinline__ int bps_code_of(int bps)
-{
-    switch (bps) {
-    case 8: return 1;
-    case 12: return 2;
-    case 16: return 4;
-    case 20: return 5;
-    case 24: return 6;
-    case 32: return 7;
-    default: return -1;
-    }
-}
-
-__device__ __forceinline__ uint32_t crc8_byte(uint32_t c, uint32_t b)
-{
-    c ^= b;
-    for (int k = 0; k < 8; k++) c = (c & 0x80u) ? ((c << 1) ^ 0x07u) : (c << 1);
-    return c & 0xFFu;
-}
-
 __device__ __forceinline__ uint32_t crc16_byte(uint32_t c, uint32_t b)
 {
     c ^= b << 8;
@@ -86,15 +49,15 @@ __device__ __forceinline__ uint32_t crc16_byte(uint32_t c, uint32_t b)
     return c & 0xFFFFu;
 }
 
-// a * b mod the CRC-16 polynomial x^16 + x^15 + x^2 + 1 (GF(2)); a, b < 2^16
-__device__ __forceinline__ uint32_t gf16_mul(uint32_t a, uint32_t b)
+// a * b mod the CRC-16 polynomial x^16 + x^15 + x^2 + 1 (GF(2)); a, b < 2^16.  Also for static_asserts.
+__host__ __device__ __forceinline__ constexpr uint32_t gf16_mul(uint32_t a, uint32_t b)
 {
     uint32_t r = 0;
     for (int i = 15; i >= 0; i--) {
-        r = (r & 0x8000u) ? (((r << 1) ^ 0x8005u) & 0xFFFFu) : ((r << 1) & 0xFFFFu);
+        r = (r & 0x8000u) ? ((r << 1) ^ 0x8005u) : (r << 1);
         if ((b >> i) & 1u) r ^= a;
     }
-    return r;
+    return r & 0xFFFFu;
 }
 
 // x^(8 m) mod the polynomial: the factor that moves a chunk's CRC past m further bytes
@@ -113,8 +76,9 @@ __device__ uint32_t gf16_xpow8(long long m)
 
 struct HdrOut { int status; long long bit; int n; int hdr_bits; int ch_code; unsigned long long number; };
 
-// a: channels, bps, sample_rate and block_size are what the header codes are held against; allow_vbs is the
-// blocking-strategy bit the frame must carry
+// Not flac_header_ok's yes or no but where the first check fails, and which.  a: channels, bps, sample_rate and
+// block_size are what the header codes are held against (block_size is the largest block, and always a limit);
+// allow_vbs is the blocking-strategy bit the frame must carry.
 __device__ HdrOut parse_header(const VerifyArgs &a, const Bits &bs)
 {
     HdrOut h{FHIP_VERIFY_OK, 0, 0, 0, 0, 0};
@@ -130,12 +94,12 @@ __device__ HdrOut parse_header(const VerifyArgs &a, const Bits &bs)
     const int bs_code = (int)((w >> 12) & 15u), sr_code = (int)((w >> 8) & 15u);
     const int ch_code = (int)((w >> 4) & 15u), bps_code = (int)((w >> 1) & 7u);
     if (bs_code == 0) VFAIL(16, FHIP_VERIFY_HEADER);
-    int n = bs_code == 1 ? 192 : (bs_code <= 5 ? 576 << (bs_code - 2) : (bs_code >= 8 ? 256 << (bs_code - 8) : 0));
+    int n = flac_block_size_of_code(bs_code);
     if (n && n > a.block_size) VFAIL(16, FHIP_VERIFY_NUMBER);
-    if (sr_code == 15 || (sr_code < 12 && !sample_rate_code_ok(sr_code, a.sample_rate))) VFAIL(20, FHIP_VERIFY_HEADER);
+    if (sr_code == 15 || (sr_code < 12 && !flac_rate_code_ok(sr_code, a.sample_rate))) VFAIL(20, FHIP_VERIFY_HEADER);
     if (ch_code > 10 || (ch_code < 8 && ch_code + 1 != a.channels) || (ch_code >= 8 && a.channels != 2))
         VFAIL(24, FHIP_VERIFY_HEADER);
-    if (bps_code != 0 && bps_code != bps_code_of(a.bps)) VFAIL(28, FHIP_VERIFY_HEADER);
+    if (bps_code != 0 && bps_code != flac_bps_code(a.bps)) VFAIL(28, FHIP_VERIFY_HEADER);
     if (w & 1u) VFAIL(31, FHIP_VERIFY_HEADER);
     // UTF-8 style number: 1 .. 7 bytes, up to 36 bits
     long long p = 32;
@@ -177,7 +141,7 @@ __device__ HdrOut parse_header(const VerifyArgs &a, const Bits &bs)
     }
     NEED(p, 8);
     uint32_t c8 = 0;
-    for (long long i = 0; i < (p >> 3); i++) c8 = crc8_byte(c8, bs.byte(i));
+    for (long long i = 0; i < (p >> 3); i++) c8 = flac_crc8_step(c8, bs.byte(i));
     if (bs.rd(p, 8) != c8) VFAIL(p, FHIP_VERIFY_CRC8);
     h.n = n;
     h.hdr_bits = (int)(p + 8);

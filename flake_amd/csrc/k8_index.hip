@@ -1,9 +1,10 @@
 // k8_index.hip -- K8: frame discovery.  Where do the frames of a FLAC stream begin?  The answer is the CPU indexer's
 // (flake_amd_index_frames, host/flake_decode.c), exactly, for every input, good or corrupt.
 //
-// A position is a CANDIDATE when a header that agrees with STREAMINFO and its own CRC-8 stands there (index_header
-// below mirrors the CPU's fa_parse_header line by line).  A frame [a, q) is closed by a CRC-16 over [a, q - 2) that
-// equals the two bytes at q - 2; this CRC has zero init and no final xor, so that is crc(s[a .. q)) == 0.  With
+// A position is a CANDIDATE when a header that agrees with STREAMINFO and its own CRC-8 stands there: flac_header_ok
+// (flac_header.h), the one function the CPU indexer compiles too.  A frame [a, q) is closed by a CRC-16 over
+// [a, q - 2) that equals the two bytes at q - 2; this CRC has zero init and no final xor, so that is
+// crc(s[a .. q)) == 0.  With
 // P(p) = crc(s[0 .. p)) linearity gives P(q) = P(a) x^(8 (q - a)) + crc(s[a .. q)) in GF(2)[x] modulo the polynomial,
 // and x is invertible there (the constant term is 1), so with key(p) = P(p) x^(-8 p) the condition is
 // key(q) == key(a): two 16-bit values computed once per position.  The keys are an XOR prefix sum of the terms
@@ -30,6 +31,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "flac_parse.h"            // CRC-16 and its GF(2) products, the workgroup scan
 
 namespace fhip {
 namespace {
@@ -43,16 +45,7 @@ constexpr int IDX_XORDER = 32767;                       // the order of x
 
 static_assert(IDX_END_BYTES * 64 == IDX_WG_BYTES, "a wave covers one scan workgroup's bytes");
 
-constexpr uint32_t gf16_mul_c(uint32_t a, uint32_t b)
-{
-    uint32_t r = 0;
-    for (int i = 15; i >= 0; i--) {
-        r = (r & 0x8000u) ? (((r << 1) ^ 0x8005u) & 0xFFFFu) : ((r << 1) & 0xFFFFu);
-        if ((b >> i) & 1u) r ^= a;
-    }
-    return r;
-}
-static_assert(gf16_mul_c(IDX_XINV8, 0x100u) == 1u, "IDX_XINV8 is the inverse of x^8");
+static_assert(gf16_mul(IDX_XINV8, 0x100u) == 1u, "IDX_XINV8 is the inverse of x^8");
 
 // r / x: the polynomial has constant term 1, so an odd r becomes even by adding it
 constexpr uint32_t gf16_divx(uint32_t r) { return (r & 1u) ? ((r ^ 0x18005u) >> 1) : (r >> 1); }
@@ -73,33 +66,6 @@ constexpr XinvTable kXinvHost{};
 static_assert(kXinvHost.v[1] == IDX_XINV8, "the table's step is x^(-8)");
 __device__ const XinvTable c_xinv{};
 
-__device__ __forceinline__ uint32_t gf16_mul_d(uint32_t a, uint32_t b)
-{
-    uint32_t r = 0;
-#pragma unroll
-    for (int i = 15; i >= 0; i--) {
-        r = (r & 0x8000u) ? ((r << 1) ^ 0x8005u) : (r << 1);
-        if ((b >> i) & 1u) r ^= a;
-    }
-    return r & 0xFFFFu;
-}
-
-__device__ __forceinline__ uint32_t crc16_step(uint32_t c, uint32_t b)
-{
-    c ^= b << 8;
-#pragma unroll
-    for (int k = 0; k < 8; k++) c = (c & 0x8000u) ? ((c << 1) ^ 0x8005u) : (c << 1);
-    return c & 0xFFFFu;
-}
-
-__device__ __forceinline__ uint32_t crc8_step(uint32_t c, uint32_t b)
-{
-    c ^= b;
-#pragma unroll
-    for (int k = 0; k < 8; k++) c = (c & 0x80u) ? ((c << 1) ^ 0x07u) : (c << 1);
-    return c & 0xFFu;
-}
-
 // x^(-8 base) for a workgroup's first byte
 __device__ uint32_t xinv_pow(long long base)
 {
@@ -107,7 +73,7 @@ __device__ uint32_t xinv_pow(long long base)
     const int e = e8 ? IDX_XORDER - e8 : 0;             // x^(-k) = x^(order - k)
     uint32_t r = 1u;
     for (int bit = 14; bit >= 0; bit--) {
-        r = gf16_mul_d(r, r);
+        r = gf16_mul(r, r);
         if ((e >> bit) & 1) r = (r & 0x8000u) ? (((r << 1) ^ 0x8005u) & 0xFFFFu) : (r << 1);
     }
     return r;
@@ -140,99 +106,8 @@ __device__ bool range_of(const IndexArgs &a, long long p, long long *lo, long lo
     return p >= *lo && p < *hi;
 }
 
-struct IdxHdr { int n, vbs, len; unsigned long long number; };
-
-__device__ __forceinline__ bool rate_code_ok(int code, long long rate)
-{
-    switch (code) {
-    case 0: return true;
-    case 1: return rate == 88200;
-    case 2: return rate == 176400;
-    case 3: return rate == 192000;
-    case 4: return rate == 8000;
-    case 5: return rate == 16000;
-    case 6: return rate == 22050;
-    case 7: return rate == 24000;
-    case 8: return rate == 32000;
-    case 9: return rate == 44100;
-    case 10: return rate == 48000;
-    case 11: return rate == 96000;
-    default: return false;
-    }
-}
-
-__device__ __forceinline__ int bps_code(int bps)
-{
-    switch (bps) {
-    case 8: return 1;
-    case 12: return 2;
-    case 16: return 4;
-    case 20: return 5;
-    case 24: return 6;
-    case 32: return 7;
-    default: return -1;
-    }
-}
-
-// The CPU's fa_parse_header, check for check: the header at d[0 .. avail) is one whose codes agree with the format and
-// whose CRC-8 holds.  Never reads at or past avail.
-__device__ bool index_header(const IndexArgs &a, const uint8_t *d, long long avail, IdxHdr *h)
-{
-    if (avail < 6 || d[0] != 0xFF || (d[1] & 0xFE) != 0xF8) return false;
-    const int bs_code = d[2] >> 4, sr_code = d[2] & 15, ch_code = d[3] >> 4, bpc = (d[3] >> 1) & 7;
-    if (bs_code == 0 || sr_code == 15 || (d[3] & 1)) return false;
-    if (sr_code < 12 && !rate_code_ok(sr_code, a.sample_rate)) return false;
-    if (ch_code > 10 || (ch_code < 8 && ch_code + 1 != a.channels) || (ch_code >= 8 && a.channels != 2)) return false;
-    if (bpc != 0 && bpc != bps_code(a.bps)) return false;
-    long long p = 4;
-    const uint32_t b0 = d[p++];
-    int extra = 0;
-    unsigned long long num = b0;
-    if (b0 >= 0x80u) {
-        int ones = 0;
-        while (ones < 8 && ((b0 << ones) & 0x80u)) ones++;
-        if (ones < 2 || ones > 7) return false;
-        extra = ones - 1;
-        num = ones == 7 ? 0 : (b0 & (0x7Fu >> ones));
-    }
-    if (p + extra > avail) return false;
-    for (int i = 0; i < extra; i++) {
-        const uint32_t c = d[p++];
-        if ((c & 0xC0u) != 0x80u) return false;
-        num = (num << 6) | (c & 0x3Fu);
-    }
-    int n = bs_code == 1 ? 192 : (bs_code <= 5 ? 576 << (bs_code - 2) : (bs_code >= 8 ? 256 << (bs_code - 8) : 0));
-    if (bs_code == 6) {
-        if (p + 1 > avail) return false;
-        n = d[p] + 1;
-        p += 1;
-    } else if (bs_code == 7) {
-        if (p + 2 > avail) return false;
-        n = (d[p] << 8 | d[p + 1]) + 1;
-        p += 2;
-    }
-    if (n > 65535 || (a.max_block_size && n > a.max_block_size)) return false;
-    if (sr_code >= 12) {
-        const int nb = sr_code == 12 ? 1 : 2;
-        if (p + nb > avail) return false;
-        const long long v = nb == 1 ? d[p] : (d[p] << 8 | d[p + 1]);
-        const long long rate = sr_code == 12 ? v * 1000 : (sr_code == 13 ? v : v * 10);
-        if (rate != a.sample_rate) return false;
-        p += nb;
-    }
-    if (p + 1 > avail) return false;
-    uint32_t c8 = 0;
-    for (long long i = 0; i < p; i++) c8 = crc8_step(c8, d[i]);
-    if (c8 != d[p]) return false;
-    h->n = n;
-    h->vbs = d[1] & 1;
-    h->len = (int)p + 1;
-    h->number = num;
-    return true;
-}
-
 // a candidate's packed fields: meta = len | vbs << 5 | n << 6, numkey = number (36 bits) | key << 48
-__device__ __forceinline__ uint32_t pack_meta(const IdxHdr &h) { return (uint32_t)h.len | (uint32_t)h.vbs << 5 | (uint32_t)h.n << 6; }
+__device__ __forceinline__ uint32_t pack_meta(const flac_header &h) { return (uint32_t)h.len | (uint32_t)h.vbs << 5 | (uint32_t)h.n << 6; }
 __device__ __forceinline__ int meta_len(uint32_t m) { return (int)(m & 31u); }
 __device__ __forceinline__ int meta_vbs(uint32_t m) { return (int)((m >> 5) & 1u); }
 __device__ __forceinline__ int meta_n(uint32_t m) { return (int)(m >> 6); }
@@ -291,11 +166,11 @@ __global__ void __launch_bounds__(IDX_T) k_index_scan(IndexArgs a)
 #pragma unroll
     for (int j = 0; j < IDX_LANE_BYTES; j++) {
         if (j < cnt) {
-            crc = crc16_step(crc, IDX_BYTE(j));
+            crc = crc16_byte(crc, IDX_BYTE(j));
             if (IDX_BYTE(j) == 0xFFu && (IDX_BYTE(j + 1) & 0xFEu) == 0xF8u) syncs |= 1u << j;
         }
     }
-    const uint32_t term = cnt ? gf16_mul_d(crc, c_xinv.v[t * IDX_LANE_BYTES + cnt]) : 0u;
+    const uint32_t term = cnt ? gf16_mul(crc, c_xinv.v[t * IDX_LANE_BYTES + cnt]) : 0u;
     // the header predicate on every sync hit (rare: bytes are read where they lie)
     int mine = 0;
     uint32_t good = 0;
@@ -303,8 +178,8 @@ __global__ void __launch_bounds__(IDX_T) k_index_scan(IndexArgs a)
         for (int j = 0; j < IDX_LANE_BYTES; j++) {
             if (!((syncs >> j) & 1u)) continue;
             long long lo, hi;
-            IdxHdr h;
-            if (range_of(a, p0 + j, &lo, &hi) && index_header(a, a.stream + p0 + j, hi - (p0 + j), &h)) {
+            flac_header h;
+            if (range_of(a, p0 + j, &lo, &hi) && flac_header_ok(&a.fmt, a.stream + p0 + j, hi - (p0 + j), &h)) {
                 mine++;
                 good |= 1u << j;
             }
@@ -317,7 +192,7 @@ __global__ void __launch_bounds__(IDX_T) k_index_scan(IndexArgs a)
     if (!SCATTER) {
         if (t == 0) {
             a.wg_cnt[blockIdx.x] = tc;
-            a.wg_key[blockIdx.x] = gf16_mul_d(wpow, tx);
+            a.wg_key[blockIdx.x] = gf16_mul(wpow, tx);
         }
         return;
     }
@@ -329,16 +204,16 @@ __global__ void __launch_bounds__(IDX_T) k_index_scan(IndexArgs a)
     for (int j = 0; j < IDX_LANE_BYTES; j++) {
         if ((good >> j) & 1u) {
             long long lo, hi;
-            IdxHdr h;
-            if (at < a.table_cap && range_of(a, p0 + j, &lo, &hi) && index_header(a, a.stream + p0 + j, hi - (p0 + j), &h)) {
-                const uint32_t key = key0 ^ gf16_mul_d(wpow, ex ^ gf16_mul_d(c, c_xinv.v[t * IDX_LANE_BYTES + j]));
+            flac_header h;
+            if (at < a.table_cap && range_of(a, p0 + j, &lo, &hi) && flac_header_ok(&a.fmt, a.stream + p0 + j, hi - (p0 + j), &h)) {
+                const uint32_t key = key0 ^ gf16_mul(wpow, ex ^ gf16_mul(c, c_xinv.v[t * IDX_LANE_BYTES + j]));
                 a.cand_pos[at] = (int32_t)(p0 + j);
                 a.cand_meta[at] = pack_meta(h);
                 a.cand_numkey[at] = (h.number & NUM_MASK) | (unsigned long long)key << 48;
             }
             at++;
         }
-        c = crc16_step(c, (uint32_t)((j < 8 ? wl : wh) >> (8 * (j & 7))) & 0xFFu);
+        c = crc16_byte(c, (uint32_t)((j < 8 ? wl : wh) >> (8 * (j & 7))) & 0xFFu);
     }
 #undef IDX_BYTE
 }
@@ -401,9 +276,9 @@ __device__ uint32_t key_at(const IndexArgs &a, long long q)
     n = n < 0 ? 0 : (n > IDX_END_BYTES ? IDX_END_BYTES : n);
     uint32_t c = 0;
     const uint8_t *s = a.stream + base + lane * IDX_END_BYTES;
-    for (int i = 0; i < n; i++) c = crc16_step(c, s[i]);
-    const uint32_t term = n ? gf16_mul_d(c, c_xinv.v[lane * IDX_END_BYTES + n]) : 0u;
-    return key0 ^ gf16_mul_d(xinv_pow(base), wave_xor(term));
+    for (int i = 0; i < n; i++) c = crc16_byte(c, s[i]);
+    const uint32_t term = n ? gf16_mul(c, c_xinv.v[lane * IDX_END_BYTES + n]) : 0u;
+    return key0 ^ gf16_mul(xinv_pow(base), wave_xor(term));
 }
 
 struct Cand { long long pos; uint32_t meta; unsigned long long numkey; };
@@ -493,27 +368,13 @@ __global__ void __launch_bounds__(64) k_index_walk(IndexArgs a)
 __global__ void __launch_bounds__(IDX_T) k_index_ranges(IndexArgs a)
 {
     __shared__ long long ss[IDX_T / 64];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     long long carry = 0;
     for (int r0 = 0; r0 < a.nranges; r0 += IDX_T) {
         const int r = r0 + threadIdx.x;
         const int cnt = r < a.nranges ? a.rng_cnt[r] : 0;
-        const long long v = cnt > 0 ? cnt : 0;
-        long long incl = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long o = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += o;
-        }
-        if (lane == 63) ss[wid] = incl;
-        __syncthreads();
-        long long before = 0, all = 0;
-        for (int q = 0; q < IDX_T / 64; q++) {
-            if (q < wid) before += ss[q];
-            all += ss[q];
-        }
-        __syncthreads();
+        long long all = 0;
+        const long long off = carry + block_excl_scan(cnt > 0 ? cnt : 0, ss, IDX_T / 64, &all);
         if (r < a.nranges) {
-            const long long off = carry + before + incl - v;
             const long long room = off < a.frame_cap ? a.frame_cap - off : 0;
             long long lo, hi;
             range_bounds(a, r, &lo, &hi);

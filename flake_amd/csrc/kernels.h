@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "flakehip.h"
+#include "flac_header.h"
 
 namespace fhip {
 
@@ -368,7 +369,7 @@ hipError_t launch_md5_final(hipStream_t st, const fhip_md5_state *states, int ns
 struct IndexArgs {
     const uint8_t *stream; long long stream_bytes;
     const long long *range_first; int nranges;   // [nranges + 1]; read clamped into the stream
-    int channels, bps, sample_rate, max_block_size;      // what the header codes are held against (max_block_size 0: not checked)
+    flac_format fmt;                             // what the header codes are held against (max_block_size 0: not checked)
     long long frame_cap;
     int32_t *frame_bytes, *range_frames; long long *range_consumed; int32_t *range_variable;
     // working memory (the handle's)

@@ -5,7 +5,8 @@
  * hashes what it returns, so that the caller can hold it against STREAMINFO's MD5.
  *
  * flake_amd_read_streaminfo and flake_amd_index_frames make no call into the HIP layer.  flake_amd_decode_index is the
- * same discovery on the device (fhip_index_frames, K8), held to flake_amd_index_frames' answer.
+ * same discovery on the device (fhip_index_frames, K8), held to flake_amd_index_frames' answer.  What counts as a frame
+ * header is csrc/flac_header.h's predicate, the source K8 compiles too.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -33,89 +34,16 @@ FLAKE_AMD_API int flake_amd_read_streaminfo(const unsigned char d[34], FlakeAmdS
     return d[13] & 15;          /* bits 32..35 of the sample count, which the struct's 32-bit field cannot hold */
 }
 
-/* ---- a frame header on the CPU ---------------------------------------- */
+/* ---- a frame header ---------------------------------------------------- */
 
-static unsigned fa_crc8(const unsigned char *d, size_t n)
+/* flac_header_ok (csrc/flac_header.h) held against STREAMINFO: 0 when a header of this stream stands at
+ * d[0 .. avail), else -1.  A max_block_size above what a header can carry limits nothing.  (Also for
+ * flake_decode_set.c: host_internal.h.) */
+int fa_parse_header(const FlakeAmdStreaminfo *si, const unsigned char *d, size_t avail, flac_header *h)
 {
-    unsigned c = 0;
-    for (size_t i = 0; i < n; i++) {
-        c ^= d[i];
-        for (int k = 0; k < 8; k++) c = (c & 0x80u) ? ((c << 1) ^ 0x07u) & 0xFFu : (c << 1) & 0xFFu;
-    }
-    return c;
-}
-
-static int fa_rate_code_ok(int code, unsigned rate)
-{
-    static const unsigned tab[12] = {0, 88200, 176400, 192000, 8000, 16000, 22050, 24000, 32000, 44100, 48000, 96000};
-    return code == 0 || (code < 12 && tab[code] == rate);
-}
-
-static int fa_bps_code(unsigned bps)
-{
-    switch (bps) {
-    case 8: return 1;
-    case 12: return 2;
-    case 16: return 4;
-    case 20: return 5;
-    case 24: return 6;
-    case 32: return 7;
-    default: return -1;
-    }
-}
-
-/* The header at d[0 .. avail): 0 when it is one whose codes agree with si and whose CRC-8 holds, else -1.  Never
- * reads at or past avail.  (Shared with flake_decode_set.c: host_internal.h.) */
-int fa_parse_header(const FlakeAmdStreaminfo *si, const unsigned char *d, size_t avail, fa_hdr *h)
-{
-    if (avail < 6 || d[0] != 0xFF || (d[1] & 0xFE) != 0xF8) return -1;
-    const int bs_code = d[2] >> 4, sr_code = d[2] & 15, ch_code = d[3] >> 4, bps_code = (d[3] >> 1) & 7;
-    if (bs_code == 0 || sr_code == 15 || (d[3] & 1)) return -1;
-    if (sr_code < 12 && !fa_rate_code_ok(sr_code, si->sample_rate)) return -1;
-    if (ch_code > 10 || (ch_code < 8 && (unsigned)ch_code + 1 != si->channels) || (ch_code >= 8 && si->channels != 2)) return -1;
-    if (bps_code != 0 && bps_code != fa_bps_code(si->bits_per_sample)) return -1;
-    size_t p = 4;
-    const unsigned b0 = d[p++];
-    int extra = 0;
-    unsigned long long num = b0;
-    if (b0 >= 0x80u) {
-        int ones = 0;
-        while (ones < 8 && ((b0 << ones) & 0x80u)) ones++;
-        if (ones < 2 || ones > 7) return -1;
-        extra = ones - 1;
-        num = ones == 7 ? 0 : (b0 & (0x7Fu >> ones));
-    }
-    if (p + (size_t)extra > avail) return -1;
-    for (int i = 0; i < extra; i++) {
-        const unsigned c = d[p++];
-        if ((c & 0xC0u) != 0x80u) return -1;
-        num = (num << 6) | (c & 0x3Fu);
-    }
-    int n = bs_code == 1 ? 192 : (bs_code <= 5 ? 576 << (bs_code - 2) : (bs_code >= 8 ? 256 << (bs_code - 8) : 0));
-    if (bs_code == 6) {
-        if (p + 1 > avail) return -1;
-        n = d[p] + 1;
-        p += 1;
-    } else if (bs_code == 7) {
-        if (p + 2 > avail) return -1;
-        n = (d[p] << 8 | d[p + 1]) + 1;
-        p += 2;
-    }
-    if (n > 65535 || (si->max_block_size && (unsigned)n > si->max_block_size)) return -1;
-    if (sr_code >= 12) {
-        const size_t nb = sr_code == 12 ? 1 : 2;
-        if (p + nb > avail) return -1;
-        const unsigned long v = nb == 1 ? d[p] : (unsigned long)(d[p] << 8 | d[p + 1]);
-        const unsigned long rate = sr_code == 12 ? v * 1000 : (sr_code == 13 ? v : v * 10);
-        if (rate != si->sample_rate) return -1;
-        p += nb;
-    }
-    if (p + 1 > avail || fa_crc8(d, p) != d[p]) return -1;
-    h->n = n;
-    h->vbs = d[1] & 1;
-    h->len = (int)p + 1;
-    h->number = num;
-    return 0;
+    const flac_format f = {(int)si->channels, (int)si->bits_per_sample, (int)si->sample_rate,
+                           si->max_block_size > 65535u ? 0 : (int)si->max_block_size};
+    return flac_header_ok(&f, d, (long long)avail, h) ? 0 : -1;
 }
 
 /* ---- frame discovery --------------------------------------------------- */
@@ -132,7 +60,7 @@ FLAKE_AMD_API long long flake_amd_index_frames(const FlakeAmdStreaminfo *si, con
         tab[b] = (unsigned short)c;
     }
     if (bytes == 0 || cap == 0) return 0;
-    fa_hdr cur;
+    flac_header cur;
     if (fa_parse_header(si, s, bytes, &cur)) return -1;         /* garbage at the start */
     const int vbs = cur.vbs;
     size_t start = 0;
@@ -143,13 +71,13 @@ FLAKE_AMD_API long long flake_amd_index_frames(const FlakeAmdStreaminfo *si, con
         const unsigned long long want = cur.number + (vbs ? (unsigned long long)cur.n : 1ull);
         size_t k = start, end = 0;
         unsigned crc = 0;                       /* of [start, k) */
-        fa_hdr next;
+        flac_header next;
         memset(&next, 0, sizeof next);
         for (size_t q = start + (size_t)cur.len + 2; q <= bytes; q++) {
             while (k < q - 2) crc = ((crc << 8) & 0xFFFFu) ^ tab[((crc >> 8) ^ s[k++]) & 0xFFu];
             if (crc != ((unsigned)s[q - 2] << 8 | s[q - 1])) continue;
             if (q == bytes) { end = q; break; }
-            fa_hdr h;
+            flac_header h;
             if (fa_parse_header(si, s + q, bytes - q, &h) == 0 && h.vbs == vbs && h.number == want) {
                 end = q;
                 next = h;
@@ -240,7 +168,7 @@ FLAKE_AMD_API long long flake_amd_decode_frames(FlakeAmdDecoder *d, const unsign
         return -1;
     }
     if (nframes && !d->started) {
-        fa_hdr h;
+        flac_header h;
         if (frame_sizes[0] < 1 || (size_t)frame_sizes[0] > bytes || fa_parse_header(&d->si, stream, (size_t)frame_sizes[0], &h)) {
             snprintf(d->err, sizeof d->err, "frame 0: not a frame header of this stream");
             return -1;

@@ -174,7 +174,7 @@ FLAKE_AMD_API long long flake_amd_decode_set_frames(FlakeAmdDecodeSet *g, int nr
         for (int r = 0; r < nruns; r++) {
             const int s = stream_of_run[r];
             if (frames_of_run[r] > 0 && !g->st[s].started && !g->st[s].failed) {
-                fa_hdr h;
+                flac_header h;
                 if (fa_parse_header(&g->si, stream + at, (size_t)frame_sizes[f], &h)) {
                     /* not a header this parser takes: the device decides what is wrong with it (its status is the
                      * stream's, as for any later frame); it is shown the strategy bit the frame carries */
@@ -224,7 +224,7 @@ FLAKE_AMD_API long long flake_amd_decode_set_frames(FlakeAmdDecodeSet *g, int nr
             }
             if (!t->failed && b->seg_number[k] < 0 && b->seg_prev[k] >= 0) {
                 /* a variable-block-size stream's later segment of the batch: numbered on from the earlier one */
-                fa_hdr h;
+                flac_header h;
                 if (fa_parse_header(&g->si, stream + seg_bytes_at, (size_t)frame_sizes[b->frame0 + b->seg_first[k]], &h) ||
                     (long long)h.number != t->next_number)
                     ds_fail_stream(g, s, g->sx[s].frames_done, FHIP_VERIFY_NUMBER);
@@ -233,7 +233,7 @@ FLAKE_AMD_API long long flake_amd_decode_set_frames(FlakeAmdDecodeSet *g, int nr
                 ds_fail_stream(g, s, g->sx[s].frames_done, FHIP_VERIFY_HEADER);
             if (!t->failed && !t->variable) {
                 /* fixed blocks: the size rule from segment to segment (fa_ds_fixed_sizes), on the first and last header */
-                fa_hdr h0, h1;
+                flac_header h0, h1;
                 const size_t last_bytes = (size_t)frame_sizes[b->frame0 + b->seg_first[k + 1] - 1];
                 if (fa_parse_header(&g->si, stream + seg_bytes_at, (size_t)frame_sizes[b->frame0 + b->seg_first[k]], &h0) ||
                     fa_parse_header(&g->si, stream + hdr_at - last_bytes, last_bytes, &h1) ||

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../csrc/flac_header.h"
+
 typedef struct fa_md5 {
     uint32_t h[4];
     uint64_t len;
@@ -18,11 +20,10 @@ void fa_md5_final(const fa_md5 *m, uint8_t out[16]);
 void fa_md5_pcm(fa_md5 *m, const int32_t *pcm, size_t nvalues, int bps);
 void fa_md5_pcm16(fa_md5 *m, const int16_t *pcm, size_t nvalues, int bps);
 
-/* A frame header read on the CPU (flake_decode.c): block size, blocking-strategy bit, header length in bytes, the
- * coded frame or sample number. */
-typedef struct { int n, vbs, len; unsigned long long number; } fa_hdr;
+/* The frame-header predicate of csrc/flac_header.h held against a STREAMINFO (flake_decode.c): 0 and *h for a header
+ * of that stream at d[0 .. avail), else -1. */
 struct FlakeAmdStreaminfo;
-int fa_parse_header(const struct FlakeAmdStreaminfo *si, const unsigned char *d, size_t avail, fa_hdr *h);
+int fa_parse_header(const struct FlakeAmdStreaminfo *si, const unsigned char *d, size_t avail, flac_header *h);
 
 /* K8 for the decoder and the decode set (flake_decode.c): fhip_index_frames over nranges ranges of stream, the answers
  * in the host layer's types.  0, -1 for a bad argument, -2 where the device could not answer (err says why). */

@@ -299,6 +299,33 @@ def flacgen_header_len(frame):
     raise AssertionError("no header")
 
 
+# ---- the header predicate, compiled for the device ---------------------------------------------------
+
+def test_header_catalogue_a_range_per_case(handles):
+    """The header catalogue of tests/test_flac_header_cpu.py laid end to end, each case a range of its own that ends at
+    the case's `avail`: K8 answers -1 where the range does not begin with a header and 0 where it does (a header alone
+    closes no frame), so range_frames against the CPU indexer's is the predicate's verdict from both compilers.  One
+    format, one call: every valid header, every truncation of those whose strategy bit is 0, every bit flip of the two
+    longest of them and the reserved and disagreeing codes."""
+    import test_flac_header_cpu as H
+    valid = H.valid_headers()
+    fixed = [h for h in valid if not h[1] & 1]
+    pieces = list(valid)
+    pieces += [h[:avail] for h in fixed for avail in range(1, len(h))]
+    for h in sorted(fixed, key=len)[-2:]:
+        for bit in range(8 * len(h)):
+            x = bytearray(h)
+            x[bit >> 3] ^= 0x80 >> (bit & 7)
+            pieces.append(bytes(x))
+    pieces += [h for fmt, h, _ in H.field_cases() if fmt == H.BASE]
+    assert 300 <= len(pieces) <= 800 and max(map(len, pieces)) == 16
+    si = streaminfo(channels=H.BASE[0], bps=H.BASE[1], rate=H.BASE[2], max_block=H.BASE[3])
+    first = [0] + [int(v) for v in np.cumsum([len(p) for p in pieces])]
+    want = agree(handles, si, b"".join(pieces), first=first)
+    assert want[0] == [] and want[1].count(0) >= 40 and want[1].count(-1) >= 40
+    assert want[1] == [0 if H.reference(H.BASE, p, len(p)) else -1 for p in pieces]
+
+
 # ---- many ranges -------------------------------------------------------------------------------------
 
 def test_eight_ranges_one_call(handles):

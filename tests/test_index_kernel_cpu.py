@@ -1,7 +1,7 @@
 """K8's kernels (k8_index.hip): every one is there and compiles for gfx950 without scratch, without spills and without
-AGPRs; and K5's and K7's register and LDS figures are what they were before K8 came (the new file shares no code with
-them, so nothing they compile to may move).  Runs without a GPU.  The figures are printed (pytest -s) and recorded in
-DESIGN.md."""
+AGPRs; and K5's and K7's register and LDS figures are what they were before K8 came (K8 shares flac_header.h's tables
+and flac_parse.h's CRC-16 and scan with them, and sharing must not move what they compile to).  Runs without a GPU.
+The figures are printed (pytest -s) and recorded in DESIGN.md."""
 import ctypes as C
 import os
 import subprocess
