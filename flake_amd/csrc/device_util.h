@@ -28,8 +28,8 @@ static __device__ long long g_fhip_stamps[64];   // one per kernel file; api.hip
     {                                                                                  \
         return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fhip_stamps), sizeof(long long) * 64); \
     }
-// accumulating timers (tools/stamps_k1.py): TICK reads the clock, ACCUM adds an
-// interval to slot i for the first wave pair of workgroup 0
+// interval timers (tools/stamps_k1.py, tools/stamps_k1_waves.py): TICK reads the clock; k1_autocorr.hip adds the
+// intervals up in registers and stores them once per wave (its ACC_* macros)
 #define TICK(v_)                                                                       \
     unsigned long long v_;                                                             \
     do {                                                                               \
@@ -37,32 +37,9 @@ static __device__ long long g_fhip_stamps[64];   // one per kernel file; api.hip
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v_)::"memory");      \
         __builtin_amdgcn_sched_barrier(0);                                             \
     } while (0)
-#define ACCUM(i, a_, b_)                                                               \
-    do {                                                                               \
-        if (blockIdx.x == 0 && (threadIdx.x & 255) == 0) g_fhip_stamps[i] += (long long)((b_) - (a_)); \
-    } while (0)
-#define ACC_RESET(lo, hi)                                                              \
-    do {                                                                               \
-        if (blockIdx.x == 0 && (threadIdx.x & 255) == 0) for (int z_ = lo; z_ < hi; z_++) g_fhip_stamps[z_] = 0; \
-    } while (0)
-// per wave (tools/stamps_k1_waves.py): wave w of workgroup 0 (w < 4) adds to slot i + w
-#define ACCUM_W(i, a_, b_)                                                             \
-    do {                                                                               \
-        if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && threadIdx.x < 256)           \
-            g_fhip_stamps[(i) + (threadIdx.x >> 6)] += (long long)((b_) - (a_));       \
-    } while (0)
-#define ACC_RESET_W(i)                                                                 \
-    do {                                                                               \
-        if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && threadIdx.x < 256)           \
-            g_fhip_stamps[(i) + (threadIdx.x >> 6)] = 0;                               \
-    } while (0)
 #else
-#define ACCUM_W(i, a_, b_) do { } while (0)
-#define ACC_RESET_W(i) do { } while (0)
 #define STAMP(i) do { } while (0)
 #define TICK(v_) do { } while (0)
-#define ACCUM(i, a_, b_) do { } while (0)
-#define ACC_RESET(lo, hi) do { } while (0)
 #endif
 
 namespace fhip {

@@ -8,6 +8,25 @@
 
 #ifdef FHIP_STAMPS
 FHIP_DEFINE_STAMP_READER(fhip_debug_read_stamps_k1)      // slots 40..63 (tools/stamps_k1.py)
+// The wave-typed kernel's timers (tools/stamps_k1.py, tools/stamps_k1_waves.py) add up in registers and are stored
+// once, when the wave is done.  Until round 8 every interval was a read-modify-write of global memory, whose load
+// a wave waits for with vmcnt(0) -- behind every load a producer has in flight, so the stamped producers ran
+// without their prefetch, and each consumer tile carried three such round trips in its walk time.
+// Slots of this file's own array (fhip_debug_read_stamps_k1): 0..11 the producers' staging / issue_loads /
+// barrier wait (slot + producer), 16..23 the HW_ID register of waves 0..7 (SIMD_ID in bits 5:4), 40..63 the
+// consumers' as before.
+#define ACC_DECL(v_, n_) unsigned long long v_[n_] = {}
+#define ACC_ADD(v_, i_, a_, b_) v_[i_] += (b_) - (a_)
+#define ACC_PUT(slot_, val_)                                                           \
+    do {                                                                               \
+        if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) g_fhip_stamps[slot_] = (long long)(val_); \
+    } while (0)
+#define STAMP_HWID() ACC_PUT(16 + (threadIdx.x >> 6), __builtin_amdgcn_s_getreg((31 << 11) | 4))
+#else
+#define ACC_DECL(v_, n_) do { } while (0)
+#define ACC_ADD(v_, i_, a_, b_) do { } while (0)
+#define ACC_PUT(slot_, val_) do { } while (0)
+#define STAMP_HWID() do { } while (0)
 #endif
 
 namespace fhip {
@@ -534,13 +553,19 @@ void k_autocorr_ps(const int32_t *__restrict__ smp, double *__restrict__ autoc,
 // groups, but on two SIMDs: it pays only with 64 subframes per CU, which the LDS does
 // not hold at this tile size.
 // Requires n % AC_TILE == 0 (launch_autocorr falls back otherwise).
-constexpr int WT_SUB = 32;                           // subframes per workgroup
-#ifndef FHIP_WT_ROWS0
-#define FHIP_WT_ROWS0 8
-#endif
-constexpr int WT_ROWS0 = FHIP_WT_ROWS0;              // rows staged by the producer next to consumer 0
-constexpr int WT_ROWS1 = (WT_SUB - WT_ROWS0) / 3;    // ... by each of the other three
-static_assert(WT_ROWS0 + 3 * WT_ROWS1 == WT_SUB, "producer row split");
+// WT_SUB = 32 subframes per workgroup (kernels.h).  Which producer stages which rows is a build constant
+// per instance (kernels.h: wt_split, one row count per producer wave, prefix sums give its first row):
+// WT_SPLIT_O8 for <3, false, 8>, whose four groups are always {0,2,4} {6,8} {1,3} {5,7} (max order 8,
+// unsplit), WT_SPLIT_EVEN (8/8/8/8) for every other instance -- their groups differ and were not measured.
+// Round 8 (per-producer stamps, tools/stamps_k1_waves.py, profiles/r08_k1_wave_stamps.txt) separated a
+// producer's issue time from its waiting: the producer beside {0,2,4} is the last wave at every barrier (its
+// row-pass costs 217 cycles on the SIMD it shares with the heaviest walk, 170-182 elsewhere) and consumer 0
+// waits 298 cycles per hand-over for it.  6/10/8/8 removes that wait and slows consumer 0's walk by 0.5
+// cycles per step: the headline overlaps 8/8/8/8 (0.1311-0.1319 ms against 0.1317-0.1323), the other splits
+// timed lose, twelve rows in one producer take <3, false, 8> from 170 to 201-205 VGPRs.  WT_SPLIT_O8 stays
+// 8/8/8/8 (DESIGN.md sections 3 and 8).
+template <int NCH, bool FUSED, int LPCMO>
+constexpr wt_split wt_split_of() { return (NCH == 3 && !FUSED && LPCMO == 8) ? WT_SPLIT_O8 : WT_SPLIT_EVEN; }
 // LDS geometry: the `a` stream is read 16 bytes (two steps) at a time, so arrays
 // start on even doubles; ds_read_b128 serves 16 lanes per LDS cycle and is
 // conflict-free when their 16-byte slots differ mod 16: stride/2 odd (83).  The
@@ -684,6 +709,7 @@ void wt_body(const int32_t *__restrict__ smp, double *__restrict__ autoc,
     const int half = n >> 1;
     const int ntiles = n / TL;
     const int ntiles_pad = ((ntiles + T_UT - 1) / T_UT) * T_UT;               // the producers' unroll
+    STAMP_HWID();
 
     if (wv >= 4) {
         // ------------------------------ producer ------------------------------
@@ -691,10 +717,9 @@ void wt_body(const int32_t *__restrict__ smp, double *__restrict__ autoc,
         // 512 contiguous bytes per row and instruction.  The loop is unrolled by
         // the prefetch depth so every tile has its own registers, and it has no
         // branches, so the waits stay counted (vmcnt(N), never 0).
-        // A producer shares its SIMD with consumer wv-4.  The split of the 32 rows
-        // between the producer next to consumer 0 (largest lag group) and the other
-        // three is a build constant; measured 2/10/10/10: 60.3 us, 5/9/9/9 and
-        // 8/8/8/8: 58.2 -- the walk of consumer 0, not the staging, sets the time.
+        // A producer shares its SIMD with consumer wv-4 (HW_ID of both, round 8).  The split of the
+        // 32 rows between the four producers is a build constant per instance (wt_split_of);
+        // measured in round 1, 2/10/10/10: 60.3 us, 5/9/9/9 and 8/8/8/8: 58.2.
         // ALLNAR: every row of this wave is a 16-bit row (the usual case for 16-bit input):
         // 4-byte loads and no per-row width select
         auto produce = [&](auto nrows_c, int q0, auto allnar_c) {
@@ -774,7 +799,7 @@ void wt_body(const int32_t *__restrict__ smp, double *__restrict__ autoc,
                 return valid ? (1.0 - (tt * tt)) : 0.0;
             };
             int bi = 0;                                        // t % T_NBUF
-            ACC_RESET(44, 48);
+            ACC_DECL(pacc, 3);                                 // staging, issue_loads, barrier wait
             for (int t0 = 0; t0 < ntiles_pad; t0 += T_UT) {
 #pragma unroll
                 for (int a = 0; a < T_UT; a++) {
@@ -855,7 +880,7 @@ void wt_body(const int32_t *__restrict__ smp, double *__restrict__ autoc,
                         TICK(tp1);
                         issue_loads(pre[ai], tb + T_AHEAD * AC_TILE);
                         TICK(tp2);
-                        ACCUM(44, tp0, tp1); ACCUM(45, tp1, tp2);
+                        ACC_ADD(pacc, 0, tp0, tp1); ACC_ADD(pacc, 1, tp1, tp2);
                         if (h < T_UNITS - 1) {
                             // keep the second pass's conversions below this point, as below the barrier
                             __builtin_amdgcn_sched_barrier(0);
@@ -864,26 +889,49 @@ void wt_body(const int32_t *__restrict__ smp, double *__restrict__ autoc,
                     TICK(tp2);
                     __syncthreads();                                 // tile handed over
                     TICK(tp3);
-                    ACCUM(46, tp2, tp3);
+                    ACC_ADD(pacc, 2, tp2, tp3);
                     // keep the next tile's conversions below this point: hoisted, they
                     // would wait for loads that still have two tiles of time
                     __builtin_amdgcn_sched_barrier(0);
                     bi = bnx;
                 }
             }
+            // per producer wave; 44..46: wave 4's, as tools/stamps_k1.py reads them
+            ACC_PUT(wv - 4, pacc[0]); ACC_PUT(wv, pacc[1]); ACC_PUT(wv + 4, pacc[2]);
+            if (wv == 4) { ACC_PUT(44, pacc[0]); ACC_PUT(45, pacc[1]); ACC_PUT(46, pacc[2]); }
         };
-        const int q0w = (wv == 4) ? 0 : WT_ROWS0 + (wv - 5) * WT_ROWS1;
-        const int nrw = (wv == 4) ? WT_ROWS0 : WT_ROWS1;
+        // this wave's share of the 32 rows: SP.rows[wv - 4] rows from the prefix sum on (selects, as for grp.l0)
+        constexpr wt_split SP = wt_split_of<NCH, FUSED, LPCMO>();
+        static_assert(wt_split_valid(SP), "producer row split");
+        const int q0w = (wv == 4) ? 0 : (wv == 5) ? wt_split_first(SP, 1) : (wv == 6) ? wt_split_first(SP, 2)
+                                                                                      : wt_split_first(SP, 3);
+        const int nrw = (wv == 4) ? SP.rows[0] : (wv == 5) ? SP.rows[1] : (wv == 6) ? SP.rows[2] : SP.rows[3];
+        // Every row's width flag in ONE round trip: lane r reads the flag of row q0w + r (lanes past the share
+        // read its last row again) and a ballot joins them.  The loop that was here asked row after row and left
+        // at the first wide one: up to nrw dependent loads, each a miss in this CU's caches (K0 wrote the
+        // records), before the wave could issue its first sample load.  Round 8, the consumers' wait for tile 0
+        // at the headline: 11.6 k cycles -> 6.8 k (128 form 9.8 k -> 4.4 k), step 0.1342 -> 0.1320 ms; it also
+        // made every producer's start-up grow with its row count, which is what the splits timed before this
+        // were really measuring (profiles/r08_k1_wave_stamps.txt).
         bool alln = !FUSED && narrow_ok != 0;
-        for (int r = 0; alln && r < nrw; r++) alln = (info[min(sub0 + q0w + r, nsub - 1)].reserved & 0xFF) != 0;
-        alln = __builtin_amdgcn_readfirstlane((int)alln) != 0;
-        if (wv == 4) {
-            if (alln) produce(std::integral_constant<int, WT_ROWS0>{}, q0w, std::true_type{});
-            else produce(std::integral_constant<int, WT_ROWS0>{}, q0w, std::false_type{});
-        } else {
-            if (alln) produce(std::integral_constant<int, WT_ROWS1>{}, q0w, std::true_type{});
-            else produce(std::integral_constant<int, WT_ROWS1>{}, q0w, std::false_type{});
+        if (alln) {
+            const int wide = (info[min(sub0 + q0w + min(lane, nrw - 1), nsub - 1)].reserved & 0xFF) == 0;
+            alln = __ballot(wide) == 0;
         }
+        // one instance of produce per distinct row count (producers with equal counts share its code)
+        auto produce_rows = [&](auto kc) {
+            constexpr int K = decltype(kc)::value;
+            if constexpr (wt_split_first_with(SP, K)) {
+                if (nrw == SP.rows[K]) {
+                    if (alln) produce(std::integral_constant<int, SP.rows[K]>{}, q0w, std::true_type{});
+                    else produce(std::integral_constant<int, SP.rows[K]>{}, q0w, std::false_type{});
+                }
+            }
+        };
+        produce_rows(std::integral_constant<int, 0>{});
+        produce_rows(std::integral_constant<int, 1>{});
+        produce_rows(std::integral_constant<int, 2>{});
+        produce_rows(std::integral_constant<int, 3>{});
         if (LPCMO > 0) __syncthreads();                    // the tail's barrier (below)
         return;
     }
@@ -1030,12 +1078,13 @@ void wt_body(const int32_t *__restrict__ smp, double *__restrict__ autoc,
 #pragma unroll
         for (int k = 0; k < (HD > 0 ? HD : 1); k++) hist[k] = 0.0;
         int bi = 0;
+        ACC_DECL(cacc, 4);                                     // barrier wait, walk, tile 0, the wait for tile 0
         for (int t = 0; t < ntiles_pad; t++) {
             TICK(tc0);
             __syncthreads();                                   // tile t is in buffer bi
             TICK(tc1);
-            ACCUM(40, tc0, tc1);
-            ACCUM_W(56, tc0, tc1);
+            ACC_ADD(cacc, 0, tc0, tc1);
+            if (t == 0) ACC_ADD(cacc, 3, tc0, tc1);            // cycles before the first walk can start
             if (t >= ntiles || wt_probe_nowalk || nch <= 0) continue;    // padding of the producers' unroll
             const double *buf = wt_lds + bi * T_BUF;
             if (t == 0 && pi == pih) {
@@ -1083,13 +1132,14 @@ void wt_body(const int32_t *__restrict__ smp, double *__restrict__ autoc,
             else walk_tile(buf + offA, buf + offB, std::false_type{}, same, histc, kc, hist);
             bi = (bi == T_NBUF - 1) ? 0 : bi + 1;
             TICK(tc2);
-            ACCUM(t == 0 ? 42 : 41, tc1, tc2);
-            ACCUM_W(t == 0 ? 52 : 48, tc1, tc2);
+            if (t == 0) ACC_ADD(cacc, 2, tc1, tc2);
+            else ACC_ADD(cacc, 1, tc1, tc2);
         }
+        // per consumer wave: walk, tile 0, barrier wait, first wait; 40..42: wave 0's, as tools/stamps_k1.py reads them
+        ACC_PUT(48 + wv, cacc[1]); ACC_PUT(52 + wv, cacc[2]); ACC_PUT(56 + wv, cacc[0]); ACC_PUT(60 + wv, cacc[3]);
+        if (wv == 0) { ACC_PUT(40, cacc[0]); ACC_PUT(41, cacc[1]); ACC_PUT(42, cacc[2]); }
     };
 
-    ACC_RESET(40, 44);
-    ACC_RESET_W(48); ACC_RESET_W(52); ACC_RESET_W(56);    // per consumer wave: walk, tile 0, barrier wait
     using KF = std::integral_constant<int, NCH>;
     using KL = std::integral_constant<int, (NCH > 1) ? NCH - 1 : 1>;
     using H0 = std::integral_constant<int, 0>;
@@ -1305,7 +1355,8 @@ bool autocorr_fuses_prepare(const fhip_params &p, int nsub, int n)
     // Off by default: measured on configs[1] the decision-only K0 saves 18 us and 134 MB
     // of HBM writes, but the producers' extra work costs K1 11 us on the SIMDs that
     // are its bottleneck, and the step ends up 2 % slower (0.2106 vs 0.2057 ms).
-    static const bool on = getenv("FHIP_FUSE") != nullptr && (WT_ROWS0 % 2) == 0 && (WT_ROWS1 % 2) == 0;
+    // (the fused instances stage channel pairs: wt_split_valid keeps every producer's row count even)
+    static const bool on = getenv("FHIP_FUSE") != nullptr;
     if (!on || p.channels != 2 || (n & 3) != 0 || n > 4096 || (nsub & 1)) return false;
     return pick_autocorr(nsub, n, p.max_prediction_order).kernel == 2;
 }

@@ -80,6 +80,47 @@ bool narrow_rows_ok(const fhip_params &p, int nsub, int n, bool lpc_path, bool w
 // tiles, the wave-typed kernel): launch_prepare(decide_only) + launch_autocorr(pcm).
 bool autocorr_fuses_prepare(const fhip_params &p, int nsub, int n);
 
+// The wave-typed K1: a workgroup owns WT_SUB subframes, and its four producer waves stage rows[0..3] of them
+// each, in row order (producer p starts at the prefix sum wt_split_first(s, p)).  Counts are even (the fused
+// instances stage channel pairs) and positive, and they sum to WT_SUB, so every row is staged exactly once.
+constexpr int WT_SUB = 32;
+struct wt_split { int rows[4]; };
+constexpr int wt_split_first(const wt_split &s, int p)
+{
+    int q = 0;
+    for (int k = 0; k < p; k++) q += s.rows[k];
+    return q;
+}
+constexpr bool wt_split_valid(const wt_split &s)
+{
+    for (int k = 0; k < 4; k++) if (s.rows[k] < 2 || (s.rows[k] & 1)) return false;
+    return wt_split_first(s, 4) == WT_SUB;
+}
+// true when no producer before p has p's row count (one instance of the staging code per distinct count)
+constexpr bool wt_split_first_with(const wt_split &s, int p)
+{
+    for (int k = 0; k < p; k++) if (s.rows[k] == s.rows[p]) return false;
+    return true;
+}
+// FHIP_WT_ROWS_P0 .. _P3: the split of k_autocorr_wt<3, false, 8> (max order 8, unsplit: the headline's K1),
+// one build constant per producer (-DFHIP_WT_ROWS_P0=6 -DFHIP_WT_ROWS_P1=12 ... for timing another split);
+// every other instance stages 8/8/8/8 (k1_autocorr.hip: wt_split_of).
+#ifndef FHIP_WT_ROWS_P0
+#define FHIP_WT_ROWS_P0 8
+#endif
+#ifndef FHIP_WT_ROWS_P1
+#define FHIP_WT_ROWS_P1 8
+#endif
+#ifndef FHIP_WT_ROWS_P2
+#define FHIP_WT_ROWS_P2 8
+#endif
+#ifndef FHIP_WT_ROWS_P3
+#define FHIP_WT_ROWS_P3 8
+#endif
+constexpr wt_split WT_SPLIT_EVEN = {{8, 8, 8, 8}};
+constexpr wt_split WT_SPLIT_O8 = {{FHIP_WT_ROWS_P0, FHIP_WT_ROWS_P1, FHIP_WT_ROWS_P2, FHIP_WT_ROWS_P3}};
+static_assert(wt_split_valid(WT_SPLIT_EVEN) && wt_split_valid(WT_SPLIT_O8), "producer row split");
+
 // K1: apply_welch_window + compute_autocorr (lpc.c:28-71).
 // smp [nsub][n] -> autoc [nsub][FHIP_MAX_LAGS].
 // With pcm_fused (stereo PCM) the producers read it instead of smp, apply info[]'s
