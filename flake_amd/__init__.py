@@ -276,6 +276,10 @@ def load_library() -> C.CDLL:
         "fhip_device_alloc": (vp, [C.c_size_t]),
         "fhip_device_free": (None, [vp]),
         "fhip_autocorr_tile": (i, [i, i, i]),
+        "fhip_gather_spans_dev": (i, [vp, vp, i64, vp, i64, vp, i64, vp, i]),
+        "fhip_frames_packed_gather": (i, [vp, C.POINTER(Batch), vp, vp, i64, vp, i64, vp, i]),
+        "fhip_decode_frames_segments_keep": (i, [vp, C.POINTER(DecodeIn), C.POINTER(DecodeSegments), C.POINTER(DecodeOut),
+                                                 C.POINTER(DecodeMd5)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -309,7 +313,20 @@ ABI_SYMBOLS = (
     "fhip_decode_frames_dev", "fhip_decode_frames",
     "fhip_decode_frames_segments_dev", "fhip_decode_frames_segments", "fhip_md5_update_ranges_dev",
     "fhip_index_frames_dev", "fhip_index_frames", "fhip_index_geometry",
+    "fhip_gather_spans_dev", "fhip_frames_packed_gather", "fhip_decode_frames_segments_keep",
 )
+
+# fhip_gather_piece (24 bytes): K9's unit, in samples per channel
+GATHER_PIECE_DTYPE = np.dtype([("src_buf", "<i4"), ("count", "<i4"), ("src", "<i8"), ("dst", "<i8")])
+assert GATHER_PIECE_DTYPE.itemsize == 24
+
+
+def gather_pieces(rows) -> np.ndarray:
+    """[(src_buf, src, dst, count)] as a fhip_gather_piece table."""
+    t = np.zeros(len(rows), dtype=GATHER_PIECE_DTYPE)
+    for k, (buf, src, dst, count) in enumerate(rows):
+        t[k] = (buf, count, src, dst)
+    return t
 
 
 def _ptr(a) -> int | None:
@@ -663,6 +680,30 @@ class Encoder:
         io = IndexOut(_ptr(frame_bytes), _ptr(range_frames), _ptr(range_consumed), _ptr(range_variable))
         self._check(self.lib.fhip_index_frames_dev(self._h, C.byref(ii), C.byref(io)), "fhip_index_frames_dev")
 
+    # -- K9: gathering spans on the device ---------------------------------
+    def gather_spans_dev(self, dst, dst_cap: int, src0, src0_cap: int, src1, src1_cap: int, pieces) -> int:
+        """fhip_gather_spans_dev: dst, src0, src1 are int32 device memory (torch tensors or raw addresses; a source may
+        be None with capacity 0), capacities in samples per channel; pieces a GATHER_PIECE_DTYPE host table (see
+        gather_pieces).  Async on the handle's stream.  Returns the code: E_INVALID means nothing was queued."""
+        t = np.ascontiguousarray(pieces, dtype=GATHER_PIECE_DTYPE)
+        return self.lib.fhip_gather_spans_dev(self._h, _ptr(dst) if not isinstance(dst, int) else dst, int(dst_cap),
+                                              _ptr(src0) if not isinstance(src0, int) else src0, int(src0_cap),
+                                              _ptr(src1) if not isinstance(src1, int) else src1, int(src1_cap),
+                                              t.ctypes.data if len(t) else None, len(t))
+
+    def frames_packed_gather(self, token: int, nframes: int, block_size: int, src0, src0_cap: int, src1, src1_cap: int,
+                             pieces, block_sizes=None) -> int:
+        """fhip_frames_packed_gather: the handle's PCM staging filled through a piece table from device sources, in
+        place of fhip_frames_packed_upload(_ragged).  token: the value the following _begin's Batch.pcm must carry (it
+        names the batch and is never followed).  Returns the code."""
+        t = np.ascontiguousarray(pieces, dtype=GATHER_PIECE_DTYPE)
+        sz = None if block_sizes is None else np.ascontiguousarray(block_sizes, dtype=np.int32)
+        b = Batch(pcm=token, nframes=nframes, block_size=block_size)
+        return self.lib.fhip_frames_packed_gather(self._h, C.byref(b), None if sz is None else sz.ctypes.data,
+                                                  _ptr(src0) if not isinstance(src0, int) else src0, int(src0_cap),
+                                                  _ptr(src1) if not isinstance(src1, int) else src1, int(src1_cap),
+                                                  t.ctypes.data if len(t) else None, len(t))
+
     def kernel_times(self, reset: bool = True) -> dict:
         names = (C.c_char_p * 32)()
         ms = (C.c_double * 32)()
@@ -943,6 +984,28 @@ def load_host_library() -> C.CDLL:
     lib.flake_amd_decode_set_last_error.restype = C.c_char_p
     lib.flake_amd_decode_set_close.argtypes = [C.c_void_p]
     lib.flake_amd_decode_set_close.restype = None
+    vp = C.c_void_p
+    lib.flake_amd_recode_set_open.argtypes = [C.POINTER(HostStreaminfo), cp, C.c_int, C.c_uint]
+    lib.flake_amd_recode_set_open.restype = vp
+    lib.flake_amd_recode_set_frames.argtypes = [vp, C.c_int, vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp, vp, C.c_int,
+                                                C.POINTER(C.c_int)]
+    lib.flake_amd_recode_set_frames.restype = C.c_longlong
+    lib.flake_amd_recode_set_out_bound.argtypes = [vp, C.c_longlong, C.POINTER(C.c_size_t), C.POINTER(C.c_longlong)]
+    lib.flake_amd_recode_set_out_bound.restype = C.c_int
+    lib.flake_amd_recode_set_finish.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(C.c_int)]
+    lib.flake_amd_recode_set_finish.restype = C.c_longlong
+    lib.flake_amd_recode_set_get_streaminfo.argtypes = [vp, C.c_int, C.POINTER(HostStreaminfo)]
+    lib.flake_amd_recode_set_get_streaminfo.restype = C.c_int
+    lib.flake_amd_recode_set_failed.argtypes = [vp, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
+    lib.flake_amd_recode_set_failed.restype = C.c_int
+    lib.flake_amd_recode_set_device_batches.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    lib.flake_amd_recode_set_device_batches.restype = C.c_int
+    lib.flake_amd_recode_set_enable_verify.argtypes = [vp, C.c_int]
+    lib.flake_amd_recode_set_enable_verify.restype = C.c_int
+    lib.flake_amd_recode_set_last_error.argtypes = [vp]
+    lib.flake_amd_recode_set_last_error.restype = C.c_char_p
+    lib.flake_amd_recode_set_close.argtypes = [vp]
+    lib.flake_amd_recode_set_close.restype = None
     _host = lib
     return lib
 
@@ -1380,6 +1443,141 @@ class DecodeSet:
     def close(self) -> None:
         if getattr(self, "_g", None):
             self.lib.flake_amd_decode_set_close(self._g)
+            self._g = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RecodeSet:
+    """A recode set of the host C layer (flake_amd_recode_set_*): FLAC frames of many streams of one format in, FLAC
+    frames at other parameters out, the PCM never leaving the device.  like: the sources' STREAMINFO (format and largest
+    block); level / over: the encoder's parameters, as StreamSet takes them; flags: SET_VBS (levels 9-12), SET_MD5_OFF.
+    ctypes only; no compute here."""
+
+    def __init__(self, like: HostStreaminfo, nstreams: int, level: int = 5, flags: int = 0, channels: int | None = None,
+                 bits_per_sample: int | None = None, sample_rate: int | None = None, **over):
+        self.lib = load_host_library()
+        self.si = like
+        self.ctx = HostContext(channels=like.channels if channels is None else channels,
+                               sample_rate=like.sample_rate if sample_rate is None else sample_rate,
+                               bits_per_sample=like.bits_per_sample if bits_per_sample is None else bits_per_sample)
+        self.ctx.params.compression = level
+        if self.lib.flake_amd_set_defaults(C.byref(self.ctx.params)) != 0:
+            raise ValueError("flake_amd_set_defaults")
+        for k, v in over.items():
+            if not hasattr(self.ctx.params, k):
+                raise AttributeError(k)
+            setattr(self.ctx.params, k, v)
+        self.nstreams = int(nstreams)
+        self.block_size = self.ctx.params.block_size
+        self._g = self.lib.flake_amd_recode_set_open(C.byref(like), C.byref(self.ctx), self.nstreams, int(flags))
+        if not self._g:
+            raise FlakeHipError(-1, "flake_amd_recode_set_open", self.lib.flake_amd_recode_set_last_error(None).decode())
+
+    def last_error(self) -> str:
+        return self.lib.flake_amd_recode_set_last_error(self._g).decode()
+
+    def out_bound(self, nframes: int):
+        """(bytes, blocks) a recode_runs call of nframes frames may write at most; nframes -1: finish's."""
+        nb, nk = C.c_size_t(0), C.c_longlong(0)
+        self.lib.flake_amd_recode_set_out_bound(self._g, int(nframes), C.byref(nb), C.byref(nk))
+        return nb.value, nk.value
+
+    @staticmethod
+    def _split(out, streams, sizes, n):
+        res, at = [], 0
+        for b in range(n):
+            res.append((int(streams[b]), out[at:at + sizes[b]].tobytes()))
+            at += int(sizes[b])
+        return res
+
+    def recode_runs(self, runs, out_size: int | None = None, block_cap: int | None = None):
+        """runs: [(stream index, frame bytes, frame sizes)], as DecodeSet.decode_runs takes them.  Returns the whole
+        blocks the call completed as [(stream, bytes)], each stream's in stream order.  out_size / block_cap default
+        to the call's bound.  Raises FlakeHipError when the call is refused (nothing changed then) or fails."""
+        sor = np.asarray([r[0] for r in runs], dtype=np.int32)
+        fs = [np.ascontiguousarray(r[2], dtype=np.int32) for r in runs]
+        fof = np.asarray([len(f) for f in fs], dtype=np.int32)
+        parts = [np.frombuffer(bytes(r[1]), dtype=np.uint8) if isinstance(r[1], (bytes, bytearray))
+                 else np.asarray(r[1], dtype=np.uint8) for r in runs]
+        st = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, np.uint8)
+        sizes = np.ascontiguousarray(np.concatenate(fs)) if fs else np.zeros(0, np.int32)
+        need_bytes, need_blocks = self.out_bound(int(fof.sum()))
+        out_size = need_bytes if out_size is None else int(out_size)
+        block_cap = need_blocks if block_cap is None else int(block_cap)
+        out = np.zeros(max(out_size, 1), dtype=np.uint8)
+        bst, bby = np.zeros(max(block_cap, 1), dtype=np.int32), np.zeros(max(block_cap, 1), dtype=np.int32)
+        nb = C.c_int(0)
+        w = self.lib.flake_amd_recode_set_frames(self._g, len(runs), sor.ctypes.data if len(runs) else None,
+                                                 fof.ctypes.data if len(runs) else None,
+                                                 st.ctypes.data if st.size else None, st.size,
+                                                 sizes.ctypes.data if sizes.size else None, out.ctypes.data, out_size,
+                                                 bst.ctypes.data, bby.ctypes.data, block_cap, C.byref(nb))
+        if w < 0:
+            raise FlakeHipError(int(w), "flake_amd_recode_set_frames", self.last_error())
+        assert int(bby[:nb.value].sum()) == w
+        return self._split(out, bst, bby, nb.value)
+
+    def finish(self, out_size: int | None = None, block_cap: int | None = None):
+        """flake_amd_recode_set_finish: every good stream's tail as [(stream, bytes)]."""
+        need_bytes, need_blocks = self.out_bound(-1)
+        out_size = need_bytes if out_size is None else int(out_size)
+        block_cap = need_blocks if block_cap is None else int(block_cap)
+        out = np.zeros(max(out_size, 1), dtype=np.uint8)
+        bst, bby = np.zeros(max(block_cap, 1), dtype=np.int32), np.zeros(max(block_cap, 1), dtype=np.int32)
+        nb = C.c_int(0)
+        w = self.lib.flake_amd_recode_set_finish(self._g, out.ctypes.data, out_size, bst.ctypes.data, bby.ctypes.data,
+                                                 block_cap, C.byref(nb))
+        if w < 0:
+            raise FlakeHipError(int(w), "flake_amd_recode_set_finish", self.last_error())
+        return self._split(out, bst, bby, nb.value)
+
+    def streaminfo(self, stream: int):
+        """The new STREAMINFO of a good stream (md5sum: the decode side's digest), None for a failed one."""
+        si = HostStreaminfo()
+        if self.lib.flake_amd_recode_set_get_streaminfo(self._g, int(stream), C.byref(si)) != 0:
+            return None
+        return si
+
+    def streaminfo_bytes(self, stream: int):
+        si = self.streaminfo(stream)
+        if si is None:
+            return None
+        buf = (C.c_ubyte * 34)()
+        self.lib.flake_amd_write_streaminfo(C.byref(si), buf)
+        return bytes(buf)
+
+    def failed(self, stream: int):
+        """None while the stream is good, else (frame counted from the stream's first, FHIP_VERIFY_* status)."""
+        fr, st = C.c_longlong(-1), C.c_int(0)
+        rc = self.lib.flake_amd_recode_set_failed(self._g, int(stream), C.byref(fr), C.byref(st))
+        if rc < 0:
+            raise IndexError(stream)
+        return (fr.value, st.value) if rc else None
+
+    def device_batches(self):
+        """(decode batches, encode batches) so far."""
+        d, e = C.c_longlong(0), C.c_longlong(0)
+        self.lib.flake_amd_recode_set_device_batches(self._g, C.byref(d), C.byref(e))
+        return d.value, e.value
+
+    def set_verify(self, on: bool) -> None:
+        if self.lib.flake_amd_recode_set_enable_verify(self._g, int(on)) != 0:
+            raise RuntimeError("flake_amd_recode_set_enable_verify")
+
+    def close(self) -> None:
+        if getattr(self, "_g", None):
+            self.lib.flake_amd_recode_set_close(self._g)
             self._g = None
 
     def __enter__(self):

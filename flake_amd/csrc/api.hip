@@ -155,6 +155,10 @@ struct fhip_ctx {
                                               // range_frames, range_variable [nranges], frame_bytes
     std::vector<long long> h_iio;             // ... and the host image the outputs come back to
 
+    // K9 (fhip_gather_spans_dev, fhip_frames_packed_gather): the piece table on the device, grow-only
+    DevBuf<fhip_gather_piece> d_gather;
+    std::vector<fhip_gather_piece> h_gather;  // ... and the host image it is uploaded from
+
     std::vector<std::string> launches;        // fhip_last_launches: what the most recent call queued
 
     // ragged batches (fhip_frames_packed_*_ragged): the per-frame tables, one device block laid out as
@@ -209,13 +213,13 @@ void note_launch(const char *fmt, ...)
 
 namespace {
 
-constexpr int kNumKernels = 8 + fhip::INDEX_STEPS;
+constexpr int kNumKernels = 9 + fhip::INDEX_STEPS;
 const char *const kKernelNames[kNumKernels] = {"k_prepare", "k_autocorr", "k_lpc", "k_encode", "k_assemble",
                                                "k_order_search", "k_verify", "k_decode",
                                                // K8's launches, one name each (fhip::index_step_name without the <>)
                                                "k_index_count", "k_index_wgscan", "k_index_scatter", "k_index_walk",
-                                               "k_index_ranges", "k_index_emit"};
-constexpr int kProfVerify = 6, kProfDecode = 7, kProfIndex = 8;
+                                               "k_index_ranges", "k_index_emit", "k_gather_spans"};
+constexpr int kProfVerify = 6, kProfDecode = 7, kProfIndex = 8, kProfGather = 8 + fhip::INDEX_STEPS;
 
 int fail_hip(fhip_ctx *c, hipError_t e, const char *what)
 {
@@ -1493,6 +1497,105 @@ int fhip_frames_packed_begin_ragged(fhip_ctx *c, const fhip_batch *b, const int3
     return c->verify ? verify_verdict(c, vj) : FHIP_OK;
 }
 
+// ---- K9: gathering spans on the device ----------------------------------------------------------
+
+// The table's checks, all on the host: what the kernel is launched with has passed them.  *total = the samples per
+// channel the pieces cover.
+static int gather_check(fhip_ctx *c, int64_t dst_cap, const int32_t *src0, int64_t src0_cap, const int32_t *src1,
+                        int64_t src1_cap, const fhip_gather_piece *pieces, int npieces, long long *total)
+{
+    if (npieces < 0 || dst_cap < 0 || src0_cap < 0 || src1_cap < 0) return fail(c, FHIP_E_INVALID, "negative count");
+    if (npieces > 0 && !pieces) return fail(c, FHIP_E_INVALID, "null piece table");
+    if ((src0_cap > 0 && !src0) || (src1_cap > 0 && !src1)) return fail(c, FHIP_E_INVALID, "null source");
+    long long at = 0;
+    for (int i = 0; i < npieces; i++) {
+        const fhip_gather_piece &p = pieces[i];
+        if (p.src_buf != 0 && p.src_buf != 1) return fail(c, FHIP_E_INVALID, "piece: src_buf is 0 or 1");
+        if (p.count < 1) return fail(c, FHIP_E_INVALID, "piece: count must be at least 1");
+        if (p.dst != at) return fail(c, FHIP_E_INVALID, "pieces must be sorted by dst and tile the destination exactly");
+        const long long cap = p.src_buf ? src1_cap : src0_cap;
+        if (p.src < 0 || p.src > cap - p.count) return fail(c, FHIP_E_INVALID, "piece: source span outside its buffer");
+        at += p.count;
+        if (at > dst_cap) return fail(c, FHIP_E_INVALID, "pieces run past the destination's capacity");
+    }
+    *total = at;
+    return FHIP_OK;
+}
+
+// Upload the (checked) table and queue K9 on the handle's stream.
+static int run_gather(fhip_ctx *c, int32_t *dst, int64_t dst_cap, const int32_t *src0, int64_t src0_cap,
+                      const int32_t *src1, int64_t src1_cap, const fhip_gather_piece *pieces, int npieces, long long total)
+{
+    if (npieces == 0) return FHIP_OK;
+    HIP_TRY(c, c->d_gather.reserve((size_t)npieces));
+    // (from the handle's own image, as the ragged tables are: the caller's table is free when the call returns)
+    c->h_gather.assign(pieces, pieces + npieces);
+    HIP_TRY(c, hipMemcpyAsync(c->d_gather, c->h_gather.data(), (size_t)npieces * sizeof(fhip_gather_piece),
+                              hipMemcpyHostToDevice, c->stream));
+    const fhip::GatherArgs a{dst, dst_cap, src0, src0_cap, src1, src1_cap, c->d_gather, npieces, total, c->p.channels};
+    Prof pr(c, kProfGather, c->profiling);
+    HIP_TRY(c, fhip::launch_gather_spans(c->stream, a));
+    return FHIP_OK;
+}
+
+int fhip_gather_spans_dev(fhip_ctx *c, int32_t *dst, int64_t dst_cap, const int32_t *src0, int64_t src0_cap,
+                          const int32_t *src1, int64_t src1_cap, const fhip_gather_piece *pieces, int npieces)
+{
+    if (!c) return FHIP_E_INVALID;
+    c->launches.clear();
+    c->md5_log_entry = -1;
+    if (c->pcm_format == FHIP_PCM_S16) return fail(c, FHIP_E_UNSUPPORTED, "gathering takes int32 PCM only (FHIP_PCM_S16 is set)");
+    long long total = 0;
+    int rc = gather_check(c, dst_cap, src0, src0_cap, src1, src1_cap, pieces, npieces, &total);
+    if (rc != FHIP_OK) return rc;
+    if (total > 0 && !dst) return fail(c, FHIP_E_INVALID, "null destination");
+    LaunchScope ls(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    rc = run_gather(c, dst, dst_cap, src0, src0_cap, src1, src1_cap, pieces, npieces, total);
+    return rc;
+}
+
+int fhip_frames_packed_gather(fhip_ctx *c, const fhip_batch *b, const int32_t *block_sizes, const int32_t *src0,
+                              int64_t src0_cap, const int32_t *src1, int64_t src1_cap, const fhip_gather_piece *pieces,
+                              int npieces)
+{
+    long long want = 0;
+    int rc = block_sizes ? check_ragged(c, b, block_sizes, true, &want, true) : check_range(c, b, true, "null argument");
+    if (rc != FHIP_OK) return rc;
+    c->launches.clear();
+    c->md5_log_entry = -1;
+    if (c->pcm_format == FHIP_PCM_S16) return fail(c, FHIP_E_UNSUPPORTED, "gathering takes int32 PCM only (FHIP_PCM_S16 is set)");
+    if (!block_sizes) want = (long long)b->nframes * b->block_size;
+    long long total = 0;
+    const int64_t room = (int64_t)c->max_frames * c->p.block_size;
+    rc = gather_check(c, room, src0, src0_cap, src1, src1_cap, pieces, npieces, &total);
+    if (rc != FHIP_OK) return rc;
+    if (total != want) return fail(c, FHIP_E_INVALID, "the pieces do not cover exactly the batch's samples");
+    c->uploaded_pcm = nullptr;
+    if (b->nframes == 0) return FHIP_OK;
+    LaunchScope ls(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int64_t stride = fhip_frame_stride(&c->p, block_sizes ? c->p.block_size : b->block_size);
+    rc = ensure_staging(c, (size_t)b->nframes * c->p.channels * (size_t)((stride + 3) & ~(int64_t)3));
+    if (rc != FHIP_OK) return rc;
+    // what stage_pcm does before it writes the staging PCM: an MD5 update that still reads it finishes first
+    if (c->md5_up_pending) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_md5_up, 0));
+    rc = run_gather(c, c->d_pcm, room, src0, src0_cap, src1, src1_cap, pieces, npieces, total);
+    if (rc != FHIP_OK) return rc;
+    if (block_sizes) {
+        rc = upload_ragged_tables(c, block_sizes, b->nframes);
+        if (rc != FHIP_OK) return rc;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->md5_up_pending = false;               // (the stream waited for it)
+    c->uploaded_pcm = b->pcm;
+    c->uploaded_vals = (size_t)total * (size_t)c->p.channels;
+    c->uploaded_frames = b->nframes;
+    c->uploaded_n = block_sizes ? -1 : b->block_size;
+    if (block_sizes) c->uploaded_sizes.assign(block_sizes, block_sizes + b->nframes);
+    return FHIP_OK;
+}
+
 // ---- K6: the MD5 of many streams ----------------------------------------------------------------
 // The *_dev entries run on the caller's stream, fhip_md5_update_uploaded on md5_stream; each side waits for the
 // other's last launch, so updates of the same states run in call order whichever entries make them.
@@ -2644,11 +2747,15 @@ int fhip_decode_frames(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_
 // The host form, with and without segments.  The segment tables travel in one block of the handle's (d_dseg): the
 // 8-byte ones first -- seg_number, seg_start, seg_samples -- then seg_first, seg_variable, seg_failed and, with md5, K6's
 // CSR (md5_first [nstreams + 1], md5_range [nsegs]), which is built here.
-int fhip_decode_frames_segments(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
-                                const fhip_decode_out *out, const fhip_decode_md5 *md5)
+// keep: out->pcm is DEVICE memory that K7 writes and K6 reads where it lies; nothing of it is downloaded
+// (fhip_decode_frames_segments_keep).
+static int decode_segments_host(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
+                                const fhip_decode_out *out, const fhip_decode_md5 *md5, bool keep)
 {
     int rc = decode_check(c, in, out, segs);
     if (rc != FHIP_OK) return rc;
+    if (keep && c->pcm_format == FHIP_PCM_S16)
+        return fail(c, FHIP_E_UNSUPPORTED, "keeping the PCM on the device takes int32 PCM only (FHIP_PCM_S16 is set)");
     if (md5 && !segs) return fail(c, FHIP_E_INVALID, "md5 needs a segment table");
     const size_t ns = segs ? (size_t)segs->nsegs : 0, nst = md5 ? (size_t)(md5->nstreams > 0 ? md5->nstreams : 0) : 0;
     if (segs) {
@@ -2683,13 +2790,14 @@ int fhip_decode_frames_segments(fhip_ctx *c, const fhip_decode_in *in, const fhi
     const size_t nv = (size_t)cap * (size_t)c->p.channels;
     HIP_TRY(c, c->d_vstream.reserve(sb));
     HIP_TRY(c, c->d_vfb.reserve(nf));
-    HIP_TRY(c, c->d_vpcm.reserve(nv));
+    if (!keep) HIP_TRY(c, c->d_vpcm.reserve(nv));
+    int32_t *const dpcm = keep ? out->pcm : c->d_vpcm.get();
     if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_vstream, in->stream, sb, hipMemcpyHostToDevice, c->stream));
     if (nf) HIP_TRY(c, hipMemcpyAsync(c->d_vfb, in->frame_bytes, nf * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     fhip_decode_in din = *in;
     din.stream = c->d_vstream; din.frame_bytes = c->d_vfb;
     // summary [0..4), K7's key scratch [4], the sample count [5], the end of what was written [6]
-    fhip_decode_out dout{c->d_vpcm, cap, c->d_vrec, reinterpret_cast<int64_t *>(c->d_vsum.get()),
+    fhip_decode_out dout{dpcm, cap, c->d_vrec, reinterpret_cast<int64_t *>(c->d_vsum.get()),
                          reinterpret_cast<int64_t *>(c->d_vsum.get() + 5)};
     fhip_decode_segments dsegs{};
     int32_t *d_i32 = nullptr;
@@ -2724,7 +2832,7 @@ int fhip_decode_frames_segments(fhip_ctx *c, const fhip_decode_in *in, const fhi
     if (md5) {
         // the hash reads the PCM where K7 left it and the ranges K7 named, behind it on the same stream
         if ((rc = md5_dev_begin(c)) != FHIP_OK) return rc;
-        rc = md5_ranges(c, md5->states, md5->nstreams, c->d_vpcm, d_i32 + 3 * ns + 1, d_i32 + 3 * ns + 1 + nst + 1,
+        rc = md5_ranges(c, md5->states, md5->nstreams, dpcm, d_i32 + 3 * ns + 1, d_i32 + 3 * ns + 1 + nst + 1,
                         dsegs.seg_start, dsegs.seg_samples);
         if (rc != FHIP_OK) return rc;
         if ((rc = md5_dev_end(c)) != FHIP_OK) return rc;
@@ -2743,7 +2851,7 @@ int fhip_decode_frames_segments(fhip_ctx *c, const fhip_decode_in *in, const fhi
     // the samples, up to the end of the last frame that was placed and written: nothing behind it is touched (a frame
     // refused for pcm_cap leaves the caller's buffer as it was); a failed frame before it leaves its own range unspecified
     const long long wend = sum[6] < cap ? sum[6] : cap;
-    if (wend > 0) {
+    if (wend > 0 && !keep) {
         HIP_TRY(c, hipMemcpyAsync(out->pcm, c->d_vpcm, (size_t)wend * (size_t)c->p.channels * c->pcm_width(),
                                   hipMemcpyDeviceToHost, c->stream));
         rc = fhip_sync(c);
@@ -2762,6 +2870,18 @@ int fhip_decode_frames_segments(fhip_ctx *c, const fhip_decode_in *in, const fhi
              sum[1], sum[0], sum[2], verify_status_name((int)sum[3]), r.subframe, r.bit);
     c->err = buf;
     return FHIP_E_VERIFY;
+}
+
+int fhip_decode_frames_segments(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
+                                const fhip_decode_out *out, const fhip_decode_md5 *md5)
+{
+    return decode_segments_host(c, in, segs, out, md5, false);
+}
+
+int fhip_decode_frames_segments_keep(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
+                                     const fhip_decode_out *out, const fhip_decode_md5 *md5)
+{
+    return decode_segments_host(c, in, segs, out, md5, true);
 }
 
 // ---- K8: frame discovery ---------------------------------------------------------------------------

@@ -429,4 +429,20 @@ int index_nwg(long long stream_bytes);
 void index_geometry(int *lane_bytes, int *wg_bytes, int *end_lane_bytes, int *xinv8);
 hipError_t launch_index_step(hipStream_t st, const IndexArgs &a, int step);
 
+// K9 (k9_gather.hip): spans of channel-interleaved int32 samples from up to two sources into one destination.  One
+// launch on st, a workgroup per GATHER_TILE_VALS interleaved values of the destination (4 KiB).  pieces is a DEVICE
+// table, sorted by dst and tiling [0, total); every read of it is clamped to [0, npieces), every source read into
+// [0, srcN_cap) and every write below min(total, dst_cap) samples, whatever it holds.
+using GatherPiece = fhip_gather_piece;
+struct GatherArgs {
+    int32_t *dst; long long dst_cap;             // capacities in samples per channel
+    const int32_t *src0; long long src0_cap;
+    const int32_t *src1; long long src1_cap;
+    const GatherPiece *pieces; int npieces;
+    long long total;                             // the samples per channel the table covers
+    int channels;
+};
+constexpr int GATHER_TILE_VALS = 1024;
+hipError_t launch_gather_spans(hipStream_t st, const GatherArgs &a);
+
 }  // namespace fhip

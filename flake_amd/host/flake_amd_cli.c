@@ -33,6 +33,15 @@
  * first's is an error that names it.  A file that fails is named on stderr and makes the exit status non-zero; the other
  * files are still written in full.
  *
+ *   flake_amd_cli [-0..-12] [-b blocksize] --recode --set OUTDIR [--verify] a.flac b.flac ...
+ *
+ * --recode --set re-encodes FLAC files of one format at another level through one recode set (flake_amd_recode_set_*):
+ * frames found as in --decode --set, decoded, re-cut into the new block size and encoded without the samples leaving
+ * the device.  OUTDIR/<name>.flac is "fLaC" + the new STREAMINFO + frames, as the encoder writes it; other metadata
+ * blocks are NOT carried over.  A file whose decode fails, or whose digest differs from a non-zero source digest, is
+ * named on stderr, gets no output (one left by an earlier run is removed) and makes the exit status non-zero; the
+ * other files are written.  --verify turns the recode set's on-device verification on.
+ *
  * Only canonical PCM WAV (8/16/24/32 bit) is read; this is a harness for the
  * host API, not a replacement for the reference's libpcm_io.
  */
@@ -701,12 +710,221 @@ out:
     return rc;
 }
 
+/* ---- --recode --set: many FLAC files of one format re-encoded through one recode set ---- */
+#define RECODE_USAGE "usage: %s [-0..-12] [-b blocksize] --recode --set OUTDIR [--verify] a.flac b.flac ...\n" \
+                     "       (files of one format; only STREAMINFO is written: other metadata blocks are not carried over)\n"
+
+static int run_recode_set(const char *outdir, char **inputs, int n, int level, int bsize, int verify)
+{
+    if (n < 1) { fprintf(stderr, "--recode --set needs input files\n"); return 2; }
+    dset_file *fs = (dset_file *)calloc((size_t)n, sizeof *fs);
+    bytes_t *outs = (bytes_t *)calloc((size_t)n, sizeof *outs);
+    if (!fs || !outs) { free(fs); free(outs); return 1; }
+    int rc = 0, ref = -1;
+    unsigned maxn = 16;
+    int *sor = NULL, *fof = NULL, *csz = NULL, *bstream = NULL, *bbytes = NULL;
+    uint8_t *bytes = NULL, *obuf = NULL, *header = NULL;
+    size_t bytes_cap = 0, obuf_cap = 0;
+    int bcap = 0, hlen = 0;
+    FlakeAmdDecodeSet *ix = NULL;
+    FlakeAmdRecodeSet *g = NULL;
+    for (int i = 0; i < n; i++) {
+        dset_file *f = &fs[i];
+        f->path = inputs[i];
+        if (dset_load(f)) { f->bad = f->skip = 1; rc = 1; continue; }
+        if (ref < 0) ref = i;
+        if (f->si.channels != fs[ref].si.channels || f->si.bits_per_sample != fs[ref].si.bits_per_sample ||
+            f->si.sample_rate != fs[ref].si.sample_rate) {
+            fprintf(stderr, "%s: its format (%u channels, %u bits, %u Hz) differs from %s's: a recode set takes one format\n",
+                    f->path, f->si.channels, f->si.bits_per_sample, f->si.sample_rate, fs[ref].path);
+            rc = 1;
+            goto out;
+        }
+        const unsigned mb = f->si.max_block_size ? f->si.max_block_size : 65535u;
+        if (mb > maxn) maxn = mb;
+        const char *base = strrchr(f->path, '/');
+        base = base ? base + 1 : f->path;
+        const char *dot = strrchr(base, '.');
+        snprintf(f->name, sizeof f->name, "%s/%.*s.flac", outdir, (int)(dot ? dot - base : (long)strlen(base)), base);
+        for (int j = 0; j < i; j++)
+            if (!fs[j].skip && !strcmp(fs[j].name, f->name)) {
+                fprintf(stderr, "%s and %s would both be written to %s\n", fs[j].path, f->path, f->name);
+                rc = 1;
+                goto out;
+            }
+    }
+    if (ref < 0) { rc = 1; goto out; }
+    FlakeAmdStreaminfo like = fs[ref].si;
+    like.max_block_size = maxn;
+    /* the encoder's parameters, and the stream header of the single-input form with STREAMINFO rewritten per file */
+    FlakeAmdContext s;
+    memset(&s, 0, sizeof s);
+    s.channels = (int)like.channels; s.sample_rate = (int)like.sample_rate; s.bits_per_sample = (int)like.bits_per_sample;
+    s.params.compression = level;
+    if (flake_amd_set_defaults(&s.params)) { rc = 1; goto out; }
+    if (bsize > 0) s.params.block_size = bsize;
+    if (flake_amd_validate_params(&s) < 0) { fprintf(stderr, "invalid parameters\n"); rc = 1; goto out; }
+    hlen = flake_amd_encode_init(&s);
+    if (hlen < 0) { fprintf(stderr, "encoder init failed (%d)\n", hlen); rc = 1; goto out; }
+    header = (uint8_t *)malloc((size_t)hlen);
+    if (header) memcpy(header, s.header, (size_t)hlen);
+    flake_amd_encode_close(&s);
+    if (!header) { rc = 1; goto out; }
+    /* the frames of every file, found on the device (K8) through a decode set's handle; on the CPU with
+     * FLAKE_AMD_INDEX_HOST=1 or where the device cannot answer */
+    if (!index_on_host()) ix = flake_amd_decode_set_open(&like, 1, FLAKE_AMD_SET_MD5_OFF);
+    for (int i = 0; i < n; i++) {
+        dset_file *f = &fs[i];
+        if (f->skip) continue;
+        const size_t left = f->len - f->pos;
+        const int cap = (int)(left / 8 + 2);
+        size_t used = 0;
+        f->sizes = (int *)malloc(sizeof(int) * (size_t)cap);
+        f->own_sizes = 1;
+        if (!f->sizes) { fprintf(stderr, "out of memory\n"); rc = 1; goto out; }
+        const size_t first[2] = {0, left};
+        long long nf = -1;
+        if (!ix || left >= ((size_t)1 << 31) ||
+            flake_amd_decode_set_index(ix, f->si.max_block_size, f->file + f->pos, first, 1, f->sizes, cap, &nf, &used) != 0)
+            nf = flake_amd_index_frames(&f->si, f->file + f->pos, left, f->sizes, cap, &used);
+        f->nframes = nf;
+        if (nf < 0 || used != left) {
+            fprintf(stderr, "%s: frame %lld (at byte %llu): %s\n", f->path, nf < 0 ? 0ll : nf, (unsigned long long)(f->pos + used),
+                    nf < 0 ? "not a frame header of this stream" : "the frame is cut or its CRC-16 fails");
+            f->bad = 1;
+            rc = 1;
+            if (nf < 0) f->nframes = 0;
+        }
+    }
+    if (ix) { flake_amd_decode_set_close(ix); ix = NULL; }
+    g = flake_amd_recode_set_open(&like, &s, n, s.params.variable_block_size ? FLAKE_AMD_SET_VBS : 0);
+    if (!g) { fprintf(stderr, "recode set init failed: %s\n", flake_amd_recode_set_last_error(NULL)); rc = 1; goto out; }
+    if (verify && flake_amd_recode_set_enable_verify(g, 1)) { fprintf(stderr, "cannot turn verification on\n"); rc = 1; goto out; }
+    int per = (int)((4u << 20) / maxn / (unsigned)n);
+    if (per > 64) per = 64;
+    if (per < 1) per = 1;
+    sor = (int *)malloc(sizeof(int) * (size_t)n);
+    fof = (int *)malloc(sizeof(int) * (size_t)n);
+    csz = (int *)malloc(sizeof(int) * (size_t)n * (size_t)per);
+    if (!sor || !fof || !csz) { fprintf(stderr, "out of memory\n"); rc = 1; goto out; }
+    for (int last = 0; !last;) {
+        int nruns = 0, nfr = 0, nb = 0;
+        size_t nbytes = 0;
+        for (int i = 0; i < n; i++) {
+            dset_file *f = &fs[i];
+            if (f->skip || f->next >= f->nframes || flake_amd_recode_set_failed(g, i, NULL, NULL) == 1) continue;
+            const int take = f->nframes - f->next < per ? (int)(f->nframes - f->next) : per;
+            size_t rb = 0;
+            for (int k = 0; k < take; k++) { csz[nfr++] = f->sizes[f->next + k]; rb += (size_t)f->sizes[f->next + k]; }
+            if (nbytes + rb > bytes_cap) {
+                uint8_t *more = (uint8_t *)realloc(bytes, (nbytes + rb) * 2);
+                if (!more) { fprintf(stderr, "out of memory\n"); rc = 1; goto out; }
+                bytes = more;
+                bytes_cap = (nbytes + rb) * 2;
+            }
+            memcpy(bytes + nbytes, f->file + f->pos, rb);
+            nbytes += rb;
+            f->pos += rb;
+            f->next += take;
+            sor[nruns] = i;
+            fof[nruns++] = take;
+        }
+        last = !nruns;                     /* no frames left: the tails */
+        size_t need = 0;
+        long long need_blocks = 0;
+        flake_amd_recode_set_out_bound(g, last ? -1 : nfr, &need, &need_blocks);
+        if (need > obuf_cap || need_blocks > bcap) {
+            free(obuf); free(bstream); free(bbytes);
+            obuf_cap = need + 65536;
+            bcap = (int)need_blocks + 1024;
+            obuf = (uint8_t *)malloc(obuf_cap);
+            bstream = (int *)malloc(sizeof(int) * (size_t)bcap);
+            bbytes = (int *)malloc(sizeof(int) * (size_t)bcap);
+            if (!obuf || !bstream || !bbytes) { fprintf(stderr, "out of memory\n"); rc = 1; goto out; }
+        }
+        const long long w = last ? flake_amd_recode_set_finish(g, obuf, obuf_cap, bstream, bbytes, bcap, &nb)
+                                 : flake_amd_recode_set_frames(g, nruns, sor, fof, bytes, nbytes, csz, obuf, obuf_cap, bstream,
+                                                               bbytes, bcap, &nb);
+        if (w < 0) { fprintf(stderr, "recode error: %s\n", flake_amd_recode_set_last_error(g)); rc = 1; goto out; }
+        size_t at = 0;
+        for (int b = 0; b < nb; b++) {
+            if (bytes_add(&outs[bstream[b]], obuf + at, (size_t)bbytes[b])) { fprintf(stderr, "out of memory\n"); rc = 1; goto out; }
+            at += (size_t)bbytes[b];
+        }
+    }
+    for (int i = 0; i < n; i++) {
+        dset_file *f = &fs[i];
+        if (f->skip) continue;
+        long long fr = -1;
+        int st = 0;
+        FlakeAmdStreaminfo si;
+        static const uint8_t zero[16] = {0};
+        memset(&si, 0, sizeof si);
+        if (flake_amd_recode_set_failed(g, i, &fr, &st) == 1) {
+            fprintf(stderr, "%s: frame %lld does not decode (status %d)\n", f->path, fr, st);
+            f->bad = 1;
+        } else if (!f->bad && flake_amd_recode_set_get_streaminfo(g, i, &si)) {
+            fprintf(stderr, "%s: %s\n", f->path, flake_amd_recode_set_last_error(g));
+            f->bad = 1;
+        } else if (!f->bad && memcmp(f->si.md5sum, zero, 16) && memcmp(f->si.md5sum, si.md5sum, 16)) {
+            fprintf(stderr, "%s: MD5 mismatch: the decoded samples are not what STREAMINFO's signature was made of\n", f->path);
+            f->bad = 1;
+        } else if (!f->bad && f->si.samples && f->si.samples != si.samples) {
+            fprintf(stderr, "%s: %u samples decoded, STREAMINFO says %u\n", f->path, si.samples, f->si.samples);
+            f->bad = 1;
+        }
+        if (f->bad) {
+            /* named above; it gets no output, and one from an earlier run does not stay in its place */
+            remove(f->name);
+            rc = 1;
+            continue;
+        }
+        flake_amd_write_streaminfo(&si, header + 8);
+        FILE *fo = fopen(f->name, "wb");
+        if (!fo) { perror(f->name); rc = 1; continue; }
+        fwrite(header, 1, (size_t)hlen, fo);
+        fwrite(outs[i].p, 1, outs[i].n, fo);
+        fclose(fo);
+        fprintf(stderr, "%s: %u sample-frames -> %llu bytes\n", f->path, si.samples, (unsigned long long)hlen + outs[i].n);
+    }
+    {
+        long long db = 0, eb = 0;
+        flake_amd_recode_set_device_batches(g, &db, &eb);
+        fprintf(stderr, "%lld decode batches, %lld encode batches\n", db, eb);
+    }
+out:
+    if (ix) flake_amd_decode_set_close(ix);
+    if (g) flake_amd_recode_set_close(g);
+    for (int i = 0; i < n; i++) free(outs[i].p);
+    free(outs); free(sor); free(fof); free(csz); free(bstream); free(bbytes); free(bytes); free(obuf); free(header);
+    dset_free(fs, n);
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
     FlakeAmdContext s;
     memset(&s, 0, sizeof s);
     int level = 5, bsize = -1, synth = 0, channels = 2, bps = 16, verify = 0, synth_streams = 0;
     const char *in = NULL, *out = NULL, *setdir = NULL;
+    for (int i = 1; i < argc; i++) {
+        if (strcmp(argv[i], "--recode")) continue;
+        /* --recode --set OUTDIR a.flac b.flac ...: everything that is neither switch nor OUTDIR is an input */
+        char **inputs = (char **)calloc((size_t)argc, sizeof(char *));
+        int ninputs = 0;
+        for (int k = 1; k < argc && inputs; k++) {
+            if (k == i) continue;
+            if (argv[k][0] == '-' && argv[k][1] >= '0' && argv[k][1] <= '9') level = atoi(argv[k] + 1);
+            else if (!strcmp(argv[k], "-b") && k + 1 < argc) bsize = atoi(argv[++k]);
+            else if (!strcmp(argv[k], "--set") && k + 1 < argc) setdir = argv[++k];
+            else if (!strcmp(argv[k], "--verify")) verify = 1;
+            else inputs[ninputs++] = argv[k];
+        }
+        if (!inputs || !setdir || !ninputs) { fprintf(stderr, RECODE_USAGE, argv[0]); free(inputs); return 2; }
+        const int rcs = run_recode_set(setdir, inputs, ninputs, level, bsize, verify);
+        free(inputs);
+        return rcs;
+    }
     for (int i = 1; i < argc; i++) {
         if (strcmp(argv[i], "--decode")) continue;
         for (int j = 1; j + 1 < argc; j++) {
@@ -759,6 +977,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "usage: %s [-0..-12] [-b blocksize] [--verify] (in.wav | --synth FRAMES [--channels C] [--bps B]) out.flac\n"
                         "       %s [-0..-12] [-b blocksize] --set OUTDIR [--verify] (in1.wav in2.wav ... | --synth-streams S --synth FRAMES [--channels C] [--bps B])\n",
                 argv[0], argv[0]);
+        fprintf(stderr, RECODE_USAGE, argv[0]);
         return 2;
     }
     wav_t w;

@@ -36,6 +36,8 @@ struct FlakeAmdDecodeSet {
     fa_ds_batch b;                /* the planner's tables and the device's answers, max_batch entries each */
     int64_t *seg_start, *seg_samples;
     int32_t *seg_failed;
+    unsigned char *seg_ok;        /* what the set made of each segment of the batch (the keep form's consumer reads it) */
+    int max_block;                /* the handle's largest block */
     fhip_verify_rec *recs;
     long long *run_off;           /* the last call's run offsets in pcm */
     int run_off_cap, run_off_n;
@@ -79,6 +81,7 @@ FLAKE_AMD_API FlakeAmdDecodeSet *flake_amd_decode_set_open(const FlakeAmdStreami
     fhip_params p;
     memset(&p, 0, sizeof p);
     p.channels = (int)like->channels; p.sample_rate = (int)like->sample_rate; p.bits_per_sample = (int)like->bits_per_sample;
+    g->max_block = bs;
     p.block_size = bs; p.order_method = 1; p.stereo_method = 1; p.prediction_type = 2;
     p.min_prediction_order = 1; p.max_prediction_order = 8; p.min_partition_order = 0; p.max_partition_order = 5;
     p.lpc_precision = 15;
@@ -102,9 +105,10 @@ FLAKE_AMD_API FlakeAmdDecodeSet *flake_amd_decode_set_open(const FlakeAmdStreami
     g->seg_samples = (int64_t *)calloc(mb, sizeof(int64_t));
     g->seg_failed = (int32_t *)calloc(mb, sizeof(int32_t));
     g->recs = (fhip_verify_rec *)calloc(mb, sizeof(fhip_verify_rec));
+    g->seg_ok = (unsigned char *)calloc(mb, 1);
     const int have = g->st && g->sx && g->digests && b->seg_first && b->seg_number && b->seg_variable && b->seg_stream &&
                      b->seg_run && b->seg_frame0 && b->seg_prev && b->md5_first && b->md5_range && b->last_seg &&
-                     b->planned && g->seg_start && g->seg_samples && g->seg_failed && g->recs;
+                     b->planned && g->seg_start && g->seg_samples && g->seg_failed && g->recs && g->seg_ok;
     int rc = have ? fhip_create(&g->hip, ed ? atoi(ed) : 0, &p, g->max_batch) : FHIP_E_NOMEM;
     if (rc == FHIP_OK && ds_device_md5(g)) {
         g->states = (fhip_md5_state *)fhip_device_alloc(ns * sizeof(fhip_md5_state));
@@ -128,10 +132,11 @@ static void ds_fail_stream(FlakeAmdDecodeSet *g, int s, long long frame, int sta
     g->sx[s].fail_status = status;
 }
 
-FLAKE_AMD_API long long flake_amd_decode_set_frames(FlakeAmdDecodeSet *g, int nruns, const int *stream_of_run,
-                                                    const int *frames_of_run, const unsigned char *stream, size_t bytes,
-                                                    const int *frame_sizes, void *pcm, int sample_bytes,
-                                                    size_t pcm_cap_samples, long long *run_samples)
+/* keep_fn: the keep-on-device destination (fa_decode_set_frames_keep) -- pcm is device memory that every batch decodes
+ * to from its start, and each batch is handed to keep_fn once its segments are judged. */
+static long long ds_frames(FlakeAmdDecodeSet *g, int nruns, const int *stream_of_run, const int *frames_of_run,
+                           const unsigned char *stream, size_t bytes, const int *frame_sizes, void *pcm, int sample_bytes,
+                           size_t pcm_cap_samples, long long *run_samples, fa_ds_batch_fn keep_fn, void *keep_user)
 {
     if (!g) return -1;
     g->err[0] = 0;
@@ -203,12 +208,14 @@ FLAKE_AMD_API long long flake_amd_decode_set_frames(FlakeAmdDecodeSet *g, int nr
         fhip_decode_out out = {(int32_t *)((char *)pcm + base * nch * (size_t)sample_bytes),
                                (int64_t)(pcm_cap_samples - base), g->recs, summary, &nsmp};
         fhip_decode_md5 md = {g->states, g->nstreams, b->seg_stream};
-        const int rc = fhip_decode_frames_segments(g->hip, &in, &sg, &out, ds_device_md5(g) ? &md : NULL);
+        const int rc = keep_fn ? fhip_decode_frames_segments_keep(g->hip, &in, &sg, &out, ds_device_md5(g) ? &md : NULL)
+                               : fhip_decode_frames_segments(g->hip, &in, &sg, &out, ds_device_md5(g) ? &md : NULL);
         g->device_batches++;
         if (rc != FHIP_OK && rc != FHIP_E_VERIFY) {
             snprintf(g->err, sizeof g->err, "fhip_decode_frames_segments: %s", fhip_last_error(g->hip));
             return -1;
         }
+        memset(g->seg_ok, 0, (size_t)b->nsegs);
         /* the batch's segments in order: a good one commits its stream, a bad one fails it */
         size_t extent = 0;
         size_t hdr_at = b->byte0;
@@ -244,6 +251,7 @@ FLAKE_AMD_API long long flake_amd_decode_set_frames(FlakeAmdDecodeSet *g, int nr
                 run_samples[r] = -1;
                 continue;
             }
+            g->seg_ok[k] = 1;
             const size_t at = base + (size_t)g->seg_start[k], n = (size_t)g->seg_samples[k];
             if (b->seg_frame0[k] == 0) g->run_off[r] = (long long)at;
             if (g->flags & FLAKE_AMD_SET_MD5_HOST) {
@@ -255,6 +263,13 @@ FLAKE_AMD_API long long flake_amd_decode_set_frames(FlakeAmdDecodeSet *g, int nr
             run_samples[r] += (long long)n;
             if (at + n - base > extent) extent = at + n - base;
         }
+        if (keep_fn) {
+            if (keep_fn(keep_user, b->nsegs, b->seg_stream, g->seg_start, g->seg_samples, g->seg_ok) < 0) {
+                if (!g->err[0]) snprintf(g->err, sizeof g->err, "the batch's consumer failed");
+                return -1;
+            }
+            continue;                                 /* (the next batch decodes to the buffer's start again) */
+        }
         base += extent;
     }
     for (int r = 0; r < nruns; r++)
@@ -262,6 +277,32 @@ FLAKE_AMD_API long long flake_amd_decode_set_frames(FlakeAmdDecodeSet *g, int nr
     (void)total_frames;
     return total;
 }
+
+FLAKE_AMD_API long long flake_amd_decode_set_frames(FlakeAmdDecodeSet *g, int nruns, const int *stream_of_run,
+                                                    const int *frames_of_run, const unsigned char *stream, size_t bytes,
+                                                    const int *frame_sizes, void *pcm, int sample_bytes,
+                                                    size_t pcm_cap_samples, long long *run_samples)
+{
+    return ds_frames(g, nruns, stream_of_run, frames_of_run, stream, bytes, frame_sizes, pcm, sample_bytes, pcm_cap_samples,
+                     run_samples, NULL, NULL);
+}
+
+long long fa_decode_set_frames_keep(FlakeAmdDecodeSet *g, int nruns, const int *stream_of_run, const int *frames_of_run,
+                                    const unsigned char *stream, size_t bytes, const int *frame_sizes, int32_t *dev_pcm,
+                                    size_t dev_cap_samples, long long *run_samples, fa_ds_batch_fn fn, void *user)
+{
+    if (!g || !fn) return -1;
+    if (g->flags & FLAKE_AMD_SET_MD5_HOST) {
+        snprintf(g->err, sizeof g->err, "FLAKE_AMD_SET_MD5_HOST has no samples to hash when they stay on the device");
+        return -1;
+    }
+    return ds_frames(g, nruns, stream_of_run, frames_of_run, stream, bytes, frame_sizes, dev_pcm, 4, dev_cap_samples,
+                     run_samples, fn, user);
+}
+
+size_t fa_decode_set_batch_samples(const FlakeAmdDecodeSet *g) { return (size_t)g->max_batch * (size_t)g->max_block; }
+int fa_decode_set_max_batch(const FlakeAmdDecodeSet *g) { return g->max_batch; }
+int fa_decode_set_max_block(const FlakeAmdDecodeSet *g) { return g->max_block; }
 
 FLAKE_AMD_API int flake_amd_decode_set_run_offsets(const FlakeAmdDecodeSet *g, long long *offsets, int cap)
 {
@@ -335,7 +376,7 @@ FLAKE_AMD_API void flake_amd_decode_set_close(FlakeAmdDecodeSet *g)
     fa_ds_batch *b = &g->b;
     free(b->seg_first); free(b->seg_number); free(b->seg_variable); free(b->seg_stream); free(b->seg_run);
     free(b->seg_frame0); free(b->seg_prev); free(b->md5_first); free(b->md5_range); free(b->last_seg); free(b->planned);
-    free(g->seg_start); free(g->seg_samples); free(g->seg_failed); free(g->recs); free(g->run_off);
+    free(g->seg_start); free(g->seg_samples); free(g->seg_failed); free(g->recs); free(g->seg_ok); free(g->run_off);
     free(g->st); free(g->sx); free(g->digests);
     free(g);
 }

@@ -28,6 +28,7 @@
 #include "flake_amd.h"
 #include "flakehip.h"
 #include "host_internal.h"
+#include "recode_plan.h"
 
 struct FlakeAmdSet {
     fhip_ctx *hip;
@@ -229,9 +230,23 @@ static long long set_verify_failed(FlakeAmdSet *g, const char *what, const int *
              verify_status_name(vr.status), vr.subframe, vr.sample, vr.bit);
 }
 
-FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples, int sample_bytes, int nblocks,
-                                             int block_size, const int *stream_of_block, unsigned char *out,
-                                             size_t out_size, int *frame_sizes)
+/* The upload step of a chunk, or its stand-in for a call whose samples are gather pieces (fa_set_source): the chunk is
+ * samples lo .. hi of the call; bt->pcm is then a token that names the batch. */
+static int set_bring(FlakeAmdSet *g, fa_set_source *src, const fhip_batch *bt, const int32_t *sizes, long long lo,
+                     long long hi, const char **what)
+{
+    if (!src) {
+        *what = sizes ? "fhip_frames_packed_upload_ragged" : "fhip_frames_packed_upload";
+        return sizes ? fhip_frames_packed_upload_ragged(g->hip, bt, sizes) : fhip_frames_packed_upload(g->hip, bt);
+    }
+    *what = "fhip_frames_packed_gather";
+    const int m = fa_rc_slice(src->pieces, src->npieces, &src->cur, lo, hi, src->work);
+    return fhip_frames_packed_gather(g->hip, bt, sizes, src->src0, src->src0_cap, src->src1, src->src1_cap, src->work, m);
+}
+
+static long long set_encode(FlakeAmdSet *g, fa_set_source *src, const void *samples, int sample_bytes, int nblocks,
+                            int block_size, const int *stream_of_block, unsigned char *out, size_t out_size,
+                            int *frame_sizes)
 {
     if (!g) return -1;
     g->err[0] = 0;
@@ -286,8 +301,7 @@ FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples
         bt.nframes = cnt; bt.block_size = block_size;
         bt.frame_bytes = g->fbytes + b0;
         bt.frame_numbers = g->fnum + b0;
-        what = "fhip_frames_packed_upload";
-        rc = fhip_frames_packed_upload(g->hip, &bt);
+        rc = set_bring(g, src, &bt, NULL, (long long)b0 * block_size, (long long)(b0 + cnt) * block_size, &what);
         if (rc == FHIP_OK && g->dev_md5) {
             /* the chunk's blocks per stream, in batch order (CSR), for the hash that runs beside the encode kernels */
             int *first = g->scratch;
@@ -359,15 +373,24 @@ FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples
     return total;
 }
 
+FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples, int sample_bytes, int nblocks,
+                                             int block_size, const int *stream_of_block, unsigned char *out,
+                                             size_t out_size, int *frame_sizes)
+{
+    return set_encode(g, NULL, samples, sample_bytes, nblocks, block_size, stream_of_block, out, out_size, frame_sizes);
+}
+
 /* The short blocks of a call through the ragged packed path: cnt blocks back to back, block b sizes[b] samples long
  * (every one shorter than the set's block size, one per stream: the caller has checked).  The twin of the loop in
  * flake_amd_set_encode.  With variable block size the chunk goes through fhip_encode_blocks_vbs_ragged_numbered
  * instead: a block may become several frames, is numbered from its stream's sample count and ends nothing
  * (encode.c:993); the bytes come back before the call returns, as on that path of flake_amd_set_encode.  Returns the bytes written, -1 on an error, or -2 when the ABI does not cover this handle
  * (FHIP_E_UNSUPPORTED on the first chunk: nothing has changed, the caller takes the per-length calls). */
-static long long set_encode_short(FlakeAmdSet *g, const void *samples, int sample_bytes, int cnt_all, const int *sizes,
-                                  const int *stream_of_block, unsigned char *out, size_t out_size, int *frame_sizes)
+static long long set_encode_short(FlakeAmdSet *g, fa_set_source *src, const void *samples, int sample_bytes, int cnt_all,
+                                  const int *sizes, const int *stream_of_block, unsigned char *out, size_t out_size,
+                                  int *frame_sizes)
 {
+    long long done_samples = 0;           /* of the chunks before this one */
     if (grow_call_tables(g, cnt_all)) SET_FAIL("flake_amd_set_encode_ragged: out of host memory");
     const int fmt = sample_bytes == 2 ? FHIP_PCM_S16 : FHIP_PCM_S32;
     if (fmt != g->pcm_format) {
@@ -395,8 +418,8 @@ static long long set_encode_short(FlakeAmdSet *g, const void *samples, int sampl
         bt.nframes = cnt; bt.block_size = largest;
         bt.frame_bytes = g->fbytes + b0;
         bt.frame_numbers = g->fnum + b0;
-        what = "fhip_frames_packed_upload_ragged";
-        rc = fhip_frames_packed_upload_ragged(g->hip, &bt, (const int32_t *)(sizes + b0));
+        rc = set_bring(g, src, &bt, (const int32_t *)(sizes + b0), done_samples, done_samples + (long long)chunk_samples, &what);
+        done_samples += (long long)chunk_samples;
         if (rc == FHIP_E_UNSUPPORTED && b0 == 0) return -2;
         if (rc == FHIP_OK && g->dev_md5) {
             int *first = g->scratch;
@@ -509,7 +532,7 @@ FLAKE_AMD_API long long flake_amd_set_encode_ragged(FlakeAmdSet *g, const void *
     const char *er = getenv("FLAKE_AMD_SET_RAGGED");
     int ragged = !(er && er[0] == '0');
     if (ragged && nshort == nblocks) {
-        const long long r = set_encode_short(g, samples, sample_bytes, nblocks, block_sizes, stream_of_block, out, out_size, frame_sizes);
+        const long long r = set_encode_short(g, NULL, samples, sample_bytes, nblocks, block_sizes, stream_of_block, out, out_size, frame_sizes);
         if (r != -2) return r;
         ragged = 0;
     }
@@ -569,7 +592,7 @@ FLAKE_AMD_API long long flake_amd_set_encode_ragged(FlakeAmdSet *g, const void *
         if (cnt == 0) continue;
         long long r;
         if (k == 1 && ragged) {
-            r = set_encode_short(g, gpcm, sample_bytes, cnt, gsizes, gstreams, stash + stash_at, out_size - stash_at, gfs);
+            r = set_encode_short(g, NULL, gpcm, sample_bytes, cnt, gsizes, gstreams, stash + stash_at, out_size - stash_at, gfs);
             if (r == -2) {
                 /* the ABI does not cover this handle: nothing of the short blocks has run; take the per-length calls */
                 ragged = 0;
@@ -621,6 +644,50 @@ FLAKE_AMD_API long long flake_amd_set_encode_ragged(FlakeAmdSet *g, const void *
     RAGGED_DONE();
 #undef RAGGED_DONE
     return result;
+}
+
+/* ---- the hooks of a recode set (host_internal.h) ---- */
+
+struct fhip_ctx *fa_set_handle(FlakeAmdSet *g) { return g ? g->hip : NULL; }
+int fa_set_max_batch(const FlakeAmdSet *g) { return g ? g->max_batch : 0; }
+
+long long fa_set_encode_from(FlakeAmdSet *g, fa_set_source *src, int nblocks, int block_size, const int *stream_of_block,
+                             unsigned char *out, size_t out_size, int *frame_sizes)
+{
+    if (!g || !src) return -1;
+    if (g->host_md5) SET_FAIL("flake_amd_set_encode: a set that hashes on the host needs its samples there");
+    src->cur = 0;
+    /* (the samples pointer is the batch's token: it is compared, never followed) */
+    return set_encode(g, src, (const void *)src, 4, nblocks, block_size, stream_of_block, out, out_size, frame_sizes);
+}
+
+long long fa_set_encode_short_from(FlakeAmdSet *g, fa_set_source *src, int nblocks, const int *block_sizes,
+                                   const int *stream_of_block, unsigned char *out, size_t out_size, int *frame_sizes)
+{
+    if (!g || !src) return -1;
+    g->err[0] = 0;
+    g->vfail = 0;
+    if (g->broken) SET_FAIL("flake_amd_set_encode_ragged: an earlier device error left the set unusable");
+    if (g->host_md5) SET_FAIL("flake_amd_set_encode_ragged: a set that hashes on the host needs its samples there");
+    if (nblocks < 0 || (nblocks > 0 && (!block_sizes || !stream_of_block || !out)))
+        SET_FAIL("flake_amd_set_encode_ragged: null argument or negative block count");
+    if (nblocks == 0) return 0;
+    /* flake_amd_set_encode_ragged's checks, for a call whose blocks are all short */
+    int *per = g->scratch;
+    memset(per, 0, sizeof(int) * (size_t)g->nstreams);
+    for (int b = 0; b < nblocks; b++) {
+        const int s = stream_of_block[b], n = block_sizes[b];
+        if (n < 1 || n >= g->hp.block_size) SET_FAIL("flake_amd_set_encode_ragged: block_sizes[%d] = %d is not a short block", b, n);
+        if (s < 0 || s >= g->nstreams) SET_FAIL("flake_amd_set_encode_ragged: stream_of_block[%d] = %d is outside the set's %d streams", b, s, g->nstreams);
+        if (g->ended[s] || per[s])
+            SET_FAIL("flake_amd_set_encode_ragged: block %d belongs to stream %d, which a short block has ended", b, s);
+        per[s] = 1;
+    }
+    src->cur = 0;
+    const long long r = set_encode_short(g, src, (const void *)src, 4, nblocks, block_sizes, stream_of_block, out, out_size,
+                                         frame_sizes);
+    if (r == -2) SET_FAIL("flake_amd_set_encode_ragged: the ragged packed path does not cover this set (block size above 16384)");
+    return r;
 }
 
 FLAKE_AMD_API int flake_amd_set_get_streaminfo(FlakeAmdSet *g, int stream, FlakeAmdStreaminfo *si)

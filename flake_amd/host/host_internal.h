@@ -47,4 +47,44 @@ static inline int fa_block_of_frame(long long frame, const int32_t *block_frames
     return -1;
 }
 
+/* ---- what a recode set (flake_recode_set.c) opens inside a stream set and a decode set ---- */
+
+/* An encode call's samples as gather pieces from device memory instead of a host buffer (flake_set.c).  pieces tile the
+ * call's samples (all blocks back to back); each chunk of the call gathers its part of them (fa_rc_slice into work,
+ * which has room for npieces; cur is that walk's place, 0 before the call). */
+struct fhip_gather_piece;
+typedef struct fa_set_source {
+    const struct fhip_gather_piece *pieces;
+    int npieces;
+    const int32_t *src0, *src1;   /* device memory, capacities in samples per channel */
+    int64_t src0_cap, src1_cap;
+    struct fhip_gather_piece *work;
+    int cur;
+} fa_set_source;
+struct FlakeAmdSet;
+/* flake_amd_set_encode / flake_amd_set_encode_ragged (every block short, one per stream) with int32 samples from src;
+ * not for a set that hashes on the host.  The ragged form needs the ragged packed path: -1 where the set has none. */
+long long fa_set_encode_from(struct FlakeAmdSet *g, fa_set_source *src, int nblocks, int block_size,
+                             const int *stream_of_block, unsigned char *out, size_t out_size, int *frame_sizes);
+long long fa_set_encode_short_from(struct FlakeAmdSet *g, fa_set_source *src, int nblocks, const int *block_sizes,
+                                   const int *stream_of_block, unsigned char *out, size_t out_size, int *frame_sizes);
+struct fhip_ctx *fa_set_handle(struct FlakeAmdSet *g);
+int fa_set_max_batch(const struct FlakeAmdSet *g);
+
+/* flake_amd_decode_set_frames with the samples LEFT ON THE DEVICE (flake_decode_set.c): every device batch decodes to
+ * dev_pcm[0 ..) (int32, dev_cap_samples per channel: fa_decode_set_batch_samples() always suffices) and, once the set
+ * has judged its segments, is handed to fn: segment k is seg_samples[k] samples of stream seg_stream[k] at seg_start[k],
+ * good where seg_ok[k] -- a segment that is not fails its stream, as the set has already noted.  fn returns below 0 to
+ * stop the call (it returns -1 then).  The next batch overwrites dev_pcm. */
+struct FlakeAmdDecodeSet;
+typedef int (*fa_ds_batch_fn)(void *user, int nsegs, const int32_t *seg_stream, const int64_t *seg_start,
+                              const int64_t *seg_samples, const unsigned char *seg_ok);
+long long fa_decode_set_frames_keep(struct FlakeAmdDecodeSet *g, int nruns, const int *stream_of_run,
+                                    const int *frames_of_run, const unsigned char *stream, size_t bytes,
+                                    const int *frame_sizes, int32_t *dev_pcm, size_t dev_cap_samples,
+                                    long long *run_samples, fa_ds_batch_fn fn, void *user);
+size_t fa_decode_set_batch_samples(const struct FlakeAmdDecodeSet *g);     /* frames per batch x the largest block */
+int fa_decode_set_max_batch(const struct FlakeAmdDecodeSet *g);
+int fa_decode_set_max_block(const struct FlakeAmdDecodeSet *g);
+
 #endif

@@ -371,6 +371,68 @@ FLAKE_AMD_API int flake_amd_decode_set_index(FlakeAmdDecodeSet *g, unsigned max_
 FLAKE_AMD_API const char *flake_amd_decode_set_last_error(const FlakeAmdDecodeSet *g);
 FLAKE_AMD_API void flake_amd_decode_set_close(FlakeAmdDecodeSet *g);
 
+/* ---- recoding: FLAC in, FLAC out, the PCM never leaving the device ------ */
+
+/*
+ * A recode set joins a decode set to a stream set ON THE DEVICE: the frames of many streams go in as
+ * flake_amd_decode_set_frames takes them, and what comes out is, for every stream, byte for byte what a FlakeAmdSet at
+ * enc_like's parameters writes for that stream's samples -- whole blocks while frames arrive, the tail at the end,
+ * STREAMINFO included.  The decoder's blocks (1152, 4608, variable, whatever the source used) are re-cut into the
+ * encoder's block size by a gather kernel (K9, fhip_frames_packed_gather); a stream's samples that do not fill a block
+ * wait in a device carry (below one block per stream) for the next call.  The samples cross the link in neither
+ * direction and are hashed once: STREAMINFO's md5sum is the DECODE side's digest (K6 over the ranges K7 left), the
+ * encode set inside runs without a hash.  Comparing that digest with the source file's is the caller's.
+ *
+ * flake_amd_recode_set_open: all streams share src_like's channels, sample rate and bits per sample, which must equal
+ * enc_like's; their source blocks are at most src_like->max_block_size (65535 when 0).  flags: FLAKE_AMD_SET_VBS is
+ * required exactly when enc_like has variable block size (levels 9-12); FLAKE_AMD_SET_MD5_OFF leaves md5sum zero;
+ * FLAKE_AMD_SET_MD5_HOST is refused (there is no PCM on the host), as is an encoder block size above 16384 (the tails
+ * need the ragged packed path).  Two handles, a decode one and an encode one, each
+ * with FLAKE_AMD_BATCH frames / blocks per device batch.  NULL on failure: flake_amd_recode_set_last_error(NULL).
+ *
+ * flake_amd_recode_set_frames: the input is flake_amd_decode_set_frames' (runs of frames, back to back in `stream`).
+ * `out` receives the whole blocks the call completes, back to back; block b of them belongs to stream block_stream[b]
+ * and is block_bytes[b] bytes (all its frames' under variable block size), so the caller scatters; *nblocks is their
+ * count.  A stream's blocks come in stream order; the order is otherwise unspecified.  Returns the bytes written, or
+ * -1.  out_size and block_cap must reach flake_amd_recode_set_out_bound(g, frames of the call): the carries plus that
+ * many source blocks of the largest size, at verbatim size.  Below it, or with a stream index outside the set, a run
+ * that names a failed stream, bad frame sizes, or after flake_amd_recode_set_finish, the call returns -1 with NOTHING
+ * changed.
+ *
+ * Failure is per stream, as in a decode set: a frame that fails fails its stream for good
+ * (flake_amd_recode_set_failed: 1 with the frame, counted from the stream's first, and its FHIP_VERIFY_* status).
+ * Blocks of it already returned stand; nothing further of it is encoded, neither from the failing run on nor at the
+ * end, and it has no STREAMINFO.  Every other stream is unaffected.  A device error, or a verification failure on the
+ * encode side, makes the call return -1 and the set refuse further calls.
+ *
+ * flake_amd_recode_set_finish: every good stream's carry is encoded as its tail through the ragged path
+ * (flake_amd_set_encode_ragged's: one device batch per FLAKE_AMD_BATCH tails); outputs as above, bound
+ * flake_amd_recode_set_out_bound(g, -1).  The set takes no more frames afterwards.
+ * flake_amd_recode_set_get_streaminfo: the new STREAMINFO of a good stream (-1 for a failed one).
+ * flake_amd_recode_set_enable_verify: the inner set's flake_amd_set_enable_verify -- K5 checks the new frames against
+ * the gathered PCM where it lies.  flake_amd_recode_set_device_batches: the decode and the encode batches so far.
+ * One format per set; other metadata blocks, int16 device PCM and overlapping a batch's encode with the next batch's
+ * decode are out of scope.
+ */
+typedef struct FlakeAmdRecodeSet FlakeAmdRecodeSet;
+FLAKE_AMD_API FlakeAmdRecodeSet *flake_amd_recode_set_open(const FlakeAmdStreaminfo *src_like, const FlakeAmdContext *enc_like,
+                                                           int nstreams, unsigned flags);
+FLAKE_AMD_API long long flake_amd_recode_set_frames(FlakeAmdRecodeSet *g, int nruns, const int *stream_of_run,
+                                                    const int *frames_of_run, const unsigned char *stream, size_t bytes,
+                                                    const int *frame_sizes, unsigned char *out, size_t out_size,
+                                                    int *block_stream, int *block_bytes, int block_cap, int *nblocks);
+/* nframes >= 0: the bound of a flake_amd_recode_set_frames call of that many frames, as the set stands; -1: of
+ * flake_amd_recode_set_finish.  Either output may be NULL.  0, or -1 without a set. */
+FLAKE_AMD_API int flake_amd_recode_set_out_bound(const FlakeAmdRecodeSet *g, long long nframes, size_t *bytes, long long *blocks);
+FLAKE_AMD_API long long flake_amd_recode_set_finish(FlakeAmdRecodeSet *g, unsigned char *out, size_t out_size,
+                                                    int *block_stream, int *block_bytes, int block_cap, int *nblocks);
+FLAKE_AMD_API int flake_amd_recode_set_get_streaminfo(FlakeAmdRecodeSet *g, int stream, FlakeAmdStreaminfo *si);
+FLAKE_AMD_API int flake_amd_recode_set_failed(const FlakeAmdRecodeSet *g, int stream, long long *frame, int *status);
+FLAKE_AMD_API int flake_amd_recode_set_device_batches(const FlakeAmdRecodeSet *g, long long *decode, long long *encode);
+FLAKE_AMD_API int flake_amd_recode_set_enable_verify(FlakeAmdRecodeSet *g, int on);
+FLAKE_AMD_API const char *flake_amd_recode_set_last_error(const FlakeAmdRecodeSet *g);
+FLAKE_AMD_API void flake_amd_recode_set_close(FlakeAmdRecodeSet *g);
+
 /* Deterministic synthetic PCM, channel-interleaved int32 as
  * flake_encode_frame() expects: nframes blocks of n samples per channel,
  * starting at absolute frame index first_frame. */

@@ -816,6 +816,54 @@ FHIP_API int fhip_md5_update_uploaded_ragged(fhip_ctx *ctx, fhip_md5_state *stat
                                              const int32_t *block_sizes, const int32_t *seg_first,
                                              const int32_t *seg_block);
 
+/* ---- gathering spans on the device (K9) ------------------------------ */
+
+/*
+ * What joins a decode to an encode without the samples leaving the device: spans of channel-interleaved int32 samples
+ * copied from up to two device buffers into one destination.  A piece is count samples per channel (>= 1) found at
+ * sample src of source buffer src_buf (0 or 1) and going to sample dst of the destination; the table is HOST memory,
+ * sorted by dst, and tiles [0, total) of the destination exactly (total = the sum of the counts).  All three entries
+ * below take int32 PCM only: FHIP_E_UNSUPPORTED under FHIP_PCM_S16.
+ */
+typedef struct fhip_gather_piece {
+    int32_t src_buf;              /* 0 or 1 */
+    int32_t count;                /* samples per channel, >= 1 */
+    int64_t src;                  /* first sample (per channel) in its source */
+    int64_t dst;                  /* first sample (per channel) in the destination */
+} fhip_gather_piece;              /* 24 bytes */
+
+/* dst, src0, src1: DEVICE memory, with their capacities in samples per channel (a source of capacity 0 may be null
+ * and must not be named by a piece).  Asynchronous on the handle's stream; the table is copied before the call
+ * returns.  It is checked on the host before anything is queued -- src_buf 0 or 1, counts >= 1, sorted and tiling
+ * [0, total) with no gap and no overlap, every source span inside its capacity, total <= dst_cap -- and a table that
+ * fails is FHIP_E_INVALID with nothing queued and an empty launch list, as are null pointers and negative counts.
+ * The kernel clamps every table index, read and write regardless (K7's rule).  The destination must not overlap a
+ * source span that a LATER tile still reads.  npieces == 0: nothing is queued.  Launch list: "k_gather_spans"; timed
+ * under that name with fhip_set_profiling.  Where the source and destination addresses of four values agree modulo
+ * 16 bytes they move with 16-byte loads and stores, elsewhere with 4-byte loads. */
+FHIP_API int fhip_gather_spans_dev(fhip_ctx *ctx, int32_t *dst, int64_t dst_cap, const int32_t *src0, int64_t src0_cap,
+                                   const int32_t *src1, int64_t src1_cap, const fhip_gather_piece *pieces, int npieces);
+
+/* The optional first step of a packed encode, in place of fhip_frames_packed_upload / _upload_ragged: the handle's own
+ * PCM staging is filled through a piece table from device sources instead of from host memory.  b->nframes,
+ * b->block_size and (block_sizes != NULL: the ragged form, a HOST table [b->nframes]) are what they are for the upload
+ * entries, with the same checks and the same restrictions on a handle with allow_vbs; the pieces must tile exactly the
+ * batch's samples (nframes * block_size, or the sum of block_sizes).  b->pcm is a TOKEN here: non-null and never
+ * dereferenced, it only names the batch, and the steps that follow -- fhip_frames_packed_begin(_ragged),
+ * fhip_md5_update_uploaded(_ragged), fhip_encode_blocks_vbs_packed_numbered / _ragged_numbered, with K5 behind them
+ * under fhip_set_verify -- take a batch with the same pcm as they take an upload.  Returns when the gather is done
+ * (as the uploads return when the copy is).  The sources must not be the handle's own staging. */
+FHIP_API int fhip_frames_packed_gather(fhip_ctx *ctx, const fhip_batch *b, const int32_t *block_sizes,
+                                       const int32_t *src0, int64_t src0_cap, const int32_t *src1, int64_t src1_cap,
+                                       const fhip_gather_piece *pieces, int npieces);
+
+/* fhip_decode_frames_segments with the samples LEFT ON THE DEVICE: out->pcm is DEVICE memory of out->pcm_cap samples
+ * per channel (int32), K7 writes there and nothing of it is downloaded.  Everything else is the host form's: host
+ * stream, tables, records, summary, nsamples and per-segment outputs, the optional K6 hash queued behind K7 (reading
+ * out->pcm), one synchronisation, FHIP_OK or FHIP_E_VERIFY. */
+FHIP_API int fhip_decode_frames_segments_keep(fhip_ctx *ctx, const fhip_decode_in *in, const fhip_decode_segments *segs,
+                                              const fhip_decode_out *out, const fhip_decode_md5 *md5);
+
 /* ---- measurement ---------------------------------------------------- */
 
 /* With profiling on, every kernel launch of the hot path is bracketed by
@@ -831,7 +879,8 @@ FHIP_API int fhip_get_kernel_times(fhip_ctx *ctx, const char **names, double *ms
  * one or two workgroups per tile), "tail" (K2 runs inside K1), "fused" (K1 applies K0's decisions),
  * "narrow" (16-bit sample rows).  The calls that start a new list are the encode entries
  * (fhip_encode_subframes*, fhip_frames_packed_begin / fhip_encode_frames_packed, the VBS entries)
- * and fhip_prepare_ahead, the fhip_md5_* entries, fhip_decode_frames(_dev), fhip_decode_frames_segments(_dev) and fhip_index_frames(_dev).  A host-side record: it adds no device work.  (One exception:
+ * and fhip_prepare_ahead, the fhip_md5_* entries, fhip_decode_frames(_dev), fhip_decode_frames_segments(_dev, _keep),
+ * fhip_index_frames(_dev), fhip_gather_spans_dev and fhip_frames_packed_gather.  A host-side record: it adds no device work.  (One exception:
  * "k_md5_streams<int16_t,2> fast" / "... general" name a choice that is made on the device when the block shape
  * allows the fast path; asking for the list then waits for that launch.)  names[0 .. cap) receive
  * strings owned by the handle, valid until its next such call; returns the number of launches. */
