@@ -16,6 +16,9 @@ def test_self_launch_reaches_the_ranks_and_fails_loudly_without_a_gpu():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
+    # the launcher ends the other ranks as soon as it sees one fail, and by default it looks ten times a second: a
+    # rank that is a moment slower to start is then ended before it has spoken.  Let it look once, after both have
+    env["PET_MONITOR_INTERVAL"] = "20"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1",
                         "--warmup", "0"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode != 0

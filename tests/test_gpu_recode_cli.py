@@ -54,6 +54,35 @@ def test_recode_set(picks, tmp_path, switches):
         assert wav_data(wav / f"{n}.wav") == x["pcm"].astype("<i2").tobytes(), n
 
 
+def test_recode_set_is_the_same_with_either_indexer(picks, tmp_path):
+    """Blocks of 64, 256 and 64 are two index calls on the device, one call per file on the CPU: the same exit status,
+    stderr and files.  A file cut inside its last frame is named by both and gets no output, its whole frames having
+    gone through the set like everyone's."""
+    names = []
+    for n, x in zip(NAMES, picks):
+        flac_file(tmp_path / f"{n}.flac", x)
+        names.append(tmp_path / f"{n}.flac")
+    x = picks[0]
+    flac_file(tmp_path / "cut.flac", x, x["frames"][:len(x["frames"]) - 9])
+    names.append(tmp_path / "cut.flac")
+    runs = {}
+    for leg, env in (("device", {}), ("host", {"FLAKE_AMD_INDEX_HOST": "1"})):
+        e = {k: v for k, v in os.environ.items() if k != "FLAKE_AMD_INDEX_HOST"}
+        e.update(env)
+        out = tmp_path / f"out_{leg}"
+        out.mkdir()
+        p = subprocess.run([os.path.join(V.LIB_DIR, "flake_amd_cli"), "-8", "--recode", "--set", str(out), *map(str, names)],
+                           capture_output=True, text=True, timeout=120, env=e)
+        runs[leg] = (p.returncode, p.stderr.replace(str(out), "OUT"), [(f, (out / f).read_bytes()) for f in sorted(os.listdir(out))])
+    assert runs["device"] == runs["host"]
+    status, stderr, files = runs["device"]
+    assert status == 1 and [f for f, _ in files] == [f"{n}.flac" for n in NAMES]
+    cut = [ln for ln in stderr.splitlines() if "cut.flac" in ln]
+    assert len(cut) == 1 and cut[0].endswith("the frame is cut or its CRC-16 fails"), stderr
+    for n in NAMES:
+        assert f"{n}.flac: {len(picks[NAMES.index(n)]['pcm'])} sample-frames -> " in stderr, stderr
+
+
 def test_a_corrupt_source_is_named_and_the_others_are_written(picks, tmp_path):
     for n, x in zip(NAMES, picks):
         flac_file(tmp_path / f"{n}.flac", x)
