@@ -155,6 +155,11 @@ class DecodeSegments(C.Structure):
                 ("seg_failed", C.c_void_p)]
 
 
+class DecodeWindows(C.Structure):
+    """``fhip_decode_windows``"""
+    _fields_ = [("seg_skip", C.c_void_p), ("seg_take", C.c_void_p)]
+
+
 class IndexIn(C.Structure):
     """``fhip_index_in``"""
     _fields_ = [("stream", C.c_void_p), ("stream_bytes", C.c_int64), ("range_first", C.c_void_p),
@@ -278,6 +283,10 @@ def load_library() -> C.CDLL:
         "fhip_autocorr_tile": (i, [i, i, i]),
         "fhip_gather_spans_dev": (i, [vp, vp, i64, vp, i64, vp, i64, vp, i]),
         "fhip_frames_packed_gather": (i, [vp, C.POINTER(Batch), vp, vp, i64, vp, i64, vp, i]),
+        "fhip_decode_frames_windows_dev": (i, [vp, C.POINTER(DecodeIn), C.POINTER(DecodeSegments),
+                                               C.POINTER(DecodeWindows), C.POINTER(DecodeOut)]),
+        "fhip_decode_frames_windows": (i, [vp, C.POINTER(DecodeIn), C.POINTER(DecodeSegments), C.POINTER(DecodeWindows),
+                                           C.POINTER(DecodeOut)]),
         "fhip_decode_frames_segments_keep": (i, [vp, C.POINTER(DecodeIn), C.POINTER(DecodeSegments), C.POINTER(DecodeOut),
                                                  C.POINTER(DecodeMd5)]),
     }
@@ -314,6 +323,7 @@ ABI_SYMBOLS = (
     "fhip_decode_frames_segments_dev", "fhip_decode_frames_segments", "fhip_md5_update_ranges_dev",
     "fhip_index_frames_dev", "fhip_index_frames", "fhip_index_geometry",
     "fhip_gather_spans_dev", "fhip_frames_packed_gather", "fhip_decode_frames_segments_keep",
+    "fhip_decode_frames_windows_dev", "fhip_decode_frames_windows",
 )
 
 # fhip_gather_piece (24 bytes): K9's unit, in samples per channel
@@ -650,6 +660,59 @@ class Encoder:
         self._check(self.lib.fhip_decode_frames_segments_dev(self._h, C.byref(di), C.byref(sg), C.byref(do)),
                     "fhip_decode_frames_segments_dev")
 
+    def decode_frames_windows(self, stream, frame_bytes, pcm_cap: int, seg_first, seg_skip, seg_take, seg_number=None,
+                              seg_variable=None, out=None, null_table=None):
+        """fhip_decode_frames_windows on host data: decode_frames_segments' arguments plus, per segment, the samples to
+        drop from its front (seg_skip int64[nsegs]) and the most to deliver behind them (seg_take int64[nsegs], -1: to
+        the segment's end).  The delivered samples lie back to back in pcm; seg_start / seg_samples / nsamples are
+        about them.  null_table ("skip" / "take" / "win" / "segs"): pass a null pointer there (the refusals).  Returns
+        decode_frames_segments' tuple."""
+        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
+                                  else stream, dtype=np.uint8)
+        fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
+        sf = np.ascontiguousarray(seg_first, dtype=np.int32)
+        ns = len(sf) - 1
+        ch = self.params.channels
+        if out is None:
+            out = np.zeros((pcm_cap, ch), dtype=self.pcm_dtype)
+        if out.dtype != self.pcm_dtype or out.size < pcm_cap * ch:
+            raise ValueError("out must hold pcm_cap * channels values of the handle's PCM dtype")
+        k = max(ns, 1)
+        num = np.full(k, -1, np.int64) if seg_number is None else np.ascontiguousarray(seg_number, dtype=np.int64)
+        var = np.zeros(k, np.int32) if seg_variable is None else np.ascontiguousarray(seg_variable, dtype=np.int32)
+        skip = np.ascontiguousarray(seg_skip, dtype=np.int64)
+        take = np.ascontiguousarray(seg_take, dtype=np.int64)
+        if len(skip) != ns or len(take) != ns:
+            raise ValueError("seg_skip and seg_take hold one value per segment")
+        s_start, s_samples = np.full(k, -7, np.int64), np.full(k, -7, np.int64)
+        s_failed = np.full(k, -7, np.int32)
+        recs = np.zeros(len(fb), dtype=VERIFY_REC_DTYPE)
+        summary = np.zeros(4, dtype=np.int64)
+        nsm = np.zeros(1, dtype=np.int64)
+        di = DecodeIn(st.ctypes.data if st.size else None, st.size, fb.ctypes.data if fb.size else None, len(fb), 0, -1)
+        do = DecodeOut(_ptr(out) if out.size else None, pcm_cap, recs.ctypes.data if len(fb) else None,
+                       summary.ctypes.data, nsm.ctypes.data)
+        sg = DecodeSegments(sf.ctypes.data, ns, num.ctypes.data, var.ctypes.data, s_start.ctypes.data,
+                            s_samples.ctypes.data, s_failed.ctypes.data)
+        wn = DecodeWindows(None if null_table == "skip" else skip.ctypes.data,
+                           None if null_table == "take" else take.ctypes.data)
+        rc = self.lib.fhip_decode_frames_windows(self._h, C.byref(di), None if null_table == "segs" else C.byref(sg),
+                                                 None if null_table == "win" else C.byref(wn), C.byref(do))
+        return (rc, out, int(nsm[0]), recs, summary, s_start[:ns], s_samples[:ns], s_failed[:ns],
+                self.lib.fhip_last_error(self._h).decode() if rc else "")
+
+    def decode_frames_windows_dev(self, stream, stream_bytes: int, frame_bytes, nframes: int, pcm, pcm_cap: int,
+                                  summary, nsamples, seg_first, nsegs: int, seg_number, seg_variable, seg_start,
+                                  seg_samples, seg_failed, seg_skip, seg_take, records=None) -> int:
+        """K7's window mode on device-resident data (torch tensors or raw device addresses); async.  Returns the
+        entry's code (E_INVALID for a null table: nothing queued)."""
+        di = DecodeIn(_ptr(stream), stream_bytes, _ptr(frame_bytes), nframes, 0, -1)
+        do = DecodeOut(_ptr(pcm), pcm_cap, _ptr(records), _ptr(summary), _ptr(nsamples))
+        sg = DecodeSegments(_ptr(seg_first), nsegs, _ptr(seg_number), _ptr(seg_variable), _ptr(seg_start),
+                            _ptr(seg_samples), _ptr(seg_failed))
+        wn = DecodeWindows(_ptr(seg_skip), _ptr(seg_take))
+        return int(self.lib.fhip_decode_frames_windows_dev(self._h, C.byref(di), C.byref(sg), C.byref(wn), C.byref(do)))
+
     # -- K8: frame discovery ----------------------------------------------
     def index_ranges(self, stream, range_first, max_block_size: int = 0, frame_cap: int | None = None, sentinel=None):
         """fhip_index_frames on host data: the CPU indexer's answer for the streams stream[range_first[r] :
@@ -972,6 +1035,14 @@ def load_host_library() -> C.CDLL:
     lib.flake_amd_decode_set_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                 C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
     lib.flake_amd_decode_set_frames.restype = C.c_longlong
+    lib.flake_amd_decode_set_windows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t,
+                                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
+    lib.flake_amd_decode_set_windows.restype = C.c_longlong
+    lib.flake_amd_read_seektable.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
+    lib.flake_amd_read_seektable.restype = C.c_longlong
+    lib.flake_amd_seek_lookup.argtypes = [C.c_void_p, C.c_int, C.c_ulonglong]
+    lib.flake_amd_seek_lookup.restype = C.c_longlong
     lib.flake_amd_decode_set_run_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.flake_amd_decode_set_run_offsets.restype = C.c_int
     lib.flake_amd_decode_set_md5.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -1150,6 +1221,30 @@ def read_streaminfo(data34: bytes):
     if hi < 0:
         raise ValueError("invalid STREAMINFO")
     return si, hi
+
+
+# numpy view of FlakeAmdSeekPoint (24 bytes)
+SEEK_POINT_DTYPE = np.dtype([("sample", "<u8"), ("offset", "<u8"), ("frame_samples", "<u4"), ("pad", "<u4")])
+
+
+def read_seektable(block, cap: int | None = None):
+    """flake_amd_read_seektable: the points of a SEEKTABLE block's content that are not placeholders, as a
+    SEEK_POINT_DTYPE array -- at most cap of them (default: all) -- and how many the block holds.  Raises ValueError
+    for a block that is refused (a length that is no multiple of 18, sample numbers not strictly ascending)."""
+    data = np.frombuffer(bytes(block), dtype=np.uint8)
+    if cap is None:
+        cap = data.size // 18
+    pts = np.zeros(max(cap, 1), dtype=SEEK_POINT_DTYPE)
+    n = load_host_library().flake_amd_read_seektable(data.ctypes.data if data.size else None, data.size, pts.ctypes.data, cap)
+    if n < 0:
+        raise ValueError("invalid SEEKTABLE")
+    return pts[:min(int(n), cap)].copy(), int(n)
+
+
+def seek_lookup(points, sample: int) -> int:
+    """flake_amd_seek_lookup: the index of the last point at or before `sample`, -1 if there is none."""
+    pts = np.ascontiguousarray(points, dtype=SEEK_POINT_DTYPE)
+    return int(load_host_library().flake_amd_seek_lookup(pts.ctypes.data if len(pts) else None, len(pts), int(sample)))
 
 
 def index_frames(si: HostStreaminfo, stream, cap: int | None = None):
@@ -1392,6 +1487,49 @@ class DecodeSet:
         off = np.zeros(max(len(runs), 1), dtype=np.int64)
         self.lib.flake_amd_decode_set_run_offsets(self._g, off.ctypes.data, len(runs))
         return [None if rs[r] < 0 else out[off[r]:off[r] + rs[r]] if rs[r] else out[:0] for r in range(len(runs))]
+
+    def decode_windows(self, windows, pcm_cap: int | None = None, sample_bytes: int = 4, out=None):
+        """flake_amd_decode_set_windows.  windows: [(run bytes, frame sizes, fixed block size or 0, first sample,
+        count)], a run being consecutive frames of one stream from any frame on.  Returns (one entry per window: its
+        samples [n][channels], a view of one buffer, or None for a window that failed; win_status int32[]; the frames
+        handed to the device; where each window begins in the buffer).  pcm_cap defaults to the sum of the counts; out
+        (optional) is decoded into.  Raises FlakeHipError when the call is refused: nothing was written then."""
+        fs = [np.ascontiguousarray(w[1], dtype=np.int32) for w in windows]
+        fow = np.asarray([len(f) for f in fs], dtype=np.int32)
+        parts = [np.frombuffer(bytes(w[0]), dtype=np.uint8) if isinstance(w[0], (bytes, bytearray))
+                 else np.asarray(w[0], dtype=np.uint8) for w in windows]
+        st = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, np.uint8)
+        sizes = np.ascontiguousarray(np.concatenate(fs)) if fs else np.zeros(0, np.int32)
+        fixed = np.asarray([w[2] for w in windows], dtype=np.uint32)
+        first = np.asarray([w[3] for w in windows], dtype=np.uint64)
+        count = np.asarray([w[4] for w in windows], dtype=np.int64)
+        if pcm_cap is None:
+            pcm_cap = int(np.maximum(count, 0).sum())
+        if out is None:
+            out = np.zeros((pcm_cap, self.si.channels), dtype=np.int16 if sample_bytes == 2 else np.int32)
+        k = max(len(windows), 1)
+        ws, wst = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int32)
+        nfd = C.c_longlong(0)
+        have = len(windows) > 0
+        n = self.lib.flake_amd_decode_set_windows(self._g, len(windows), fow.ctypes.data if have else None,
+                                                  st.ctypes.data if st.size else None, st.size,
+                                                  sizes.ctypes.data if sizes.size else None,
+                                                  fixed.ctypes.data if have else None, first.ctypes.data if have else None,
+                                                  count.ctypes.data if have else None,
+                                                  out.ctypes.data if out.size else None, sample_bytes, pcm_cap,
+                                                  ws.ctypes.data, wst.ctypes.data, C.byref(nfd))
+        if n < 0:
+            raise FlakeHipError(int(n), "flake_amd_decode_set_windows", self.last_error())
+        res, begins, at = [], [], 0
+        for w in range(len(windows)):
+            begins.append(at)
+            if ws[w] < 0:
+                res.append(None)
+                at += int(count[w])
+            else:
+                res.append(out[at:at + ws[w]])
+                at += int(ws[w])
+        return res, wst[:len(windows)], int(nfd.value), begins
 
     def index(self, streams, max_block_size: int | None = None):
         """flake_amd_decode_set_index: the frames of many files in one device call (K8).  streams: the files' bytes,

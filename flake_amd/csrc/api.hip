@@ -140,6 +140,7 @@ struct fhip_ctx {
     DevBuf<uint32_t> d_vnum;                  // fhip_verify_frames_numbered: the host number table uploaded
     DevBuf<long long> d_dseg;                 // fhip_decode_frames_segments: the segment tables, their outputs, K6's CSR
     std::vector<long long> h_dseg;            // ... and the host image they are uploaded from
+    DevBuf<fhip::DecodeClip> d_dclip;         // fhip_decode_frames_windows: K7's clip per frame
     long long vfail_sum[4] = {0, 0, -1, 0};   // fhip_last_verify_failure: the most recent verdict's summary ...
     fhip_verify_rec vfail_rec{0, -1, -1, -1}; // ... and its first failing frame's record
     bool vfail_has_number = false;            // fhip_last_verify_number: the number that frame had to carry, where a
@@ -2692,7 +2693,9 @@ int decode_check(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *o
 // frame records through K5's workspace: an encode call that follows overwrites both from the start, as it always has.
 // segs (optional, device memory as well): the segment mode; its end reads the frames' records, so a caller who asks for
 // none gets the handle's own.
-int run_decode(fhip_ctx *c, const fhip_decode_in &in, const fhip_decode_out &out, const fhip_decode_segments *segs = nullptr)
+// win (optional, with segs; device memory): the window mode, whose clips go through the handle's d_dclip.
+int run_decode(fhip_ctx *c, const fhip_decode_in &in, const fhip_decode_out &out, const fhip_decode_segments *segs = nullptr,
+               const fhip_decode_windows *win = nullptr)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     int rc = ensure_verify(c, (size_t)in.nframes);
@@ -2715,8 +2718,15 @@ int run_decode(fhip_ctx *c, const fhip_decode_in &in, const fhip_decode_out &out
         a.seg_samples = reinterpret_cast<long long *>(segs->seg_samples);
         a.seg_failed = segs->seg_failed;
     }
+    if (win) HIP_TRY(c, c->d_dclip.reserve((size_t)in.nframes));
     Prof pr(c, kProfDecode, c->profiling);
-    HIP_TRY(c, fhip::launch_decode(c->stream, a));
+    if (win) {
+        const fhip::DecodeWindowArgs w{a, reinterpret_cast<const long long *>(win->seg_skip),
+                                       reinterpret_cast<const long long *>(win->seg_take), c->d_dclip.get()};
+        HIP_TRY(c, fhip::launch_decode_windows(c->stream, w));
+    } else {
+        HIP_TRY(c, fhip::launch_decode(c->stream, a));
+    }
     return FHIP_OK;
 }
 }  // namespace
@@ -2739,6 +2749,17 @@ int fhip_decode_frames_segments_dev(fhip_ctx *c, const fhip_decode_in *in, const
     return run_decode(c, *in, *out, segs);
 }
 
+int fhip_decode_frames_windows_dev(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
+                                   const fhip_decode_windows *win, const fhip_decode_out *out)
+{
+    if (c && (!segs || !win)) { c->launches.clear(); c->md5_log_entry = -1; return fail(c, FHIP_E_INVALID, "null argument"); }
+    int rc = decode_check(c, in, out, segs);
+    if (rc != FHIP_OK) return rc;
+    if (!win->seg_skip || !win->seg_take) return fail(c, FHIP_E_INVALID, "null window table");
+    LaunchScope ls(c);
+    return run_decode(c, *in, *out, segs, win);
+}
+
 int fhip_decode_frames(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *out)
 {
     return fhip_decode_frames_segments(c, in, nullptr, out, nullptr);
@@ -2749,11 +2770,20 @@ int fhip_decode_frames(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_
 // CSR (md5_first [nstreams + 1], md5_range [nsegs]), which is built here.
 // keep: out->pcm is DEVICE memory that K7 writes and K6 reads where it lies; nothing of it is downloaded
 // (fhip_decode_frames_segments_keep).
+// win (with segs, without md5): the window mode; its two tables travel behind everything else in the same block.
 static int decode_segments_host(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
-                                const fhip_decode_out *out, const fhip_decode_md5 *md5, bool keep)
+                                const fhip_decode_out *out, const fhip_decode_md5 *md5, bool keep,
+                                const fhip_decode_windows *win = nullptr)
 {
     int rc = decode_check(c, in, out, segs);
     if (rc != FHIP_OK) return rc;
+    if (win) {
+        if (!win->seg_skip || !win->seg_take) return fail(c, FHIP_E_INVALID, "null window table");
+        for (int s = 0; s < segs->nsegs; s++) {
+            if (win->seg_skip[s] < 0) return fail(c, FHIP_E_INVALID, "negative seg_skip");
+            if (win->seg_take[s] < -1) return fail(c, FHIP_E_INVALID, "seg_take is -1 or a count");
+        }
+    }
     if (keep && c->pcm_format == FHIP_PCM_S16)
         return fail(c, FHIP_E_UNSUPPORTED, "keeping the PCM on the device takes int32 PCM only (FHIP_PCM_S16 is set)");
     if (md5 && !segs) return fail(c, FHIP_E_INVALID, "md5 needs a segment table");
@@ -2800,9 +2830,10 @@ static int decode_segments_host(fhip_ctx *c, const fhip_decode_in *in, const fhi
     fhip_decode_out dout{dpcm, cap, c->d_vrec, reinterpret_cast<int64_t *>(c->d_vsum.get()),
                          reinterpret_cast<int64_t *>(c->d_vsum.get() + 5)};
     fhip_decode_segments dsegs{};
+    fhip_decode_windows dwin{};
     int32_t *d_i32 = nullptr;
     if (segs) {
-        const size_t n32 = 4 * ns + nst + 2, words = 3 * ns + (n32 + 1) / 2;
+        const size_t n32 = 4 * ns + nst + 2, wwin = 3 * ns + (n32 + 1) / 2, words = wwin + (win ? 2 * ns : 0);
         c->h_dseg.assign(words, 0);
         HIP_TRY(c, c->d_dseg.reserve(words));
         int32_t *h_i32 = reinterpret_cast<int32_t *>(c->h_dseg.data() + 3 * ns);
@@ -2818,6 +2849,12 @@ static int decode_segments_host(fhip_ctx *c, const fhip_decode_in *in, const fhi
             std::vector<int32_t> at(first, first + nst);
             for (size_t s = 0; s < ns; s++) range[at[md5->seg_stream[s]]++] = (int32_t)s;
         }
+        if (win) {
+            memcpy(c->h_dseg.data() + wwin, win->seg_skip, ns * sizeof(int64_t));
+            memcpy(c->h_dseg.data() + wwin + ns, win->seg_take, ns * sizeof(int64_t));
+            dwin.seg_skip = reinterpret_cast<const int64_t *>(c->d_dseg.get() + wwin);
+            dwin.seg_take = reinterpret_cast<const int64_t *>(c->d_dseg.get() + wwin + ns);
+        }
         HIP_TRY(c, hipMemcpyAsync(c->d_dseg, c->h_dseg.data(), words * sizeof(long long), hipMemcpyHostToDevice, c->stream));
         dsegs.seg_first = d_i32;
         dsegs.nsegs = segs->nsegs;
@@ -2827,7 +2864,7 @@ static int decode_segments_host(fhip_ctx *c, const fhip_decode_in *in, const fhi
         dsegs.seg_samples = reinterpret_cast<int64_t *>(c->d_dseg.get() + 2 * ns);
         dsegs.seg_failed = d_i32 + 2 * ns + 1;
     }
-    rc = run_decode(c, din, dout, segs ? &dsegs : nullptr);
+    rc = run_decode(c, din, dout, segs ? &dsegs : nullptr, win ? &dwin : nullptr);
     if (rc != FHIP_OK) return rc;
     if (md5) {
         // the hash reads the PCM where K7 left it and the ranges K7 named, behind it on the same stream
@@ -2876,6 +2913,13 @@ int fhip_decode_frames_segments(fhip_ctx *c, const fhip_decode_in *in, const fhi
                                 const fhip_decode_out *out, const fhip_decode_md5 *md5)
 {
     return decode_segments_host(c, in, segs, out, md5, false);
+}
+
+int fhip_decode_frames_windows(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
+                               const fhip_decode_windows *win, const fhip_decode_out *out)
+{
+    if (c && (!segs || !win)) { c->launches.clear(); c->md5_log_entry = -1; return fail(c, FHIP_E_INVALID, "null argument"); }
+    return decode_segments_host(c, in, segs, out, nullptr, false, win);
 }
 
 int fhip_decode_frames_segments_keep(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,

@@ -22,11 +22,23 @@
 // k_decode_frames); a partition never yields more residuals than the block has left (the walk is driven by
 // the sample index, not by the stream); every PCM write is inside [0, pcm_cap) and inside the frame's own
 // sample range; every row write is inside the frame's own rows.  A corrupt stream ends in a status code.
+//
+// The window mode (FHIP_K7_WINDOWS): k7_decode_windows.hip defines the macro and includes this file, which then makes
+// k_decode_frames_windows and k_decode_windows of the same text instead of the kernels above, and launch_decode_windows
+// instead of launch_decode.  Segment s delivers only samples [seg_skip[s], seg_skip[s] + seg_take[s]) of its own, counted
+// over the sizes of its good headers.  Every frame is still parsed, restored and checked in full; what changes is where a
+// frame's samples go and which of them: the header pass leaves a DecodeClip per frame, and the write-out of the frame
+// pass runs over the clip alone.  Every difference is under #if, so that without the macro this file is, token for
+// token, what it was: the register and LDS figures of its kernels are pinned by tests.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "kernels.h"
 #include "flac_parse.h"
+
+#ifndef FHIP_K7_WINDOWS
+#define FHIP_K7_WINDOWS 0
+#endif
 
 namespace fhip {
 namespace {
@@ -45,9 +57,30 @@ __device__ __forceinline__ bool hdr_parsed(int status) { return status == FHIP_V
 // SEG: the segment mode (DecodeArgs::seg_first): the strategy bit, the first number, continuity and the size rule of
 // fixed blocks are a segment's; placement, pcm_cap, the records and the counts stay the batch's.  The carry across the
 // chunks of DHDR_T frames is about frame f - 1 whatever its segment: a segment's first frame never looks at it.
+//
+// The window mode (on top of SEG): the scan S stays what it is -- the sizes of the good headers before the frame -- and
+// gives the frame's place in its SEGMENT, S less S at the segment's head (kept in LDS for the chunk, carried across
+// chunks for the one segment that can straddle a chunk's start: the one the last frame of the chunk before belongs to).
+// The frame's clip against the segment's window follows; the scan of the clips' lengths is the frame's place in pcm, and
+// pcm_cap, seg_start, seg_samples, nsamples and written_end are about the clips.
+#if FHIP_K7_WINDOWS
+#define K7_PLACE place      /* where the frame's delivered samples begin in pcm */
+#define K7_SIZE cnt         /* how many it delivers */
+__global__ void __launch_bounds__(DHDR_T) k_decode_frames_windows(DecodeWindowArgs w)
+{
+    constexpr bool SEG = true;
+    const DecodeArgs &a = w.d;
+    __shared__ long long s_S[DHDR_T];                  // S of each frame of the chunk
+    __shared__ long long s_carry_head;                 // S at the head of the segment of the chunk's last frame
+    if (threadIdx.x == 0) s_carry_head = 0;            // (first read behind the chunk loop's barriers)
+    long long dbase = 0;
+#else
+#define K7_PLACE S
+#define K7_SIZE h.n
 template <bool SEG>
 __global__ void __launch_bounds__(DHDR_T) k_decode_frames(DecodeArgs a)
 {
+#endif
     __shared__ long long scratch[DHDR_T / 64];
     __shared__ unsigned long long s_num[DHDR_T];      // the number and size each frame of the chunk carries
     __shared__ int s_n[DHDR_T];
@@ -91,6 +124,9 @@ __global__ void __launch_bounds__(DHDR_T) k_decode_frames(DecodeArgs a)
         // the frame's segment: the last one that starts at or before it (empty segments in front of it start there too)
         int seg = 0, variable = a.variable_blocks;
         bool seg_head = f == 0, seg_last = f == count - 1;
+#if FHIP_K7_WINDOWS
+        int head = 0;                                  // the first frame of the segment
+#endif
         if constexpr (SEG) {
             if (live) {
                 int lo = 0, hi = a.nsegs - 1;
@@ -100,6 +136,9 @@ __global__ void __launch_bounds__(DHDR_T) k_decode_frames(DecodeArgs a)
                 }
                 seg = lo;
                 seg_head = a.seg_first[seg] == f;
+#if FHIP_K7_WINDOWS
+                head = a.seg_first[seg];
+#endif
                 seg_last = a.seg_first[seg + 1] == f + 1;
                 variable = a.seg_variable[seg] != 0;
                 va.allow_vbs = variable;
@@ -123,6 +162,26 @@ __global__ void __launch_bounds__(DHDR_T) k_decode_frames(DecodeArgs a)
         long long stot = 0;
         const long long S = sbase + block_excl_scan(parsed ? (long long)h.n : 0ll, scratch, DHDR_T / 64, &stot);
         sbase += stot;
+#if FHIP_K7_WINDOWS
+        // the frame's clip [lo, lo + cnt) of its own samples and where it goes (a header that did not parse: none)
+        s_S[t] = S;
+        __syncthreads();
+        // (head <= f: inside the chunk or before it; a table that says otherwise reads nothing outside the chunk)
+        const long long head_S = live && head >= f0 && head <= f ? s_S[head - f0] : s_carry_head;
+        int lo = 0, cnt = 0;
+        if (parsed) {
+            const long long o = S - head_S;                                    // >= 0: S does not decrease
+            const long long skip = w.seg_skip[seg] > 0 ? w.seg_skip[seg] : 0, take = w.seg_take[seg];
+            const long long lim = (take < 0 || take > 0x7FFFFFFFFFFFFFFFll - skip) ? 0x7FFFFFFFFFFFFFFFll : skip + take;
+            const long long c0 = o > skip ? o : skip, c1 = o + h.n < lim ? o + h.n : lim;
+            if (c1 > c0) { lo = (int)(c0 - o); cnt = (int)(c1 - c0); }
+        }
+        long long dtot = 0;
+        const long long place = dbase + block_excl_scan((long long)cnt, scratch, DHDR_T / 64, &dtot);
+        dbase += dtot;
+        __syncthreads();                                                       // (s_carry_head has been read by everyone)
+        if (t == DHDR_T - 1) s_carry_head = head_S;
+#endif
         if (live && h.status == FHIP_VERIFY_OK) {
             // (a frame whose own header is broken has already failed: its successor is not blamed for it)
             const unsigned long long prev_num = t ? s_num[t - 1] : s_carry_num;
@@ -138,12 +197,16 @@ __global__ void __launch_bounds__(DHDR_T) k_decode_frames(DecodeArgs a)
             // fixed blocks: every frame but the last holds the same number of samples
             bool size_ok = true;
             if (!variable && prev_ok) size_ok = seg_last ? h.n <= prev_n : h.n == prev_n;
-            const bool fits = S + h.n <= a.pcm_cap;
+            const bool fits = K7_PLACE + K7_SIZE <= a.pcm_cap;      // (windows: a frame that delivers nothing fits, below)
             if (h.number != want) { h.status = FHIP_VERIFY_NUMBER; h.bit = 32; }
+#if FHIP_K7_WINDOWS
+            else if (!size_ok || (!fits && cnt > 0)) { h.status = FHIP_VERIFY_NUMBER; h.bit = 16; }
+#else
             else if (!size_ok || !fits) { h.status = FHIP_VERIFY_NUMBER; h.bit = 16; }
+#endif
         }
         long long gtot = 0;
-        const long long G = good + block_excl_scan(live && h.status == FHIP_VERIFY_OK ? (long long)h.n : 0ll, scratch,
+        const long long G = good + block_excl_scan(live && h.status == FHIP_VERIFY_OK ? (long long)K7_SIZE : 0ll, scratch,
                                                    DHDR_T / 64, &gtot);
         good += gtot;
         if constexpr (SEG) {
@@ -151,16 +214,21 @@ __global__ void __launch_bounds__(DHDR_T) k_decode_frames(DecodeArgs a)
                 // the segment begins at S, and G good samples lie before it: they end the count of the last segment
                 // with a frame and start this one's (two adds per segment, in any order).  Empty segments in front
                 // of this frame begin here as well.
-                a.seg_start[seg] = S;
+                a.seg_start[seg] = K7_PLACE;
                 atomicAdd((unsigned long long *)&a.seg_samples[seg], (unsigned long long)-G);
                 int sp = seg - 1;
-                for (; sp >= 0 && a.seg_first[sp] == f; sp--) a.seg_start[sp] = S;
+                for (; sp >= 0 && a.seg_first[sp] == f; sp--) a.seg_start[sp] = K7_PLACE;
                 if (sp >= 0) atomicAdd((unsigned long long *)&a.seg_samples[sp], (unsigned long long)G);
             }
         }
+#if FHIP_K7_WINDOWS
+        if (live && h.status == FHIP_VERIFY_OK && cnt > 0) atomicMax(&s_end, (unsigned long long)(place + cnt));
+        if (live) w.clip[f] = DecodeClip{place, lo, h.status == FHIP_VERIFY_OK ? cnt : 0};
+#else
         if (live && h.status == FHIP_VERIFY_OK) atomicMax(&s_end, (unsigned long long)(S + h.n));
+#endif
         if (live) {
-            vf.rel_start = S;
+            vf.rel_start = K7_PLACE;
             vf.n = h.n;
             vf.hdr_bits = h.hdr_bits;
             vf.ch_code = h.ch_code;
@@ -178,7 +246,11 @@ __global__ void __launch_bounds__(DHDR_T) k_decode_frames(DecodeArgs a)
         if constexpr (SEG) {
             // segments behind the last frame are empty and begin at the batch's end; the last one with a frame ends there
             int sp = a.nsegs - 1;
+#if FHIP_K7_WINDOWS
+            for (; sp >= 0 && a.seg_first[sp] == count; sp--) a.seg_start[sp] = dbase;
+#else
             for (; sp >= 0 && a.seg_first[sp] == count; sp--) a.seg_start[sp] = sbase;
+#endif
             if (sp >= 0) atomicAdd((unsigned long long *)&a.seg_samples[sp], (unsigned long long)good);
         }
     }
@@ -197,8 +269,16 @@ __device__ __forceinline__ int32_t rd_signed(const Bits &bs, long long p, int w)
     return (int32_t)v;
 }
 
+// The window mode: the frame's clip (DecodeClip, left by the header pass) replaces [rel_start, rel_start + n) in the
+// write-out; everything before it is the same code.
+#if FHIP_K7_WINDOWS
+__global__ void __launch_bounds__(DT) k_decode_windows(DecodeWindowArgs w)
+{
+    const DecodeArgs &a = w.d;
+#else
 __global__ void __launch_bounds__(DT) k_decode(DecodeArgs a)
 {
+#endif
     __shared__ uint8_t fb_lds[DFB_CAP];
     __shared__ int32_t ybuf[RING];
     __shared__ SubHdr s_sh;
@@ -397,11 +477,20 @@ __global__ void __launch_bounds__(DT) k_decode(DecodeArgs a)
         if (key == KEY_NONE) {
             // the frame passed: wasted-bit shift, channel recombination, interleave.  k_decode_frames placed
             // [rel_start, rel_start + n) inside [0, pcm_cap)
+#if FHIP_K7_WINDOWS
+            // the clip [lo, lo + cnt) of the frame goes to [dst, dst + cnt): i runs over the clip alone, inside the frame
+            // whatever the table holds, and g = dst + (i - lo)
+            const DecodeClip cl = w.clip[f];
+            const long long S = cl.dst - cl.lo;
+            const int i0 = max(cl.lo, 0), i1 = min(cl.lo + cl.cnt, n);
+#else
             const long long S = vf.rel_start;
+            const int i0 = 0, i1 = n;
+#endif
             int16_t *const out16 = reinterpret_cast<int16_t *>(a.pcm);
             int32_t *const out32 = reinterpret_cast<int32_t *>(a.pcm);
             const bool s16 = a.pcm_format == FHIP_PCM_S16;
-            for (int i = lane; i < n; i += DT) {
+            for (int i = i0 + lane; i < i1; i += DT) {
                 const long long g = S + i;
                 if (g < 0 || g >= a.pcm_cap) continue;
                 if (vf.ch_code >= 8) {
@@ -449,6 +538,7 @@ __global__ void __launch_bounds__(DT) k_decode(DecodeArgs a)
     }
 }
 
+#if !FHIP_K7_WINDOWS
 __global__ void k_decode_final(DecodeArgs a)
 {
     const unsigned long long k = a.key[0];
@@ -473,7 +563,36 @@ __global__ void __launch_bounds__(DT) k_decode_seg_final(DecodeArgs a)
     }
 }
 
+#endif
+
 }  // namespace
+
+#if FHIP_K7_WINDOWS
+hipError_t launch_decode_windows(hipStream_t st, const DecodeWindowArgs &w)
+{
+    const DecodeArgs &a = w.d;
+    if (!a.seg_first || a.nsegs < 1 || !a.seg_number || !a.seg_variable || !a.seg_start || !a.seg_samples || !a.seg_failed ||
+        !w.seg_skip || !w.seg_take || (a.nframes > 0 && (!a.recs || !w.clip)))
+        return hipErrorInvalidValue;
+    note_launch("k_decode_frames windows");
+    hipLaunchKernelGGL(k_decode_frames_windows, dim3(1), dim3(DHDR_T), 0, st, w);
+    if (a.nframes > 0) {
+        note_launch("k_decode windows");
+        hipLaunchKernelGGL(k_decode_windows, dim3(a.nframes), dim3(DT), 0, st, w);
+    }
+    return launch_decode_end(st, a);
+}
+#else
+hipError_t launch_decode_end(hipStream_t st, const DecodeArgs &a)
+{
+    note_launch("k_decode_final");
+    hipLaunchKernelGGL(k_decode_final, dim3(1), dim3(1), 0, st, a);
+    if (a.seg_first && a.nframes > 0) {
+        note_launch("k_decode_seg_final");
+        hipLaunchKernelGGL(k_decode_seg_final, dim3(a.nsegs), dim3(DT), 0, st, a);
+    }
+    return hipGetLastError();
+}
 
 hipError_t launch_decode(hipStream_t st, const DecodeArgs &a)
 {
@@ -492,13 +611,8 @@ hipError_t launch_decode(hipStream_t st, const DecodeArgs &a)
         note_launch("k_decode");
         hipLaunchKernelGGL(k_decode, dim3(a.nframes), dim3(DT), 0, st, a);
     }
-    note_launch("k_decode_final");
-    hipLaunchKernelGGL(k_decode_final, dim3(1), dim3(1), 0, st, a);
-    if (seg && a.nframes > 0) {
-        note_launch("k_decode_seg_final");
-        hipLaunchKernelGGL(k_decode_seg_final, dim3(a.nsegs), dim3(DT), 0, st, a);
-    }
-    return hipGetLastError();
+    return launch_decode_end(st, a);
 }
+#endif
 
 }  // namespace fhip

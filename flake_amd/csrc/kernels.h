@@ -378,6 +378,26 @@ struct DecodeArgs {
     int32_t *seg_failed = nullptr;               // [nsegs] out: index in the batch of its first failing frame, -1: none
 };
 hipError_t launch_decode(hipStream_t st, const DecodeArgs &a);
+// k_decode_final and, in the segment mode, k_decode_seg_final: the end of launch_decode and of launch_decode_windows.
+hipError_t launch_decode_end(hipStream_t st, const DecodeArgs &a);
+
+// K7's window mode (k7_decode_windows.hip): the segment mode, of which every table of d is required, with a window of
+// samples per segment.  A frame whose samples are [o, o + n) of its segment -- o the sizes of the segment's good headers
+// before it -- delivers [max(o, skip), min(o + n, skip + take)), and what the batch delivers lies back to back in pcm:
+// seg_start, seg_samples, nsamples, written_end and pcm_cap are about the delivered samples.  Every frame is decoded
+// and checked in full.  The header pass leaves each frame's clip in clip[], which the frame pass writes out by.
+// Launches: "k_decode_frames windows", "k_decode windows", then launch_decode_end's.
+struct DecodeClip {
+    long long dst;          // where the clip's first sample goes in pcm
+    int lo, cnt;            // the clip: samples lo .. lo + cnt of the frame (cnt 0: nothing)
+};
+struct DecodeWindowArgs {
+    DecodeArgs d;
+    const long long *seg_skip;                   // [nsegs] samples to drop from the segment's front (below 0: 0)
+    const long long *seg_take;                   // [nsegs] the most to deliver behind them; < 0: to the segment's end
+    DecodeClip *clip;                            // [nframes] workspace
+};
+hipError_t launch_decode_windows(hipStream_t st, const DecodeWindowArgs &w);
 
 // K6 (k6_md5.hip): the STREAMINFO MD5 of many streams, one lane per stream.  The update hashes, for stream s, the
 // blocks seg_block[seg_first[s] .. seg_first[s + 1]) -- indices of block_vals-sample blocks (block_size * channels

@@ -30,6 +30,11 @@
  * does not decode, or an MD5 mismatch, ends in a non-zero exit status with the frame named on stderr.
  *
  *   flake_amd_cli --decode --set OUTDIR a.flac b.flac ...
+ *   flake_amd_cli --decode [--set OUTDIR] --skip N --until N ...
+ *       a window of samples out of every file (sample counts, as flac's options of those names; --until is exclusive, 0 or
+ *       absent: to the end): flake_amd_decode_set_windows on a set without MD5 -- the frames that overlap the window
+ *       are found from the headers, indexing starts at the file's SEEKTABLE point at or before --skip where it has one
+ *       (the whole file where that piece is refused), the WAV holds exactly the window and the MD5 is not checked.
  *
  * run_decode_set decodes files of one format (flac_set_load) through one decode set (flake_amd_decode_set_*): the
  * device finds every file's frames, one call per max_block_size among the files (flac_set_index; the CPU with
@@ -69,6 +74,8 @@ static void wr32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v
 typedef struct {
     int level, bsize, synth, synth_streams, channels, bps, verify;
     const char *setdir, *in, *out;
+    int window;                      /* --skip or --until was given */
+    unsigned long long skip, until;  /* samples; until 0: to the end */
     char **pos;
     int npos;
 } opts;
@@ -484,6 +491,8 @@ typedef struct {
     const char *path;
     uint8_t *file;
     size_t len, pos;                 /* the file, and where its next frame starts */
+    const uint8_t *seek;             /* its SEEKTABLE block's content, where it has one */
+    size_t seek_len;
     FlakeAmdStreaminfo si;
     int *sizes;                      /* every frame's size (flac_set_index, over the whole file) */
     size_t used;                     /* ... the bytes they cover */
@@ -530,7 +539,9 @@ static int flac_load(const char *path, flac_in *f)
     int last = 0;
     while (!last && pos + 4 <= f->len) {                                     /* skip every metadata block */
         last = f->file[pos] >> 7;
-        pos += 4 + ((size_t)f->file[pos + 1] << 16 | (size_t)f->file[pos + 2] << 8 | f->file[pos + 3]);
+        const size_t blen = (size_t)f->file[pos + 1] << 16 | (size_t)f->file[pos + 2] << 8 | f->file[pos + 3];
+        if ((f->file[pos] & 0x7F) == 3 && pos + 4 + blen <= f->len) { f->seek = f->file + pos + 4; f->seek_len = blen; }   /* (kept) */
+        pos += 4 + blen;
     }
     if (!last || pos > f->len) { fprintf(stderr, "%s: metadata runs past the file\n", path); return 1; }
     f->pos = pos;
@@ -968,13 +979,168 @@ out:
     return rc;
 }
 
+/* ---- --decode --skip N --until N: a window of samples out of every file ---- */
+
+/* The frames the window needs, by the file's SEEKTABLE: the piece from the last seek point at or before `skip` to the first
+ * one at or behind `until` is indexed on its own.  0 with f->pos, f->sizes, f->nframes describing the piece; -1 where the
+ * file has no usable table or the piece is refused (a point that lies inside a frame): the whole file is indexed then */
+static int seek_piece(flac_in *f, unsigned long long skip, unsigned long long until)
+{
+    if (!f->seek || !f->seek_len) return -1;
+    const long long np = flake_amd_read_seektable(f->seek, f->seek_len, NULL, 0);
+    if (np < 1) return -1;
+    FlakeAmdSeekPoint *pts = (FlakeAmdSeekPoint *)malloc(sizeof *pts * (size_t)np);
+    int rc = -1;
+    if (pts && flake_amd_read_seektable(f->seek, f->seek_len, pts, (int)np) == np) {
+        const long long a = flake_amd_seek_lookup(pts, (int)np, skip);
+        long long b = until ? flake_amd_seek_lookup(pts, (int)np, until - 1) + 1 : np;     /* the first point at or behind until */
+        const size_t left = f->len - f->pos;
+        const size_t from = a < 0 ? 0 : (size_t)pts[a].offset, to = b < np ? (size_t)pts[b].offset : left;
+        if ((a < 0 || pts[a].offset < left) && (b >= np || pts[b].offset <= left) && from < to) {
+            const int cap = (int)((to - from) / 8 + 2);
+            int *sizes = (int *)malloc(sizeof(int) * (size_t)cap);
+            size_t used = 0;
+            const long long nf = sizes ? flake_amd_index_frames(&f->si, f->file + f->pos + from, to - from, sizes, cap, &used) : -1;
+            if (nf > 0 && used == to - from) {
+                f->pos += from;
+                f->sizes = sizes;
+                f->nframes = nf;
+                f->used = used;
+                rc = 0;
+            } else {
+                free(sizes);
+            }
+        }
+    }
+    free(pts);
+    return rc;
+}
+
+static int run_decode_windows(const opts *o)
+{
+    const int single = !o->setdir, n = single ? 1 : o->npos;
+    if (n < 1) { fprintf(stderr, "--decode --set needs input files\n"); return 2; }
+    int rc = 1;
+    FlakeAmdStreaminfo like;
+    FlakeAmdDecodeSet *g = NULL;
+    int *fow = NULL, *sizes = NULL, *status = NULL, *pieced = NULL;
+    unsigned *fixed = NULL;
+    unsigned long long *first = NULL;
+    long long *count = NULL, *got = NULL;
+    uint8_t *bytes = NULL, *raw = NULL;
+    void *pcm = NULL;
+    flac_in *fs = (flac_in *)calloc((size_t)n, sizeof *fs);
+    if (!fs) goto out;
+    if (single) {
+        if (flac_load(o->pos[0], &fs[0])) goto out;
+        snprintf(fs[0].name, sizeof fs[0].name, "%s", o->pos[1]);
+        like = fs[0].si;
+        if (!like.max_block_size || like.max_block_size < 16) like.max_block_size = like.max_block_size ? 16 : 65535u;
+    } else if (flac_set_load(fs, o->pos, n, o->setdir, "wav", "decode", &like)) {
+        goto out;
+    }
+    fprintf(stderr, "--skip / --until: the MD5 of the decoded samples is not checked\n");
+    const size_t nch = like.channels;
+    const int narrow = like.bits_per_sample == 16;
+    g = flake_amd_decode_set_open(&like, n, FLAKE_AMD_SET_MD5_OFF);
+    if (!g) { fprintf(stderr, "decode set init failed: %s\n", flake_amd_decode_set_last_error(NULL)); goto out; }
+    /* the frames: a piece between two seek points where the file's SEEKTABLE gives one, else the whole file */
+    pieced = (int *)calloc((size_t)n, sizeof(int));
+    if (!pieced) { fprintf(stderr, "out of memory\n"); goto out; }
+    for (int i = 0; i < n; i++)
+        if (!fs[i].skip && seek_piece(&fs[i], o->skip, o->until) == 0) pieced[i] = fs[i].skip = 1;    /* (hidden from the indexer) */
+    flac_set_index(fs, n, index_on_host() ? NULL : g);
+    for (int i = 0; i < n; i++)
+        if (pieced[i]) fs[i].skip = 0;
+    /* one window per file, all in one call */
+    fow = (int *)calloc((size_t)n, sizeof(int));
+    fixed = (unsigned *)calloc((size_t)n, sizeof(unsigned));
+    first = (unsigned long long *)calloc((size_t)n, sizeof *first);
+    count = (long long *)calloc((size_t)n, sizeof *count);
+    got = (long long *)calloc((size_t)n, sizeof *got);
+    status = (int *)calloc((size_t)n, sizeof(int));
+    if (!fow || !fixed || !first || !count || !got || !status) { fprintf(stderr, "out of memory\n"); goto out; }
+    size_t nbytes = 0, cap = 0;
+    long long nframes = 0, most = 0;
+    for (int i = 0; i < n; i++) {
+        const flac_in *f = &fs[i];
+        if (f->skip || f->nframes <= 0) continue;
+        const unsigned maxn = f->si.max_block_size ? f->si.max_block_size : 65535u;
+        const long long room = f->nframes * (long long)maxn;          /* no run delivers more */
+        fow[i] = (int)f->nframes;
+        fixed[i] = f->si.min_block_size == f->si.max_block_size ? f->si.max_block_size : 0;
+        first[i] = o->skip;
+        count[i] = o->until ? (o->until > o->skip ? (long long)(o->until - o->skip < (unsigned long long)room ? o->until - o->skip : (unsigned long long)room) : 0)
+                            : room;
+        nframes += f->nframes;
+        nbytes += f->used;
+        cap += (size_t)count[i];
+        if (count[i] > most) most = count[i];
+    }
+    bytes = (uint8_t *)malloc(nbytes ? nbytes : 1);
+    sizes = (int *)malloc(sizeof(int) * (size_t)(nframes ? nframes : 1));
+    pcm = malloc((cap ? cap : 1) * nch * (narrow ? 2 : 4));
+    raw = (uint8_t *)malloc((size_t)(most ? most : 1) * nch * ((like.bits_per_sample + 7) / 8));
+    if (!bytes || !sizes || !pcm || !raw) { fprintf(stderr, "out of memory\n"); goto out; }
+    {
+        size_t at = 0;
+        long long fr = 0;
+        for (int i = 0; i < n; i++) {
+            const flac_in *f = &fs[i];
+            if (!fow[i]) continue;
+            memcpy(bytes + at, f->file + f->pos, f->used);
+            memcpy(sizes + fr, f->sizes, sizeof(int) * (size_t)f->nframes);
+            at += f->used;
+            fr += f->nframes;
+        }
+    }
+    long long decoded = 0;
+    if (flake_amd_decode_set_windows(g, n, fow, bytes, nbytes, sizes, fixed, first, count, pcm, narrow ? 2 : 4, cap, got, status,
+                                     &decoded) < 0) {
+        fprintf(stderr, "decode error: %s\n", flake_amd_decode_set_last_error(g));
+        goto out;
+    }
+    size_t at = 0;
+    for (int i = 0; i < n; i++) {
+        flac_in *f = &fs[i];
+        if (f->skip) continue;
+        f->fo = wav_begin(f->name);
+        if (!f->fo) goto out;
+        if (got[i] < 0) {
+            fprintf(stderr, "%s: the window does not decode (status %d)\n", f->path, status[i]);
+            f->bad = 1;
+            at += (size_t)count[i];
+        } else {
+            wav_samples(f->fo, &like, (const char *)pcm + at * nch * (narrow ? 2 : 4), (size_t)got[i], raw);
+            f->total = (unsigned long long)got[i];
+            at += (size_t)got[i];
+        }
+        wav_end(f->fo, &like, f->total);
+        f->fo = NULL;
+        if (!f->bad) fprintf(stderr, "%s: %llu sample-frames decoded\n", f->path, f->total);
+    }
+    fprintf(stderr, "%lld of %lld frames decoded\n", decoded, nframes);
+    rc = any_bad(fs, n);
+out:
+    if (g) flake_amd_decode_set_close(g);
+    free(fow); free(fixed); free(first); free(count); free(got); free(status); free(pieced);
+    free(bytes); free(sizes); free(pcm); free(raw);
+    flac_free(fs, n);
+    return rc;
+}
+
 static int run_decode_mode(const opts *o, const char *argv0)
 {
-    if (o->setdir) return run_decode_set(o);
-    if (o->npos != 2) {
-        fprintf(stderr, "usage: %s --decode in.flac out.wav\n       %s --decode --set OUTDIR a.flac b.flac ...\n", argv0, argv0);
+    if (!o->setdir && o->npos != 2) {
+        if (o->window)
+            fprintf(stderr, "usage: %s --decode --skip N --until N in.flac out.wav\n"
+                            "       %s --decode --set OUTDIR --skip N --until N a.flac b.flac ...\n", argv0, argv0);
+        else
+            fprintf(stderr, "usage: %s --decode in.flac out.wav\n       %s --decode --set OUTDIR a.flac b.flac ...\n", argv0, argv0);
         return 2;
     }
+    if (o->window) return run_decode_windows(o);
+    if (o->setdir) return run_decode_set(o);
     return run_decode(o->pos[0], o->pos[1]);
 }
 
@@ -986,7 +1152,8 @@ enum {
     A_SET_FIRST = 8,       /* --set OUTDIR, the first one only */
     A_SYNTH = 16,          /* --synth N, --channels N, --bps N */
     A_STREAMS = 32,        /* --synth-streams N */
-    A_VERIFY = 64          /* --verify */
+    A_VERIFY = 64,         /* --verify */
+    A_WINDOW = 128         /* --skip N, --until N (samples) */
 };
 
 typedef struct {
@@ -997,7 +1164,7 @@ typedef struct {
 
 static const mode modes[] = {
     {"--recode", A_LEVEL | A_BSIZE | A_SET | A_VERIFY, run_recode_set},
-    {"--decode", A_SET_FIRST, run_decode_mode},
+    {"--decode", A_SET_FIRST | A_WINDOW, run_decode_mode},
     {"--set", A_LEVEL | A_BSIZE | A_SET | A_SYNTH | A_STREAMS | A_VERIFY, run_set},
     {NULL, A_LEVEL | A_BSIZE | A_SYNTH | A_VERIFY, run_encode},
 };
@@ -1029,6 +1196,8 @@ int main(int argc, char **argv)
         else if ((acc & A_SYNTH) && val && !strcmp(w, "--channels")) o.channels = atoi(argv[++i]);
         else if ((acc & A_SYNTH) && val && !strcmp(w, "--bps")) o.bps = atoi(argv[++i]);
         else if ((acc & A_VERIFY) && !strcmp(w, "--verify")) o.verify = 1;
+        else if ((acc & A_WINDOW) && val && !strcmp(w, "--skip")) { o.skip = strtoull(argv[++i], NULL, 10); o.window = 1; }
+        else if ((acc & A_WINDOW) && val && !strcmp(w, "--until")) { o.until = strtoull(argv[++i], NULL, 10); o.window = 1; }
         else if (i != at) {
             o.pos[o.npos++] = argv[i];
             /* (the single-file form: the first word is the input unless --synth came before it, the last the output) */

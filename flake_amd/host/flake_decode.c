@@ -15,6 +15,7 @@
 #include "flake_amd.h"
 #include "flakehip.h"
 #include "host_internal.h"
+#include "seektable.h"
 
 /* ---- STREAMINFO ------------------------------------------------------ */
 
@@ -44,6 +45,18 @@ int fa_parse_header(const FlakeAmdStreaminfo *si, const unsigned char *d, size_t
     const flac_format f = {(int)si->channels, (int)si->bits_per_sample, (int)si->sample_rate,
                            si->max_block_size > 65535u ? 0 : (int)si->max_block_size};
     return flac_header_ok(&f, d, (long long)avail, h) ? 0 : -1;
+}
+
+/* ---- SEEKTABLE ----------------------------------------------------------- */
+
+FLAKE_AMD_API long long flake_amd_read_seektable(const unsigned char *block, size_t bytes, FlakeAmdSeekPoint *points, int cap)
+{
+    return fa_read_seektable(block, bytes, points, cap);
+}
+
+FLAKE_AMD_API long long flake_amd_seek_lookup(const FlakeAmdSeekPoint *points, int n, unsigned long long sample)
+{
+    return fa_seek_lookup(points, n, sample);
 }
 
 /* ---- frame discovery --------------------------------------------------- */

@@ -14,6 +14,7 @@
 #include "flakehip.h"
 #include "host_internal.h"
 #include "decode_set_plan.h"
+#include "decode_window_plan.h"
 
 typedef struct {
     long long frames_done;        /* frames committed so far */
@@ -41,6 +42,20 @@ struct FlakeAmdDecodeSet {
     fhip_verify_rec *recs;
     long long *run_off;           /* the last call's run offsets in pcm */
     int run_off_cap, run_off_n;
+    /* flake_amd_decode_set_windows: the planner's tables (max_batch entries each), the selections and the runs' tables
+     * (one per window, grown on demand), the offsets of the call's frames and the staged bytes of a batch */
+    fa_dw_batch wb;
+    fa_dw_sel *wsel;
+    const unsigned char **wdata;
+    const int **wsizes;
+    const size_t **woff;
+    long long *wat;
+    int wcap;
+    size_t *foff;
+    size_t foff_cap;
+    unsigned char *wstage;
+    size_t wstage_cap;
+    int32_t *wfb;
     char err[384];
 };
 
@@ -106,9 +121,20 @@ FLAKE_AMD_API FlakeAmdDecodeSet *flake_amd_decode_set_open(const FlakeAmdStreami
     g->seg_failed = (int32_t *)calloc(mb, sizeof(int32_t));
     g->recs = (fhip_verify_rec *)calloc(mb, sizeof(fhip_verify_rec));
     g->seg_ok = (unsigned char *)calloc(mb, 1);
+    g->wb.seg_first = (int32_t *)calloc(mb + 1, sizeof(int32_t));
+    g->wb.seg_number = (int64_t *)calloc(mb, sizeof(int64_t));
+    g->wb.seg_variable = (int32_t *)calloc(mb, sizeof(int32_t));
+    g->wb.seg_skip = (int64_t *)calloc(mb, sizeof(int64_t));
+    g->wb.seg_take = (int64_t *)calloc(mb, sizeof(int64_t));
+    g->wb.seg_win = (int32_t *)calloc(mb, sizeof(int32_t));
+    g->wb.seg_frame0 = (int32_t *)calloc(mb, sizeof(int32_t));
+    g->wb.seg_last = (int32_t *)calloc(mb, sizeof(int32_t));
+    g->wfb = (int32_t *)calloc(mb, sizeof(int32_t));
     const int have = g->st && g->sx && g->digests && b->seg_first && b->seg_number && b->seg_variable && b->seg_stream &&
                      b->seg_run && b->seg_frame0 && b->seg_prev && b->md5_first && b->md5_range && b->last_seg &&
-                     b->planned && g->seg_start && g->seg_samples && g->seg_failed && g->recs && g->seg_ok;
+                     b->planned && g->seg_start && g->seg_samples && g->seg_failed && g->recs && g->seg_ok &&
+                     g->wb.seg_first && g->wb.seg_number && g->wb.seg_variable && g->wb.seg_skip && g->wb.seg_take &&
+                     g->wb.seg_win && g->wb.seg_frame0 && g->wb.seg_last && g->wfb;
     int rc = have ? fhip_create(&g->hip, ed ? atoi(ed) : 0, &p, g->max_batch) : FHIP_E_NOMEM;
     if (rc == FHIP_OK && ds_device_md5(g)) {
         g->states = (fhip_md5_state *)fhip_device_alloc(ns * sizeof(fhip_md5_state));
@@ -351,6 +377,186 @@ FLAKE_AMD_API long long flake_amd_decode_set_device_batches(const FlakeAmdDecode
     return g ? g->device_batches : -1;
 }
 
+/* ---- windows ------------------------------------------------------------------------------------------------------
+ * Stateless, as flake_amd_decode_set_index is: the set lends its handle and its format.  decode_window_plan.h selects
+ * the frames and cuts the batches; each batch's selected bytes are staged back to back and go through
+ * fhip_decode_frames_windows, which delivers the batch's clips back to back where the call's output has got to.  A window
+ * that failed keeps the room it asked for: what the batch left behind it is moved up by the difference. */
+static int ds_grow(void **p, size_t *cap, size_t want, size_t elem)
+{
+    if (want <= *cap) return 0;
+    void *n = realloc(*p, want * elem);
+    if (!n) return -1;
+    *p = n;
+    *cap = want;
+    return 0;
+}
+
+FLAKE_AMD_API long long flake_amd_decode_set_windows(FlakeAmdDecodeSet *g, int nwin, const int *frames_of_win,
+        const unsigned char *stream, size_t bytes, const int *frame_sizes,
+        const unsigned *fixed_block_size, const unsigned long long *first_sample, const long long *count,
+        void *pcm, int sample_bytes, size_t pcm_cap_samples,
+        long long *win_samples, int *win_status, long long *frames_decoded)
+{
+    if (!g) return -1;
+    g->err[0] = 0;
+    if (nwin < 0 || (nwin > 0 && (!frames_of_win || !fixed_block_size || !first_sample || !count || !win_samples || !win_status)) ||
+        (!stream && bytes) || (!pcm && pcm_cap_samples) || (sample_bytes != 2 && sample_bytes != 4)) {
+        snprintf(g->err, sizeof g->err, "bad argument");
+        return -1;
+    }
+    if (sample_bytes == 2 && g->si.bits_per_sample > 16) {
+        snprintf(g->err, sizeof g->err, "2-byte samples need bits_per_sample <= 16");
+        return -1;
+    }
+    long long nf = 0, asked = 0;
+    for (int w = 0; w < nwin; w++) {
+        if (frames_of_win[w] < 0 || count[w] < 0 || count[w] > (long long)pcm_cap_samples - asked) {
+            snprintf(g->err, sizeof g->err, "%s", frames_of_win[w] < 0 || count[w] < 0 ? "negative count"
+                                                  : "pcm_cap_samples is below the samples the windows ask for");
+            return -1;
+        }
+        asked += count[w];
+        nf += frames_of_win[w];
+    }
+    if (nf && !frame_sizes) { snprintf(g->err, sizeof g->err, "bad argument"); return -1; }
+    {
+        size_t cap = g->foff_cap;
+        if (ds_grow((void **)&g->foff, &cap, (size_t)nf + 1, sizeof(size_t))) goto nomem;
+        g->foff_cap = cap;
+        size_t wc = (size_t)g->wcap, wc2 = wc, wc3 = wc, wc4 = wc, wc5 = wc;
+        if (ds_grow((void **)&g->wsel, &wc, (size_t)nwin + 1, sizeof *g->wsel) ||
+            ds_grow((void **)&g->wsizes, &wc2, (size_t)nwin + 1, sizeof *g->wsizes) ||
+            ds_grow((void **)&g->woff, &wc3, (size_t)nwin + 1, sizeof *g->woff) ||
+            ds_grow((void **)&g->wat, &wc4, (size_t)nwin + 1, sizeof *g->wat) ||
+            ds_grow((void **)&g->wdata, &wc5, (size_t)nwin + 1, sizeof *g->wdata)) {
+            g->wcap = 0;                              /* (whichever grew is at least as large as before) */
+            goto nomem;
+        }
+        g->wcap = (int)wc;
+    }
+    size_t at = 0;
+    g->foff[0] = 0;
+    for (long long f = 0; f < nf; f++) {
+        if (frame_sizes[f] < 1 || (size_t)frame_sizes[f] > bytes - at) {
+            snprintf(g->err, sizeof g->err, "the frame sizes run past the stream");
+            return -1;
+        }
+        at += (size_t)frame_sizes[f];
+        g->foff[f + 1] = at;
+    }
+    if (fhip_set_pcm_format(g->hip, sample_bytes == 2 ? FHIP_PCM_S16 : FHIP_PCM_S32) != FHIP_OK) {
+        snprintf(g->err, sizeof g->err, "%s", fhip_last_error(g->hip));
+        return -1;
+    }
+    /* the selection */
+    const flac_format fmt = {(int)g->si.channels, (int)g->si.bits_per_sample, (int)g->si.sample_rate,
+                             g->si.max_block_size > 65535u ? 0 : (int)g->si.max_block_size};
+    {
+        long long f = 0;
+        for (int w = 0; w < nwin; w++) {
+            g->wdata[w] = stream;                     /* (the offsets count from the call's first byte) */
+            g->wsizes[w] = frame_sizes + f;
+            g->woff[w] = g->foff + f;
+            fa_dw_select(&fmt, stream, g->wsizes[w], g->woff[w], frames_of_win[w], fixed_block_size[w], first_sample[w],
+                         count[w], &g->wsel[w]);
+            win_samples[w] = 0;
+            win_status[w] = 0;
+            g->wat[w] = -1;                           /* where the window's samples begin: not known yet */
+            f += frames_of_win[w];
+        }
+    }
+    const size_t nch = g->si.channels, unit = nch * (size_t)sample_bytes;
+    fa_dw_cursor cur;
+    memset(&cur, 0, sizeof cur);
+    fa_dw_batch *b = &g->wb;
+    long long decoded = 0;
+    long long out_at = 0;                             /* where the next delivered sample goes */
+    int settled = 0;                                  /* windows before this one have their place and count */
+    while (fa_dw_plan(&cur, nwin, g->wsel, &fmt, (const unsigned char *const *)g->wdata, (const int *const *)g->wsizes,
+                      (const size_t *const *)g->woff,
+                      g->max_batch, b) > 0) {
+        /* the batch's bytes, back to back */
+        {
+            size_t cap = g->wstage_cap;
+            if (ds_grow((void **)&g->wstage, &cap, b->nbytes, 1)) goto nomem;
+            g->wstage_cap = cap;
+        }
+        size_t sb = 0;
+        for (int k = 0; k < b->nsegs; k++) {
+            const int w = b->seg_win[k], f0 = b->seg_frame0[k], n = b->seg_first[k + 1] - b->seg_first[k];
+            const size_t len = g->woff[w][f0 + n] - g->woff[w][f0];
+            memcpy(g->wstage + sb, stream + g->woff[w][f0], len);
+            memcpy(g->wfb + b->seg_first[k], g->wsizes[w] + f0, (size_t)n * sizeof(int32_t));
+            sb += len;
+        }
+        /* windows that deliver nothing, or failed in the planner, before the batch's first one take their room now */
+        for (; settled < b->seg_win[0]; settled++) {
+            const fa_dw_sel *s = &g->wsel[settled];
+            if (g->wat[settled] < 0) g->wat[settled] = out_at;
+            if (s->status == FA_DW_FAILED_HEADER && !win_status[settled]) win_status[settled] = FHIP_VERIFY_HEADER;
+            if (win_status[settled]) out_at = g->wat[settled] + count[settled];
+        }
+        int64_t summary[4] = {0, 0, -1, 0}, nsmp = 0;
+        fhip_decode_in in = {g->wstage, (int64_t)sb, g->wfb, b->nframes, 0, -1};
+        fhip_decode_segments sg = {b->seg_first, b->nsegs, b->seg_number, b->seg_variable, g->seg_start, g->seg_samples,
+                                   g->seg_failed};
+        fhip_decode_windows wn = {b->seg_skip, b->seg_take};
+        const long long base = out_at;
+        fhip_decode_out out = {(int32_t *)((char *)pcm + (size_t)base * unit), (int64_t)pcm_cap_samples - base, g->recs,
+                               summary, &nsmp};
+        const int rc = fhip_decode_frames_windows(g->hip, &in, &sg, &wn, &out);
+        g->device_batches++;
+        decoded += b->nframes;
+        if (rc != FHIP_OK && rc != FHIP_E_VERIFY) {
+            snprintf(g->err, sizeof g->err, "fhip_decode_frames_windows: %s", fhip_last_error(g->hip));
+            return -1;
+        }
+        /* where each segment's samples belong; a failed window's are dropped and its room is what it asked for */
+        for (int k = 0; k < b->nsegs; k++) {
+            const int w = b->seg_win[k];
+            for (; settled < w; settled++) {          /* windows between two segments: nothing to decode */
+                const fa_dw_sel *s = &g->wsel[settled];
+                if (g->wat[settled] < 0) g->wat[settled] = out_at;
+                if (s->status == FA_DW_FAILED_HEADER && !win_status[settled]) win_status[settled] = FHIP_VERIFY_HEADER;
+                if (win_status[settled]) out_at = g->wat[settled] + count[settled];
+            }
+            if (g->wat[w] < 0) g->wat[w] = out_at;
+            if (!win_status[w] && g->seg_failed[k] >= 0) win_status[w] = (int)g->recs[g->seg_failed[k]].status;
+            if (!win_status[w] && g->wsel[w].status == FA_DW_FAILED_HEADER) win_status[w] = FHIP_VERIFY_HEADER;
+            b->seg_take[k] = out_at;                  /* (the table has been uploaded: it now holds the segment's target) */
+            if (!win_status[w]) {
+                win_samples[w] += g->seg_samples[k];
+                out_at += g->seg_samples[k];
+            } else {
+                g->seg_samples[k] = 0;
+            }
+            if (b->seg_last[k]) {
+                if (win_status[w]) out_at = g->wat[w] + count[w];
+                settled = w + 1;
+            }
+        }
+        for (int k = b->nsegs - 1; k >= 0; k--) {     /* targets never lie before the sources: from the back */
+            const long long src = base + g->seg_start[k], dst = b->seg_take[k];
+            if (g->seg_samples[k] > 0 && dst != src)
+                memmove((char *)pcm + (size_t)dst * unit, (char *)pcm + (size_t)src * unit, (size_t)g->seg_samples[k] * unit);
+        }
+    }
+    for (; settled < nwin; settled++)
+        if (g->wsel[settled].status == FA_DW_FAILED_HEADER && !win_status[settled]) win_status[settled] = FHIP_VERIFY_HEADER;
+    long long total = 0;
+    for (int w = 0; w < nwin; w++) {
+        if (g->wsel[w].status == FA_DW_FAILED_HEADER && !win_status[w]) win_status[w] = FHIP_VERIFY_HEADER;
+        if (win_status[w]) win_samples[w] = -1;
+        else total += win_samples[w];
+    }
+    if (frames_decoded) *frames_decoded = decoded;
+    return total;
+nomem:
+    snprintf(g->err, sizeof g->err, "out of memory");
+    return -1;
+}
+
 FLAKE_AMD_API int flake_amd_decode_set_index(FlakeAmdDecodeSet *g, unsigned max_block_size, const unsigned char *stream,
                                              const size_t *range_first, int nranges, int *frame_sizes, int cap,
                                              long long *range_frames, size_t *range_consumed)
@@ -378,5 +584,8 @@ FLAKE_AMD_API void flake_amd_decode_set_close(FlakeAmdDecodeSet *g)
     free(b->seg_frame0); free(b->seg_prev); free(b->md5_first); free(b->md5_range); free(b->last_seg); free(b->planned);
     free(g->seg_start); free(g->seg_samples); free(g->seg_failed); free(g->recs); free(g->seg_ok); free(g->run_off);
     free(g->st); free(g->sx); free(g->digests);
+    free(g->wb.seg_first); free(g->wb.seg_number); free(g->wb.seg_variable); free(g->wb.seg_skip); free(g->wb.seg_take);
+    free(g->wb.seg_win); free(g->wb.seg_frame0); free(g->wb.seg_last); free(g->wfb);
+    free(g->wsel); free((void *)g->wdata); free((void *)g->wsizes); free((void *)g->woff); free(g->wat); free(g->foff); free(g->wstage);
     free(g);
 }

@@ -250,6 +250,22 @@ FLAKE_AMD_API void flake_amd_set_close(FlakeAmdSet *g);
  */
 FLAKE_AMD_API int flake_amd_read_streaminfo(const unsigned char data34[34], FlakeAmdStreaminfo *si);
 /*
+ * A SEEKTABLE block's points (the block's content, without the 4-byte metadata header): 18 bytes each -- the first
+ * sample of a target frame, the frame's offset in bytes from the first frame's header, the frame's samples.
+ * flake_amd_read_seektable stores the first cap points that are not placeholders (sample number all ones) and returns
+ * how many such points the block holds; -1 for a null pointer, a length that is no multiple of 18, or points whose
+ * sample numbers are not strictly ascending.  flake_amd_seek_lookup returns the index of the last point at or before
+ * `sample`, -1 if there is none.  Pure host code.  Nothing in the library trusts a seek point: a caller starts
+ * flake_amd_index_frames at the point's byte and falls back to the stream's first frame where that returns -1.
+ */
+typedef struct FlakeAmdSeekPoint {
+    unsigned long long sample;
+    unsigned long long offset;
+    unsigned frame_samples;
+} FlakeAmdSeekPoint;
+FLAKE_AMD_API long long flake_amd_read_seektable(const unsigned char *block, size_t bytes, FlakeAmdSeekPoint *points, int cap);
+FLAKE_AMD_API long long flake_amd_seek_lookup(const FlakeAmdSeekPoint *points, int n, unsigned long long sample);
+/*
  * Frame discovery in a foreign stream, on the CPU (no call into the HIP layer): the sizes of the whole frames that
  * stream[0 .. bytes) begins with, at most cap of them, into frame_sizes; the return value is their count and *consumed
  * (optional) the bytes they cover, so that a caller can feed a file in pieces, each starting where the last one's
@@ -368,6 +384,32 @@ FLAKE_AMD_API long long flake_amd_decode_set_device_batches(const FlakeAmdDecode
 FLAKE_AMD_API int flake_amd_decode_set_index(FlakeAmdDecodeSet *g, unsigned max_block_size, const unsigned char *stream,
                                              const size_t *range_first, int nranges, int *frame_sizes, int cap,
                                              long long *range_frames, size_t *range_consumed);
+/*
+ * WINDOWS of samples out of many streams in shared device batches -- seeking.  Window w is count[w] samples per channel
+ * from absolute sample first_sample[w] of its stream, asked of a RUN: frames_of_win[w] consecutive frames of that stream,
+ * starting at any frame (a whole file's, or what flake_amd_index_frames found from a seek point on), all runs back to
+ * back in stream / frame_sizes as for flake_amd_decode_set_frames.  fixed_block_size[w] is the stream's STREAMINFO block
+ * size where minimum and maximum agree, else 0 (the run's first frame's size then stands for it; a variable-block-size
+ * stream carries sample numbers and needs neither).  The frames that overlap each window are found on the host from
+ * their headers (bisection: the numbers increase), only their bytes are uploaded, and the device delivers of them
+ * exactly the window (K7's window mode): nothing is trimmed afterwards.
+ *
+ * Stateless, like flake_amd_decode_set_index: the call runs on the set's handle with the set's format and neither
+ * reads nor changes any stream's numbering, hash or failed state.  The windows' samples lie back to back in pcm, in
+ * call order (sample_bytes 4 or 2 as for flake_amd_decode_set_frames).  win_samples[w] is what window w delivers: count[w],
+ * less where the run ends inside the window, 0 where the window begins before the run's first frame or at or behind
+ * its end, or count[w] is 0.  win_status[w] is 0 for a good window, else the FHIP_VERIFY_* status of its first failing
+ * frame (HEADER also where the search met something that is no header of the stream); such a window has
+ * win_samples[w] = -1 and keeps the room it ASKED for, count[w] samples of unspecified content, and every other window is
+ * delivered as if nothing had happened.  *frames_decoded (optional) is the number of frames handed to the device.
+ * Returns the good windows' samples; -1 with nothing written for a bad argument: sizes that do not add up inside bytes, a
+ * negative count, 2-byte samples above 16 bits, pcm_cap_samples below the sum of the counts.
+ */
+FLAKE_AMD_API long long flake_amd_decode_set_windows(FlakeAmdDecodeSet *g, int nwin, const int *frames_of_win,
+        const unsigned char *stream, size_t bytes, const int *frame_sizes,
+        const unsigned *fixed_block_size, const unsigned long long *first_sample, const long long *count,
+        void *pcm, int sample_bytes, size_t pcm_cap_samples,
+        long long *win_samples, int *win_status, long long *frames_decoded);
 FLAKE_AMD_API const char *flake_amd_decode_set_last_error(const FlakeAmdDecodeSet *g);
 FLAKE_AMD_API void flake_amd_decode_set_close(FlakeAmdDecodeSet *g);
 

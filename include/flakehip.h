@@ -690,6 +690,36 @@ FHIP_API int fhip_decode_frames_segments_dev(fhip_ctx *ctx, const fhip_decode_in
 FHIP_API int fhip_decode_frames_segments(fhip_ctx *ctx, const fhip_decode_in *in, const fhip_decode_segments *segs,
                                          const fhip_decode_out *out, const fhip_decode_md5 *md5);
 
+/*
+ * WINDOWS: of every segment only a range of its samples is delivered -- seeking, for the frames of many streams at once.
+ * seg_skip[s] (>= 0) samples per channel are dropped from the front of segment s and at most seg_take[s] delivered behind
+ * them (-1: to the segment's end); both are counted over the sizes of the segment's good headers, as placement is.  A
+ * frame whose samples are [o, o + n) of its segment -- o the sum of the sizes carried by the good headers before it in
+ * the segment -- delivers [max(o, skip), min(o + n, skip + take)), which may be empty; skip may exceed the first frame
+ * or the whole segment.  What the batch delivers lies back to back in pcm, in batch order, and the outputs speak of
+ * delivered samples: seg_start[s] is where segment s's begin, seg_samples[s] how many it delivers (of the frames whose
+ * header, number and place were good, as before), nsamples the batch's total; pcm_cap and the refusal of a frame that
+ * does not fit (NUMBER, bit 16) are about the delivered range, and a frame that delivers nothing always fits.  Every
+ * frame of the batch is still decoded and checked in full -- the recurrence needs the whole frame, the CRC-16 covers it
+ * -- so records, summary and seg_failed keep their meaning: a frame that fails names itself even where all of its
+ * samples are clipped away.  Both PCM formats.  The launch list is "k_decode_frames windows", "k_decode windows",
+ * "k_decode_final", "k_decode_seg_final"; timed as "k_decode".
+ */
+typedef struct fhip_decode_windows {
+    const int64_t *seg_skip;      /* [nsegs] >= 0 */
+    const int64_t *seg_take;      /* [nsegs] >= 0, or -1 */
+} fhip_decode_windows;
+
+/* As fhip_decode_frames_segments_dev, with both tables of win in DEVICE memory (their values are the caller's: a
+ * negative skip counts as 0, a negative take as -1).  FHIP_E_INVALID with nothing queued and an empty launch list also
+ * for segs == NULL, win == NULL or a null table. */
+FHIP_API int fhip_decode_frames_windows_dev(fhip_ctx *ctx, const fhip_decode_in *in, const fhip_decode_segments *segs,
+                                            const fhip_decode_windows *win, const fhip_decode_out *out);
+/* As fhip_decode_frames_segments without md5 (windows are not hashed), with HOST tables in win: also FHIP_E_INVALID,
+ * nothing queued, for a negative seg_skip or a seg_take below -1.  Only the delivered samples are downloaded. */
+FHIP_API int fhip_decode_frames_windows(fhip_ctx *ctx, const fhip_decode_in *in, const fhip_decode_segments *segs,
+                                        const fhip_decode_windows *win, const fhip_decode_out *out);
+
 /* ---- frame discovery (K8) --------------------------------------------- */
 
 /*
@@ -879,7 +909,7 @@ FHIP_API int fhip_get_kernel_times(fhip_ctx *ctx, const char **names, double *ms
  * one or two workgroups per tile), "tail" (K2 runs inside K1), "fused" (K1 applies K0's decisions),
  * "narrow" (16-bit sample rows).  The calls that start a new list are the encode entries
  * (fhip_encode_subframes*, fhip_frames_packed_begin / fhip_encode_frames_packed, the VBS entries)
- * and fhip_prepare_ahead, the fhip_md5_* entries, fhip_decode_frames(_dev), fhip_decode_frames_segments(_dev, _keep),
+ * and fhip_prepare_ahead, the fhip_md5_* entries, fhip_decode_frames(_dev), fhip_decode_frames_segments(_dev, _keep), fhip_decode_frames_windows(_dev),
  * fhip_index_frames(_dev), fhip_gather_spans_dev and fhip_frames_packed_gather.  A host-side record: it adds no device work.  (One exception:
  * "k_md5_streams<int16_t,2> fast" / "... general" name a choice that is made on the device when the block shape
  * allows the fast path; asking for the list then waits for that launch.)  names[0 .. cap) receive
