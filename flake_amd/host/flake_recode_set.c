@@ -101,8 +101,13 @@ FLAKE_AMD_API FlakeAmdRecodeSet *flake_amd_recode_set_open(const FlakeAmdStreami
     {
         const int bps = enc_like->bits_per_sample, n = g->block, ch = enc_like->channels;      /* encode.c:521-527 */
         const int verbatim = ch == 2 ? 16 + ((n * (bps + bps + 1) + 7) >> 3) : 16 + ((n * ch * bps + 7) >> 3);
-        /* variable block size: up to eight frames, each with its own header and rounding */
-        g->per_block = verbatim + (g->vbs ? 7 * 16 + 8 : 0);
+        /* That is the size above which a block is written again as VERBATIM, not the largest frame: the VERBATIM frame
+         * itself is its header (16 bytes at most: 4, a number of up to 7, 2 of block size, 2 of sample rate, the CRC-8),
+         * a byte per subframe, the samples and the CRC-16.  With eight channels that is above `verbatim` as soon as the
+         * header takes 7 bytes (8 x 24 bits, blocks of 16: 401 against 400).  Variable block size: up to eight frames,
+         * each with its own header and rounding. */
+        const int frames = g->vbs ? 8 : 1;
+        g->per_block = (verbatim - 16) + frames * (16 + ch + 2) + (frames - 1);
     }
     const size_t ns = (size_t)nstreams, nch = (size_t)enc_like->channels;
     const size_t segs = (size_t)fa_decode_set_max_batch(g->dec);

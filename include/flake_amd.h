@@ -437,7 +437,8 @@ FLAKE_AMD_API void flake_amd_decode_set_close(FlakeAmdDecodeSet *g);
  * and is block_bytes[b] bytes (all its frames' under variable block size), so the caller scatters; *nblocks is their
  * count.  A stream's blocks come in stream order; the order is otherwise unspecified.  Returns the bytes written, or
  * -1.  out_size and block_cap must reach flake_amd_recode_set_out_bound(g, frames of the call): the carries plus that
- * many source blocks of the largest size, at verbatim size.  Below it, or with a stream index outside the set, a run
+ * many source blocks of the largest size, each block at the largest VERBATIM frame (a full header, a byte per subframe,
+ * the samples, the CRC-16; eight of them under variable block size).  Below it, or with a stream index outside the set, a run
  * that names a failed stream, bad frame sizes, or after flake_amd_recode_set_finish, the call returns -1 with NOTHING
  * changed.
  *
