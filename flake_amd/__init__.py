@@ -1043,6 +1043,21 @@ def load_host_library() -> C.CDLL:
     lib.flake_amd_read_seektable.restype = C.c_longlong
     lib.flake_amd_seek_lookup.argtypes = [C.c_void_p, C.c_int, C.c_ulonglong]
     lib.flake_amd_seek_lookup.restype = C.c_longlong
+    lib.flake_amd_write_seektable.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    lib.flake_amd_write_seektable.restype = C.c_longlong
+    lib.flake_amd_seekpoints_of_frames.argtypes = [C.POINTER(HostStreaminfo), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
+                                                   C.c_ulonglong, C.c_void_p, C.c_int]
+    lib.flake_amd_seekpoints_of_frames.restype = C.c_longlong
+    lib.flake_amd_seekpoints.argtypes = [cp, C.c_ulonglong]
+    lib.flake_amd_seekpoints.restype = C.c_int
+    lib.flake_amd_get_seekpoints.argtypes = [cp, C.c_void_p, C.c_int]
+    lib.flake_amd_get_seekpoints.restype = C.c_longlong
+    for name in ("flake_amd_set_seekpoints", "flake_amd_recode_set_seekpoints"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_ulonglong]
+        getattr(lib, name).restype = C.c_int
+    for name in ("flake_amd_set_get_seekpoints", "flake_amd_recode_set_get_seekpoints"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        getattr(lib, name).restype = C.c_longlong
     lib.flake_amd_decode_set_run_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.flake_amd_decode_set_run_offsets.restype = C.c_int
     lib.flake_amd_decode_set_md5.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -1179,6 +1194,15 @@ class HostEncoder:
         if self.lib.flake_amd_set_verify(C.byref(self.ctx), int(on)) != 0:
             raise RuntimeError("flake_amd_set_verify")
 
+    def seekpoints(self, spacing: int) -> None:
+        """flake_amd_seekpoints: record a seek point every `spacing` samples (0: off); before the first block."""
+        if self.lib.flake_amd_seekpoints(C.byref(self.ctx), int(spacing)) != 0:
+            raise RuntimeError("flake_amd_seekpoints: refused (after the first block?)")
+
+    def get_seekpoints(self):
+        """flake_amd_get_seekpoints: the points recorded so far, a SEEK_POINT_DTYPE array."""
+        return _seekpoints_from(self.lib.flake_amd_get_seekpoints, "flake_amd_get_seekpoints", C.byref(self.ctx))
+
     def streaminfo(self) -> HostStreaminfo:
         si = HostStreaminfo()
         if self.lib.flake_amd_get_streaminfo(C.byref(self.ctx), C.byref(si)) != 0:
@@ -1245,6 +1269,50 @@ def seek_lookup(points, sample: int) -> int:
     """flake_amd_seek_lookup: the index of the last point at or before `sample`, -1 if there is none."""
     pts = np.ascontiguousarray(points, dtype=SEEK_POINT_DTYPE)
     return int(load_host_library().flake_amd_seek_lookup(pts.ctypes.data if len(pts) else None, len(pts), int(sample)))
+
+
+def write_seektable(points, placeholders: int = 0) -> bytes:
+    """flake_amd_write_seektable: a SEEKTABLE block's content -- the points (a SEEK_POINT_DTYPE array, or rows of
+    (sample, offset, frame_samples)) and `placeholders` placeholder points behind them.  Raises ValueError for a table
+    that is refused (sample numbers not strictly ascending, too many points)."""
+    if not isinstance(points, np.ndarray) or points.dtype != SEEK_POINT_DTYPE:
+        rows = [tuple(int(v) for v in p) for p in points]
+        points = np.zeros(len(rows), dtype=SEEK_POINT_DTYPE)
+        for i, (sample, offset, fs) in enumerate(rows):
+            points[i] = (sample, offset, fs, 0)
+    pts = np.ascontiguousarray(points)
+    buf = np.zeros(max(18 * (len(pts) + max(int(placeholders), 0)), 1), dtype=np.uint8)
+    n = load_host_library().flake_amd_write_seektable(pts.ctypes.data if len(pts) else None, len(pts), int(placeholders),
+                                                      buf.ctypes.data, buf.size)
+    if n < 0:
+        raise ValueError("flake_amd_write_seektable refused the table")
+    return buf[:n].tobytes()
+
+
+def _seekpoints_from(fn, what: str, *handle):
+    """A getter of recorded seek points (count first, then all of them) as a SEEK_POINT_DTYPE array."""
+    n = fn(*handle, None, 0)
+    if n < 0:
+        raise ValueError(what)
+    pts = np.zeros(max(int(n), 1), dtype=SEEK_POINT_DTYPE)
+    if fn(*handle, pts.ctypes.data, int(n)) != n:
+        raise ValueError(what)
+    return pts[:int(n)].copy()
+
+
+def seekpoints_of_frames(si: HostStreaminfo, stream, sizes, spacing: int):
+    """flake_amd_seekpoints_of_frames: the seek points of a finished stream at `spacing` samples, each frame a block
+    (sizes from index_frames), as a SEEK_POINT_DTYPE array.  Raises ValueError for a bad argument or a frame whose
+    header does not parse."""
+    st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
+                              else stream, dtype=np.uint8)
+    fs = np.ascontiguousarray(sizes, dtype=np.int32)
+    lib = load_host_library()
+
+    def fn(p, cap):
+        return lib.flake_amd_seekpoints_of_frames(C.byref(si), st.ctypes.data if st.size else None, st.size,
+                                                  fs.ctypes.data if fs.size else None, len(fs), int(spacing), p, cap)
+    return _seekpoints_from(fn, "flake_amd_seekpoints_of_frames")
 
 
 def index_frames(si: HostStreaminfo, stream, cap: int | None = None):
@@ -1415,6 +1483,16 @@ class StreamSet:
         if not self.lib.flake_amd_set_last_verify_failure(self._g, C.byref(s), C.byref(n), C.byref(st)):
             return None
         return s.value, n.value, st.value
+
+    def seekpoints(self, spacing: int) -> None:
+        """flake_amd_set_seekpoints: record seek points per stream every `spacing` samples (0: off); before the first
+        block."""
+        if self.lib.flake_amd_set_seekpoints(self._g, int(spacing)) != 0:
+            raise RuntimeError("flake_amd_set_seekpoints: refused (after the first block?)")
+
+    def get_seekpoints(self, stream: int):
+        """flake_amd_set_get_seekpoints: one stream's points so far, a SEEK_POINT_DTYPE array."""
+        return _seekpoints_from(self.lib.flake_amd_set_get_seekpoints, "flake_amd_set_get_seekpoints", self._g, int(stream))
 
     def streaminfo(self, stream: int) -> HostStreaminfo:
         si = HostStreaminfo()
@@ -1712,6 +1790,20 @@ class RecodeSet:
     def set_verify(self, on: bool) -> None:
         if self.lib.flake_amd_recode_set_enable_verify(self._g, int(on)) != 0:
             raise RuntimeError("flake_amd_recode_set_enable_verify")
+
+    def seekpoints(self, spacing: int) -> None:
+        """flake_amd_recode_set_seekpoints: record the NEW streams' seek points every `spacing` samples (0: off);
+        before the first block."""
+        if self.lib.flake_amd_recode_set_seekpoints(self._g, int(spacing)) != 0:
+            raise RuntimeError("flake_amd_recode_set_seekpoints: refused (after the first block?)")
+
+    def get_seekpoints(self, stream: int):
+        """flake_amd_recode_set_get_seekpoints: a good stream's points so far (a SEEK_POINT_DTYPE array), None for a
+        failed one."""
+        if self.lib.flake_amd_recode_set_get_seekpoints(self._g, int(stream), None, 0) < 0:
+            return None
+        return _seekpoints_from(self.lib.flake_amd_recode_set_get_seekpoints, "flake_amd_recode_set_get_seekpoints",
+                                self._g, int(stream))
 
     def close(self) -> None:
         if getattr(self, "_g", None):

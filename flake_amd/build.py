@@ -34,7 +34,7 @@ HOST_SRCS = ["host/flake_host.c", "host/flake_set.c", "host/synth.c", "host/md5.
 # has no decoder
 HOST_DECODE_SRCS = ["host/flake_decode.c", "host/flake_decode_set.c", "host/flake_recode_set.c"]
 HOST_DEPS = HOST_SRCS + HOST_DECODE_SRCS + ["host/host_internal.h", "host/decode_set_plan.h", "host/recode_plan.h",
-                                            "host/decode_window_plan.h", "host/seektable.h",
+                                            "host/decode_window_plan.h", "host/seektable.h", "host/seekpoints.h",
                                             "csrc/flac_header.h",
                                             "../include/flakehip.h", "../include/flake_amd.h"]
 

@@ -52,6 +52,22 @@
  * non-zero source digest, is named on stderr, gets no output (one left by an earlier run is removed) and makes the exit
  * status non-zero; the other files are written.  --verify turns the recode set's on-device verification on.
  *
+ *   flake_amd_cli ... --seekpoints N ...        (the single-file encode, --set and --recode --set)
+ *
+ * A seek point every N samples (flake_amd_seekpoints and its set forms; N at least 1): the file is "fLaC", STREAMINFO,
+ * a SEEKTABLE block, then the header as without the switch (vendor comment, padding) and the frames.  The set modes
+ * hold every file's frames until the end and write the exact table.  The single-file mode streams to disk: it reserves
+ * ceil(samples / N) points (the total is the WAV's, or --synth's), and rewrites the table at the end, beside
+ * STREAMINFO, the remainder filled with placeholder points.
+ *
+ *   flake_amd_cli --reseek N --set OUTDIR a.flac b.flac ...
+ *
+ * run_reseek adds or replaces the SEEKTABLE of existing files without decoding anything: files loaded and frames found
+ * as in --decode --set (flac_set_load, flac_set_index), the points computed from the frames' headers
+ * (flake_amd_seekpoints_of_frames), and OUTDIR/<name>.flac written as every metadata block of the source in order
+ * except SEEKTABLE blocks, the new table right behind STREAMINFO, the frames byte for byte.  A file whose frames do not
+ * cover it to the end is named on stderr, gets no output and makes the exit status non-zero; the others are written.
+ *
  * Every mode leaves through one place that releases what it holds.  Only canonical PCM WAV (8/16/24/32 bit) is read;
  * this is a harness for the host API, not a replacement for the reference's libpcm_io.
  */
@@ -65,6 +81,10 @@
 #define SET_USAGE "%s [-0..-12] [-b blocksize] --set OUTDIR [--verify] (in1.wav in2.wav ... | --synth-streams S --synth FRAMES [--channels C] [--bps B])\n"
 #define RECODE_USAGE "usage: %s [-0..-12] [-b blocksize] --recode --set OUTDIR [--verify] a.flac b.flac ...\n" \
                      "       (files of one format; only STREAMINFO is written: other metadata blocks are not carried over)\n"
+#define SEEK_USAGE "usage: %s ... --seekpoints N ...   (a seek point every N samples, N at least 1; with the single-file encode,\n" \
+                   "       --set and --recode --set, not with --decode)\n" \
+                   "       %s --reseek N --set OUTDIR a.flac b.flac ...   (a new SEEKTABLE for existing files)\n"
+#define MAX_SEEK_POINTS 932067            /* what a metadata block's 24-bit length holds */
 
 static uint32_t rd32(const uint8_t *p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
 static uint16_t rd16(const uint8_t *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
@@ -76,6 +96,7 @@ typedef struct {
     const char *setdir, *in, *out;
     int window;                      /* --skip or --until was given */
     unsigned long long skip, until;  /* samples; until 0: to the end */
+    unsigned long long seekpoints;   /* --seekpoints N / --reseek N: a seek point every N samples; 0: none */
     char **pos;
     int npos;
 } opts;
@@ -235,13 +256,56 @@ static uint8_t *set_header(FlakeAmdContext *s, int *hlen)
     return header;
 }
 
-/* one file of a set: the header with its own STREAMINFO (flake.c:668-679), then its frames */
-static int flac_write(const char *path, uint8_t *header, int hlen, const FlakeAmdStreaminfo *si, const bytes_t *frames)
+/* A whole SEEKTABLE metadata block, its 4-byte header (never the last block: `last` 0, or 1) and its content: n points
+ * and `placeholders` placeholder points behind them.  malloc'd, *len bytes; NULL (with a word on stderr) where the
+ * table is refused or memory is short */
+static uint8_t *seektable_block(const FlakeAmdSeekPoint *pts, int n, long long placeholders, int last, size_t *len)
+{
+    const long long all = (long long)n + placeholders;
+    uint8_t *b = all <= MAX_SEEK_POINTS ? (uint8_t *)malloc(4 + 18 * (size_t)all + 1) : NULL;
+    if (!b || flake_amd_write_seektable(pts, n, (int)placeholders, b + 4, 18 * (size_t)all) != 18 * all) {
+        fprintf(stderr, "cannot write a SEEKTABLE of %lld points (a block holds %d)\n", all, MAX_SEEK_POINTS);
+        free(b);
+        return NULL;
+    }
+    b[0] = (uint8_t)((last ? 0x80 : 0) | 3);
+    b[1] = (uint8_t)((18 * all) >> 16); b[2] = (uint8_t)((18 * all) >> 8); b[3] = (uint8_t)(18 * all);
+    *len = 4 + 18 * (size_t)all;
+    return b;
+}
+
+/* the recorded points of one stream as its SEEKTABLE block: `get` is a set's getter, the exact table without placeholders */
+typedef long long (*seek_getter)(const void *g, int stream, FlakeAmdSeekPoint *p, int cap);
+static long long get_of_set(const void *g, int stream, FlakeAmdSeekPoint *p, int cap)
+{
+    return flake_amd_set_get_seekpoints((const FlakeAmdSet *)g, stream, p, cap);
+}
+static long long get_of_recode_set(const void *g, int stream, FlakeAmdSeekPoint *p, int cap)
+{
+    return flake_amd_recode_set_get_seekpoints((const FlakeAmdRecodeSet *)g, stream, p, cap);
+}
+static uint8_t *stream_seektable(seek_getter get, const void *g, int stream, size_t *len)
+{
+    const long long n = get(g, stream, NULL, 0);
+    FlakeAmdSeekPoint *pts = n >= 0 && n <= MAX_SEEK_POINTS ? (FlakeAmdSeekPoint *)malloc(sizeof *pts * (size_t)(n ? n : 1)) : NULL;
+    uint8_t *b = NULL;
+    if (pts && get(g, stream, pts, (int)n) == n) b = seektable_block(pts, (int)n, 0, 0, len);
+    else fprintf(stderr, "stream %d: its seek points cannot be read\n", stream);
+    free(pts);
+    return b;
+}
+
+/* one file of a set: the header with its own STREAMINFO (flake.c:668-679), then its frames; a SEEKTABLE block (seek,
+ * or NULL for none) goes right behind STREAMINFO */
+static int flac_write(const char *path, uint8_t *header, int hlen, const FlakeAmdStreaminfo *si, const uint8_t *seek,
+                      size_t seek_len, const bytes_t *frames)
 {
     FILE *fo = fopen(path, "wb");
     if (!fo) { perror(path); return -1; }
     flake_amd_write_streaminfo(si, header + 8);
-    fwrite(header, 1, (size_t)hlen, fo);
+    fwrite(header, 1, 42, fo);
+    if (seek) fwrite(seek, 1, seek_len, fo);
+    fwrite(header + 42, 1, (size_t)hlen - 42, fo);
     fwrite(frames->p, 1, frames->n, fo);
     fclose(fo);
     return 0;
@@ -262,7 +326,7 @@ static int run_encode(const opts *o, const char *argv0)
     FILE *fo = NULL;
     int32_t *pcm = NULL;
     int16_t *pcm16 = NULL;
-    uint8_t *buf = NULL;
+    uint8_t *buf = NULL, *seek = NULL;
     memset(&s, 0, sizeof s);
     memset(&w, 0, sizeof w);
     if (o->in) {
@@ -277,9 +341,21 @@ static int run_encode(const opts *o, const char *argv0)
     if (hlen < 0) { fprintf(stderr, "encoder init failed (%d)\n", hlen); goto out; }
     open = 1;
     if (o->verify && flake_amd_set_verify(&s, 1)) { fprintf(stderr, "cannot turn verification on\n"); goto out; }
+    /* --seekpoints: the table is reserved now, ceil(samples / N) points -- no stream of that length has more -- and
+     * rewritten at the end */
+    long long reserved = 0;
+    size_t seek_len = 0;
+    if (o->seekpoints) {
+        reserved = (long long)(((unsigned long long)s.samples + o->seekpoints - 1) / o->seekpoints);
+        if (flake_amd_seekpoints(&s, o->seekpoints)) { fprintf(stderr, "cannot turn seek points on\n"); goto out; }
+        seek = seektable_block(NULL, 0, reserved, 0, &seek_len);
+        if (!seek) goto out;
+    }
     fo = fopen(o->out, "wb");
     if (!fo) { perror(o->out); goto out; }
-    fwrite(s.header, 1, (size_t)hlen, fo);
+    fwrite(s.header, 1, 42, fo);                                     /* "fLaC" and STREAMINFO */
+    if (seek) fwrite(seek, 1, seek_len, fo);
+    fwrite(s.header + 42, 1, (size_t)hlen - 42, fo);
 
     const int bs = s.params.block_size, nch = s.channels, batch = 256;
     /* 16 bits per sample or fewer at a level without variable block size: the samples stay int16 all the way
@@ -293,7 +369,7 @@ static int run_encode(const opts *o, const char *argv0)
     pcm16 = narrow ? (int16_t *)malloc(sizeof(int16_t) * (size_t)batch * bs * nch) : NULL;
     buf = (uint8_t *)malloc(cap);
     if (!pcm || (narrow && !pcm16) || !buf) { fprintf(stderr, "out of memory\n"); goto out; }
-    uint64_t total_in = 0, total_out = (uint64_t)hlen;
+    uint64_t total_in = 0, total_out = (uint64_t)hlen + seek_len;
     int64_t synth_left = o->synth, synth_pos = 0;
     for (;;) {
         uint32_t frames;
@@ -326,6 +402,20 @@ static int run_encode(const opts *o, const char *argv0)
         fseek(fo, 8, SEEK_SET);
         fwrite(sib, 1, 34, fo);
     }
+    if (seek) {
+        /* the points that were recorded, as many as were reserved at the most, the remainder placeholders */
+        const long long have = flake_amd_get_seekpoints(&s, NULL, 0);
+        const long long take = have < reserved ? have : reserved;
+        FlakeAmdSeekPoint *pts = take >= 0 ? (FlakeAmdSeekPoint *)malloc(sizeof *pts * (size_t)(take ? take : 1)) : NULL;
+        size_t len = 0;
+        uint8_t *table = pts && flake_amd_get_seekpoints(&s, pts, (int)take) == have
+                             ? seektable_block(pts, (int)take, reserved - take, 0, &len) : NULL;
+        free(pts);
+        if (!table || len != seek_len) { fprintf(stderr, "the seek table could not be rewritten\n"); free(table); goto out; }
+        fseek(fo, 42, SEEK_SET);
+        fwrite(table, 1, len, fo);
+        free(table);
+    }
     fprintf(stderr, "%llu sample-frames -> %llu bytes (ratio %.3f)\n", (unsigned long long)total_in,
             (unsigned long long)total_out,
             total_in ? (double)total_out / ((double)total_in * nch * ((s.bits_per_sample + 7) / 8)) : 0.0);
@@ -334,7 +424,7 @@ out:
     if (fo) fclose(fo);
     if (open) flake_amd_encode_close(&s);
     wav_close(&w);
-    free(pcm); free(pcm16); free(buf);
+    free(pcm); free(pcm16); free(buf); free(seek);
     return rc;
 }
 
@@ -425,6 +515,7 @@ static int run_set(const opts *o, const char *argv0)
     r.g = flake_amd_set_open(&s, S, s.params.variable_block_size ? FLAKE_AMD_SET_VBS : 0);
     if (!r.g) { fprintf(stderr, "%s\n", flake_amd_set_last_error(NULL)); goto out; }
     if (o->verify && flake_amd_set_enable_verify(r.g, 1)) { fprintf(stderr, "cannot turn verification on\n"); goto out; }
+    if (o->seekpoints && flake_amd_set_seekpoints(r.g, o->seekpoints)) { fprintf(stderr, "cannot turn seek points on\n"); goto out; }
     r.sample_bytes = sample_bytes; r.nch = nch; r.cap_blocks = 1024; r.outs = outs;
     r.pcm = (char *)malloc((size_t)r.cap_blocks * bs * nch * sample_bytes);
     r.stream_of = (int *)malloc(sizeof(int) * (size_t)r.cap_blocks);
@@ -472,8 +563,12 @@ static int run_set(const opts *o, const char *argv0)
         }
         FlakeAmdStreaminfo si;
         if (flake_amd_set_get_streaminfo(r.g, i, &si)) { fprintf(stderr, "%s\n", flake_amd_set_last_error(r.g)); goto out; }
-        if (flac_write(path, header, hlen, &si, &outs[i])) goto out;
-        total_in += frames[i]; total_out += (unsigned long long)hlen + outs[i].n;
+        size_t seek_len = 0;
+        uint8_t *seek = o->seekpoints ? stream_seektable(get_of_set, r.g, i, &seek_len) : NULL;
+        const int wrote = (o->seekpoints && !seek) ? -1 : flac_write(path, header, hlen, &si, seek, seek_len, &outs[i]);
+        free(seek);
+        if (wrote) goto out;
+        total_in += frames[i]; total_out += (unsigned long long)hlen + seek_len + outs[i].n;
     }
     fprintf(stderr, "%d streams, %llu sample-frames -> %llu bytes (ratio %.3f)\n", S, total_in, total_out,
             total_in ? (double)total_out / ((double)total_in * nch * ((s.bits_per_sample + 7) / 8)) : 0.0);
@@ -920,6 +1015,7 @@ static int run_recode_set(const opts *o, const char *argv0)
     g = flake_amd_recode_set_open(&like, &s, n, s.params.variable_block_size ? FLAKE_AMD_SET_VBS : 0);
     if (!g) { fprintf(stderr, "recode set init failed: %s\n", flake_amd_recode_set_last_error(NULL)); goto out; }
     if (o->verify && flake_amd_recode_set_enable_verify(g, 1)) { fprintf(stderr, "cannot turn verification on\n"); goto out; }
+    if (o->seekpoints && flake_amd_recode_set_seekpoints(g, o->seekpoints)) { fprintf(stderr, "cannot turn seek points on\n"); goto out; }
     if (pack_open(&p, n, like.max_block_size)) { fprintf(stderr, "out of memory\n"); goto out; }
     for (int last = 0; !last;) {
         int nb = 0;
@@ -962,9 +1058,13 @@ static int run_recode_set(const opts *o, const char *argv0)
             f->bad = source_check(f->path, &f->si, si.md5sum, si.samples);
         }
         /* a file named above gets no output, and one from an earlier run does not stay in its place */
+        size_t seek_len = 0;
+        uint8_t *seek = (!f->bad && o->seekpoints) ? stream_seektable(get_of_recode_set, g, i, &seek_len) : NULL;
+        if (!f->bad && o->seekpoints && !seek) f->bad = 1;
         if (f->bad) remove(f->name);
-        else if (flac_write(f->name, header, hlen, &si, &outs[i])) f->bad = 1;
-        else fprintf(stderr, "%s: %u sample-frames -> %llu bytes\n", f->path, si.samples, (unsigned long long)hlen + outs[i].n);
+        else if (flac_write(f->name, header, hlen, &si, seek, seek_len, &outs[i])) f->bad = 1;
+        else fprintf(stderr, "%s: %u sample-frames -> %llu bytes\n", f->path, si.samples, (unsigned long long)hlen + seek_len + outs[i].n);
+        free(seek);
     }
     long long db = 0, eb = 0;
     flake_amd_recode_set_device_batches(g, &db, &eb);
@@ -975,6 +1075,70 @@ out:
     for (int i = 0; i < n && outs; i++) free(outs[i].p);
     pack_free(&p);
     free(outs); free(bstream); free(bbytes); free(obuf); free(header);
+    flac_free(fs, n);
+    return rc;
+}
+
+/* ---- --reseek N --set: a new SEEKTABLE for existing files, nothing decoded ---- */
+
+/* f as OUTDIR/<name>.flac with the table `seek` (a whole metadata block): STREAMINFO, the table, every other metadata
+ * block of the source in order except its SEEKTABLE blocks, the last of them all flagged as such, then the frames */
+static int reseek_write(const flac_in *f, uint8_t *seek, size_t seek_len)
+{
+    FILE *fo = fopen(f->name, "wb");
+    if (!fo) { perror(f->name); return -1; }
+    int kept = 0;                          /* the source's blocks behind STREAMINFO that stay (flac_load has walked them) */
+    for (size_t pos = 4 + 4 + 34; pos < f->pos; pos += 4 + ((size_t)f->file[pos + 1] << 16 | (size_t)f->file[pos + 2] << 8 | f->file[pos + 3]))
+        kept += (f->file[pos] & 0x7F) != 3;
+    fwrite(f->file, 1, 4, fo);
+    fputc(0, fo);                          /* STREAMINFO, not the last block: the table follows */
+    fwrite(f->file + 5, 1, 3 + 34, fo);
+    seek[0] = (uint8_t)((kept ? 0 : 0x80) | 3);
+    fwrite(seek, 1, seek_len, fo);
+    for (size_t pos = 4 + 4 + 34; pos < f->pos;) {
+        const size_t blen = (size_t)f->file[pos + 1] << 16 | (size_t)f->file[pos + 2] << 8 | f->file[pos + 3];
+        if ((f->file[pos] & 0x7F) != 3) {
+            fputc((f->file[pos] & 0x7F) | (--kept ? 0 : 0x80), fo);
+            fwrite(f->file + pos + 1, 1, 3 + blen, fo);
+        }
+        pos += 4 + blen;
+    }
+    fwrite(f->file + f->pos, 1, f->len - f->pos, fo);
+    const int bad = ferror(fo);
+    fclose(fo);
+    if (bad) fprintf(stderr, "%s: write error\n", f->name);
+    return bad ? -1 : 0;
+}
+
+static int run_reseek(const opts *o, const char *argv0)
+{
+    const int n = o->npos;
+    if (!o->setdir || !n || !o->seekpoints) { fprintf(stderr, SEEK_USAGE, argv0, argv0); return 2; }
+    int rc = 1;
+    FlakeAmdStreaminfo like;
+    flac_in *fs = (flac_in *)calloc((size_t)n, sizeof *fs);
+    if (!fs || flac_set_load(fs, o->pos, n, o->setdir, "flac", "reseek", &like)) goto out;
+    /* the frames of every file, found through a throwaway decode set's handle */
+    FlakeAmdDecodeSet *ix = index_on_host() ? NULL : flake_amd_decode_set_open(&like, 1, FLAKE_AMD_SET_MD5_OFF);
+    flac_set_index(fs, n, ix);
+    if (ix) flake_amd_decode_set_close(ix);
+    for (int i = 0; i < n; i++) {
+        flac_in *f = &fs[i];
+        if (f->skip || f->bad) continue;   /* named already: it did not load, or its frames do not cover it to the end */
+        const uint8_t *frames = f->file + f->pos;
+        const long long np = flake_amd_seekpoints_of_frames(&f->si, frames, f->used, f->sizes, (int)f->nframes, o->seekpoints, NULL, 0);
+        FlakeAmdSeekPoint *pts = np >= 0 && np <= MAX_SEEK_POINTS ? (FlakeAmdSeekPoint *)malloc(sizeof *pts * (size_t)(np ? np : 1)) : NULL;
+        size_t seek_len = 0;
+        uint8_t *seek = NULL;
+        if (pts && flake_amd_seekpoints_of_frames(&f->si, frames, f->used, f->sizes, (int)f->nframes, o->seekpoints, pts, (int)np) == np)
+            seek = seektable_block(pts, (int)np, 0, 0, &seek_len);
+        if (!seek) fprintf(stderr, "%s: no seek table could be made of its %lld frames\n", f->path, f->nframes);
+        if (!seek || reseek_write(f, seek, seek_len)) f->bad = 1;
+        else fprintf(stderr, "%s: %lld seek points over %lld frames\n", f->path, np, f->nframes);
+        free(pts); free(seek);
+    }
+    rc = any_bad(fs, n);
+out:
     flac_free(fs, n);
     return rc;
 }
@@ -1153,7 +1317,9 @@ enum {
     A_SYNTH = 16,          /* --synth N, --channels N, --bps N */
     A_STREAMS = 32,        /* --synth-streams N */
     A_VERIFY = 64,         /* --verify */
-    A_WINDOW = 128         /* --skip N, --until N (samples) */
+    A_WINDOW = 128,        /* --skip N, --until N (samples) */
+    A_SEEK = 256,          /* --seekpoints N (samples) */
+    A_MODE_VALUE = 512     /* the mode's own word takes N: --reseek N */
 };
 
 typedef struct {
@@ -1163,10 +1329,11 @@ typedef struct {
 } mode;
 
 static const mode modes[] = {
-    {"--recode", A_LEVEL | A_BSIZE | A_SET | A_VERIFY, run_recode_set},
+    {"--reseek", A_SET | A_MODE_VALUE, run_reseek},
+    {"--recode", A_LEVEL | A_BSIZE | A_SET | A_VERIFY | A_SEEK, run_recode_set},
     {"--decode", A_SET_FIRST | A_WINDOW, run_decode_mode},
-    {"--set", A_LEVEL | A_BSIZE | A_SET | A_SYNTH | A_STREAMS | A_VERIFY, run_set},
-    {NULL, A_LEVEL | A_BSIZE | A_SYNTH | A_VERIFY, run_encode},
+    {"--set", A_LEVEL | A_BSIZE | A_SET | A_SYNTH | A_STREAMS | A_VERIFY | A_SEEK, run_set},
+    {NULL, A_LEVEL | A_BSIZE | A_SYNTH | A_VERIFY | A_SEEK, run_encode},
 };
 
 int main(int argc, char **argv)
@@ -1183,6 +1350,7 @@ int main(int argc, char **argv)
     o.pos = (char **)calloc((size_t)argc, sizeof(char *));
     if (!o.pos) return 1;
     unsigned acc = m->accepts;
+    int seek_bad = 0;                  /* --seekpoints where it cannot be, or without a count of at least 1 */
     /* a switch that the mode does not accept, or one whose value is missing, is a positional argument; so is every
      * other word but the mode's own */
     for (int i = 1; i < argc; i++) {
@@ -1198,13 +1366,19 @@ int main(int argc, char **argv)
         else if ((acc & A_VERIFY) && !strcmp(w, "--verify")) o.verify = 1;
         else if ((acc & A_WINDOW) && val && !strcmp(w, "--skip")) { o.skip = strtoull(argv[++i], NULL, 10); o.window = 1; }
         else if ((acc & A_WINDOW) && val && !strcmp(w, "--until")) { o.until = strtoull(argv[++i], NULL, 10); o.window = 1; }
+        else if (!strcmp(w, "--seekpoints")) {
+            o.seekpoints = ((acc & A_SEEK) && val) ? strtoull(argv[++i], NULL, 10) : 0;
+            seek_bad |= !o.seekpoints;
+        }
+        else if (i == at && (acc & A_MODE_VALUE)) o.seekpoints = val ? strtoull(argv[++i], NULL, 10) : 0;
         else if (i != at) {
             o.pos[o.npos++] = argv[i];
             /* (the single-file form: the first word is the input unless --synth came before it, the last the output) */
             if (!o.in && !o.synth) o.in = w; else o.out = w;
         }
     }
-    const int rc = m->run(&o, argv[0]);
+    if (seek_bad) fprintf(stderr, SEEK_USAGE, argv[0], argv[0]);
+    const int rc = seek_bad ? 2 : m->run(&o, argv[0]);
     free(o.pos);
     return rc;
 }

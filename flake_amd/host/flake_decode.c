@@ -16,6 +16,7 @@
 #include "flakehip.h"
 #include "host_internal.h"
 #include "seektable.h"
+#include "seekpoints.h"
 
 /* ---- STREAMINFO ------------------------------------------------------ */
 
@@ -57,6 +58,19 @@ FLAKE_AMD_API long long flake_amd_read_seektable(const unsigned char *block, siz
 FLAKE_AMD_API long long flake_amd_seek_lookup(const FlakeAmdSeekPoint *points, int n, unsigned long long sample)
 {
     return fa_seek_lookup(points, n, sample);
+}
+
+FLAKE_AMD_API long long flake_amd_write_seektable(const FlakeAmdSeekPoint *points, int n, int placeholders,
+                                                  unsigned char *block, size_t cap)
+{
+    return fa_write_seektable(points, n, placeholders, block, cap);
+}
+
+FLAKE_AMD_API long long flake_amd_seekpoints_of_frames(const FlakeAmdStreaminfo *si, const unsigned char *stream, size_t bytes,
+                                                       const int *frame_sizes, int nframes, unsigned long long spacing,
+                                                       FlakeAmdSeekPoint *points, int cap)
+{
+    return fa_seekpoints_of_frames(si, stream, bytes, frame_sizes, nframes, spacing, points, cap);
 }
 
 /* ---- frame discovery --------------------------------------------------- */

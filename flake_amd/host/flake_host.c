@@ -26,6 +26,7 @@
 #include "flake_amd.h"
 #include "flakehip.h"
 #include "host_internal.h"
+#include "seekpoints.h"
 
 #define VBS_PARTS 8                       /* VBS_MAX_FRAMES, vbs.h:26 */
 #define MIN_BLOCK 16                      /* FLAC_MIN_BLOCKSIZE, encode.h:34 */
@@ -79,6 +80,8 @@ typedef struct host_ctx {
     int pin_off;
     int q_pinned, fb_pinned;
     struct { void *ptr; size_t bytes; int ok; } pin[2];      /* 0: PCM in, 1: stream out */
+    fa_seekrec seek;                      /* flake_amd_seekpoints: fed where a batch's blocks are committed */
+    flac_format seek_fmt;                 /* what the recorder reads a block's first header against */
     char err[256];
 } host_ctx;
 
@@ -463,6 +466,7 @@ FLAKE_AMD_API void flake_amd_encode_close(FlakeAmdContext *s)
         if (c->hip2) fhip_destroy(c->hip2);
         free(c->info); free(c->bits); free(c->gather);
         free(c->frames); free(c->fbytes); free(c->fnum);
+        fa_seekrec_free(&c->seek);
         free(c);
     }
     free(s->header);
@@ -824,6 +828,7 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const void *pcm_a
     if (!pieces || !scratch) { free(pieces); free(scratch); return -1; }
     /* hash a copy of the state; it is committed only if the batch succeeds */
     fa_md5 md5_next = c->md5;
+    const fa_seekrec_mark seek0 = fa_seekrec_save(&c->seek);       /* as is the recorder: put back if it fails */
     md5_job job = { &md5_next, pcm_any, (size_t)count * bstride, c->hp.bits_per_sample, (int)width };
     pthread_t md5_thread;
     int md5_running = 0, md5_done = 0;
@@ -848,6 +853,21 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const void *pcm_a
                      fhip_last_error(c->hip));
             if (md5_running) pthread_join(md5_thread, NULL);
             return -1;
+        }
+        if (c->seek.spacing) {
+            /* a point names its block's first frame: block b is block_bytes[b] bytes, all its frames' */
+            const int *block_bytes = frame_sizes ? frame_sizes : c->fbytes;
+            size_t at = 0;
+            for (int b = 0; b < count; b++) {
+                if (fa_seekrec_block_at(&c->seek, &c->seek_fmt, out + at, (unsigned long long)block_size,
+                                        (unsigned long long)block_bytes[b])) {
+                    snprintf(c->err, sizeof c->err, "seek points: block %d of the batch could not be recorded", b);
+                    fa_seekrec_restore(&c->seek, &seek0);
+                    if (md5_running) pthread_join(md5_thread, NULL);
+                    return -1;
+                }
+                at += (size_t)block_bytes[b];
+            }
         }
         if (mx > c->max_frame_size) c->max_frame_size = mx;        /* encode.c:967 */
         c->frame_count = next;                                     /* encode.c:969-975 */
@@ -951,6 +971,7 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const void *pcm_a
             }
             t_gpu = now_ms() - tg0; ngroups = 1;
             int cur_block = -1;
+            size_t at = 0, block_at = 0;                           /* in out: behind frame i, the start of its block */
             for (int i = 0; i < np; i++) {
                 const int fs = c->fbytes[i];
                 if (fs <= 0) { snprintf(c->err, sizeof c->err, "frame %d was not encoded", i); goto out; }
@@ -959,6 +980,15 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const void *pcm_a
                 if (frame_sizes) {
                     if (pieces[i].block != cur_block) { cur_block = pieces[i].block; frame_sizes[cur_block] = 0; }
                     frame_sizes[cur_block] += fs;
+                }
+                at += (size_t)fs;
+                if (c->seek.spacing && (i + 1 == np || pieces[i + 1].block != pieces[i].block)) {
+                    if (fa_seekrec_block_at(&c->seek, &c->seek_fmt, out + block_at, (unsigned long long)block_size,
+                                            (unsigned long long)(at - block_at))) {
+                        snprintf(c->err, sizeof c->err, "seek points: block %d of the batch could not be recorded", pieces[i].block);
+                        goto out;
+                    }
+                    block_at = at;
                 }
             }
             total = (long long)wrote;
@@ -1017,7 +1047,7 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const void *pcm_a
     /* host: frames in stream order */
     {
         const double to0 = now_ms();
-        size_t pos = 0;
+        size_t pos = 0, block_at = 0;
         int cur_block = -1;
         for (int i = 0; i < np; i++) {
             int fs;
@@ -1041,6 +1071,14 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const void *pcm_a
                 frame_sizes[cur_block] += fs;
             }
             pos += (size_t)fs;
+            if (c->seek.spacing && (i + 1 == np || pieces[i + 1].block != pieces[i].block)) {
+                if (fa_seekrec_block_at(&c->seek, &c->seek_fmt, out + block_at, (unsigned long long)block_size,
+                                        (unsigned long long)(pos - block_at))) {
+                    snprintf(c->err, sizeof c->err, "seek points: block %d of the batch could not be recorded", pieces[i].block);
+                    goto out;
+                }
+                block_at = pos;
+            }
         }
         total = (long long)pos;
         t_out = now_ms() - to0;
@@ -1055,7 +1093,8 @@ static long long encode_batch(FlakeAmdContext *s, host_ctx *c, const void *pcm_a
         const int rc = fhip_verify_frames(c->hip, &vi, &vo);
         if (rc != FHIP_OK) {
             snprintf(c->err, sizeof c->err, "fhip_verify_frames: %s (%s)", fhip_strerror(rc), fhip_last_error(c->hip));
-            c->frame_count = frame_count0;           /* the batch's frames are not part of the stream */
+            c->frame_count = frame_count0;           /* the batch's frames are not part of the stream (nor its seek
+                                                        points: `out` below takes the recorder back) */
             total = -1;
             goto out;
         }
@@ -1071,6 +1110,7 @@ hashed:
         md5_done = 1;
     }
 out:
+    if (total < 0) fa_seekrec_restore(&c->seek, &seek0);
     if (md5_running) pthread_join(md5_thread, NULL);
     if (md5_done && total >= 0) c->md5 = md5_next;
     free(dev_nf); free(dev_sizes);
@@ -1217,6 +1257,29 @@ FLAKE_AMD_API int flake_amd_encode_frame(FlakeAmdContext *s, const int *samples,
     return (int)w;
 }
 
+
+/* ------------------------------------------------------------------ */
+/* seek points (host/seekpoints.h)                                     */
+/* ------------------------------------------------------------------ */
+/* Not in the drop-in libflake.so: libflake writes no seek table. */
+#ifndef FLAKE_AMD_EXPORT_FLAKE_NAMES
+FLAKE_AMD_API int flake_amd_seekpoints(FlakeAmdContext *s, unsigned long long spacing)
+{
+    if (!s || !s->private_ctx) return -1;
+    host_ctx *c = (host_ctx *)s->private_ctx;
+    if (c->frame_count || c->last_frame || c->q_seen) return -1;   /* a block has been handed in */
+    fa_seekrec_init(&c->seek, spacing);
+    c->seek_fmt.channels = s->channels; c->seek_fmt.bps = s->bits_per_sample;
+    c->seek_fmt.sample_rate = s->sample_rate; c->seek_fmt.max_block_size = 0;
+    return 0;
+}
+
+FLAKE_AMD_API long long flake_amd_get_seekpoints(const FlakeAmdContext *s, FlakeAmdSeekPoint *p, int cap)
+{
+    if (!s || !s->private_ctx || cap < 0 || (cap > 0 && !p)) return -1;
+    return fa_seekrec_get(&((const host_ctx *)s->private_ctx)->seek, p, cap);
+}
+#endif
 
 /* ------------------------------------------------------------------ */
 /* libflake's own symbol names (flake.h:217-295)                       */

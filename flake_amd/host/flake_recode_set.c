@@ -144,6 +144,19 @@ FLAKE_AMD_API int flake_amd_recode_set_enable_verify(FlakeAmdRecodeSet *g, int o
     return g ? flake_amd_set_enable_verify(g->enc, on) : -1;
 }
 
+/* Seek points are the inner stream set's: it commits the new blocks. */
+FLAKE_AMD_API int flake_amd_recode_set_seekpoints(FlakeAmdRecodeSet *g, unsigned long long spacing)
+{
+    return g ? flake_amd_set_seekpoints(g->enc, spacing) : -1;
+}
+
+FLAKE_AMD_API long long flake_amd_recode_set_get_seekpoints(const FlakeAmdRecodeSet *g, int stream, FlakeAmdSeekPoint *p, int cap)
+{
+    if (!g || stream < 0 || stream >= g->nstreams) return -1;
+    if (g->st[stream].failed || flake_amd_decode_set_failed(g->dec, stream, NULL, NULL) == 1) return -1;
+    return flake_amd_set_get_seekpoints(g->enc, stream, p, cap);
+}
+
 static long long rc_carry_total(const FlakeAmdRecodeSet *g)
 {
     long long n = 0;

@@ -29,6 +29,7 @@
 #include "flakehip.h"
 #include "host_internal.h"
 #include "recode_plan.h"
+#include "seekpoints.h"
 
 struct FlakeAmdSet {
     fhip_ctx *hip;
@@ -50,6 +51,8 @@ struct FlakeAmdSet {
     char *ended;
     int *scratch;                         /* [nstreams + 1] blocks per stream in a call / a chunk's CSR rows */
     fa_md5 *host_md5;                     /* FLAKE_AMD_SET_MD5_HOST */
+    fa_seekrec *seek;                     /* flake_amd_set_seekpoints: one recorder per stream; null: off */
+    flac_format seek_fmt;                 /* what a recorder reads a block's first header against */
     fhip_md5_state *dev_md5;              /* device memory */
     uint8_t *digests;                     /* [nstreams][16], fetched for all streams at once ... */
     int digests_valid;                    /* ... by the first request after an encode */
@@ -78,6 +81,8 @@ FLAKE_AMD_API void flake_amd_set_close(FlakeAmdSet *g)
     free(g->frame_count); free(g->samples); free(g->min_frame); free(g->max_frame); free(g->ended);
     free(g->scratch); free(g->host_md5); free(g->digests); free(g->fnum); free(g->fbytes); free(g->seg_block);
     free(g->bframes); free(g->bmax);
+    if (g->seek) for (int s = 0; s < g->nstreams; s++) fa_seekrec_free(&g->seek[s]);
+    free(g->seek);
     free(g);
 }
 
@@ -353,8 +358,14 @@ static long long set_encode(FlakeAmdSet *g, fa_set_source *src, const void *samp
         if (g->fbytes[b] <= 0) { g->broken = 1; SET_FAIL("flake_amd_set_encode: frame %d was not encoded", b); }
     /* the batch is part of its streams now */
     const size_t nvals = (size_t)block_size * (size_t)g->hp.channels;
+    size_t at = 0;                         /* block b's first frame in out */
     for (int b = 0; b < nblocks; b++) {
         const int s = stream_of_block[b], fs = g->fbytes[b];
+        if (g->seek && fa_seekrec_block_at(&g->seek[s], &g->seek_fmt, out + at, (unsigned long long)block_size, (unsigned long long)fs)) {
+            g->broken = 1;
+            SET_FAIL("flake_amd_set_encode: the seek point of block %d could not be recorded", b);
+        }
+        at += (size_t)fs;
         if (frame_sizes) frame_sizes[b] = fs;
         const int largest = split ? g->bmax[b] : fs;                        /* of the block's frames */
         if (largest > g->max_frame[s]) g->max_frame[s] = largest;           /* encode.c:967 */
@@ -473,9 +484,15 @@ static long long set_encode_short(FlakeAmdSet *g, fa_set_source *src, const void
     for (int b = 0; b < cnt_all; b++)
         if (g->fbytes[b] <= 0) { g->broken = 1; SET_FAIL("flake_amd_set_encode_ragged: frame %d was not encoded", b); }
     pcm = (const char *)samples;
+    size_t at = 0;                         /* block b's first frame in out */
     for (int b = 0; b < cnt_all; b++) {
         const int s = stream_of_block[b], fs = g->fbytes[b];
         const size_t nvals = (size_t)sizes[b] * (size_t)g->hp.channels;
+        if (g->seek && fa_seekrec_block_at(&g->seek[s], &g->seek_fmt, out + at, (unsigned long long)sizes[b], (unsigned long long)fs)) {
+            g->broken = 1;
+            SET_FAIL("flake_amd_set_encode_ragged: the seek point of block %d could not be recorded", b);
+        }
+        at += (size_t)fs;
         if (frame_sizes) frame_sizes[b] = fs;
         const int largest = g->vbs ? g->bmax[b] : fs;                       /* of the block's frames */
         if (largest > g->max_frame[s]) g->max_frame[s] = largest;           /* encode.c:967 */
@@ -551,9 +568,10 @@ FLAKE_AMD_API long long flake_amd_set_encode_ragged(FlakeAmdSet *g, const void *
     int *sv_mm = (int *)malloc(ns * 2 * sizeof(int));
     char *sv_en = (char *)malloc(ns);
     fa_md5 *sv_md = g->host_md5 ? (fa_md5 *)malloc(ns * sizeof(fa_md5)) : NULL;
+    fa_seekrec_mark *sv_sk = g->seek ? (fa_seekrec_mark *)malloc(ns * sizeof(fa_seekrec_mark)) : NULL;
     long long result = -1;
-#define RAGGED_DONE() do { free(gid); free(off); free(gpcm); free(stash); free(sv_fc); free(sv_sm); free(sv_mm); free(sv_en); free(sv_md); } while (0)
-    if (!gid || !off || !gpcm || !stash || !sv_fc || !sv_sm || !sv_mm || !sv_en || (g->host_md5 && !sv_md)) {
+#define RAGGED_DONE() do { free(gid); free(off); free(gpcm); free(stash); free(sv_fc); free(sv_sm); free(sv_mm); free(sv_en); free(sv_md); free(sv_sk); } while (0)
+    if (!gid || !off || !gpcm || !stash || !sv_fc || !sv_sm || !sv_mm || !sv_en || (g->host_md5 && !sv_md) || (g->seek && !sv_sk)) {
         RAGGED_DONE();
         SET_FAIL("flake_amd_set_encode_ragged: out of host memory");
     }
@@ -576,6 +594,7 @@ FLAKE_AMD_API long long flake_amd_set_encode_ragged(FlakeAmdSet *g, const void *
     memcpy(sv_mm, g->min_frame, ns * sizeof(int)); memcpy(sv_mm + ns, g->max_frame, ns * sizeof(int));
     memcpy(sv_en, g->ended, ns);
     if (sv_md) memcpy(sv_md, g->host_md5, ns * sizeof(fa_md5));
+    if (sv_sk) for (int s = 0; s < g->nstreams; s++) sv_sk[s] = fa_seekrec_save(&g->seek[s]);
     size_t stash_at = 0;
     int ok = 1;
     for (int k = 0; k < ngroups && ok; k++) {
@@ -624,6 +643,7 @@ FLAKE_AMD_API long long flake_amd_set_encode_ragged(FlakeAmdSet *g, const void *
         memcpy(g->frame_count, sv_fc, ns * sizeof(uint32_t)); memcpy(g->samples, sv_sm, ns * sizeof(uint64_t));
         memcpy(g->min_frame, sv_mm, ns * sizeof(int)); memcpy(g->max_frame, sv_mm + ns, ns * sizeof(int));
         memcpy(g->ended, sv_en, ns);
+        if (sv_sk) for (int s = 0; s < g->nstreams; s++) fa_seekrec_restore(&g->seek[s], &sv_sk[s]);
         if (sv_md) {
             memcpy(g->host_md5, sv_md, ns * sizeof(fa_md5));
             for (int s = 0; s < g->nstreams; s++) fa_md5_final(&g->host_md5[s], g->digests + 16 * (size_t)s);
@@ -689,6 +709,29 @@ long long fa_set_encode_short_from(FlakeAmdSet *g, fa_set_source *src, int nbloc
     if (r == -2) SET_FAIL("flake_amd_set_encode_ragged: the ragged packed path does not cover this set (block size above 16384)");
     return r;
 }
+
+/* ---- seek points (host/seekpoints.h); not in the drop-in libflake.so ---- */
+#ifndef FLAKE_AMD_EXPORT_FLAKE_NAMES
+FLAKE_AMD_API int flake_amd_set_seekpoints(FlakeAmdSet *g, unsigned long long spacing)
+{
+    if (!g) return -1;
+    for (int s = 0; s < g->nstreams; s++) if (g->samples[s] || g->ended[s]) return -1;      /* a block has been committed */
+    if (!g->seek && spacing) {
+        g->seek = (fa_seekrec *)calloc((size_t)g->nstreams, sizeof(fa_seekrec));
+        if (!g->seek) return -1;
+    }
+    if (g->seek) for (int s = 0; s < g->nstreams; s++) fa_seekrec_init(&g->seek[s], spacing);
+    g->seek_fmt.channels = g->hp.channels; g->seek_fmt.bps = g->hp.bits_per_sample;
+    g->seek_fmt.sample_rate = g->hp.sample_rate; g->seek_fmt.max_block_size = 0;
+    return 0;
+}
+
+FLAKE_AMD_API long long flake_amd_set_get_seekpoints(const FlakeAmdSet *g, int stream, FlakeAmdSeekPoint *p, int cap)
+{
+    if (!g || stream < 0 || stream >= g->nstreams || cap < 0 || (cap > 0 && !p)) return -1;
+    return g->seek ? fa_seekrec_get(&g->seek[stream], p, cap) : 0;
+}
+#endif
 
 FLAKE_AMD_API int flake_amd_set_get_streaminfo(FlakeAmdSet *g, int stream, FlakeAmdStreaminfo *si)
 {

@@ -1,8 +1,8 @@
 /*
- * seektable.h -- reading a SEEKTABLE block's points and looking a sample up in them: the bodies of
- * flake_amd_read_seektable and flake_amd_seek_lookup (include/flake_amd.h says what they answer).  Plain C on plain
- * tables, in a header of its own so that a stand-alone program runs them under the sanitizers on the CPU
- * (tests/test_seektable_cpu.py).  Not installed.
+ * seektable.h -- reading a SEEKTABLE block's points, looking a sample up in them and writing such a block: the bodies
+ * of flake_amd_read_seektable, flake_amd_seek_lookup and flake_amd_write_seektable (include/flake_amd.h says what they
+ * answer).  Plain C on plain tables, in a header of its own so that a stand-alone program runs them under the
+ * sanitizers on the CPU (tests/test_seektable_cpu.py).  Not installed.
  */
 #ifndef FLAKE_AMD_SEEKTABLE_H
 #define FLAKE_AMD_SEEKTABLE_H
@@ -36,6 +36,35 @@ static inline long long fa_read_seektable(const unsigned char *block, size_t byt
         n++;
     }
     return n;
+}
+
+/* The inverse: n points and `placeholders` placeholder points behind them into block[0 .. cap).  Everything is checked
+ * before the first byte is written. */
+#define FA_SEEKTABLE_MAX_POINTS 932067      /* a metadata block's length has 24 bits: (2^24 - 1) / 18 */
+
+static inline long long fa_write_seektable(const FlakeAmdSeekPoint *points, int n, int placeholders,
+                                           unsigned char *block, size_t cap)
+{
+    if (n < 0 || placeholders < 0 || (n > 0 && !points)) return -1;
+    const long long all = (long long)n + placeholders;
+    if (all > FA_SEEKTABLE_MAX_POINTS || (all > 0 && !block) || cap < (size_t)all * 18) return -1;
+    for (int i = 0; i < n; i++)
+        if (points[i].sample == 0xFFFFFFFFFFFFFFFFull || (i > 0 && points[i].sample <= points[i - 1].sample) ||
+            points[i].frame_samples > 0xFFFFu)
+            return -1;
+    for (long long i = 0; i < all; i++) {
+        unsigned char *d = block + 18 * i;
+        const unsigned long long sample = i < n ? points[i].sample : 0xFFFFFFFFFFFFFFFFull;
+        const unsigned long long offset = i < n ? points[i].offset : 0;
+        const unsigned fs = i < n ? points[i].frame_samples : 0;
+        for (int k = 0; k < 8; k++) {
+            d[k] = (unsigned char)(sample >> (56 - 8 * k));
+            d[8 + k] = (unsigned char)(offset >> (56 - 8 * k));
+        }
+        d[16] = (unsigned char)(fs >> 8);
+        d[17] = (unsigned char)fs;
+    }
+    return all * 18;
 }
 
 static inline long long fa_seek_lookup(const FlakeAmdSeekPoint *points, int n, unsigned long long sample)

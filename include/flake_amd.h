@@ -266,6 +266,48 @@ typedef struct FlakeAmdSeekPoint {
 FLAKE_AMD_API long long flake_amd_read_seektable(const unsigned char *block, size_t bytes, FlakeAmdSeekPoint *points, int cap);
 FLAKE_AMD_API long long flake_amd_seek_lookup(const FlakeAmdSeekPoint *points, int n, unsigned long long sample);
 /*
+ * The inverse of flake_amd_read_seektable: the n points, 18 bytes each and big-endian, followed by `placeholders`
+ * placeholder points (sample number all ones, the rest zero), into block[0 .. cap) -- the block's content, without the
+ * 4-byte metadata header.  Returns the bytes written, 18 * (n + placeholders); -1 with NOTHING written for a null
+ * pointer with a non-zero count, a negative count, sample numbers that are not strictly ascending or equal the
+ * placeholder value, a frame_samples above 65535 (the field has 16 bits), a cap that is too small, or n + placeholders
+ * above 932067: a metadata block's length has 24 bits and (2^24 - 1) / 18 = 932067.  For every table it accepts,
+ * flake_amd_read_seektable returns exactly those points.  Pure host code.
+ */
+FLAKE_AMD_API long long flake_amd_write_seektable(const FlakeAmdSeekPoint *points, int n, int placeholders,
+                                                  unsigned char *block, size_t cap);
+/*
+ * Seek points while encoding, off by default; with recording off nothing changes, and with it on every frame byte and
+ * every STREAMINFO is what it is with it off.  The targets are k * spacing samples, k = 0, 1, 2, ...; a committed block
+ * gets a point exactly when at least one target lies in [first, first + its samples), `first` being the stream's sample
+ * count before it, and at most one -- so the first block always gets one.  The point is sample = first, offset = the
+ * stream's frame bytes before the block, frame_samples = the samples of the block's first frame, read from that frame's
+ * header: under variable block size (levels 9-12) a block may be several frames and the point names the first (any
+ * frame start is a legal seek point; the inner frames' byte sizes never reach the host).
+ *
+ * flake_amd_seekpoints / flake_amd_set_seekpoints / flake_amd_recode_set_seekpoints switch recording on with spacing
+ * in samples (0: off), after init / open and before the first block: afterwards, and for a null handle, they return
+ * -1; else 0.  A set keeps one recorder per stream; a recode set forwards to the stream set inside it.  The getters
+ * store the first cap points recorded so far and return how many there are (flake_amd_read_seektable's convention; 0
+ * with recording off); -1 for a null handle, a stream index outside the set, a failed stream of a recode set, a
+ * negative cap or a null table with cap > 0.  An encode call that returns -1 "with nothing changed" changes no points
+ * either; what a single stream or a ragged set call takes back of its bookkeeping after a failure, it takes back of its
+ * points.  flake_amd_encode_frame's look-ahead queue records when it flushes.
+ *
+ * flake_amd_seekpoints_of_frames applies the same rule to a finished stream, each FRAME a block: stream[0 .. bytes)
+ * holds nframes frames back to back with the sizes flake_amd_index_frames (or the device's indexer) found, every
+ * frame's samples are read from its header against si, and offsets count from stream[0].  It returns the number of
+ * points and stores the first cap; -1 for a bad argument (spacing 0 included) or a frame whose header does not parse.
+ * Pure host code.
+ */
+FLAKE_AMD_API int flake_amd_seekpoints(FlakeAmdContext *s, unsigned long long spacing);
+FLAKE_AMD_API long long flake_amd_get_seekpoints(const FlakeAmdContext *s, FlakeAmdSeekPoint *p, int cap);
+FLAKE_AMD_API int flake_amd_set_seekpoints(FlakeAmdSet *g, unsigned long long spacing);
+FLAKE_AMD_API long long flake_amd_set_get_seekpoints(const FlakeAmdSet *g, int stream, FlakeAmdSeekPoint *p, int cap);
+FLAKE_AMD_API long long flake_amd_seekpoints_of_frames(const FlakeAmdStreaminfo *si, const unsigned char *stream, size_t bytes,
+                                                       const int *frame_sizes, int nframes, unsigned long long spacing,
+                                                       FlakeAmdSeekPoint *points, int cap);
+/*
  * Frame discovery in a foreign stream, on the CPU (no call into the HIP layer): the sizes of the whole frames that
  * stream[0 .. bytes) begins with, at most cap of them, into frame_sizes; the return value is their count and *consumed
  * (optional) the bytes they cover, so that a caller can feed a file in pieces, each starting where the last one's
@@ -473,6 +515,9 @@ FLAKE_AMD_API int flake_amd_recode_set_get_streaminfo(FlakeAmdRecodeSet *g, int 
 FLAKE_AMD_API int flake_amd_recode_set_failed(const FlakeAmdRecodeSet *g, int stream, long long *frame, int *status);
 FLAKE_AMD_API int flake_amd_recode_set_device_batches(const FlakeAmdRecodeSet *g, long long *decode, long long *encode);
 FLAKE_AMD_API int flake_amd_recode_set_enable_verify(FlakeAmdRecodeSet *g, int on);
+/* Seek points of the NEW streams (see flake_amd_seekpoints above): the inner stream set's recorders. */
+FLAKE_AMD_API int flake_amd_recode_set_seekpoints(FlakeAmdRecodeSet *g, unsigned long long spacing);
+FLAKE_AMD_API long long flake_amd_recode_set_get_seekpoints(const FlakeAmdRecodeSet *g, int stream, FlakeAmdSeekPoint *p, int cap);
 FLAKE_AMD_API const char *flake_amd_recode_set_last_error(const FlakeAmdRecodeSet *g);
 FLAKE_AMD_API void flake_amd_recode_set_close(FlakeAmdRecodeSet *g);
 

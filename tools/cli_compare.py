@@ -32,6 +32,7 @@ def commands(src):
             base = os.path.basename(f)[:-5]
             cmds.append((f"dec_{base}_{leg}", env, ["--decode", f, f"@OUT@/dec_{base}_{leg}.wav"]))
         cmds.append((f"decset_{leg}", env, ["--decode", "--set", f"@OUT@/decset_{leg}", *files]))
+        cmds.append((f"decwin_{leg}", env, ["--decode", "--set", f"@OUT@/decwin_{leg}", "--skip", "1000", "--until", "9000", *files]))
         cmds.append((f"rec8_{leg}", env, ["-8", "--recode", "--set", f"@OUT@/rec8_{leg}", *files]))
         cmds.append((f"rec10v_{leg}", env, ["-10", "--verify", "--recode", "--set", f"@OUT@/rec10v_{leg}", *files]))
     return cmds

@@ -9,8 +9,13 @@ w is one call, p is sixteen calls of 256 streams into one buffer, sliced call by
 the first round discarded, medians of the rest with min and max.  Then K7 alone on both legs' device batches
 (fhip_set_profiling, "k_decode"): the windows' selected frames through fhip_decode_frames_windows, every frame through
 fhip_decode_frames_segments.  Every w answer is compared with p's first.  Writes profiles/decode_window_bench.txt.
-    python tools/decode_window_bench.py [timed rounds] [output file]"""
-import ctypes as C, os, statistics, sys, time
+Last, what a SEEKTABLE buys one file: the 4096 frames as ONE file, written by flake_amd_cli with --seekpoints 441000 and
+without, one window of 4096 samples out of each by the steps of `flake_amd_cli --decode --skip --until`:
+  t  the piece between two seek points indexed (flake_amd_index_frames), then flake_amd_decode_set_windows over it
+  n  no table: the whole file indexed on the device (flake_amd_decode_set_index, K8), then the same entry over all of it
+    python tools/decode_window_bench.py [timed rounds] [output file] [seek]
+With `seek` as the third argument only that last leg runs, and its section replaces the one in the output file."""
+import ctypes as C, os, statistics, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, torch, flake_amd
@@ -18,6 +23,8 @@ import numpy as np, torch, flake_amd
 V = flake_amd
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 out_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "decode_window_bench.txt")
+SEEK_ONLY = len(sys.argv) > 3 and sys.argv[3] == "seek"
+SEEK_MARK = "One file of "
 NF, n, ch, PER, WIN = 4096, 4096, 2, 16, 4096
 S0 = NF // PER
 os.environ["FLAKE_AMD_BATCH"] = str(NF)
@@ -28,6 +35,99 @@ def say(s=""):
     print(s, flush=True)
     lines.append(s)
 
+
+hlib = V.load_host_library()
+
+
+def seek_leg():
+    """One window out of one long file, with a SEEKTABLE and without."""
+    SPACING, SKIP = 441000, NF * n // 2 + 1234
+    cli = os.path.join(V.LIB_DIR, "flake_amd_cli")
+    files = {}
+    with tempfile.TemporaryDirectory() as d:
+        for k, extra in (("t", ["--seekpoints", str(SPACING)]), ("n", [])):
+            path = os.path.join(d, k + ".flac")
+            subprocess.run([cli, "--synth", str(NF), "-b", str(n), *extra, path], check=True, capture_output=True, timeout=600)
+            raw = np.fromfile(path, np.uint8)
+            at, table, last = 4, None, 0
+            while not last:                       # the metadata blocks: STREAMINFO, the SEEKTABLE where there is one
+                last, kind, size = raw[at] >> 7, raw[at] & 0x7F, int.from_bytes(raw[at + 1:at + 4].tobytes(), "big")
+                if kind == 3:
+                    table = raw[at + 4:at + 4 + size].tobytes()
+                at += 4 + size
+            files[k] = dict(si=V.read_streaminfo(raw[8:42].tobytes())[0], frames=np.ascontiguousarray(raw[at:]), table=table)
+    assert files["t"]["table"] and not files["n"]["table"] and np.array_equal(files["t"]["frames"], files["n"]["frames"])
+    fsi = files["n"]["si"]
+    g = hlib.flake_amd_decode_set_open(C.byref(fsi), 1, V.SET_MD5_OFF)
+    assert g, hlib.flake_amd_decode_set_last_error(None)
+    out = {k: np.ones((WIN, ch), np.int16) for k in files}
+    indexed, cap_all = {}, files["n"]["frames"].size // 8 + 2
+    all_sizes = np.zeros(cap_all, np.int32)
+
+    def window(k, piece, sizes):
+        fow, fixed = np.asarray([len(sizes)], np.int32), np.asarray([n], np.uint32)
+        first, count = np.asarray([SKIP], np.uint64), np.asarray([WIN], np.int64)
+        ws, wst, nfd = np.zeros(1, np.int64), np.zeros(1, np.int32), C.c_longlong(0)
+        got = hlib.flake_amd_decode_set_windows(g, 1, fow.ctypes.data, piece.ctypes.data, piece.size, sizes.ctypes.data,
+                                                fixed.ctypes.data, first.ctypes.data, count.ctypes.data, out[k].ctypes.data, 2,
+                                                WIN, ws.ctypes.data, wst.ctypes.data, C.byref(nfd))
+        assert got == WIN and not wst.any(), hlib.flake_amd_decode_set_last_error(g)
+        indexed[k] = (len(sizes), nfd.value)
+
+    def leg_t():
+        f = files["t"]
+        t0 = time.perf_counter()
+        pts, _ = V.read_seektable(f["table"])
+        a, b = V.seek_lookup(pts, SKIP), V.seek_lookup(pts, SKIP + WIN - 1) + 1
+        lo = int(pts[a]["offset"]) if a >= 0 else 0
+        hi = int(pts[b]["offset"]) if b < len(pts) else f["frames"].size
+        piece = f["frames"][lo:hi]
+        sizes, used = V.index_frames(f["si"], piece)
+        assert used == piece.size
+        window("t", piece, sizes)
+        return (time.perf_counter() - t0) * 1e3
+
+    def leg_n():
+        f = files["n"]
+        t0 = time.perf_counter()
+        first = np.asarray([0, f["frames"].size], np.uintp)
+        frames, cons = np.zeros(1, np.int64), np.zeros(1, np.uintp)
+        rc = hlib.flake_amd_decode_set_index(g, n, f["frames"].ctypes.data, first.ctypes.data, 1, all_sizes.ctypes.data, cap_all,
+                                             frames.ctypes.data, cons.ctypes.data)
+        assert rc == 0 and frames[0] == NF and cons[0] == f["frames"].size, hlib.flake_amd_decode_set_last_error(g)
+        window("n", f["frames"], all_sizes[:NF])
+        return (time.perf_counter() - t0) * 1e3
+
+    ms = {"t": [], "n": []}
+    for r in range(rounds + 1):
+        for k, fn in (("t", leg_t), ("n", leg_n)):
+            v = fn()
+            if r:
+                ms[k].append(v)
+    hlib.flake_amd_decode_set_close(g)
+    assert np.array_equal(out["t"], out["n"])
+    npts = V.read_seektable(files["t"]["table"])[1]
+    sec = [f"{SEEK_MARK}{NF} frames of {n} ({files['n']['frames'].size} bytes of frames), written by flake_amd_cli with --seekpoints "
+           f"{SPACING} ({npts} points) and without; one window of {WIN} samples from sample {SKIP}; index + "
+           f"flake_amd_decode_set_windows, medians of {rounds} after one discarded, {torch.cuda.get_device_name(0)}:"]
+    for k, what in (("t", "SEEKTABLE: the piece between two points indexed on the CPU"),
+                    ("n", "no table: the whole file indexed on the device (K8)")):
+        v = ms[k]
+        sec.append(f"  {k}  {what:62s} {indexed[k][0]:5d} frames indexed, {indexed[k][1]} decoded {statistics.median(v):9.2f} ms  "
+                   f"(min {min(v):.2f}, max {max(v):.2f})")
+    return sec
+
+
+if SEEK_ONLY:
+    sec = seek_leg()
+    print("\n".join(sec), flush=True)
+    old = open(out_path).read().split("\n") if os.path.exists(out_path) else []
+    cut = next((i for i, ln in enumerate(old) if ln.startswith(SEEK_MARK)), len(old))
+    kept = old[:cut]
+    while kept and not kept[-1]:
+        kept.pop()
+    open(out_path, "w").write("\n".join(kept + [""] + sec) + "\n")
+    sys.exit(0)
 
 pcm = np.ascontiguousarray(V.synth_pcm(NF, n, ch, 16).reshape(NF, n * ch), np.int32)
 p = V.level_params(5, block_size=n, variable_block_size=0)
@@ -44,7 +144,6 @@ with V.Encoder(p, max_frames=NF) as enc:
         wrote = C.c_int64(0)
         assert enc.lib.fhip_encode_frames_packed(enc._h, C.byref(b), buf.ctypes.data, cap, C.byref(wrote)) == 0
         data.append((buf[:wrote.value].copy(), fb))
-hlib = V.load_host_library()
 rng = np.random.default_rng(7)
 
 
@@ -158,4 +257,7 @@ with V.Encoder(p, max_frames=NF) as enc:
                 tp.append(kt[0] * mult)
         say(f"  {c['S']:5d} streams: windows' frames ({len(wfb)} frames in {done} calls) {statistics.median(tw):8.3f} ms;  "
             f"every frame ({NF * mult} frames, {mult} x one call's time) {statistics.median(tp):8.3f} ms")
+say()
+for ln in seek_leg():
+    say(ln)
 open(out_path, "w").write("\n".join(lines) + "\n")
