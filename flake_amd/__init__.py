@@ -160,6 +160,15 @@ class DecodeWindows(C.Structure):
     _fields_ = [("seg_skip", C.c_void_p), ("seg_take", C.c_void_p)]
 
 
+class RowsOut(C.Structure):
+    """``fhip_rows_out``"""
+    _fields_ = [("rows", C.c_void_p), ("nrows", C.c_int32), ("format", C.c_int32), ("row_len", C.c_int64)]
+
+
+# FHIP_ROWS_* / FLAKE_AMD_ROWS_*: what an element of a row is
+ROWS_I32, ROWS_I16, ROWS_F32 = 0, 1, 2
+
+
 class IndexIn(C.Structure):
     """``fhip_index_in``"""
     _fields_ = [("stream", C.c_void_p), ("stream_bytes", C.c_int64), ("range_first", C.c_void_p),
@@ -289,6 +298,11 @@ def load_library() -> C.CDLL:
                                            C.POINTER(DecodeOut)]),
         "fhip_decode_frames_segments_keep": (i, [vp, C.POINTER(DecodeIn), C.POINTER(DecodeSegments), C.POINTER(DecodeOut),
                                                  C.POINTER(DecodeMd5)]),
+        "fhip_rows_from_segments_dev": (i, [vp, vp, i64, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(RowsOut)]),
+        "fhip_rows_zero_dev": (i, [vp, C.POINTER(RowsOut), C.c_int32, C.c_int32]),
+        "fhip_decode_frames_windows_rows": (i, [vp, C.POINTER(DecodeIn), C.POINTER(DecodeSegments),
+                                                C.POINTER(DecodeWindows), vp, vp, C.POINTER(RowsOut),
+                                                C.POINTER(DecodeOut)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -324,6 +338,7 @@ ABI_SYMBOLS = (
     "fhip_index_frames_dev", "fhip_index_frames", "fhip_index_geometry",
     "fhip_gather_spans_dev", "fhip_frames_packed_gather", "fhip_decode_frames_segments_keep",
     "fhip_decode_frames_windows_dev", "fhip_decode_frames_windows",
+    "fhip_rows_from_segments_dev", "fhip_rows_zero_dev", "fhip_decode_frames_windows_rows",
 )
 
 # fhip_gather_piece (24 bytes): K9's unit, in samples per channel
@@ -713,6 +728,58 @@ class Encoder:
         wn = DecodeWindows(_ptr(seg_skip), _ptr(seg_take))
         return int(self.lib.fhip_decode_frames_windows_dev(self._h, C.byref(di), C.byref(sg), C.byref(wn), C.byref(do)))
 
+    # -- K10: windows as rows on the device --------------------------------
+    def rows_from_segments_dev(self, pcm, pcm_cap: int, nsegs: int, seg_start, seg_samples, seg_failed, seg_row, seg_col,
+                               rows, nrows: int, row_len: int, fmt: int) -> int:
+        """fhip_rows_from_segments_dev (K10 alone): everything is device memory (torch tensors or raw addresses) -- pcm
+        int32 [pcm_cap][channels], seg_start / seg_samples / seg_col int64, seg_failed / seg_row int32, rows
+        [nrows][channels][row_len] of the format fmt (ROWS_*).  Async on the handle's stream.  Returns the code:
+        E_INVALID means nothing was queued."""
+        ro = RowsOut(_ptr(rows), int(nrows), int(fmt), int(row_len))
+        return int(self.lib.fhip_rows_from_segments_dev(self._h, _ptr(pcm), int(pcm_cap), int(nsegs), _ptr(seg_start),
+                                                        _ptr(seg_samples), _ptr(seg_failed), _ptr(seg_row), _ptr(seg_col),
+                                                        C.byref(ro)))
+
+    def rows_zero_dev(self, rows, nrows: int, row_len: int, fmt: int, first_row: int, count: int) -> int:
+        """fhip_rows_zero_dev: zero rows first_row .. first_row + count of the destination; async.  Returns the code."""
+        ro = RowsOut(_ptr(rows), int(nrows), int(fmt), int(row_len))
+        return int(self.lib.fhip_rows_zero_dev(self._h, C.byref(ro), int(first_row), int(count)))
+
+    def decode_frames_windows_rows(self, stream, frame_bytes, pcm_cap: int, seg_first, seg_skip, seg_take, seg_row, seg_col,
+                                   rows, nrows: int, row_len: int, fmt: int, seg_number=None, seg_variable=None):
+        """fhip_decode_frames_windows_rows: decode_frames_windows' host arguments, host tables seg_row (int32) and
+        seg_col (int64) and a device destination rows [nrows][channels][row_len] of the format fmt.  Returns
+        decode_frames_windows' tuple with None where the samples were."""
+        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
+                                  else stream, dtype=np.uint8)
+        fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
+        sf = np.ascontiguousarray(seg_first, dtype=np.int32)
+        ns = len(sf) - 1
+        k = max(ns, 1)
+        num = np.full(k, -1, np.int64) if seg_number is None else np.ascontiguousarray(seg_number, dtype=np.int64)
+        var = np.zeros(k, np.int32) if seg_variable is None else np.ascontiguousarray(seg_variable, dtype=np.int32)
+        skip = np.ascontiguousarray(seg_skip, dtype=np.int64)
+        take = np.ascontiguousarray(seg_take, dtype=np.int64)
+        srow = np.ascontiguousarray(seg_row, dtype=np.int32)
+        scol = np.ascontiguousarray(seg_col, dtype=np.int64)
+        if len(skip) != ns or len(take) != ns or len(srow) != ns or len(scol) != ns:
+            raise ValueError("seg_skip, seg_take, seg_row and seg_col hold one value per segment")
+        s_start, s_samples = np.full(k, -7, np.int64), np.full(k, -7, np.int64)
+        s_failed = np.full(k, -7, np.int32)
+        recs = np.zeros(len(fb), dtype=VERIFY_REC_DTYPE)
+        summary = np.zeros(4, dtype=np.int64)
+        nsm = np.zeros(1, dtype=np.int64)
+        di = DecodeIn(st.ctypes.data if st.size else None, st.size, fb.ctypes.data if fb.size else None, len(fb), 0, -1)
+        do = DecodeOut(None, pcm_cap, recs.ctypes.data if len(fb) else None, summary.ctypes.data, nsm.ctypes.data)
+        sg = DecodeSegments(sf.ctypes.data, ns, num.ctypes.data, var.ctypes.data, s_start.ctypes.data,
+                            s_samples.ctypes.data, s_failed.ctypes.data)
+        wn = DecodeWindows(skip.ctypes.data, take.ctypes.data)
+        ro = RowsOut(_ptr(rows), int(nrows), int(fmt), int(row_len))
+        rc = self.lib.fhip_decode_frames_windows_rows(self._h, C.byref(di), C.byref(sg), C.byref(wn), srow.ctypes.data,
+                                                      scol.ctypes.data, C.byref(ro), C.byref(do))
+        return (rc, None, int(nsm[0]), recs, summary, s_start[:ns], s_samples[:ns], s_failed[:ns],
+                self.lib.fhip_last_error(self._h).decode() if rc else "")
+
     # -- K8: frame discovery ----------------------------------------------
     def index_ranges(self, stream, range_first, max_block_size: int = 0, frame_cap: int | None = None, sentinel=None):
         """fhip_index_frames on host data: the CPU indexer's answer for the streams stream[range_first[r] :
@@ -1039,6 +1106,10 @@ def load_host_library() -> C.CDLL:
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t,
                                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
     lib.flake_amd_decode_set_windows.restype = C.c_longlong
+    lib.flake_amd_decode_set_windows_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong,
+                                                      C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
+    lib.flake_amd_decode_set_windows_rows.restype = C.c_longlong
     lib.flake_amd_read_seektable.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
     lib.flake_amd_read_seektable.restype = C.c_longlong
     lib.flake_amd_seek_lookup.argtypes = [C.c_void_p, C.c_int, C.c_ulonglong]
@@ -1534,6 +1605,7 @@ class DecodeSet:
         self.lib = load_host_library()
         self.si = like
         self.nstreams = int(nstreams)
+        self.device = int(os.environ.get("FLAKE_AMD_DEVICE") or 0)      # (what flake_amd_decode_set_open reads)
         self._g = self.lib.flake_amd_decode_set_open(C.byref(like), self.nstreams, int(flags))
         if not self._g:
             raise FlakeHipError(-1, "flake_amd_decode_set_open", self.lib.flake_amd_decode_set_last_error(None).decode())
@@ -1608,6 +1680,55 @@ class DecodeSet:
                 res.append(out[at:at + ws[w]])
                 at += int(ws[w])
         return res, wst[:len(windows)], int(nfd.value), begins
+
+    def decode_windows_rows(self, windows, row_len: int, dtype=None, out=None):
+        """flake_amd_decode_set_windows_rows: decode_windows' windows as a padded planar batch that stays on the set's
+        device.  Returns (tensor [nwin, channels, row_len] of dtype torch.int32, torch.int16 or torch.float32 -- the
+        default, samples scaled to [-1, 1) --; lengths, an int64 CPU tensor, -1 for a window that failed; win_status
+        int32[]; the frames handed to the device).  Whatever no good window delivered is zero.  out (optional): a
+        contiguous tensor on the set's device whose first nwin rows are written; it may hold more rows, which are not
+        touched.  Raises FlakeHipError when the call is refused: nothing was written then.  Nothing is pending afterwards.
+        ctypes only; no compute here."""
+        import torch
+        if dtype is None:
+            dtype = torch.float32 if out is None else out.dtype
+        fmt = {torch.int32: ROWS_I32, torch.int16: ROWS_I16, torch.float32: ROWS_F32}.get(dtype)
+        if fmt is None:
+            raise ValueError("dtype is torch.int32, torch.int16 or torch.float32")
+        nwin, ch, row_len = len(windows), int(self.si.channels), int(row_len)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((nwin, ch, max(row_len, 0)), dtype=dtype, device=dev)
+        elif (out.dtype != dtype or out.device != dev or not out.is_contiguous() or out.dim() != 3 or out.shape[0] < nwin
+              or tuple(out.shape[1:]) != (ch, row_len)):
+            raise ValueError("out must be a contiguous [>= nwin, channels, row_len] tensor of dtype on the set's device")
+        fs = [np.ascontiguousarray(w[1], dtype=np.int32) for w in windows]
+        fow = np.asarray([len(f) for f in fs], dtype=np.int32)
+        parts = [np.frombuffer(bytes(w[0]), dtype=np.uint8) if isinstance(w[0], (bytes, bytearray))
+                 else np.asarray(w[0], dtype=np.uint8) for w in windows]
+        st = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, np.uint8)
+        sizes = np.ascontiguousarray(np.concatenate(fs)) if fs else np.zeros(0, np.int32)
+        fixed = np.asarray([w[2] for w in windows], dtype=np.uint32)
+        first = np.asarray([w[3] for w in windows], dtype=np.uint64)
+        count = np.asarray([w[4] for w in windows], dtype=np.int64)
+        k = max(nwin, 1)
+        ws, wst = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int32)
+        nfd = C.c_longlong(0)
+        have = nwin > 0
+        # the library writes on its handle's stream: whatever torch's own stream still has queued on this memory (the
+        # caching allocator may have handed out a block whose last use is pending there) finishes first
+        torch.cuda.current_stream(dev).synchronize()
+        n = self.lib.flake_amd_decode_set_windows_rows(self._g, nwin, fow.ctypes.data if have else None,
+                                                       st.ctypes.data if st.size else None, st.size,
+                                                       sizes.ctypes.data if sizes.size else None,
+                                                       fixed.ctypes.data if have else None,
+                                                       first.ctypes.data if have else None,
+                                                       count.ctypes.data if have else None,
+                                                       out.data_ptr() if have else None, fmt, row_len,
+                                                       ws.ctypes.data, wst.ctypes.data, C.byref(nfd))
+        if n < 0:
+            raise FlakeHipError(int(n), "flake_amd_decode_set_windows_rows", self.last_error())
+        return out[:nwin], torch.from_numpy(ws[:nwin].copy()), wst[:nwin], int(nfd.value)
 
     def index(self, streams, max_block_size: int | None = None):
         """flake_amd_decode_set_index: the frames of many files in one device call (K8).  streams: the files' bytes,

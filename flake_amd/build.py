@@ -24,7 +24,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIP_SRCS = ["csrc/k0_prepare.hip", "csrc/k1_autocorr.hip", "csrc/k2_lpc.hip", "csrc/k3_encode.hip", "csrc/k3s_search.hip",
             "csrc/k4_assemble.hip", "csrc/k5_verify.hip", "csrc/k6_md5.hip", "csrc/k7_decode.hip", "csrc/k7_decode_windows.hip",
             "csrc/k8_index.hip",
-            "csrc/k9_gather.hip", "csrc/api.hip"]
+            "csrc/k9_gather.hip", "csrc/k10_rows.hip", "csrc/api.hip"]
 HIP_HDRS = ["csrc/kernels.h", "csrc/device_util.h", "csrc/lpc_reg.h", "csrc/k3_common.h", "csrc/vbs_schedule.h",
             "csrc/vbs_block_lookup.h", "csrc/flac_parse.h", "csrc/flac_header.h", "../include/flakehip.h",
             "csrc/k7_decode.hip"]       # (k7_decode_windows.hip includes k7_decode.hip)

@@ -4,6 +4,7 @@
 // grow.  Every entry point maps HIP failures to FHIP_E_HIP and never throws.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -214,13 +215,14 @@ void note_launch(const char *fmt, ...)
 
 namespace {
 
-constexpr int kNumKernels = 9 + fhip::INDEX_STEPS;
+constexpr int kNumKernels = 10 + fhip::INDEX_STEPS;
 const char *const kKernelNames[kNumKernels] = {"k_prepare", "k_autocorr", "k_lpc", "k_encode", "k_assemble",
                                                "k_order_search", "k_verify", "k_decode",
                                                // K8's launches, one name each (fhip::index_step_name without the <>)
                                                "k_index_count", "k_index_wgscan", "k_index_scatter", "k_index_walk",
-                                               "k_index_ranges", "k_index_emit", "k_gather_spans"};
-constexpr int kProfVerify = 6, kProfDecode = 7, kProfIndex = 8, kProfGather = 8 + fhip::INDEX_STEPS;
+                                               "k_index_ranges", "k_index_emit", "k_gather_spans", "k_window_rows"};
+constexpr int kProfVerify = 6, kProfDecode = 7, kProfIndex = 8, kProfGather = 8 + fhip::INDEX_STEPS,
+              kProfRows = 9 + fhip::INDEX_STEPS;
 
 int fail_hip(fhip_ctx *c, hipError_t e, const char *what)
 {
@@ -2668,7 +2670,9 @@ int fhip_last_verify_failure(const fhip_ctx *c, int64_t *summary, fhip_verify_re
 namespace {
 // The entries' checks, with nothing queued and the launch list left empty where they refuse.
 // (segs: the segment mode, which does not read the call's variable_blocks and first_number; its tables must be there)
-int decode_check(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *out, const fhip_decode_segments *segs = nullptr)
+// (need_pcm false: the rows form, which decodes into the handle's staging and does not read out->pcm)
+int decode_check(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *out, const fhip_decode_segments *segs = nullptr,
+                 bool need_pcm = true)
 {
     if (!c) return FHIP_E_INVALID;
     c->launches.clear();
@@ -2679,7 +2683,7 @@ int decode_check(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *o
     if (in->nframes > c->max_frames) return fail(c, FHIP_E_INVALID, "nframes exceeds the handle's max_frames");
     if (!segs && in->variable_blocks != 0 && in->variable_blocks != 1) return fail(c, FHIP_E_INVALID, "variable_blocks is 0 or 1");
     if (in->nframes > 0 && (!in->stream || !in->frame_bytes)) return fail(c, FHIP_E_INVALID, "null stream");
-    if (out->pcm_cap > 0 && !out->pcm) return fail(c, FHIP_E_INVALID, "null pcm");
+    if (need_pcm && out->pcm_cap > 0 && !out->pcm) return fail(c, FHIP_E_INVALID, "null pcm");
     if (segs) {
         if (segs->nsegs < 1) return fail(c, FHIP_E_INVALID, "nsegs must be at least 1");
         if (!segs->seg_first || !segs->seg_number || !segs->seg_variable || !segs->seg_start || !segs->seg_samples ||
@@ -2729,7 +2733,68 @@ int run_decode(fhip_ctx *c, const fhip_decode_in &in, const fhip_decode_out &out
     }
     return FHIP_OK;
 }
+
+// K10's destination: what every rows entry refuses of it.
+int rows_check(fhip_ctx *c, const fhip_rows_out *rows)
+{
+    if (!rows || !rows->rows) return fail(c, FHIP_E_INVALID, "null rows");
+    if (rows->nrows < 1 || rows->row_len < 1) return fail(c, FHIP_E_INVALID, "nrows and row_len must be at least 1");
+    if (rows->format != FHIP_ROWS_I32 && rows->format != FHIP_ROWS_I16 && rows->format != FHIP_ROWS_F32)
+        return fail(c, FHIP_E_INVALID, "unknown rows format");
+    if (rows->format == FHIP_ROWS_I16 && c->p.bits_per_sample > 16)
+        return fail(c, FHIP_E_INVALID, "FHIP_ROWS_I16 needs bits_per_sample <= 16");
+    return FHIP_OK;
+}
+
+size_t rows_elem_bytes(int format) { return format == FHIP_ROWS_I16 ? sizeof(int16_t) : sizeof(int32_t); }
+
+// Queue K10 on the handle's stream; everything is device memory.
+int run_rows(fhip_ctx *c, const int32_t *pcm, int64_t pcm_cap, int nsegs, const int64_t *seg_start, const int64_t *seg_samples,
+             const int32_t *seg_failed, const int32_t *seg_row, const int64_t *seg_col, const fhip_rows_out &rows)
+{
+    if (nsegs < 1 || pcm_cap < 1) return FHIP_OK;
+    const fhip::WindowRowsArgs a{pcm, pcm_cap, nsegs, reinterpret_cast<const long long *>(seg_start),
+                                 reinterpret_cast<const long long *>(seg_samples), seg_failed, seg_row,
+                                 reinterpret_cast<const long long *>(seg_col), rows.rows, rows.nrows, rows.row_len,
+                                 rows.format, c->p.channels, ldexpf(1.0f, -(c->p.bits_per_sample - 1))};
+    Prof pr(c, kProfRows, c->profiling);
+    HIP_TRY(c, fhip::launch_window_rows(c->stream, a));
+    return FHIP_OK;
+}
 }  // namespace
+
+int fhip_rows_from_segments_dev(fhip_ctx *c, const int32_t *pcm, int64_t pcm_cap, int32_t nsegs, const int64_t *seg_start,
+                                const int64_t *seg_samples, const int32_t *seg_failed, const int32_t *seg_row,
+                                const int64_t *seg_col, const fhip_rows_out *rows)
+{
+    if (!c) return FHIP_E_INVALID;
+    c->launches.clear();
+    c->md5_log_entry = -1;
+    if (c->pcm_format == FHIP_PCM_S16) return fail(c, FHIP_E_UNSUPPORTED, "rows take int32 PCM only (FHIP_PCM_S16 is set)");
+    if (nsegs < 0 || pcm_cap < 0) return fail(c, FHIP_E_INVALID, "negative count");
+    if (!pcm || !seg_start || !seg_samples || !seg_failed || !seg_row || !seg_col) return fail(c, FHIP_E_INVALID, "null argument");
+    int rc = rows_check(c, rows);
+    if (rc != FHIP_OK) return rc;
+    LaunchScope ls(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    return run_rows(c, pcm, pcm_cap, nsegs, seg_start, seg_samples, seg_failed, seg_row, seg_col, *rows);
+}
+
+int fhip_rows_zero_dev(fhip_ctx *c, const fhip_rows_out *rows, int32_t first_row, int32_t count)
+{
+    if (!c) return FHIP_E_INVALID;
+    c->launches.clear();
+    c->md5_log_entry = -1;
+    int rc = rows_check(c, rows);
+    if (rc != FHIP_OK) return rc;
+    if (first_row < 0 || count < 0 || first_row > rows->nrows - count) return fail(c, FHIP_E_INVALID, "rows outside the destination");
+    if (count == 0) return FHIP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t row_bytes = (size_t)c->p.channels * (size_t)rows->row_len * rows_elem_bytes(rows->format);
+    HIP_TRY(c, hipMemsetAsync(static_cast<char *>(rows->rows) + (size_t)first_row * row_bytes, 0, (size_t)count * row_bytes,
+                              c->stream));
+    return FHIP_OK;
+}
 
 int fhip_decode_frames_dev(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *out)
 {
@@ -2771,12 +2836,20 @@ int fhip_decode_frames(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_
 // keep: out->pcm is DEVICE memory that K7 writes and K6 reads where it lies; nothing of it is downloaded
 // (fhip_decode_frames_segments_keep).
 // win (with segs, without md5): the window mode; its two tables travel behind everything else in the same block.
+// rows (with win): K7 decodes into d_vpcm as ever, K10 re-lays the segments into rows->out behind it, reading the
+// per-segment outputs where K7 left them, and no sample is downloaded (fhip_decode_frames_windows_rows); seg_col and
+// seg_row travel behind the window tables.
+struct RowsSink { const int32_t *seg_row; const int64_t *seg_col; const fhip_rows_out *out; };
 static int decode_segments_host(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
                                 const fhip_decode_out *out, const fhip_decode_md5 *md5, bool keep,
-                                const fhip_decode_windows *win = nullptr)
+                                const fhip_decode_windows *win = nullptr, const RowsSink *rows = nullptr)
 {
-    int rc = decode_check(c, in, out, segs);
+    int rc = decode_check(c, in, out, segs, !rows);
     if (rc != FHIP_OK) return rc;
+    if (rows) {
+        if (!rows->seg_row || !rows->seg_col) return fail(c, FHIP_E_INVALID, "null rows table");
+        if ((rc = rows_check(c, rows->out)) != FHIP_OK) return rc;
+    }
     if (win) {
         if (!win->seg_skip || !win->seg_take) return fail(c, FHIP_E_INVALID, "null window table");
         for (int s = 0; s < segs->nsegs; s++) {
@@ -2784,7 +2857,7 @@ static int decode_segments_host(fhip_ctx *c, const fhip_decode_in *in, const fhi
             if (win->seg_take[s] < -1) return fail(c, FHIP_E_INVALID, "seg_take is -1 or a count");
         }
     }
-    if (keep && c->pcm_format == FHIP_PCM_S16)
+    if ((keep || rows) && c->pcm_format == FHIP_PCM_S16)
         return fail(c, FHIP_E_UNSUPPORTED, "keeping the PCM on the device takes int32 PCM only (FHIP_PCM_S16 is set)");
     if (md5 && !segs) return fail(c, FHIP_E_INVALID, "md5 needs a segment table");
     const size_t ns = segs ? (size_t)segs->nsegs : 0, nst = md5 ? (size_t)(md5->nstreams > 0 ? md5->nstreams : 0) : 0;
@@ -2832,8 +2905,11 @@ static int decode_segments_host(fhip_ctx *c, const fhip_decode_in *in, const fhi
     fhip_decode_segments dsegs{};
     fhip_decode_windows dwin{};
     int32_t *d_i32 = nullptr;
+    const int64_t *d_seg_col = nullptr;
+    const int32_t *d_seg_row = nullptr;
     if (segs) {
-        const size_t n32 = 4 * ns + nst + 2, wwin = 3 * ns + (n32 + 1) / 2, words = wwin + (win ? 2 * ns : 0);
+        const size_t n32 = 4 * ns + nst + 2, wwin = 3 * ns + (n32 + 1) / 2, wrows = wwin + (win ? 2 * ns : 0),
+                     words = wrows + (rows ? ns + (ns + 1) / 2 : 0);
         c->h_dseg.assign(words, 0);
         HIP_TRY(c, c->d_dseg.reserve(words));
         int32_t *h_i32 = reinterpret_cast<int32_t *>(c->h_dseg.data() + 3 * ns);
@@ -2855,6 +2931,12 @@ static int decode_segments_host(fhip_ctx *c, const fhip_decode_in *in, const fhi
             dwin.seg_skip = reinterpret_cast<const int64_t *>(c->d_dseg.get() + wwin);
             dwin.seg_take = reinterpret_cast<const int64_t *>(c->d_dseg.get() + wwin + ns);
         }
+        if (rows) {
+            memcpy(c->h_dseg.data() + wrows, rows->seg_col, ns * sizeof(int64_t));
+            memcpy(c->h_dseg.data() + wrows + ns, rows->seg_row, ns * sizeof(int32_t));
+            d_seg_col = reinterpret_cast<const int64_t *>(c->d_dseg.get() + wrows);
+            d_seg_row = reinterpret_cast<const int32_t *>(c->d_dseg.get() + wrows + ns);
+        }
         HIP_TRY(c, hipMemcpyAsync(c->d_dseg, c->h_dseg.data(), words * sizeof(long long), hipMemcpyHostToDevice, c->stream));
         dsegs.seg_first = d_i32;
         dsegs.nsegs = segs->nsegs;
@@ -2874,6 +2956,11 @@ static int decode_segments_host(fhip_ctx *c, const fhip_decode_in *in, const fhi
         if (rc != FHIP_OK) return rc;
         if ((rc = md5_dev_end(c)) != FHIP_OK) return rc;
     }
+    if (rows) {
+        rc = run_rows(c, dpcm, cap, segs->nsegs, dsegs.seg_start, dsegs.seg_samples, dsegs.seg_failed, d_seg_row, d_seg_col,
+                      *rows->out);
+        if (rc != FHIP_OK) return rc;
+    }
     long long sum[7] = {0, 0, -1, 0, 0, 0, 0};
     HIP_TRY(c, hipMemcpyAsync(sum, c->d_vsum, sizeof sum, hipMemcpyDeviceToHost, c->stream));
     if (out->frames && nf)
@@ -2888,7 +2975,7 @@ static int decode_segments_host(fhip_ctx *c, const fhip_decode_in *in, const fhi
     // the samples, up to the end of the last frame that was placed and written: nothing behind it is touched (a frame
     // refused for pcm_cap leaves the caller's buffer as it was); a failed frame before it leaves its own range unspecified
     const long long wend = sum[6] < cap ? sum[6] : cap;
-    if (wend > 0 && !keep) {
+    if (wend > 0 && !keep && !rows) {
         HIP_TRY(c, hipMemcpyAsync(out->pcm, c->d_vpcm, (size_t)wend * (size_t)c->p.channels * c->pcm_width(),
                                   hipMemcpyDeviceToHost, c->stream));
         rc = fhip_sync(c);
@@ -2926,6 +3013,15 @@ int fhip_decode_frames_segments_keep(fhip_ctx *c, const fhip_decode_in *in, cons
                                      const fhip_decode_out *out, const fhip_decode_md5 *md5)
 {
     return decode_segments_host(c, in, segs, out, md5, true);
+}
+
+int fhip_decode_frames_windows_rows(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
+                                    const fhip_decode_windows *win, const int32_t *seg_row, const int64_t *seg_col,
+                                    const fhip_rows_out *rows, const fhip_decode_out *out)
+{
+    if (c && (!segs || !win)) { c->launches.clear(); c->md5_log_entry = -1; return fail(c, FHIP_E_INVALID, "null argument"); }
+    const RowsSink sink{seg_row, seg_col, rows};
+    return decode_segments_host(c, in, segs, out, nullptr, false, win, &sink);
 }
 
 // ---- K8: frame discovery ---------------------------------------------------------------------------

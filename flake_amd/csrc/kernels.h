@@ -465,4 +465,25 @@ struct GatherArgs {
 constexpr int GATHER_TILE_VALS = 1024;
 hipError_t launch_gather_spans(hipStream_t st, const GatherArgs &a);
 
+// K10 (k10_rows.hip): the segments K7's window mode left interleaved in pcm, as rows[nrows][channels][row_len] of int32,
+// int16 or float32 (format: FHIP_ROWS_*).  One launch on st, a workgroup per segment and tile of ROWS_TILE samples, sized
+// for the longest segment there can be.  All five tables are DEVICE memory; every read of them is clamped to
+// [0, nsegs), every source read into [0, pcm_cap * channels) and every write into the row's own [0, row_len) of a row in
+// [0, nrows), whatever they hold.  Segment k is delivered when seg_failed[k] < 0 and its row, column and start are in
+// range, cut at the row's end and at pcm_cap.  Nothing else is written.
+struct WindowRowsArgs {
+    const int32_t *pcm; long long pcm_cap;       // K7's interleaved output, samples per channel
+    int nsegs;
+    const long long *seg_start, *seg_samples;    // [nsegs] as K7 left them
+    const int32_t *seg_failed;                   // [nsegs]
+    const int32_t *seg_row;                      // [nsegs] the destination row; outside [0, nrows): not delivered
+    const long long *seg_col;                    // [nsegs] the first column
+    void *rows; int nrows; long long row_len;
+    int format, channels;
+    float scale;                                 // FHIP_ROWS_F32: 2^-(bits_per_sample - 1)
+    int tiles = 0;                               // (the launch's: tiles per segment)
+};
+constexpr int ROWS_TILE = 512;
+hipError_t launch_window_rows(hipStream_t st, const WindowRowsArgs &a);
+
 }  // namespace fhip

@@ -56,6 +56,8 @@ struct FlakeAmdDecodeSet {
     unsigned char *wstage;
     size_t wstage_cap;
     int32_t *wfb;
+    int32_t *wrow;                /* flake_amd_decode_set_windows_rows: each segment's row and first column */
+    int64_t *wcol;
     char err[384];
 };
 
@@ -130,11 +132,13 @@ FLAKE_AMD_API FlakeAmdDecodeSet *flake_amd_decode_set_open(const FlakeAmdStreami
     g->wb.seg_frame0 = (int32_t *)calloc(mb, sizeof(int32_t));
     g->wb.seg_last = (int32_t *)calloc(mb, sizeof(int32_t));
     g->wfb = (int32_t *)calloc(mb, sizeof(int32_t));
+    g->wrow = (int32_t *)calloc(mb, sizeof(int32_t));
+    g->wcol = (int64_t *)calloc(mb, sizeof(int64_t));
     const int have = g->st && g->sx && g->digests && b->seg_first && b->seg_number && b->seg_variable && b->seg_stream &&
                      b->seg_run && b->seg_frame0 && b->seg_prev && b->md5_first && b->md5_range && b->last_seg &&
                      b->planned && g->seg_start && g->seg_samples && g->seg_failed && g->recs && g->seg_ok &&
                      g->wb.seg_first && g->wb.seg_number && g->wb.seg_variable && g->wb.seg_skip && g->wb.seg_take &&
-                     g->wb.seg_win && g->wb.seg_frame0 && g->wb.seg_last && g->wfb;
+                     g->wb.seg_win && g->wb.seg_frame0 && g->wb.seg_last && g->wfb && g->wrow && g->wcol;
     int rc = have ? fhip_create(&g->hip, ed ? atoi(ed) : 0, &p, g->max_batch) : FHIP_E_NOMEM;
     if (rc == FHIP_OK && ds_device_md5(g)) {
         g->states = (fhip_md5_state *)fhip_device_alloc(ns * sizeof(fhip_md5_state));
@@ -381,7 +385,19 @@ FLAKE_AMD_API long long flake_amd_decode_set_device_batches(const FlakeAmdDecode
  * Stateless, as flake_amd_decode_set_index is: the set lends its handle and its format.  decode_window_plan.h selects
  * the frames and cuts the batches; each batch's selected bytes are staged back to back and go through
  * fhip_decode_frames_windows, which delivers the batch's clips back to back where the call's output has got to.  A window
- * that failed keeps the room it asked for: what the batch left behind it is moved up by the difference. */
+ * that failed keeps the room it asked for: what the batch left behind it is moved up by the difference.
+ *
+ * The rows sink (flake_amd_decode_set_windows_rows) is the same loop with another destination: window w is row w of a
+ * device buffer, each batch goes through fhip_decode_frames_windows_rows with the segment's window as its row and what
+ * the window has delivered so far as its column, and nothing is moved on the host.  The destination is zeroed on the
+ * handle's stream before the first batch and a failed window's row again at the end, so that whatever no good window
+ * delivered is zero. */
+typedef struct {
+    void *dev_rows;
+    int format;
+    long long row_len;
+} ds_rows_sink;
+
 static int ds_grow(void **p, size_t *cap, size_t want, size_t elem)
 {
     if (want <= *cap) return 0;
@@ -392,14 +408,25 @@ static int ds_grow(void **p, size_t *cap, size_t want, size_t elem)
     return 0;
 }
 
-FLAKE_AMD_API long long flake_amd_decode_set_windows(FlakeAmdDecodeSet *g, int nwin, const int *frames_of_win,
+static long long ds_windows(FlakeAmdDecodeSet *g, int nwin, const int *frames_of_win,
         const unsigned char *stream, size_t bytes, const int *frame_sizes,
         const unsigned *fixed_block_size, const unsigned long long *first_sample, const long long *count,
-        void *pcm, int sample_bytes, size_t pcm_cap_samples,
+        void *pcm, int sample_bytes, size_t pcm_cap_samples, const ds_rows_sink *rows,
         long long *win_samples, int *win_status, long long *frames_decoded)
 {
     if (!g) return -1;
     g->err[0] = 0;
+    if (rows) {                                       /* (pcm is null, sample_bytes 4; the room is what the windows ask for) */
+        if (rows->row_len < 1 || (!rows->dev_rows && nwin > 0) ||
+            (rows->format != FHIP_ROWS_I32 && rows->format != FHIP_ROWS_I16 && rows->format != FHIP_ROWS_F32)) {
+            snprintf(g->err, sizeof g->err, "bad argument");
+            return -1;
+        }
+        if (rows->format == FHIP_ROWS_I16 && g->si.bits_per_sample > 16) {
+            snprintf(g->err, sizeof g->err, "int16 rows need bits_per_sample <= 16");
+            return -1;
+        }
+    }
     if (nwin < 0 || (nwin > 0 && (!frames_of_win || !fixed_block_size || !first_sample || !count || !win_samples || !win_status)) ||
         (!stream && bytes) || (!pcm && pcm_cap_samples) || (sample_bytes != 2 && sample_bytes != 4)) {
         snprintf(g->err, sizeof g->err, "bad argument");
@@ -410,15 +437,21 @@ FLAKE_AMD_API long long flake_amd_decode_set_windows(FlakeAmdDecodeSet *g, int n
         return -1;
     }
     long long nf = 0, asked = 0;
+    const long long room = rows ? 0x7FFFFFFFFFFFFFFFll : (long long)pcm_cap_samples;
     for (int w = 0; w < nwin; w++) {
-        if (frames_of_win[w] < 0 || count[w] < 0 || count[w] > (long long)pcm_cap_samples - asked) {
+        if (frames_of_win[w] < 0 || count[w] < 0 || count[w] > room - asked) {
             snprintf(g->err, sizeof g->err, "%s", frames_of_win[w] < 0 || count[w] < 0 ? "negative count"
                                                   : "pcm_cap_samples is below the samples the windows ask for");
+            return -1;
+        }
+        if (rows && count[w] > rows->row_len) {
+            snprintf(g->err, sizeof g->err, "a window asks for more than row_len samples");
             return -1;
         }
         asked += count[w];
         nf += frames_of_win[w];
     }
+    if (rows) pcm_cap_samples = (size_t)asked;
     if (nf && !frame_sizes) { snprintf(g->err, sizeof g->err, "bad argument"); return -1; }
     {
         size_t cap = g->foff_cap;
@@ -470,6 +503,12 @@ FLAKE_AMD_API long long flake_amd_decode_set_windows(FlakeAmdDecodeSet *g, int n
     fa_dw_cursor cur;
     memset(&cur, 0, sizeof cur);
     fa_dw_batch *b = &g->wb;
+    /* from here on the rows sink writes: everything is zero before the first batch delivers */
+    fhip_rows_out ro = {rows ? rows->dev_rows : NULL, nwin, rows ? rows->format : 0, rows ? rows->row_len : 0};
+    if (rows && nwin > 0 && fhip_rows_zero_dev(g->hip, &ro, 0, nwin) != FHIP_OK) {
+        snprintf(g->err, sizeof g->err, "fhip_rows_zero_dev: %s", fhip_last_error(g->hip));
+        return -1;
+    }
     long long decoded = 0;
     long long out_at = 0;                             /* where the next delivered sample goes */
     int settled = 0;                                  /* windows before this one have their place and count */
@@ -503,9 +542,16 @@ FLAKE_AMD_API long long flake_amd_decode_set_windows(FlakeAmdDecodeSet *g, int n
                                    g->seg_failed};
         fhip_decode_windows wn = {b->seg_skip, b->seg_take};
         const long long base = out_at;
-        fhip_decode_out out = {(int32_t *)((char *)pcm + (size_t)base * unit), (int64_t)pcm_cap_samples - base, g->recs,
-                               summary, &nsmp};
-        const int rc = fhip_decode_frames_windows(g->hip, &in, &sg, &wn, &out);
+        fhip_decode_out out = {rows ? NULL : (int32_t *)((char *)pcm + (size_t)base * unit), (int64_t)pcm_cap_samples - base,
+                               g->recs, summary, &nsmp};
+        if (rows)                                     /* a window continues where its earlier segments got to */
+            for (int k = 0; k < b->nsegs; k++) {
+                const int w = b->seg_win[k];
+                g->wrow[k] = win_status[w] ? -1 : w;
+                g->wcol[k] = win_samples[w];
+            }
+        const int rc = rows ? fhip_decode_frames_windows_rows(g->hip, &in, &sg, &wn, g->wrow, g->wcol, &ro, &out)
+                            : fhip_decode_frames_windows(g->hip, &in, &sg, &wn, &out);
         g->device_batches++;
         decoded += b->nframes;
         if (rc != FHIP_OK && rc != FHIP_E_VERIFY) {
@@ -536,7 +582,7 @@ FLAKE_AMD_API long long flake_amd_decode_set_windows(FlakeAmdDecodeSet *g, int n
                 settled = w + 1;
             }
         }
-        for (int k = b->nsegs - 1; k >= 0; k--) {     /* targets never lie before the sources: from the back */
+        for (int k = b->nsegs - 1; k >= 0 && !rows; k--) {    /* targets never lie before the sources: from the back */
             const long long src = base + g->seg_start[k], dst = b->seg_take[k];
             if (g->seg_samples[k] > 0 && dst != src)
                 memmove((char *)pcm + (size_t)dst * unit, (char *)pcm + (size_t)src * unit, (size_t)g->seg_samples[k] * unit);
@@ -550,11 +596,47 @@ FLAKE_AMD_API long long flake_amd_decode_set_windows(FlakeAmdDecodeSet *g, int n
         if (win_status[w]) win_samples[w] = -1;
         else total += win_samples[w];
     }
+    if (rows && nwin > 0) {
+        /* a failed window's row may hold what its earlier segments delivered: zero again, run by run, then wait */
+        int rc = FHIP_OK;
+        for (int w = 0; w < nwin && rc == FHIP_OK;) {
+            int e = w;
+            while (e < nwin && win_status[e]) e++;
+            if (e > w) rc = fhip_rows_zero_dev(g->hip, &ro, w, e - w);
+            w = e + 1;
+        }
+        if (rc == FHIP_OK) rc = fhip_sync(g->hip);
+        if (rc != FHIP_OK) {
+            snprintf(g->err, sizeof g->err, "flake_amd_decode_set_windows_rows: %s", fhip_last_error(g->hip));
+            return -1;
+        }
+    }
     if (frames_decoded) *frames_decoded = decoded;
     return total;
 nomem:
     snprintf(g->err, sizeof g->err, "out of memory");
     return -1;
+}
+
+FLAKE_AMD_API long long flake_amd_decode_set_windows(FlakeAmdDecodeSet *g, int nwin, const int *frames_of_win,
+        const unsigned char *stream, size_t bytes, const int *frame_sizes,
+        const unsigned *fixed_block_size, const unsigned long long *first_sample, const long long *count,
+        void *pcm, int sample_bytes, size_t pcm_cap_samples,
+        long long *win_samples, int *win_status, long long *frames_decoded)
+{
+    return ds_windows(g, nwin, frames_of_win, stream, bytes, frame_sizes, fixed_block_size, first_sample, count, pcm,
+                      sample_bytes, pcm_cap_samples, NULL, win_samples, win_status, frames_decoded);
+}
+
+FLAKE_AMD_API long long flake_amd_decode_set_windows_rows(FlakeAmdDecodeSet *g, int nwin, const int *frames_of_win,
+        const unsigned char *stream, size_t bytes, const int *frame_sizes,
+        const unsigned *fixed_block_size, const unsigned long long *first_sample, const long long *count,
+        void *dev_rows, int row_format, long long row_len,
+        long long *win_samples, int *win_status, long long *frames_decoded)
+{
+    const ds_rows_sink sink = {dev_rows, row_format, row_len};
+    return ds_windows(g, nwin, frames_of_win, stream, bytes, frame_sizes, fixed_block_size, first_sample, count, NULL, 4, 0,
+                      &sink, win_samples, win_status, frames_decoded);
 }
 
 FLAKE_AMD_API int flake_amd_decode_set_index(FlakeAmdDecodeSet *g, unsigned max_block_size, const unsigned char *stream,
@@ -586,6 +668,7 @@ FLAKE_AMD_API void flake_amd_decode_set_close(FlakeAmdDecodeSet *g)
     free(g->st); free(g->sx); free(g->digests);
     free(g->wb.seg_first); free(g->wb.seg_number); free(g->wb.seg_variable); free(g->wb.seg_skip); free(g->wb.seg_take);
     free(g->wb.seg_win); free(g->wb.seg_frame0); free(g->wb.seg_last); free(g->wfb);
+    free(g->wrow); free(g->wcol);
     free(g->wsel); free((void *)g->wdata); free((void *)g->wsizes); free((void *)g->woff); free(g->wat); free(g->foff); free(g->wstage);
     free(g);
 }

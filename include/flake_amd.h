@@ -452,6 +452,33 @@ FLAKE_AMD_API long long flake_amd_decode_set_windows(FlakeAmdDecodeSet *g, int n
         const unsigned *fixed_block_size, const unsigned long long *first_sample, const long long *count,
         void *pcm, int sample_bytes, size_t pcm_cap_samples,
         long long *win_samples, int *win_status, long long *frames_decoded);
+/*
+ * The same windows as a padded planar batch that STAYS ON THE DEVICE, for a consumer there (a training loop that crops a
+ * corpus): window w is row w of dev_rows, DEVICE memory on the set's device of nwin x channels x row_len elements laid
+ * out [window][channel][time].  row_format says what an element is: FLAKE_AMD_ROWS_I32 the sample, FLAKE_AMD_ROWS_I16
+ * the sample as int16_t (sets of at most 16 bits), FLAKE_AMD_ROWS_F32 (float)sample * 2^-(bits_per_sample - 1), a value in
+ * [-1, 1) that is exact up to 24 bits and rounded once, to nearest even, above.  Arguments, selection, batches,
+ * win_samples, win_status, *frames_decoded and the return value are flake_amd_decode_set_windows', value for value.
+ * No sample crosses to the host: each batch's windows are re-laid on the device behind the decoder (K10), a window
+ * that a batch cuts continuing at the column it had reached.
+ *
+ * On return the rows are complete, nothing is pending, and every element of all nwin rows that no good window's
+ * delivered samples cover is zero: the padding behind a window, the row of a window that delivers nothing, and the whole
+ * row of a window that failed -- also where an earlier batch had written part of it.  (The destination is zeroed on the
+ * device before the first batch and a failed window's row again at the end.)  The library writes on its handle's
+ * stream: work of the caller's that still uses dev_rows on another stream must have finished before the call.
+ * Returns -1 with nothing written to dev_rows for what flake_amd_decode_set_windows refuses, a count[w] above row_len,
+ * row_len < 1, a null dev_rows with nwin > 0, an unknown row_format or FLAKE_AMD_ROWS_I16 above 16 bits.  Stateless like
+ * its sibling.
+ */
+#define FLAKE_AMD_ROWS_I32 0
+#define FLAKE_AMD_ROWS_I16 1
+#define FLAKE_AMD_ROWS_F32 2
+FLAKE_AMD_API long long flake_amd_decode_set_windows_rows(FlakeAmdDecodeSet *g, int nwin, const int *frames_of_win,
+        const unsigned char *stream, size_t bytes, const int *frame_sizes,
+        const unsigned *fixed_block_size, const unsigned long long *first_sample, const long long *count,
+        void *dev_rows, int row_format, long long row_len,
+        long long *win_samples, int *win_status, long long *frames_decoded);
 FLAKE_AMD_API const char *flake_amd_decode_set_last_error(const FlakeAmdDecodeSet *g);
 FLAKE_AMD_API void flake_amd_decode_set_close(FlakeAmdDecodeSet *g);
 

@@ -894,6 +894,61 @@ FHIP_API int fhip_frames_packed_gather(fhip_ctx *ctx, const fhip_batch *b, const
 FHIP_API int fhip_decode_frames_segments_keep(fhip_ctx *ctx, const fhip_decode_in *in, const fhip_decode_segments *segs,
                                               const fhip_decode_out *out, const fhip_decode_md5 *md5);
 
+/* ---- windows as a padded planar batch on the device (K10) ------------- */
+
+/*
+ * What K7's window mode leaves -- the segments' samples back to back, channel-interleaved int32 -- re-laid as
+ * rows[nrows][channels][row_len] in DEVICE memory of the caller's, for a consumer on the same device.  Sample x is
+ * written as
+ *   FHIP_ROWS_I32   x
+ *   FHIP_ROWS_I16   (int16_t)x                                    handles of bits_per_sample <= 16 only
+ *   FHIP_ROWS_F32   (float)x * 2^-(bits_per_sample - 1)           in [-1, 1): the conversion rounds to nearest even, the
+ *                   scaling is exact (exact altogether up to 24 bits)
+ * Segment k goes to row seg_row[k] from column seg_col[k] on.  It is delivered when seg_failed[k] < 0,
+ * 0 <= seg_row[k] < nrows, 0 <= seg_col[k] < row_len and 0 <= seg_start[k] < pcm_cap, and then writes, for i in
+ * [0, min(seg_samples[k], row_len - seg_col[k], pcm_cap - seg_start[k])) and every channel c,
+ *   rows[seg_row[k]][c][seg_col[k] + i] = conv(pcm[(seg_start[k] + i) * channels + c]).
+ * Every other segment writes nothing, and nothing else is written: the kernel zeroes nothing -- padding is the caller's
+ * (fhip_rows_zero_dev).  Segments that share a row must not overlap.
+ */
+#define FHIP_ROWS_I32 0
+#define FHIP_ROWS_I16 1
+#define FHIP_ROWS_F32 2
+
+typedef struct fhip_rows_out {
+    void   *rows;                 /* DEVICE [nrows][channels][row_len] elements of the format */
+    int32_t nrows;                /* >= 1 */
+    int32_t format;               /* FHIP_ROWS_* */
+    int64_t row_len;              /* >= 1 */
+} fhip_rows_out;
+
+/* K10 alone.  All pointers DEVICE pointers: pcm [pcm_cap][channels] int32, seg_start / seg_samples (int64) and
+ * seg_failed (int32) as K7 left them, seg_row (int32) and seg_col (int64) the caller's, [nsegs] each.  Asynchronous on
+ * the handle's stream.  The kernel clamps every table index to [0, nsegs), every read into the source and every write
+ * into its row whatever the tables hold.  Launch list: "k_window_rows"; timed under that name with fhip_set_profiling.
+ * FHIP_E_INVALID with nothing queued and an empty launch list for null pointers, nsegs < 0, pcm_cap < 0, nrows < 1,
+ * row_len < 1, an unknown format or FHIP_ROWS_I16 on a handle above 16 bits; FHIP_E_UNSUPPORTED under FHIP_PCM_S16
+ * (the source is int32).  nsegs == 0 or pcm_cap == 0: nothing is queued. */
+FHIP_API int fhip_rows_from_segments_dev(fhip_ctx *ctx, const int32_t *pcm, int64_t pcm_cap, int32_t nsegs,
+                                         const int64_t *seg_start, const int64_t *seg_samples, const int32_t *seg_failed,
+                                         const int32_t *seg_row, const int64_t *seg_col, const fhip_rows_out *rows);
+/* Zero bits -- zero in all three formats -- into rows first_row .. first_row + count of rows, on the handle's stream
+ * (a memset, no kernel: the launch list is left empty).  FHIP_E_INVALID for what the entry above refuses of rows, for a
+ * negative first_row or count, or a range that ends behind nrows.  count == 0: nothing is queued. */
+FHIP_API int fhip_rows_zero_dev(fhip_ctx *ctx, const fhip_rows_out *rows, int32_t first_row, int32_t count);
+/* fhip_decode_frames_windows with the samples delivered as rows ON THE DEVICE: host in / segs / win as there, host
+ * tables seg_row (int32) and seg_col (int64) [nsegs], rows->rows DEVICE memory.  K7's window mode decodes into the
+ * handle's own staging and K10 runs behind it on the same stream, reading seg_start / seg_samples / seg_failed where K7
+ * left them: no host round trip in between and no sample downloaded.  Records, summary, nsamples and the per-segment
+ * outputs come back as from the host form, with one synchronisation, after which the rows are written.  out->pcm is
+ * not read; out->pcm_cap bounds the staging as it does there.  The launch list is the window list with "k_window_rows"
+ * at its end.  FHIP_OK or FHIP_E_VERIFY as the host form; FHIP_E_INVALID also for what fhip_rows_from_segments_dev
+ * refuses of rows and for null tables; FHIP_E_UNSUPPORTED under FHIP_PCM_S16. */
+FHIP_API int fhip_decode_frames_windows_rows(fhip_ctx *ctx, const fhip_decode_in *in, const fhip_decode_segments *segs,
+                                             const fhip_decode_windows *win, const int32_t *seg_row,
+                                             const int64_t *seg_col, const fhip_rows_out *rows,
+                                             const fhip_decode_out *out);
+
 /* ---- measurement ---------------------------------------------------- */
 
 /* With profiling on, every kernel launch of the hot path is bracketed by
@@ -909,7 +964,8 @@ FHIP_API int fhip_get_kernel_times(fhip_ctx *ctx, const char **names, double *ms
  * one or two workgroups per tile), "tail" (K2 runs inside K1), "fused" (K1 applies K0's decisions),
  * "narrow" (16-bit sample rows).  The calls that start a new list are the encode entries
  * (fhip_encode_subframes*, fhip_frames_packed_begin / fhip_encode_frames_packed, the VBS entries)
- * and fhip_prepare_ahead, the fhip_md5_* entries, fhip_decode_frames(_dev), fhip_decode_frames_segments(_dev, _keep), fhip_decode_frames_windows(_dev),
+ * and fhip_prepare_ahead, the fhip_md5_* entries, fhip_decode_frames(_dev), fhip_decode_frames_segments(_dev, _keep), fhip_decode_frames_windows(_dev, _rows),
+ * fhip_rows_from_segments_dev, fhip_rows_zero_dev (which leaves it empty),
  * fhip_index_frames(_dev), fhip_gather_spans_dev and fhip_frames_packed_gather.  A host-side record: it adds no device work.  (One exception:
  * "k_md5_streams<int16_t,2> fast" / "... general" name a choice that is made on the device when the block shape
  * allows the fast path; asking for the list then waits for that launch.)  names[0 .. cap) receive
