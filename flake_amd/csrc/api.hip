@@ -16,6 +16,7 @@
 
 #include "flakehip.h"
 #include "kernels.h"
+#include "table_block.h"
 #include "vbs_schedule.h"
 #include "vbs_block_lookup.h"
 
@@ -41,6 +42,40 @@ template <class T> struct DevBuf {
     }
     T *get() const { return p; }
     operator T *() const { return p; }
+};
+
+// A finished table layout (table_block.h) bound to one of the handle's blocks and, where the tables travel, to the host
+// image of its first host_bytes.  Constructing it is the block's one reserve -- DevBuf::reserve frees the old block when
+// it grows -- and pointers come from here alone: none can be formed before that reserve, or from a layout that is still
+// growing.  status() says whether the reserve succeeded and is looked at first.
+class TableBlock {
+    char *d_, *h_ = nullptr;
+    size_t host_bytes_ = 0;
+    hipError_t status_;
+
+public:
+    TableBlock(const fhip::TableLayout &l, DevBuf<long long> &dev)
+        : status_(dev.reserve(l.words())) { d_ = reinterpret_cast<char *>(dev.get()); }
+    // with a host image, all zero to begin with, of the block's first host_bytes
+    TableBlock(const fhip::TableLayout &l, DevBuf<long long> &dev, std::vector<long long> &image, size_t host_bytes)
+        : TableBlock(l, dev)
+    {
+        image.assign((host_bytes + sizeof(long long) - 1) / sizeof(long long), 0);
+        h_ = reinterpret_cast<char *>(image.data());
+        host_bytes_ = host_bytes;
+    }
+    TableBlock(const TableBlock &) = delete;
+    TableBlock &operator=(const TableBlock &) = delete;
+    hipError_t status() const { return status_; }
+    template <class T> T *dev(const fhip::TableSlot<T> &s) const { return reinterpret_cast<T *>(d_ + s.off); }
+    template <class T> T *host(const fhip::TableSlot<T> &s) const { return reinterpret_cast<T *>(h_ + s.off); }
+    // the caller's table into its slot of the image
+    template <class T> void fill(const fhip::TableSlot<T> &s, const T *from) const { memcpy(h_ + s.off, from, s.bytes); }
+    // the whole image to the device
+    hipError_t upload(hipStream_t stream) const
+    {
+        return hipMemcpyAsync(d_, h_, host_bytes_, hipMemcpyHostToDevice, stream);
+    }
 };
 
 struct fhip_ctx {
@@ -148,13 +183,12 @@ struct fhip_ctx {
     uint32_t vfail_number = 0;                // table said so
 
     // K8 (fhip_index_frames*): working memory, grow-only, allocated at first use (ensure_index)
-    DevBuf<int32_t> d_iwg;                    // wg_cnt [nwg], wg_key [nwg + 1], ncand [1]
-    DevBuf<int32_t> d_icand;                  // cand_pos, cand_meta, cand_end: [table_cap] each
+    DevBuf<long long> d_iwg;                  // table blocks (run_index): wg_cnt [nwg], wg_key [nwg + 1], ncand [1]
+    DevBuf<long long> d_icand;                // cand_pos, cand_meta, cand_end: [table_cap] each
     DevBuf<unsigned long long> d_inumkey;     // [table_cap]
-    DevBuf<long long> d_irng;                 // rng_off [nranges], then rng_cf, rng_cnt, rng_vbs as int32
+    DevBuf<long long> d_irng;                 // rng_off, rng_cf, rng_cnt, rng_vbs: [nranges] each
     DevBuf<uint8_t> d_istream;                // fhip_index_frames: the host stream uploaded ...
-    DevBuf<long long> d_iio;                  // ... range_first [nranges + 1], range_consumed [nranges], then int32:
-                                              // range_frames, range_variable [nranges], frame_bytes
+    DevBuf<long long> d_iio;                  // ... and the table block of its ranges and outputs
     std::vector<long long> h_iio;             // ... and the host image the outputs come back to
 
     // K9 (fhip_gather_spans_dev, fhip_frames_packed_gather): the piece table on the device, grow-only
@@ -2668,6 +2702,20 @@ int fhip_last_verify_failure(const fhip_ctx *c, int64_t *summary, fhip_verify_re
 // ---- K7: decoding ----------------------------------------------------------------------------------
 
 namespace {
+// How every K7 and K10 entry begins: the last call's launch list is gone, whatever this call goes on to do ...
+void entry_reset(fhip_ctx *c)
+{
+    c->launches.clear();
+    c->md5_log_entry = -1;
+}
+
+// ... and how it ends where a table or a structure it cannot do without is missing.
+int refuse_null(fhip_ctx *c)
+{
+    entry_reset(c);
+    return fail(c, FHIP_E_INVALID, "null argument");
+}
+
 // The entries' checks, with nothing queued and the launch list left empty where they refuse.
 // (segs: the segment mode, which does not read the call's variable_blocks and first_number; its tables must be there)
 // (need_pcm false: the rows form, which decodes into the handle's staging and does not read out->pcm)
@@ -2675,9 +2723,8 @@ int decode_check(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *o
                  bool need_pcm = true)
 {
     if (!c) return FHIP_E_INVALID;
-    c->launches.clear();
-    c->md5_log_entry = -1;
-    if (!in || !out || !out->summary || !out->nsamples) return fail(c, FHIP_E_INVALID, "null argument");
+    if (!in || !out || !out->summary || !out->nsamples) return refuse_null(c);
+    entry_reset(c);
     if (in->nframes < 0 || in->stream_bytes < 0 || out->pcm_cap < 0 || (!segs && in->first_number < -1))
         return fail(c, FHIP_E_INVALID, "negative count");
     if (in->nframes > c->max_frames) return fail(c, FHIP_E_INVALID, "nframes exceeds the handle's max_frames");
@@ -2768,8 +2815,7 @@ int fhip_rows_from_segments_dev(fhip_ctx *c, const int32_t *pcm, int64_t pcm_cap
                                 const int64_t *seg_col, const fhip_rows_out *rows)
 {
     if (!c) return FHIP_E_INVALID;
-    c->launches.clear();
-    c->md5_log_entry = -1;
+    entry_reset(c);
     if (c->pcm_format == FHIP_PCM_S16) return fail(c, FHIP_E_UNSUPPORTED, "rows take int32 PCM only (FHIP_PCM_S16 is set)");
     if (nsegs < 0 || pcm_cap < 0) return fail(c, FHIP_E_INVALID, "negative count");
     if (!pcm || !seg_start || !seg_samples || !seg_failed || !seg_row || !seg_col) return fail(c, FHIP_E_INVALID, "null argument");
@@ -2783,8 +2829,7 @@ int fhip_rows_from_segments_dev(fhip_ctx *c, const int32_t *pcm, int64_t pcm_cap
 int fhip_rows_zero_dev(fhip_ctx *c, const fhip_rows_out *rows, int32_t first_row, int32_t count)
 {
     if (!c) return FHIP_E_INVALID;
-    c->launches.clear();
-    c->md5_log_entry = -1;
+    entry_reset(c);
     int rc = rows_check(c, rows);
     if (rc != FHIP_OK) return rc;
     if (first_row < 0 || count < 0 || first_row > rows->nrows - count) return fail(c, FHIP_E_INVALID, "rows outside the destination");
@@ -2817,7 +2862,7 @@ int fhip_decode_frames_segments_dev(fhip_ctx *c, const fhip_decode_in *in, const
 int fhip_decode_frames_windows_dev(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
                                    const fhip_decode_windows *win, const fhip_decode_out *out)
 {
-    if (c && (!segs || !win)) { c->launches.clear(); c->md5_log_entry = -1; return fail(c, FHIP_E_INVALID, "null argument"); }
+    if (c && (!segs || !win)) return refuse_null(c);
     int rc = decode_check(c, in, out, segs);
     if (rc != FHIP_OK) return rc;
     if (!win->seg_skip || !win->seg_take) return fail(c, FHIP_E_INVALID, "null window table");
@@ -2830,37 +2875,56 @@ int fhip_decode_frames(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_
     return fhip_decode_frames_segments(c, in, nullptr, out, nullptr);
 }
 
-// The host form, with and without segments.  The segment tables travel in one block of the handle's (d_dseg): the
-// 8-byte ones first -- seg_number, seg_start, seg_samples -- then seg_first, seg_variable, seg_failed and, with md5, K6's
-// CSR (md5_first [nstreams + 1], md5_range [nsegs]), which is built here.
+// The host form, with and without segments.  What a call asks for beyond plain decoding:
+// segs: the segment mode; its tables, their outputs and whatever else the mode adds travel in one block (d_dseg).
+// md5 (with segs): K6 hashes every stream's segments behind K7, over a CSR that is built here.
 // keep: out->pcm is DEVICE memory that K7 writes and K6 reads where it lies; nothing of it is downloaded
 // (fhip_decode_frames_segments_keep).
-// win (with segs, without md5): the window mode; its two tables travel behind everything else in the same block.
+// win (with segs, without md5): the window mode.
 // rows (with win): K7 decodes into d_vpcm as ever, K10 re-lays the segments into rows->out behind it, reading the
-// per-segment outputs where K7 left them, and no sample is downloaded (fhip_decode_frames_windows_rows); seg_col and
-// seg_row travel behind the window tables.
+// per-segment outputs where K7 left them, and no sample is downloaded (fhip_decode_frames_windows_rows).
+namespace {
 struct RowsSink { const int32_t *seg_row; const int64_t *seg_col; const fhip_rows_out *out; };
-static int decode_segments_host(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
-                                const fhip_decode_out *out, const fhip_decode_md5 *md5, bool keep,
-                                const fhip_decode_windows *win = nullptr, const RowsSink *rows = nullptr)
+struct DecodeMode {
+    const fhip_decode_segments *segs = nullptr;
+    const fhip_decode_md5 *md5 = nullptr;
+    bool keep = false;
+    const fhip_decode_windows *win = nullptr;
+    const RowsSink *rows = nullptr;
+};
+
+// The call as the device sees it: what staging leaves for the launches and the collection.
+struct DecodeStaged {
+    fhip_decode_in in;
+    fhip_decode_out out;          // (pcm: the caller's with keep, d_vpcm otherwise; pcm_cap: no more than the frames can hold)
+    fhip_decode_segments segs{};
+    fhip_decode_windows win{};
+    const int32_t *md5_first = nullptr, *md5_range = nullptr;
+    const int64_t *seg_col = nullptr;
+    const int32_t *seg_row = nullptr;
+};
+
+// Everything the host form refuses, with nothing queued.
+int decode_host_check(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *out, const DecodeMode &m)
 {
-    int rc = decode_check(c, in, out, segs, !rows);
+    const fhip_decode_segments *segs = m.segs;
+    int rc = decode_check(c, in, out, segs, !m.rows);
     if (rc != FHIP_OK) return rc;
-    if (rows) {
-        if (!rows->seg_row || !rows->seg_col) return fail(c, FHIP_E_INVALID, "null rows table");
-        if ((rc = rows_check(c, rows->out)) != FHIP_OK) return rc;
+    if (m.rows) {
+        if (!m.rows->seg_row || !m.rows->seg_col) return fail(c, FHIP_E_INVALID, "null rows table");
+        if ((rc = rows_check(c, m.rows->out)) != FHIP_OK) return rc;
     }
-    if (win) {
-        if (!win->seg_skip || !win->seg_take) return fail(c, FHIP_E_INVALID, "null window table");
+    if (m.win) {
+        if (!m.win->seg_skip || !m.win->seg_take) return fail(c, FHIP_E_INVALID, "null window table");
         for (int s = 0; s < segs->nsegs; s++) {
-            if (win->seg_skip[s] < 0) return fail(c, FHIP_E_INVALID, "negative seg_skip");
-            if (win->seg_take[s] < -1) return fail(c, FHIP_E_INVALID, "seg_take is -1 or a count");
+            if (m.win->seg_skip[s] < 0) return fail(c, FHIP_E_INVALID, "negative seg_skip");
+            if (m.win->seg_take[s] < -1) return fail(c, FHIP_E_INVALID, "seg_take is -1 or a count");
         }
     }
-    if ((keep || rows) && c->pcm_format == FHIP_PCM_S16)
+    if ((m.keep || m.rows) && c->pcm_format == FHIP_PCM_S16)
         return fail(c, FHIP_E_UNSUPPORTED, "keeping the PCM on the device takes int32 PCM only (FHIP_PCM_S16 is set)");
-    if (md5 && !segs) return fail(c, FHIP_E_INVALID, "md5 needs a segment table");
-    const size_t ns = segs ? (size_t)segs->nsegs : 0, nst = md5 ? (size_t)(md5->nstreams > 0 ? md5->nstreams : 0) : 0;
+    if (m.md5 && !segs) return fail(c, FHIP_E_INVALID, "md5 needs a segment table");
+    const size_t ns = segs ? (size_t)segs->nsegs : 0;
     if (segs) {
         if (segs->seg_first[0] != 0) return fail(c, FHIP_E_INVALID, "seg_first[0] must be 0");
         for (size_t s = 0; s < ns; s++) {
@@ -2870,112 +2934,124 @@ static int decode_segments_host(fhip_ctx *c, const fhip_decode_in *in, const fhi
         }
         if (segs->seg_first[ns] != in->nframes) return fail(c, FHIP_E_INVALID, "seg_first must end at nframes");
     }
-    if (md5) {
-        if (!md5->states || !md5->seg_stream || md5->nstreams < 1) return fail(c, FHIP_E_INVALID, "null md5 argument");
+    if (m.md5) {
+        if (!m.md5->states || !m.md5->seg_stream || m.md5->nstreams < 1) return fail(c, FHIP_E_INVALID, "null md5 argument");
         for (size_t s = 0; s < ns; s++)
-            if (md5->seg_stream[s] < 0 || md5->seg_stream[s] >= md5->nstreams)
+            if (m.md5->seg_stream[s] < 0 || m.md5->seg_stream[s] >= m.md5->nstreams)
                 return fail(c, FHIP_E_INVALID, "seg_stream entry outside the states");
     }
-    const size_t nf = (size_t)in->nframes, sb = (size_t)in->stream_bytes;
     long long total = 0;
-    for (size_t f = 0; f < nf; f++) {
+    for (int f = 0; f < in->nframes; f++) {
         if (in->frame_bytes[f] < 0) return fail(c, FHIP_E_INVALID, "negative frame size");
         total += in->frame_bytes[f];
     }
     if (total != in->stream_bytes) return fail(c, FHIP_E_INVALID, "frame_bytes do not add up to stream_bytes");
-    LaunchScope ls(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    rc = ensure_verify(c, nf);
+    return FHIP_OK;
+}
+
+// The segment mode's tables: laid out, filled in the host image, uploaded in one copy, and named in st.
+int decode_host_stage_tables(fhip_ctx *c, const DecodeMode &m, DecodeStaged &st)
+{
+    const fhip_decode_segments *segs = m.segs;
+    const size_t ns = (size_t)segs->nsegs, nst = m.md5 ? (size_t)m.md5->nstreams : 0;
+    fhip::TableLayout l;
+    const auto number = l.add<int64_t>(ns), start = l.add<int64_t>(ns), samples = l.add<int64_t>(ns);
+    const auto first = l.add<int32_t>(ns + 1), variable = l.add<int32_t>(ns), failed = l.add<int32_t>(ns);
+    const auto md5_first = l.add<int32_t>(m.md5 ? nst + 1 : 0), md5_range = l.add<int32_t>(m.md5 ? ns : 0);
+    const auto skip = l.add<int64_t>(m.win ? ns : 0), take = l.add<int64_t>(m.win ? ns : 0);
+    const auto col = l.add<int64_t>(m.rows ? ns : 0);
+    const auto row = l.add<int32_t>(m.rows ? ns : 0);
+    const TableBlock tb(l, c->d_dseg, c->h_dseg, l.bytes());
+    HIP_TRY(c, tb.status());
+    tb.fill(number, segs->seg_number);
+    tb.fill(first, segs->seg_first);
+    tb.fill(variable, segs->seg_variable);
+    if (m.md5) {
+        // stream s absorbs its segments in batch order: a counting sort of the segments by stream
+        int32_t *sfirst = tb.host(md5_first), *range = tb.host(md5_range);
+        for (size_t s = 0; s < ns; s++) sfirst[m.md5->seg_stream[s] + 1]++;
+        for (size_t k = 0; k < nst; k++) sfirst[k + 1] += sfirst[k];
+        std::vector<int32_t> at(sfirst, sfirst + nst);
+        for (size_t s = 0; s < ns; s++) range[at[m.md5->seg_stream[s]]++] = (int32_t)s;
+    }
+    if (m.win) {
+        tb.fill(skip, m.win->seg_skip);
+        tb.fill(take, m.win->seg_take);
+    }
+    if (m.rows) {
+        tb.fill(col, m.rows->seg_col);
+        tb.fill(row, m.rows->seg_row);
+    }
+    HIP_TRY(c, tb.upload(c->stream));
+    st.segs = fhip_decode_segments{tb.dev(first), segs->nsegs, tb.dev(number), tb.dev(variable), tb.dev(start),
+                                   tb.dev(samples), tb.dev(failed)};
+    st.win = fhip_decode_windows{tb.dev(skip), tb.dev(take)};
+    st.md5_first = tb.dev(md5_first);
+    st.md5_range = tb.dev(md5_range);
+    st.seg_col = tb.dev(col);
+    st.seg_row = tb.dev(row);
+    return FHIP_OK;
+}
+
+// Staging: the stream and its frame sizes uploaded, room for the samples, the segment tables.
+int decode_host_stage(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *out, const DecodeMode &m, DecodeStaged &st)
+{
+    const size_t nf = (size_t)in->nframes, sb = (size_t)in->stream_bytes;
+    const int rc = ensure_verify(c, nf);
     if (rc != FHIP_OK) return rc;
     // no frame holds more than block_size samples: the staging output never needs more than that, whatever pcm_cap says
     const long long most = (long long)nf * c->p.block_size;
     const long long cap = out->pcm_cap < most ? out->pcm_cap : most;
-    const size_t nv = (size_t)cap * (size_t)c->p.channels;
     HIP_TRY(c, c->d_vstream.reserve(sb));
     HIP_TRY(c, c->d_vfb.reserve(nf));
-    if (!keep) HIP_TRY(c, c->d_vpcm.reserve(nv));
-    int32_t *const dpcm = keep ? out->pcm : c->d_vpcm.get();
+    if (!m.keep) HIP_TRY(c, c->d_vpcm.reserve((size_t)cap * (size_t)c->p.channels));
     if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_vstream, in->stream, sb, hipMemcpyHostToDevice, c->stream));
     if (nf) HIP_TRY(c, hipMemcpyAsync(c->d_vfb, in->frame_bytes, nf * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    fhip_decode_in din = *in;
-    din.stream = c->d_vstream; din.frame_bytes = c->d_vfb;
+    st.in = *in;
+    st.in.stream = c->d_vstream; st.in.frame_bytes = c->d_vfb;
     // summary [0..4), K7's key scratch [4], the sample count [5], the end of what was written [6]
-    fhip_decode_out dout{dpcm, cap, c->d_vrec, reinterpret_cast<int64_t *>(c->d_vsum.get()),
-                         reinterpret_cast<int64_t *>(c->d_vsum.get() + 5)};
-    fhip_decode_segments dsegs{};
-    fhip_decode_windows dwin{};
-    int32_t *d_i32 = nullptr;
-    const int64_t *d_seg_col = nullptr;
-    const int32_t *d_seg_row = nullptr;
-    if (segs) {
-        const size_t n32 = 4 * ns + nst + 2, wwin = 3 * ns + (n32 + 1) / 2, wrows = wwin + (win ? 2 * ns : 0),
-                     words = wrows + (rows ? ns + (ns + 1) / 2 : 0);
-        c->h_dseg.assign(words, 0);
-        HIP_TRY(c, c->d_dseg.reserve(words));
-        int32_t *h_i32 = reinterpret_cast<int32_t *>(c->h_dseg.data() + 3 * ns);
-        d_i32 = reinterpret_cast<int32_t *>(c->d_dseg.get() + 3 * ns);
-        memcpy(c->h_dseg.data(), segs->seg_number, ns * sizeof(int64_t));
-        memcpy(h_i32, segs->seg_first, (ns + 1) * sizeof(int32_t));
-        memcpy(h_i32 + ns + 1, segs->seg_variable, ns * sizeof(int32_t));
-        if (md5) {
-            // stream s absorbs its segments in batch order: a counting sort of the segments by stream
-            int32_t *first = h_i32 + 3 * ns + 1, *range = first + nst + 1;
-            for (size_t s = 0; s < ns; s++) first[md5->seg_stream[s] + 1]++;
-            for (size_t k = 0; k < nst; k++) first[k + 1] += first[k];
-            std::vector<int32_t> at(first, first + nst);
-            for (size_t s = 0; s < ns; s++) range[at[md5->seg_stream[s]]++] = (int32_t)s;
-        }
-        if (win) {
-            memcpy(c->h_dseg.data() + wwin, win->seg_skip, ns * sizeof(int64_t));
-            memcpy(c->h_dseg.data() + wwin + ns, win->seg_take, ns * sizeof(int64_t));
-            dwin.seg_skip = reinterpret_cast<const int64_t *>(c->d_dseg.get() + wwin);
-            dwin.seg_take = reinterpret_cast<const int64_t *>(c->d_dseg.get() + wwin + ns);
-        }
-        if (rows) {
-            memcpy(c->h_dseg.data() + wrows, rows->seg_col, ns * sizeof(int64_t));
-            memcpy(c->h_dseg.data() + wrows + ns, rows->seg_row, ns * sizeof(int32_t));
-            d_seg_col = reinterpret_cast<const int64_t *>(c->d_dseg.get() + wrows);
-            d_seg_row = reinterpret_cast<const int32_t *>(c->d_dseg.get() + wrows + ns);
-        }
-        HIP_TRY(c, hipMemcpyAsync(c->d_dseg, c->h_dseg.data(), words * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-        dsegs.seg_first = d_i32;
-        dsegs.nsegs = segs->nsegs;
-        dsegs.seg_number = reinterpret_cast<const int64_t *>(c->d_dseg.get());
-        dsegs.seg_variable = d_i32 + ns + 1;
-        dsegs.seg_start = reinterpret_cast<int64_t *>(c->d_dseg.get() + ns);
-        dsegs.seg_samples = reinterpret_cast<int64_t *>(c->d_dseg.get() + 2 * ns);
-        dsegs.seg_failed = d_i32 + 2 * ns + 1;
-    }
-    rc = run_decode(c, din, dout, segs ? &dsegs : nullptr, win ? &dwin : nullptr);
+    st.out = fhip_decode_out{m.keep ? out->pcm : c->d_vpcm.get(), cap, c->d_vrec, reinterpret_cast<int64_t *>(c->d_vsum.get()),
+                             reinterpret_cast<int64_t *>(c->d_vsum.get() + 5)};
+    return m.segs ? decode_host_stage_tables(c, m, st) : FHIP_OK;
+}
+
+// The launches: K7, then K6 or K10 behind it on the same stream, reading the PCM and the ranges where K7 left them.
+int decode_host_launch(fhip_ctx *c, const DecodeMode &m, const DecodeStaged &st)
+{
+    int rc = run_decode(c, st.in, st.out, m.segs ? &st.segs : nullptr, m.win ? &st.win : nullptr);
     if (rc != FHIP_OK) return rc;
-    if (md5) {
-        // the hash reads the PCM where K7 left it and the ranges K7 named, behind it on the same stream
+    if (m.md5) {
         if ((rc = md5_dev_begin(c)) != FHIP_OK) return rc;
-        rc = md5_ranges(c, md5->states, md5->nstreams, dpcm, d_i32 + 3 * ns + 1, d_i32 + 3 * ns + 1 + nst + 1,
-                        dsegs.seg_start, dsegs.seg_samples);
+        rc = md5_ranges(c, m.md5->states, m.md5->nstreams, st.out.pcm, st.md5_first, st.md5_range, st.segs.seg_start,
+                        st.segs.seg_samples);
         if (rc != FHIP_OK) return rc;
         if ((rc = md5_dev_end(c)) != FHIP_OK) return rc;
     }
-    if (rows) {
-        rc = run_rows(c, dpcm, cap, segs->nsegs, dsegs.seg_start, dsegs.seg_samples, dsegs.seg_failed, d_seg_row, d_seg_col,
-                      *rows->out);
-        if (rc != FHIP_OK) return rc;
-    }
+    if (m.rows)
+        rc = run_rows(c, st.out.pcm, st.out.pcm_cap, st.segs.nsegs, st.segs.seg_start, st.segs.seg_samples, st.segs.seg_failed,
+                      st.seg_row, st.seg_col, *m.rows->out);
+    return rc;
+}
+
+// The results into the caller's memory, and the verdict.
+int decode_host_collect(fhip_ctx *c, const fhip_decode_out *out, const DecodeMode &m, const DecodeStaged &st)
+{
+    const size_t nf = (size_t)st.in.nframes, ns = m.segs ? (size_t)m.segs->nsegs : 0;
     long long sum[7] = {0, 0, -1, 0, 0, 0, 0};
     HIP_TRY(c, hipMemcpyAsync(sum, c->d_vsum, sizeof sum, hipMemcpyDeviceToHost, c->stream));
     if (out->frames && nf)
         HIP_TRY(c, hipMemcpyAsync(out->frames, c->d_vrec, nf * sizeof(fhip_verify_rec), hipMemcpyDeviceToHost, c->stream));
-    if (segs) {
-        HIP_TRY(c, hipMemcpyAsync(segs->seg_start, dsegs.seg_start, ns * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(segs->seg_samples, dsegs.seg_samples, ns * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(segs->seg_failed, dsegs.seg_failed, ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (m.segs) {
+        HIP_TRY(c, hipMemcpyAsync(m.segs->seg_start, st.segs.seg_start, ns * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(m.segs->seg_samples, st.segs.seg_samples, ns * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(m.segs->seg_failed, st.segs.seg_failed, ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     }
-    rc = fhip_sync(c);
+    int rc = fhip_sync(c);
     if (rc != FHIP_OK) return rc;
     // the samples, up to the end of the last frame that was placed and written: nothing behind it is touched (a frame
     // refused for pcm_cap leaves the caller's buffer as it was); a failed frame before it leaves its own range unspecified
-    const long long wend = sum[6] < cap ? sum[6] : cap;
-    if (wend > 0 && !keep && !rows) {
+    const long long wend = sum[6] < st.out.pcm_cap ? sum[6] : st.out.pcm_cap;
+    if (wend > 0 && !m.keep && !m.rows) {
         HIP_TRY(c, hipMemcpyAsync(out->pcm, c->d_vpcm, (size_t)wend * (size_t)c->p.channels * c->pcm_width(),
                                   hipMemcpyDeviceToHost, c->stream));
         rc = fhip_sync(c);
@@ -2996,32 +3072,45 @@ static int decode_segments_host(fhip_ctx *c, const fhip_decode_in *in, const fhi
     return FHIP_E_VERIFY;
 }
 
+int decode_segments_host(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *out, const DecodeMode &m)
+{
+    int rc = decode_host_check(c, in, out, m);
+    if (rc != FHIP_OK) return rc;
+    LaunchScope ls(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    DecodeStaged st;
+    if ((rc = decode_host_stage(c, in, out, m, st)) != FHIP_OK) return rc;
+    if ((rc = decode_host_launch(c, m, st)) != FHIP_OK) return rc;
+    return decode_host_collect(c, out, m, st);
+}
+}  // namespace
+
 int fhip_decode_frames_segments(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
                                 const fhip_decode_out *out, const fhip_decode_md5 *md5)
 {
-    return decode_segments_host(c, in, segs, out, md5, false);
+    return decode_segments_host(c, in, out, DecodeMode{segs, md5});
 }
 
 int fhip_decode_frames_windows(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
                                const fhip_decode_windows *win, const fhip_decode_out *out)
 {
-    if (c && (!segs || !win)) { c->launches.clear(); c->md5_log_entry = -1; return fail(c, FHIP_E_INVALID, "null argument"); }
-    return decode_segments_host(c, in, segs, out, nullptr, false, win);
+    if (c && (!segs || !win)) return refuse_null(c);
+    return decode_segments_host(c, in, out, DecodeMode{segs, nullptr, false, win});
 }
 
 int fhip_decode_frames_segments_keep(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
                                      const fhip_decode_out *out, const fhip_decode_md5 *md5)
 {
-    return decode_segments_host(c, in, segs, out, md5, true);
+    return decode_segments_host(c, in, out, DecodeMode{segs, md5, true});
 }
 
 int fhip_decode_frames_windows_rows(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
                                     const fhip_decode_windows *win, const int32_t *seg_row, const int64_t *seg_col,
                                     const fhip_rows_out *rows, const fhip_decode_out *out)
 {
-    if (c && (!segs || !win)) { c->launches.clear(); c->md5_log_entry = -1; return fail(c, FHIP_E_INVALID, "null argument"); }
+    if (c && (!segs || !win)) return refuse_null(c);
     const RowsSink sink{seg_row, seg_col, rows};
-    return decode_segments_host(c, in, segs, out, nullptr, false, win, &sink);
+    return decode_segments_host(c, in, out, DecodeMode{segs, nullptr, false, win, &sink});
 }
 
 // ---- K8: frame discovery ---------------------------------------------------------------------------
@@ -3030,8 +3119,7 @@ namespace {
 int index_check(fhip_ctx *c, const fhip_index_in *in, const fhip_index_out *out)
 {
     if (!c) return FHIP_E_INVALID;
-    c->launches.clear();
-    c->md5_log_entry = -1;
+    entry_reset(c);
     if (!in || !out || !in->range_first || !out->range_frames || !out->range_consumed || !out->range_variable)
         return fail(c, FHIP_E_INVALID, "null argument");
     if (in->nranges < 1) return fail(c, FHIP_E_INVALID, "nranges must be at least 1");
@@ -3053,11 +3141,20 @@ int run_index(fhip_ctx *c, const fhip_index_in &in, const fhip_index_out &out)
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t nr = (size_t)in.nranges, cap = index_table_cap(in.stream_bytes, in.nranges);
     const int nwg = fhip::index_nwg(in.stream_bytes);
-    HIP_TRY(c, c->d_iwg.reserve(2 * (size_t)nwg + 2));
-    HIP_TRY(c, c->d_icand.reserve(3 * cap));
+    fhip::TableLayout lwg, lcand, lrng;
+    const auto wg_cnt = lwg.add<int32_t>((size_t)nwg);
+    const auto wg_key = lwg.add<uint32_t>((size_t)nwg + 1);
+    const auto ncand = lwg.add<int32_t>(1);
+    const auto cand_pos = lcand.add<int32_t>(cap);
+    const auto cand_meta = lcand.add<uint32_t>(cap);
+    const auto cand_end = lcand.add<int32_t>(cap);
+    const auto rng_off = lrng.add<long long>(nr);
+    const auto rng_cf = lrng.add<int32_t>(nr), rng_cnt = lrng.add<int32_t>(nr), rng_vbs = lrng.add<int32_t>(nr);
+    const TableBlock twg(lwg, c->d_iwg), tcand(lcand, c->d_icand), trng(lrng, c->d_irng);
+    HIP_TRY(c, twg.status());
+    HIP_TRY(c, tcand.status());
+    HIP_TRY(c, trng.status());
     HIP_TRY(c, c->d_inumkey.reserve(cap));
-    HIP_TRY(c, c->d_irng.reserve(nr + (3 * nr + 1) / 2));
-    int32_t *rng32 = reinterpret_cast<int32_t *>(c->d_irng.get() + nr);
     fhip::IndexArgs a{};
     a.stream = in.stream; a.stream_bytes = in.stream_bytes;
     a.range_first = reinterpret_cast<const long long *>(in.range_first); a.nranges = in.nranges;
@@ -3066,11 +3163,11 @@ int run_index(fhip_ctx *c, const fhip_index_in &in, const fhip_index_out &out)
     a.frame_bytes = out.frame_bytes; a.range_frames = out.range_frames;
     a.range_consumed = reinterpret_cast<long long *>(out.range_consumed); a.range_variable = out.range_variable;
     a.nwg = nwg;
-    a.wg_cnt = c->d_iwg; a.wg_key = reinterpret_cast<uint32_t *>(c->d_iwg.get() + nwg); a.ncand = c->d_iwg.get() + 2 * (size_t)nwg + 1;
+    a.wg_cnt = twg.dev(wg_cnt); a.wg_key = twg.dev(wg_key); a.ncand = twg.dev(ncand);
     a.table_cap = (long long)cap;
-    a.cand_pos = c->d_icand; a.cand_meta = reinterpret_cast<uint32_t *>(c->d_icand.get() + cap); a.cand_end = c->d_icand.get() + 2 * cap;
+    a.cand_pos = tcand.dev(cand_pos); a.cand_meta = tcand.dev(cand_meta); a.cand_end = tcand.dev(cand_end);
     a.cand_numkey = c->d_inumkey;
-    a.rng_off = c->d_irng; a.rng_cf = rng32; a.rng_cnt = rng32 + nr; a.rng_vbs = rng32 + 2 * nr;
+    a.rng_off = trng.dev(rng_off); a.rng_cf = trng.dev(rng_cf); a.rng_cnt = trng.dev(rng_cnt); a.rng_vbs = trng.dev(rng_vbs);
     for (int step = 0; step < fhip::INDEX_STEPS; step++) {
         Prof pr(c, kProfIndex + step, c->profiling);
         HIP_TRY(c, fhip::launch_index_step(c->stream, a, step));
@@ -3101,41 +3198,41 @@ int fhip_index_frames(fhip_ctx *c, const fhip_index_in *in, const fhip_index_out
     // no range holds more frames than candidates: the device never needs more room than the table has
     const size_t tcap = index_table_cap(in->stream_bytes, in->nranges);
     const size_t fcap = (size_t)in->frame_cap < tcap ? (size_t)in->frame_cap : tcap;
-    // one block: range_first [nr + 1], range_consumed [nr] (8 bytes each), then range_frames, range_variable [nr] and
-    // frame_bytes [fcap] (4 bytes each).  The sizes come back with the rest as far as `first` entries go -- one wait
-    // for any batch the decoder takes -- and the remainder, where there is one, in a second copy.
-    const size_t words = 2 * nr + 1 + (2 * nr + fcap + 1) / 2;
+    // one block: range_first, then what comes back -- range_consumed, range_frames, range_variable and the frame sizes,
+    // next to each other in this order.  The sizes come back with the rest as far as `first` entries go -- one wait for
+    // any batch the decoder takes -- and the remainder, where there is one, in a second copy.
     const size_t first = fcap < 65536 ? fcap : 65536;
+    fhip::TableLayout l;
+    const auto range_first = l.add<int64_t>(nr + 1), consumed = l.add<int64_t>(nr);
+    const auto frames = l.add<int32_t>(nr), variable = l.add<int32_t>(nr), sizes = l.add<int32_t>(fcap);
+    const auto back = sizes.head(first);              // where the first download ends
     HIP_TRY(c, c->d_istream.reserve(sb));
-    HIP_TRY(c, c->d_iio.reserve(words));
-    c->h_iio.resize(2 * nr + 1 + (2 * nr + first + 1) / 2);
+    const TableBlock tb(l, c->d_iio, c->h_iio, back.end());
+    HIP_TRY(c, tb.status());
     if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_istream, in->stream, sb, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_iio, in->range_first, (nr + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    int32_t *d32 = reinterpret_cast<int32_t *>(c->d_iio.get() + 2 * nr + 1);
+    HIP_TRY(c, hipMemcpyAsync(tb.dev(range_first), in->range_first, range_first.bytes, hipMemcpyHostToDevice, c->stream));
     fhip_index_in din = *in;
-    din.stream = c->d_istream; din.range_first = reinterpret_cast<const int64_t *>(c->d_iio.get());
+    din.stream = c->d_istream; din.range_first = tb.dev(range_first);
     din.frame_cap = (int32_t)fcap;
-    fhip_index_out dout{d32 + 2 * nr, d32, reinterpret_cast<int64_t *>(c->d_iio.get() + nr + 1), d32 + nr};
+    fhip_index_out dout{tb.dev(sizes), tb.dev(frames), tb.dev(consumed), tb.dev(variable)};
     rc = run_index(c, din, dout);
     if (rc != FHIP_OK) return rc;
-    long long *h = c->h_iio.data();
-    HIP_TRY(c, hipMemcpyAsync(h + nr + 1, c->d_iio.get() + nr + 1, nr * sizeof(int64_t) + (2 * nr + first) * sizeof(int32_t),
-                              hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(tb.host(consumed), tb.dev(consumed), back.end() - consumed.off, hipMemcpyDeviceToHost, c->stream));
     rc = fhip_sync(c);
     if (rc != FHIP_OK) return rc;
-    const int32_t *h32 = reinterpret_cast<const int32_t *>(h + 2 * nr + 1);
+    const int32_t *h_frames = tb.host(frames);
     size_t total = 0;
     for (size_t r = 0; r < nr; r++) {
-        out->range_frames[r] = h32[r];
-        out->range_consumed[r] = h[nr + 1 + r];
-        out->range_variable[r] = h32[nr + r];
-        if (h32[r] > 0) total += (size_t)h32[r];
+        out->range_frames[r] = h_frames[r];
+        out->range_consumed[r] = tb.host(consumed)[r];
+        out->range_variable[r] = tb.host(variable)[r];
+        if (h_frames[r] > 0) total += (size_t)h_frames[r];
     }
     if (total > fcap) total = fcap;
     const size_t got = total < first ? total : first;
-    if (got) memcpy(out->frame_bytes, h32 + 2 * nr, got * sizeof(int32_t));
+    if (got) memcpy(out->frame_bytes, tb.host(sizes), got * sizeof(int32_t));
     if (total > got) {
-        HIP_TRY(c, hipMemcpyAsync(out->frame_bytes + got, d32 + 2 * nr + got, (total - got) * sizeof(int32_t),
+        HIP_TRY(c, hipMemcpyAsync(out->frame_bytes + got, tb.dev(sizes) + got, (total - got) * sizeof(int32_t),
                                   hipMemcpyDeviceToHost, c->stream));
         rc = fhip_sync(c);
         if (rc != FHIP_OK) return rc;

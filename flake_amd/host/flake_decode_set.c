@@ -15,6 +15,7 @@
 #include "host_internal.h"
 #include "decode_set_plan.h"
 #include "decode_window_plan.h"
+#include "decode_window_place.h"
 
 typedef struct {
     long long frames_done;        /* frames committed so far */
@@ -28,6 +29,7 @@ struct FlakeAmdDecodeSet {
     FlakeAmdStreaminfo si;
     int nstreams, max_batch;
     unsigned flags;
+    void *tables;                 /* one block: every table below that nstreams or max_batch sizes (ds_carve) */
     fa_ds_stream *st;             /* what the planner reads */
     ds_stream *sx;                /* the rest */
     fhip_md5_state *states;       /* device: one per stream (neither _HOST nor _OFF) */
@@ -43,27 +45,71 @@ struct FlakeAmdDecodeSet {
     long long *run_off;           /* the last call's run offsets in pcm */
     int run_off_cap, run_off_n;
     /* flake_amd_decode_set_windows: the planner's tables (max_batch entries each), the selections and the runs' tables
-     * (one per window, grown on demand), the offsets of the call's frames and the staged bytes of a batch */
+     * (one per window: one block, wtables, grown on demand), the offsets of the call's frames and the staged bytes of a
+     * batch */
     fa_dw_batch wb;
+    void *wtables;
+    int wcap;
     fa_dw_sel *wsel;
     const unsigned char **wdata;
     const int **wsizes;
     const size_t **woff;
     long long *wat;
-    int wcap;
     size_t *foff;
     size_t foff_cap;
     unsigned char *wstage;
     size_t wstage_cap;
     int32_t *wfb;
+    int32_t *wstat;               /* each segment's failing frame's status, and where its samples belong (decode_window_place.h) */
+    long long *wtarget;
     int32_t *wrow;                /* flake_amd_decode_set_windows_rows: each segment's row and first column */
     int64_t *wcol;
     char err[384];
 };
 
+typedef char ds_header_status_agrees[(int)FA_WP_HEADER == (int)FHIP_VERIFY_HEADER ? 1 : -1];
+
 static char g_open_err[256];
 
 static int ds_device_md5(const FlakeAmdDecodeSet *g) { return !(g->flags & (FLAKE_AMD_SET_MD5_HOST | FLAKE_AMD_SET_MD5_OFF)); }
+
+/* One table of a block: count elements of elem bytes at *at, which moves on to the next 8-byte boundary behind them.
+ * Without a block (base NULL) only the sizes add up. */
+static void *ds_slot(unsigned char *base, size_t *at, size_t count, size_t elem)
+{
+    void *p = base ? base + *at : NULL;
+    *at += (count * elem + 7) & ~(size_t)7;
+    return p;
+}
+#define DS_SLOT(p, count) ((p) = ds_slot(base, &at, (count), sizeof *(p)))
+
+/* The tables of fixed size, [nstreams] and [max_batch] ones, in one block at base.  Returns the block's size. */
+static size_t ds_carve(FlakeAmdDecodeSet *g, unsigned char *base)
+{
+    const size_t mb = (size_t)g->max_batch, ns = (size_t)g->nstreams;
+    fa_ds_batch *b = &g->b;
+    fa_dw_batch *wb = &g->wb;
+    size_t at = 0;
+    DS_SLOT(g->st, ns); DS_SLOT(g->sx, ns);
+    g->digests = (unsigned char *)ds_slot(base, &at, ns, 16);
+    DS_SLOT(b->seg_first, mb + 1); DS_SLOT(b->seg_number, mb); DS_SLOT(b->seg_variable, mb); DS_SLOT(b->seg_stream, mb);
+    DS_SLOT(b->seg_run, mb); DS_SLOT(b->seg_frame0, mb); DS_SLOT(b->seg_prev, mb);
+    DS_SLOT(b->md5_first, ns + 1); DS_SLOT(b->md5_range, mb); DS_SLOT(b->last_seg, ns); DS_SLOT(b->planned, ns);
+    DS_SLOT(g->seg_start, mb); DS_SLOT(g->seg_samples, mb); DS_SLOT(g->seg_failed, mb); DS_SLOT(g->recs, mb);
+    DS_SLOT(g->seg_ok, mb);
+    DS_SLOT(wb->seg_first, mb + 1); DS_SLOT(wb->seg_number, mb); DS_SLOT(wb->seg_variable, mb); DS_SLOT(wb->seg_skip, mb);
+    DS_SLOT(wb->seg_take, mb); DS_SLOT(wb->seg_win, mb); DS_SLOT(wb->seg_frame0, mb); DS_SLOT(wb->seg_last, mb);
+    DS_SLOT(g->wfb, mb); DS_SLOT(g->wstat, mb); DS_SLOT(g->wtarget, mb); DS_SLOT(g->wrow, mb); DS_SLOT(g->wcol, mb);
+    return at;
+}
+
+/* The tables with an entry per window, n of them, likewise. */
+static size_t ds_carve_windows(FlakeAmdDecodeSet *g, unsigned char *base, size_t n)
+{
+    size_t at = 0;
+    DS_SLOT(g->wsel, n); DS_SLOT(g->wdata, n); DS_SLOT(g->wsizes, n); DS_SLOT(g->woff, n); DS_SLOT(g->wat, n);
+    return at;
+}
 
 FLAKE_AMD_API FlakeAmdDecodeSet *flake_amd_decode_set_open(const FlakeAmdStreaminfo *like, int nstreams, unsigned flags)
 {
@@ -102,46 +148,11 @@ FLAKE_AMD_API FlakeAmdDecodeSet *flake_amd_decode_set_open(const FlakeAmdStreami
     p.block_size = bs; p.order_method = 1; p.stereo_method = 1; p.prediction_type = 2;
     p.min_prediction_order = 1; p.max_prediction_order = 8; p.min_partition_order = 0; p.max_partition_order = 5;
     p.lpc_precision = 15;
-    const size_t mb = (size_t)g->max_batch, ns = (size_t)nstreams;
-    fa_ds_batch *b = &g->b;
-    g->st = (fa_ds_stream *)calloc(ns, sizeof *g->st);
-    g->sx = (ds_stream *)calloc(ns, sizeof *g->sx);
-    g->digests = (unsigned char *)calloc(ns, 16);
-    b->seg_first = (int32_t *)calloc(mb + 1, sizeof(int32_t));
-    b->seg_number = (int64_t *)calloc(mb, sizeof(int64_t));
-    b->seg_variable = (int32_t *)calloc(mb, sizeof(int32_t));
-    b->seg_stream = (int32_t *)calloc(mb, sizeof(int32_t));
-    b->seg_run = (int32_t *)calloc(mb, sizeof(int32_t));
-    b->seg_frame0 = (int32_t *)calloc(mb, sizeof(int32_t));
-    b->seg_prev = (int32_t *)calloc(mb, sizeof(int32_t));
-    b->md5_first = (int32_t *)calloc(ns + 1, sizeof(int32_t));
-    b->md5_range = (int32_t *)calloc(mb, sizeof(int32_t));
-    b->last_seg = (int32_t *)calloc(ns, sizeof(int32_t));
-    b->planned = (long long *)calloc(ns, sizeof(long long));
-    g->seg_start = (int64_t *)calloc(mb, sizeof(int64_t));
-    g->seg_samples = (int64_t *)calloc(mb, sizeof(int64_t));
-    g->seg_failed = (int32_t *)calloc(mb, sizeof(int32_t));
-    g->recs = (fhip_verify_rec *)calloc(mb, sizeof(fhip_verify_rec));
-    g->seg_ok = (unsigned char *)calloc(mb, 1);
-    g->wb.seg_first = (int32_t *)calloc(mb + 1, sizeof(int32_t));
-    g->wb.seg_number = (int64_t *)calloc(mb, sizeof(int64_t));
-    g->wb.seg_variable = (int32_t *)calloc(mb, sizeof(int32_t));
-    g->wb.seg_skip = (int64_t *)calloc(mb, sizeof(int64_t));
-    g->wb.seg_take = (int64_t *)calloc(mb, sizeof(int64_t));
-    g->wb.seg_win = (int32_t *)calloc(mb, sizeof(int32_t));
-    g->wb.seg_frame0 = (int32_t *)calloc(mb, sizeof(int32_t));
-    g->wb.seg_last = (int32_t *)calloc(mb, sizeof(int32_t));
-    g->wfb = (int32_t *)calloc(mb, sizeof(int32_t));
-    g->wrow = (int32_t *)calloc(mb, sizeof(int32_t));
-    g->wcol = (int64_t *)calloc(mb, sizeof(int64_t));
-    const int have = g->st && g->sx && g->digests && b->seg_first && b->seg_number && b->seg_variable && b->seg_stream &&
-                     b->seg_run && b->seg_frame0 && b->seg_prev && b->md5_first && b->md5_range && b->last_seg &&
-                     b->planned && g->seg_start && g->seg_samples && g->seg_failed && g->recs && g->seg_ok &&
-                     g->wb.seg_first && g->wb.seg_number && g->wb.seg_variable && g->wb.seg_skip && g->wb.seg_take &&
-                     g->wb.seg_win && g->wb.seg_frame0 && g->wb.seg_last && g->wfb && g->wrow && g->wcol;
-    int rc = have ? fhip_create(&g->hip, ed ? atoi(ed) : 0, &p, g->max_batch) : FHIP_E_NOMEM;
+    g->tables = calloc(1, ds_carve(g, NULL));
+    if (g->tables) ds_carve(g, (unsigned char *)g->tables);
+    int rc = g->tables ? fhip_create(&g->hip, ed ? atoi(ed) : 0, &p, g->max_batch) : FHIP_E_NOMEM;
     if (rc == FHIP_OK && ds_device_md5(g)) {
-        g->states = (fhip_md5_state *)fhip_device_alloc(ns * sizeof(fhip_md5_state));
+        g->states = (fhip_md5_state *)fhip_device_alloc((size_t)nstreams * sizeof(fhip_md5_state));
         rc = g->states ? fhip_md5_init_dev(g->hip, g->states, nstreams) : FHIP_E_NOMEM;
         if (rc == FHIP_OK) rc = fhip_sync(g->hip);
     }
@@ -162,16 +173,10 @@ static void ds_fail_stream(FlakeAmdDecodeSet *g, int s, long long frame, int sta
     g->sx[s].fail_status = status;
 }
 
-/* keep_fn: the keep-on-device destination (fa_decode_set_frames_keep) -- pcm is device memory that every batch decodes
- * to from its start, and each batch is handed to keep_fn once its segments are judged. */
-static long long ds_frames(FlakeAmdDecodeSet *g, int nruns, const int *stream_of_run, const int *frames_of_run,
-                           const unsigned char *stream, size_t bytes, const int *frame_sizes, void *pcm, int sample_bytes,
-                           size_t pcm_cap_samples, long long *run_samples, fa_ds_batch_fn keep_fn, void *keep_user)
+/* What both sinks refuse of the samples' width; bad_argument: the call's own null and range checks, first in line. */
+static int ds_refuse_samples(FlakeAmdDecodeSet *g, int bad_argument, int sample_bytes)
 {
-    if (!g) return -1;
-    g->err[0] = 0;
-    if ((!stream && bytes) || (!pcm && pcm_cap_samples) || (nruns > 0 && !run_samples) ||
-        (sample_bytes != 2 && sample_bytes != 4)) {
+    if (bad_argument || (sample_bytes != 2 && sample_bytes != 4)) {
         snprintf(g->err, sizeof g->err, "bad argument");
         return -1;
     }
@@ -179,6 +184,13 @@ static long long ds_frames(FlakeAmdDecodeSet *g, int nruns, const int *stream_of
         snprintf(g->err, sizeof g->err, "2-byte samples need bits_per_sample <= 16");
         return -1;
     }
+    return 0;
+}
+
+/* The rest of what flake_amd_decode_set_frames refuses, and what it needs before it changes the set. */
+static int ds_frames_begin(FlakeAmdDecodeSet *g, int nruns, const int *stream_of_run, const int *frames_of_run,
+                           const int *frame_sizes, size_t bytes, int sample_bytes)
+{
     long long total_frames = 0;
     const int chk = fa_ds_check(g->nstreams, g->st, nruns, stream_of_run, frames_of_run, frame_sizes, bytes, &total_frames);
     if (chk != FA_DS_OK) {
@@ -198,33 +210,108 @@ static long long ds_frames(FlakeAmdDecodeSet *g, int nruns, const int *stream_of
         snprintf(g->err, sizeof g->err, "%s", fhip_last_error(g->hip));
         return -1;
     }
+    return 0;
+}
+
+/* A stream seen for the first time tells its blocking strategy and first number in its first frame. */
+static void ds_first_frames(FlakeAmdDecodeSet *g, int nruns, const int *stream_of_run, const int *frames_of_run,
+                            const unsigned char *stream, const int *frame_sizes)
+{
+    size_t at = 0;
+    long long f = 0;
+    for (int r = 0; r < nruns; r++) {
+        const int s = stream_of_run[r];
+        if (frames_of_run[r] > 0 && !g->st[s].started && !g->st[s].failed) {
+            flac_header h;
+            if (fa_parse_header(&g->si, stream + at, (size_t)frame_sizes[f], &h)) {
+                /* not a header this parser takes: the device decides what is wrong with it (its status is the
+                 * stream's, as for any later frame); it is shown the strategy bit the frame carries */
+                g->st[s].variable = frame_sizes[f] >= 2 ? (stream[at + 1] & 1) : 0;
+            } else {
+                g->st[s].started = 1;
+                g->st[s].variable = h.vbs;
+                g->st[s].next_number = (long long)h.number;
+            }
+        }
+        for (int k = 0; k < frames_of_run[r]; k++) at += (size_t)frame_sizes[f++];
+    }
+}
+
+/* The batch's segments in order, once the device has answered: a good one commits its stream, a bad one fails it.
+ * base: where the batch's samples begin in pcm.  Returns how far the good segments reach from there. */
+static size_t ds_judge_batch(FlakeAmdDecodeSet *g, const unsigned char *stream, const int *frame_sizes, const void *pcm,
+                             int sample_bytes, size_t base, long long *run_samples)
+{
+    const fa_ds_batch *b = &g->b;
+    const size_t nch = g->si.channels;
+    const int bps = (int)g->si.bits_per_sample;
+    size_t extent = 0;
+    size_t hdr_at = b->byte0;
+    memset(g->seg_ok, 0, (size_t)b->nsegs);
+    for (int k = 0; k < b->nsegs; k++) {
+        const int s = b->seg_stream[k], r = b->seg_run[k];
+        const int nf = b->seg_first[k + 1] - b->seg_first[k];
+        fa_ds_stream *t = &g->st[s];
+        const size_t seg_bytes_at = hdr_at;
+        for (int f = b->seg_first[k]; f < b->seg_first[k + 1]; f++) hdr_at += (size_t)frame_sizes[b->frame0 + f];
+        if (!t->failed && g->seg_failed[k] >= 0) {
+            const int bad = g->seg_failed[k];
+            ds_fail_stream(g, s, g->sx[s].frames_done + (bad - b->seg_first[k]), (int)g->recs[bad].status);
+        }
+        if (!t->failed && b->seg_number[k] < 0 && b->seg_prev[k] >= 0) {
+            /* a variable-block-size stream's later segment of the batch: numbered on from the earlier one */
+            flac_header h;
+            if (fa_parse_header(&g->si, stream + seg_bytes_at, (size_t)frame_sizes[b->frame0 + b->seg_first[k]], &h) ||
+                (long long)h.number != t->next_number)
+                ds_fail_stream(g, s, g->sx[s].frames_done, FHIP_VERIFY_NUMBER);
+        }
+        if (!t->failed && !t->started)       /* the device took a first frame that the CPU parser did not */
+            ds_fail_stream(g, s, g->sx[s].frames_done, FHIP_VERIFY_HEADER);
+        if (!t->failed && !t->variable) {
+            /* fixed blocks: the size rule from segment to segment (fa_ds_fixed_sizes), on the first and last header */
+            flac_header h0, h1;
+            const size_t last_bytes = (size_t)frame_sizes[b->frame0 + b->seg_first[k + 1] - 1];
+            if (fa_parse_header(&g->si, stream + seg_bytes_at, (size_t)frame_sizes[b->frame0 + b->seg_first[k]], &h0) ||
+                fa_parse_header(&g->si, stream + hdr_at - last_bytes, last_bytes, &h1) ||
+                fa_ds_fixed_sizes(t, nf, h0.n, h1.n))
+                ds_fail_stream(g, s, g->sx[s].frames_done, FHIP_VERIFY_NUMBER);
+        }
+        if (t->failed) {
+            run_samples[r] = -1;
+            continue;
+        }
+        g->seg_ok[k] = 1;
+        const size_t at = base + (size_t)g->seg_start[k], n = (size_t)g->seg_samples[k];
+        if (b->seg_frame0[k] == 0) g->run_off[r] = (long long)at;
+        if (g->flags & FLAKE_AMD_SET_MD5_HOST) {
+            if (sample_bytes == 2) fa_md5_pcm16(&g->sx[s].md5, (const int16_t *)pcm + at * nch, n * nch, bps);
+            else fa_md5_pcm(&g->sx[s].md5, (const int32_t *)pcm + at * nch, n * nch, bps);
+        }
+        t->next_number += t->variable ? (long long)n : (long long)nf;
+        g->sx[s].frames_done += nf;
+        run_samples[r] += (long long)n;
+        if (at + n - base > extent) extent = at + n - base;
+    }
+    return extent;
+}
+
+/* keep_fn: the keep-on-device destination (fa_decode_set_frames_keep) -- pcm is device memory that every batch decodes
+ * to from its start, and each batch is handed to keep_fn once its segments are judged. */
+static long long ds_frames(FlakeAmdDecodeSet *g, int nruns, const int *stream_of_run, const int *frames_of_run,
+                           const unsigned char *stream, size_t bytes, const int *frame_sizes, void *pcm, int sample_bytes,
+                           size_t pcm_cap_samples, long long *run_samples, fa_ds_batch_fn keep_fn, void *keep_user)
+{
+    if (!g) return -1;
+    g->err[0] = 0;
+    if (ds_refuse_samples(g, (!stream && bytes) || (!pcm && pcm_cap_samples) || (nruns > 0 && !run_samples), sample_bytes) ||
+        ds_frames_begin(g, nruns, stream_of_run, frames_of_run, frame_sizes, bytes, sample_bytes))
+        return -1;
     /* from here on the call changes the set */
     g->have_digests = 0;
     g->run_off_n = nruns;
     for (int r = 0; r < nruns; r++) { run_samples[r] = 0; g->run_off[r] = -1; }
-    /* a stream seen for the first time tells its blocking strategy and first number in its first frame */
-    {
-        size_t at = 0;
-        long long f = 0;
-        for (int r = 0; r < nruns; r++) {
-            const int s = stream_of_run[r];
-            if (frames_of_run[r] > 0 && !g->st[s].started && !g->st[s].failed) {
-                flac_header h;
-                if (fa_parse_header(&g->si, stream + at, (size_t)frame_sizes[f], &h)) {
-                    /* not a header this parser takes: the device decides what is wrong with it (its status is the
-                     * stream's, as for any later frame); it is shown the strategy bit the frame carries */
-                    g->st[s].variable = frame_sizes[f] >= 2 ? (stream[at + 1] & 1) : 0;
-                } else {
-                    g->st[s].started = 1;
-                    g->st[s].variable = h.vbs;
-                    g->st[s].next_number = (long long)h.number;
-                }
-            }
-            for (int k = 0; k < frames_of_run[r]; k++) at += (size_t)frame_sizes[f++];
-        }
-    }
+    ds_first_frames(g, nruns, stream_of_run, frames_of_run, stream, frame_sizes);
     const size_t nch = g->si.channels;
-    const int bps = (int)g->si.bits_per_sample;
     fa_ds_cursor cur;
     memset(&cur, 0, sizeof cur);
     fa_ds_batch *b = &g->b;
@@ -245,54 +332,7 @@ static long long ds_frames(FlakeAmdDecodeSet *g, int nruns, const int *stream_of
             snprintf(g->err, sizeof g->err, "fhip_decode_frames_segments: %s", fhip_last_error(g->hip));
             return -1;
         }
-        memset(g->seg_ok, 0, (size_t)b->nsegs);
-        /* the batch's segments in order: a good one commits its stream, a bad one fails it */
-        size_t extent = 0;
-        size_t hdr_at = b->byte0;
-        for (int k = 0; k < b->nsegs; k++) {
-            const int s = b->seg_stream[k], r = b->seg_run[k];
-            const int nf = b->seg_first[k + 1] - b->seg_first[k];
-            fa_ds_stream *t = &g->st[s];
-            const size_t seg_bytes_at = hdr_at;
-            for (int f = b->seg_first[k]; f < b->seg_first[k + 1]; f++) hdr_at += (size_t)frame_sizes[b->frame0 + f];
-            if (!t->failed && g->seg_failed[k] >= 0) {
-                const int bad = g->seg_failed[k];
-                ds_fail_stream(g, s, g->sx[s].frames_done + (bad - b->seg_first[k]), (int)g->recs[bad].status);
-            }
-            if (!t->failed && b->seg_number[k] < 0 && b->seg_prev[k] >= 0) {
-                /* a variable-block-size stream's later segment of the batch: numbered on from the earlier one */
-                flac_header h;
-                if (fa_parse_header(&g->si, stream + seg_bytes_at, (size_t)frame_sizes[b->frame0 + b->seg_first[k]], &h) ||
-                    (long long)h.number != t->next_number)
-                    ds_fail_stream(g, s, g->sx[s].frames_done, FHIP_VERIFY_NUMBER);
-            }
-            if (!t->failed && !t->started)       /* the device took a first frame that the CPU parser did not */
-                ds_fail_stream(g, s, g->sx[s].frames_done, FHIP_VERIFY_HEADER);
-            if (!t->failed && !t->variable) {
-                /* fixed blocks: the size rule from segment to segment (fa_ds_fixed_sizes), on the first and last header */
-                flac_header h0, h1;
-                const size_t last_bytes = (size_t)frame_sizes[b->frame0 + b->seg_first[k + 1] - 1];
-                if (fa_parse_header(&g->si, stream + seg_bytes_at, (size_t)frame_sizes[b->frame0 + b->seg_first[k]], &h0) ||
-                    fa_parse_header(&g->si, stream + hdr_at - last_bytes, last_bytes, &h1) ||
-                    fa_ds_fixed_sizes(t, nf, h0.n, h1.n))
-                    ds_fail_stream(g, s, g->sx[s].frames_done, FHIP_VERIFY_NUMBER);
-            }
-            if (t->failed) {
-                run_samples[r] = -1;
-                continue;
-            }
-            g->seg_ok[k] = 1;
-            const size_t at = base + (size_t)g->seg_start[k], n = (size_t)g->seg_samples[k];
-            if (b->seg_frame0[k] == 0) g->run_off[r] = (long long)at;
-            if (g->flags & FLAKE_AMD_SET_MD5_HOST) {
-                if (sample_bytes == 2) fa_md5_pcm16(&g->sx[s].md5, (const int16_t *)pcm + at * nch, n * nch, bps);
-                else fa_md5_pcm(&g->sx[s].md5, (const int32_t *)pcm + at * nch, n * nch, bps);
-            }
-            t->next_number += t->variable ? (long long)n : (long long)nf;
-            g->sx[s].frames_done += nf;
-            run_samples[r] += (long long)n;
-            if (at + n - base > extent) extent = at + n - base;
-        }
+        const size_t extent = ds_judge_batch(g, stream, frame_sizes, pcm, sample_bytes, base, run_samples);
         if (keep_fn) {
             if (keep_fn(keep_user, b->nsegs, b->seg_stream, g->seg_start, g->seg_samples, g->seg_ok) < 0) {
                 if (!g->err[0]) snprintf(g->err, sizeof g->err, "the batch's consumer failed");
@@ -304,7 +344,6 @@ static long long ds_frames(FlakeAmdDecodeSet *g, int nruns, const int *stream_of
     }
     for (int r = 0; r < nruns; r++)
         if (run_samples[r] > 0) total += run_samples[r];              /* (a stream's runs before its failing one stand) */
-    (void)total_frames;
     return total;
 }
 
@@ -384,8 +423,9 @@ FLAKE_AMD_API long long flake_amd_decode_set_device_batches(const FlakeAmdDecode
 /* ---- windows ------------------------------------------------------------------------------------------------------
  * Stateless, as flake_amd_decode_set_index is: the set lends its handle and its format.  decode_window_plan.h selects
  * the frames and cuts the batches; each batch's selected bytes are staged back to back and go through
- * fhip_decode_frames_windows, which delivers the batch's clips back to back where the call's output has got to.  A window
- * that failed keeps the room it asked for: what the batch left behind it is moved up by the difference.
+ * fhip_decode_frames_windows, which delivers the batch's clips back to back where the call's output has got to.
+ * decode_window_place.h says where each clip belongs -- a window that failed keeps the room it asked for -- and what the
+ * batch left behind such a window is moved up by the difference.
  *
  * The rows sink (flake_amd_decode_set_windows_rows) is the same loop with another destination: window w is row w of a
  * device buffer, each batch goes through fhip_decode_frames_windows_rows with the segment's window as its row and what
@@ -398,6 +438,23 @@ typedef struct {
     long long row_len;
 } ds_rows_sink;
 
+typedef struct {                  /* a call's arguments */
+    int nwin;
+    const int *frames_of_win;
+    const unsigned char *stream;
+    size_t bytes;
+    const int *frame_sizes;
+    const unsigned *fixed_block_size;
+    const unsigned long long *first_sample;
+    const long long *count;
+    void *pcm;
+    int sample_bytes;
+    size_t pcm_cap_samples;
+    const ds_rows_sink *rows;     /* (then pcm is null, sample_bytes 4, and the room is what the windows ask for) */
+    long long *win_samples;
+    int *win_status;
+} ds_win_call;
+
 static int ds_grow(void **p, size_t *cap, size_t want, size_t elem)
 {
     if (want <= *cap) return 0;
@@ -408,15 +465,18 @@ static int ds_grow(void **p, size_t *cap, size_t want, size_t elem)
     return 0;
 }
 
-static long long ds_windows(FlakeAmdDecodeSet *g, int nwin, const int *frames_of_win,
-        const unsigned char *stream, size_t bytes, const int *frame_sizes,
-        const unsigned *fixed_block_size, const unsigned long long *first_sample, const long long *count,
-        void *pcm, int sample_bytes, size_t pcm_cap_samples, const ds_rows_sink *rows,
-        long long *win_samples, int *win_status, long long *frames_decoded)
+static long long ds_nomem(FlakeAmdDecodeSet *g)
 {
-    if (!g) return -1;
-    g->err[0] = 0;
-    if (rows) {                                       /* (pcm is null, sample_bytes 4; the room is what the windows ask for) */
+    snprintf(g->err, sizeof g->err, "out of memory");
+    return -1;
+}
+
+/* What a windows call refuses of its arguments.  Leaves the call's frames in *nf and the samples it asks for in *asked. */
+static int ds_windows_check(FlakeAmdDecodeSet *g, const ds_win_call *q, long long *nf, long long *asked)
+{
+    const ds_rows_sink *rows = q->rows;
+    const int nwin = q->nwin;
+    if (rows) {
         if (rows->row_len < 1 || (!rows->dev_rows && nwin > 0) ||
             (rows->format != FHIP_ROWS_I32 && rows->format != FHIP_ROWS_I16 && rows->format != FHIP_ROWS_F32)) {
             snprintf(g->err, sizeof g->err, "bad argument");
@@ -427,82 +487,125 @@ static long long ds_windows(FlakeAmdDecodeSet *g, int nwin, const int *frames_of
             return -1;
         }
     }
-    if (nwin < 0 || (nwin > 0 && (!frames_of_win || !fixed_block_size || !first_sample || !count || !win_samples || !win_status)) ||
-        (!stream && bytes) || (!pcm && pcm_cap_samples) || (sample_bytes != 2 && sample_bytes != 4)) {
-        snprintf(g->err, sizeof g->err, "bad argument");
+    if (ds_refuse_samples(g, nwin < 0 || (nwin > 0 && (!q->frames_of_win || !q->fixed_block_size || !q->first_sample ||
+                                                       !q->count || !q->win_samples || !q->win_status)) ||
+                             (!q->stream && q->bytes) || (!q->pcm && q->pcm_cap_samples), q->sample_bytes))
         return -1;
-    }
-    if (sample_bytes == 2 && g->si.bits_per_sample > 16) {
-        snprintf(g->err, sizeof g->err, "2-byte samples need bits_per_sample <= 16");
-        return -1;
-    }
-    long long nf = 0, asked = 0;
-    const long long room = rows ? 0x7FFFFFFFFFFFFFFFll : (long long)pcm_cap_samples;
+    const long long room = rows ? 0x7FFFFFFFFFFFFFFFll : (long long)q->pcm_cap_samples;
+    *nf = *asked = 0;
     for (int w = 0; w < nwin; w++) {
-        if (frames_of_win[w] < 0 || count[w] < 0 || count[w] > room - asked) {
-            snprintf(g->err, sizeof g->err, "%s", frames_of_win[w] < 0 || count[w] < 0 ? "negative count"
+        if (q->frames_of_win[w] < 0 || q->count[w] < 0 || q->count[w] > room - *asked) {
+            snprintf(g->err, sizeof g->err, "%s", q->frames_of_win[w] < 0 || q->count[w] < 0 ? "negative count"
                                                   : "pcm_cap_samples is below the samples the windows ask for");
             return -1;
         }
-        if (rows && count[w] > rows->row_len) {
+        if (rows && q->count[w] > rows->row_len) {
             snprintf(g->err, sizeof g->err, "a window asks for more than row_len samples");
             return -1;
         }
-        asked += count[w];
-        nf += frames_of_win[w];
+        *asked += q->count[w];
+        *nf += q->frames_of_win[w];
     }
-    if (rows) pcm_cap_samples = (size_t)asked;
-    if (nf && !frame_sizes) { snprintf(g->err, sizeof g->err, "bad argument"); return -1; }
-    {
-        size_t cap = g->foff_cap;
-        if (ds_grow((void **)&g->foff, &cap, (size_t)nf + 1, sizeof(size_t))) goto nomem;
-        g->foff_cap = cap;
-        size_t wc = (size_t)g->wcap, wc2 = wc, wc3 = wc, wc4 = wc, wc5 = wc;
-        if (ds_grow((void **)&g->wsel, &wc, (size_t)nwin + 1, sizeof *g->wsel) ||
-            ds_grow((void **)&g->wsizes, &wc2, (size_t)nwin + 1, sizeof *g->wsizes) ||
-            ds_grow((void **)&g->woff, &wc3, (size_t)nwin + 1, sizeof *g->woff) ||
-            ds_grow((void **)&g->wat, &wc4, (size_t)nwin + 1, sizeof *g->wat) ||
-            ds_grow((void **)&g->wdata, &wc5, (size_t)nwin + 1, sizeof *g->wdata)) {
-            g->wcap = 0;                              /* (whichever grew is at least as large as before) */
-            goto nomem;
-        }
-        g->wcap = (int)wc;
+    if (*nf && !q->frame_sizes) { snprintf(g->err, sizeof g->err, "bad argument"); return -1; }
+    return 0;
+}
+
+/* Room for nf frames' offsets and nwin windows' tables: the latter grow together, in one block, or not at all. */
+static int ds_windows_room(FlakeAmdDecodeSet *g, int nwin, long long nf)
+{
+    if (ds_grow((void **)&g->foff, &g->foff_cap, (size_t)nf + 1, sizeof(size_t))) return -1;
+    if (nwin < g->wcap) return 0;
+    void *n = malloc(ds_carve_windows(g, NULL, (size_t)nwin + 1));
+    if (!n) {
+        ds_carve_windows(g, (unsigned char *)g->wtables, (size_t)g->wcap);      /* (as they were) */
+        return -1;
     }
+    free(g->wtables);
+    g->wtables = n;
+    g->wcap = nwin + 1;
+    ds_carve_windows(g, (unsigned char *)n, (size_t)g->wcap);
+    return 0;
+}
+
+/* The frames' offsets, the handle's sample format and every window's selection. */
+static int ds_windows_select(FlakeAmdDecodeSet *g, const ds_win_call *q, long long nf, const flac_format *fmt)
+{
     size_t at = 0;
     g->foff[0] = 0;
     for (long long f = 0; f < nf; f++) {
-        if (frame_sizes[f] < 1 || (size_t)frame_sizes[f] > bytes - at) {
+        if (q->frame_sizes[f] < 1 || (size_t)q->frame_sizes[f] > q->bytes - at) {
             snprintf(g->err, sizeof g->err, "the frame sizes run past the stream");
             return -1;
         }
-        at += (size_t)frame_sizes[f];
+        at += (size_t)q->frame_sizes[f];
         g->foff[f + 1] = at;
     }
-    if (fhip_set_pcm_format(g->hip, sample_bytes == 2 ? FHIP_PCM_S16 : FHIP_PCM_S32) != FHIP_OK) {
+    if (fhip_set_pcm_format(g->hip, q->sample_bytes == 2 ? FHIP_PCM_S16 : FHIP_PCM_S32) != FHIP_OK) {
         snprintf(g->err, sizeof g->err, "%s", fhip_last_error(g->hip));
         return -1;
     }
-    /* the selection */
+    long long f = 0;
+    for (int w = 0; w < q->nwin; w++) {
+        g->wdata[w] = q->stream;                      /* (the offsets count from the call's first byte) */
+        g->wsizes[w] = q->frame_sizes + f;
+        g->woff[w] = g->foff + f;
+        fa_dw_select(fmt, q->stream, g->wsizes[w], g->woff[w], q->frames_of_win[w], q->fixed_block_size[w],
+                     q->first_sample[w], q->count[w], &g->wsel[w]);
+        f += q->frames_of_win[w];
+    }
+    return 0;
+}
+
+/* The batch's bytes, back to back, and its frame sizes.  Returns the bytes; -1: out of memory. */
+static long long ds_windows_stage(FlakeAmdDecodeSet *g, const unsigned char *stream)
+{
+    const fa_dw_batch *b = &g->wb;
+    if (ds_grow((void **)&g->wstage, &g->wstage_cap, b->nbytes, 1)) return -1;
+    size_t sb = 0;
+    for (int k = 0; k < b->nsegs; k++) {
+        const int w = b->seg_win[k], f0 = b->seg_frame0[k], n = b->seg_first[k + 1] - b->seg_first[k];
+        const size_t len = g->woff[w][f0 + n] - g->woff[w][f0];
+        memcpy(g->wstage + sb, stream + g->woff[w][f0], len);
+        memcpy(g->wfb + b->seg_first[k], g->wsizes[w] + f0, (size_t)n * sizeof(int32_t));
+        sb += len;
+    }
+    return (long long)sb;
+}
+
+/* A failed window's row may hold what its earlier segments delivered: zero again, run by run, then wait. */
+static int ds_rows_rezero(FlakeAmdDecodeSet *g, const fhip_rows_out *ro, int nwin, const int *win_status)
+{
+    int rc = FHIP_OK;
+    for (int w = 0; w < nwin && rc == FHIP_OK;) {
+        int e = w;
+        while (e < nwin && win_status[e]) e++;
+        if (e > w) rc = fhip_rows_zero_dev(g->hip, ro, w, e - w);
+        w = e + 1;
+    }
+    if (rc == FHIP_OK) rc = fhip_sync(g->hip);
+    if (rc != FHIP_OK) snprintf(g->err, sizeof g->err, "flake_amd_decode_set_windows_rows: %s", fhip_last_error(g->hip));
+    return rc == FHIP_OK ? 0 : -1;
+}
+
+static long long ds_windows(FlakeAmdDecodeSet *g, const ds_win_call *q, long long *frames_decoded)
+{
+    if (!g) return -1;
+    g->err[0] = 0;
+    const ds_rows_sink *rows = q->rows;
+    const int nwin = q->nwin;
+    long long nf = 0, asked = 0;
+    if (ds_windows_check(g, q, &nf, &asked)) return -1;
+    const size_t pcm_cap_samples = rows ? (size_t)asked : q->pcm_cap_samples;
+    if (ds_windows_room(g, nwin, nf)) return ds_nomem(g);
     const flac_format fmt = {(int)g->si.channels, (int)g->si.bits_per_sample, (int)g->si.sample_rate,
                              g->si.max_block_size > 65535u ? 0 : (int)g->si.max_block_size};
-    {
-        long long f = 0;
-        for (int w = 0; w < nwin; w++) {
-            g->wdata[w] = stream;                     /* (the offsets count from the call's first byte) */
-            g->wsizes[w] = frame_sizes + f;
-            g->woff[w] = g->foff + f;
-            fa_dw_select(&fmt, stream, g->wsizes[w], g->woff[w], frames_of_win[w], fixed_block_size[w], first_sample[w],
-                         count[w], &g->wsel[w]);
-            win_samples[w] = 0;
-            win_status[w] = 0;
-            g->wat[w] = -1;                           /* where the window's samples begin: not known yet */
-            f += frames_of_win[w];
-        }
-    }
-    const size_t nch = g->si.channels, unit = nch * (size_t)sample_bytes;
+    if (ds_windows_select(g, q, nf, &fmt)) return -1;
+    const size_t unit = g->si.channels * (size_t)q->sample_bytes;
     fa_dw_cursor cur;
     memset(&cur, 0, sizeof cur);
     fa_dw_batch *b = &g->wb;
+    fa_wp_state place;
+    fa_wp_begin(&place, nwin, g->wsel, q->count, g->wat, q->win_samples, q->win_status);
     /* from here on the rows sink writes: everything is zero before the first batch delivers */
     fhip_rows_out ro = {rows ? rows->dev_rows : NULL, nwin, rows ? rows->format : 0, rows ? rows->row_len : 0};
     if (rows && nwin > 0 && fhip_rows_zero_dev(g->hip, &ro, 0, nwin) != FHIP_OK) {
@@ -510,46 +613,19 @@ static long long ds_windows(FlakeAmdDecodeSet *g, int nwin, const int *frames_of
         return -1;
     }
     long long decoded = 0;
-    long long out_at = 0;                             /* where the next delivered sample goes */
-    int settled = 0;                                  /* windows before this one have their place and count */
     while (fa_dw_plan(&cur, nwin, g->wsel, &fmt, (const unsigned char *const *)g->wdata, (const int *const *)g->wsizes,
-                      (const size_t *const *)g->woff,
-                      g->max_batch, b) > 0) {
-        /* the batch's bytes, back to back */
-        {
-            size_t cap = g->wstage_cap;
-            if (ds_grow((void **)&g->wstage, &cap, b->nbytes, 1)) goto nomem;
-            g->wstage_cap = cap;
-        }
-        size_t sb = 0;
-        for (int k = 0; k < b->nsegs; k++) {
-            const int w = b->seg_win[k], f0 = b->seg_frame0[k], n = b->seg_first[k + 1] - b->seg_first[k];
-            const size_t len = g->woff[w][f0 + n] - g->woff[w][f0];
-            memcpy(g->wstage + sb, stream + g->woff[w][f0], len);
-            memcpy(g->wfb + b->seg_first[k], g->wsizes[w] + f0, (size_t)n * sizeof(int32_t));
-            sb += len;
-        }
-        /* windows that deliver nothing, or failed in the planner, before the batch's first one take their room now */
-        for (; settled < b->seg_win[0]; settled++) {
-            const fa_dw_sel *s = &g->wsel[settled];
-            if (g->wat[settled] < 0) g->wat[settled] = out_at;
-            if (s->status == FA_DW_FAILED_HEADER && !win_status[settled]) win_status[settled] = FHIP_VERIFY_HEADER;
-            if (win_status[settled]) out_at = g->wat[settled] + count[settled];
-        }
+                      (const size_t *const *)g->woff, g->max_batch, b) > 0) {
+        const long long sb = ds_windows_stage(g, q->stream);
+        if (sb < 0) return ds_nomem(g);
+        /* the device writes the batch's clips from base on; with rows, a window continues where its earlier segments got to */
+        const long long base = fa_wp_batch(&place, b->nsegs, b->seg_win, rows ? g->wrow : NULL, rows ? g->wcol : NULL);
         int64_t summary[4] = {0, 0, -1, 0}, nsmp = 0;
         fhip_decode_in in = {g->wstage, (int64_t)sb, g->wfb, b->nframes, 0, -1};
         fhip_decode_segments sg = {b->seg_first, b->nsegs, b->seg_number, b->seg_variable, g->seg_start, g->seg_samples,
                                    g->seg_failed};
         fhip_decode_windows wn = {b->seg_skip, b->seg_take};
-        const long long base = out_at;
-        fhip_decode_out out = {rows ? NULL : (int32_t *)((char *)pcm + (size_t)base * unit), (int64_t)pcm_cap_samples - base,
+        fhip_decode_out out = {rows ? NULL : (int32_t *)((char *)q->pcm + (size_t)base * unit), (int64_t)pcm_cap_samples - base,
                                g->recs, summary, &nsmp};
-        if (rows)                                     /* a window continues where its earlier segments got to */
-            for (int k = 0; k < b->nsegs; k++) {
-                const int w = b->seg_win[k];
-                g->wrow[k] = win_status[w] ? -1 : w;
-                g->wcol[k] = win_samples[w];
-            }
         const int rc = rows ? fhip_decode_frames_windows_rows(g->hip, &in, &sg, &wn, g->wrow, g->wcol, &ro, &out)
                             : fhip_decode_frames_windows(g->hip, &in, &sg, &wn, &out);
         g->device_batches++;
@@ -558,64 +634,19 @@ static long long ds_windows(FlakeAmdDecodeSet *g, int nwin, const int *frames_of
             snprintf(g->err, sizeof g->err, "fhip_decode_frames_windows: %s", fhip_last_error(g->hip));
             return -1;
         }
-        /* where each segment's samples belong; a failed window's are dropped and its room is what it asked for */
-        for (int k = 0; k < b->nsegs; k++) {
-            const int w = b->seg_win[k];
-            for (; settled < w; settled++) {          /* windows between two segments: nothing to decode */
-                const fa_dw_sel *s = &g->wsel[settled];
-                if (g->wat[settled] < 0) g->wat[settled] = out_at;
-                if (s->status == FA_DW_FAILED_HEADER && !win_status[settled]) win_status[settled] = FHIP_VERIFY_HEADER;
-                if (win_status[settled]) out_at = g->wat[settled] + count[settled];
-            }
-            if (g->wat[w] < 0) g->wat[w] = out_at;
-            if (!win_status[w] && g->seg_failed[k] >= 0) win_status[w] = (int)g->recs[g->seg_failed[k]].status;
-            if (!win_status[w] && g->wsel[w].status == FA_DW_FAILED_HEADER) win_status[w] = FHIP_VERIFY_HEADER;
-            b->seg_take[k] = out_at;                  /* (the table has been uploaded: it now holds the segment's target) */
-            if (!win_status[w]) {
-                win_samples[w] += g->seg_samples[k];
-                out_at += g->seg_samples[k];
-            } else {
-                g->seg_samples[k] = 0;
-            }
-            if (b->seg_last[k]) {
-                if (win_status[w]) out_at = g->wat[w] + count[w];
-                settled = w + 1;
-            }
-        }
+        for (int k = 0; k < b->nsegs; k++) g->wstat[k] = g->seg_failed[k] >= 0 ? (int32_t)g->recs[g->seg_failed[k]].status : 0;
+        fa_wp_answers(&place, b->nsegs, b->seg_win, b->seg_last, g->seg_samples, g->seg_failed, g->wstat, g->wtarget);
         for (int k = b->nsegs - 1; k >= 0 && !rows; k--) {    /* targets never lie before the sources: from the back */
-            const long long src = base + g->seg_start[k], dst = b->seg_take[k];
-            if (g->seg_samples[k] > 0 && dst != src)
-                memmove((char *)pcm + (size_t)dst * unit, (char *)pcm + (size_t)src * unit, (size_t)g->seg_samples[k] * unit);
+            const long long src = base + g->seg_start[k], dst = g->wtarget[k];
+            if (dst >= 0 && g->seg_samples[k] > 0 && dst != src)
+                memmove((char *)q->pcm + (size_t)dst * unit, (char *)q->pcm + (size_t)src * unit,
+                        (size_t)g->seg_samples[k] * unit);
         }
     }
-    for (; settled < nwin; settled++)
-        if (g->wsel[settled].status == FA_DW_FAILED_HEADER && !win_status[settled]) win_status[settled] = FHIP_VERIFY_HEADER;
-    long long total = 0;
-    for (int w = 0; w < nwin; w++) {
-        if (g->wsel[w].status == FA_DW_FAILED_HEADER && !win_status[w]) win_status[w] = FHIP_VERIFY_HEADER;
-        if (win_status[w]) win_samples[w] = -1;
-        else total += win_samples[w];
-    }
-    if (rows && nwin > 0) {
-        /* a failed window's row may hold what its earlier segments delivered: zero again, run by run, then wait */
-        int rc = FHIP_OK;
-        for (int w = 0; w < nwin && rc == FHIP_OK;) {
-            int e = w;
-            while (e < nwin && win_status[e]) e++;
-            if (e > w) rc = fhip_rows_zero_dev(g->hip, &ro, w, e - w);
-            w = e + 1;
-        }
-        if (rc == FHIP_OK) rc = fhip_sync(g->hip);
-        if (rc != FHIP_OK) {
-            snprintf(g->err, sizeof g->err, "flake_amd_decode_set_windows_rows: %s", fhip_last_error(g->hip));
-            return -1;
-        }
-    }
+    const long long total = fa_wp_end(&place);
+    if (rows && nwin > 0 && ds_rows_rezero(g, &ro, nwin, q->win_status)) return -1;
     if (frames_decoded) *frames_decoded = decoded;
     return total;
-nomem:
-    snprintf(g->err, sizeof g->err, "out of memory");
-    return -1;
 }
 
 FLAKE_AMD_API long long flake_amd_decode_set_windows(FlakeAmdDecodeSet *g, int nwin, const int *frames_of_win,
@@ -624,8 +655,9 @@ FLAKE_AMD_API long long flake_amd_decode_set_windows(FlakeAmdDecodeSet *g, int n
         void *pcm, int sample_bytes, size_t pcm_cap_samples,
         long long *win_samples, int *win_status, long long *frames_decoded)
 {
-    return ds_windows(g, nwin, frames_of_win, stream, bytes, frame_sizes, fixed_block_size, first_sample, count, pcm,
-                      sample_bytes, pcm_cap_samples, NULL, win_samples, win_status, frames_decoded);
+    const ds_win_call q = {nwin, frames_of_win, stream, bytes, frame_sizes, fixed_block_size, first_sample, count, pcm,
+                           sample_bytes, pcm_cap_samples, NULL, win_samples, win_status};
+    return ds_windows(g, &q, frames_decoded);
 }
 
 FLAKE_AMD_API long long flake_amd_decode_set_windows_rows(FlakeAmdDecodeSet *g, int nwin, const int *frames_of_win,
@@ -635,8 +667,9 @@ FLAKE_AMD_API long long flake_amd_decode_set_windows_rows(FlakeAmdDecodeSet *g, 
         long long *win_samples, int *win_status, long long *frames_decoded)
 {
     const ds_rows_sink sink = {dev_rows, row_format, row_len};
-    return ds_windows(g, nwin, frames_of_win, stream, bytes, frame_sizes, fixed_block_size, first_sample, count, NULL, 4, 0,
-                      &sink, win_samples, win_status, frames_decoded);
+    const ds_win_call q = {nwin, frames_of_win, stream, bytes, frame_sizes, fixed_block_size, first_sample, count, NULL, 4, 0,
+                           &sink, win_samples, win_status};
+    return ds_windows(g, &q, frames_decoded);
 }
 
 FLAKE_AMD_API int flake_amd_decode_set_index(FlakeAmdDecodeSet *g, unsigned max_block_size, const unsigned char *stream,
@@ -661,14 +694,6 @@ FLAKE_AMD_API void flake_amd_decode_set_close(FlakeAmdDecodeSet *g)
     if (!g) return;
     if (g->hip) { (void)fhip_sync(g->hip); fhip_destroy(g->hip); }
     if (g->states) fhip_device_free(g->states);
-    fa_ds_batch *b = &g->b;
-    free(b->seg_first); free(b->seg_number); free(b->seg_variable); free(b->seg_stream); free(b->seg_run);
-    free(b->seg_frame0); free(b->seg_prev); free(b->md5_first); free(b->md5_range); free(b->last_seg); free(b->planned);
-    free(g->seg_start); free(g->seg_samples); free(g->seg_failed); free(g->recs); free(g->seg_ok); free(g->run_off);
-    free(g->st); free(g->sx); free(g->digests);
-    free(g->wb.seg_first); free(g->wb.seg_number); free(g->wb.seg_variable); free(g->wb.seg_skip); free(g->wb.seg_take);
-    free(g->wb.seg_win); free(g->wb.seg_frame0); free(g->wb.seg_last); free(g->wfb);
-    free(g->wrow); free(g->wcol);
-    free(g->wsel); free((void *)g->wdata); free((void *)g->wsizes); free((void *)g->woff); free(g->wat); free(g->foff); free(g->wstage);
+    free(g->tables); free(g->wtables); free(g->run_off); free(g->foff); free(g->wstage);
     free(g);
 }
