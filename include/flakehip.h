@@ -125,7 +125,14 @@ FHIP_API int fhip_create(fhip_ctx **out, int device, const fhip_params *p, int m
 FHIP_API void fhip_destroy(fhip_ctx *ctx);                       /* flake_encode_close, encode.c:1010 */
 
 /* Run on a caller-owned hipStream_t (e.g. torch's current stream); NULL
- * returns to the handle's own stream. */
+ * returns to the handle's own stream.
+ * The contract (tests/test_gpu_stream_order.py): every *_dev entry is ordered on the current stream on both
+ * sides -- it sees what the caller queued there before the call, and what the caller queues there afterwards
+ * sees its results -- with no host synchronisation needed around it.  Its inputs may be rewritten by later work
+ * on that stream.  Whatever the entry runs on streams of the handle's own is joined into the current stream
+ * before the entry returns.  Switching streams only swaps a pointer: it does NOT order the new stream after the
+ * old one; the caller does that (an event, or torch's S2.wait_stream(S1)) before the first call on the new stream.
+ * fhip_prepare_ahead is the one exception and says so below. */
 FHIP_API int fhip_set_stream(fhip_ctx *ctx, void *hip_stream);
 FHIP_API int fhip_sync(fhip_ctx *ctx);
 
