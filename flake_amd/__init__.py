@@ -181,6 +181,12 @@ class IndexOut(C.Structure):
                 ("range_variable", C.c_void_p)]
 
 
+# numpy view of fhip_frame_head (16 bytes): what a frame's header says.  flags: bit 0 ok, bit 1 variable block size,
+# bits 8..15 the header's length
+FRAME_HEAD_DTYPE = np.dtype([("number", "<u8"), ("n", "<i4"), ("flags", "<i4")])
+assert FRAME_HEAD_DTYPE.itemsize == 16
+
+
 class DecodeMd5(C.Structure):
     """``fhip_decode_md5``"""
     _fields_ = [("states", C.c_void_p), ("nstreams", C.c_int32), ("seg_stream", C.c_void_p)]
@@ -303,6 +309,14 @@ def load_library() -> C.CDLL:
         "fhip_decode_frames_windows_rows": (i, [vp, C.POINTER(DecodeIn), C.POINTER(DecodeSegments),
                                                 C.POINTER(DecodeWindows), vp, vp, C.POINTER(RowsOut),
                                                 C.POINTER(DecodeOut)]),
+        "fhip_frame_heads_dev": (i, [vp, vp, i64, vp, vp, C.c_int32, C.c_int32, vp]),
+        "fhip_gather_frames_dev": (i, [vp, vp, i64, vp, vp, i64, vp, vp, C.c_int32]),
+        "fhip_decode_frames_windows_held": (i, [vp, vp, i64, vp, vp, C.c_int32, C.POINTER(DecodeSegments),
+                                                C.POINTER(DecodeWindows), C.POINTER(DecodeOut)]),
+        "fhip_decode_frames_windows_rows_held": (i, [vp, vp, i64, vp, vp, C.c_int32, C.POINTER(DecodeSegments),
+                                                     C.POINTER(DecodeWindows), vp, vp, C.POINTER(RowsOut),
+                                                     C.POINTER(DecodeOut)]),
+        "fhip_hold_frames": (i, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -340,6 +354,11 @@ ABI_SYMBOLS = (
     "fhip_decode_frames_windows_dev", "fhip_decode_frames_windows",
     "fhip_rows_from_segments_dev", "fhip_rows_zero_dev", "fhip_decode_frames_windows_rows",
 )
+# ... and what include/flakehip_held.h, which it includes, declares: the held-streams entries (K11)
+HELD_ABI_SYMBOLS = (
+    "fhip_frame_heads_dev", "fhip_gather_frames_dev", "fhip_decode_frames_windows_held",
+    "fhip_decode_frames_windows_rows_held", "fhip_hold_frames",
+)
 
 # fhip_gather_piece (24 bytes): K9's unit, in samples per channel
 GATHER_PIECE_DTYPE = np.dtype([("src_buf", "<i4"), ("count", "<i4"), ("src", "<i8"), ("dst", "<i8")])
@@ -357,6 +376,8 @@ def gather_pieces(rows) -> np.ndarray:
 def _ptr(a) -> int | None:
     if a is None:
         return None
+    if isinstance(a, int):          # a raw address
+        return a
     if isinstance(a, np.ndarray):
         if not a.flags["C_CONTIGUOUS"]:
             raise ValueError("arrays handed to the C ABI must be C-contiguous")
@@ -780,6 +801,85 @@ class Encoder:
         return (rc, None, int(nsm[0]), recs, summary, s_start[:ns], s_samples[:ns], s_failed[:ns],
                 self.lib.fhip_last_error(self._h).decode() if rc else "")
 
+    # -- K11: held streams -------------------------------------------------
+    def frame_heads_dev(self, stream, stream_bytes: int, frame_off, frame_bytes, nframes: int, max_block_size: int,
+                        heads) -> int:
+        """fhip_frame_heads_dev (k_frame_heads): everything is device memory (torch tensors or raw addresses) --
+        frame_off int64, frame_bytes int32, heads nframes records of FRAME_HEAD_DTYPE.  Async.  Returns the code:
+        E_INVALID means nothing was queued."""
+        return int(self.lib.fhip_frame_heads_dev(self._h, _ptr(stream), int(stream_bytes), _ptr(frame_off),
+                                                 _ptr(frame_bytes), int(nframes), int(max_block_size), _ptr(heads)))
+
+    def gather_frames_dev(self, dst, dst_cap: int, dst_frame_bytes, src, src_bytes: int, frame_src, frame_len,
+                          nframes: int) -> int:
+        """fhip_gather_frames_dev (k_gather_offsets, k_gather_frames): everything is device memory (torch tensors or raw
+        addresses) -- frame_src int64, frame_len and dst_frame_bytes int32.  Async.  Returns the code."""
+        return int(self.lib.fhip_gather_frames_dev(self._h, _ptr(dst), int(dst_cap), _ptr(dst_frame_bytes), _ptr(src),
+                                                   int(src_bytes), _ptr(frame_src), _ptr(frame_len), int(nframes)))
+
+    def _held_call(self, rows, src_dev, src_bytes, frame_src, frame_len, pcm_cap, seg_first, seg_skip, seg_take, seg_number,
+                   seg_variable, out, null_table):
+        fs = np.ascontiguousarray(frame_src, dtype=np.int64)
+        fl = np.ascontiguousarray(frame_len, dtype=np.int32)
+        if len(fs) != len(fl):
+            raise ValueError("frame_src and frame_len hold one value per frame")
+        sf = np.ascontiguousarray(seg_first, dtype=np.int32)
+        ns = len(sf) - 1
+        k = max(ns, 1)
+        num = np.full(k, -1, np.int64) if seg_number is None else np.ascontiguousarray(seg_number, dtype=np.int64)
+        var = np.zeros(k, np.int32) if seg_variable is None else np.ascontiguousarray(seg_variable, dtype=np.int32)
+        skip = np.ascontiguousarray(seg_skip, dtype=np.int64)
+        take = np.ascontiguousarray(seg_take, dtype=np.int64)
+        if len(skip) != ns or len(take) != ns:
+            raise ValueError("seg_skip and seg_take hold one value per segment")
+        s_start, s_samples = np.full(k, -7, np.int64), np.full(k, -7, np.int64)
+        s_failed = np.full(k, -7, np.int32)
+        recs = np.zeros(len(fl), dtype=VERIFY_REC_DTYPE)
+        summary = np.zeros(4, dtype=np.int64)
+        nsm = np.zeros(1, dtype=np.int64)
+        do = DecodeOut(_ptr(out) if out is not None and out.size else None, pcm_cap, recs.ctypes.data if len(fl) else None,
+                       summary.ctypes.data, nsm.ctypes.data)
+        sg = DecodeSegments(sf.ctypes.data, ns, num.ctypes.data, var.ctypes.data, s_start.ctypes.data,
+                            s_samples.ctypes.data, s_failed.ctypes.data)
+        wn = DecodeWindows(skip.ctypes.data, take.ctypes.data)
+        head = (self._h, None if null_table == "src" else _ptr(src_dev), int(src_bytes),
+                None if null_table == "frame_src" else (fs.ctypes.data if len(fs) else None),
+                None if null_table == "frame_len" else (fl.ctypes.data if len(fl) else None), len(fl),
+                None if null_table == "segs" else C.byref(sg), None if null_table == "win" else C.byref(wn))
+        if rows is None:
+            rc = self.lib.fhip_decode_frames_windows_held(*head, C.byref(do))
+        else:
+            srow, scol, ro = rows
+            if len(srow) != ns or len(scol) != ns:
+                raise ValueError("seg_row and seg_col hold one value per segment")
+            rc = self.lib.fhip_decode_frames_windows_rows_held(*head, srow.ctypes.data, scol.ctypes.data, C.byref(ro),
+                                                               C.byref(do))
+        return (rc, out, int(nsm[0]), recs, summary, s_start[:ns], s_samples[:ns], s_failed[:ns],
+                self.lib.fhip_last_error(self._h).decode() if rc else "")
+
+    def decode_frames_windows_held(self, src_dev, src_bytes: int, frame_src, frame_len, pcm_cap: int, seg_first, seg_skip,
+                                   seg_take, seg_number=None, seg_variable=None, out=None, null_table=None):
+        """fhip_decode_frames_windows_held: decode_frames_windows with the stream taken from device memory -- frame f is
+        the frame_len[f] bytes at src_dev + frame_src[f] (src_dev a torch tensor or raw address of src_bytes bytes;
+        frame_src int64 and frame_len int32 host tables).  null_table ("src" / "frame_src" / "frame_len" / "segs" /
+        "win"): pass a null pointer there (the refusals).  Returns decode_frames_windows' tuple."""
+        if out is None:
+            out = np.zeros((pcm_cap, self.params.channels), dtype=self.pcm_dtype)
+        if out.dtype != self.pcm_dtype or out.size < pcm_cap * self.params.channels:
+            raise ValueError("out must hold pcm_cap * channels values of the handle's PCM dtype")
+        return self._held_call(None, src_dev, src_bytes, frame_src, frame_len, pcm_cap, seg_first, seg_skip, seg_take,
+                               seg_number, seg_variable, out, null_table)
+
+    def decode_frames_windows_rows_held(self, src_dev, src_bytes: int, frame_src, frame_len, pcm_cap: int, seg_first,
+                                        seg_skip, seg_take, seg_row, seg_col, rows, nrows: int, row_len: int, fmt: int,
+                                        seg_number=None, seg_variable=None, null_table=None):
+        """fhip_decode_frames_windows_rows_held: decode_frames_windows_rows with the stream taken from device memory, as
+        decode_frames_windows_held takes it.  Returns its tuple with None where the samples were."""
+        sink = (np.ascontiguousarray(seg_row, dtype=np.int32), np.ascontiguousarray(seg_col, dtype=np.int64),
+                RowsOut(_ptr(rows), int(nrows), int(fmt), int(row_len)))
+        return self._held_call(sink, src_dev, src_bytes, frame_src, frame_len, pcm_cap, seg_first, seg_skip, seg_take,
+                               seg_number, seg_variable, None, null_table)
+
     # -- K8: frame discovery ----------------------------------------------
     def index_ranges(self, stream, range_first, max_block_size: int = 0, frame_cap: int | None = None, sentinel=None):
         """fhip_index_frames on host data: the CPU indexer's answer for the streams stream[range_first[r] :
@@ -1110,6 +1210,24 @@ def load_host_library() -> C.CDLL:
                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong,
                                                       C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
     lib.flake_amd_decode_set_windows_rows.restype = C.c_longlong
+    lib.flake_amd_decode_set_hold.argtypes = [C.c_void_p, C.c_size_t]
+    lib.flake_amd_decode_set_hold.restype = C.c_int
+    lib.flake_amd_decode_set_hold_add.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                  C.c_void_p]
+    lib.flake_amd_decode_set_hold_add.restype = C.c_longlong
+    lib.flake_amd_decode_set_held_windows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_int, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                      C.POINTER(C.c_longlong)]
+    lib.flake_amd_decode_set_held_windows.restype = C.c_longlong
+    lib.flake_amd_decode_set_held_windows_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p,
+                                                           C.POINTER(C.c_longlong)]
+    lib.flake_amd_decode_set_held_windows_rows.restype = C.c_longlong
+    lib.flake_amd_decode_set_held_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                                   C.POINTER(C.c_longlong)]
+    lib.flake_amd_decode_set_held_info.restype = C.c_int
+    lib.flake_amd_decode_set_held_stats.argtypes = [C.c_void_p, C.c_void_p]
+    lib.flake_amd_decode_set_held_stats.restype = C.c_int
     lib.flake_amd_read_seektable.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
     lib.flake_amd_read_seektable.restype = C.c_longlong
     lib.flake_amd_seek_lookup.argtypes = [C.c_void_p, C.c_int, C.c_ulonglong]
@@ -1758,6 +1876,117 @@ class DecodeSet:
             out.append((sizes[at:at + frames[r]].copy(), int(cons[r])))
             at += int(frames[r])
         return out
+
+    # -- held streams: a corpus that stays on the device --------------------
+    def hold(self, capacity_bytes: int) -> None:
+        """flake_amd_decode_set_hold: allocate the set's store on the device, once."""
+        if self.lib.flake_amd_decode_set_hold(self._g, int(capacity_bytes)) != 0:
+            raise FlakeHipError(-1, "flake_amd_decode_set_hold", self.last_error())
+
+    def hold_add(self, streams, fixed_block_sizes=None, max_block_size: int | None = None):
+        """flake_amd_decode_set_hold_add: append files to the store and index them where they lie.  streams: the files'
+        bytes, each from its first frame header on; fixed_block_sizes: per file, STREAMINFO's block size where minimum
+        and maximum agree, else 0 (default: all 0); max_block_size: their STREAMINFO value (default: the set's).
+        Returns the files' ids, in order.  Raises FlakeHipError when the call is refused: nothing changed then."""
+        parts = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.asarray(x, dtype=np.uint8)
+                 for x in streams]
+        if not parts:
+            return []
+        st = np.ascontiguousarray(np.concatenate(parts))
+        first = np.zeros(len(parts) + 1, dtype=np.uintp)
+        first[1:] = np.cumsum([x.size for x in parts])
+        fixed = (np.zeros(len(parts), dtype=np.uint32) if fixed_block_sizes is None
+                 else np.ascontiguousarray(fixed_block_sizes, dtype=np.uint32))
+        if len(fixed) != len(parts):
+            raise ValueError("fixed_block_sizes holds one value per stream")
+        ids = np.full(len(parts), -1, dtype=np.int32)
+        n = self.lib.flake_amd_decode_set_hold_add(self._g, int(self.si.max_block_size if max_block_size is None else max_block_size),
+                                                   st.ctypes.data if st.size else None, first.ctypes.data, len(parts),
+                                                   fixed.ctypes.data, ids.ctypes.data)
+        if n < 0:
+            raise FlakeHipError(int(n), "flake_amd_decode_set_hold_add", self.last_error())
+        return [int(x) for x in ids]
+
+    def held_windows(self, windows, pcm_cap: int | None = None, sample_bytes: int = 4, out=None):
+        """flake_amd_decode_set_held_windows.  windows: [(held id, first sample, count)].  Returns what decode_windows
+        returns for the same windows asked of the streams' whole runs."""
+        nwin = len(windows)
+        ids = np.asarray([w[0] for w in windows], dtype=np.int32)
+        first = np.asarray([w[1] for w in windows], dtype=np.uint64)
+        count = np.asarray([w[2] for w in windows], dtype=np.int64)
+        if pcm_cap is None:
+            pcm_cap = int(np.maximum(count, 0).sum())
+        if out is None:
+            out = np.zeros((pcm_cap, self.si.channels), dtype=np.int16 if sample_bytes == 2 else np.int32)
+        k = max(nwin, 1)
+        ws, wst = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int32)
+        nfd = C.c_longlong(0)
+        have = nwin > 0
+        n = self.lib.flake_amd_decode_set_held_windows(self._g, nwin, ids.ctypes.data if have else None,
+                                                       first.ctypes.data if have else None,
+                                                       count.ctypes.data if have else None,
+                                                       out.ctypes.data if out.size else None, sample_bytes, pcm_cap,
+                                                       ws.ctypes.data, wst.ctypes.data, C.byref(nfd))
+        if n < 0:
+            raise FlakeHipError(int(n), "flake_amd_decode_set_held_windows", self.last_error())
+        res, begins, at = [], [], 0
+        for w in range(nwin):
+            begins.append(at)
+            if ws[w] < 0:
+                res.append(None)
+                at += int(count[w])
+            else:
+                res.append(out[at:at + ws[w]])
+                at += int(ws[w])
+        return res, wst[:nwin], int(nfd.value), begins
+
+    def held_windows_rows(self, windows, row_len: int, dtype=None, out=None):
+        """flake_amd_decode_set_held_windows_rows.  windows: [(held id, first sample, count)].  Returns what
+        decode_windows_rows returns for the same windows asked of the streams' whole runs; out as there."""
+        import torch
+        if dtype is None:
+            dtype = torch.float32 if out is None else out.dtype
+        fmt = {torch.int32: ROWS_I32, torch.int16: ROWS_I16, torch.float32: ROWS_F32}.get(dtype)
+        if fmt is None:
+            raise ValueError("dtype is torch.int32, torch.int16 or torch.float32")
+        nwin, ch, row_len = len(windows), int(self.si.channels), int(row_len)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((nwin, ch, max(row_len, 0)), dtype=dtype, device=dev)
+        elif (out.dtype != dtype or out.device != dev or not out.is_contiguous() or out.dim() != 3 or out.shape[0] < nwin
+              or tuple(out.shape[1:]) != (ch, row_len)):
+            raise ValueError("out must be a contiguous [>= nwin, channels, row_len] tensor of dtype on the set's device")
+        ids = np.asarray([w[0] for w in windows], dtype=np.int32)
+        first = np.asarray([w[1] for w in windows], dtype=np.uint64)
+        count = np.asarray([w[2] for w in windows], dtype=np.int64)
+        k = max(nwin, 1)
+        ws, wst = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int32)
+        nfd = C.c_longlong(0)
+        have = nwin > 0
+        # (as decode_windows_rows: torch's own stream finishes with this memory first)
+        torch.cuda.current_stream(dev).synchronize()
+        n = self.lib.flake_amd_decode_set_held_windows_rows(self._g, nwin, ids.ctypes.data if have else None,
+                                                            first.ctypes.data if have else None,
+                                                            count.ctypes.data if have else None,
+                                                            out.data_ptr() if have else None, fmt, row_len,
+                                                            ws.ctypes.data, wst.ctypes.data, C.byref(nfd))
+        if n < 0:
+            raise FlakeHipError(int(n), "flake_amd_decode_set_held_windows_rows", self.last_error())
+        return out[:nwin], torch.from_numpy(ws[:nwin].copy()), wst[:nwin], int(nfd.value)
+
+    def held_info(self, held_id: int):
+        """(frames, samples, bytes) of a held stream."""
+        fr, sm, by = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        if self.lib.flake_amd_decode_set_held_info(self._g, int(held_id), C.byref(fr), C.byref(sm), C.byref(by)) != 0:
+            raise IndexError(held_id)
+        return int(fr.value), int(sm.value), int(by.value)
+
+    def held_stats(self):
+        """(bytes resident, frames in the table, bytes uploaded by hold_add, bytes uploaded by held window calls)."""
+        out = np.zeros(4, dtype=np.int64)
+        if self.lib.flake_amd_decode_set_held_stats(self._g, out.ctypes.data) != 0:
+            raise FlakeHipError(-1, "flake_amd_decode_set_held_stats", self.last_error())
+        return tuple(int(x) for x in out)
 
     def md5(self, stream: int):
         """The digest of everything the stream has returned, or None (a failed stream; a set without MD5)."""

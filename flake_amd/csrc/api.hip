@@ -195,6 +195,11 @@ struct fhip_ctx {
     DevBuf<fhip_gather_piece> d_gather;
     std::vector<fhip_gather_piece> h_gather;  // ... and the host image it is uploaded from
 
+    // K11 (fhip_gather_frames_dev, fhip_decode_frames_windows*_held): each frame's place, and for the held forms the
+    // host's frame_src / frame_len tables in front of it, in one block, grow-only
+    DevBuf<long long> d_held;
+    std::vector<long long> h_held;            // ... and the host image the two tables are uploaded from
+
     std::vector<std::string> launches;        // fhip_last_launches: what the most recent call queued
 
     // ragged batches (fhip_frames_packed_*_ragged): the per-frame tables, one device block laid out as
@@ -249,14 +254,18 @@ void note_launch(const char *fmt, ...)
 
 namespace {
 
-constexpr int kNumKernels = 10 + fhip::INDEX_STEPS;
+constexpr int kNumKernels = 14 + fhip::INDEX_STEPS;
 const char *const kKernelNames[kNumKernels] = {"k_prepare", "k_autocorr", "k_lpc", "k_encode", "k_assemble",
                                                "k_order_search", "k_verify", "k_decode",
                                                // K8's launches, one name each (fhip::index_step_name without the <>)
                                                "k_index_count", "k_index_wgscan", "k_index_scatter", "k_index_walk",
-                                               "k_index_ranges", "k_index_emit", "k_gather_spans", "k_window_rows"};
+                                               "k_index_ranges", "k_index_emit", "k_gather_spans", "k_window_rows",
+                                               "k_frame_heads", "k_gather_offsets", "k_gather_frames",
+                                               "k_frame_offsets"};
 constexpr int kProfVerify = 6, kProfDecode = 7, kProfIndex = 8, kProfGather = 8 + fhip::INDEX_STEPS,
-              kProfRows = 9 + fhip::INDEX_STEPS;
+              kProfRows = 9 + fhip::INDEX_STEPS, kProfHeads = 10 + fhip::INDEX_STEPS,
+              kProfGatherOffsets = 11 + fhip::INDEX_STEPS, kProfGatherFrames = 12 + fhip::INDEX_STEPS,
+              kProfFrameOffsets = 13 + fhip::INDEX_STEPS;
 
 int fail_hip(fhip_ctx *c, hipError_t e, const char *what)
 {
@@ -2884,13 +2893,18 @@ int fhip_decode_frames(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_
 // rows (with win): K7 decodes into d_vpcm as ever, K10 re-lays the segments into rows->out behind it, reading the
 // per-segment outputs where K7 left them, and no sample is downloaded (fhip_decode_frames_windows_rows).
 namespace {
+// held (with win): in->stream is DEVICE memory that is not the batch's stream but a store of in->stream_bytes bytes
+// the batch's frames lie in, frame f at held->frame_src[f] with in->frame_bytes[f] bytes (host tables); K11 gathers them
+// into d_vstream / d_vfb, where an upload would have put them (fhip_decode_frames_windows_held, _rows_held).
 struct RowsSink { const int32_t *seg_row; const int64_t *seg_col; const fhip_rows_out *out; };
+struct HeldSource { const int64_t *frame_src; };
 struct DecodeMode {
     const fhip_decode_segments *segs = nullptr;
     const fhip_decode_md5 *md5 = nullptr;
     bool keep = false;
     const fhip_decode_windows *win = nullptr;
     const RowsSink *rows = nullptr;
+    const HeldSource *held = nullptr;
 };
 
 // The call as the device sees it: what staging leaves for the launches and the collection.
@@ -2943,10 +2957,46 @@ int decode_host_check(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_o
     long long total = 0;
     for (int f = 0; f < in->nframes; f++) {
         if (in->frame_bytes[f] < 0) return fail(c, FHIP_E_INVALID, "negative frame size");
+        if (m.held && (m.held->frame_src[f] < 0 || m.held->frame_src[f] > in->stream_bytes - in->frame_bytes[f]))
+            return fail(c, FHIP_E_INVALID, "a frame's range lies outside the store");
         total += in->frame_bytes[f];
     }
-    if (total != in->stream_bytes) return fail(c, FHIP_E_INVALID, "frame_bytes do not add up to stream_bytes");
+    if (!m.held && total != in->stream_bytes) return fail(c, FHIP_E_INVALID, "frame_bytes do not add up to stream_bytes");
     return FHIP_OK;
+}
+
+// Queue K11's gather on the handle's stream; everything is device memory, off [nframes] the handle's workspace.
+int run_gather_frames(fhip_ctx *c, uint8_t *dst, int64_t dst_cap, int32_t *dst_frame_bytes, const uint8_t *src,
+                      int64_t src_bytes, const long long *frame_src, const int32_t *frame_len, int nframes, long long *off)
+{
+    const fhip::GatherFramesArgs a{dst, dst_cap, dst_frame_bytes, src, src_bytes, frame_src, frame_len, nframes, off};
+    {
+        Prof pr(c, kProfGatherOffsets, c->profiling);
+        HIP_TRY(c, fhip::launch_gather_offsets(c->stream, a));
+    }
+    Prof pr(c, kProfGatherFrames, c->profiling);
+    HIP_TRY(c, fhip::launch_gather_frames(c->stream, a));
+    return FHIP_OK;
+}
+
+// The held form's staging: the two host tables uploaded in one copy, the frames gathered out of the store into
+// d_vstream, their sizes left in d_vfb.  sb: the lengths added up, which is what the gather accepts of frames the
+// check has held against the store.
+int decode_host_stage_held(fhip_ctx *c, const fhip_decode_in *in, const DecodeMode &m, size_t sb)
+{
+    const size_t nf = (size_t)in->nframes;
+    if (!nf) return FHIP_OK;
+    fhip::TableLayout l;
+    const auto src = l.add<int64_t>(nf);
+    const auto len = l.add<int32_t>(nf);
+    const auto off = l.add<long long>(nf);
+    const TableBlock tb(l, c->d_held, c->h_held, len.end());
+    HIP_TRY(c, tb.status());
+    tb.fill(src, m.held->frame_src);
+    tb.fill(len, in->frame_bytes);
+    HIP_TRY(c, tb.upload(c->stream));
+    return run_gather_frames(c, c->d_vstream, (int64_t)sb, c->d_vfb, in->stream, in->stream_bytes,
+                             reinterpret_cast<const long long *>(tb.dev(src)), tb.dev(len), in->nframes, tb.dev(off));
 }
 
 // The segment mode's tables: laid out, filled in the host image, uploaded in one copy, and named in st.
@@ -2996,8 +3046,13 @@ int decode_host_stage_tables(fhip_ctx *c, const DecodeMode &m, DecodeStaged &st)
 // Staging: the stream and its frame sizes uploaded, room for the samples, the segment tables.
 int decode_host_stage(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *out, const DecodeMode &m, DecodeStaged &st)
 {
-    const size_t nf = (size_t)in->nframes, sb = (size_t)in->stream_bytes;
-    const int rc = ensure_verify(c, nf);
+    const size_t nf = (size_t)in->nframes;
+    size_t sb = (size_t)in->stream_bytes;
+    if (m.held) {
+        sb = 0;
+        for (size_t f = 0; f < nf; f++) sb += (size_t)in->frame_bytes[f];
+    }
+    int rc = ensure_verify(c, nf);
     if (rc != FHIP_OK) return rc;
     // no frame holds more than block_size samples: the staging output never needs more than that, whatever pcm_cap says
     const long long most = (long long)nf * c->p.block_size;
@@ -3005,10 +3060,14 @@ int decode_host_stage(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_o
     HIP_TRY(c, c->d_vstream.reserve(sb));
     HIP_TRY(c, c->d_vfb.reserve(nf));
     if (!m.keep) HIP_TRY(c, c->d_vpcm.reserve((size_t)cap * (size_t)c->p.channels));
-    if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_vstream, in->stream, sb, hipMemcpyHostToDevice, c->stream));
-    if (nf) HIP_TRY(c, hipMemcpyAsync(c->d_vfb, in->frame_bytes, nf * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (m.held) {
+        if ((rc = decode_host_stage_held(c, in, m, sb)) != FHIP_OK) return rc;
+    } else {
+        if (sb) HIP_TRY(c, hipMemcpyAsync(c->d_vstream, in->stream, sb, hipMemcpyHostToDevice, c->stream));
+        if (nf) HIP_TRY(c, hipMemcpyAsync(c->d_vfb, in->frame_bytes, nf * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
     st.in = *in;
-    st.in.stream = c->d_vstream; st.in.frame_bytes = c->d_vfb;
+    st.in.stream = c->d_vstream; st.in.frame_bytes = c->d_vfb; st.in.stream_bytes = (int64_t)sb;
     // summary [0..4), K7's key scratch [4], the sample count [5], the end of what was written [6]
     st.out = fhip_decode_out{m.keep ? out->pcm : c->d_vpcm.get(), cap, c->d_vrec, reinterpret_cast<int64_t *>(c->d_vsum.get()),
                              reinterpret_cast<int64_t *>(c->d_vsum.get() + 5)};
@@ -3111,6 +3170,78 @@ int fhip_decode_frames_windows_rows(fhip_ctx *c, const fhip_decode_in *in, const
     if (c && (!segs || !win)) return refuse_null(c);
     const RowsSink sink{seg_row, seg_col, rows};
     return decode_segments_host(c, in, out, DecodeMode{segs, nullptr, false, win, &sink});
+}
+
+// ---- K11: held streams -----------------------------------------------------------------------------
+
+int fhip_frame_heads_dev(fhip_ctx *c, const uint8_t *stream, int64_t stream_bytes, const int64_t *frame_off,
+                         const int32_t *frame_bytes, int32_t nframes, int32_t max_block_size, fhip_frame_head *heads)
+{
+    if (!c) return FHIP_E_INVALID;
+    entry_reset(c);
+    if (nframes < 0 || stream_bytes < 0 || max_block_size < 0) return fail(c, FHIP_E_INVALID, "negative count");
+    if (!frame_off || !frame_bytes || !heads || (stream_bytes > 0 && !stream)) return fail(c, FHIP_E_INVALID, "null argument");
+    LaunchScope ls(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const fhip::FrameHeadsArgs a{stream, stream_bytes, reinterpret_cast<const long long *>(frame_off), frame_bytes, nframes,
+                                 flac_format{c->p.channels, c->p.bits_per_sample, c->p.sample_rate, max_block_size}, heads};
+    Prof pr(c, kProfHeads, c->profiling);
+    HIP_TRY(c, fhip::launch_frame_heads(c->stream, a));
+    return FHIP_OK;
+}
+
+int fhip_gather_frames_dev(fhip_ctx *c, uint8_t *dst, int64_t dst_cap, int32_t *dst_frame_bytes, const uint8_t *src,
+                           int64_t src_bytes, const int64_t *frame_src, const int32_t *frame_len, int32_t nframes)
+{
+    if (!c) return FHIP_E_INVALID;
+    entry_reset(c);
+    if (nframes < 0 || dst_cap < 0 || src_bytes < 0) return fail(c, FHIP_E_INVALID, "negative count");
+    if (nframes > c->max_frames) return fail(c, FHIP_E_INVALID, "nframes exceeds the handle's max_frames");
+    if (!dst_frame_bytes || !frame_src || !frame_len || (dst_cap > 0 && !dst) || (src_bytes > 0 && !src))
+        return fail(c, FHIP_E_INVALID, "null argument");
+    if (nframes == 0) return FHIP_OK;
+    LaunchScope ls(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, c->d_held.reserve((size_t)nframes));
+    return run_gather_frames(c, dst, dst_cap, dst_frame_bytes, src, src_bytes, reinterpret_cast<const long long *>(frame_src),
+                             frame_len, nframes, c->d_held);
+}
+
+namespace {
+// What the held forms refuse before the host forms' checks see the call, and the call as those take it: the store as
+// the stream, the lengths as the frame sizes.
+int held_check(fhip_ctx *c, const uint8_t *src_dev, int64_t src_bytes, const int64_t *frame_src, const int32_t *frame_len,
+               int32_t nframes, const fhip_decode_segments *segs, const fhip_decode_windows *win, fhip_decode_in *in)
+{
+    if (!c) return FHIP_E_INVALID;
+    if (!segs || !win || (nframes > 0 && (!src_dev || !frame_src || !frame_len))) return refuse_null(c);
+    *in = fhip_decode_in{src_dev, src_bytes, frame_len, nframes, 0, -1};
+    return FHIP_OK;
+}
+}  // namespace
+
+int fhip_decode_frames_windows_held(fhip_ctx *c, const uint8_t *src_dev, int64_t src_bytes, const int64_t *frame_src,
+                                    const int32_t *frame_len, int32_t nframes, const fhip_decode_segments *segs,
+                                    const fhip_decode_windows *win, const fhip_decode_out *out)
+{
+    fhip_decode_in in;
+    const int rc = held_check(c, src_dev, src_bytes, frame_src, frame_len, nframes, segs, win, &in);
+    if (rc != FHIP_OK) return rc;
+    const HeldSource held{frame_src};
+    return decode_segments_host(c, &in, out, DecodeMode{segs, nullptr, false, win, nullptr, &held});
+}
+
+int fhip_decode_frames_windows_rows_held(fhip_ctx *c, const uint8_t *src_dev, int64_t src_bytes, const int64_t *frame_src,
+                                         const int32_t *frame_len, int32_t nframes, const fhip_decode_segments *segs,
+                                         const fhip_decode_windows *win, const int32_t *seg_row, const int64_t *seg_col,
+                                         const fhip_rows_out *rows, const fhip_decode_out *out)
+{
+    fhip_decode_in in;
+    const int rc = held_check(c, src_dev, src_bytes, frame_src, frame_len, nframes, segs, win, &in);
+    if (rc != FHIP_OK) return rc;
+    const RowsSink sink{seg_row, seg_col, rows};
+    const HeldSource held{frame_src};
+    return decode_segments_host(c, &in, out, DecodeMode{segs, nullptr, false, win, &sink, &held});
 }
 
 // ---- K8: frame discovery ---------------------------------------------------------------------------
@@ -3234,6 +3365,88 @@ int fhip_index_frames(fhip_ctx *c, const fhip_index_in *in, const fhip_index_out
     if (total > got) {
         HIP_TRY(c, hipMemcpyAsync(out->frame_bytes + got, tb.dev(sizes) + got, (total - got) * sizeof(int32_t),
                                   hipMemcpyDeviceToHost, c->stream));
+        rc = fhip_sync(c);
+        if (rc != FHIP_OK) return rc;
+    }
+    return FHIP_OK;
+}
+
+// Bytes appended to a store on the device, indexed where they lie and every frame's header read: the upload, K8 on the
+// resident copy, k_frame_offsets and k_frame_heads behind it on the same stream, one download, one wait.
+int fhip_hold_frames(fhip_ctx *c, const fhip_hold_in *h, const fhip_hold_out *o)
+{
+    if (!c) return FHIP_E_INVALID;
+    if (!h || !o || !o->heads) { entry_reset(c); return fail(c, FHIP_E_INVALID, "null argument"); }
+    fhip_index_in in{h->bytes, h->nbytes, h->range_first, h->nranges, h->max_block_size, h->frame_cap};
+    const fhip_index_out out{o->frame_bytes, o->range_frames, o->range_consumed, o->range_variable};
+    int rc = index_check(c, &in, &out);
+    if (rc != FHIP_OK) return rc;
+    if (h->base < 0 || h->store_bytes < 0 || h->base > h->store_bytes - h->nbytes)
+        return fail(c, FHIP_E_INVALID, "the bytes do not fit the store");
+    if (!h->store && h->nbytes) return fail(c, FHIP_E_INVALID, "null store");
+    const size_t nr = (size_t)in.nranges, sb = (size_t)in.stream_bytes;
+    if (in.range_first[0] != 0) return fail(c, FHIP_E_INVALID, "range_first[0] must be 0");
+    for (size_t r = 0; r < nr; r++)
+        if (in.range_first[r + 1] < in.range_first[r]) return fail(c, FHIP_E_INVALID, "range_first must not decrease");
+    if (in.range_first[nr] != in.stream_bytes) return fail(c, FHIP_E_INVALID, "range_first must end at stream_bytes");
+    LaunchScope ls(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t tcap = index_table_cap(in.stream_bytes, in.nranges);
+    const size_t fcap = (size_t)in.frame_cap < tcap ? (size_t)in.frame_cap : tcap;
+    const size_t first = fcap < 65536 ? fcap : 65536;       // what comes back with the first wait (fhip_index_frames' rule)
+    fhip::TableLayout l;
+    const auto range_first = l.add<int64_t>(nr + 1), consumed = l.add<int64_t>(nr);
+    const auto frames = l.add<int32_t>(nr), variable = l.add<int32_t>(nr), sizes = l.add<int32_t>(fcap);
+    const auto back = sizes.head(first);
+    const auto heads = l.add<long long>(2 * fcap), offs = l.add<long long>(fcap);
+    static_assert(sizeof(fhip_frame_head) == 2 * sizeof(long long), "a head is two words of the block");
+    const TableBlock tb(l, c->d_iio, c->h_iio, back.end());
+    HIP_TRY(c, tb.status());
+    uint8_t *at = h->store + h->base;
+    if (sb) HIP_TRY(c, hipMemcpyAsync(at, h->bytes, sb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(tb.dev(range_first), in.range_first, range_first.bytes, hipMemcpyHostToDevice, c->stream));
+    fhip_index_in din = in;
+    din.stream = at; din.range_first = tb.dev(range_first);
+    din.frame_cap = (int32_t)fcap;
+    const fhip_index_out dout{tb.dev(sizes), tb.dev(frames), tb.dev(consumed), tb.dev(variable)};
+    rc = run_index(c, din, dout);
+    if (rc != FHIP_OK) return rc;
+    fhip_frame_head *d_heads = reinterpret_cast<fhip_frame_head *>(tb.dev(heads));
+    if (fcap) {
+        // an entry that no frame owns is offset -1: not a frame, its record zero
+        HIP_TRY(c, hipMemsetAsync(tb.dev(offs), 0xFF, offs.bytes, c->stream));
+        const fhip::FrameOffsetsArgs fo{reinterpret_cast<const long long *>(tb.dev(range_first)), tb.dev(frames), in.nranges,
+                                        tb.dev(sizes), (long long)fcap, h->base, tb.dev(offs)};
+        {
+            Prof pr(c, kProfFrameOffsets, c->profiling);
+            HIP_TRY(c, fhip::launch_frame_offsets(c->stream, fo));
+        }
+        const fhip::FrameHeadsArgs fh{h->store, h->base + in.stream_bytes, tb.dev(offs), tb.dev(sizes), (long long)fcap,
+                                      flac_format{c->p.channels, c->p.bits_per_sample, c->p.sample_rate, in.max_block_size},
+                                      d_heads};
+        Prof pr(c, kProfHeads, c->profiling);
+        HIP_TRY(c, fhip::launch_frame_heads(c->stream, fh));
+    }
+    HIP_TRY(c, hipMemcpyAsync(tb.host(consumed), tb.dev(consumed), back.end() - consumed.off, hipMemcpyDeviceToHost, c->stream));
+    if (first) HIP_TRY(c, hipMemcpyAsync(o->heads, d_heads, first * sizeof(fhip_frame_head), hipMemcpyDeviceToHost, c->stream));
+    rc = fhip_sync(c);
+    if (rc != FHIP_OK) return rc;
+    const int32_t *h_frames = tb.host(frames);
+    size_t total = 0;
+    for (size_t r = 0; r < nr; r++) {
+        o->range_frames[r] = h_frames[r];
+        o->range_consumed[r] = tb.host(consumed)[r];
+        o->range_variable[r] = tb.host(variable)[r];
+        if (h_frames[r] > 0) total += (size_t)h_frames[r];
+    }
+    if (total > fcap) total = fcap;
+    const size_t got = total < first ? total : first;
+    if (got) memcpy(o->frame_bytes, tb.host(sizes), got * sizeof(int32_t));
+    if (total > got) {
+        HIP_TRY(c, hipMemcpyAsync(o->frame_bytes + got, tb.dev(sizes) + got, (total - got) * sizeof(int32_t),
+                                  hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(o->heads + got, d_heads + got, (total - got) * sizeof(fhip_frame_head), hipMemcpyDeviceToHost,
+                                  c->stream));
         rc = fhip_sync(c);
         if (rc != FHIP_OK) return rc;
     }

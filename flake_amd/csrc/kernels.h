@@ -486,4 +486,38 @@ struct WindowRowsArgs {
 constexpr int ROWS_TILE = 512;
 hipError_t launch_window_rows(hipStream_t st, const WindowRowsArgs &a);
 
+// K11 (k11_held.hip): frames of a store that stays on the device.  All tables are DEVICE memory.
+// k_frame_heads: heads[f] is flac_header_ok(fmt, stream + frame_off[f], frame_bytes[f]) as a record, all zero where it
+// answers 0, where frame_bytes[f] <= 0 and where the frame's range leaves [0, stream_bytes).  One lane per frame.
+struct FrameHeadsArgs {
+    const uint8_t *stream; long long stream_bytes;
+    const long long *frame_off; const int32_t *frame_bytes; long long nframes;
+    flac_format fmt;
+    fhip_frame_head *heads;                      // [nframes]
+};
+hipError_t launch_frame_heads(hipStream_t st, const FrameHeadsArgs &a);
+// k_frame_offsets: K8's answers (frame_bytes back to back in range order, range_frames) turned into the table
+// k_frame_heads reads: frame_off[f] = base + range_first[r] + the sizes of range r's frames before f.  A wave per range;
+// nothing at or past frame_cap is read or written.
+struct FrameOffsetsArgs {
+    const long long *range_first; const int32_t *range_frames; int nranges;
+    const int32_t *frame_bytes; long long frame_cap;
+    long long base;
+    long long *frame_off;                        // [frame_cap]
+};
+hipError_t launch_frame_offsets(hipStream_t st, const FrameOffsetsArgs &a);
+// k_gather_offsets (one workgroup), then k_gather_frames (a wave per frame): frame f is accepted when frame_len[f] >= 1,
+// [frame_src[f], frame_src[f] + frame_len[f]) lies inside [0, src_bytes) and its place -- the accepted lengths before it,
+// added up -- fits dst_cap.  An accepted frame is copied to its place and dst_frame_bytes[f] is its length; any other
+// gets 0 and copies nothing.  No read outside [0, src_bytes), no write outside the frame's own range of [0, dst_cap).
+struct GatherFramesArgs {
+    uint8_t *dst; long long dst_cap;
+    int32_t *dst_frame_bytes;                    // [nframes]
+    const uint8_t *src; long long src_bytes;
+    const long long *frame_src; const int32_t *frame_len; int nframes;
+    long long *dst_off;                          // [nframes] workspace: each frame's place
+};
+hipError_t launch_gather_offsets(hipStream_t st, const GatherFramesArgs &a);
+hipError_t launch_gather_frames(hipStream_t st, const GatherFramesArgs &a);
+
 }  // namespace fhip

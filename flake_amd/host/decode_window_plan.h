@@ -11,6 +11,11 @@
  * run's first frame.  The numbers increase along a run, so the frames that overlap a window are found by bisection: the
  * planner reads the run's first header, the headers it probes, and nothing else.  It trusts no header beyond that: the
  * device decodes and checks every selected frame, its numbering held from the number the planner names.
+ *
+ * Where a header comes from is an ACCESSOR's business (fa_dw_headers: "the header of frame k of window w's run"): the one
+ * here parses it out of the run's bytes, held_plan.h's reads it out of the table the device left when the stream was
+ * taken into a held store.  fa_dw_select_by / fa_dw_plan_by are the one selection and the one batch rule over either;
+ * fa_dw_select / fa_dw_plan are those over the bytes.
  * Not installed.
  */
 #ifndef FLAKE_AMD_DECODE_WINDOW_PLAN_H
@@ -38,16 +43,35 @@ typedef struct fa_dw_sel {
     int block;                    /* fixed blocks: the size a frame number is multiplied by */
 } fa_dw_sel;
 
+/* The header of frame k of window w's run: 1 and *h where it is one of this stream, else 0. */
+typedef struct fa_dw_headers {
+    int (*get)(const void *ctx, int w, int k, flac_header *h);
+    const void *ctx;
+} fa_dw_headers;
+
+/* The accessor over the runs' bytes: run_data[w] / run_sizes[w] / run_off[w] are window w's run. */
+typedef struct fa_dw_bytes {
+    const flac_format *fmt;
+    const unsigned char *const *run_data;
+    const int *const *run_sizes;
+    const size_t *const *run_off;
+} fa_dw_bytes;
+
+static inline int fa_dw_bytes_get(const void *ctx, int w, int k, flac_header *h)
+{
+    const fa_dw_bytes *b = (const fa_dw_bytes *)ctx;
+    return flac_header_ok(b->fmt, b->run_data[w] + b->run_off[w][k], b->run_sizes[w][k], h);
+}
+
 static inline long long fa_dw_start(const flac_header *h, int block)
 {
     return h->vbs ? (long long)h->number : (long long)h->number * block;
 }
 
-/* Select the frames of a run that overlap [first_sample, first_sample + count).  sizes [nframes] and off [nframes + 1]
- * (off[k] = where frame k begins in data, off[nframes] = the run's end) describe the run; count >= 0. */
-static inline int fa_dw_select(const flac_format *fmt, const unsigned char *data, const int *sizes, const size_t *off,
-                               int nframes, unsigned fixed_block_size, unsigned long long first_sample, long long count,
-                               fa_dw_sel *o)
+/* Select the frames of window w's run that overlap [first_sample, first_sample + count).  hd answers for the run's
+ * headers; off [nframes + 1] (off[k] = where frame k begins, off[nframes] = the run's end) are its bytes; count >= 0. */
+static inline int fa_dw_select_by(const fa_dw_headers *hd, int w, const size_t *off, int nframes, unsigned fixed_block_size,
+                                  unsigned long long first_sample, long long count, fa_dw_sel *o)
 {
     flac_header h0, ha, hb;
     o->status = FA_DW_EMPTY;
@@ -59,7 +83,7 @@ static inline int fa_dw_select(const flac_format *fmt, const unsigned char *data
     o->block = 0;
     if (count <= 0 || nframes <= 0) return o->status;
     if (first_sample > 0x7FFFFFFFFFFFFFFFull - (unsigned long long)count) return o->status;    /* behind any stream's end */
-    if (!flac_header_ok(fmt, data + off[0], sizes[0], &h0)) return o->status = FA_DW_FAILED_HEADER;
+    if (!hd->get(hd->ctx, w, 0, &h0)) return o->status = FA_DW_FAILED_HEADER;
     const int block = h0.vbs ? 0 : (fixed_block_size ? (int)fixed_block_size : h0.n);
     const long long first = (long long)first_sample, end = first + count;
     if (first < fa_dw_start(&h0, block)) return o->status;              /* begins before the run's first frame */
@@ -69,7 +93,7 @@ static inline int fa_dw_select(const flac_format *fmt, const unsigned char *data
     while (lo < hi) {
         const int mid = lo + (hi - lo + 1) / 2;
         flac_header h;
-        if (!flac_header_ok(fmt, data + off[mid], sizes[mid], &h)) return o->status = FA_DW_FAILED_HEADER;
+        if (!hd->get(hd->ctx, w, mid, &h)) return o->status = FA_DW_FAILED_HEADER;
         if (fa_dw_start(&h, block) <= first) { lo = mid; ha = h; } else hi = mid - 1;
     }
     const int a = lo;
@@ -82,7 +106,7 @@ static inline int fa_dw_select(const flac_format *fmt, const unsigned char *data
     while (lo < hi) {
         const int mid = lo + (hi - lo + 1) / 2;
         flac_header h;
-        if (!flac_header_ok(fmt, data + off[mid], sizes[mid], &h)) return o->status = FA_DW_FAILED_HEADER;
+        if (!hd->get(hd->ctx, w, mid, &h)) return o->status = FA_DW_FAILED_HEADER;
         if (fa_dw_start(&h, block) < end) { lo = mid; hb = h; } else hi = mid - 1;
     }
     const int b = lo;
@@ -100,6 +124,16 @@ static inline int fa_dw_select(const flac_format *fmt, const unsigned char *data
     o->start = start_a;
     o->block = block;
     return o->status;
+}
+
+/* The same over the run's bytes: sizes [nframes] and off describe the run in data. */
+static inline int fa_dw_select(const flac_format *fmt, const unsigned char *data, const int *sizes, const size_t *off,
+                               int nframes, unsigned fixed_block_size, unsigned long long first_sample, long long count,
+                               fa_dw_sel *o)
+{
+    const fa_dw_bytes by = {fmt, &data, &sizes, &off};
+    const fa_dw_headers hd = {fa_dw_bytes_get, &by};
+    return fa_dw_select_by(&hd, 0, off, nframes, fixed_block_size, first_sample, count, o);
 }
 
 /* ---- batches --------------------------------------------------------------------------------------------------------
@@ -129,11 +163,10 @@ typedef struct fa_dw_batch {
 } fa_dw_batch;
 
 /* The next batch: fills *b from *cur (all zero before the first) and moves *cur behind it.  sel [nwin] are the windows'
- * selections; run_data[w] / run_sizes[w] / run_off[w] are window w's run as fa_dw_select took it.
+ * selections; hd and run_off[w] are window w's run as fa_dw_select_by took it.
  * Returns the batch's frames; 0 when the call is used up. */
-static inline int fa_dw_plan(fa_dw_cursor *cur, int nwin, fa_dw_sel *sel, const flac_format *fmt,
-                             const unsigned char *const *run_data, const int *const *run_sizes,
-                             const size_t *const *run_off, int max_batch, fa_dw_batch *b)
+static inline int fa_dw_plan_by(fa_dw_cursor *cur, int nwin, fa_dw_sel *sel, const fa_dw_headers *hd,
+                                const size_t *const *run_off, int max_batch, fa_dw_batch *b)
 {
     b->nframes = b->nsegs = 0;
     b->nbytes = 0;
@@ -150,7 +183,7 @@ static inline int fa_dw_plan(fa_dw_cursor *cur, int nwin, fa_dw_sel *sel, const 
             /* a cut inside the window: the header behind it says where the next part begins */
             flac_header h;
             const int f = f0 + take;
-            if (!flac_header_ok(fmt, run_data[w] + run_off[w][f], run_sizes[w][f], &h) || h.vbs != s->variable ||
+            if (!hd->get(hd->ctx, w, f, &h) || h.vbs != s->variable ||
                 fa_dw_start(&h, s->block) <= cur->start) {
                 /* the whole window fails: its earlier parts' results are the caller's to drop */
                 s->status = FA_DW_FAILED_HEADER;
@@ -186,6 +219,16 @@ static inline int fa_dw_plan(fa_dw_cursor *cur, int nwin, fa_dw_sel *sel, const 
         }
     }
     return b->nframes;
+}
+
+/* The same over the runs' bytes: run_data[w] / run_sizes[w] / run_off[w] are window w's run as fa_dw_select took it. */
+static inline int fa_dw_plan(fa_dw_cursor *cur, int nwin, fa_dw_sel *sel, const flac_format *fmt,
+                             const unsigned char *const *run_data, const int *const *run_sizes,
+                             const size_t *const *run_off, int max_batch, fa_dw_batch *b)
+{
+    const fa_dw_bytes by = {fmt, run_data, run_sizes, run_off};
+    const fa_dw_headers hd = {fa_dw_bytes_get, &by};
+    return fa_dw_plan_by(cur, nwin, sel, &hd, run_off, max_batch, b);
 }
 
 #endif

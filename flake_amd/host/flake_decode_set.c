@@ -16,6 +16,7 @@
 #include "decode_set_plan.h"
 #include "decode_window_plan.h"
 #include "decode_window_place.h"
+#include "held_plan.h"
 
 typedef struct {
     long long frames_done;        /* frames committed so far */
@@ -64,10 +65,26 @@ struct FlakeAmdDecodeSet {
     long long *wtarget;
     int32_t *wrow;                /* flake_amd_decode_set_windows_rows: each segment's row and first column */
     int64_t *wcol;
+    /* held streams (flake_amd_decode_set_hold ...): the store on the device, and the host's table of what it holds --
+     * every stream's entry, every frame's size and head, every frame's offset in the store (and each stream's end) */
+    unsigned char *hstore;
+    size_t hcap, hused;
+    fa_held_stream *hs;
+    size_t hs_cap;
+    int hn;
+    int32_t *hsize;
+    fa_held_head *hhead;
+    size_t *hoff;
+    size_t hsize_cap, hhead_cap, hoff_cap;
+    long long hframes, hoffs;     /* entries in use */
+    long long hup_add, hup_win;   /* bytes uploaded by hold_add and by held window calls */
+    int64_t *wsrc;                /* a held batch's frames' offsets in the store [max_batch] */
+    long long *wfirst;            /* a held call's windows' first records [per window] */
     char err[384];
 };
 
 typedef char ds_header_status_agrees[(int)FA_WP_HEADER == (int)FHIP_VERIFY_HEADER ? 1 : -1];
+typedef char ds_held_head_agrees[sizeof(fa_held_head) == sizeof(fhip_frame_head) && sizeof(fa_held_head) == 16 ? 1 : -1];
 
 static char g_open_err[256];
 
@@ -100,6 +117,7 @@ static size_t ds_carve(FlakeAmdDecodeSet *g, unsigned char *base)
     DS_SLOT(wb->seg_first, mb + 1); DS_SLOT(wb->seg_number, mb); DS_SLOT(wb->seg_variable, mb); DS_SLOT(wb->seg_skip, mb);
     DS_SLOT(wb->seg_take, mb); DS_SLOT(wb->seg_win, mb); DS_SLOT(wb->seg_frame0, mb); DS_SLOT(wb->seg_last, mb);
     DS_SLOT(g->wfb, mb); DS_SLOT(g->wstat, mb); DS_SLOT(g->wtarget, mb); DS_SLOT(g->wrow, mb); DS_SLOT(g->wcol, mb);
+    DS_SLOT(g->wsrc, mb);
     return at;
 }
 
@@ -108,6 +126,7 @@ static size_t ds_carve_windows(FlakeAmdDecodeSet *g, unsigned char *base, size_t
 {
     size_t at = 0;
     DS_SLOT(g->wsel, n); DS_SLOT(g->wdata, n); DS_SLOT(g->wsizes, n); DS_SLOT(g->woff, n); DS_SLOT(g->wat, n);
+    DS_SLOT(g->wfirst, n);
     return at;
 }
 
@@ -453,6 +472,8 @@ typedef struct {                  /* a call's arguments */
     const ds_rows_sink *rows;     /* (then pcm is null, sample_bytes 4, and the room is what the windows ask for) */
     long long *win_samples;
     int *win_status;
+    const int *held_of_win;       /* held streams: window w is asked of this one's whole run, and frames_of_win, stream,
+                                   * bytes, frame_sizes and fixed_block_size are null: the set's table has them */
 } ds_win_call;
 
 static int ds_grow(void **p, size_t *cap, size_t want, size_t elem)
@@ -487,15 +508,21 @@ static int ds_windows_check(FlakeAmdDecodeSet *g, const ds_win_call *q, long lon
             return -1;
         }
     }
-    if (ds_refuse_samples(g, nwin < 0 || (nwin > 0 && (!q->frames_of_win || !q->fixed_block_size || !q->first_sample ||
-                                                       !q->count || !q->win_samples || !q->win_status)) ||
+    const int held = q->held_of_win != NULL;
+    if (ds_refuse_samples(g, nwin < 0 || (nwin > 0 && ((!held && (!q->frames_of_win || !q->fixed_block_size)) ||
+                                                       !q->first_sample || !q->count || !q->win_samples || !q->win_status)) ||
                              (!q->stream && q->bytes) || (!q->pcm && q->pcm_cap_samples), q->sample_bytes))
         return -1;
     const long long room = rows ? 0x7FFFFFFFFFFFFFFFll : (long long)q->pcm_cap_samples;
     *nf = *asked = 0;
     for (int w = 0; w < nwin; w++) {
-        if (q->frames_of_win[w] < 0 || q->count[w] < 0 || q->count[w] > room - *asked) {
-            snprintf(g->err, sizeof g->err, "%s", q->frames_of_win[w] < 0 || q->count[w] < 0 ? "negative count"
+        if (held && (q->held_of_win[w] < 0 || q->held_of_win[w] >= g->hn)) {
+            snprintf(g->err, sizeof g->err, "a window names a held stream the set does not have");
+            return -1;
+        }
+        const int frames = held ? g->hs[q->held_of_win[w]].frames : q->frames_of_win[w];
+        if (frames < 0 || q->count[w] < 0 || q->count[w] > room - *asked) {
+            snprintf(g->err, sizeof g->err, "%s", frames < 0 || q->count[w] < 0 ? "negative count"
                                                   : "pcm_cap_samples is below the samples the windows ask for");
             return -1;
         }
@@ -504,7 +531,7 @@ static int ds_windows_check(FlakeAmdDecodeSet *g, const ds_win_call *q, long lon
             return -1;
         }
         *asked += q->count[w];
-        *nf += q->frames_of_win[w];
+        *nf += held ? 0 : frames;                     /* (a held call brings no frame sizes: nothing to lay out) */
     }
     if (*nf && !q->frame_sizes) { snprintf(g->err, sizeof g->err, "bad argument"); return -1; }
     return 0;
@@ -556,6 +583,40 @@ static int ds_windows_select(FlakeAmdDecodeSet *g, const ds_win_call *q, long lo
     return 0;
 }
 
+/* The same for a held call: every window's run is its stream's entry of the set's table. */
+static int ds_held_select(FlakeAmdDecodeSet *g, const ds_win_call *q, const fa_dw_headers *hd)
+{
+    if (fhip_set_pcm_format(g->hip, q->sample_bytes == 2 ? FHIP_PCM_S16 : FHIP_PCM_S32) != FHIP_OK) {
+        snprintf(g->err, sizeof g->err, "%s", fhip_last_error(g->hip));
+        return -1;
+    }
+    for (int w = 0; w < q->nwin; w++) {
+        const fa_held_stream *t = &g->hs[q->held_of_win[w]];
+        g->wdata[w] = NULL;
+        g->wsizes[w] = (const int *)g->hsize + t->frame0;
+        g->woff[w] = g->hoff + t->off0;               /* (the offsets count from the store's first byte) */
+        g->wfirst[w] = t->frame0;
+        fa_dw_select_by(hd, w, g->woff[w], t->frames, t->fixed_block_size, q->first_sample[w], q->count[w], &g->wsel[w]);
+    }
+    return 0;
+}
+
+/* A held batch's frames: where each lies in the store, and its size.  Returns the bytes of the tables the device entry
+ * uploads for it -- its segment tables and 12 bytes a frame, each table to the next 8-byte boundary (api.hip). */
+static long long ds_held_stage(FlakeAmdDecodeSet *g, int rows)
+{
+    const fa_dw_batch *b = &g->wb;
+    for (int k = 0; k < b->nsegs; k++) {
+        const int w = b->seg_win[k], f0 = b->seg_frame0[k], n = b->seg_first[k + 1] - b->seg_first[k];
+        for (int i = 0; i < n; i++) g->wsrc[b->seg_first[k] + i] = (int64_t)g->woff[w][f0 + i];
+        memcpy(g->wfb + b->seg_first[k], g->wsizes[w] + f0, (size_t)n * sizeof(int32_t));
+    }
+    const long long ns = b->nsegs, nf = b->nframes;
+#define DS_R8(x) (((x) + 7) & ~7ll)
+    return 8 * ns * 5 + DS_R8(4 * (ns + 1)) + 2 * DS_R8(4 * ns) + (rows ? 8 * ns + DS_R8(4 * ns) : 0) + 8 * nf + DS_R8(4 * nf);
+#undef DS_R8
+}
+
 /* The batch's bytes, back to back, and its frame sizes.  Returns the bytes; -1: out of memory. */
 static long long ds_windows_stage(FlakeAmdDecodeSet *g, const unsigned char *stream)
 {
@@ -599,7 +660,12 @@ static long long ds_windows(FlakeAmdDecodeSet *g, const ds_win_call *q, long lon
     if (ds_windows_room(g, nwin, nf)) return ds_nomem(g);
     const flac_format fmt = {(int)g->si.channels, (int)g->si.bits_per_sample, (int)g->si.sample_rate,
                              g->si.max_block_size > 65535u ? 0 : (int)g->si.max_block_size};
-    if (ds_windows_select(g, q, nf, &fmt)) return -1;
+    const int held = q->held_of_win != NULL;
+    const fa_dw_bytes by = {&fmt, (const unsigned char *const *)g->wdata, (const int *const *)g->wsizes,
+                            (const size_t *const *)g->woff};
+    const fa_held_table tab = {g->hhead, g->wfirst};
+    const fa_dw_headers hd = {held ? fa_held_get : fa_dw_bytes_get, held ? (const void *)&tab : (const void *)&by};
+    if (held ? ds_held_select(g, q, &hd) : ds_windows_select(g, q, nf, &fmt)) return -1;
     const size_t unit = g->si.channels * (size_t)q->sample_bytes;
     fa_dw_cursor cur;
     memset(&cur, 0, sizeof cur);
@@ -613,10 +679,10 @@ static long long ds_windows(FlakeAmdDecodeSet *g, const ds_win_call *q, long lon
         return -1;
     }
     long long decoded = 0;
-    while (fa_dw_plan(&cur, nwin, g->wsel, &fmt, (const unsigned char *const *)g->wdata, (const int *const *)g->wsizes,
-                      (const size_t *const *)g->woff, g->max_batch, b) > 0) {
-        const long long sb = ds_windows_stage(g, q->stream);
+    while (fa_dw_plan_by(&cur, nwin, g->wsel, &hd, (const size_t *const *)g->woff, g->max_batch, b) > 0) {
+        const long long sb = held ? ds_held_stage(g, rows != NULL) : ds_windows_stage(g, q->stream);
         if (sb < 0) return ds_nomem(g);
+        if (held) g->hup_win += sb;
         /* the device writes the batch's clips from base on; with rows, a window continues where its earlier segments got to */
         const long long base = fa_wp_batch(&place, b->nsegs, b->seg_win, rows ? g->wrow : NULL, rows ? g->wcol : NULL);
         int64_t summary[4] = {0, 0, -1, 0}, nsmp = 0;
@@ -626,8 +692,13 @@ static long long ds_windows(FlakeAmdDecodeSet *g, const ds_win_call *q, long lon
         fhip_decode_windows wn = {b->seg_skip, b->seg_take};
         fhip_decode_out out = {rows ? NULL : (int32_t *)((char *)q->pcm + (size_t)base * unit), (int64_t)pcm_cap_samples - base,
                                g->recs, summary, &nsmp};
-        const int rc = rows ? fhip_decode_frames_windows_rows(g->hip, &in, &sg, &wn, g->wrow, g->wcol, &ro, &out)
-                            : fhip_decode_frames_windows(g->hip, &in, &sg, &wn, &out);
+        const int rc =
+            held ? (rows ? fhip_decode_frames_windows_rows_held(g->hip, g->hstore, (int64_t)g->hused, g->wsrc, g->wfb, b->nframes,
+                                                                &sg, &wn, g->wrow, g->wcol, &ro, &out)
+                         : fhip_decode_frames_windows_held(g->hip, g->hstore, (int64_t)g->hused, g->wsrc, g->wfb, b->nframes,
+                                                           &sg, &wn, &out))
+                 : (rows ? fhip_decode_frames_windows_rows(g->hip, &in, &sg, &wn, g->wrow, g->wcol, &ro, &out)
+                         : fhip_decode_frames_windows(g->hip, &in, &sg, &wn, &out));
         g->device_batches++;
         decoded += b->nframes;
         if (rc != FHIP_OK && rc != FHIP_E_VERIFY) {
@@ -656,7 +727,7 @@ FLAKE_AMD_API long long flake_amd_decode_set_windows(FlakeAmdDecodeSet *g, int n
         long long *win_samples, int *win_status, long long *frames_decoded)
 {
     const ds_win_call q = {nwin, frames_of_win, stream, bytes, frame_sizes, fixed_block_size, first_sample, count, pcm,
-                           sample_bytes, pcm_cap_samples, NULL, win_samples, win_status};
+                           sample_bytes, pcm_cap_samples, NULL, win_samples, win_status, NULL};
     return ds_windows(g, &q, frames_decoded);
 }
 
@@ -668,8 +739,149 @@ FLAKE_AMD_API long long flake_amd_decode_set_windows_rows(FlakeAmdDecodeSet *g, 
 {
     const ds_rows_sink sink = {dev_rows, row_format, row_len};
     const ds_win_call q = {nwin, frames_of_win, stream, bytes, frame_sizes, fixed_block_size, first_sample, count, NULL, 4, 0,
-                           &sink, win_samples, win_status};
+                           &sink, win_samples, win_status, NULL};
     return ds_windows(g, &q, frames_decoded);
+}
+
+/* ---- held streams ---------------------------------------------------------------------------------------------------
+ * The store is one device allocation that streams are appended to; the host keeps, per stream, where its frames lie in
+ * the set's tables, and per frame its size, its offset in the store and its header as k_frame_heads read it.  A window
+ * call selects and cuts batches over that table (held_plan.h) and sends the device the frames' offsets and sizes; the
+ * bytes never cross the link again. */
+FLAKE_AMD_API int flake_amd_decode_set_hold(FlakeAmdDecodeSet *g, size_t capacity_bytes)
+{
+    if (!g) return -1;
+    g->err[0] = 0;
+    if (g->hstore || capacity_bytes < 1) {
+        snprintf(g->err, sizeof g->err, "%s", g->hstore ? "the set holds a store already" : "bad argument");
+        return -1;
+    }
+    g->hstore = (unsigned char *)fhip_device_alloc(capacity_bytes);
+    if (!g->hstore) {
+        snprintf(g->err, sizeof g->err, "no device memory for a store of %zu bytes", capacity_bytes);
+        return -1;
+    }
+    g->hcap = capacity_bytes;
+    return 0;
+}
+
+FLAKE_AMD_API long long flake_amd_decode_set_hold_add(FlakeAmdDecodeSet *g, unsigned max_block_size, const unsigned char *stream,
+                                                      const size_t *range_first, int nranges, const unsigned *fixed_block_size,
+                                                      int *held_ids)
+{
+    if (!g) return -1;
+    g->err[0] = 0;
+    if (!g->hstore || !range_first || nranges < 1 || !fixed_block_size || !held_ids || range_first[0] != 0 ||
+        (!stream && range_first[nranges]) || g->hn > 0x7FFFFFFF - nranges) {
+        snprintf(g->err, sizeof g->err, "%s", g && !g->hstore ? "the set holds no store" : "bad argument");
+        return -1;
+    }
+    for (int r = 0; r < nranges; r++)
+        if (range_first[r + 1] < range_first[r]) { snprintf(g->err, sizeof g->err, "bad argument"); return -1; }
+    const size_t bytes = range_first[nranges], nr = (size_t)nranges;
+    if (bytes >= ((size_t)1 << 31)) {
+        snprintf(g->err, sizeof g->err, "the device indexes less than 2 GiB per call");
+        return -1;
+    }
+    if (bytes > g->hcap - g->hused) {
+        snprintf(g->err, sizeof g->err, "the store has %zu bytes left, the call brings %zu", g->hcap - g->hused, bytes);
+        return -1;
+    }
+    /* no frame is shorter than a header, a subframe and the CRC-16: room for as many as the bytes can hold */
+    size_t cap = bytes / 9 + nr + 1;
+    if (cap > 0x7FFFFFFFu) cap = 0x7FFFFFFFu;
+    int64_t *w = (int64_t *)malloc((2 * nr + 1) * sizeof(int64_t) + 2 * nr * sizeof(int32_t));
+    if (!w || ds_grow((void **)&g->hs, &g->hs_cap, (size_t)g->hn + nr, sizeof *g->hs) ||
+        ds_grow((void **)&g->hsize, &g->hsize_cap, (size_t)g->hframes + cap, sizeof *g->hsize) ||
+        ds_grow((void **)&g->hhead, &g->hhead_cap, (size_t)g->hframes + cap, sizeof *g->hhead) ||
+        ds_grow((void **)&g->hoff, &g->hoff_cap, (size_t)g->hoffs + cap + nr, sizeof *g->hoff)) {
+        free(w);
+        return ds_nomem(g);
+    }
+    int64_t *first = w, *cons = w + nr + 1;
+    int32_t *frames = (int32_t *)(w + 2 * nr + 1), *variable = frames + nr;
+    for (size_t r = 0; r <= nr; r++) first[r] = (int64_t)range_first[r];
+    int32_t *sizes = g->hsize + g->hframes;
+    fa_held_head *heads = g->hhead + g->hframes;
+    const fhip_hold_in in = {g->hstore, (int64_t)g->hcap, (int64_t)g->hused, stream, (int64_t)bytes, first, nranges,
+                             (int32_t)(max_block_size > 65535u ? 65535u : max_block_size), (int32_t)cap};
+    const fhip_hold_out out = {sizes, (fhip_frame_head *)heads, frames, cons, variable};
+    const int rc = fhip_hold_frames(g->hip, &in, &out);
+    long long total = 0;
+    for (size_t r = 0; r < nr && rc == FHIP_OK; r++) total += frames[r] > 0 ? frames[r] : 0;
+    if (rc != FHIP_OK || (size_t)total > cap) {
+        if (rc != FHIP_OK) snprintf(g->err, sizeof g->err, "fhip_hold_frames: %s", fhip_last_error(g->hip));
+        else snprintf(g->err, sizeof g->err, "more frames than the bytes can hold");
+        free(w);
+        return -1;
+    }
+    /* from here on the call changes the set */
+    long long f = 0;
+    for (size_t r = 0; r < nr; r++) {
+        fa_held_stream *t = &g->hs[g->hn];
+        held_ids[r] = g->hn++;
+        t->frame0 = g->hframes + f;
+        t->off0 = g->hoffs;
+        t->frames = frames[r] > 0 ? frames[r] : 0;
+        t->fixed_block_size = fixed_block_size[r];
+        t->samples = 0;
+        size_t at = g->hused + range_first[r];
+        for (int k = 0; k < t->frames; k++, f++) {
+            g->hoff[g->hoffs++] = at;
+            at += (size_t)sizes[f];
+            if (heads[f].flags & 1) t->samples += heads[f].n;
+        }
+        g->hoff[g->hoffs++] = at;
+    }
+    g->hframes += total;
+    g->hused += bytes;
+    g->hup_add += (long long)bytes + (long long)((nr + 1) * sizeof(int64_t));
+    free(w);
+    return total;
+}
+
+FLAKE_AMD_API long long flake_amd_decode_set_held_windows(FlakeAmdDecodeSet *g, int nwin, const int *held_of_win,
+        const unsigned long long *first_sample, const long long *count, void *pcm, int sample_bytes, size_t pcm_cap_samples,
+        long long *win_samples, int *win_status, long long *frames_decoded)
+{
+    static const int none = 0;
+    if (g && nwin > 0 && !held_of_win) { snprintf(g->err, sizeof g->err, "bad argument"); return -1; }
+    const ds_win_call q = {nwin, NULL, NULL, 0, NULL, NULL, first_sample, count, pcm, sample_bytes, pcm_cap_samples, NULL,
+                           win_samples, win_status, held_of_win ? held_of_win : &none};
+    return ds_windows(g, &q, frames_decoded);
+}
+
+FLAKE_AMD_API long long flake_amd_decode_set_held_windows_rows(FlakeAmdDecodeSet *g, int nwin, const int *held_of_win,
+        const unsigned long long *first_sample, const long long *count, void *dev_rows, int row_format, long long row_len,
+        long long *win_samples, int *win_status, long long *frames_decoded)
+{
+    static const int none = 0;
+    if (g && nwin > 0 && !held_of_win) { snprintf(g->err, sizeof g->err, "bad argument"); return -1; }
+    const ds_rows_sink sink = {dev_rows, row_format, row_len};
+    const ds_win_call q = {nwin, NULL, NULL, 0, NULL, NULL, first_sample, count, NULL, 4, 0, &sink, win_samples, win_status,
+                           held_of_win ? held_of_win : &none};
+    return ds_windows(g, &q, frames_decoded);
+}
+
+FLAKE_AMD_API int flake_amd_decode_set_held_info(const FlakeAmdDecodeSet *g, int id, long long *frames, long long *samples,
+                                                 long long *bytes)
+{
+    if (!g || id < 0 || id >= g->hn) return -1;
+    const fa_held_stream *t = &g->hs[id];
+    if (frames) *frames = t->frames;
+    if (samples) *samples = t->samples;
+    if (bytes) *bytes = (long long)(g->hoff[t->off0 + t->frames] - g->hoff[t->off0]);
+    return 0;
+}
+
+FLAKE_AMD_API int flake_amd_decode_set_held_stats(const FlakeAmdDecodeSet *g, long long out[4])
+{
+    if (!g || !out) return -1;
+    out[0] = (long long)g->hused;
+    out[1] = g->hframes;
+    out[2] = g->hup_add;
+    out[3] = g->hup_win;
+    return 0;
 }
 
 FLAKE_AMD_API int flake_amd_decode_set_index(FlakeAmdDecodeSet *g, unsigned max_block_size, const unsigned char *stream,
@@ -694,6 +906,8 @@ FLAKE_AMD_API void flake_amd_decode_set_close(FlakeAmdDecodeSet *g)
     if (!g) return;
     if (g->hip) { (void)fhip_sync(g->hip); fhip_destroy(g->hip); }
     if (g->states) fhip_device_free(g->states);
+    if (g->hstore) fhip_device_free(g->hstore);
+    free(g->hs); free(g->hsize); free(g->hhead); free(g->hoff);
     free(g->tables); free(g->wtables); free(g->run_off); free(g->foff); free(g->wstage);
     free(g);
 }

@@ -1,4 +1,4 @@
-"""Identity of the kernel sources: a SHA-1 over flake_amd/csrc and include/flakehip.h.  The
+"""Identity of the kernel sources: a SHA-1 over flake_amd/csrc, include/flakehip.h and include/flakehip_held.h.  The
 PMC summary under profiles/ records the one it was measured with, bench.py reports whether
 the library it times still is that code (the traffic figure must not go stale
 silently)."""
@@ -13,6 +13,7 @@ def kernel_sources_sha1() -> str:
     h = hashlib.sha1()
     files = sorted(glob.glob(os.path.join(ROOT, "flake_amd", "csrc", "*")))
     files.append(os.path.join(ROOT, "include", "flakehip.h"))
+    files.append(os.path.join(ROOT, "include", "flakehip_held.h"))
     for p in files:
         if os.path.isfile(p):
             h.update(os.path.basename(p).encode())

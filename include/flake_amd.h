@@ -479,6 +479,51 @@ FLAKE_AMD_API long long flake_amd_decode_set_windows_rows(FlakeAmdDecodeSet *g, 
         const unsigned *fixed_block_size, const unsigned long long *first_sample, const long long *count,
         void *dev_rows, int row_format, long long row_len,
         long long *win_samples, int *win_status, long long *frames_decoded);
+/*
+ * HELD STREAMS: a corpus that stays on the device.  The set owns one store of capacity_bytes of device memory, streams
+ * are appended to it and indexed where they lie, and windows are then asked for by (held stream, first_sample, count):
+ * no stream byte crosses the link again, a call uploads only its tables and 12 bytes per selected frame.  The set's
+ * handle, format and FLAKE_AMD_BATCH apply.
+ *
+ * flake_amd_decode_set_hold allocates the store, once per set: -1 on a second call, for capacity_bytes 0 or when the
+ * allocation fails.
+ *
+ * flake_amd_decode_set_hold_add appends ranges as flake_amd_decode_set_index takes them -- one file each, from its first
+ * frame header on -- and gives every range the set's next id in held_ids[r], a range K8 refuses (-1) included: such a
+ * held stream has 0 frames and its windows deliver 0.  fixed_block_size[r] is STREAMINFO's block size where minimum and
+ * maximum agree, else 0.  The bytes are uploaded behind what the store holds, K8 runs on the resident copy, every
+ * frame's header is read on the device (k_frame_heads), and the frames' sizes and heads come back into the set's table,
+ * with one synchronisation (a second beyond 65536 frames in one call).  Returns the frames found; -1 with nothing
+ * changed for a bad argument, a set without a store, 2 GiB or more in one call (K8's limit), no room in the store or a
+ * HIP failure.  Files whose max_block_size differ go through calls of their own.
+ *
+ * flake_amd_decode_set_held_windows / _held_windows_rows are flake_amd_decode_set_windows / _windows_rows, value for
+ * value, with window w asked of the whole run of held stream held_of_win[w]: the frames and sizes hold_add found, the
+ * stream's fixed_block_size, the samples or rows, win_samples, win_status, *frames_decoded, the return value, the room a
+ * failed window keeps and the zeroing rule of the rows.  Selection is the same bisection, over the table's heads instead
+ * of the bytes: it probes the same frames in the same order.  Stateless like their siblings; also -1 for an id outside
+ * the set's held streams.
+ *
+ * flake_amd_decode_set_held_info: a held stream's frames, the samples its good headers add up to and its bytes (any
+ * pointer may be null); -1 for an id the set does not have.  flake_amd_decode_set_held_stats: out[0] bytes resident,
+ * out[1] frames in the table, out[2] bytes uploaded by hold_add, out[3] bytes uploaded by held window calls.
+ * flake_amd_decode_set_close frees the store.  Streams cannot be removed or replaced.
+ */
+FLAKE_AMD_API int flake_amd_decode_set_hold(FlakeAmdDecodeSet *g, size_t capacity_bytes);
+FLAKE_AMD_API long long flake_amd_decode_set_hold_add(FlakeAmdDecodeSet *g, unsigned max_block_size,
+        const unsigned char *stream, const size_t *range_first, int nranges, const unsigned *fixed_block_size,
+        int *held_ids);
+FLAKE_AMD_API long long flake_amd_decode_set_held_windows(FlakeAmdDecodeSet *g, int nwin, const int *held_of_win,
+        const unsigned long long *first_sample, const long long *count,
+        void *pcm, int sample_bytes, size_t pcm_cap_samples,
+        long long *win_samples, int *win_status, long long *frames_decoded);
+FLAKE_AMD_API long long flake_amd_decode_set_held_windows_rows(FlakeAmdDecodeSet *g, int nwin, const int *held_of_win,
+        const unsigned long long *first_sample, const long long *count,
+        void *dev_rows, int row_format, long long row_len,
+        long long *win_samples, int *win_status, long long *frames_decoded);
+FLAKE_AMD_API int flake_amd_decode_set_held_info(const FlakeAmdDecodeSet *g, int id, long long *frames, long long *samples,
+                                                 long long *bytes);
+FLAKE_AMD_API int flake_amd_decode_set_held_stats(const FlakeAmdDecodeSet *g, long long out[4]);
 FLAKE_AMD_API const char *flake_amd_decode_set_last_error(const FlakeAmdDecodeSet *g);
 FLAKE_AMD_API void flake_amd_decode_set_close(FlakeAmdDecodeSet *g);
 
