@@ -169,6 +169,29 @@ class RowsOut(C.Structure):
 ROWS_I32, ROWS_I16, ROWS_F32 = 0, 1, 2
 
 
+class RowsIn(C.Structure):
+    """``fhip_rows_in``"""
+    _fields_ = [("rows", C.c_void_p), ("nrows", C.c_int32), ("format", C.c_int32), ("row_len", C.c_int64)]
+
+
+class RowPiece(C.Structure):
+    """``fhip_row_piece``: count samples per channel from column col of row `row` to sample dst of the destination"""
+    _fields_ = [("row", C.c_int32), ("count", C.c_int32), ("col", C.c_int64), ("dst", C.c_int64)]
+
+
+# numpy view of fhip_row_piece (24 bytes): K12's unit, in samples per channel
+ROW_PIECE_DTYPE = np.dtype([("row", "<i4"), ("count", "<i4"), ("col", "<i8"), ("dst", "<i8")])
+assert ROW_PIECE_DTYPE.itemsize == 24 == C.sizeof(RowPiece)
+
+
+def row_pieces(rows) -> np.ndarray:
+    """[(row, col, dst, count)] as a fhip_row_piece table."""
+    t = np.zeros(len(rows), dtype=ROW_PIECE_DTYPE)
+    for k, (row, col, dst, count) in enumerate(rows):
+        t[k] = (row, count, col, dst)
+    return t
+
+
 class IndexIn(C.Structure):
     """``fhip_index_in``"""
     _fields_ = [("stream", C.c_void_p), ("stream_bytes", C.c_int64), ("range_first", C.c_void_p),
@@ -317,6 +340,8 @@ def load_library() -> C.CDLL:
                                                      C.POINTER(DecodeWindows), vp, vp, C.POINTER(RowsOut),
                                                      C.POINTER(DecodeOut)]),
         "fhip_hold_frames": (i, [vp, vp, vp]),
+        "fhip_pcm_from_rows_dev": (i, [vp, vp, i64, C.POINTER(RowsIn), vp, i]),
+        "fhip_frames_packed_from_rows": (i, [vp, C.POINTER(Batch), vp, C.POINTER(RowsIn), vp, i]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -359,6 +384,8 @@ HELD_ABI_SYMBOLS = (
     "fhip_frame_heads_dev", "fhip_gather_frames_dev", "fhip_decode_frames_windows_held",
     "fhip_decode_frames_windows_rows_held", "fhip_hold_frames",
 )
+# ... and include/flakehip_rows_in.h: the encode-rows entries (K12)
+ROWS_IN_ABI_SYMBOLS = ("fhip_pcm_from_rows_dev", "fhip_frames_packed_from_rows")
 
 # fhip_gather_piece (24 bytes): K9's unit, in samples per channel
 GATHER_PIECE_DTYPE = np.dtype([("src_buf", "<i4"), ("count", "<i4"), ("src", "<i8"), ("dst", "<i8")])
@@ -934,6 +961,29 @@ class Encoder:
                                                   _ptr(src1) if not isinstance(src1, int) else src1, int(src1_cap),
                                                   t.ctypes.data if len(t) else None, len(t))
 
+    # -- K12: rows of a planar device batch into interleaved PCM ------------
+    def pcm_from_rows_dev(self, dst, dst_cap: int, rows, nrows: int, row_len: int, fmt: int, pieces) -> int:
+        """fhip_pcm_from_rows_dev (K12 alone): dst is int32 device memory [dst_cap][channels], rows device memory
+        [nrows][channels][row_len] of the format fmt (ROWS_*) (torch tensors or raw addresses); pieces a ROW_PIECE_DTYPE
+        host table (see row_pieces).  Async on the handle's stream.  Returns the code: E_INVALID means nothing was
+        queued."""
+        t = np.ascontiguousarray(pieces, dtype=ROW_PIECE_DTYPE)
+        ri = RowsIn(_ptr(rows), int(nrows), int(fmt), int(row_len))
+        return int(self.lib.fhip_pcm_from_rows_dev(self._h, _ptr(dst), int(dst_cap), C.byref(ri),
+                                                   t.ctypes.data if len(t) else None, len(t)))
+
+    def frames_packed_from_rows(self, token: int, nframes: int, block_size: int, rows, nrows: int, row_len: int, fmt: int,
+                                pieces, block_sizes=None) -> int:
+        """fhip_frames_packed_from_rows: the handle's PCM staging filled from rows through a piece table, in place of
+        fhip_frames_packed_upload(_ragged).  token: the value the following _begin's Batch.pcm must carry (it names the
+        batch and is never followed).  Returns the code."""
+        t = np.ascontiguousarray(pieces, dtype=ROW_PIECE_DTYPE)
+        sz = None if block_sizes is None else np.ascontiguousarray(block_sizes, dtype=np.int32)
+        b = Batch(pcm=token, nframes=nframes, block_size=block_size)
+        ri = RowsIn(_ptr(rows), int(nrows), int(fmt), int(row_len))
+        return int(self.lib.fhip_frames_packed_from_rows(self._h, C.byref(b), None if sz is None else sz.ctypes.data,
+                                                         C.byref(ri), t.ctypes.data if len(t) else None, len(t)))
+
     def kernel_times(self, reset: bool = True) -> dict:
         names = (C.c_char_p * 32)()
         ms = (C.c_double * 32)()
@@ -1163,6 +1213,9 @@ def load_host_library() -> C.CDLL:
     lib.flake_amd_set_encode_ragged.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_size_t, C.c_void_p]
     lib.flake_amd_set_encode_ragged.restype = C.c_longlong
+    lib.flake_amd_set_encode_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.flake_amd_set_encode_rows.restype = C.c_longlong
     lib.flake_amd_set_get_streaminfo.argtypes = [C.c_void_p, C.c_int, C.POINTER(HostStreaminfo)]
     lib.flake_amd_set_get_streaminfo.restype = C.c_int
     lib.flake_amd_set_last_error.argtypes = [C.c_void_p]
@@ -1654,6 +1707,40 @@ class StreamSet:
         if w < 0:
             raise FlakeHipError(int(w), "flake_amd_set_encode_ragged", self.last_error())
         return out[:w].copy(), sizes[:nblocks]
+
+    def encode_rows(self, rows, lengths, streams=None):
+        """flake_amd_set_encode_rows: rows is a contiguous torch tensor [nrows][channels][row_len] of torch.int32,
+        torch.int16 or torch.float32 (samples in [-1, 1)) on the set's device; row r is the next lengths[r] samples of
+        stream streams[r] (default: row r is of stream r).  Returns a list with each row's bytes: the frames of its whole
+        blocks, then of its short block.  Nothing is pending afterwards.  ctypes only; no compute here."""
+        import torch
+        fmt = {torch.int32: ROWS_I32, torch.int16: ROWS_I16, torch.float32: ROWS_F32}.get(rows.dtype)
+        if fmt is None:
+            raise ValueError("rows is a tensor of torch.int32, torch.int16 or torch.float32")
+        ch = int(self.ctx.channels)
+        dev = torch.device("cuda", int(os.environ.get("FLAKE_AMD_DEVICE") or 0))
+        if rows.dim() != 3 or rows.shape[1] != ch or not rows.is_contiguous() or rows.device != dev:
+            raise ValueError("rows must be a contiguous [nrows, channels, row_len] tensor on the set's device")
+        nrows, row_len = int(rows.shape[0]), int(rows.shape[2])
+        lens = np.ascontiguousarray(lengths, dtype=np.int64)
+        sor = np.ascontiguousarray(np.arange(nrows) if streams is None else streams, dtype=np.int32)
+        if len(lens) != nrows or len(sor) != nrows:
+            raise ValueError("lengths and streams hold one value per row")
+        nblocks = int(sum(-(-int(n) // self.block_size) for n in lens if n > 0))
+        cap = 64 + int(np.clip(lens, 0, None).sum()) * ch * 5 + 64 * (nblocks + 1) * 8
+        out = np.zeros(cap, dtype=np.uint8)
+        whole, tail = np.zeros(max(nrows, 1), dtype=np.int64), np.zeros(max(nrows, 1), dtype=np.int64)
+        # the library reads on its handle's stream: whatever torch's own stream still has queued that writes the rows
+        # finishes first
+        torch.cuda.current_stream(dev).synchronize()
+        w = self.lib.flake_amd_set_encode_rows(self._g, rows.data_ptr() if nrows else None, fmt, nrows, row_len,
+                                               sor.ctypes.data, lens.ctypes.data, out.ctypes.data, cap,
+                                               whole.ctypes.data, tail.ctypes.data)
+        if w < 0:
+            raise FlakeHipError(int(w), "flake_amd_set_encode_rows", self.last_error())
+        wat = np.concatenate([[0], np.cumsum(whole[:nrows])])
+        tat = wat[-1] + np.concatenate([[0], np.cumsum(tail[:nrows])])
+        return [bytes(out[wat[r]:wat[r + 1]]) + bytes(out[tat[r]:tat[r + 1]]) for r in range(nrows)]
 
     def device_batches(self) -> int:
         """flake_amd_set_device_batches: chunks handed to an encode entry of the HIP layer since the set was opened."""

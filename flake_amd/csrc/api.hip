@@ -195,6 +195,10 @@ struct fhip_ctx {
     DevBuf<fhip_gather_piece> d_gather;
     std::vector<fhip_gather_piece> h_gather;  // ... and the host image it is uploaded from
 
+    // K12 (fhip_pcm_from_rows_dev, fhip_frames_packed_from_rows): the same for its piece table
+    DevBuf<fhip_row_piece> d_rowpieces;
+    std::vector<fhip_row_piece> h_rowpieces;
+
     // K11 (fhip_gather_frames_dev, fhip_decode_frames_windows*_held): each frame's place, and for the held forms the
     // host's frame_src / frame_len tables in front of it, in one block, grow-only
     DevBuf<long long> d_held;
@@ -254,18 +258,18 @@ void note_launch(const char *fmt, ...)
 
 namespace {
 
-constexpr int kNumKernels = 14 + fhip::INDEX_STEPS;
+constexpr int kNumKernels = 15 + fhip::INDEX_STEPS;
 const char *const kKernelNames[kNumKernels] = {"k_prepare", "k_autocorr", "k_lpc", "k_encode", "k_assemble",
                                                "k_order_search", "k_verify", "k_decode",
                                                // K8's launches, one name each (fhip::index_step_name without the <>)
                                                "k_index_count", "k_index_wgscan", "k_index_scatter", "k_index_walk",
                                                "k_index_ranges", "k_index_emit", "k_gather_spans", "k_window_rows",
                                                "k_frame_heads", "k_gather_offsets", "k_gather_frames",
-                                               "k_frame_offsets"};
+                                               "k_frame_offsets", "k_rows_to_pcm"};
 constexpr int kProfVerify = 6, kProfDecode = 7, kProfIndex = 8, kProfGather = 8 + fhip::INDEX_STEPS,
               kProfRows = 9 + fhip::INDEX_STEPS, kProfHeads = 10 + fhip::INDEX_STEPS,
               kProfGatherOffsets = 11 + fhip::INDEX_STEPS, kProfGatherFrames = 12 + fhip::INDEX_STEPS,
-              kProfFrameOffsets = 13 + fhip::INDEX_STEPS;
+              kProfFrameOffsets = 13 + fhip::INDEX_STEPS, kProfRowsIn = 14 + fhip::INDEX_STEPS;
 
 int fail_hip(fhip_ctx *c, hipError_t e, const char *what)
 {
@@ -1601,20 +1605,23 @@ int fhip_gather_spans_dev(fhip_ctx *c, int32_t *dst, int64_t dst_cap, const int3
     return rc;
 }
 
-int fhip_frames_packed_gather(fhip_ctx *c, const fhip_batch *b, const int32_t *block_sizes, const int32_t *src0,
-                              int64_t src0_cap, const int32_t *src1, int64_t src1_cap, const fhip_gather_piece *pieces,
-                              int npieces)
+// The body of the entries that fill the handle's PCM staging from device memory through a piece table, in place of an
+// upload: check(room, &total) holds the table against the staging's capacity and run(dst, room, total) queues the
+// kernel on the handle's stream.  s16_refusal: the text of the refusal under FHIP_PCM_S16 (the staging is int32).
+extern "C++" template <class Check, class Run>
+static int packed_fill(fhip_ctx *c, const fhip_batch *b, const int32_t *block_sizes, const char *s16_refusal, Check check,
+                       Run run)
 {
     long long want = 0;
     int rc = block_sizes ? check_ragged(c, b, block_sizes, true, &want, true) : check_range(c, b, true, "null argument");
     if (rc != FHIP_OK) return rc;
     c->launches.clear();
     c->md5_log_entry = -1;
-    if (c->pcm_format == FHIP_PCM_S16) return fail(c, FHIP_E_UNSUPPORTED, "gathering takes int32 PCM only (FHIP_PCM_S16 is set)");
+    if (c->pcm_format == FHIP_PCM_S16) return fail(c, FHIP_E_UNSUPPORTED, s16_refusal);
     if (!block_sizes) want = (long long)b->nframes * b->block_size;
     long long total = 0;
     const int64_t room = (int64_t)c->max_frames * c->p.block_size;
-    rc = gather_check(c, room, src0, src0_cap, src1, src1_cap, pieces, npieces, &total);
+    rc = check(room, &total);
     if (rc != FHIP_OK) return rc;
     if (total != want) return fail(c, FHIP_E_INVALID, "the pieces do not cover exactly the batch's samples");
     c->uploaded_pcm = nullptr;
@@ -1626,7 +1633,7 @@ int fhip_frames_packed_gather(fhip_ctx *c, const fhip_batch *b, const int32_t *b
     if (rc != FHIP_OK) return rc;
     // what stage_pcm does before it writes the staging PCM: an MD5 update that still reads it finishes first
     if (c->md5_up_pending) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_md5_up, 0));
-    rc = run_gather(c, c->d_pcm, room, src0, src0_cap, src1, src1_cap, pieces, npieces, total);
+    rc = run(c->d_pcm, room, total);
     if (rc != FHIP_OK) return rc;
     if (block_sizes) {
         rc = upload_ragged_tables(c, block_sizes, b->nframes);
@@ -1640,6 +1647,95 @@ int fhip_frames_packed_gather(fhip_ctx *c, const fhip_batch *b, const int32_t *b
     c->uploaded_n = block_sizes ? -1 : b->block_size;
     if (block_sizes) c->uploaded_sizes.assign(block_sizes, block_sizes + b->nframes);
     return FHIP_OK;
+}
+
+int fhip_frames_packed_gather(fhip_ctx *c, const fhip_batch *b, const int32_t *block_sizes, const int32_t *src0,
+                              int64_t src0_cap, const int32_t *src1, int64_t src1_cap, const fhip_gather_piece *pieces,
+                              int npieces)
+{
+    return packed_fill(
+        c, b, block_sizes, "gathering takes int32 PCM only (FHIP_PCM_S16 is set)",
+        [&](int64_t room, long long *total) {
+            return gather_check(c, room, src0, src0_cap, src1, src1_cap, pieces, npieces, total);
+        },
+        [&](int32_t *dst, int64_t room, long long total) {
+            return run_gather(c, dst, room, src0, src0_cap, src1, src1_cap, pieces, npieces, total);
+        });
+}
+
+// ---- K12: rows of a planar device batch into interleaved PCM ------------------------------------
+
+// The checks of the rows and of the table, all on the host: what the kernel is launched with has passed them.
+// *total = the samples per channel the pieces cover.
+static int rows_in_check(fhip_ctx *c, int64_t dst_cap, const fhip_rows_in *rows, const fhip_row_piece *pieces, int npieces,
+                         long long *total)
+{
+    if (npieces < 0 || dst_cap < 0) return fail(c, FHIP_E_INVALID, "negative count");
+    if (!rows || !rows->rows) return fail(c, FHIP_E_INVALID, "null rows");
+    if (npieces > 0 && !pieces) return fail(c, FHIP_E_INVALID, "null piece table");
+    if (rows->nrows < 1 || rows->row_len < 1) return fail(c, FHIP_E_INVALID, "rows: nrows and row_len must be at least 1");
+    if (rows->format != FHIP_ROWS_I32 && rows->format != FHIP_ROWS_I16 && rows->format != FHIP_ROWS_F32)
+        return fail(c, FHIP_E_INVALID, "rows: unknown format");
+    if (rows->format == FHIP_ROWS_I16 && c->p.bits_per_sample > 16)
+        return fail(c, FHIP_E_INVALID, "rows: FHIP_ROWS_I16 needs bits_per_sample <= 16");
+    long long at = 0;
+    for (int i = 0; i < npieces; i++) {
+        const fhip_row_piece &p = pieces[i];
+        if (p.count < 1) return fail(c, FHIP_E_INVALID, "piece: count must be at least 1");
+        if (p.dst != at) return fail(c, FHIP_E_INVALID, "pieces must be sorted by dst and tile the destination exactly");
+        if (p.row < 0 || p.row >= rows->nrows) return fail(c, FHIP_E_INVALID, "piece: row outside the rows");
+        if (p.col < 0 || p.col > rows->row_len - p.count) return fail(c, FHIP_E_INVALID, "piece: columns outside the row");
+        at += p.count;
+        if (at > dst_cap) return fail(c, FHIP_E_INVALID, "pieces run past the destination's capacity");
+    }
+    *total = at;
+    return FHIP_OK;
+}
+
+// Upload the (checked) table and queue K12 on the handle's stream.
+static int run_rows_in(fhip_ctx *c, int32_t *dst, int64_t dst_cap, const fhip_rows_in *rows, const fhip_row_piece *pieces,
+                       int npieces, long long total)
+{
+    if (npieces == 0) return FHIP_OK;
+    HIP_TRY(c, c->d_rowpieces.reserve((size_t)npieces));
+    // (from the handle's own image: the caller's table is free when the call returns)
+    c->h_rowpieces.assign(pieces, pieces + npieces);
+    HIP_TRY(c, hipMemcpyAsync(c->d_rowpieces, c->h_rowpieces.data(), (size_t)npieces * sizeof(fhip_row_piece),
+                              hipMemcpyHostToDevice, c->stream));
+    fhip::RowsInArgs a{};
+    a.dst = dst; a.dst_cap = dst_cap;
+    a.rows = rows->rows; a.nrows = rows->nrows; a.row_len = rows->row_len;
+    a.pieces = c->d_rowpieces; a.npieces = npieces;
+    a.total = total;
+    a.channels = c->p.channels; a.format = rows->format; a.bits = c->p.bits_per_sample;
+    Prof pr(c, kProfRowsIn, c->profiling);
+    HIP_TRY(c, fhip::launch_rows_to_pcm(c->stream, a));
+    return FHIP_OK;
+}
+
+int fhip_pcm_from_rows_dev(fhip_ctx *c, int32_t *dst, int64_t dst_cap, const fhip_rows_in *rows,
+                           const fhip_row_piece *pieces, int npieces)
+{
+    if (!c) return FHIP_E_INVALID;
+    c->launches.clear();
+    c->md5_log_entry = -1;
+    if (c->pcm_format == FHIP_PCM_S16) return fail(c, FHIP_E_UNSUPPORTED, "rows become int32 PCM only (FHIP_PCM_S16 is set)");
+    long long total = 0;
+    int rc = rows_in_check(c, dst_cap, rows, pieces, npieces, &total);
+    if (rc != FHIP_OK) return rc;
+    if (total > 0 && !dst) return fail(c, FHIP_E_INVALID, "null destination");
+    LaunchScope ls(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    return run_rows_in(c, dst, dst_cap, rows, pieces, npieces, total);
+}
+
+int fhip_frames_packed_from_rows(fhip_ctx *c, const fhip_batch *b, const int32_t *block_sizes, const fhip_rows_in *rows,
+                                 const fhip_row_piece *pieces, int npieces)
+{
+    return packed_fill(
+        c, b, block_sizes, "rows become int32 PCM only (FHIP_PCM_S16 is set)",
+        [&](int64_t room, long long *total) { return rows_in_check(c, room, rows, pieces, npieces, total); },
+        [&](int32_t *dst, int64_t room, long long total) { return run_rows_in(c, dst, room, rows, pieces, npieces, total); });
 }
 
 // ---- K6: the MD5 of many streams ----------------------------------------------------------------

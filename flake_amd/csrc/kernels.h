@@ -486,6 +486,23 @@ struct WindowRowsArgs {
 constexpr int ROWS_TILE = 512;
 hipError_t launch_window_rows(hipStream_t st, const WindowRowsArgs &a);
 
+// K12 (k12_rows_in.hip): K10's inverse -- spans of rows[nrows][channels][row_len] (int32, int16 or float32; format:
+// FHIP_ROWS_*) converted and laid channel-interleaved as int32 into dst.  One launch on st, a workgroup per ROWS_IN_TILE
+// samples of the destination.  pieces is a DEVICE table, sorted by dst and tiling [0, total); every read of it is
+// clamped to [0, npieces), every row to [0, nrows), every column to [0, row_len) and every write below
+// min(total, dst_cap) samples, whatever it holds.  float32: x = clamp(rne(e * 2^(bits-1))), NaN -> 0.
+using RowPiece = fhip_row_piece;
+struct RowsInArgs {
+    int32_t *dst; long long dst_cap;             // capacity in samples per channel
+    const void *rows; int nrows; long long row_len;
+    const RowPiece *pieces; int npieces;
+    long long total;                             // the samples per channel the table covers
+    int channels, format, bits;                  // bits: the handle's bits_per_sample
+    float two_pow = 0.f; int32_t imax = 0;       // (the launch's: 2^(bits-1) and 2^(bits-1) - 1)
+};
+constexpr int ROWS_IN_TILE = 1024;
+hipError_t launch_rows_to_pcm(hipStream_t st, const RowsInArgs &a);
+
 // K11 (k11_held.hip): frames of a store that stays on the device.  All tables are DEVICE memory.
 // k_frame_heads: heads[f] is flac_header_ok(fmt, stream + frame_off[f], frame_bytes[f]) as a record, all zero where it
 // answers 0, where frame_bytes[f] <= 0 and where the frame's range leaves [0, stream_bytes).  One lane per frame.

@@ -20,6 +20,10 @@
  * number; every other length goes through the packed path as one frame per block, with fhip_set_block_numbering on.
  * The short blocks of a flake_amd_set_encode_ragged call -- splittable or not, each of its own length -- go through
  * fhip_encode_blocks_vbs_ragged_numbered, one device batch per FLAKE_AMD_BATCH of them.
+ *
+ * Encode rows (flake_amd_set_encode_rows): the samples are rows of a planar batch that already lies on the device.  The
+ * call is planned into whole blocks and short blocks (rows_plan.h) and runs the two paths above with a source of row
+ * pieces in place of a host buffer: each chunk's upload becomes fhip_frames_packed_from_rows (K12), nothing else changes.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -29,6 +33,7 @@
 #include "flakehip.h"
 #include "host_internal.h"
 #include "recode_plan.h"
+#include "rows_plan.h"
 #include "seekpoints.h"
 
 struct FlakeAmdSet {
@@ -235,14 +240,19 @@ static long long set_verify_failed(FlakeAmdSet *g, const char *what, const int *
              verify_status_name(vr.status), vr.subframe, vr.sample, vr.bit);
 }
 
-/* The upload step of a chunk, or its stand-in for a call whose samples are gather pieces (fa_set_source): the chunk is
- * samples lo .. hi of the call; bt->pcm is then a token that names the batch. */
+/* The upload step of a chunk, or its stand-in for a call whose samples are gather pieces or row pieces (fa_set_source):
+ * the chunk is samples lo .. hi of the call; bt->pcm is then a token that names the batch. */
 static int set_bring(FlakeAmdSet *g, fa_set_source *src, const fhip_batch *bt, const int32_t *sizes, long long lo,
                      long long hi, const char **what)
 {
     if (!src) {
         *what = sizes ? "fhip_frames_packed_upload_ragged" : "fhip_frames_packed_upload";
         return sizes ? fhip_frames_packed_upload_ragged(g->hip, bt, sizes) : fhip_frames_packed_upload(g->hip, bt);
+    }
+    if (src->rows) {
+        *what = "fhip_frames_packed_from_rows";
+        const int k = fa_rows_slice(src->row_pieces, src->npieces, &src->cur, lo, hi, src->row_work);
+        return fhip_frames_packed_from_rows(g->hip, bt, sizes, src->rows, src->row_work, k);
     }
     *what = "fhip_frames_packed_gather";
     const int m = fa_rc_slice(src->pieces, src->npieces, &src->cur, lo, hi, src->work);
@@ -708,6 +718,96 @@ long long fa_set_encode_short_from(FlakeAmdSet *g, fa_set_source *src, int nbloc
                                          frame_sizes);
     if (r == -2) SET_FAIL("flake_amd_set_encode_ragged: the ragged packed path does not cover this set (block size above 16384)");
     return r;
+}
+
+/* ---- encode rows: a planar batch on the device (host/rows_plan.h, K12) ---- */
+
+/* The rows become two calls' worth of blocks -- every row's whole blocks, then every row's short block -- and each part
+ * runs through the set's own path with its samples named by row pieces (fa_set_source), which set_bring() hands to
+ * fhip_frames_packed_from_rows chunk by chunk.  Both parts' argument rules are held here first, against the streams as
+ * they are: the whole blocks change nothing the short blocks' rules read (they end no stream). */
+FLAKE_AMD_API long long flake_amd_set_encode_rows(FlakeAmdSet *g, const void *rows_dev, int format, int nrows, long long row_len,
+                                                  const int *stream_of_row, const long long *len_of_row,
+                                                  unsigned char *out, size_t out_size,
+                                                  long long *row_whole_bytes, long long *row_tail_bytes)
+{
+    if (!g) return -1;
+    g->err[0] = 0;
+    g->vfail = 0;
+    if (g->broken) SET_FAIL("flake_amd_set_encode_rows: an earlier device error left the set unusable");
+    if (g->host_md5) SET_FAIL("flake_amd_set_encode_rows: a set that hashes on the host (FLAKE_AMD_SET_MD5_HOST) needs its samples there");
+    if (nrows < 0 || (nrows > 0 && (!rows_dev || !stream_of_row || !len_of_row || !out || !row_whole_bytes || !row_tail_bytes)))
+        SET_FAIL("flake_amd_set_encode_rows: null argument or negative row count");
+    if (format != FHIP_ROWS_I32 && format != FHIP_ROWS_I16 && format != FHIP_ROWS_F32)
+        SET_FAIL("flake_amd_set_encode_rows: format must be FLAKE_AMD_ROWS_I32, _I16 or _F32");
+    if (format == FHIP_ROWS_I16 && g->hp.bits_per_sample > 16)
+        SET_FAIL("flake_amd_set_encode_rows: int16 rows need bits_per_sample <= 16");
+    if (nrows == 0) return 0;
+    if (row_len < 1 || row_len > INT32_MAX) SET_FAIL("flake_amd_set_encode_rows: row_len out of range");
+    const int B = g->hp.block_size;
+    int *per = g->scratch;                /* 1: the stream has a short block in this call */
+    memset(per, 0, sizeof(int) * (size_t)g->nstreams);
+    for (int r = 0; r < nrows; r++) {
+        const int s = stream_of_row[r];
+        const long long len = len_of_row[r];
+        if (len < 0 || len > row_len) SET_FAIL("flake_amd_set_encode_rows: len_of_row[%d] = %lld is outside the row's %lld columns", r, len, row_len);
+        if (s < 0 || s >= g->nstreams) SET_FAIL("flake_amd_set_encode_rows: stream_of_row[%d] = %d is outside the set's %d streams", r, s, g->nstreams);
+        if (len == 0) continue;
+        if (g->ended[s]) SET_FAIL("flake_amd_set_encode_rows: row %d belongs to stream %d, which a short block has ended", r, s);
+        if (len % B) {
+            if (per[s]) SET_FAIL("flake_amd_set_encode_rows: row %d gives stream %d a second short block in one call", r, s);
+            per[s] = 1;
+        }
+    }
+    fa_rows_counts n;
+    if (fa_rows_count(nrows, len_of_row, B, &n) != 0) SET_FAIL("flake_amd_set_encode_rows: too many blocks for one call");
+    if (n.nshort > 0 && B > 16384)
+        SET_FAIL("flake_amd_set_encode_rows: the ragged packed path does not cover this set (block size above 16384): "
+                 "rows must be multiples of the block size");
+    for (int r = 0; r < nrows; r++) row_whole_bytes[r] = row_tail_bytes[r] = 0;
+    if (n.nwhole + n.nshort == 0) return 0;
+    /* one block of int32 tables, one of pieces */
+    const size_t ni = (size_t)n.nwhole * 2 + (size_t)n.nshort * 4 + (size_t)nrows + 1;
+    const size_t npc = ((size_t)n.nwhole_pieces + (size_t)n.nshort) * 2;
+    int32_t *tab = (int32_t *)malloc(ni * sizeof(int32_t));
+    fhip_row_piece *pc = (fhip_row_piece *)malloc((npc ? npc : 1) * sizeof(fhip_row_piece));
+    if (!tab || !pc) { free(tab); free(pc); SET_FAIL("flake_amd_set_encode_rows: out of host memory"); }
+    int32_t *whole_stream = tab, *whole_fs = whole_stream + n.nwhole, *short_size = whole_fs + n.nwhole;
+    int32_t *short_stream = short_size + n.nshort, *short_row = short_stream + n.nshort, *short_fs = short_row + n.nshort;
+    int32_t *first = short_fs + n.nshort;
+    fhip_row_piece *whole_pieces = pc, *short_pieces = pc + n.nwhole_pieces;
+    fhip_row_piece *work = short_pieces + n.nshort;              /* room for the larger table's slice */
+    fa_rows_plan(nrows, len_of_row, stream_of_row, B, whole_stream, whole_pieces, short_size, short_stream, short_pieces,
+                 first, short_row);
+    const fhip_rows_in rows = {rows_dev, nrows, format, row_len};
+    long long total = 0;
+    if (n.nwhole > 0) {
+        fa_set_source src;
+        memset(&src, 0, sizeof src);
+        src.npieces = n.nwhole_pieces; src.rows = &rows; src.row_pieces = whole_pieces; src.row_work = work;
+        const long long w = fa_set_encode_from(g, &src, n.nwhole, B, (const int *)whole_stream, out, out_size, (int *)whole_fs);
+        if (w < 0) { free(tab); free(pc); return -1; }
+        total = w;
+        for (int r = 0; r < nrows; r++)
+            for (int b = first[r]; b < first[r + 1]; b++) row_whole_bytes[r] += whole_fs[b];
+    }
+    if (n.nshort > 0) {
+        fa_set_source src;
+        memset(&src, 0, sizeof src);
+        src.npieces = n.nshort; src.rows = &rows; src.row_pieces = short_pieces; src.row_work = work;
+        const long long w = fa_set_encode_short_from(g, &src, n.nshort, (const int *)short_size, (const int *)short_stream,
+                                                     out + total, out_size - (size_t)total, (int *)short_fs);
+        if (w < 0) {
+            /* the whole blocks are part of their streams already: what the caller holds no longer matches the set */
+            if (n.nwhole > 0) g->broken = 1;
+            free(tab); free(pc);
+            return -1;
+        }
+        total += w;
+        for (int i = 0; i < n.nshort; i++) row_tail_bytes[short_row[i]] = short_fs[i];
+    }
+    free(tab); free(pc);
+    return total;
 }
 
 /* ---- seek points (host/seekpoints.h); not in the drop-in libflake.so ---- */

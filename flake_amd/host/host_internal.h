@@ -51,8 +51,13 @@ static inline int fa_block_of_frame(long long frame, const int32_t *block_frames
 
 /* An encode call's samples as gather pieces from device memory instead of a host buffer (flake_set.c).  pieces tile the
  * call's samples (all blocks back to back); each chunk of the call gathers its part of them (fa_rc_slice into work,
- * which has room for npieces; cur is that walk's place, 0 before the call). */
+ * which has room for npieces; cur is that walk's place, 0 before the call).
+ * The second kind, rows (non-null: flake_amd_set_encode_rows): the samples are row pieces of a planar batch on the
+ * device, converted by K12; row_pieces tile the call's samples as pieces do, each chunk converts its part of them
+ * (fa_rows_slice into row_work, room for npieces), and the gather fields are unused. */
 struct fhip_gather_piece;
+struct fhip_rows_in;
+struct fhip_row_piece;
 typedef struct fa_set_source {
     const struct fhip_gather_piece *pieces;
     int npieces;
@@ -60,6 +65,9 @@ typedef struct fa_set_source {
     int64_t src0_cap, src1_cap;
     struct fhip_gather_piece *work;
     int cur;
+    const struct fhip_rows_in *rows;
+    const struct fhip_row_piece *row_pieces;
+    struct fhip_row_piece *row_work;
 } fa_set_source;
 struct FlakeAmdSet;
 /* flake_amd_set_encode / flake_amd_set_encode_ragged (every block short, one per stream) with int32 samples from src;

@@ -213,6 +213,37 @@ FLAKE_AMD_API long long flake_amd_set_encode(FlakeAmdSet *g, const void *samples
 FLAKE_AMD_API long long flake_amd_set_encode_ragged(FlakeAmdSet *g, const void *samples, int sample_bytes, int nblocks,
                                                     const int *block_sizes, const int *stream_of_block,
                                                     unsigned char *out, size_t out_size, int *frame_sizes);
+/*
+ * Encode rows: audio that already lies on the set's device as a padded planar batch -- rows_dev, DEVICE memory
+ * [nrows][channels][row_len] of int32, int16 (sets of at most 16 bits) or float32 (format: FLAKE_AMD_ROWS_I32 / _I16 /
+ * _F32, below) -- encoded without a sample crossing the link.  The counterpart of flake_amd_decode_set_windows_rows.
+ * Row r is the next len_of_row[r] samples (0 .. row_len) of stream stream_of_row[r]; it is cut into len / B whole blocks
+ * (B: the streams' block size) and, where len % B != 0, one short block.  An element e becomes the sample
+ *   int32, int16   e
+ *   float32        clamp(rne(e * 2^(bits_per_sample - 1)), -2^(b-1), 2^(b-1) - 1): round to nearest, ties to even; NaN
+ *                  gives 0, infinities clamp -- the exact inverse of FLAKE_AMD_ROWS_F32 on the decode side for every
+ *                  sample of up to 24 bits, so rows -> FLAC -> rows is the identity.
+ * (K12, fhip_frames_packed_from_rows in include/flakehip_rows_in.h, converts into the handle's own staging.)
+ * Contract: for every stream the frames, the STREAMINFO (MD5 included) and the stream's state afterwards are what two
+ * host calls on the converted samples give: flake_amd_set_encode on the call's whole blocks, in (row, block) order,
+ * followed by flake_amd_set_encode_ragged on its short blocks, in row order.  So the set's own rules decide: a short
+ * block ends its stream on a fixed-block set and not on a FLAKE_AMD_SET_VBS set; a stream has at most one short block
+ * in a call and may have several rows as long as the resulting block sequence is legal; a row whose length is a
+ * multiple of B leaves its stream open, so long audio continues in a later call.  Chunking by FLAKE_AMD_BATCH, seek
+ * points, verification, the device MD5 and the VBS levels work as for those calls.
+ * out receives all whole blocks' frames in (row, block) order, then the short blocks' frames in row order;
+ * row_whole_bytes[r] and row_tail_bytes[r] (both required, [nrows]) say how many bytes of each part are row r's, so
+ * that prefix sums place every row.  Returns the total, or -1.  Every argument rule of both parts is checked before
+ * anything is encoded: such an error leaves every stream unchanged.  A device failure or an output buffer that is too
+ * small behaves as in flake_amd_set_encode; where it strikes the short blocks after the whole blocks were committed,
+ * the set refuses further calls.  Refused with -1 and a message: sets opened with FLAKE_AMD_SET_MD5_HOST (no PCM is on
+ * the host) and, where a row has a short block, sets whose block size is above 16384 (no ragged path there).  Nothing
+ * is pending on the device when the call returns; the caller makes sure the rows are written before it calls.
+ */
+FLAKE_AMD_API long long flake_amd_set_encode_rows(FlakeAmdSet *g, const void *rows_dev, int format, int nrows,
+                                                  long long row_len, const int *stream_of_row,
+                                                  const long long *len_of_row, unsigned char *out, size_t out_size,
+                                                  long long *row_whole_bytes, long long *row_tail_bytes);
 /* flake_get_streaminfo() for one stream of the set.  The first request after an encode finalises and fetches the
  * digests of ALL streams (one synchronisation); the streams stay open. */
 FLAKE_AMD_API int flake_amd_set_get_streaminfo(FlakeAmdSet *g, int stream, FlakeAmdStreaminfo *si);
