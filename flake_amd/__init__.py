@@ -169,6 +169,13 @@ class RowsOut(C.Structure):
 ROWS_I32, ROWS_I16, ROWS_F32 = 0, 1, 2
 
 
+class SpanRows(C.Structure):
+    """``fhip_span_rows``: K13's tables -- every segment's span's first row, its rows and the segment's position in it --
+    with the hop, and for the device entry the CSR of the tiles"""
+    _fields_ = [("seg_row0", C.c_void_p), ("seg_nrows", C.c_void_p), ("seg_pos", C.c_void_p), ("hop", C.c_int64),
+                ("tile_first", C.c_void_p), ("ntiles", C.c_int32)]
+
+
 class RowsIn(C.Structure):
     """``fhip_rows_in``"""
     _fields_ = [("rows", C.c_void_p), ("nrows", C.c_int32), ("format", C.c_int32), ("row_len", C.c_int64)]
@@ -342,6 +349,14 @@ def load_library() -> C.CDLL:
         "fhip_hold_frames": (i, [vp, vp, vp]),
         "fhip_pcm_from_rows_dev": (i, [vp, vp, i64, C.POINTER(RowsIn), vp, i]),
         "fhip_frames_packed_from_rows": (i, [vp, C.POINTER(Batch), vp, C.POINTER(RowsIn), vp, i]),
+        "fhip_span_rows_from_segments_dev": (i, [vp, vp, i64, C.c_int32, vp, vp, vp, C.POINTER(SpanRows),
+                                                 C.POINTER(RowsOut)]),
+        "fhip_decode_frames_windows_spans": (i, [vp, C.POINTER(DecodeIn), C.POINTER(DecodeSegments),
+                                                 C.POINTER(DecodeWindows), C.POINTER(SpanRows), C.POINTER(RowsOut),
+                                                 C.POINTER(DecodeOut)]),
+        "fhip_decode_frames_windows_spans_held": (i, [vp, vp, i64, vp, vp, C.c_int32, C.POINTER(DecodeSegments),
+                                                      C.POINTER(DecodeWindows), C.POINTER(SpanRows), C.POINTER(RowsOut),
+                                                      C.POINTER(DecodeOut)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -386,6 +401,9 @@ HELD_ABI_SYMBOLS = (
 )
 # ... and include/flakehip_rows_in.h: the encode-rows entries (K12)
 ROWS_IN_ABI_SYMBOLS = ("fhip_pcm_from_rows_dev", "fhip_frames_packed_from_rows")
+# ... and include/flakehip_spans.h: the span-rows entries (K13)
+SPANS_ABI_SYMBOLS = ("fhip_span_rows_from_segments_dev", "fhip_decode_frames_windows_spans",
+                     "fhip_decode_frames_windows_spans_held")
 
 # fhip_gather_piece (24 bytes): K9's unit, in samples per channel
 GATHER_PIECE_DTYPE = np.dtype([("src_buf", "<i4"), ("count", "<i4"), ("src", "<i8"), ("dst", "<i8")])
@@ -828,6 +846,20 @@ class Encoder:
         return (rc, None, int(nsm[0]), recs, summary, s_start[:ns], s_samples[:ns], s_failed[:ns],
                 self.lib.fhip_last_error(self._h).decode() if rc else "")
 
+    # -- K13: spans as hop-spaced rows on the device -------------------------
+    def span_rows_from_segments_dev(self, pcm, pcm_cap: int, nsegs: int, seg_start, seg_samples, seg_failed, seg_row0,
+                                    seg_nrows, seg_pos, tile_first, ntiles: int, hop: int, rows, nrows: int, row_len: int,
+                                    fmt: int) -> int:
+        """fhip_span_rows_from_segments_dev (K13 alone): everything is device memory (torch tensors or raw addresses) --
+        pcm int32 [pcm_cap][channels], seg_start / seg_samples / seg_pos int64, seg_failed / seg_row0 / seg_nrows int32,
+        tile_first int32 [nsegs + 1] (the CSR of the 512-sample tiles each segment gets, ntiles in all), rows
+        [nrows][channels][row_len] of the format fmt (ROWS_*).  Async on the handle's stream.  Returns the code:
+        E_INVALID means nothing was queued."""
+        sp = SpanRows(_ptr(seg_row0), _ptr(seg_nrows), _ptr(seg_pos), int(hop), _ptr(tile_first), int(ntiles))
+        ro = RowsOut(_ptr(rows), int(nrows), int(fmt), int(row_len))
+        return int(self.lib.fhip_span_rows_from_segments_dev(self._h, _ptr(pcm), int(pcm_cap), int(nsegs), _ptr(seg_start),
+                                                             _ptr(seg_samples), _ptr(seg_failed), C.byref(sp), C.byref(ro)))
+
     # -- K11: held streams -------------------------------------------------
     def frame_heads_dev(self, stream, stream_bytes: int, frame_off, frame_bytes, nframes: int, max_block_size: int,
                         heads) -> int:
@@ -875,6 +907,12 @@ class Encoder:
                 None if null_table == "segs" else C.byref(sg), None if null_table == "win" else C.byref(wn))
         if rows is None:
             rc = self.lib.fhip_decode_frames_windows_held(*head, C.byref(do))
+        elif len(rows) == 5:                # (span rows: K13's three host tables and the hop)
+            row0, nrows, pos, hop, ro = rows
+            if len(row0) != ns or len(nrows) != ns or len(pos) != ns:
+                raise ValueError("seg_row0, seg_nrows and seg_pos hold one value per segment")
+            sp = SpanRows(row0.ctypes.data, nrows.ctypes.data, pos.ctypes.data, int(hop), None, 0)
+            rc = self.lib.fhip_decode_frames_windows_spans_held(*head, C.byref(sp), C.byref(ro), C.byref(do))
         else:
             srow, scol, ro = rows
             if len(srow) != ns or len(scol) != ns:
@@ -904,6 +942,17 @@ class Encoder:
         decode_frames_windows_held takes it.  Returns its tuple with None where the samples were."""
         sink = (np.ascontiguousarray(seg_row, dtype=np.int32), np.ascontiguousarray(seg_col, dtype=np.int64),
                 RowsOut(_ptr(rows), int(nrows), int(fmt), int(row_len)))
+        return self._held_call(sink, src_dev, src_bytes, frame_src, frame_len, pcm_cap, seg_first, seg_skip, seg_take,
+                               seg_number, seg_variable, None, null_table)
+
+    def decode_frames_windows_spans_held(self, src_dev, src_bytes: int, frame_src, frame_len, pcm_cap: int, seg_first,
+                                         seg_skip, seg_take, seg_row0, seg_nrows, seg_pos, hop: int, rows, nrows: int,
+                                         row_len: int, fmt: int, seg_number=None, seg_variable=None, null_table=None):
+        """fhip_decode_frames_windows_spans_held: decode_frames_windows_rows_held with K13 behind K7 -- host tables
+        seg_row0 / seg_nrows (int32) and seg_pos (int64) and the hop in seg_row's and seg_col's place.  Returns its
+        tuple."""
+        sink = (np.ascontiguousarray(seg_row0, dtype=np.int32), np.ascontiguousarray(seg_nrows, dtype=np.int32),
+                np.ascontiguousarray(seg_pos, dtype=np.int64), int(hop), RowsOut(_ptr(rows), int(nrows), int(fmt), int(row_len)))
         return self._held_call(sink, src_dev, src_bytes, frame_src, frame_len, pcm_cap, seg_first, seg_skip, seg_take,
                                seg_number, seg_variable, None, null_table)
 
@@ -1276,6 +1325,17 @@ def load_host_library() -> C.CDLL:
                                                            C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p,
                                                            C.POINTER(C.c_longlong)]
     lib.flake_amd_decode_set_held_windows_rows.restype = C.c_longlong
+    lib.flake_amd_span_rows_count.argtypes = [C.c_longlong, C.c_longlong, C.c_longlong]
+    lib.flake_amd_span_rows_count.restype = C.c_longlong
+    lib.flake_amd_decode_set_span_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int,
+                                                   C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(C.c_longlong)]
+    lib.flake_amd_decode_set_span_rows.restype = C.c_longlong
+    lib.flake_amd_decode_set_held_span_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_longlong, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
+    lib.flake_amd_decode_set_held_span_rows.restype = C.c_longlong
     lib.flake_amd_decode_set_held_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
                                                    C.POINTER(C.c_longlong)]
     lib.flake_amd_decode_set_held_info.restype = C.c_int
@@ -1555,6 +1615,13 @@ def seekpoints_of_frames(si: HostStreaminfo, stream, sizes, spacing: int):
         return lib.flake_amd_seekpoints_of_frames(C.byref(si), st.ctypes.data if st.size else None, st.size,
                                                   fs.ctypes.data if fs.size else None, len(fs), int(spacing), p, cap)
     return _seekpoints_from(fn, "flake_amd_seekpoints_of_frames")
+
+
+def span_rows_count(count: int, row_len: int, hop: int) -> int:
+    """flake_amd_span_rows_count: the rows of row_len samples, hop apart, that a span of count samples has -- 0 for
+    count 0, else min(ceil(count / hop), 1 + ceil(max(count - row_len, 0) / hop)); -1 for a negative count, row_len < 1
+    or hop outside 1 .. 2^31 - 1.  Pure: no device, no set."""
+    return int(load_host_library().flake_amd_span_rows_count(int(count), int(row_len), int(hop)))
 
 
 def index_frames(si: HostStreaminfo, stream, cap: int | None = None):
@@ -2060,6 +2127,77 @@ class DecodeSet:
         if n < 0:
             raise FlakeHipError(int(n), "flake_amd_decode_set_held_windows_rows", self.last_error())
         return out[:nwin], torch.from_numpy(ws[:nwin].copy()), wst[:nwin], int(nfd.value)
+
+    def _span_rows(self, what, nspans, count, row_len, hop, dtype, out, call):
+        """What decode_span_rows and held_span_rows share: the destination, the call (call(tail) with the arguments from
+        hop on) and what is returned."""
+        import torch
+        if dtype is None:
+            dtype = torch.float32 if out is None else out.dtype
+        fmt = {torch.int32: ROWS_I32, torch.int16: ROWS_I16, torch.float32: ROWS_F32}.get(dtype)
+        if fmt is None:
+            raise ValueError("dtype is torch.int32, torch.int16 or torch.float32")
+        ch, row_len, hop = int(self.si.channels), int(row_len), int(hop)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            # (a call the library will refuse gets no rows: it is the library that says why)
+            need = [span_rows_count(int(c), row_len, hop) for c in count]
+            total = sum(need) if need and min(need) >= 0 and sum(need) < 2 ** 31 else 0
+            out = torch.empty((max(total, 1), ch, max(row_len, 0)), dtype=dtype, device=dev)
+        elif (out.dtype != dtype or out.device != dev or not out.is_contiguous() or out.dim() != 3
+              or tuple(out.shape[1:]) != (ch, row_len)):
+            raise ValueError("out must be a contiguous [rows, channels, row_len] tensor of dtype on the set's device")
+        cap = int(out.shape[0])
+        first_row = np.zeros(nspans + 1, dtype=np.int32)
+        lengths, status = np.zeros(max(cap, 1), dtype=np.int64), np.zeros(max(nspans, 1), dtype=np.int32)
+        nfd = C.c_longlong(0)
+        # (as decode_windows_rows: torch's own stream finishes with this memory first)
+        torch.cuda.current_stream(dev).synchronize()
+        n = call((hop, out.data_ptr() if nspans > 0 else None, fmt, row_len, cap, first_row.ctypes.data, lengths.ctypes.data,
+                  status.ctypes.data, C.byref(nfd)))
+        if n < 0:
+            raise FlakeHipError(int(n), what, self.last_error())
+        return out[:n], torch.from_numpy(lengths[:n].copy()), first_row, status[:nspans], int(nfd.value)
+
+    def decode_span_rows(self, spans, row_len: int, hop: int, dtype=None, out=None):
+        """flake_amd_decode_set_span_rows: every window of row_len samples, hop apart, of each span, with every frame
+        decoded once.  spans: decode_windows' tuples (bytes, frame sizes, fixed block size, first sample, count), the
+        count of any length.  Returns (tensor [R, channels, row_len] on the set's device, dtype as decode_windows_rows';
+        lengths, an int64 CPU tensor [R], -1 for the rows of a span that failed; span_first_row int32[nspans + 1];
+        span_status int32[nspans]; the frames handed to the device).  Span s owns rows span_first_row[s] ..
+        span_first_row[s + 1], span_rows_count(count, row_len, hop) of them; whatever no good span delivered is zero.  out
+        (optional): a contiguous [>= R, channels, row_len] tensor on the set's device whose first R rows are written; the
+        rest is not touched.  Raises FlakeHipError when the call is refused: nothing was written then.  Nothing is
+        pending afterwards.  ctypes only; no compute here."""
+        nspans = len(spans)
+        fs = [np.ascontiguousarray(w[1], dtype=np.int32) for w in spans]
+        fow = np.asarray([len(f) for f in fs], dtype=np.int32)
+        parts = [np.frombuffer(bytes(w[0]), dtype=np.uint8) if isinstance(w[0], (bytes, bytearray))
+                 else np.asarray(w[0], dtype=np.uint8) for w in spans]
+        st = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, np.uint8)
+        sizes = np.ascontiguousarray(np.concatenate(fs)) if fs else np.zeros(0, np.int32)
+        fixed = np.asarray([w[2] for w in spans], dtype=np.uint32)
+        first = np.asarray([w[3] for w in spans], dtype=np.uint64)
+        count = np.asarray([w[4] for w in spans], dtype=np.int64)
+        have = nspans > 0
+        head = (self._g, nspans, fow.ctypes.data if have else None, st.ctypes.data if st.size else None, st.size,
+                sizes.ctypes.data if sizes.size else None, fixed.ctypes.data if have else None,
+                first.ctypes.data if have else None, count.ctypes.data if have else None)
+        return self._span_rows("flake_amd_decode_set_span_rows", nspans, count, row_len, hop, dtype, out,
+                               lambda tail: self.lib.flake_amd_decode_set_span_rows(*head, *tail))
+
+    def held_span_rows(self, spans, row_len: int, hop: int, dtype=None, out=None):
+        """flake_amd_decode_set_held_span_rows.  spans: [(held id, first sample, count)].  Returns what decode_span_rows
+        returns for the same spans asked of the streams' whole runs; out as there."""
+        nspans = len(spans)
+        ids = np.asarray([w[0] for w in spans], dtype=np.int32)
+        first = np.asarray([w[1] for w in spans], dtype=np.uint64)
+        count = np.asarray([w[2] for w in spans], dtype=np.int64)
+        have = nspans > 0
+        head = (self._g, nspans, ids.ctypes.data if have else None, first.ctypes.data if have else None,
+                count.ctypes.data if have else None)
+        return self._span_rows("flake_amd_decode_set_held_span_rows", nspans, count, row_len, hop, dtype, out,
+                               lambda tail: self.lib.flake_amd_decode_set_held_span_rows(*head, *tail))
 
     def held_info(self, held_id: int):
         """(frames, samples, bytes) of a held stream."""

@@ -24,10 +24,12 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIP_SRCS = ["csrc/k0_prepare.hip", "csrc/k1_autocorr.hip", "csrc/k2_lpc.hip", "csrc/k3_encode.hip", "csrc/k3s_search.hip",
             "csrc/k4_assemble.hip", "csrc/k5_verify.hip", "csrc/k6_md5.hip", "csrc/k7_decode.hip", "csrc/k7_decode_windows.hip",
             "csrc/k8_index.hip",
-            "csrc/k9_gather.hip", "csrc/k10_rows.hip", "csrc/k11_held.hip", "csrc/k12_rows_in.hip", "csrc/api.hip"]
+            "csrc/k9_gather.hip", "csrc/k10_rows.hip", "csrc/k11_held.hip", "csrc/k12_rows_in.hip", "csrc/k13_span_rows.hip",
+            "csrc/api.hip"]
 HIP_HDRS = ["csrc/kernels.h", "csrc/device_util.h", "csrc/lpc_reg.h", "csrc/k3_common.h", "csrc/vbs_schedule.h",
             "csrc/vbs_block_lookup.h", "csrc/flac_parse.h", "csrc/flac_header.h", "csrc/table_block.h",
-            "../include/flakehip.h", "../include/flakehip_held.h", "../include/flakehip_rows_in.h", "csrc/k7_decode.hip"]       # (k7_decode_windows.hip includes k7_decode.hip)
+            "../include/flakehip.h", "../include/flakehip_held.h", "../include/flakehip_rows_in.h", "../include/flakehip_spans.h",
+            "csrc/k7_decode.hip"]       # (k7_decode_windows.hip includes k7_decode.hip)
 HIP_DEPS = HIP_SRCS + HIP_HDRS
 HOST_SRCS = ["host/flake_host.c", "host/flake_set.c", "host/synth.c", "host/md5.c"]
 # the decoding side goes into libflake_amd.so only: the drop-in libflake.so exports what libflake has, and libflake
@@ -35,12 +37,12 @@ HOST_SRCS = ["host/flake_host.c", "host/flake_set.c", "host/synth.c", "host/md5.
 HOST_DECODE_SRCS = ["host/flake_decode.c", "host/flake_decode_set.c", "host/flake_recode_set.c"]
 HOST_DEPS = HOST_SRCS + HOST_DECODE_SRCS + ["host/host_internal.h", "host/decode_set_plan.h", "host/recode_plan.h",
                                             "host/decode_window_plan.h", "host/decode_window_place.h", "host/held_plan.h",
-                                            "host/rows_plan.h",
+                                            "host/rows_plan.h", "host/span_rows_plan.h",
                                             "host/seektable.h",
                                             "host/seekpoints.h",
                                             "csrc/flac_header.h",
                                             "../include/flakehip.h", "../include/flakehip_held.h", "../include/flakehip_rows_in.h",
-                                            "../include/flake_amd.h"]
+                                            "../include/flakehip_spans.h", "../include/flake_amd.h"]
 
 # -ffp-contract=off is load-bearing: the fp64 LPC stages must round after every
 # multiply and add to reproduce the reference bit for bit.

@@ -258,18 +258,19 @@ void note_launch(const char *fmt, ...)
 
 namespace {
 
-constexpr int kNumKernels = 15 + fhip::INDEX_STEPS;
+constexpr int kNumKernels = 16 + fhip::INDEX_STEPS;
 const char *const kKernelNames[kNumKernels] = {"k_prepare", "k_autocorr", "k_lpc", "k_encode", "k_assemble",
                                                "k_order_search", "k_verify", "k_decode",
                                                // K8's launches, one name each (fhip::index_step_name without the <>)
                                                "k_index_count", "k_index_wgscan", "k_index_scatter", "k_index_walk",
                                                "k_index_ranges", "k_index_emit", "k_gather_spans", "k_window_rows",
                                                "k_frame_heads", "k_gather_offsets", "k_gather_frames",
-                                               "k_frame_offsets", "k_rows_to_pcm"};
+                                               "k_frame_offsets", "k_rows_to_pcm", "k_span_rows"};
 constexpr int kProfVerify = 6, kProfDecode = 7, kProfIndex = 8, kProfGather = 8 + fhip::INDEX_STEPS,
               kProfRows = 9 + fhip::INDEX_STEPS, kProfHeads = 10 + fhip::INDEX_STEPS,
               kProfGatherOffsets = 11 + fhip::INDEX_STEPS, kProfGatherFrames = 12 + fhip::INDEX_STEPS,
-              kProfFrameOffsets = 13 + fhip::INDEX_STEPS, kProfRowsIn = 14 + fhip::INDEX_STEPS;
+              kProfFrameOffsets = 13 + fhip::INDEX_STEPS, kProfRowsIn = 14 + fhip::INDEX_STEPS,
+              kProfSpanRows = 15 + fhip::INDEX_STEPS;
 
 int fail_hip(fhip_ctx *c, hipError_t e, const char *what)
 {
@@ -2913,7 +2914,48 @@ int run_rows(fhip_ctx *c, const int32_t *pcm, int64_t pcm_cap, int nsegs, const 
     HIP_TRY(c, fhip::launch_window_rows(c->stream, a));
     return FHIP_OK;
 }
+
+// K13's own arguments: what every span entry refuses of them.
+int spans_check(fhip_ctx *c, const fhip_span_rows *sp)
+{
+    if (!sp || !sp->seg_row0 || !sp->seg_nrows || !sp->seg_pos) return fail(c, FHIP_E_INVALID, "null span table");
+    if (sp->hop < 1 || sp->hop > 0x7FFFFFFFll) return fail(c, FHIP_E_INVALID, "hop must be 1 .. 2^31 - 1");
+    return FHIP_OK;
+}
+
+// Queue K13 on the handle's stream; everything is device memory.
+int run_span_rows(fhip_ctx *c, const int32_t *pcm, int64_t pcm_cap, int nsegs, const int64_t *seg_start,
+                  const int64_t *seg_samples, const int32_t *seg_failed, const fhip_span_rows &sp, const fhip_rows_out &rows)
+{
+    if (nsegs < 1 || pcm_cap < 1 || sp.ntiles < 1) return FHIP_OK;
+    const fhip::SpanRowsArgs a{pcm, pcm_cap, nsegs, reinterpret_cast<const long long *>(seg_start),
+                               reinterpret_cast<const long long *>(seg_samples), seg_failed, sp.seg_row0, sp.seg_nrows,
+                               reinterpret_cast<const long long *>(sp.seg_pos), sp.tile_first, sp.ntiles, rows.rows,
+                               rows.nrows, rows.row_len, sp.hop, rows.format, c->p.channels,
+                               ldexpf(1.0f, -(c->p.bits_per_sample - 1))};
+    Prof pr(c, kProfSpanRows, c->profiling);
+    HIP_TRY(c, fhip::launch_span_rows(c->stream, a));
+    return FHIP_OK;
+}
 }  // namespace
+
+int fhip_span_rows_from_segments_dev(fhip_ctx *c, const int32_t *pcm, int64_t pcm_cap, int32_t nsegs, const int64_t *seg_start,
+                                     const int64_t *seg_samples, const int32_t *seg_failed, const fhip_span_rows *spans,
+                                     const fhip_rows_out *rows)
+{
+    if (!c) return FHIP_E_INVALID;
+    entry_reset(c);
+    if (c->pcm_format == FHIP_PCM_S16) return fail(c, FHIP_E_UNSUPPORTED, "rows take int32 PCM only (FHIP_PCM_S16 is set)");
+    if (nsegs < 0 || pcm_cap < 0 || (spans && spans->ntiles < 0)) return fail(c, FHIP_E_INVALID, "negative count");
+    if (!pcm || !seg_start || !seg_samples || !seg_failed || !spans || !spans->tile_first)
+        return fail(c, FHIP_E_INVALID, "null argument");
+    int rc = spans_check(c, spans);
+    if (rc != FHIP_OK) return rc;
+    if ((rc = rows_check(c, rows)) != FHIP_OK) return rc;
+    LaunchScope ls(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    return run_span_rows(c, pcm, pcm_cap, nsegs, seg_start, seg_samples, seg_failed, *spans, *rows);
+}
 
 int fhip_rows_from_segments_dev(fhip_ctx *c, const int32_t *pcm, int64_t pcm_cap, int32_t nsegs, const int64_t *seg_start,
                                 const int64_t *seg_samples, const int32_t *seg_failed, const int32_t *seg_row,
@@ -2992,7 +3034,9 @@ namespace {
 // held (with win): in->stream is DEVICE memory that is not the batch's stream but a store of in->stream_bytes bytes
 // the batch's frames lie in, frame f at held->frame_src[f] with in->frame_bytes[f] bytes (host tables); K11 gathers them
 // into d_vstream / d_vfb, where an upload would have put them (fhip_decode_frames_windows_held, _rows_held).
-struct RowsSink { const int32_t *seg_row; const int64_t *seg_col; const fhip_rows_out *out; };
+// (spans: K13 in K10's place -- seg_row and seg_col are not read, the three span tables are host memory and the tile CSR
+// is built here)
+struct RowsSink { const int32_t *seg_row; const int64_t *seg_col; const fhip_rows_out *out; const fhip_span_rows *spans = nullptr; };
 struct HeldSource { const int64_t *frame_src; };
 struct DecodeMode {
     const fhip_decode_segments *segs = nullptr;
@@ -3012,7 +3056,16 @@ struct DecodeStaged {
     const int32_t *md5_first = nullptr, *md5_range = nullptr;
     const int64_t *seg_col = nullptr;
     const int32_t *seg_row = nullptr;
+    fhip_span_rows spans{};       // (device tables, with the tile CSR)
 };
+
+// The tiles K13 gets for a segment: what its frames can hold, and no more than it was told to take.
+long long span_seg_tiles(const fhip_ctx *c, const DecodeMode &m, int s)
+{
+    long long most = (long long)(m.segs->seg_first[s + 1] - m.segs->seg_first[s]) * c->p.block_size;
+    if (m.win->seg_take[s] >= 0 && m.win->seg_take[s] < most) most = m.win->seg_take[s];
+    return (most + fhip::ROWS_TILE - 1) / fhip::ROWS_TILE;
+}
 
 // Everything the host form refuses, with nothing queued.
 int decode_host_check(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_out *out, const DecodeMode &m)
@@ -3021,7 +3074,11 @@ int decode_host_check(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_o
     int rc = decode_check(c, in, out, segs, !m.rows);
     if (rc != FHIP_OK) return rc;
     if (m.rows) {
-        if (!m.rows->seg_row || !m.rows->seg_col) return fail(c, FHIP_E_INVALID, "null rows table");
+        if (m.rows->spans) {
+            if ((rc = spans_check(c, m.rows->spans)) != FHIP_OK) return rc;
+        } else if (!m.rows->seg_row || !m.rows->seg_col) {
+            return fail(c, FHIP_E_INVALID, "null rows table");
+        }
         if ((rc = rows_check(c, m.rows->out)) != FHIP_OK) return rc;
     }
     if (m.win) {
@@ -3043,6 +3100,11 @@ int decode_host_check(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_o
             if (segs->seg_number[s] < -1) return fail(c, FHIP_E_INVALID, "seg_number is -1 or a number");
         }
         if (segs->seg_first[ns] != in->nframes) return fail(c, FHIP_E_INVALID, "seg_first must end at nframes");
+    }
+    if (m.rows && m.rows->spans && m.win) {
+        long long tiles = 0;
+        for (size_t s = 0; s < ns; s++) tiles += span_seg_tiles(c, m, (int)s);
+        if (tiles > 0x7FFFFFFFll) return fail(c, FHIP_E_INVALID, "the segments hold more tiles than one launch takes");
     }
     if (m.md5) {
         if (!m.md5->states || !m.md5->seg_stream || m.md5->nstreams < 1) return fail(c, FHIP_E_INVALID, "null md5 argument");
@@ -3105,8 +3167,10 @@ int decode_host_stage_tables(fhip_ctx *c, const DecodeMode &m, DecodeStaged &st)
     const auto first = l.add<int32_t>(ns + 1), variable = l.add<int32_t>(ns), failed = l.add<int32_t>(ns);
     const auto md5_first = l.add<int32_t>(m.md5 ? nst + 1 : 0), md5_range = l.add<int32_t>(m.md5 ? ns : 0);
     const auto skip = l.add<int64_t>(m.win ? ns : 0), take = l.add<int64_t>(m.win ? ns : 0);
+    const fhip_span_rows *sp = m.rows ? m.rows->spans : nullptr;
     const auto col = l.add<int64_t>(m.rows ? ns : 0);
     const auto row = l.add<int32_t>(m.rows ? ns : 0);
+    const auto span_nrows = l.add<int32_t>(sp ? ns : 0), tile_first = l.add<int32_t>(sp ? ns + 1 : 0);
     const TableBlock tb(l, c->d_dseg, c->h_dseg, l.bytes());
     HIP_TRY(c, tb.status());
     tb.fill(number, segs->seg_number);
@@ -3125,8 +3189,15 @@ int decode_host_stage_tables(fhip_ctx *c, const DecodeMode &m, DecodeStaged &st)
         tb.fill(take, m.win->seg_take);
     }
     if (m.rows) {
-        tb.fill(col, m.rows->seg_col);
-        tb.fill(row, m.rows->seg_row);
+        tb.fill(col, sp ? sp->seg_pos : m.rows->seg_col);
+        tb.fill(row, sp ? sp->seg_row0 : m.rows->seg_row);
+    }
+    if (sp) {
+        tb.fill(span_nrows, sp->seg_nrows);
+        int32_t *tf = tb.host(tile_first);
+        tf[0] = 0;
+        for (size_t s = 0; s < ns; s++) tf[s + 1] = tf[s] + (int32_t)span_seg_tiles(c, m, (int)s);
+        st.spans = fhip_span_rows{tb.dev(row), tb.dev(span_nrows), tb.dev(col), sp->hop, tb.dev(tile_first), tf[ns]};
     }
     HIP_TRY(c, tb.upload(c->stream));
     st.segs = fhip_decode_segments{tb.dev(first), segs->nsegs, tb.dev(number), tb.dev(variable), tb.dev(start),
@@ -3182,7 +3253,10 @@ int decode_host_launch(fhip_ctx *c, const DecodeMode &m, const DecodeStaged &st)
         if (rc != FHIP_OK) return rc;
         if ((rc = md5_dev_end(c)) != FHIP_OK) return rc;
     }
-    if (m.rows)
+    if (m.rows && m.rows->spans)
+        rc = run_span_rows(c, st.out.pcm, st.out.pcm_cap, st.segs.nsegs, st.segs.seg_start, st.segs.seg_samples,
+                           st.segs.seg_failed, st.spans, *m.rows->out);
+    else if (m.rows)
         rc = run_rows(c, st.out.pcm, st.out.pcm_cap, st.segs.nsegs, st.segs.seg_start, st.segs.seg_samples, st.segs.seg_failed,
                       st.seg_row, st.seg_col, *m.rows->out);
     return rc;
@@ -3268,6 +3342,15 @@ int fhip_decode_frames_windows_rows(fhip_ctx *c, const fhip_decode_in *in, const
     return decode_segments_host(c, in, out, DecodeMode{segs, nullptr, false, win, &sink});
 }
 
+int fhip_decode_frames_windows_spans(fhip_ctx *c, const fhip_decode_in *in, const fhip_decode_segments *segs,
+                                     const fhip_decode_windows *win, const fhip_span_rows *spans, const fhip_rows_out *rows,
+                                     const fhip_decode_out *out)
+{
+    if (c && (!segs || !win || !spans)) return refuse_null(c);
+    const RowsSink sink{nullptr, nullptr, rows, spans};
+    return decode_segments_host(c, in, out, DecodeMode{segs, nullptr, false, win, &sink});
+}
+
 // ---- K11: held streams -----------------------------------------------------------------------------
 
 int fhip_frame_heads_dev(fhip_ctx *c, const uint8_t *stream, int64_t stream_bytes, const int64_t *frame_off,
@@ -3336,6 +3419,20 @@ int fhip_decode_frames_windows_rows_held(fhip_ctx *c, const uint8_t *src_dev, in
     const int rc = held_check(c, src_dev, src_bytes, frame_src, frame_len, nframes, segs, win, &in);
     if (rc != FHIP_OK) return rc;
     const RowsSink sink{seg_row, seg_col, rows};
+    const HeldSource held{frame_src};
+    return decode_segments_host(c, &in, out, DecodeMode{segs, nullptr, false, win, &sink, &held});
+}
+
+int fhip_decode_frames_windows_spans_held(fhip_ctx *c, const uint8_t *src_dev, int64_t src_bytes, const int64_t *frame_src,
+                                          const int32_t *frame_len, int32_t nframes, const fhip_decode_segments *segs,
+                                          const fhip_decode_windows *win, const fhip_span_rows *spans,
+                                          const fhip_rows_out *rows, const fhip_decode_out *out)
+{
+    fhip_decode_in in;
+    const int rc = held_check(c, src_dev, src_bytes, frame_src, frame_len, nframes, segs, win, &in);
+    if (rc != FHIP_OK) return rc;
+    if (!spans) return refuse_null(c);
+    const RowsSink sink{nullptr, nullptr, rows, spans};
     const HeldSource held{frame_src};
     return decode_segments_host(c, &in, out, DecodeMode{segs, nullptr, false, win, &sink, &held});
 }

@@ -486,6 +486,30 @@ struct WindowRowsArgs {
 constexpr int ROWS_TILE = 512;
 hipError_t launch_window_rows(hipStream_t st, const WindowRowsArgs &a);
 
+// K13 (k13_span_rows.hip): K10 one to many -- a segment is a run of a SPAN whose samples go into every row of row_len
+// samples, hop apart, that they belong to: sample i of segment k is at span position p = seg_pos[k] + i and is written
+// to column p - j * hop of row seg_row0[k] + j for every j in [0, seg_nrows[k]) with j * hop <= p < j * hop + row_len.
+// One launch on st of ntiles workgroups, a workgroup per segment and tile of ROWS_TILE samples: tile_first [nsegs + 1]
+// is the CSR of the tiles the caller allots each segment (from an upper bound of its length; samples behind a
+// segment's tiles are not delivered).  All seven tables are DEVICE memory; every read of them is clamped to
+// [0, nsegs), every source read into [0, pcm_cap * channels) and every write into the own [0, row_len) of a row in
+// [seg_row0, seg_row0 + seg_nrows), itself in [0, nrows), whatever they hold.  Segment k is delivered when
+// seg_failed[k] < 0, seg_nrows[k] >= 1, its rows lie in [0, nrows), seg_pos[k] >= 0 and its start is in range, cut at
+// pcm_cap.  Nothing else is written.
+struct SpanRowsArgs {
+    const int32_t *pcm; long long pcm_cap;       // K7's interleaved output, samples per channel
+    int nsegs;
+    const long long *seg_start, *seg_samples;    // [nsegs] as K7 left them
+    const int32_t *seg_failed;                   // [nsegs]
+    const int32_t *seg_row0, *seg_nrows;         // [nsegs] the span's first row and its rows
+    const long long *seg_pos;                    // [nsegs] the span position of the segment's first delivered sample
+    const int32_t *tile_first; int ntiles;       // [nsegs + 1] from 0 to ntiles, not decreasing
+    void *rows; int nrows; long long row_len, hop;
+    int format, channels;
+    float scale;                                 // FHIP_ROWS_F32: 2^-(bits_per_sample - 1)
+};
+hipError_t launch_span_rows(hipStream_t st, const SpanRowsArgs &a);
+
 // K12 (k12_rows_in.hip): K10's inverse -- spans of rows[nrows][channels][row_len] (int32, int16 or float32; format:
 // FHIP_ROWS_*) converted and laid channel-interleaved as int32 into dst.  One launch on st, a workgroup per ROWS_IN_TILE
 // samples of the destination.  pieces is a DEVICE table, sorted by dst and tiling [0, total); every read of it is

@@ -17,6 +17,7 @@
 #include "decode_window_plan.h"
 #include "decode_window_place.h"
 #include "held_plan.h"
+#include "span_rows_plan.h"
 
 typedef struct {
     long long frames_done;        /* frames committed so far */
@@ -65,6 +66,10 @@ struct FlakeAmdDecodeSet {
     long long *wtarget;
     int32_t *wrow;                /* flake_amd_decode_set_windows_rows: each segment's row and first column */
     int64_t *wcol;
+    int32_t *wnrows;              /* flake_amd_decode_set_span_rows: each segment's span's rows [max_batch], every span's
+                                   * first row [per span, and the end] and what it has delivered [per span] */
+    int32_t *wspanrow;
+    long long *wspansmp;
     /* held streams (flake_amd_decode_set_hold ...): the store on the device, and the host's table of what it holds --
      * every stream's entry, every frame's size and head, every frame's offset in the store (and each stream's end) */
     unsigned char *hstore;
@@ -117,7 +122,7 @@ static size_t ds_carve(FlakeAmdDecodeSet *g, unsigned char *base)
     DS_SLOT(wb->seg_first, mb + 1); DS_SLOT(wb->seg_number, mb); DS_SLOT(wb->seg_variable, mb); DS_SLOT(wb->seg_skip, mb);
     DS_SLOT(wb->seg_take, mb); DS_SLOT(wb->seg_win, mb); DS_SLOT(wb->seg_frame0, mb); DS_SLOT(wb->seg_last, mb);
     DS_SLOT(g->wfb, mb); DS_SLOT(g->wstat, mb); DS_SLOT(g->wtarget, mb); DS_SLOT(g->wrow, mb); DS_SLOT(g->wcol, mb);
-    DS_SLOT(g->wsrc, mb);
+    DS_SLOT(g->wsrc, mb); DS_SLOT(g->wnrows, mb);
     return at;
 }
 
@@ -126,7 +131,7 @@ static size_t ds_carve_windows(FlakeAmdDecodeSet *g, unsigned char *base, size_t
 {
     size_t at = 0;
     DS_SLOT(g->wsel, n); DS_SLOT(g->wdata, n); DS_SLOT(g->wsizes, n); DS_SLOT(g->woff, n); DS_SLOT(g->wat, n);
-    DS_SLOT(g->wfirst, n);
+    DS_SLOT(g->wfirst, n); DS_SLOT(g->wspanrow, n + 1); DS_SLOT(g->wspansmp, n);
     return at;
 }
 
@@ -450,11 +455,20 @@ FLAKE_AMD_API long long flake_amd_decode_set_device_batches(const FlakeAmdDecode
  * device buffer, each batch goes through fhip_decode_frames_windows_rows with the segment's window as its row and what
  * the window has delivered so far as its column, and nothing is moved on the host.  The destination is zeroed on the
  * handle's stream before the first batch and a failed window's row again at the end, so that whatever no good window
- * delivered is zero. */
+ * delivered is zero.
+ *
+ * Span rows (flake_amd_decode_set_span_rows) are the rows sink with K13 behind K7 in K10's place: a span is a window of
+ * any length, selected, cut, staged and placed as one, and what the window has delivered so far is the segment's
+ * position in its span.  span_rows_plan.h has the rows: span s owns rows span_first_row[s] .. span_first_row[s + 1], all
+ * the call's rows are zeroed before the first batch and a failed span's again at the end. */
 typedef struct {
     void *dev_rows;
     int format;
     long long row_len;
+    long long hop;                /* 0: window rows.  Otherwise span rows, and the rest is theirs: */
+    long long rows_cap;
+    int *span_first_row;          /* [nwin + 1] */
+    long long *row_samples;       /* [rows_cap] */
 } ds_rows_sink;
 
 typedef struct {                  /* a call's arguments */
@@ -498,7 +512,8 @@ static int ds_windows_check(FlakeAmdDecodeSet *g, const ds_win_call *q, long lon
     const ds_rows_sink *rows = q->rows;
     const int nwin = q->nwin;
     if (rows) {
-        if (rows->row_len < 1 || (!rows->dev_rows && nwin > 0) ||
+        if (rows->row_len < 1 || (!rows->dev_rows && nwin > 0) || rows->hop < 0 || rows->hop > FA_SR_MAX_HOP ||
+            (rows->hop && (rows->rows_cap < 0 || !rows->span_first_row || (!rows->row_samples && rows->rows_cap))) ||
             (rows->format != FHIP_ROWS_I32 && rows->format != FHIP_ROWS_I16 && rows->format != FHIP_ROWS_F32)) {
             snprintf(g->err, sizeof g->err, "bad argument");
             return -1;
@@ -510,7 +525,8 @@ static int ds_windows_check(FlakeAmdDecodeSet *g, const ds_win_call *q, long lon
     }
     const int held = q->held_of_win != NULL;
     if (ds_refuse_samples(g, nwin < 0 || (nwin > 0 && ((!held && (!q->frames_of_win || !q->fixed_block_size)) ||
-                                                       !q->first_sample || !q->count || !q->win_samples || !q->win_status)) ||
+                                                       !q->first_sample || !q->count || (!q->win_samples && !(rows && rows->hop)) ||
+                                                       !q->win_status)) ||
                              (!q->stream && q->bytes) || (!q->pcm && q->pcm_cap_samples), q->sample_bytes))
         return -1;
     const long long room = rows ? 0x7FFFFFFFFFFFFFFFll : (long long)q->pcm_cap_samples;
@@ -526,7 +542,7 @@ static int ds_windows_check(FlakeAmdDecodeSet *g, const ds_win_call *q, long lon
                                                   : "pcm_cap_samples is below the samples the windows ask for");
             return -1;
         }
-        if (rows && q->count[w] > rows->row_len) {
+        if (rows && !rows->hop && q->count[w] > rows->row_len) {
             snprintf(g->err, sizeof g->err, "a window asks for more than row_len samples");
             return -1;
         }
@@ -602,7 +618,8 @@ static int ds_held_select(FlakeAmdDecodeSet *g, const ds_win_call *q, const fa_d
 }
 
 /* A held batch's frames: where each lies in the store, and its size.  Returns the bytes of the tables the device entry
- * uploads for it -- its segment tables and 12 bytes a frame, each table to the next 8-byte boundary (api.hip). */
+ * uploads for it -- its segment tables and 12 bytes a frame, each table to the next 8-byte boundary (api.hip).  rows: 0,
+ * 1 for the rows sink's two tables, 2 for span rows' four. */
 static long long ds_held_stage(FlakeAmdDecodeSet *g, int rows)
 {
     const fa_dw_batch *b = &g->wb;
@@ -613,7 +630,8 @@ static long long ds_held_stage(FlakeAmdDecodeSet *g, int rows)
     }
     const long long ns = b->nsegs, nf = b->nframes;
 #define DS_R8(x) (((x) + 7) & ~7ll)
-    return 8 * ns * 5 + DS_R8(4 * (ns + 1)) + 2 * DS_R8(4 * ns) + (rows ? 8 * ns + DS_R8(4 * ns) : 0) + 8 * nf + DS_R8(4 * nf);
+    return 8 * ns * 5 + DS_R8(4 * (ns + 1)) + 2 * DS_R8(4 * ns) + (rows ? 8 * ns + DS_R8(4 * ns) : 0) +
+           (rows == 2 ? DS_R8(4 * ns) + DS_R8(4 * (ns + 1)) : 0) + 8 * nf + DS_R8(4 * nf);
 #undef DS_R8
 }
 
@@ -633,14 +651,16 @@ static long long ds_windows_stage(FlakeAmdDecodeSet *g, const unsigned char *str
     return (long long)sb;
 }
 
-/* A failed window's row may hold what its earlier segments delivered: zero again, run by run, then wait. */
-static int ds_rows_rezero(FlakeAmdDecodeSet *g, const fhip_rows_out *ro, int nwin, const int *win_status)
+/* A failed window's row may hold what its earlier segments delivered: zero again, run by run, then wait.  first_row
+ * (span rows; null: window w is row w): window w's rows are first_row[w] .. first_row[w + 1]. */
+static int ds_rows_rezero(FlakeAmdDecodeSet *g, const fhip_rows_out *ro, int nwin, const int *win_status, const int32_t *first_row)
 {
     int rc = FHIP_OK;
     for (int w = 0; w < nwin && rc == FHIP_OK;) {
         int e = w;
         while (e < nwin && win_status[e]) e++;
-        if (e > w) rc = fhip_rows_zero_dev(g->hip, ro, w, e - w);
+        const int32_t r0 = first_row ? first_row[w] : w, r1 = first_row ? first_row[e] : e;
+        if (r1 > r0) rc = fhip_rows_zero_dev(g->hip, ro, r0, r1 - r0);
         w = e + 1;
     }
     if (rc == FHIP_OK) rc = fhip_sync(g->hip);
@@ -667,24 +687,35 @@ static long long ds_windows(FlakeAmdDecodeSet *g, const ds_win_call *q, long lon
     const fa_dw_headers hd = {held ? fa_held_get : fa_dw_bytes_get, held ? (const void *)&tab : (const void *)&by};
     if (held ? ds_held_select(g, q, &hd) : ds_windows_select(g, q, nf, &fmt)) return -1;
     const size_t unit = g->si.channels * (size_t)q->sample_bytes;
+    /* span rows: every span's rows, held against the caller's room before anything is written */
+    const int spans = rows && rows->hop;
+    long long nrows = nwin;
+    if (spans && (nrows = fa_sr_first_rows(nwin, q->count, rows->row_len, rows->hop, rows->rows_cap, g->wspanrow)) < 0) {
+        snprintf(g->err, sizeof g->err, "the spans have more rows than rows_cap or than 2^31 - 1");
+        return -1;
+    }
+    long long *const win_samples = spans ? g->wspansmp : q->win_samples;
     fa_dw_cursor cur;
     memset(&cur, 0, sizeof cur);
     fa_dw_batch *b = &g->wb;
     fa_wp_state place;
-    fa_wp_begin(&place, nwin, g->wsel, q->count, g->wat, q->win_samples, q->win_status);
+    fa_wp_begin(&place, nwin, g->wsel, q->count, g->wat, win_samples, q->win_status);
     /* from here on the rows sink writes: everything is zero before the first batch delivers */
-    fhip_rows_out ro = {rows ? rows->dev_rows : NULL, nwin, rows ? rows->format : 0, rows ? rows->row_len : 0};
-    if (rows && nwin > 0 && fhip_rows_zero_dev(g->hip, &ro, 0, nwin) != FHIP_OK) {
+    fhip_rows_out ro = {rows ? rows->dev_rows : NULL, (int32_t)nrows, rows ? rows->format : 0, rows ? rows->row_len : 0};
+    const fhip_span_rows sp = {g->wrow, g->wnrows, g->wcol, spans ? rows->hop : 0, NULL, 0};
+    if (rows && nrows > 0 && fhip_rows_zero_dev(g->hip, &ro, 0, (int32_t)nrows) != FHIP_OK) {
         snprintf(g->err, sizeof g->err, "fhip_rows_zero_dev: %s", fhip_last_error(g->hip));
         return -1;
     }
     long long decoded = 0;
-    while (fa_dw_plan_by(&cur, nwin, g->wsel, &hd, (const size_t *const *)g->woff, g->max_batch, b) > 0) {
-        const long long sb = held ? ds_held_stage(g, rows != NULL) : ds_windows_stage(g, q->stream);
+    while ((!spans || nrows > 0) &&
+           fa_dw_plan_by(&cur, nwin, g->wsel, &hd, (const size_t *const *)g->woff, g->max_batch, b) > 0) {
+        const long long sb = held ? ds_held_stage(g, spans ? 2 : rows != NULL) : ds_windows_stage(g, q->stream);
         if (sb < 0) return ds_nomem(g);
         if (held) g->hup_win += sb;
         /* the device writes the batch's clips from base on; with rows, a window continues where its earlier segments got to */
         const long long base = fa_wp_batch(&place, b->nsegs, b->seg_win, rows ? g->wrow : NULL, rows ? g->wcol : NULL);
+        if (spans) fa_sr_batch(b->nsegs, g->wspanrow, g->wrow, g->wnrows);
         int64_t summary[4] = {0, 0, -1, 0}, nsmp = 0;
         fhip_decode_in in = {g->wstage, (int64_t)sb, g->wfb, b->nframes, 0, -1};
         fhip_decode_segments sg = {b->seg_first, b->nsegs, b->seg_number, b->seg_variable, g->seg_start, g->seg_samples,
@@ -693,6 +724,9 @@ static long long ds_windows(FlakeAmdDecodeSet *g, const ds_win_call *q, long lon
         fhip_decode_out out = {rows ? NULL : (int32_t *)((char *)q->pcm + (size_t)base * unit), (int64_t)pcm_cap_samples - base,
                                g->recs, summary, &nsmp};
         const int rc =
+            spans ? (held ? fhip_decode_frames_windows_spans_held(g->hip, g->hstore, (int64_t)g->hused, g->wsrc, g->wfb,
+                                                                  b->nframes, &sg, &wn, &sp, &ro, &out)
+                          : fhip_decode_frames_windows_spans(g->hip, &in, &sg, &wn, &sp, &ro, &out)) :
             held ? (rows ? fhip_decode_frames_windows_rows_held(g->hip, g->hstore, (int64_t)g->hused, g->wsrc, g->wfb, b->nframes,
                                                                 &sg, &wn, g->wrow, g->wcol, &ro, &out)
                          : fhip_decode_frames_windows_held(g->hip, g->hstore, (int64_t)g->hused, g->wsrc, g->wfb, b->nframes,
@@ -715,8 +749,13 @@ static long long ds_windows(FlakeAmdDecodeSet *g, const ds_win_call *q, long lon
         }
     }
     const long long total = fa_wp_end(&place);
-    if (rows && nwin > 0 && ds_rows_rezero(g, &ro, nwin, q->win_status)) return -1;
+    if (rows && nrows > 0 && ds_rows_rezero(g, &ro, nwin, q->win_status, spans ? g->wspanrow : NULL)) return -1;
     if (frames_decoded) *frames_decoded = decoded;
+    if (spans) {
+        fa_sr_lengths(nwin, g->wspanrow, win_samples, rows->row_len, rows->hop, rows->row_samples);
+        for (int w = 0; w <= nwin; w++) rows->span_first_row[w] = g->wspanrow[w];
+        return nrows;
+    }
     return total;
 }
 
@@ -737,7 +776,7 @@ FLAKE_AMD_API long long flake_amd_decode_set_windows_rows(FlakeAmdDecodeSet *g, 
         void *dev_rows, int row_format, long long row_len,
         long long *win_samples, int *win_status, long long *frames_decoded)
 {
-    const ds_rows_sink sink = {dev_rows, row_format, row_len};
+    const ds_rows_sink sink = {dev_rows, row_format, row_len, 0, 0, NULL, NULL};
     const ds_win_call q = {nwin, frames_of_win, stream, bytes, frame_sizes, fixed_block_size, first_sample, count, NULL, 4, 0,
                            &sink, win_samples, win_status, NULL};
     return ds_windows(g, &q, frames_decoded);
@@ -857,9 +896,43 @@ FLAKE_AMD_API long long flake_amd_decode_set_held_windows_rows(FlakeAmdDecodeSet
 {
     static const int none = 0;
     if (g && nwin > 0 && !held_of_win) { snprintf(g->err, sizeof g->err, "bad argument"); return -1; }
-    const ds_rows_sink sink = {dev_rows, row_format, row_len};
+    const ds_rows_sink sink = {dev_rows, row_format, row_len, 0, 0, NULL, NULL};
     const ds_win_call q = {nwin, NULL, NULL, 0, NULL, NULL, first_sample, count, NULL, 4, 0, &sink, win_samples, win_status,
                            held_of_win ? held_of_win : &none};
+    return ds_windows(g, &q, frames_decoded);
+}
+
+FLAKE_AMD_API long long flake_amd_span_rows_count(long long count, long long row_len, long long hop)
+{
+    return fa_sr_count(count, row_len, hop);
+}
+
+FLAKE_AMD_API long long flake_amd_decode_set_span_rows(FlakeAmdDecodeSet *g, int nspans, const int *frames_of_span,
+        const unsigned char *stream, size_t bytes, const int *frame_sizes,
+        const unsigned *fixed_block_size, const unsigned long long *first_sample, const long long *count, long long hop,
+        void *dev_rows, int row_format, long long row_len, long long rows_cap,
+        int *span_first_row, long long *row_samples, int *span_status, long long *frames_decoded)
+{
+    if (g && hop < 1) { snprintf(g->err, sizeof g->err, "hop must be 1 .. 2^31 - 1"); return -1; }
+    const ds_rows_sink sink = {dev_rows, row_format, row_len, hop, rows_cap, span_first_row, row_samples};
+    const ds_win_call q = {nspans, frames_of_span, stream, bytes, frame_sizes, fixed_block_size, first_sample, count, NULL, 4, 0,
+                           &sink, NULL, span_status, NULL};
+    return ds_windows(g, &q, frames_decoded);
+}
+
+FLAKE_AMD_API long long flake_amd_decode_set_held_span_rows(FlakeAmdDecodeSet *g, int nspans, const int *held_of_span,
+        const unsigned long long *first_sample, const long long *count, long long hop,
+        void *dev_rows, int row_format, long long row_len, long long rows_cap,
+        int *span_first_row, long long *row_samples, int *span_status, long long *frames_decoded)
+{
+    static const int none = 0;
+    if (g && (hop < 1 || (nspans > 0 && !held_of_span))) {
+        snprintf(g->err, sizeof g->err, "%s", hop < 1 ? "hop must be 1 .. 2^31 - 1" : "bad argument");
+        return -1;
+    }
+    const ds_rows_sink sink = {dev_rows, row_format, row_len, hop, rows_cap, span_first_row, row_samples};
+    const ds_win_call q = {nspans, NULL, NULL, 0, NULL, NULL, first_sample, count, NULL, 4, 0, &sink, NULL, span_status,
+                           held_of_span ? held_of_span : &none};
     return ds_windows(g, &q, frames_decoded);
 }
 

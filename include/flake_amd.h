@@ -555,6 +555,43 @@ FLAKE_AMD_API long long flake_amd_decode_set_held_windows_rows(FlakeAmdDecodeSet
 FLAKE_AMD_API int flake_amd_decode_set_held_info(const FlakeAmdDecodeSet *g, int id, long long *frames, long long *samples,
                                                  long long *bytes);
 FLAKE_AMD_API int flake_amd_decode_set_held_stats(const FlakeAmdDecodeSet *g, long long out[4]);
+/*
+ * SPAN ROWS: every window of row_len samples, hop samples apart, of a span of a stream -- with every frame decoded once.
+ * What a caller gets that walks whole recordings in consecutive (hop == row_len), overlapping (hop < row_len) or spaced
+ * (hop > row_len) chunks; asked as one window per chunk, a frame that two chunks touch is decoded twice.
+ *
+ * A call has one row_len >= 1 and one hop in 1 .. 2^31 - 1 and names spans (stream, first_sample[s], count[s] >= 0) as
+ * the windows calls name windows: _span_rows of runs the caller brings (flake_amd_decode_set_windows_rows' arguments),
+ * _held_span_rows of held streams by id.  Span s has
+ *   R_s = 0 for count[s] == 0, else min(ceil(count[s] / hop), 1 + ceil(max(count[s] - row_len, 0) / hop))
+ * rows (flake_amd_span_rows_count; -1 for a negative count, row_len < 1 or a hop out of range): the rows j with
+ * j * hop < count[s] whose predecessor has not reached the span's end.  The spans' rows lie span after span in dev_rows,
+ * [row][channel][row_len] of row_format as the windows' rows: span_first_row[s] is span s's first row and
+ * span_first_row[nspans] the call's rows, which is also what is returned.
+ *
+ * A span is decoded as ONE window: selection, batches, the held gather and the placement are the window calls', and
+ * *frames_decoded counts every selected frame once.  With D_s <= count[s] the samples that window delivers (cut at the
+ * stream's end; 0 behind it) and x_s those samples, row span_first_row[s] + j holds x_s[j * hop + i] at column i where
+ * j * hop + i < D_s and zero elsewhere, row_samples[...] = clamp(D_s - j * hop, 0, row_len) and span_status[s] = 0.  A
+ * span fails as the window would -- any of its frames on the device, a header the planner needs -- and fails whole and
+ * alone: all its rows are zero, their row_samples -1, span_status[s] the window's status.  (K13 lays each batch's
+ * samples into every row they belong to behind the decoder; all the call's rows are zeroed before the first batch and a
+ * failed span's again at the end.)  Rows behind the call's are never touched.  The stream rule is the windows' rows'.
+ *
+ * Returns -1 with nothing written for what the window rows calls refuse of their stream arguments, a negative count,
+ * hop < 1 or above 2^31 - 1, row_len < 1, an unknown row_format, FLAKE_AMD_ROWS_I16 above 16 bits, null tables, and for
+ * more rows than rows_cap (the rows dev_rows and row_samples have room for) or than 2^31 - 1.  Stateless.
+ */
+FLAKE_AMD_API long long flake_amd_span_rows_count(long long count, long long row_len, long long hop);
+FLAKE_AMD_API long long flake_amd_decode_set_span_rows(FlakeAmdDecodeSet *g, int nspans, const int *frames_of_span,
+        const unsigned char *stream, size_t bytes, const int *frame_sizes,
+        const unsigned *fixed_block_size, const unsigned long long *first_sample, const long long *count, long long hop,
+        void *dev_rows, int row_format, long long row_len, long long rows_cap,
+        int *span_first_row, long long *row_samples, int *span_status, long long *frames_decoded);
+FLAKE_AMD_API long long flake_amd_decode_set_held_span_rows(FlakeAmdDecodeSet *g, int nspans, const int *held_of_span,
+        const unsigned long long *first_sample, const long long *count, long long hop,
+        void *dev_rows, int row_format, long long row_len, long long rows_cap,
+        int *span_first_row, long long *row_samples, int *span_status, long long *frames_decoded);
 FLAKE_AMD_API const char *flake_amd_decode_set_last_error(const FlakeAmdDecodeSet *g);
 FLAKE_AMD_API void flake_amd_decode_set_close(FlakeAmdDecodeSet *g);
 

@@ -968,6 +968,10 @@ FHIP_API int fhip_decode_frames_windows_rows(fhip_ctx *ctx, const fhip_decode_in
 /* fhip_pcm_from_rows_dev and fhip_frames_packed_from_rows, with fhip_rows_in and fhip_row_piece: declared in
  * flakehip_rows_in.h, which is part of this interface and needs nothing but this file. */
 #include "flakehip_rows_in.h"
+/* ---- span rows: a span decoded once into every hop-spaced row (K13) --- */
+/* fhip_span_rows_from_segments_dev, fhip_decode_frames_windows_spans and fhip_decode_frames_windows_spans_held, with
+ * fhip_span_rows: declared in flakehip_spans.h, which is part of this interface and needs nothing but this file. */
+#include "flakehip_spans.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -990,8 +994,8 @@ FHIP_API int fhip_get_kernel_times(fhip_ctx *ctx, const char **names, double *ms
  * and fhip_prepare_ahead, the fhip_md5_* entries, fhip_decode_frames(_dev), fhip_decode_frames_segments(_dev, _keep), fhip_decode_frames_windows(_dev, _rows),
  * fhip_rows_from_segments_dev, fhip_rows_zero_dev (which leaves it empty),
  * fhip_index_frames(_dev), fhip_gather_spans_dev, fhip_frames_packed_gather, fhip_frame_heads_dev, fhip_gather_frames_dev,
- * fhip_decode_frames_windows_held, fhip_decode_frames_windows_rows_held, fhip_hold_frames, fhip_pcm_from_rows_dev and
- * fhip_frames_packed_from_rows.  A host-side record: it adds no device work.  (One exception:
+ * fhip_decode_frames_windows_held, fhip_decode_frames_windows_rows_held, fhip_hold_frames, fhip_pcm_from_rows_dev,
+ * fhip_frames_packed_from_rows, fhip_span_rows_from_segments_dev and fhip_decode_frames_windows_spans(_held).  A host-side record: it adds no device work.  (One exception:
  * "k_md5_streams<int16_t,2> fast" / "... general" name a choice that is made on the device when the block shape
  * allows the fast path; asking for the list then waits for that launch.)  names[0 .. cap) receive
  * strings owned by the handle, valid until its next such call; returns the number of launches. */
