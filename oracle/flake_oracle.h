@@ -12,10 +12,11 @@
  *   - Rice codeword emit                pinned against the real bitio.h
  *   - CRC-8/16                          pinned against the real crc.c
  *   - residual FIR, order-selection tree, stereo/wasted feeders, VBS split,
- *     frame assembly: optimize.c / encode.c / vbs.c need the CMake-generated
- *     config.h and are therefore NOT buildable here; these restatements are
- *     "parity unpinned" against a reference binary and are checked by FLAC
- *     format invariants instead (own decoder round trip, CRCs).
+ *     frame assembly (optimize.c / encode.c / vbs.c, which need the
+ *     CMake-generated config.h): pinned byte for byte against the reference's
+ *     own library as its CMake build makes it, through oracle/ref_frames.c
+ *     (tests/test_ref_witness_cpu.py, tests/golden/ref_frames.npz), and
+ *     checked by FLAC format invariants besides (own decoder round trip, CRCs).
  *
  * Every function cites the reference file:line it restates
  * (paths relative to /root/reference).

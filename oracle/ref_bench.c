@@ -3,8 +3,9 @@
  * flake/flake.c:624-663) over an in-memory synthetic batch, linked against the reference's
  * libflake_static.a as the reference's CMake builds it (build/ref/, git-ignored; oracle/Makefile
  * target `refbench`).  bench.py's cpu_baseline leg runs this binary as a child process and reports
- * its rate as kind "reference (timing only)".  It is NOT a parity witness: no test loads it, nothing
- * compares its bytes with anything, and no product path knows it exists.
+ * its rate as kind "reference (timing only)".  This program is not the parity witness and no test
+ * reads its output; the witness is its neighbour oracle/ref_frames.c, linked to the same library, whose
+ * frames the oracle and the HIP path are held to byte for byte.  No product path knows either exists.
  *
  * The PCM is the repository's generator (flake_amd/host/synth.c, compiled in), so the reference
  * encodes the very frames the GPU leg encodes.

@@ -21,6 +21,11 @@ Two families, kept in separate files and labelled in their `source` field:
                 and tests/test_ref_replay.py, which those tests replay where oracle/_ref cannot
                 be built (oraclelib.RecordedRef): a digest of the call and its answer where an
                 oracle function gives that very answer, the answer itself elsewhere.
+* ref_frames.npz what the reference's OWN library (its CMake build, behind oracle/ref_frames.c: the
+                witness oracle/_ref/build/ref_frames) answered to every case of tests/refcases.py:
+                effective parameters, header bytes, every flake_encode_frame() call's return
+                value, one SHA-1 and one feature word per frame, the 34 STREAMINFO bytes; no
+                frame bodies.  (python tests/golden/make_golden.py ref_frames remakes it alone.)
 * path_*.npz    whole-path outputs (prepare -> encode_residual -> emit -> frame)
                 produced by the oracle restatement, for the parts of libflake
                 that cannot be built here (optimize.c / encode.c / vbs.c need
@@ -207,6 +212,23 @@ def make_path(orc):
                         params=np.array([getattr(p, k) for k, _ in p._fields_], np.int32))
 
 
+def make_ref_frames():
+    """ref_frames.npz: the witness's record of every case in tests/refcases.py."""
+    import refcases
+    if refcases.witness_state() != "live":
+        raise SystemExit("oracle/_ref/build/ref_frames is not built (make -C oracle refframes)")
+    entries = {}
+    for c in refcases.cases():
+        pcm = c.pcm()
+        rec = refcases.run_client(refcases.WITNESS, c, pcm)
+        refused = refcases.REFUSED_CALLS.get(c.name, [])
+        assert rec.valid >= 0 and rec.si_rc == 0, c.name
+        assert all((rc == -1) if i in refused else (rc > 0) for i, (_, rc, _) in enumerate(rec.calls)), c.name
+        entries[c.name] = refcases.golden_entry(c, rec, pcm)
+    refcases.save_golden(entries)
+    print("ref_frames.npz:", len(entries), "cases,", sum(len(e["frame_sha"]) for e in entries.values()), "frames")
+
+
 def make_ref_calls():
     """Runs the two test modules with FLAKE_REF=record: the `ref` fixture records the live library's answers."""
     import subprocess
@@ -221,11 +243,15 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["ref_calls"]:                   # python tests/golden/make_golden.py ref_calls
         make_ref_calls()
         raise SystemExit(0)
+    if sys.argv[1:] == ["ref_frames"]:                  # python tests/golden/make_golden.py ref_frames
+        make_ref_frames()
+        raise SystemExit(0)
     make_ref_calls()
     make_ref_lpc(oraclelib.Ref())
     make_ref_rice(oraclelib.Ref())
     make_ref_path(oraclelib.Ref())
     make_path(oraclelib.Oracle())
+    make_ref_frames()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)))
