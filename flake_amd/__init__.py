@@ -430,6 +430,12 @@ def _ptr(a) -> int | None:
     return int(a.data_ptr())        # torch tensor
 
 
+def _u8(data) -> np.ndarray:
+    """bytes, a bytearray or an array as a C-contiguous uint8 array."""
+    return np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data,
+                                dtype=np.uint8)
+
+
 def rice_slot_bytes(p: Params, n: int) -> int:
     """Slot that any residual section of a frame that will not fall back to
     verbatim fits in: the frame's verbatim size (encode.c:521-527), rounded up."""
@@ -517,8 +523,7 @@ class Encoder:
     def _verify_host(self, what: str, args, stream, frame_bytes, pcm, first_sample: int = 0, pcm_dtype=None):
         """One host verify entry: lib.<what>(handle, VerifyIn, *args, VerifyOut) on host arrays, its rc mapped to
         (ok, records as a VERIFY_REC_DTYPE array, summary int64[4], error text)."""
-        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
-                                  else stream, dtype=np.uint8)
+        st = _u8(stream)
         fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
         pc = np.ascontiguousarray(pcm, dtype=pcm_dtype or self.pcm_dtype).reshape(-1, self.params.channels)
         recs = np.zeros(len(fb), dtype=VERIFY_REC_DTYPE)
@@ -652,6 +657,53 @@ class Encoder:
         return summary, rec[0], (num.value if have else None)
 
     # -- K7: decoding ----------------------------------------------------
+    @staticmethod
+    def _decode_in(stream, frame_bytes):
+        """(DecodeIn of host data for a segment-table entry, frame_bytes as int32[], the stream as uint8[]): the arrays
+        outlive the call."""
+        st = _u8(stream)
+        fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
+        di = DecodeIn(st.ctypes.data if st.size else None, st.size, fb.ctypes.data if fb.size else None, len(fb), 0, -1)
+        return di, fb, st
+
+    def _decode_out(self, pcm_cap, out):
+        """A host entry's PCM destination: out, or a new array, held to the handle's PCM dtype and to pcm_cap."""
+        if out is None:
+            out = np.zeros((pcm_cap, self.params.channels), dtype=self.pcm_dtype)
+        if out.dtype != self.pcm_dtype or out.size < pcm_cap * self.params.channels:
+            raise ValueError("out must hold pcm_cap * channels values of the handle's PCM dtype")
+        return out
+
+    def _segments_call(self, call, nframes, out, pcm_cap, seg_first, seg_number, seg_variable, *groups):
+        """The body of every host entry over a segment table.  Builds the tables (seg_number defaults to all -1,
+        seg_variable to all 0; the three outputs filled with -7, so that what the device did not write shows), the
+        records, the summary, DecodeOut (out None: no PCM pointer) and DecodeSegments.  groups: the entry's further
+        tables, each group (how the refusal names them, {name: (values, dtype)}): they must hold one value per segment.
+        call(sg, do, t) makes the library call with references to the two structures and the groups' tables as arrays by
+        name, and returns its code.  Returns (rc, out, nsamples, records, summary, seg_start, seg_samples, seg_failed, error text)."""
+        sf = np.ascontiguousarray(seg_first, dtype=np.int32)
+        ns = len(sf) - 1
+        k = max(ns, 1)
+        num = np.full(k, -1, np.int64) if seg_number is None else np.ascontiguousarray(seg_number, dtype=np.int64)
+        var = np.zeros(k, np.int32) if seg_variable is None else np.ascontiguousarray(seg_variable, dtype=np.int32)
+        t = {}
+        for names, group in groups:
+            t.update({name: np.ascontiguousarray(values, dtype=dtype) for name, (values, dtype) in group.items()})
+            if any(len(t[name]) != ns for name in group):
+                raise ValueError(names + " hold one value per segment")
+        s_start, s_samples = np.full(k, -7, np.int64), np.full(k, -7, np.int64)
+        s_failed = np.full(k, -7, np.int32)
+        recs = np.zeros(nframes, dtype=VERIFY_REC_DTYPE)
+        summary = np.zeros(4, dtype=np.int64)
+        nsm = np.zeros(1, dtype=np.int64)
+        do = DecodeOut(_ptr(out) if out is not None and out.size else None, pcm_cap, recs.ctypes.data if nframes else None,
+                       summary.ctypes.data, nsm.ctypes.data)
+        sg = DecodeSegments(sf.ctypes.data, ns, num.ctypes.data, var.ctypes.data, s_start.ctypes.data,
+                            s_samples.ctypes.data, s_failed.ctypes.data)
+        rc = call(C.byref(sg), C.byref(do), t)
+        return (rc, out, int(nsm[0]), recs, summary, s_start[:ns], s_samples[:ns], s_failed[:ns],
+                self.lib.fhip_last_error(self._h).decode() if rc else "")
+
     def decode_frames(self, stream, frame_bytes, pcm_cap: int, variable_blocks: bool = False, first_number: int = -1,
                       out=None):
         """fhip_decode_frames on host data.  stream: uint8 bytes, frame_bytes: int32[nframes]; pcm_cap: samples per
@@ -659,8 +711,7 @@ class Encoder:
         (at least pcm_cap * channels values), else one is made.  Returns (ok, pcm [pcm_cap][channels], nsamples,
         records as a VERIFY_REC_DTYPE array, summary int64[4], error text); pcm[:nsamples] is the decoded audio
         when ok."""
-        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
-                                  else stream, dtype=np.uint8)
+        st = _u8(stream)
         fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
         ch = self.params.channels
         if out is None:
@@ -697,38 +748,17 @@ class Encoder:
         then fhip_decode_frames with variable_blocks 0 and first_number -1).  Returns (rc, pcm [pcm_cap][channels],
         nsamples, records, summary, seg_start, seg_samples, seg_failed, error text); rc is OK or E_VERIFY, any other
         code is returned too (E_INVALID: nothing was queued)."""
-        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
-                                  else stream, dtype=np.uint8)
-        fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
-        sf = np.ascontiguousarray(seg_first, dtype=np.int32)
-        ns = len(sf) - 1
-        ch = self.params.channels
-        if out is None:
-            out = np.zeros((pcm_cap, ch), dtype=self.pcm_dtype)
-        if out.dtype != self.pcm_dtype or out.size < pcm_cap * ch:
-            raise ValueError("out must hold pcm_cap * channels values of the handle's PCM dtype")
-        k = max(ns, 1)
-        num = np.full(k, -1, np.int64) if seg_number is None else np.ascontiguousarray(seg_number, dtype=np.int64)
-        var = np.zeros(k, np.int32) if seg_variable is None else np.ascontiguousarray(seg_variable, dtype=np.int32)
-        s_start, s_samples = np.full(k, -7, np.int64), np.full(k, -7, np.int64)
-        s_failed = np.full(k, -7, np.int32)
-        recs = np.zeros(len(fb), dtype=VERIFY_REC_DTYPE)
-        summary = np.zeros(4, dtype=np.int64)
-        nsm = np.zeros(1, dtype=np.int64)
-        di = DecodeIn(st.ctypes.data if st.size else None, st.size, fb.ctypes.data if fb.size else None, len(fb), 0, -1)
-        do = DecodeOut(_ptr(out) if out.size else None, pcm_cap, recs.ctypes.data if len(fb) else None,
-                       summary.ctypes.data, nsm.ctypes.data)
-        sg = DecodeSegments(sf.ctypes.data, ns, num.ctypes.data, var.ctypes.data, s_start.ctypes.data,
-                            s_samples.ctypes.data, s_failed.ctypes.data)
+        di, fb, _st = self._decode_in(stream, frame_bytes)
+        out = self._decode_out(pcm_cap, out)
         md = None
         if md5_states is not None:
             ss = np.ascontiguousarray(seg_stream, dtype=np.int32)
             md = DecodeMd5(_ptr(md5_states) if not isinstance(md5_states, int) else md5_states, md5_nstreams,
                            ss.ctypes.data)
-        rc = self.lib.fhip_decode_frames_segments(self._h, C.byref(di), C.byref(sg) if use_segments else None,
-                                                  C.byref(do), C.byref(md) if md is not None else None)
-        return (rc, out, int(nsm[0]), recs, summary, s_start[:ns], s_samples[:ns], s_failed[:ns],
-                self.lib.fhip_last_error(self._h).decode() if rc else "")
+        return self._segments_call(
+            lambda sg, do, t: self.lib.fhip_decode_frames_segments(self._h, C.byref(di), sg if use_segments else None, do,
+                                                                   C.byref(md) if md is not None else None),
+            len(fb), out, pcm_cap, seg_first, seg_number, seg_variable)
 
     def decode_frames_segments_dev(self, stream, stream_bytes: int, frame_bytes, nframes: int, pcm, pcm_cap: int,
                                    summary, nsamples, seg_first, nsegs: int, seg_number, seg_variable, seg_start,
@@ -748,39 +778,16 @@ class Encoder:
         the segment's end).  The delivered samples lie back to back in pcm; seg_start / seg_samples / nsamples are
         about them.  null_table ("skip" / "take" / "win" / "segs"): pass a null pointer there (the refusals).  Returns
         decode_frames_segments' tuple."""
-        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
-                                  else stream, dtype=np.uint8)
-        fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
-        sf = np.ascontiguousarray(seg_first, dtype=np.int32)
-        ns = len(sf) - 1
-        ch = self.params.channels
-        if out is None:
-            out = np.zeros((pcm_cap, ch), dtype=self.pcm_dtype)
-        if out.dtype != self.pcm_dtype or out.size < pcm_cap * ch:
-            raise ValueError("out must hold pcm_cap * channels values of the handle's PCM dtype")
-        k = max(ns, 1)
-        num = np.full(k, -1, np.int64) if seg_number is None else np.ascontiguousarray(seg_number, dtype=np.int64)
-        var = np.zeros(k, np.int32) if seg_variable is None else np.ascontiguousarray(seg_variable, dtype=np.int32)
-        skip = np.ascontiguousarray(seg_skip, dtype=np.int64)
-        take = np.ascontiguousarray(seg_take, dtype=np.int64)
-        if len(skip) != ns or len(take) != ns:
-            raise ValueError("seg_skip and seg_take hold one value per segment")
-        s_start, s_samples = np.full(k, -7, np.int64), np.full(k, -7, np.int64)
-        s_failed = np.full(k, -7, np.int32)
-        recs = np.zeros(len(fb), dtype=VERIFY_REC_DTYPE)
-        summary = np.zeros(4, dtype=np.int64)
-        nsm = np.zeros(1, dtype=np.int64)
-        di = DecodeIn(st.ctypes.data if st.size else None, st.size, fb.ctypes.data if fb.size else None, len(fb), 0, -1)
-        do = DecodeOut(_ptr(out) if out.size else None, pcm_cap, recs.ctypes.data if len(fb) else None,
-                       summary.ctypes.data, nsm.ctypes.data)
-        sg = DecodeSegments(sf.ctypes.data, ns, num.ctypes.data, var.ctypes.data, s_start.ctypes.data,
-                            s_samples.ctypes.data, s_failed.ctypes.data)
-        wn = DecodeWindows(None if null_table == "skip" else skip.ctypes.data,
-                           None if null_table == "take" else take.ctypes.data)
-        rc = self.lib.fhip_decode_frames_windows(self._h, C.byref(di), None if null_table == "segs" else C.byref(sg),
-                                                 None if null_table == "win" else C.byref(wn), C.byref(do))
-        return (rc, out, int(nsm[0]), recs, summary, s_start[:ns], s_samples[:ns], s_failed[:ns],
-                self.lib.fhip_last_error(self._h).decode() if rc else "")
+        di, fb, _st = self._decode_in(stream, frame_bytes)
+
+        def call(sg, do, t):
+            wn = DecodeWindows(None if null_table == "skip" else t["seg_skip"].ctypes.data,
+                               None if null_table == "take" else t["seg_take"].ctypes.data)
+            return self.lib.fhip_decode_frames_windows(self._h, C.byref(di), None if null_table == "segs" else sg,
+                                                       None if null_table == "win" else C.byref(wn), do)
+        return self._segments_call(call, len(fb), self._decode_out(pcm_cap, out), pcm_cap, seg_first, seg_number,
+                                   seg_variable, ("seg_skip and seg_take", {"seg_skip": (seg_skip, np.int64),
+                                                                            "seg_take": (seg_take, np.int64)}))
 
     def decode_frames_windows_dev(self, stream, stream_bytes: int, frame_bytes, nframes: int, pcm, pcm_cap: int,
                                   summary, nsamples, seg_first, nsegs: int, seg_number, seg_variable, seg_start,
@@ -816,35 +823,17 @@ class Encoder:
         """fhip_decode_frames_windows_rows: decode_frames_windows' host arguments, host tables seg_row (int32) and
         seg_col (int64) and a device destination rows [nrows][channels][row_len] of the format fmt.  Returns
         decode_frames_windows' tuple with None where the samples were."""
-        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
-                                  else stream, dtype=np.uint8)
-        fb = np.ascontiguousarray(frame_bytes, dtype=np.int32)
-        sf = np.ascontiguousarray(seg_first, dtype=np.int32)
-        ns = len(sf) - 1
-        k = max(ns, 1)
-        num = np.full(k, -1, np.int64) if seg_number is None else np.ascontiguousarray(seg_number, dtype=np.int64)
-        var = np.zeros(k, np.int32) if seg_variable is None else np.ascontiguousarray(seg_variable, dtype=np.int32)
-        skip = np.ascontiguousarray(seg_skip, dtype=np.int64)
-        take = np.ascontiguousarray(seg_take, dtype=np.int64)
-        srow = np.ascontiguousarray(seg_row, dtype=np.int32)
-        scol = np.ascontiguousarray(seg_col, dtype=np.int64)
-        if len(skip) != ns or len(take) != ns or len(srow) != ns or len(scol) != ns:
-            raise ValueError("seg_skip, seg_take, seg_row and seg_col hold one value per segment")
-        s_start, s_samples = np.full(k, -7, np.int64), np.full(k, -7, np.int64)
-        s_failed = np.full(k, -7, np.int32)
-        recs = np.zeros(len(fb), dtype=VERIFY_REC_DTYPE)
-        summary = np.zeros(4, dtype=np.int64)
-        nsm = np.zeros(1, dtype=np.int64)
-        di = DecodeIn(st.ctypes.data if st.size else None, st.size, fb.ctypes.data if fb.size else None, len(fb), 0, -1)
-        do = DecodeOut(None, pcm_cap, recs.ctypes.data if len(fb) else None, summary.ctypes.data, nsm.ctypes.data)
-        sg = DecodeSegments(sf.ctypes.data, ns, num.ctypes.data, var.ctypes.data, s_start.ctypes.data,
-                            s_samples.ctypes.data, s_failed.ctypes.data)
-        wn = DecodeWindows(skip.ctypes.data, take.ctypes.data)
+        di, fb, _st = self._decode_in(stream, frame_bytes)
         ro = RowsOut(_ptr(rows), int(nrows), int(fmt), int(row_len))
-        rc = self.lib.fhip_decode_frames_windows_rows(self._h, C.byref(di), C.byref(sg), C.byref(wn), srow.ctypes.data,
-                                                      scol.ctypes.data, C.byref(ro), C.byref(do))
-        return (rc, None, int(nsm[0]), recs, summary, s_start[:ns], s_samples[:ns], s_failed[:ns],
-                self.lib.fhip_last_error(self._h).decode() if rc else "")
+
+        def call(sg, do, t):
+            wn = DecodeWindows(t["seg_skip"].ctypes.data, t["seg_take"].ctypes.data)
+            return self.lib.fhip_decode_frames_windows_rows(self._h, C.byref(di), sg, C.byref(wn), t["seg_row"].ctypes.data,
+                                                            t["seg_col"].ctypes.data, C.byref(ro), do)
+        return self._segments_call(call, len(fb), None, pcm_cap, seg_first, seg_number, seg_variable,
+                                   ("seg_skip, seg_take, seg_row and seg_col",
+                                    {"seg_skip": (seg_skip, np.int64), "seg_take": (seg_take, np.int64),
+                                     "seg_row": (seg_row, np.int32), "seg_col": (seg_col, np.int64)}))
 
     # -- K13: spans as hop-spaced rows on the device -------------------------
     def span_rows_from_segments_dev(self, pcm, pcm_cap: int, nsegs: int, seg_start, seg_samples, seg_failed, seg_row0,
@@ -876,51 +865,25 @@ class Encoder:
         return int(self.lib.fhip_gather_frames_dev(self._h, _ptr(dst), int(dst_cap), _ptr(dst_frame_bytes), _ptr(src),
                                                    int(src_bytes), _ptr(frame_src), _ptr(frame_len), int(nframes)))
 
-    def _held_call(self, rows, src_dev, src_bytes, frame_src, frame_len, pcm_cap, seg_first, seg_skip, seg_take, seg_number,
-                   seg_variable, out, null_table):
+    def _held_call(self, what, sink, sink_tables, src_dev, src_bytes, frame_src, frame_len, pcm_cap, seg_first, seg_skip,
+                   seg_take, seg_number, seg_variable, out, null_table):
+        """A held entry: lib.<what>(handle, the held source, segs, win, *sink(t), out).  sink_tables: the sink's own group
+        of tables (_segments_call), sink(t): its arguments of them."""
         fs = np.ascontiguousarray(frame_src, dtype=np.int64)
         fl = np.ascontiguousarray(frame_len, dtype=np.int32)
         if len(fs) != len(fl):
             raise ValueError("frame_src and frame_len hold one value per frame")
-        sf = np.ascontiguousarray(seg_first, dtype=np.int32)
-        ns = len(sf) - 1
-        k = max(ns, 1)
-        num = np.full(k, -1, np.int64) if seg_number is None else np.ascontiguousarray(seg_number, dtype=np.int64)
-        var = np.zeros(k, np.int32) if seg_variable is None else np.ascontiguousarray(seg_variable, dtype=np.int32)
-        skip = np.ascontiguousarray(seg_skip, dtype=np.int64)
-        take = np.ascontiguousarray(seg_take, dtype=np.int64)
-        if len(skip) != ns or len(take) != ns:
-            raise ValueError("seg_skip and seg_take hold one value per segment")
-        s_start, s_samples = np.full(k, -7, np.int64), np.full(k, -7, np.int64)
-        s_failed = np.full(k, -7, np.int32)
-        recs = np.zeros(len(fl), dtype=VERIFY_REC_DTYPE)
-        summary = np.zeros(4, dtype=np.int64)
-        nsm = np.zeros(1, dtype=np.int64)
-        do = DecodeOut(_ptr(out) if out is not None and out.size else None, pcm_cap, recs.ctypes.data if len(fl) else None,
-                       summary.ctypes.data, nsm.ctypes.data)
-        sg = DecodeSegments(sf.ctypes.data, ns, num.ctypes.data, var.ctypes.data, s_start.ctypes.data,
-                            s_samples.ctypes.data, s_failed.ctypes.data)
-        wn = DecodeWindows(skip.ctypes.data, take.ctypes.data)
-        head = (self._h, None if null_table == "src" else _ptr(src_dev), int(src_bytes),
+
+        def call(sg, do, t):
+            wn = DecodeWindows(t["seg_skip"].ctypes.data, t["seg_take"].ctypes.data)
+            return getattr(self.lib, what)(
+                self._h, None if null_table == "src" else _ptr(src_dev), int(src_bytes),
                 None if null_table == "frame_src" else (fs.ctypes.data if len(fs) else None),
                 None if null_table == "frame_len" else (fl.ctypes.data if len(fl) else None), len(fl),
-                None if null_table == "segs" else C.byref(sg), None if null_table == "win" else C.byref(wn))
-        if rows is None:
-            rc = self.lib.fhip_decode_frames_windows_held(*head, C.byref(do))
-        elif len(rows) == 5:                # (span rows: K13's three host tables and the hop)
-            row0, nrows, pos, hop, ro = rows
-            if len(row0) != ns or len(nrows) != ns or len(pos) != ns:
-                raise ValueError("seg_row0, seg_nrows and seg_pos hold one value per segment")
-            sp = SpanRows(row0.ctypes.data, nrows.ctypes.data, pos.ctypes.data, int(hop), None, 0)
-            rc = self.lib.fhip_decode_frames_windows_spans_held(*head, C.byref(sp), C.byref(ro), C.byref(do))
-        else:
-            srow, scol, ro = rows
-            if len(srow) != ns or len(scol) != ns:
-                raise ValueError("seg_row and seg_col hold one value per segment")
-            rc = self.lib.fhip_decode_frames_windows_rows_held(*head, srow.ctypes.data, scol.ctypes.data, C.byref(ro),
-                                                               C.byref(do))
-        return (rc, out, int(nsm[0]), recs, summary, s_start[:ns], s_samples[:ns], s_failed[:ns],
-                self.lib.fhip_last_error(self._h).decode() if rc else "")
+                None if null_table == "segs" else sg, None if null_table == "win" else C.byref(wn), *sink(t), do)
+        return self._segments_call(call, len(fl), out, pcm_cap, seg_first, seg_number, seg_variable,
+                                   ("seg_skip and seg_take", {"seg_skip": (seg_skip, np.int64),
+                                                              "seg_take": (seg_take, np.int64)}), *sink_tables)
 
     def decode_frames_windows_held(self, src_dev, src_bytes: int, frame_src, frame_len, pcm_cap: int, seg_first, seg_skip,
                                    seg_take, seg_number=None, seg_variable=None, out=None, null_table=None):
@@ -928,22 +891,21 @@ class Encoder:
         the frame_len[f] bytes at src_dev + frame_src[f] (src_dev a torch tensor or raw address of src_bytes bytes;
         frame_src int64 and frame_len int32 host tables).  null_table ("src" / "frame_src" / "frame_len" / "segs" /
         "win"): pass a null pointer there (the refusals).  Returns decode_frames_windows' tuple."""
-        if out is None:
-            out = np.zeros((pcm_cap, self.params.channels), dtype=self.pcm_dtype)
-        if out.dtype != self.pcm_dtype or out.size < pcm_cap * self.params.channels:
-            raise ValueError("out must hold pcm_cap * channels values of the handle's PCM dtype")
-        return self._held_call(None, src_dev, src_bytes, frame_src, frame_len, pcm_cap, seg_first, seg_skip, seg_take,
-                               seg_number, seg_variable, out, null_table)
+        return self._held_call("fhip_decode_frames_windows_held", lambda t: (), (), src_dev, src_bytes, frame_src, frame_len,
+                               pcm_cap, seg_first, seg_skip, seg_take, seg_number, seg_variable, self._decode_out(pcm_cap, out),
+                               null_table)
 
     def decode_frames_windows_rows_held(self, src_dev, src_bytes: int, frame_src, frame_len, pcm_cap: int, seg_first,
                                         seg_skip, seg_take, seg_row, seg_col, rows, nrows: int, row_len: int, fmt: int,
                                         seg_number=None, seg_variable=None, null_table=None):
         """fhip_decode_frames_windows_rows_held: decode_frames_windows_rows with the stream taken from device memory, as
         decode_frames_windows_held takes it.  Returns its tuple with None where the samples were."""
-        sink = (np.ascontiguousarray(seg_row, dtype=np.int32), np.ascontiguousarray(seg_col, dtype=np.int64),
-                RowsOut(_ptr(rows), int(nrows), int(fmt), int(row_len)))
-        return self._held_call(sink, src_dev, src_bytes, frame_src, frame_len, pcm_cap, seg_first, seg_skip, seg_take,
-                               seg_number, seg_variable, None, null_table)
+        ro = RowsOut(_ptr(rows), int(nrows), int(fmt), int(row_len))
+        return self._held_call("fhip_decode_frames_windows_rows_held",
+                               lambda t: (t["seg_row"].ctypes.data, t["seg_col"].ctypes.data, C.byref(ro)),
+                               (("seg_row and seg_col", {"seg_row": (seg_row, np.int32), "seg_col": (seg_col, np.int64)}),),
+                               src_dev, src_bytes, frame_src, frame_len, pcm_cap, seg_first, seg_skip, seg_take, seg_number,
+                               seg_variable, None, null_table)
 
     def decode_frames_windows_spans_held(self, src_dev, src_bytes: int, frame_src, frame_len, pcm_cap: int, seg_first,
                                          seg_skip, seg_take, seg_row0, seg_nrows, seg_pos, hop: int, rows, nrows: int,
@@ -951,10 +913,17 @@ class Encoder:
         """fhip_decode_frames_windows_spans_held: decode_frames_windows_rows_held with K13 behind K7 -- host tables
         seg_row0 / seg_nrows (int32) and seg_pos (int64) and the hop in seg_row's and seg_col's place.  Returns its
         tuple."""
-        sink = (np.ascontiguousarray(seg_row0, dtype=np.int32), np.ascontiguousarray(seg_nrows, dtype=np.int32),
-                np.ascontiguousarray(seg_pos, dtype=np.int64), int(hop), RowsOut(_ptr(rows), int(nrows), int(fmt), int(row_len)))
-        return self._held_call(sink, src_dev, src_bytes, frame_src, frame_len, pcm_cap, seg_first, seg_skip, seg_take,
-                               seg_number, seg_variable, None, null_table)
+        ro = RowsOut(_ptr(rows), int(nrows), int(fmt), int(row_len))
+
+        def sink(t):
+            sp = SpanRows(t["seg_row0"].ctypes.data, t["seg_nrows"].ctypes.data, t["seg_pos"].ctypes.data, int(hop), None, 0)
+            return C.byref(sp), C.byref(ro)
+        return self._held_call("fhip_decode_frames_windows_spans_held", sink,
+                               (("seg_row0, seg_nrows and seg_pos", {"seg_row0": (seg_row0, np.int32),
+                                                                     "seg_nrows": (seg_nrows, np.int32),
+                                                                     "seg_pos": (seg_pos, np.int64)}),),
+                               src_dev, src_bytes, frame_src, frame_len, pcm_cap, seg_first, seg_skip, seg_take, seg_number,
+                               seg_variable, None, null_table)
 
     # -- K8: frame discovery ----------------------------------------------
     def index_ranges(self, stream, range_first, max_block_size: int = 0, frame_cap: int | None = None, sentinel=None):
@@ -963,8 +932,7 @@ class Encoder:
         every frame there can be.  Returns (rc, frame_bytes int32[frame_cap], range_frames int32[nranges],
         range_consumed int64[nranges], range_variable int32[nranges]); entries of frame_bytes behind the last frame keep
         `sentinel` (default 0).  rc other than OK is returned, not raised (E_INVALID: nothing was queued)."""
-        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
-                                  else stream, dtype=np.uint8)
+        st = _u8(stream)
         rf = np.ascontiguousarray(range_first, dtype=np.int64)
         nr = len(rf) - 1
         if frame_cap is None:
@@ -1606,8 +1574,7 @@ def seekpoints_of_frames(si: HostStreaminfo, stream, sizes, spacing: int):
     """flake_amd_seekpoints_of_frames: the seek points of a finished stream at `spacing` samples, each frame a block
     (sizes from index_frames), as a SEEK_POINT_DTYPE array.  Raises ValueError for a bad argument or a frame whose
     header does not parse."""
-    st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
-                              else stream, dtype=np.uint8)
+    st = _u8(stream)
     fs = np.ascontiguousarray(sizes, dtype=np.int32)
     lib = load_host_library()
 
@@ -1627,8 +1594,7 @@ def span_rows_count(count: int, row_len: int, hop: int) -> int:
 def index_frames(si: HostStreaminfo, stream, cap: int | None = None):
     """flake_amd_index_frames (CPU only): (frame sizes int32[], bytes they cover), or None where the stream does not
     start with a frame."""
-    st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
-                              else stream, dtype=np.uint8)
+    st = _u8(stream)
     if cap is None:
         cap = st.size // 8 + 1            # no frame is shorter than its header and CRC-16
     sizes = np.zeros(max(cap, 1), dtype=np.int32)
@@ -1657,8 +1623,7 @@ class HostDecoder:
     def decode_frames(self, stream, frame_sizes, pcm_cap: int, sample_bytes: int = 4) -> np.ndarray:
         """The frames of stream (sizes from index_frames) as [samples][channels] int32, or int16 with sample_bytes 2.
         Raises FlakeHipError naming the frame that failed."""
-        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
-                                  else stream, dtype=np.uint8)
+        st = _u8(stream)
         fs = np.ascontiguousarray(frame_sizes, dtype=np.int32)
         out = np.zeros((pcm_cap, self.si.channels), dtype=np.int16 if sample_bytes == 2 else np.int32)
         n = self.lib.flake_amd_decode_frames(self._d, st.ctypes.data if st.size else None, st.size,
@@ -1672,8 +1637,7 @@ class HostDecoder:
         """flake_amd_decode_index: index_frames' answer, found on the device (K8) -- (frame sizes int32[], bytes they
         cover), or None where the stream does not start with a frame.  Raises FlakeHipError where the device cannot
         answer (2 GiB and more)."""
-        st = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
-                                  else stream, dtype=np.uint8)
+        st = _u8(stream)
         if cap is None:
             cap = st.size // 8 + 1            # no frame is shorter than its header and CRC-16
         sizes = np.zeros(max(cap, 1), dtype=np.int32)
@@ -1892,8 +1856,7 @@ class DecodeSet:
         sor = np.asarray([r[0] for r in runs], dtype=np.int32)
         fs = [np.ascontiguousarray(r[2], dtype=np.int32) for r in runs]
         fof = np.asarray([len(f) for f in fs], dtype=np.int32)
-        parts = [np.frombuffer(bytes(r[1]), dtype=np.uint8) if isinstance(r[1], (bytes, bytearray))
-                 else np.asarray(r[1], dtype=np.uint8) for r in runs]
+        parts = [_u8(r[1]) for r in runs]
         st = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, np.uint8)
         sizes = np.ascontiguousarray(np.concatenate(fs)) if fs else np.zeros(0, np.int32)
         out = np.zeros((pcm_cap, self.si.channels), dtype=np.int16 if sample_bytes == 2 else np.int32)
@@ -1910,40 +1873,60 @@ class DecodeSet:
         self.lib.flake_amd_decode_set_run_offsets(self._g, off.ctypes.data, len(runs))
         return [None if rs[r] < 0 else out[off[r]:off[r] + rs[r]] if rs[r] else out[:0] for r in range(len(runs))]
 
-    def decode_windows(self, windows, pcm_cap: int | None = None, sample_bytes: int = 4, out=None):
-        """flake_amd_decode_set_windows.  windows: [(run bytes, frame sizes, fixed block size or 0, first sample,
-        count)], a run being consecutive frames of one stream from any frame on.  Returns (one entry per window: its
-        samples [n][channels], a view of one buffer, or None for a window that failed; win_status int32[]; the frames
-        handed to the device; where each window begins in the buffer).  pcm_cap defaults to the sum of the counts; out
-        (optional) is decoded into.  Raises FlakeHipError when the call is refused: nothing was written then."""
+    # -- windows: two sources (the call's bytes, the held store) times three sinks (PCM, rows, span rows) ----------------
+    @staticmethod
+    def _bytes_source(windows):
+        """(run bytes, frame sizes, fixed block size, first sample, count) tuples -> (the C arguments nwin, frames_of_win,
+        stream, bytes, frame_sizes, fixed_block_size, first_sample, count -- a null pointer for an empty table --, count
+        int64[], the arrays the pointers point into: frames_of_win, stream, frame_sizes, fixed, first)."""
         fs = [np.ascontiguousarray(w[1], dtype=np.int32) for w in windows]
         fow = np.asarray([len(f) for f in fs], dtype=np.int32)
-        parts = [np.frombuffer(bytes(w[0]), dtype=np.uint8) if isinstance(w[0], (bytes, bytearray))
-                 else np.asarray(w[0], dtype=np.uint8) for w in windows]
+        parts = [_u8(w[0]) for w in windows]
         st = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, np.uint8)
         sizes = np.ascontiguousarray(np.concatenate(fs)) if fs else np.zeros(0, np.int32)
         fixed = np.asarray([w[2] for w in windows], dtype=np.uint32)
         first = np.asarray([w[3] for w in windows], dtype=np.uint64)
         count = np.asarray([w[4] for w in windows], dtype=np.int64)
+        have = len(windows) > 0
+        head = (len(windows), fow.ctypes.data if have else None, st.ctypes.data if st.size else None, st.size,
+                sizes.ctypes.data if sizes.size else None, fixed.ctypes.data if have else None,
+                first.ctypes.data if have else None, count.ctypes.data if have else None)
+        return head, count, (fow, st, sizes, fixed, first)
+
+    @staticmethod
+    def _held_source(windows):
+        """(held id, first sample, count) tuples -> (the C arguments nwin, held_of_win, first_sample, count, count int64[],
+        the arrays the pointers point into: ids, first)."""
+        ids = np.asarray([w[0] for w in windows], dtype=np.int32)
+        first = np.asarray([w[1] for w in windows], dtype=np.uint64)
+        count = np.asarray([w[2] for w in windows], dtype=np.int64)
+        have = len(windows) > 0
+        head = (len(windows), ids.ctypes.data if have else None, first.ctypes.data if have else None,
+                count.ctypes.data if have else None)
+        return head, count, (ids, first)
+
+    def _windows_call(self, what, head, sink):
+        """lib.<what>(set, *head, *sink, win_samples, win_status, frames_decoded) -> (win_samples int64[], win_status
+        int32[], the frames handed to the device); raises FlakeHipError when the call is refused."""
+        k = max(head[0], 1)
+        ws, wst = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int32)
+        nfd = C.c_longlong(0)
+        n = getattr(self.lib, what)(self._g, *head, *sink, ws.ctypes.data, wst.ctypes.data, C.byref(nfd))
+        if n < 0:
+            raise FlakeHipError(int(n), what, self.last_error())
+        return ws, wst, int(nfd.value)
+
+    def _windows_pcm(self, what, head, count, _arrays, pcm_cap, sample_bytes, out):
+        """The PCM sink (head, count, _arrays: a source's answer, the arrays alive until the call is over): pcm_cap
+        defaults to the sum of the counts, out to a new array; the call; the result split into one view per window."""
+        nwin = head[0]
         if pcm_cap is None:
             pcm_cap = int(np.maximum(count, 0).sum())
         if out is None:
             out = np.zeros((pcm_cap, self.si.channels), dtype=np.int16 if sample_bytes == 2 else np.int32)
-        k = max(len(windows), 1)
-        ws, wst = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int32)
-        nfd = C.c_longlong(0)
-        have = len(windows) > 0
-        n = self.lib.flake_amd_decode_set_windows(self._g, len(windows), fow.ctypes.data if have else None,
-                                                  st.ctypes.data if st.size else None, st.size,
-                                                  sizes.ctypes.data if sizes.size else None,
-                                                  fixed.ctypes.data if have else None, first.ctypes.data if have else None,
-                                                  count.ctypes.data if have else None,
-                                                  out.ctypes.data if out.size else None, sample_bytes, pcm_cap,
-                                                  ws.ctypes.data, wst.ctypes.data, C.byref(nfd))
-        if n < 0:
-            raise FlakeHipError(int(n), "flake_amd_decode_set_windows", self.last_error())
+        ws, wst, nfd = self._windows_call(what, head, (out.ctypes.data if out.size else None, sample_bytes, pcm_cap))
         res, begins, at = [], [], 0
-        for w in range(len(windows)):
+        for w in range(nwin):
             begins.append(at)
             if ws[w] < 0:
                 res.append(None)
@@ -1951,7 +1934,45 @@ class DecodeSet:
             else:
                 res.append(out[at:at + ws[w]])
                 at += int(ws[w])
-        return res, wst[:len(windows)], int(nfd.value), begins
+        return res, wst[:nwin], nfd, begins
+
+    def _rows_sink(self, row_len, dtype, out, new_rows, min_rows, first_dim):
+        """A rows destination: dtype (default: out's, or float32) to its format; out held to it, to the set's device and
+        to [first_dim, channels, row_len] with at least min_rows rows, or made with new_rows() rows.  Returns (out,
+        format, row_len) with nothing of torch's own stream pending on out."""
+        import torch
+        if dtype is None:
+            dtype = torch.float32 if out is None else out.dtype
+        fmt = {torch.int32: ROWS_I32, torch.int16: ROWS_I16, torch.float32: ROWS_F32}.get(dtype)
+        if fmt is None:
+            raise ValueError("dtype is torch.int32, torch.int16 or torch.float32")
+        ch, row_len = int(self.si.channels), int(row_len)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((new_rows(), ch, max(row_len, 0)), dtype=dtype, device=dev)
+        elif (out.dtype != dtype or out.device != dev or not out.is_contiguous() or out.dim() != 3 or out.shape[0] < min_rows
+              or tuple(out.shape[1:]) != (ch, row_len)):
+            raise ValueError(f"out must be a contiguous [{first_dim}, channels, row_len] tensor of dtype on the set's device")
+        # the library writes on its handle's stream: whatever torch's own stream still has queued on this memory (the
+        # caching allocator may have handed out a block whose last use is pending there) finishes first
+        torch.cuda.current_stream(dev).synchronize()
+        return out, fmt, row_len
+
+    def _windows_rows(self, what, head, _count, _arrays, row_len, dtype, out):
+        """The rows sink (head, _count, _arrays: a source's answer): window w is row w of out."""
+        import torch
+        nwin = head[0]
+        out, fmt, row_len = self._rows_sink(row_len, dtype, out, lambda: nwin, nwin, ">= nwin")
+        ws, wst, nfd = self._windows_call(what, head, (out.data_ptr() if nwin > 0 else None, fmt, row_len))
+        return out[:nwin], torch.from_numpy(ws[:nwin].copy()), wst[:nwin], nfd
+
+    def decode_windows(self, windows, pcm_cap: int | None = None, sample_bytes: int = 4, out=None):
+        """flake_amd_decode_set_windows.  windows: [(run bytes, frame sizes, fixed block size or 0, first sample,
+        count)], a run being consecutive frames of one stream from any frame on.  Returns (one entry per window: its
+        samples [n][channels], a view of one buffer, or None for a window that failed; win_status int32[]; the frames
+        handed to the device; where each window begins in the buffer).  pcm_cap defaults to the sum of the counts; out
+        (optional) is decoded into.  Raises FlakeHipError when the call is refused: nothing was written then."""
+        return self._windows_pcm("flake_amd_decode_set_windows", *self._bytes_source(windows), pcm_cap, sample_bytes, out)
 
     def decode_windows_rows(self, windows, row_len: int, dtype=None, out=None):
         """flake_amd_decode_set_windows_rows: decode_windows' windows as a padded planar batch that stays on the set's
@@ -1961,53 +1982,13 @@ class DecodeSet:
         contiguous tensor on the set's device whose first nwin rows are written; it may hold more rows, which are not
         touched.  Raises FlakeHipError when the call is refused: nothing was written then.  Nothing is pending afterwards.
         ctypes only; no compute here."""
-        import torch
-        if dtype is None:
-            dtype = torch.float32 if out is None else out.dtype
-        fmt = {torch.int32: ROWS_I32, torch.int16: ROWS_I16, torch.float32: ROWS_F32}.get(dtype)
-        if fmt is None:
-            raise ValueError("dtype is torch.int32, torch.int16 or torch.float32")
-        nwin, ch, row_len = len(windows), int(self.si.channels), int(row_len)
-        dev = torch.device("cuda", self.device)
-        if out is None:
-            out = torch.empty((nwin, ch, max(row_len, 0)), dtype=dtype, device=dev)
-        elif (out.dtype != dtype or out.device != dev or not out.is_contiguous() or out.dim() != 3 or out.shape[0] < nwin
-              or tuple(out.shape[1:]) != (ch, row_len)):
-            raise ValueError("out must be a contiguous [>= nwin, channels, row_len] tensor of dtype on the set's device")
-        fs = [np.ascontiguousarray(w[1], dtype=np.int32) for w in windows]
-        fow = np.asarray([len(f) for f in fs], dtype=np.int32)
-        parts = [np.frombuffer(bytes(w[0]), dtype=np.uint8) if isinstance(w[0], (bytes, bytearray))
-                 else np.asarray(w[0], dtype=np.uint8) for w in windows]
-        st = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, np.uint8)
-        sizes = np.ascontiguousarray(np.concatenate(fs)) if fs else np.zeros(0, np.int32)
-        fixed = np.asarray([w[2] for w in windows], dtype=np.uint32)
-        first = np.asarray([w[3] for w in windows], dtype=np.uint64)
-        count = np.asarray([w[4] for w in windows], dtype=np.int64)
-        k = max(nwin, 1)
-        ws, wst = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int32)
-        nfd = C.c_longlong(0)
-        have = nwin > 0
-        # the library writes on its handle's stream: whatever torch's own stream still has queued on this memory (the
-        # caching allocator may have handed out a block whose last use is pending there) finishes first
-        torch.cuda.current_stream(dev).synchronize()
-        n = self.lib.flake_amd_decode_set_windows_rows(self._g, nwin, fow.ctypes.data if have else None,
-                                                       st.ctypes.data if st.size else None, st.size,
-                                                       sizes.ctypes.data if sizes.size else None,
-                                                       fixed.ctypes.data if have else None,
-                                                       first.ctypes.data if have else None,
-                                                       count.ctypes.data if have else None,
-                                                       out.data_ptr() if have else None, fmt, row_len,
-                                                       ws.ctypes.data, wst.ctypes.data, C.byref(nfd))
-        if n < 0:
-            raise FlakeHipError(int(n), "flake_amd_decode_set_windows_rows", self.last_error())
-        return out[:nwin], torch.from_numpy(ws[:nwin].copy()), wst[:nwin], int(nfd.value)
+        return self._windows_rows("flake_amd_decode_set_windows_rows", *self._bytes_source(windows), row_len, dtype, out)
 
     def index(self, streams, max_block_size: int | None = None):
         """flake_amd_decode_set_index: the frames of many files in one device call (K8).  streams: the files' bytes,
         each from its first frame header on; max_block_size: their STREAMINFO value (default: the set's).  Returns one
         entry per stream, each what index_frames returns for it: (frame sizes int32[], bytes they cover) or None."""
-        parts = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.asarray(x, dtype=np.uint8)
-                 for x in streams]
+        parts = [_u8(x) for x in streams]
         if not parts:
             return []
         st = np.ascontiguousarray(np.concatenate(parts))
@@ -2042,8 +2023,7 @@ class DecodeSet:
         bytes, each from its first frame header on; fixed_block_sizes: per file, STREAMINFO's block size where minimum
         and maximum agree, else 0 (default: all 0); max_block_size: their STREAMINFO value (default: the set's).
         Returns the files' ids, in order.  Raises FlakeHipError when the call is refused: nothing changed then."""
-        parts = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.asarray(x, dtype=np.uint8)
-                 for x in streams]
+        parts = [_u8(x) for x in streams]
         if not parts:
             return []
         st = np.ascontiguousarray(np.concatenate(parts))
@@ -2064,97 +2044,29 @@ class DecodeSet:
     def held_windows(self, windows, pcm_cap: int | None = None, sample_bytes: int = 4, out=None):
         """flake_amd_decode_set_held_windows.  windows: [(held id, first sample, count)].  Returns what decode_windows
         returns for the same windows asked of the streams' whole runs."""
-        nwin = len(windows)
-        ids = np.asarray([w[0] for w in windows], dtype=np.int32)
-        first = np.asarray([w[1] for w in windows], dtype=np.uint64)
-        count = np.asarray([w[2] for w in windows], dtype=np.int64)
-        if pcm_cap is None:
-            pcm_cap = int(np.maximum(count, 0).sum())
-        if out is None:
-            out = np.zeros((pcm_cap, self.si.channels), dtype=np.int16 if sample_bytes == 2 else np.int32)
-        k = max(nwin, 1)
-        ws, wst = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int32)
-        nfd = C.c_longlong(0)
-        have = nwin > 0
-        n = self.lib.flake_amd_decode_set_held_windows(self._g, nwin, ids.ctypes.data if have else None,
-                                                       first.ctypes.data if have else None,
-                                                       count.ctypes.data if have else None,
-                                                       out.ctypes.data if out.size else None, sample_bytes, pcm_cap,
-                                                       ws.ctypes.data, wst.ctypes.data, C.byref(nfd))
-        if n < 0:
-            raise FlakeHipError(int(n), "flake_amd_decode_set_held_windows", self.last_error())
-        res, begins, at = [], [], 0
-        for w in range(nwin):
-            begins.append(at)
-            if ws[w] < 0:
-                res.append(None)
-                at += int(count[w])
-            else:
-                res.append(out[at:at + ws[w]])
-                at += int(ws[w])
-        return res, wst[:nwin], int(nfd.value), begins
+        return self._windows_pcm("flake_amd_decode_set_held_windows", *self._held_source(windows), pcm_cap, sample_bytes, out)
 
     def held_windows_rows(self, windows, row_len: int, dtype=None, out=None):
         """flake_amd_decode_set_held_windows_rows.  windows: [(held id, first sample, count)].  Returns what
         decode_windows_rows returns for the same windows asked of the streams' whole runs; out as there."""
-        import torch
-        if dtype is None:
-            dtype = torch.float32 if out is None else out.dtype
-        fmt = {torch.int32: ROWS_I32, torch.int16: ROWS_I16, torch.float32: ROWS_F32}.get(dtype)
-        if fmt is None:
-            raise ValueError("dtype is torch.int32, torch.int16 or torch.float32")
-        nwin, ch, row_len = len(windows), int(self.si.channels), int(row_len)
-        dev = torch.device("cuda", self.device)
-        if out is None:
-            out = torch.empty((nwin, ch, max(row_len, 0)), dtype=dtype, device=dev)
-        elif (out.dtype != dtype or out.device != dev or not out.is_contiguous() or out.dim() != 3 or out.shape[0] < nwin
-              or tuple(out.shape[1:]) != (ch, row_len)):
-            raise ValueError("out must be a contiguous [>= nwin, channels, row_len] tensor of dtype on the set's device")
-        ids = np.asarray([w[0] for w in windows], dtype=np.int32)
-        first = np.asarray([w[1] for w in windows], dtype=np.uint64)
-        count = np.asarray([w[2] for w in windows], dtype=np.int64)
-        k = max(nwin, 1)
-        ws, wst = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int32)
-        nfd = C.c_longlong(0)
-        have = nwin > 0
-        # (as decode_windows_rows: torch's own stream finishes with this memory first)
-        torch.cuda.current_stream(dev).synchronize()
-        n = self.lib.flake_amd_decode_set_held_windows_rows(self._g, nwin, ids.ctypes.data if have else None,
-                                                            first.ctypes.data if have else None,
-                                                            count.ctypes.data if have else None,
-                                                            out.data_ptr() if have else None, fmt, row_len,
-                                                            ws.ctypes.data, wst.ctypes.data, C.byref(nfd))
-        if n < 0:
-            raise FlakeHipError(int(n), "flake_amd_decode_set_held_windows_rows", self.last_error())
-        return out[:nwin], torch.from_numpy(ws[:nwin].copy()), wst[:nwin], int(nfd.value)
+        return self._windows_rows("flake_amd_decode_set_held_windows_rows", *self._held_source(windows), row_len, dtype, out)
 
-    def _span_rows(self, what, nspans, count, row_len, hop, dtype, out, call):
-        """What decode_span_rows and held_span_rows share: the destination, the call (call(tail) with the arguments from
-        hop on) and what is returned."""
+    def _span_rows(self, what, head, count, _arrays, row_len, hop, dtype, out):
+        """What decode_span_rows and held_span_rows share: the destination, the call (head, count, _arrays: a source's
+        answer, the arrays alive until the call is over) and what is returned."""
         import torch
-        if dtype is None:
-            dtype = torch.float32 if out is None else out.dtype
-        fmt = {torch.int32: ROWS_I32, torch.int16: ROWS_I16, torch.float32: ROWS_F32}.get(dtype)
-        if fmt is None:
-            raise ValueError("dtype is torch.int32, torch.int16 or torch.float32")
-        ch, row_len, hop = int(self.si.channels), int(row_len), int(hop)
-        dev = torch.device("cuda", self.device)
-        if out is None:
-            # (a call the library will refuse gets no rows: it is the library that says why)
-            need = [span_rows_count(int(c), row_len, hop) for c in count]
-            total = sum(need) if need and min(need) >= 0 and sum(need) < 2 ** 31 else 0
-            out = torch.empty((max(total, 1), ch, max(row_len, 0)), dtype=dtype, device=dev)
-        elif (out.dtype != dtype or out.device != dev or not out.is_contiguous() or out.dim() != 3
-              or tuple(out.shape[1:]) != (ch, row_len)):
-            raise ValueError("out must be a contiguous [rows, channels, row_len] tensor of dtype on the set's device")
+        nspans, hop = len(count), int(hop)
+
+        def new_rows():             # (a call the library will refuse gets no rows: it is the library that says why)
+            need = [span_rows_count(int(c), int(row_len), hop) for c in count]
+            return max(sum(need) if need and min(need) >= 0 and sum(need) < 2 ** 31 else 0, 1)
+        out, fmt, row_len = self._rows_sink(row_len, dtype, out, new_rows, 0, "rows")
         cap = int(out.shape[0])
         first_row = np.zeros(nspans + 1, dtype=np.int32)
         lengths, status = np.zeros(max(cap, 1), dtype=np.int64), np.zeros(max(nspans, 1), dtype=np.int32)
         nfd = C.c_longlong(0)
-        # (as decode_windows_rows: torch's own stream finishes with this memory first)
-        torch.cuda.current_stream(dev).synchronize()
-        n = call((hop, out.data_ptr() if nspans > 0 else None, fmt, row_len, cap, first_row.ctypes.data, lengths.ctypes.data,
-                  status.ctypes.data, C.byref(nfd)))
+        n = getattr(self.lib, what)(self._g, *head, hop, out.data_ptr() if nspans > 0 else None, fmt, row_len, cap,
+                                    first_row.ctypes.data, lengths.ctypes.data, status.ctypes.data, C.byref(nfd))
         if n < 0:
             raise FlakeHipError(int(n), what, self.last_error())
         return out[:n], torch.from_numpy(lengths[:n].copy()), first_row, status[:nspans], int(nfd.value)
@@ -2169,35 +2081,12 @@ class DecodeSet:
         (optional): a contiguous [>= R, channels, row_len] tensor on the set's device whose first R rows are written; the
         rest is not touched.  Raises FlakeHipError when the call is refused: nothing was written then.  Nothing is
         pending afterwards.  ctypes only; no compute here."""
-        nspans = len(spans)
-        fs = [np.ascontiguousarray(w[1], dtype=np.int32) for w in spans]
-        fow = np.asarray([len(f) for f in fs], dtype=np.int32)
-        parts = [np.frombuffer(bytes(w[0]), dtype=np.uint8) if isinstance(w[0], (bytes, bytearray))
-                 else np.asarray(w[0], dtype=np.uint8) for w in spans]
-        st = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, np.uint8)
-        sizes = np.ascontiguousarray(np.concatenate(fs)) if fs else np.zeros(0, np.int32)
-        fixed = np.asarray([w[2] for w in spans], dtype=np.uint32)
-        first = np.asarray([w[3] for w in spans], dtype=np.uint64)
-        count = np.asarray([w[4] for w in spans], dtype=np.int64)
-        have = nspans > 0
-        head = (self._g, nspans, fow.ctypes.data if have else None, st.ctypes.data if st.size else None, st.size,
-                sizes.ctypes.data if sizes.size else None, fixed.ctypes.data if have else None,
-                first.ctypes.data if have else None, count.ctypes.data if have else None)
-        return self._span_rows("flake_amd_decode_set_span_rows", nspans, count, row_len, hop, dtype, out,
-                               lambda tail: self.lib.flake_amd_decode_set_span_rows(*head, *tail))
+        return self._span_rows("flake_amd_decode_set_span_rows", *self._bytes_source(spans), row_len, hop, dtype, out)
 
     def held_span_rows(self, spans, row_len: int, hop: int, dtype=None, out=None):
         """flake_amd_decode_set_held_span_rows.  spans: [(held id, first sample, count)].  Returns what decode_span_rows
         returns for the same spans asked of the streams' whole runs; out as there."""
-        nspans = len(spans)
-        ids = np.asarray([w[0] for w in spans], dtype=np.int32)
-        first = np.asarray([w[1] for w in spans], dtype=np.uint64)
-        count = np.asarray([w[2] for w in spans], dtype=np.int64)
-        have = nspans > 0
-        head = (self._g, nspans, ids.ctypes.data if have else None, first.ctypes.data if have else None,
-                count.ctypes.data if have else None)
-        return self._span_rows("flake_amd_decode_set_held_span_rows", nspans, count, row_len, hop, dtype, out,
-                               lambda tail: self.lib.flake_amd_decode_set_held_span_rows(*head, *tail))
+        return self._span_rows("flake_amd_decode_set_held_span_rows", *self._held_source(spans), row_len, hop, dtype, out)
 
     def held_info(self, held_id: int):
         """(frames, samples, bytes) of a held stream."""
@@ -2299,8 +2188,7 @@ class RecodeSet:
         sor = np.asarray([r[0] for r in runs], dtype=np.int32)
         fs = [np.ascontiguousarray(r[2], dtype=np.int32) for r in runs]
         fof = np.asarray([len(f) for f in fs], dtype=np.int32)
-        parts = [np.frombuffer(bytes(r[1]), dtype=np.uint8) if isinstance(r[1], (bytes, bytearray))
-                 else np.asarray(r[1], dtype=np.uint8) for r in runs]
+        parts = [_u8(r[1]) for r in runs]
         st = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, np.uint8)
         sizes = np.ascontiguousarray(np.concatenate(fs)) if fs else np.zeros(0, np.int32)
         need_bytes, need_blocks = self.out_bound(int(fof.sum()))

@@ -28,24 +28,10 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "rows_tile.h"
 
 namespace fhip {
 namespace {
-
-constexpr int ROWS_T = 256;                                     // lanes of a workgroup
-constexpr int ROWS_MAX_CH = 8;
-static_assert(ROWS_TILE % 4 == 0, "a channel's line in LDS keeps 16-byte groups");
-
-template <int FMT> struct RowsElem { using type = int32_t; };
-template <> struct RowsElem<FHIP_ROWS_I16> { using type = int16_t; };
-template <> struct RowsElem<FHIP_ROWS_F32> { using type = float; };
-
-template <int FMT> __device__ inline typename RowsElem<FMT>::type rows_conv(int32_t x, float scale)
-{
-    if constexpr (FMT == FHIP_ROWS_F32) return (float)x * scale;          // round to nearest even, then an exact scaling
-    else if constexpr (FMT == FHIP_ROWS_I16) return (int16_t)x;
-    else return x;
-}
 
 template <int FMT> __global__ __launch_bounds__(ROWS_T) void k_window_rows(WindowRowsArgs a)
 {
@@ -69,33 +55,8 @@ template <int FMT> __global__ __launch_bounds__(ROWS_T) void k_window_rows(Windo
     const int nt = n - t0 < ROWS_TILE ? (int)(n - t0) : ROWS_TILE;        // samples of this tile, 1 .. ROWS_TILE
     const int nvals = nt * ch;
 
-    // in: the span [sv0, sv0 + nvals) of pcm, grouped on the source's 16-byte boundaries
-    const long long capvals = a.pcm_cap * ch, sv0 = (start + t0) * ch;
-    const int mis = (int)((reinterpret_cast<uintptr_t>(a.pcm + sv0) >> 2) & 3);
-    const int ngroups = (nvals + mis + 3) >> 2;
-    for (int g = threadIdx.x; g < ngroups; g += ROWS_T) {
-        const int lo = 4 * g - mis;                                       // the group's first value in the span
-        int32_t v[4] = {0, 0, 0, 0};
-        const bool whole = lo >= 0 && lo + 4 <= nvals && sv0 + lo + 4 <= capvals;
-        if (whole) {
-            const int4 q = *reinterpret_cast<const int4 *>(a.pcm + sv0 + lo);
-            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                long long s = sv0 + lo + j;
-                s = s < 0 ? 0 : (s >= capvals ? capvals - 1 : s);
-                if (lo + j >= 0 && lo + j < nvals) v[j] = a.pcm[s];
-            }
-        }
-        int i = (lo < 0 ? 0 : lo) / ch, c = (lo < 0 ? 0 : lo) - i * ch;   // sample and channel of the first value kept
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (lo + j < 0 || lo + j >= nvals) continue;
-            tile[c * ROWS_TILE + i] = v[j];                               // (i < nt <= ROWS_TILE, c < ch <= ROWS_MAX_CH)
-            if (++c == ch) { c = 0; i++; }
-        }
-    }
+    // in: the span of pcm that holds the tile, into LDS
+    rows_tile_load(tile, a.pcm, a.pcm_cap * ch, (start + t0) * ch, nvals, ch);
     __syncthreads();
 
     // out: four consecutive samples of one channel per lane

@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "rows_tile.h"
 
 namespace fhip {
 namespace {
@@ -38,12 +39,8 @@ constexpr int ROWS_IN_T = 256;                                  // lanes of a wo
 constexpr int ROWS_IN_LANE = 4;                                 // destination samples of a lane
 static_assert(ROWS_IN_T * ROWS_IN_LANE == ROWS_IN_TILE, "a workgroup covers one tile");
 
-template <int FMT> struct RowsInElem { using type = int32_t; };
-template <> struct RowsInElem<FHIP_ROWS_I16> { using type = int16_t; };
-template <> struct RowsInElem<FHIP_ROWS_F32> { using type = float; };
-
 // two_pow = 2^(b-1) as a float (exact for every b <= 32); imax = 2^(b-1) - 1
-template <int FMT> __device__ inline int32_t rows_in_conv(typename RowsInElem<FMT>::type e, float two_pow, int32_t imax)
+template <int FMT> __device__ inline int32_t rows_in_conv(typename RowsElem<FMT>::type e, float two_pow, int32_t imax)
 {
     if constexpr (FMT == FHIP_ROWS_F32) {
         const float r = rintf(e * two_pow);                     // exact product, then round to nearest even
@@ -56,22 +53,12 @@ template <int FMT> __device__ inline int32_t rows_in_conv(typename RowsInElem<FM
     }
 }
 
-// The last piece (in [lo, hi]) whose dst is at or before sample s; lo where none is.  Every index read is in [lo, hi].
-__device__ inline int row_piece_at(const RowPiece *__restrict__ tab, int lo, int hi, long long s)
-{
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo + 1) >> 1);              // lo < mid <= hi
-        if (tab[mid].dst <= s) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 // (eight waves per SIMD: a lane's 4 * CH values and its addresses fit 64 registers for every CH, and nothing but
 // occupancy hides the latency of a conversion that is all loads and stores)
 template <int FMT, int CH> __global__ __launch_bounds__(ROWS_IN_T) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void k_rows_to_pcm(RowsInArgs a)
 {
-    using E = typename RowsInElem<FMT>::type;
+    using E = typename RowsElem<FMT>::type;
     struct alignas(4 * sizeof(E)) Quad { E x[4]; };
     // what may be written: below the table's total and the destination's capacity (samples per channel)
     const long long lim_s = a.total < a.dst_cap ? a.total : a.dst_cap;
@@ -81,12 +68,12 @@ void k_rows_to_pcm(RowsInArgs a)
     const long long tile_last = (tile0 + ROWS_IN_TILE < lim ? tile0 + ROWS_IN_TILE : lim) - 1;
     // wave-uniform: the pieces of the tile's first and last sample
     const int last = a.npieces - 1;
-    const int p_lo = row_piece_at(a.pieces, 0, last, tile0);
-    const int p_hi = row_piece_at(a.pieces, p_lo, last, tile_last);
+    const int p_lo = piece_at(a.pieces, 0, last, tile0);
+    const int p_hi = piece_at(a.pieces, p_lo, last, tile_last);
 
     const long long s0 = tile0 + (long long)threadIdx.x * ROWS_IN_LANE;
     if (s0 >= lim) return;
-    int pi = p_lo == p_hi ? p_lo : row_piece_at(a.pieces, p_lo, p_hi, s0);
+    int pi = p_lo == p_hi ? p_lo : piece_at(a.pieces, p_lo, p_hi, s0);
     RowPiece p = a.pieces[pi];
     long long end = p.dst + p.count;                            // the piece's end in the destination
     const E *const rows = static_cast<const E *>(a.rows);

@@ -32,33 +32,19 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "rows_tile.h"
 
 namespace fhip {
 namespace {
 
-constexpr int SPAN_T = 256;                                     // lanes of a workgroup
-constexpr int SPAN_MAX_CH = 8;
 constexpr int SPAN_ROWS_PASS = 1 << 16;                         // rows per pass of the out loop: its index stays an int
-static_assert(ROWS_TILE % 4 == 0, "a channel's line in LDS keeps 16-byte groups");
 
-template <int FMT> struct SpanElem { using type = int32_t; };
-template <> struct SpanElem<FHIP_ROWS_I16> { using type = int16_t; };
-template <> struct SpanElem<FHIP_ROWS_F32> { using type = float; };
-
-// (K10's rows_conv, restated: k10_rows.hip stays as it is)
-template <int FMT> __device__ inline typename SpanElem<FMT>::type span_conv(int32_t x, float scale)
+template <int FMT> __global__ __launch_bounds__(ROWS_T) void k_span_rows(SpanRowsArgs a)
 {
-    if constexpr (FMT == FHIP_ROWS_F32) return (float)x * scale;          // round to nearest even, then an exact scaling
-    else if constexpr (FMT == FHIP_ROWS_I16) return (int16_t)x;
-    else return x;
-}
+    using E = typename RowsElem<FMT>::type;
+    __shared__ __attribute__((aligned(16))) int32_t tile[ROWS_MAX_CH * ROWS_TILE];
 
-template <int FMT> __global__ __launch_bounds__(SPAN_T) void k_span_rows(SpanRowsArgs a)
-{
-    using E = typename SpanElem<FMT>::type;
-    __shared__ __attribute__((aligned(16))) int32_t tile[SPAN_MAX_CH * ROWS_TILE];
-
-    const int ch = a.channels < 1 ? 1 : (a.channels > SPAN_MAX_CH ? SPAN_MAX_CH : a.channels);
+    const int ch = a.channels < 1 ? 1 : (a.channels > ROWS_MAX_CH ? ROWS_MAX_CH : a.channels);
     // wave-uniform: the segment and the tile of this workgroup
     if (a.nsegs < 1 || a.pcm_cap < 1 || a.row_len < 1 || a.hop < 1 || a.nrows < 1) return;
     const long long wg = blockIdx.x;
@@ -87,33 +73,8 @@ template <int FMT> __global__ __launch_bounds__(SPAN_T) void k_span_rows(SpanRow
     const long long jlo = P >= a.row_len ? (P - a.row_len) / a.hop + 1 : 0;
     if (jlo > jhi) return;                                                // (the tile lies between two rows: hop > row_len)
 
-    // in: the span [sv0, sv0 + nvals) of pcm, grouped on the source's 16-byte boundaries
-    const long long capvals = a.pcm_cap * ch, sv0 = (start + t0) * ch;
-    const int mis = (int)((reinterpret_cast<uintptr_t>(a.pcm + sv0) >> 2) & 3);
-    const int ngroups = (nvals + mis + 3) >> 2;
-    for (int g = threadIdx.x; g < ngroups; g += SPAN_T) {
-        const int lo = 4 * g - mis;                                       // the group's first value in the span
-        int32_t v[4] = {0, 0, 0, 0};
-        const bool whole = lo >= 0 && lo + 4 <= nvals && sv0 + lo + 4 <= capvals;
-        if (whole) {
-            const int4 q = *reinterpret_cast<const int4 *>(a.pcm + sv0 + lo);
-            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                long long s = sv0 + lo + j;
-                s = s < 0 ? 0 : (s >= capvals ? capvals - 1 : s);
-                if (lo + j >= 0 && lo + j < nvals) v[j] = a.pcm[s];
-            }
-        }
-        int i = (lo < 0 ? 0 : lo) / ch, c = (lo < 0 ? 0 : lo) - i * ch;   // sample and channel of the first value kept
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (lo + j < 0 || lo + j >= nvals) continue;
-            tile[c * ROWS_TILE + i] = v[j];                               // (i < nt <= ROWS_TILE, c < ch <= SPAN_MAX_CH)
-            if (++c == ch) { c = 0; i++; }
-        }
-    }
+    // in: the span of pcm that holds the tile, into LDS
+    rows_tile_load(tile, a.pcm, a.pcm_cap * ch, (start + t0) * ch, nvals, ch);
     __syncthreads();
 
     // out: a row's share of the tile is at most L samples, which no more than QPR destination quads cover
@@ -122,7 +83,7 @@ template <int FMT> __global__ __launch_bounds__(SPAN_T) void k_span_rows(SpanRow
     E *const rows = static_cast<E *>(a.rows);
     for (long long jb = jlo; jb <= jhi; jb += SPAN_ROWS_PASS) {
         const int jn = jhi - jb + 1 < SPAN_ROWS_PASS ? (int)(jhi - jb + 1) : SPAN_ROWS_PASS;
-        for (int it = threadIdx.x; it < jn * per; it += SPAN_T) {
+        for (int it = threadIdx.x; it < jn * per; it += ROWS_T) {
             const int dj = it / per, r = it - dj * per, c = r / QPR, q = r - c * QPR;
             const long long j = jb + dj, r0 = j * a.hop;                  // the row's first span position
             const long long lo = r0 > P ? r0 : P;                         // the row's share of the tile: [lo, lo + len)
@@ -142,7 +103,7 @@ template <int FMT> __global__ __launch_bounds__(SPAN_T) void k_span_rows(SpanRow
             E e[4];
 #pragma unroll
             for (int m = 0; m < 4; m++)
-                e[m] = span_conv<FMT>(s == 0 ? v[m] : (s == 1 ? v[m + 1] : (s == 2 ? v[m + 2] : v[m + 3])), a.scale);
+                e[m] = rows_conv<FMT>(s == 0 ? v[m] : (s == 1 ? v[m + 1] : (s == 2 ? v[m + 2] : v[m + 3])), a.scale);
             if (f >= 0 && f + 4 <= len && (reinterpret_cast<uintptr_t>(dst + f) & (4 * sizeof(E) - 1)) == 0) {
                 struct alignas(4 * sizeof(E)) Quad { E x[4]; };
                 *reinterpret_cast<Quad *>(dst + f) = Quad{{e[0], e[1], e[2], e[3]}};
@@ -160,10 +121,10 @@ template <int FMT> __global__ __launch_bounds__(SPAN_T) void k_span_rows(SpanRow
 hipError_t launch_span_rows(hipStream_t st, const SpanRowsArgs &a)
 {
     if (a.nsegs < 1 || a.ntiles < 1 || a.pcm_cap < 1 || a.row_len < 1 || a.nrows < 1) return hipSuccess;
-    if (a.channels < 1 || a.channels > SPAN_MAX_CH || a.hop < 1 || a.hop > 0x7FFFFFFFll) return hipErrorInvalidValue;
+    if (a.channels < 1 || a.channels > ROWS_MAX_CH || a.hop < 1 || a.hop > 0x7FFFFFFFll) return hipErrorInvalidValue;
     if (a.format != FHIP_ROWS_I32 && a.format != FHIP_ROWS_I16 && a.format != FHIP_ROWS_F32) return hipErrorInvalidValue;
     note_launch("k_span_rows");
-    const dim3 grid((unsigned)a.ntiles), block(SPAN_T);
+    const dim3 grid((unsigned)a.ntiles), block(ROWS_T);
     switch (a.format) {
     case FHIP_ROWS_I32: hipLaunchKernelGGL(k_span_rows<FHIP_ROWS_I32>, grid, block, 0, st, a); break;
     case FHIP_ROWS_I16: hipLaunchKernelGGL(k_span_rows<FHIP_ROWS_I16>, grid, block, 0, st, a); break;

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "rows_tile.h"
 
 namespace fhip {
 namespace {
@@ -27,16 +28,6 @@ namespace {
 constexpr int GATHER_T = 256;                                   // lanes of a workgroup
 constexpr int GATHER_LANE_VALS = 4;                             // one 16-byte store
 static_assert(GATHER_T * GATHER_LANE_VALS == GATHER_TILE_VALS, "a workgroup covers one tile");
-
-// The last piece (in [lo, hi]) whose dst is at or before sample s; lo where none is.  Every index read is in [lo, hi].
-__device__ inline int piece_at(const GatherPiece *__restrict__ tab, int lo, int hi, long long s)
-{
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo + 1) >> 1);              // lo < mid <= hi
-        if (tab[mid].dst <= s) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(GATHER_T) void k_gather_spans(GatherArgs a)
 {
