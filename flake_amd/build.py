@@ -27,9 +27,9 @@ HIP_SRCS = ["csrc/k0_prepare.hip", "csrc/k1_autocorr.hip", "csrc/k2_lpc.hip", "c
             "csrc/k9_gather.hip", "csrc/k10_rows.hip", "csrc/k11_held.hip", "csrc/k12_rows_in.hip", "csrc/k13_span_rows.hip",
             "csrc/api.hip"]
 HIP_HDRS = ["csrc/kernels.h", "csrc/device_util.h", "csrc/lpc_reg.h", "csrc/k3_common.h", "csrc/vbs_schedule.h",
-            "csrc/vbs_block_lookup.h", "csrc/flac_parse.h", "csrc/flac_header.h", "csrc/table_block.h", "csrc/rows_tile.h",
-            "../include/flakehip.h", "../include/flakehip_held.h", "../include/flakehip_rows_in.h", "../include/flakehip_spans.h",
-            "csrc/k7_decode.hip"]       # (k7_decode_windows.hip includes k7_decode.hip)
+            "csrc/vbs_block_lookup.h", "csrc/flac_parse.h", "csrc/flac_frame_pass.h", "csrc/k7_frame.h", "csrc/flac_header.h",
+            "csrc/table_block.h", "csrc/rows_tile.h",
+            "../include/flakehip.h", "../include/flakehip_held.h", "../include/flakehip_rows_in.h", "../include/flakehip_spans.h"]
 HIP_DEPS = HIP_SRCS + HIP_HDRS
 HOST_SRCS = ["host/flake_host.c", "host/flake_set.c", "host/synth.c", "host/md5.c"]
 # the decoding side goes into libflake_amd.so only: the drop-in libflake.so exports what libflake has, and libflake

@@ -23,7 +23,8 @@
 #include <stdint.h>
 
 #include "kernels.h"
-#include "flac_parse.h"                 // the bit reader, the header parsers, the CRCs: shared with K7
+#include "flac_frame_pass.h"            // the bit reader, the header parsers, the CRCs (flac_parse.h) and the two passes
+                                        // around the subframe walk: shared with K7
 #include "vbs_block_lookup.h"
 
 namespace fhip {
@@ -115,23 +116,8 @@ __global__ void __launch_bounds__(HDR_T) k_verify_frames(VerifyArgs a)
     for (int f0 = 0; f0 < count; f0 += HDR_T) {
         const int f = f0 + t;
         const bool live = f < count;
-        const long long fb = live ? (long long)a.frame_bytes[f] : 0;
-        long long tot = 0;
-        const long long off = base + block_excl_scan(fb > 0 ? fb : 0, scratch, HDR_T / 64, &tot);
-        base += tot;
         VerifyFrame vf{};
-        vf.off = off;
-        vf.bytes = (int)fb;
-        HdrOut h{FHIP_VERIFY_OK, 0, 0, 0, 0, 0};
-        if (live) {
-            if (fb <= 0 || off + fb > a.stream_bytes) {
-                h.status = FHIP_VERIFY_LENGTH;
-                h.bit = fb <= 0 ? 0 : (a.stream_bytes - off) * 8;
-                if (h.bit < 0) h.bit = 0;
-            } else {
-                h = parse_header(a, Bits{a.stream + off, fb});
-            }
-        }
+        HdrOut h = frame_header<HDR_T>(a, f, live, base, scratch, vf);
         // numbering: fixed blocks carry frame numbers (frame f starts at f * block_size), a variable-block-size
         // stream carries the first sample (the frame before says where this one starts).  With a number table
         // (fixed blocks of many streams) frame f carries numbers[f] and its samples lie at f * block_size of pcm:
@@ -200,11 +186,7 @@ __global__ void __launch_bounds__(HDR_T) k_verify_frames(VerifyArgs a)
             vf.rel_start = rel;
         }
         if (live) {
-            vf.n = h.n;
-            vf.hdr_bits = h.hdr_bits;
-            vf.ch_code = h.ch_code;
-            vf.status = h.status;
-            vf.bit = h.bit;
+            frame_fill(vf, h);
             a.ws[f] = vf;
         }
         __syncthreads();
@@ -319,12 +301,7 @@ __global__ void __launch_bounds__(VT) k_verify(VerifyArgs a)
     if (vf.status != FHIP_VERIFY_OK) {
         key = mkkey(vf.bit, 15, 0xFFFF, vf.status);
     } else {
-        // stage the frame (pass 1 put it inside the stream)
-        const uint8_t *src = a.stream + vf.off;
-        const bool staged = vf.bytes <= FB_CAP;
-        if (staged)
-            for (int i = t; i < vf.bytes; i += VT) fb_lds[i] = src[i];
-        const Bits bs{staged ? fb_lds : src, vf.bytes};
+        const Bits bs = frame_stage<VT>(fb_lds, a.stream + vf.off, vf.bytes);
         const long long end = (long long)vf.bytes * 8;
         const int n = vf.n;
         const int nch = a.channels;
@@ -332,9 +309,7 @@ __global__ void __launch_bounds__(VT) k_verify(VerifyArgs a)
         __syncthreads();
         for (int c = 0; c < nch; c++) {
             __syncthreads();                   // everybody is done with the previous subframe's shared state
-            const bool side = (vf.ch_code == FHIP_CH_LEFT_SIDE && c == 1) || (vf.ch_code == FHIP_CH_RIGHT_SIDE && c == 0) ||
-                              (vf.ch_code == FHIP_CH_MID_SIDE && c == 1);
-            const int sub_bps = a.bps + (side ? 1 : 0);
+            const int sub_bps = subframe_bps(a.bps, vf.ch_code, c);
             if (t == 0) {
                 const unsigned long long k = parse_subframe(bs, s_pos, end, sub_bps, n, &s_sh, c);
                 if (k != KEY_NONE) s_key = k;
@@ -476,72 +451,14 @@ __global__ void __launch_bounds__(VT) k_verify(VerifyArgs a)
             __syncthreads();
             if (s_key != KEY_NONE) break;
         }
-        // padding to the byte, CRC-16, the end
-        const bool clean = s_key == KEY_NONE;
-        __syncthreads();
-        if (clean) {
-            const long long p = s_pos;
-            const long long body = (p + 7) >> 3;                      // bytes the CRC-16 covers
-            if (t == 0) {
-                unsigned long long k = KEY_NONE;
-                if (p > end) k = mkkey(end, 15, 0xFFFF, FHIP_VERIFY_SYNTAX);
-                else if (body * 8 > p && bs.rd(p, (int)(body * 8 - p)) != 0) {
-                    const int nb = (int)(body * 8 - p);
-                    const uint32_t v = bs.rd(p, nb);
-                    k = mkkey(p + (__clz(v) - (32 - nb)), 15, 0xFFFF, FHIP_VERIFY_PADDING);
-                } else if (body + 2 > vf.bytes) {
-                    k = mkkey(end, 15, 0xFFFF, FHIP_VERIFY_LENGTH);
-                }
-                s_key = k;
-                s_crc = 0;
-            }
-            __syncthreads();
-            const bool framed = s_key == KEY_NONE;
-            __syncthreads();
-            if (framed) {
-                // CRC-16 of [0, body): a chunk per lane, moved to the end of the body in GF(2) and xor-ed
-                const long long L = (body + VT - 1) / VT;
-                const long long b0 = (long long)t * L, b1 = min(b0 + L, body);
-                uint32_t crc = 0;
-                for (long long i = b0; i < b1; i++) crc = crc16_byte(crc, bs.byte(i));
-                if (b0 < b1 && crc) crc = gf16_mul(crc, gf16_xpow8(body - b1));
-                for (int d = 32; d > 0; d >>= 1) crc ^= (uint32_t)__shfl_xor((int)crc, d, 64);
-                if ((t & 63) == 0 && crc) atomicXor(&s_crc, crc);
-                __syncthreads();
-                if (t == 0) {
-                    const uint32_t got = bs.rd(body * 8, 16);
-                    if (got != s_crc) s_key = mkkey(body * 8, 15, 0xFFFF, FHIP_VERIFY_CRC16);
-                    else if (body + 2 != vf.bytes) s_key = mkkey((body + 2) * 8, 15, 0xFFFF, FHIP_VERIFY_LENGTH);
-                }
-            }
-        }
-        __syncthreads();
-        key = s_key;
+        key = frame_tail<VT>(bs, vf.bytes, s_key, s_pos, s_crc);
     }
-    if (t == 0) {
-        const int status = key == KEY_NONE ? FHIP_VERIFY_OK : (int)(key & 15);
-        if (a.recs) {
-            fhip_verify_rec r;
-            r.status = status;
-            r.bit = status == FHIP_VERIFY_OK ? -1 : (int32_t)min((long long)(key >> 24), 0x7FFFFFFFll);
-            const int sub = (int)((key >> 20) & 15), smp = (int)((key >> 4) & 0xFFFF);
-            r.subframe = (status == FHIP_VERIFY_OK || sub == 15) ? -1 : sub;
-            r.sample = (status == FHIP_VERIFY_SAMPLES && smp != 0xFFFF) ? smp : -1;
-            a.recs[f] = r;
-        }
-        if (status != FHIP_VERIFY_OK) {
-            atomicAdd((unsigned long long *)&a.summary[1], 1ull);
-            atomicMin(&a.key[0], ((unsigned long long)f << 8) | (unsigned long long)status);
-        }
-    }
+    if (t == 0) frame_record<true>(a.recs, a.summary, a.key, f, key);
 }
 
 __global__ void k_verify_final(VerifyArgs a)
 {
-    const unsigned long long k = a.key[0];
-    a.summary[2] = k == KEY_NONE ? -1 : (long long)(k >> 8);
-    a.summary[3] = k == KEY_NONE ? 0 : (long long)(k & 0xFF);
-    if (a.totals && k != KEY_NONE) a.totals[3] |= 4;
+    if (frame_summary_end(a.key[0], a.summary) && a.totals) a.totals[3] |= 4;
 }
 
 }  // namespace

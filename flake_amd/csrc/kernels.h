@@ -385,7 +385,8 @@ hipError_t launch_decode_end(hipStream_t st, const DecodeArgs &a);
 // samples per segment.  A frame whose samples are [o, o + n) of its segment -- o the sizes of the segment's good headers
 // before it -- delivers [max(o, skip), min(o + n, skip + take)), and what the batch delivers lies back to back in pcm:
 // seg_start, seg_samples, nsamples, written_end and pcm_cap are about the delivered samples.  Every frame is decoded
-// and checked in full.  The header pass leaves each frame's clip in clip[], which the frame pass writes out by.
+// and checked in full.  The header pass leaves each frame's clip in clip[], which the frame pass writes out by.  Both
+// are the window instances of k7_frame.h's passes, of which k7_decode.hip's kernels are the others.
 // Launches: "k_decode_frames windows", "k_decode windows", then launch_decode_end's.
 struct DecodeClip {
     long long dst;          // where the clip's first sample goes in pcm

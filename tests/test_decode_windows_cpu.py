@@ -2,10 +2,10 @@
 libraries and refuse null handles, the headers document them, and the window instance of K7's frame kernel is no
 heavier than the existing one.
 
-k_decode_windows is k7_decode.hip's k_decode text compiled with FHIP_K7_WINDOWS (k7_decode_windows.hip); the twin it is
-held to is k_decode of the same source, the same flags and the same compiler, in this test run -- not a number written
-down here.  Residency of k_decode is LDS-limited, so the window instance must have exactly its LDS; and no more
-scratch."""
+k_decode_windows (k7_decode_windows.hip) is k7_frame.h's decode_frame_window, k_decode's text with the clip in its
+write-out; the twin it is held to is k_decode (k7_decode.hip), under the same flags and the same compiler, in this test
+run -- not a number written down here.  Residency of k_decode is LDS-limited, so the window
+instance must have exactly its LDS; and no more scratch."""
 import ctypes as C
 import os
 import re

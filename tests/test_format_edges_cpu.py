@@ -321,6 +321,6 @@ def test_the_limits_are_the_kernels():
     assert const("include/flakehip.h", "FHIP_MAX_PARTS", define=True) == K5_MAX_PARTS
     assert const("flake_amd/csrc/k5_verify.hip", "RES_CAP") == K5_RES_CAP
     assert const("flake_amd/csrc/k5_verify.hip", "FB_CAP") == K5_FB_CAP
-    assert const("flake_amd/csrc/k7_decode.hip", "DFB_CAP") == K7_DFB_CAP
-    assert const("flake_amd/csrc/k7_decode.hip", "DT") == K7_CHUNK
-    assert const("flake_amd/csrc/k7_decode.hip", "RING") == K7_RING
+    assert const("flake_amd/csrc/k7_frame.h", "DFB_CAP") == K7_DFB_CAP
+    assert const("flake_amd/csrc/k7_frame.h", "DT") == K7_CHUNK
+    assert const("flake_amd/csrc/k7_frame.h", "RING") == K7_RING

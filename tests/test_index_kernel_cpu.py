@@ -19,21 +19,23 @@ needs_hipcc = pytest.mark.skipif(not os.path.exists(fb.HIPCC), reason="needs hip
 
 K8 = ("k_index_scan<false>", "k_index_scan<true>", "k_index_wgscan", "k_index_walk", "k_index_ranges", "k_index_emit")
 
-# (VGPRs, TotalSGPRs, VGPRs Spill, SGPRs Spill, LDS bytes per block) of the commit before K8
+# (VGPRs, TotalSGPRs, VGPRs Spill, SGPRs Spill, LDS bytes per block).  k_decode's and the three end kernels' rows are of
+# the commit before K8; the other six of the commit that brought flac_frame_pass.h and k7_frame.h and moved their spill
+# counts, nothing else (profiles/k5_k7_frame_pass_refactor.txt holds both sides)
 BEFORE = {
     "k5_verify.hip": {
-        "k_verify(": (108, 106, 0, 14, 52480),
+        "k_verify(": (108, 106, 0, 10, 52480),
         "k_verify_final(": (4, 15, 0, 0, 0),
-        "k_verify_frames<0>(": (128, 106, 17, 123, 12432),
-        "k_verify_frames<1>(": (128, 106, 18, 100, 128),
-        "k_verify_frames<2>(": (128, 106, 16, 100, 128),
+        "k_verify_frames<0>(": (128, 106, 14, 117, 12432),
+        "k_verify_frames<1>(": (128, 106, 14, 94, 128),
+        "k_verify_frames<2>(": (128, 106, 16, 94, 128),
     },
     "k7_decode.hip": {
         "k_decode(": (49, 106, 0, 16, 17120),
         "k_decode_final(": (4, 14, 0, 0, 0),
         "k_decode_seg_final(": (4, 21, 0, 0, 0),
-        "k_decode_frames<false>(": (128, 106, 22, 27, 16536),
-        "k_decode_frames<true>(": (128, 106, 45, 86, 16536),
+        "k_decode_frames<false>(": (128, 106, 18, 31, 16536),
+        "k_decode_frames<true>(": (128, 106, 49, 88, 16536),
     },
 }
 

@@ -18,7 +18,7 @@ for f in files:
             nm = subprocess.run(["c++filt", cur["name"]], capture_output=True, text=True).stdout.strip()
             nm = re.sub(r"\(anonymous namespace\)::|fhip::|void ", "", nm)
             nm = re.sub(r"\(.*", "", nm)
-            print(f"{nm[:70]:70s} {cur.get('VGPRs','?'):>5s} {cur.get('AGPRs','?'):>5s} {cur.get('SGPRs','?'):>5s} "
+            print(f"{nm[:70]:70s} {cur.get('VGPRs','?'):>5s} {cur.get('AGPRs','?'):>5s} {cur.get('TotalSGPRs', cur.get('SGPRs','?')):>5s} "
                   f"{cur.get('VGPRs Spill','?'):>6s} {cur.get('SGPRs Spill','?'):>6s} {cur.get('ScratchSize [bytes/lane]','?'):>7s} "
                   f"{cur.get('Occupancy [waves/SIMD]','?'):>4s} {cur.get('LDS Size [bytes/block]','?'):>6s}")
     for line in out.splitlines():
