@@ -26,6 +26,8 @@ Two families, kept in separate files and labelled in their `source` field:
                 effective parameters, header bytes, every flake_encode_frame() call's return
                 value, one SHA-1 and one feature word per frame, the 34 STREAMINFO bytes; no
                 frame bodies.  (python tests/golden/make_golden.py ref_frames remakes it alone.)
+* ref_rice_cases.npz  rice.c's answers to the boundary table of tests/ricecases.py (results only; python
+                tests/golden/make_golden.py ref_rice_cases remakes it alone).
 * path_*.npz    whole-path outputs (prepare -> encode_residual -> emit -> frame)
                 produced by the oracle restatement, for the parts of libflake
                 that cannot be built here (optimize.c / encode.c / vbs.c need
@@ -121,6 +123,20 @@ def make_ref_rice(ref):
     np.savez_compressed(os.path.join(HERE, "ref_crc.npz"), source="reference crc.c", data=data, lens=lens,
                         crc8=np.array([ref.crc8(data[:l]) for l in lens], np.int32),
                         crc16=np.array([ref.crc16(data[:l]) for l in lens], np.int32))
+
+
+def make_ref_rice_cases(ref, orc):
+    """ref_rice_cases.npz: rice.c's answer (bits, method, partition order, parameters) to every case of
+    tests/ricecases.py, on the residual the oracle's record of the case holds.  Results only."""
+    import ricecases
+    answers = {}
+    for c, p, info, res in ricecases.records(orc):
+        lpc, pmin, pmax, order, bps, prec = ricecases.rice_call(p, info)
+        bits, meth, por, par = ref.calc_rice_params(lpc, pmin, pmax, res, order, bps, prec)
+        answers[c.name] = (int(bits), int(meth), int(por), [int(v) for v in par[:1 << por]])
+    np.savez_compressed(os.path.join(HERE, "ref_rice_cases.npz"), source="reference rice.c via oracle/_ref",
+                        **ricecases.pack_answers(answers))
+    print("ref_rice_cases.npz:", len(answers), "cases")
 
 
 def make_ref_path(ref):
@@ -243,12 +259,16 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["ref_calls"]:                   # python tests/golden/make_golden.py ref_calls
         make_ref_calls()
         raise SystemExit(0)
+    if sys.argv[1:] == ["ref_rice_cases"]:              # python tests/golden/make_golden.py ref_rice_cases
+        make_ref_rice_cases(oraclelib.Ref(), oraclelib.Oracle())
+        raise SystemExit(0)
     if sys.argv[1:] == ["ref_frames"]:                  # python tests/golden/make_golden.py ref_frames
         make_ref_frames()
         raise SystemExit(0)
     make_ref_calls()
     make_ref_lpc(oraclelib.Ref())
     make_ref_rice(oraclelib.Ref())
+    make_ref_rice_cases(oraclelib.Ref(), oraclelib.Oracle())
     make_ref_path(oraclelib.Ref())
     make_path(oraclelib.Oracle())
     make_ref_frames()
